@@ -7,6 +7,9 @@
 Workload = BASELINE.json configs[1]: comp_4c synthetic, 8192-sample windows, batch 256 per GPU, fp32
 (weak scaling: global batch 256*N).  One step = forward + calc_loss + backward + L1 clip + Adam
 [+ RCCL all-reduce of the 16.8 MB gradient], inputs resident in HBM.  Prints ONE JSON line on rank 0.
+
+A plain run times the headline step only.  --full adds the measurements reported beside it (HIP-graph replay, f32x3,
+per-kernel roofline, CPU baseline).  --dump-outputs DIR writes what the last timed step computed, for comparing two builds.
 """
 import argparse
 import ctypes as C
@@ -84,12 +87,16 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--prewarm-s", type=float, default=0.5, help="untimed, REPORTED pre-warm before the declared warm-up: steps are run until this many seconds "
                                                                  "have passed (clocks / caches / allocator of a cold GPU settle; `prewarm_s`, `prewarm_steps` in the JSON line)")
-    ap.add_argument("--no-f32x3", action="store_true", help="N = 1, --dtype f32: skip the f32x3 measurement reported beside the exact-fp32 value (ms_per_step_f32x3)")
+    ap.add_argument("--full", action="store_true", help="also run the measurements reported beside the headline (each in its own leg after the timed steps): "
+                                                        "HIP-graph replay, f32x3, per-kernel roofline, CPU baseline.  Without it only the headline step is timed")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed as DIR/<name>.npy (float32): params, grads "
+                                                          "(each a fixed, seeded sample when larger than 7 M values), scalars")
+    ap.add_argument("--no-f32x3", action="store_true", help="--full, N = 1, --dtype f32: skip the f32x3 measurement reported beside the exact-fp32 value (ms_per_step_f32x3)")
     ap.add_argument("--batch", type=int, default=256, help="windows per GPU")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="--full: skip the per-kernel roofline leg")
     ap.add_argument("--bk", type=int, default=0, help="GEMM k-tile depth override (16/32)")
-    ap.add_argument("--no-graph", action="store_true", help="N = 1: skip the HIP-graph replay measurement (ms_per_step_graph)")
+    ap.add_argument("--no-graph", action="store_true", help="--full, N = 1: skip the HIP-graph replay measurement (ms_per_step_graph)")
     ap.add_argument("--tune", type=int, nargs="*", default=[], help="diagnostics: st_set_tuning codes applied before the run")
     ap.add_argument("--ablate", type=int, default=0, help="diagnostics: st_set_debug bits for a library built with -DST_GEMM_ABLATE / -DST_AE_ABLATE "
                                                           "(timing-only; the numbers of such a run are INVALID as results)")
@@ -108,6 +115,8 @@ def main():
                     help="N > 1: lib = the exchange inside libsignaltrain_hip.so (its own RCCL communicator, one C call per step; torch.distributed/gloo "
                          "only bootstraps the unique id); torch = torch.distributed collectives on RCCL driven from Python")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     rank = int(os.environ.get("RANK", "0")); local = int(os.environ.get("LOCAL_RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -185,7 +194,6 @@ def main():
     np.random.seed(218 + 1000 * (rank + 1))
     ds = datasets.SynthAudioDataSet(d.L, audio.Compressor_4c(), y_size=d.y, augment=True)
     x, y, kn = ds.batch_device(B, dev)          # comp_4c windows from the device feed (csrc/st_feed.h): signals, knobs, compressor targets
-    X, Y, KN = (a.cpu().numpy() for a in (x, y, kn))
     lrs, _ = learningrate.get_1cycle_schedule(lr_max=1e-4, n_data_points=200000, epochs=100, batch_size=B * world)
 
     def step(i):
@@ -228,23 +236,45 @@ def main():
         fence()
         return time.perf_counter() - t0
 
+    def restart():
+        """Back to the freshly loaded model (zero Adam moments, step 0): the pre-warm runs as many steps as fit in --prewarm-s, so without
+        this the state of the timed steps, and the outputs --dump-outputs writes, would depend on the speed of the build and the box.
+        Device-side and stream-ordered: no host round trip that would let the warmed-up GPU idle before the warm-up steps."""
+        eng.params.copy_(init); eng.m.zero_(); eng.v.zero_(); eng.scalars.zero_(); eng.step_count = 0
+
+    def dump_outputs(path):
+        """What the last timed step computed -- the updated parameters, their gradient and the step's scalars (loss, mean log-cosh, L1 term,
+        L1 norm, clip coefficient, overflow-skipped steps) -- as float32 .npy files; a larger array is written as a fixed, seeded sample
+        (at most 7 M values each, < 64 MB in all)."""
+        os.makedirs(path, exist_ok=True)
+        cap = 7_000_000
+        for name, t in (("params", eng.params), ("grads", eng.grads), ("scalars", eng.scalars[:6])):
+            if t.numel() > cap:
+                idx = np.sort(np.random.default_rng(12345).integers(0, t.numel(), cap))
+                t = t[torch.from_numpy(idx).to(t.device)]
+            np.save(os.path.join(path, name + ".npy"), t.detach().float().cpu().numpy())
+
+    init = eng.params.clone()        # restart() point, identical on every rank; allocated last, so that the step's own tensors sit where they always did
     prewarm_steps, prewarm_s = prewarm(step)
+    restart()
     dt = timed(step)
     dt = all_max(dt)
     loss = dp.mean_loss()
     ms = dt / args.steps * 1e3
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs)
     # the same step replayed from ONE captured HIP graph (st_graph_*: step counter and learning rate on the device): reported
     # beside the eager number; `value` stays the eager one (the graph removes host launch work, which the asynchronous eager
     # loop already hides at this step length -- the GPU-side kernel boundaries cost the same either way)
     ms_graph = None
-    if world == 1 and not args.force_dp and not args.no_graph:
+    if args.full and world == 1 and not args.force_dp and not args.no_graph:
         eng.graph_capture(B, lrs)
         eng.gx.copy_(x); eng.gk.copy_(kn); eng.gy.copy_(y)
         ms_graph = timed(lambda i: eng.graph_step()) / args.steps * 1e3
         eng.graph_destroy()
     # fp32-grade STFT GEMMs from the bf16 matrix pipe (compute_dtype "f32x3"), reported BESIDE the exact-fp32 headline, never as it
     ms_x3 = None
-    if world == 1 and not args.force_dp and not args.no_f32x3 and args.dtype == "f32":
+    if args.full and world == 1 and not args.force_dp and not args.no_f32x3 and args.dtype == "f32":
         eng3 = StepEngine(d, dev, compute_dtype="f32x3")
         eng3.load_state_dict(model.state_dict())
         f3 = lambda i: eng3.train_step(x, kn, y, float(lrs[max(i - 1, 0)]))
@@ -272,7 +302,7 @@ def main():
             out["step_frac_of_16bit_mfma_peak"] = flops_step / (ms * 1e-3) / 1e12 / PEAK_HALF_MFMA_TF
 
     # ------------------------------------------------------------------ roofline leg (outside the timed region)
-    if not args.no_roofline:
+    if args.full and not args.no_roofline:
         lib = eng.lib
         _lib.check(lib.st_profile_enable(1), "profile_enable")
         nprof = min(args.steps, 20)
@@ -378,12 +408,13 @@ def main():
             out["kernels_note"] = "avg_us: per-launch HIP events recorded by the library (st_profile_enable) on loss_backward, each ~2-3 us above the rocprofv3 figure; the optimizer kernel is not in this list"
 
     # ------------------------------------------------------------------ CPU baseline (rank 0, N = 1 only, bounded)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.scale == 1:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and args.scale == 1:
         from oracle.torch_cpu_step import CpuPort          # checker-side code: timed beside, never the product path
         # a B=32 step is a handful of small ops: past a few dozen threads torch's CPU backend only adds
         # synchronisation cost (256 threads measured 75 s/step here), so probe a few counts and time the best one
         ncpu = os.cpu_count() or 1
         Bc = 32
+        X, Y, KN = (a.cpu().numpy() for a in (x, y, kn))
         port = CpuPort({k: v.detach().cpu().numpy() for k, v in model.state_dict().items()})
         xc, yc, kc = (torch.from_numpy(a[:Bc].copy()) for a in (X, Y, KN))
         best, cores = None, 1

@@ -4,6 +4,7 @@
 #   tools/ae_ablate.sh build   (in the build container)      tools/ae_ablate.sh run   (on the GPU box, via gpurun)
 REPO=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 VARIANTS="${VARIANTS:-0 1 2 4 8 16 32 64 65 127}"
+BENCH_EXTRA="--full $BENCH_EXTRA"      # the per-kernel times are in the bench's --full line
 if [ "$1" = "build" ]; then
   mkdir -p $REPO/gpurun_in
   for v in $VARIANTS; do

@@ -15,7 +15,7 @@ prof bf16_all_b1024 "--dtype bf16_all --batch 1024"
 prof scale8_b64_f32 "--scale 8 --batch 64"
 prof scale8_b64_f16_all "--scale 8 --batch 64 --dtype f16_all"
 cd $REPO
-b() { timeout 600 python bench.py $2 > $OUT/bench_$1.json 2> $OUT/bench_$1.err; tail -c 600 $OUT/bench_$1.json | head -c 300; echo; }
+b() { timeout 600 python bench.py --full $2 > $OUT/bench_$1.json 2> $OUT/bench_$1.err; tail -c 600 $OUT/bench_$1.json | head -c 300; echo; }
 b f32 ""
 b bf16 "--dtype bf16 --no-cpu-baseline"
 b bf16_all "--dtype bf16_all --no-cpu-baseline"

@@ -2,7 +2,7 @@
 # GPU box: the bench.py JSON lines that carry roofline.traffic / step_traffic / mfma_busy, run AFTER profiles/r05_pmc_traffic_*.json of the same sources are in
 # place (those fields are quoted only from a source-hash-matched file).  Output: gpurun_out/r05/bench_*.json
 REPO=${GRAFT_REPO_ROOT:-$(pwd)}; OUT=$REPO/gpurun_out/r05; mkdir -p $OUT; cd $REPO
-b() { timeout 600 python bench.py $2 > $OUT/bench_$1.json 2> $OUT/bench_$1.err; python - "$OUT/bench_$1.json" <<'PY'
+b() { timeout 600 python bench.py --full $2 > $OUT/bench_$1.json 2> $OUT/bench_$1.err; python - "$OUT/bench_$1.json" <<'PY'
 import json, sys
 d = json.loads([l for l in open(sys.argv[1]) if l.startswith("{")][-1]); r = d.get("roofline", {})
 print(sys.argv[1].split("bench_")[-1], d["ms_per_step"], "graph", d.get("ms_per_step_graph"), "roofline", r.get("kernel"), r.get("frac"), r.get("frac_rocprof"), "traffic", r.get("traffic"),

@@ -17,7 +17,7 @@ prof scale8_b64_f32 "--scale 8 --batch 64"
 prof scale8_b64_f16_all "--scale 8 --batch 64 --dtype f16_all"
 [ -n "$ONLY_PROF" ] && { ls $OUT | wc -l; exit 0; }      # ONLY_PROF=1: the profiles / PMC passes alone (after a source change that does not move any number, e.g. a header comment)
 cd $REPO
-b() { timeout 600 python bench.py $2 > $OUT/bench_$1.json 2> $OUT/bench_$1.err; tail -c 600 $OUT/bench_$1.json | head -c 300; echo; }
+b() { timeout 600 python bench.py --full $2 > $OUT/bench_$1.json 2> $OUT/bench_$1.err; tail -c 600 $OUT/bench_$1.json | head -c 300; echo; }
 b bf16 "--dtype bf16 --no-cpu-baseline"
 b f32x3 "--dtype f32x3 --no-cpu-baseline"
 b f32_b512 "--batch 512 --no-cpu-baseline"

@@ -4,7 +4,7 @@
 REPO=${GRAFT_REPO_ROOT:-$(pwd)}; OUT=$REPO/gpurun_out/var; mkdir -p "$OUT"
 for lib in "" $REPO/variants/lib_*.so; do
     n=$(basename "${lib:-intree}" .so)
-    ST_LIB_PATH=$lib python "$REPO/bench.py" --steps 50 --warmup 10 --no-cpu-baseline --no-f32x3 --no-graph "$@" > "$OUT/$n.json" 2> "$OUT/$n.err"
+    ST_LIB_PATH=$lib python "$REPO/bench.py" --full --steps 50 --warmup 10 --no-cpu-baseline --no-f32x3 --no-graph "$@" > "$OUT/$n.json" 2> "$OUT/$n.err"
     python - "$OUT/$n.json" "$n" <<'P'
 import json, sys
 try:
