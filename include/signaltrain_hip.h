@@ -359,6 +359,12 @@ int st_ae_acts(const st_dims* d, const float* v, const float* knobs, const float
  *   x [B][L] fp32, knobs_wc [B][4] = (threshold dB, ratio, attack s, release s) in WORLD coordinates
  *   (Effect.knobs_wc, audio.py:455), y [B][ysz] = the last ysz samples of the processed window (datasets.py:327-330). */
 int st_compressor_4c(const float* x, const float* knobs_wc, float sr, int B, int L, int ysz, float* y, void* stream);
+/* audio.compressor (signaltrain/audio.py:349-371), the effect of the reference's `comp` task (audio.Compressor): a dB envelope
+ * (20 log10(|x| + 1e-6)) smoothed by a first-order Butterworth low-pass at 1 / (attackrel sr) of Nyquist, started at its first sample,
+ * then the static curve on the smoothed envelope; float64 envelope and gain, y rounded to fp32 (y == x where the envelope stays at or
+ * below the threshold).  The envelope is a linear recurrence and runs as a parallel scan in one workgroup per window.
+ *   x [B][L] fp32, knobs_wc [B][3] = (threshold dB, ratio, attack / release s) in WORLD coordinates, y [B][ysz] = the last ysz samples. */
+int st_compressor(const float* x, const float* knobs_wc, float sr, int B, int L, int ysz, float* y, void* stream);
 /* One training minibatch of the synthetic comp_4c task made on the device in ONE launch (st_feed.h; replaces
  * SynthAudioDataSet.gen_single_chunk, datasets.py:312-334, over audio.synth_input_sample, audio.py:296-334, chooser set
  * {0,1,2,4,6,7}, and compressor_4controls): per window the test signal, knobs = Beta(0.8, 0.8) - 0.5 (audio.py:20-21,
@@ -375,6 +381,19 @@ int st_compressor_4c(const float* x, const float* knobs_wc, float sr, int B, int
  * Outputs x [B][L], y [B][ysz], knobs [B][4] (fp32, normalised to [-0.5, 0.5]). */
 size_t st_synth_comp4c_scratch_floats(int B, int L);
 int st_synth_comp4c(unsigned seed, unsigned long long first_window, int B, int L, int ysz, int K, float sr,
+                    const float* knob_lo, const float* knob_hi, int augment, int chooser, const float* pink_in,
+                    float* x, float* y, float* knobs, float* scratch, void* stream);
+/* The same feed for every synthetic effect the library generates on the device; `effect` is an ST_FX_* id, the other arguments are
+ * st_synth_comp4c's (which is st_synth_effect(ST_FX_COMP4C, ...) with K == 4):
+ *   ST_FX_COMP4C  compressor_4controls, 1 <= K <= 4: knobs with index >= K are fixed at knob_lo[k] (knob_lo / knob_hi always carry 4
+ *                 entries) -- e.g. Comp_Just_Thresh (K = 1: threshold, then ratio 3, attack 0.05 s, release 1 s) and Compressor_4c_OneSetting;
+ *                 for K == 4 the window stream is st_synth_comp4c's, bit for bit;
+ *   ST_FX_COMP    the envelope compressor of st_compressor, K == 3 (threshold, ratio, attack / release s); with scratch (and L % 64 == 0)
+ *                 the generator leaves the dB signal there and a second launch runs the envelope scan.
+ * Every window is a function of (seed, window index) only; knobs [B][K].  Wrong ids and knob counts are refused before any launch. */
+enum { ST_FX_COMP4C = 0, ST_FX_COMP = 1 };
+size_t st_synth_effect_scratch_floats(int effect, int B, int L);
+int st_synth_effect(int effect, unsigned seed, unsigned long long first_window, int B, int L, int ysz, int K, float sr,
                     const float* knob_lo, const float* knob_hi, int augment, int chooser, const float* pink_in,
                     float* x, float* y, float* knobs, float* scratch, void* stream);
 

@@ -17,14 +17,14 @@ if __name__ == "__main__":
     p.add_argument('--gpus', type=int, default=None, help="data-parallel world size this job is meant to run on; launch with "
                    "`python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 run_train.py --gpus N ...` "
                    "(one process per GPU); checked against WORLD_SIZE")
-    p.add_argument('--device-feed', action='store_true', default=True, help="(default) generate every training minibatch on the GPU (st_synth_comp4c) and keep the validation set in HBM")
+    p.add_argument('--device-feed', action='store_true', default=True, help="(default) generate every training minibatch on the GPU (st_synth_effect) and keep the validation set in HBM")
     p.add_argument('--host-feed', dest='device_feed', action='store_false', help="the reference's feed instead: a torch DataLoader with 10 CPU workers over the Dataset items")
     p.add_argument('--resume-optimizer', action='store_true', help="restore Adam's moments (and, if the checkpoint belongs to this schedule, the position in the run) from --checkpoint")
     p.add_argument('-b', '--batch', type=int, help="batch size (per GPU); the reference's default.  On MI355X multiples of 256 windows (8192-sample window) fill the tile rounds of the analysis "
                                                         "forward: 379 k windows/s at 200, 418-426 k at 256, 477 k at 512 in fp32 (DESIGN.md section 5)", default=200)
     p.add_argument('--checkpoint', help='name of checkpoint .tar file to start from', default='modelcheckpoint.tar')
     p.add_argument('-c', '--compand', help='mu-law compand the audio of a file dataset (datasets.py:218-220)', action='store_true')
-    p.add_argument('--effect', help="effect to learn, the reference's keys (run_train.py:55-80): comp_4c | comp_large | files are built here "
+    p.add_argument('--effect', help="effect to learn, the reference's keys (run_train.py:55-80): comp_4c | comp_large | comp | comp_t | comp_one | files are built here "
                    "(comp_4c_large is kept as an alias of comp_large); the reference's other keys are named in the error message", default='comp_4c')
     p.add_argument('--epochs', type=int, default=1000)
     p.add_argument('--lrmax', type=float, help="maximum learning rate", default=1e-4)
@@ -35,12 +35,13 @@ if __name__ == "__main__":
     p.add_argument('--shrink', type=int, help='shrink output chunk relative to input by this divisor', default=4)
     p.add_argument('-t', '--target', help='accepted for compatibility', default="stream")
     args = p.parse_args()
-    # the reference's effect table (run_train.py:55-80); the hot path carries the 4-knob compressor family and file pairs
-    EFFECTS = {'comp_4c': 'Compressor_4c', 'comp_large': 'Compressor_4c_Large', 'comp_4c_large': 'Compressor_4c_Large', 'files': 'FileEffect'}
-    NOT_BUILT = ('comp', 'comp_t', 'comp_one', 'denoise', 'lowpass')      # audio.Compressor / Comp_Just_Thresh / Compressor_4c_OneSetting / Denoise / LowPass
+    # the reference's effect table (run_train.py:55-80); the hot path carries the compressor family and file pairs
+    EFFECTS = {'comp_4c': 'Compressor_4c', 'comp_large': 'Compressor_4c_Large', 'comp_4c_large': 'Compressor_4c_Large', 'comp': 'Compressor',
+               'comp_t': 'Comp_Just_Thresh', 'comp_one': 'Compressor_4c_OneSetting', 'files': 'FileEffect'}
+    NOT_BUILT = ('denoise', 'lowpass')      # audio.Denoise / LowPass
     if args.effect not in EFFECTS:
         if args.effect in NOT_BUILT or 'VST' in args.effect:
-            raise SystemExit(f"--effect {args.effect}: a key of the reference's run_train.py that signaltrain_amd does not build (its scope is the comp_4c training path: "
+            raise SystemExit(f"--effect {args.effect}: a key of the reference's run_train.py that signaltrain_amd does not build (its scope is the compressor family and file pairs: "
                              f"{', '.join(k for k in EFFECTS if k != 'comp_4c_large')}); not built: {', '.join(NOT_BUILT)}, VST*")
         raise SystemExit(f"Effect option '{args.effect}' is not yet added (available: {', '.join(k for k in EFFECTS if k != 'comp_4c_large')})")       # run_train.py:79-80
     if args.target not in ("chunk", "stream"):

@@ -59,8 +59,12 @@ SIGNATURES = {
     "st_ae_acts_floats": (C.c_size_t, [_D]),
     "st_ae_acts": (_i, [_D, _p, _p, _p, _i, _p, _p]),
     "st_compressor_4c": (_i, [_p, _p, C.c_float, C.c_int, C.c_int, C.c_int, _p, _p]),
+    "st_compressor": (_i, [_p, _p, C.c_float, C.c_int, C.c_int, C.c_int, _p, _p]),
     "st_synth_comp4c_scratch_floats": (C.c_size_t, [_i, _i]),
     "st_synth_comp4c": (_i, [C.c_uint, C.c_ulonglong, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float),
+                             C.c_int, C.c_int, _p, _p, _p, _p, _p, _p]),
+    "st_synth_effect_scratch_floats": (C.c_size_t, [_i, _i, _i]),
+    "st_synth_effect": (_i, [_i, C.c_uint, C.c_ulonglong, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float),
                              C.c_int, C.c_int, _p, _p, _p, _p, _p, _p]),
     "st_fe_frames": (_i, [C.c_int] * 4),
     "st_fe_ws_floats": (C.c_size_t, [C.c_int] * 6),
@@ -115,6 +119,9 @@ SIGNATURES = {
     "st_dp_sync": (_i, [_p, _p]),
     "st_dp_train_step": (_i, [_p, _D, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _f, _f, _f, _f, _i, _i, _p]),
 }
+
+# effect ids of st_synth_effect (include/signaltrain_hip.h ST_FX_*)
+FX_COMP4C, FX_COMP = 0, 1
 
 # st_dims.prec levels (include/signaltrain_hip.h ST_PREC_*) by the names the Python surface uses
 PREC = {"f32": 0, "bf16": 1, "bf16_all": 2, "f16": 3, "f16_all": 4, "f32x3": 5}

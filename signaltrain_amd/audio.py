@@ -1,6 +1,7 @@
 """Effects and audio files -- the parts of signaltrain/audio.py the training driver needs: the Effect classes (:449-537, knob names / ranges,
-normalised <-> world knob coordinates), the comp_4c target effect (compressor_4controls :380-426: on the GPU through st_compressor_4c /
-st_synth_comp4c, on the host through the gcc-built helper for file datasets), wav reading / writing (:207-262) and file-defined effects
+normalised <-> world knob coordinates), the compressor target effects (compressor_4controls :380-426: on the GPU through st_compressor_4c /
+st_synth_effect, on the host through the gcc-built helper for file datasets; compressor :349-371: st_compressor / st_synth_effect, and a
+numpy / scipy restatement on the host), wav reading / writing (:207-262) and file-defined effects
 (:624-670).  The synthetic test signals themselves are generated on the GPU (csrc/st_feed.h, audio_device.py); their numpy restatement lives
 on the checker side (oracle/host_audio.py)."""
 import ctypes as C
@@ -51,12 +52,48 @@ def compressor_4controls(x, thresh=-24.0, ratio=2.0, attackTime=0.01, releaseTim
     return (lin * x).astype(np.float32)
 
 
+def compressor(x, thresh=-24.0, ratio=2.0, attackrel=0.045, sr=44100.0):
+    """audio.py:349-371 (the `comp` effect): the dB signal 20 log10(|x| + 1e-6) in float32, smoothed by the first-order Butterworth low-pass
+    at 1 / (attackrel sr) of Nyquist in float64 -- written out from the bilinear transform, k = tan(pi Wn / 2): b0 = b1 = k / (1 + k), pole
+    (1 - k) / (1 + k) -- started from its steady state at the first sample (e[0] = d[0]); the static curve on the smoothed envelope, the gain
+    applied in float64 and the result rounded to float32 (the training target's type).  The device form is st_compressor."""
+    from scipy.signal import lfilter
+    x = np.asarray(x, dtype=np.float32)
+    d = np.float32(20.0) * np.log10(np.abs(x) + np.float32(1e-6))
+    k = np.tan(np.pi / (2.0 * float(attackrel) * float(sr)))
+    b0, p = k / (1.0 + k), (1.0 - k) / (1.0 + k)
+    e = lfilter([b0, b0], [1.0, -p], d.astype(np.float64), zi=[(1.0 - b0) * float(d[0])])[0] if len(d) else np.zeros(0)
+    out = np.where(e > thresh, thresh + (e - thresh) / ratio, e)
+    return (x * np.power(10.0, (out - e) / 20)).astype(np.float32)
+
+
+def _device_effect(fn, effect, x, kw, y_size):
+    """y [B, y_size] of the library's effect `fn` (st_compressor_4c / st_compressor) on device tensors x [B, L] with world-coordinate knobs kw [B, K]."""
+    import ctypes as C
+    import torch
+    from . import _lib
+    x = x.to(torch.float32).contiguous(); B, L = x.shape
+    kw = kw.to(torch.float32).contiguous()
+    y_size = L if y_size is None else int(y_size)
+    y = torch.empty(B, y_size, dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):             # the library launches on the current device
+        _lib.check(getattr(_lib.load(), fn)(_lib.ptr(x), _lib.ptr(kw), float(effect.sr), B, L, y_size, _lib.ptr(y),
+                                            C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)), fn)
+    return y
+
+
 class Effect:
-    """audio.py:449-480."""
+    """audio.py:449-480.  feed_fx: the st_synth_effect id (_lib.FX_*) of the library's fused device feed for this effect, None if there is none;
+    feed_ranges(): the four (low, high) knob rows that feed takes (knobs past len(knob_ranges) are fixed at their low end)."""
+    feed_fx = None
 
     def __init__(self, sr=44100.0, dtype=np.float32):
         self.name = 'Generic Effect'; self.knob_names = ['knob']
         self.knob_ranges = np.array([[0, 1]], dtype=dtype); self.sr = sr; self.is_inverse = False
+
+    def feed_ranges(self):
+        r = np.asarray(self.knob_ranges, dtype=np.float64)
+        return np.concatenate([r, np.zeros((4 - len(r), 2))]) if len(r) < 4 else r
 
     def knobs_wc(self, knobs_nn):
         return (self.knob_ranges[:, 0] + (knobs_nn + 0.5) * (self.knob_ranges[:, 1] - self.knob_ranges[:, 0])).tolist()
@@ -73,8 +110,38 @@ class Effect:
         return self.go_wc(x, self.knobs_wc(knobs_nn), **kwargs)
 
 
+class Compressor(Effect):
+    """audio.py:484-491: the envelope compressor (`comp`): threshold, ratio and one attack / release time."""
+    feed_fx = 1                                   # _lib.FX_COMP
+
+    def __init__(self, **kwargs):
+        super().__init__(**kwargs)
+        self.name = 'Compressor'
+        self.knob_names = ['threshold', 'ratio', 'attackreleaseTime']
+        self.knob_ranges = np.array([[-30, 0], [1, 5], [1e-3, 4e-2]])
+
+    def go_wc(self, x, knobs_w):
+        return compressor(x, thresh=knobs_w[0], ratio=knobs_w[1], attackrel=knobs_w[2], sr=self.sr), x
+
+    def go_device(self, x, knobs_nn, y_size=None):
+        """Batched effect on the GPU (st_compressor): x [B,L] and knobs_nn [B,3] in [-.5,.5] as device tensors -> y [B,y_size]
+        (the last y_size samples).  No CPU fallback."""
+        if x.device.type != "cuda":
+            raise RuntimeError("Compressor.go_device needs ROCm device tensors")
+        return _device_effect("st_compressor", self, x, _knobs_wc_device(self.knob_ranges, knobs_nn, x.device), y_size)
+
+
+def _knobs_wc_device(knob_ranges, knobs_nn, device):
+    """Effect.knobs_wc (audio.py:455) on a [B, K] device tensor, float32."""
+    import torch
+    lo = torch.as_tensor(np.asarray(knob_ranges)[:, 0], dtype=torch.float32, device=device)
+    hi = torch.as_tensor(np.asarray(knob_ranges)[:, 1], dtype=torch.float32, device=device)
+    return (lo + (knobs_nn.to(torch.float32) + 0.5) * (hi - lo)).contiguous()
+
+
 class Compressor_4c(Effect):
     """audio.py:493-500."""
+    feed_fx = 0                                   # _lib.FX_COMP4C
 
     def __init__(self, **kwargs):
         super().__init__(**kwargs)
@@ -89,21 +156,9 @@ class Compressor_4c(Effect):
     def go_device(self, x, knobs_nn, y_size=None):
         """Batched effect on the GPU (st_compressor_4c): x [B,L] and knobs_nn [B,4] in [-.5,.5] as device tensors ->
         y [B,y_size] (the last y_size samples, datasets.py:327-330).  No CPU fallback."""
-        import ctypes as C
-        import torch
-        from . import _lib
         if x.device.type != "cuda":
             raise RuntimeError("Compressor_4c.go_device needs ROCm device tensors")
-        x = x.to(torch.float32).contiguous(); B, L = x.shape
-        y_size = L if y_size is None else int(y_size)
-        lo = torch.as_tensor(self.knob_ranges[:, 0], dtype=torch.float32, device=x.device)
-        hi = torch.as_tensor(self.knob_ranges[:, 1], dtype=torch.float32, device=x.device)
-        kw = (lo + (knobs_nn.to(torch.float32) + 0.5) * (hi - lo)).contiguous()          # Effect.knobs_wc, audio.py:455
-        y = torch.empty(B, y_size, dtype=torch.float32, device=x.device)
-        with torch.cuda.device(x.device):             # the library launches on the current device
-            _lib.check(_lib.load().st_compressor_4c(_lib.ptr(x), _lib.ptr(kw), float(self.sr), B, L, y_size, _lib.ptr(y),
-                                                    C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)), "st_compressor_4c")
-        return y
+        return _device_effect("st_compressor_4c", self, x, _knobs_wc_device(self.knob_ranges, knobs_nn, x.device), y_size)
 
 
 class Compressor_4c_Large(Compressor_4c):
@@ -113,6 +168,44 @@ class Compressor_4c_Large(Compressor_4c):
         super().__init__(**kwargs)
         self.name = 'Compressor_4c_Large'
         self.knob_ranges = np.array([[-50, 0], [1.5, 10], [1e-3, 1], [1e-3, 1]])
+
+
+class Comp_Just_Thresh(Effect):
+    """audio.py:513-526: compressor_4controls with the threshold as its only knob; ratio 3, attack 50 ms, release 1 s fixed (the reference's
+    comparison effect for the LA2A)."""
+    feed_fx = 0                                   # _lib.FX_COMP4C with K = 1
+
+    def __init__(self, **kwargs):
+        super().__init__(**kwargs)
+        self.name = 'Comp_Just_Thresh'
+        self.knob_names = ['threshold']
+        self.knob_ranges = np.array([[-50, -10]])
+        self.ratio, self.attack, self.release = 3.0, .05, 1.0
+
+    def feed_ranges(self):
+        fixed = [self.ratio, self.attack, self.release]
+        return np.array([list(self.knob_ranges[0])] + [[v, v] for v in fixed], dtype=np.float64)
+
+    def go_wc(self, x, knobs_w):
+        return compressor_4controls(x, thresh=knobs_w[0], ratio=self.ratio, attackTime=self.attack, releaseTime=self.release, sr=self.sr), x
+
+    def go_device(self, x, knobs_nn, y_size=None):
+        """st_compressor_4c with world knobs (threshold, 3, 0.05, 1): x [B,L], knobs_nn [B,1] device tensors -> y [B,y_size]."""
+        import torch
+        if x.device.type != "cuda":
+            raise RuntimeError("Comp_Just_Thresh.go_device needs ROCm device tensors")
+        thr = _knobs_wc_device(self.knob_ranges, knobs_nn, x.device)
+        fixed = torch.tensor([self.ratio, self.attack, self.release], dtype=torch.float32, device=x.device).expand(thr.shape[0], 3)
+        return _device_effect("st_compressor_4c", self, x, torch.cat([thr, fixed], 1), y_size)
+
+
+class Compressor_4c_OneSetting(Compressor_4c):
+    """audio.py:529-536: compressor_4controls locked in one setting (degenerate ranges; the threshold's is written high to low)."""
+
+    def __init__(self, **kwargs):
+        super().__init__(**kwargs)
+        self.name = 'Compressor_4c_OneSetting'
+        self.knob_ranges = np.array([[-25.001, -25.], [4, 4.001], [5e-3, 5.001e-3], [2e-2, 2.001e-2]])
 
 
 # ------------------------------------------------------------------------------------------------ wav files + file-defined effects

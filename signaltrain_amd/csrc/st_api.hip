@@ -1962,28 +1962,57 @@ extern "C" int st_compressor_4c(const float* x, const float* knobs_wc, float sr,
     ST_LAUNCHED("compressor_4c"); return ST_OK;
 }
 
-// scratch of st_synth_comp4c for the full-featured path: [gain curve B * L | world knobs 4 B] and, for power-of-two windows beyond the in-LDS FFT
+extern "C" int st_compressor(const float* x, const float* knobs_wc, float sr, int B, int L, int ysz, float* y, void* stream)
+{
+    ST_REQ(x && knobs_wc && y, "st_compressor: null pointer");
+    ST_REQ(B > 0 && L > 0 && ysz > 0 && ysz <= L && sr > 0.f, "st_compressor: bad sizes (B=%d L=%d ysz=%d)", B, L, ysz);
+    hipLaunchKernelGGL(stm::compressor_env_kernel, dim3(B), dim3(256), 0, st_stream(stream), x, nullptr, knobs_wc, 3, sr, L, ysz, y);
+    ST_LAUNCHED("compressor_env"); return ST_OK;
+}
+
+// scratch of st_synth_effect for the full-featured path: [gain curve (ST_FX_COMP: dB signal) B * L | world knobs 4 B] and, for power-of-two windows beyond the in-LDS FFT
 // (8192 < L <= 65536), [1/f noise B * L | per-window peaks | four-step FFT buffer 2 * min(B, 1024) * L]
 static const int FEED_FFT_SUB = 1024;      // windows per pass-1 / pass-2 launch pair of the long-window noise (a launch pair costs ~50 us whatever its size: few, large ones)
 static bool feed_long_fft(int L) { return L > stf::FFT_MAX && (L & (L - 1)) == 0 && L / stf::PL_N1 <= 256; }
-extern "C" size_t st_synth_comp4c_scratch_floats(int B, int L)
+static bool feed_effect_ok(int effect) { return effect == ST_FX_COMP4C || effect == ST_FX_COMP; }
+extern "C" size_t st_synth_effect_scratch_floats(int effect, int B, int L)
 {
-    if (B <= 0 || L <= 0) return 0;
-    size_t n = (size_t)B * (L + 4);
+    if (!feed_effect_ok(effect) || B <= 0 || L <= 0) return 0;
+    size_t n = (size_t)B * (L + 4);      // both effects: [gain curve or dB signal B * L | world knobs 4 B]
     if (feed_long_fft(L)) n += (size_t)B * L + (size_t)st_round_up(B, 64) + (size_t)2 * (B < FEED_FFT_SUB ? B : FEED_FFT_SUB) * L;
     return n;
 }
-extern "C" int st_synth_comp4c(unsigned seed, unsigned long long first_window, int B, int L, int ysz, int K, float sr,
+extern "C" size_t st_synth_comp4c_scratch_floats(int B, int L) { return st_synth_effect_scratch_floats(ST_FX_COMP4C, B, L); }
+template <int FX>
+static int feed_launch(const stf::FeedArgs& a, int B, size_t lds, void* stream)
+{
+    if (lds >= 65536) {      // exactly 64 KB of dynamic LDS beside a few static bytes: ask for it explicitly (the 160 KB request of ensure_dyn_lds is refused for a kernel with static LDS)
+        static std::mutex mu; static std::set<int> done;
+        int dev = 0; (void)hipGetDevice(&dev);
+        std::lock_guard<std::mutex> lk(mu);
+        if (!done.count(dev)) {
+            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&stf::synth_feed_kernel<FX>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            if (e != hipSuccess) return st_fail(ST_ERR_LAUNCH, "hipFuncSetAttribute(synth_feed_kernel, %zu B dynamic LDS): %s", lds, hipGetErrorString(e));
+            done.insert(dev);
+        }
+    }
+    hipLaunchKernelGGL(stf::synth_feed_kernel<FX>, dim3(B), dim3(256), lds, st_stream(stream), a);
+    ST_LAUNCHED(FX == ST_FX_COMP ? "synth_comp" : "synth_comp4c"); return ST_OK;
+}
+extern "C" int st_synth_effect(int effect, unsigned seed, unsigned long long first_window, int B, int L, int ysz, int K, float sr,
                                const float* knob_lo, const float* knob_hi, int augment, int chooser, const float* pink_in,
                                float* x, float* y, float* knobs, float* scratch, void* stream)
 {
-    ST_REQ(x && y && knobs && knob_lo && knob_hi, "st_synth_comp4c: null pointer");
-    ST_REQ(B > 0 && L > 0 && ysz > 0 && ysz <= L && sr > 0.f && K == 4, "st_synth_comp4c: bad sizes (B=%d L=%d ysz=%d K=%d)", B, L, ysz, K);
-    ST_REQ(chooser == -1 || chooser == 0 || chooser == 1 || chooser == 2 || chooser == 4 || chooser == 6 || chooser == 7 || chooser == 100, "st_synth_comp4c: signal family %d is not built (the compressor's set is 0,1,2,4,6,7)", chooser);
+    ST_REQ(feed_effect_ok(effect), "st_synth_effect: effect %d is not an ST_FX_* id (ST_FX_COMP4C = 0, ST_FX_COMP = 1)", effect);
+    ST_REQ(effect != ST_FX_COMP4C || (K >= 1 && K <= 4), "st_synth_effect: ST_FX_COMP4C takes 1 to 4 knobs, not K=%d", K);
+    ST_REQ(effect != ST_FX_COMP || K == 3, "st_synth_effect: ST_FX_COMP takes 3 knobs (threshold, ratio, attack/release), not K=%d", K);
+    ST_REQ(x && y && knobs && knob_lo && knob_hi, "st_synth_effect: null pointer");
+    ST_REQ(B > 0 && L > 0 && ysz > 0 && ysz <= L && sr > 0.f, "st_synth_effect: bad sizes (B=%d L=%d ysz=%d K=%d)", B, L, ysz, K);
+    ST_REQ(chooser == -1 || chooser == 0 || chooser == 1 || chooser == 2 || chooser == 4 || chooser == 6 || chooser == 7 || chooser == 100, "st_synth_effect: signal family %d is not built (the compressor's set is 0,1,2,4,6,7)", chooser);
     const bool fft_ok = L <= stf::FFT_MAX && (L & (L - 1)) == 0;
-    const bool long_fft = !fft_ok && !pink_in && scratch && feed_long_fft(L);      // scratch is then st_synth_comp4c_scratch_floats(B, L) floats (contract)
-    ST_REQ(fft_ok || pink_in || long_fft, "st_synth_comp4c: a %d-sample window needs either the 1/f noise from the caller (pink_in) or -- powers of two up to 65536 -- "
-           "st_synth_comp4c_scratch_floats() floats of scratch for the library's own transform", L);
+    const bool long_fft = !fft_ok && !pink_in && scratch && feed_long_fft(L);      // scratch is then st_synth_effect_scratch_floats(effect, B, L) floats (contract)
+    ST_REQ(fft_ok || pink_in || long_fft, "st_synth_effect: a %d-sample window needs either the 1/f noise from the caller (pink_in) or -- powers of two up to 65536 -- "
+           "st_synth_effect_scratch_floats() floats of scratch for the library's own transform", L);
     stf::FeedArgs a;
     a.x = x; a.y = y; a.knobs = knobs; a.pink_in = pink_in; a.pink_peak = nullptr; a.seed = seed; a.first = first_window;
     a.L = L; a.ysz = ysz; a.K = K; a.sr = sr; a.augment = augment; a.chooser = chooser;
@@ -2005,19 +2034,18 @@ extern "C" int st_synth_comp4c(unsigned seed, unsigned long long first_window, i
         ST_LAUNCHED("pink_long");
         a.pink_in = pink; a.pink_peak = peak;
     }
+    // dynamic LDS: the in-LDS FFT's buffer, else the in-kernel effect's (compressor_window's float[COMP_CH] holds the envelope scan's EnvLds as well)
+    static_assert(sizeof(stm::EnvLds) <= (size_t)stm::COMP_CH * sizeof(float), "the envelope scan's LDS must fit the in-kernel effect's buffer");
     const size_t lds = a.pink_in ? (split ? 0 : (size_t)stm::COMP_CH * sizeof(float)) : (size_t)stf::FFT_MAX * sizeof(float2);
-    if (lds >= 65536) {      // exactly 64 KB of dynamic LDS beside a few static bytes: ask for it explicitly (the 160 KB request of ensure_dyn_lds is refused for a kernel with static LDS)
-        static std::mutex mu; static std::set<int> done;
-        int dev = 0; (void)hipGetDevice(&dev);
-        std::lock_guard<std::mutex> lk(mu);
-        if (!done.count(dev)) {
-            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&stf::synth_comp4c_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return st_fail(ST_ERR_LAUNCH, "hipFuncSetAttribute(synth_comp4c_kernel, %zu B dynamic LDS): %s", lds, hipGetErrorString(e));
-            done.insert(dev);
+    if (effect == ST_FX_COMP) {
+        ST_TRY(feed_launch<ST_FX_COMP>(a, B, lds, stream));
+        if (split) {
+            hipLaunchKernelGGL(stm::compressor_env_kernel, dim3(B), dim3(256), 0, st_stream(stream), x, a.gc, a.kw, 4, sr, L, ysz, y);
+            ST_LAUNCHED("compressor_env");
         }
+        return ST_OK;
     }
-    hipLaunchKernelGGL(stf::synth_comp4c_kernel, dim3(B), dim3(256), lds, st_stream(stream), a);
-    ST_LAUNCHED("synth_comp4c");
+    ST_TRY(feed_launch<ST_FX_COMP4C>(a, B, lds, stream));
     if (split) {
         hipLaunchKernelGGL(stm::comp_smooth_kernel, dim3((B + 63) / 64), dim3(64), 0, st_stream(stream), a.gc, a.kw, sr, B, L);
         ST_LAUNCHED("comp_smooth");
@@ -2025,6 +2053,13 @@ extern "C" int st_synth_comp4c(unsigned seed, unsigned long long first_window, i
         ST_LAUNCHED("comp_apply");
     }
     return ST_OK;
+}
+extern "C" int st_synth_comp4c(unsigned seed, unsigned long long first_window, int B, int L, int ysz, int K, float sr,
+                               const float* knob_lo, const float* knob_hi, int augment, int chooser, const float* pink_in,
+                               float* x, float* y, float* knobs, float* scratch, void* stream)
+{
+    ST_REQ(K == 4, "st_synth_comp4c: bad sizes (B=%d L=%d ysz=%d K=%d)", B, L, ysz, K);
+    return st_synth_effect(ST_FX_COMP4C, seed, first_window, B, L, ysz, K, sr, knob_lo, knob_hi, augment, chooser, pink_in, x, y, knobs, scratch, stream);
 }
 
 // ------------------------------------------------------------------------------ generic learned-basis front end (a15)

@@ -10,8 +10,9 @@
 //          (64 KB for the 8192-sample window; longer windows take the noise from a caller-provided buffer);
 //   signal the chosen family evaluated per sample, peak-normalised (normish: two passes, the first only takes the maximum), polarity, 1e-8 noise;
 //   effect the 4-control compressor on the finished window (stm::compressor_window: parallel gain computer, sequential attack / release
-//          smoother in one lane, parallel apply) -> the last ysz samples.
-// Output contract: x [B][L], y [B][ysz], knobs [B][4] in [-0.5, 0.5] (float32), as the reference's collated batch (train.py:104-120 casts y to float).
+//          smoother in one lane, parallel apply) -> the last ysz samples; or (ST_FX_COMP) the envelope compressor of audio.py:349-371, whose
+//          linear envelope runs as a parallel scan (stm::env_compressor_window).  1 <= K <= 4 knobs: the ones past K are fixed at their low end.
+// Output contract: x [B][L], y [B][ysz], knobs [B][K] in [-0.5, 0.5] (float32), as the reference's collated batch (train.py:104-120 casts y to float).
 // Parity is DISTRIBUTIONAL (another generator than numpy's): tests compare per-family peak ranges, the even symmetry and 1/f slope of the noise,
 // the box structure, the Beta(0.8, 0.8) law, and the compressor against golden G9 through the same device function.
 #pragma once
@@ -52,7 +53,7 @@ struct FeedArgs {
     int L, ysz, K; float sr;
     float lo[4], hi[4];                     // knob ranges (Effect.knob_ranges, audio.py:493-510)
     int augment;
-    float* gc; float* kw;                   // optional scratch [B][L] + [B][4]: the generator leaves the gain curve and the world-coordinate knobs there and
+    float* gc; float* kw;                   // optional scratch [B][L] + [B][4]: the generator leaves the gain curve (ST_FX_COMP: the dB signal) and the world-coordinate knobs there and
                                             // stm::comp_smooth_apply_kernel finishes the effect (lane per window); NULL: the effect runs inside this kernel
     int chooser;                            // -1: drawn per window from {0, 1, 2, 4, 6, 7}; else forced (tests); 100 = the bare 1/f noise (tests)
 };
@@ -193,8 +194,10 @@ pink_long_pass2_kernel(const unsigned seed, const unsigned long long first, cons
     if (threadIdx.x == 0) atomicMax(reinterpret_cast<unsigned*>(peak + b), __float_as_uint(m));
 }
 
+// the effect a feed launch applies (include/signaltrain_hip.h ST_FX_*): a template parameter, so the comp_4c instantiation is the kernel it always was
+template <int FX>
 __global__ void __launch_bounds__(256)
-synth_comp4c_kernel(const FeedArgs a)
+synth_feed_kernel(const FeedArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) float feed_lds[];      // float2[FFT_MAX] (pink) -- later float[COMP_CH] (compressor)
     __shared__ float red[4];
@@ -209,6 +212,7 @@ synth_comp4c_kernel(const FeedArgs a)
     const int ch = feed_family(d, a.chooser);      // {0, 1, 2, 4, 6, 7}
     float kn[4], kw[4];
     for (int k = 0; k < 4; ++k) { kn[k] = d.beta(0.8f) - 0.5f; kw[k] = a.lo[k] + (kn[k] + 0.5f) * (a.hi[k] - a.lo[k]); }
+    for (int k = a.K; k < 4; ++k) kw[k] = a.lo[k];                   // K < 4: the remaining knobs are fixed settings (all four are drawn: one stream for every K)
     // randsine (audio.py:96-104)
     const int s_n = d.randint(1, 3);
     float s_amp[2], s_frq[2], s_t0[2];
@@ -289,24 +293,32 @@ synth_comp4c_kernel(const FeedArgs a)
             }
             const float4 v = make_float4(sample(n, pk.x), sample(n + 1, pk.y), sample(n + 2, pk.z), sample(n + 3, pk.w));
             *reinterpret_cast<float4*>(xb + n) = v;
-            if (gcb) *reinterpret_cast<float4*>(gcb + n) = make_float4(stm::comp_gain_curve(v.x, (double)kw[0], (double)kw[1]), stm::comp_gain_curve(v.y, (double)kw[0], (double)kw[1]),
+            if (gcb) {
+                if (FX == ST_FX_COMP) *reinterpret_cast<float4*>(gcb + n) = make_float4(stm::env_db(v.x), stm::env_db(v.y), stm::env_db(v.z), stm::env_db(v.w));
+                else *reinterpret_cast<float4*>(gcb + n) = make_float4(stm::comp_gain_curve(v.x, (double)kw[0], (double)kw[1]), stm::comp_gain_curve(v.y, (double)kw[0], (double)kw[1]),
                                                                        stm::comp_gain_curve(v.z, (double)kw[0], (double)kw[1]), stm::comp_gain_curve(v.w, (double)kw[0], (double)kw[1]));
+            }
         }
     } else {
         for (int n = threadIdx.x; n < L; n += 256) {
             const float pk = want_pink ? (pin ? (a.pink_peak ? pin[n] * inv_peak : pin[n]) : fa[n].x * inv_peak) : 0.f;
             const float v = sample(n, pk);
             xb[n] = v;
-            if (gcb) gcb[n] = stm::comp_gain_curve(v, (double)kw[0], (double)kw[1]);
+            if (gcb) gcb[n] = FX == ST_FX_COMP ? stm::env_db(v) : stm::comp_gain_curve(v, (double)kw[0], (double)kw[1]);
         }
     }
     if (threadIdx.x == 0) { for (int k = 0; k < 4; ++k) if (k < a.K) a.knobs[(size_t)b * a.K + k] = kn[k]; }
-    if (a.gc) {                                                      // workgroup-uniform: the recurrence + apply run lane-per-window (comp_smooth_kernel, comp_apply_kernel)
-        if (threadIdx.x == 0) { for (int k = 0; k < 4; ++k) a.kw[(size_t)b * 4 + k] = kw[k]; }
+    if (a.gc) {                                                      // workgroup-uniform: the effect finishes in the next launches (comp_smooth_kernel +
+        if (threadIdx.x == 0) { for (int k = 0; k < 4; ++k) a.kw[(size_t)b * 4 + k] = kw[k]; }      // comp_apply_kernel, or compressor_env_kernel)
         return;
     }
     __threadfence_block();
     __syncthreads();                                                 // the window is complete (and the FFT buffer is dead)
+    if (FX == ST_FX_COMP) {                                          // the envelope compressor (audio.py:349-371), a scan over the window
+        stm::env_compressor_window(xb, nullptr, a.y + (size_t)b * a.ysz, (double)kw[0], (double)kw[1], stm::env_coef((double)kw[2], (double)a.sr),
+                                   L, a.ysz, reinterpret_cast<stm::EnvLds*>(feed_lds));
+        return;
+    }
     // ---- the effect (audio.py:380-426) on the finished window, inside this workgroup
     const double alphaA = exp(-log(9.0) / ((double)a.sr * (double)kw[2])), alphaR = exp(-log(9.0) / ((double)a.sr * (double)kw[3]));
     stm::compressor_window(xb, a.y + (size_t)b * a.ysz, (double)kw[0], (double)kw[1], alphaA, alphaR, L, a.ysz, feed_lds, &carry);

@@ -941,6 +941,99 @@ compressor_4c_kernel(const float* __restrict__ x, const float* __restrict__ knob
     compressor_window(x + (size_t)b * L, y + (size_t)b * ysz, thresh, ratio, alphaA, alphaR, L, ysz, g, &carry);
 }
 
+// ---- the envelope compressor (audio.py:349-371, the `comp` effect): a dB envelope smoothed by a first-order Butterworth low-pass
+// (scipy butter(1, 1 / (attackrel sr)), lfilter started at lfilter_zi * d[0]), then the static curve on the smoothed envelope:
+//   d[n] = 20 log10(|x[n]| + 1e-6)                     float32 (float32 array, weak scalars; no -96 clip, unlike comp_gain_curve)
+//   e[0] = d[0],  e[n] = p e[n-1] + b0 (d[n] + d[n-1])  float64, as scipy's lfilter;  k = tan(pi Wn / 2), b0 = k / (1 + k), p = (1 - k) / (1 + k)
+//   y = x 10^((out - e) / 20), out = e > thresh ? thresh + (e - thresh) / ratio : e    (float64, rounded to float32; gain exactly 1 below thresh)
+// Unlike compressor_4controls' attack / release smoother (the coefficient depends on the sign of the step: a switched, non-linear recurrence),
+// this envelope is LINEAR in its state, so a run of m steps is the affine map e -> p^m e + B and maps compose associatively: the window is a
+// parallel scan.  Per LDS chunk of ENV_CH samples each thread composes the map of its ENV_R contiguous samples from a zero start, the maps
+// are scanned across the wave (shuffles) and across the four waves (LDS), and each thread re-runs its samples from its incoming state.
+constexpr int ENV_R = 8, ENV_CH = 256 * ENV_R;
+struct EnvLds {
+    double e[ENV_CH];                            // the chunk's envelope (coalesced apply pass)
+    float d[ENV_CH + ENV_CH / ENV_R];            // the chunk's d[n], one pad float per run: thread t reads from 9 t on, conflict-free
+    double wa[4], wb[4];                         // per-wave composed maps
+    double carry; float dcarry;                  // e and d of the previous chunk's last sample
+};
+__device__ __forceinline__ float env_db(const float xv) { return 20.0f * log10f(fabsf(xv) + 1e-6f); }
+struct EnvCoef { double b0, p; };
+__device__ __forceinline__ EnvCoef env_coef(const double attackrel, const double sr)
+{
+    const double k = tan(1.5707963267948966 / (attackrel * sr));       // Wn = 1 / (attackrel sr), prewarped for the bilinear transform
+    return EnvCoef{k / (1.0 + k), (1.0 - k) / (1.0 + k)};
+}
+// one window; every thread of a 256-thread workgroup calls it.  db: the window's d[n] precomputed (the feed's split form), or NULL: from x here.
+// y receives the last ysz samples.  The same function serves st_compressor and both forms of the feed, so all of them give identical y.
+__device__ __forceinline__ void
+env_compressor_window(const float* __restrict__ xb, const float* __restrict__ db, float* __restrict__ yb, const double thresh, const double ratio,
+                      const EnvCoef c, const int L, const int ysz, EnvLds* __restrict__ s)
+{
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6, i0 = t * ENV_R;
+    if (t == 0) { s->carry = 0.0; s->dcarry = 0.f; }
+    for (int c0 = 0; c0 < L; c0 += ENV_CH) {
+        const int n = L - c0 < ENV_CH ? L - c0 : ENV_CH;
+        for (int i = t; i < ENV_CH; i += 256) s->d[i + i / ENV_R] = i < n ? (db ? db[c0 + i] : env_db(xb[c0 + i])) : 0.f;
+        __syncthreads();
+        float dv[ENV_R];
+#pragma unroll
+        for (int k = 0; k < ENV_R; ++k) dv[k] = s->d[t * (ENV_R + 1) + k];
+        const float dm = t == 0 ? s->dcarry : s->d[t * (ENV_R + 1) - 2];      // d of the sample before the run
+        // the run's map e -> A e + Bv
+        double A = 1.0, Bv = 0.0;
+#pragma unroll
+        for (int k = 0; k < ENV_R; ++k) {
+            if (i0 + k >= n) break;
+            if (c0 + i0 + k == 0) { A = 0.0; Bv = (double)dv[0]; continue; }            // e[0] = d[0] whatever comes in
+            const double u = c.b0 * ((double)dv[k] + (double)(k ? dv[k - 1] : dm));
+            A *= c.p; Bv = __builtin_fma(c.p, Bv, u);
+        }
+        // inclusive scan over the wave: this map after the one of lanes below, (A, Bv) o (Ao, Bo) = (A Ao, A Bo + Bv)
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const double Ao = __shfl_up(A, o), Bo = __shfl_up(Bv, o);
+            if (lane >= o) { Bv = __builtin_fma(A, Bo, Bv); A *= Ao; }
+        }
+        if (lane == 63) { s->wa[w] = A; s->wb[w] = Bv; }
+        double Ae = __shfl_up(A, 1), Be = __shfl_up(Bv, 1);
+        if (lane == 0) { Ae = 1.0; Be = 0.0; }
+        __syncthreads();
+        double e = s->carry;                                                   // e[c0 - 1]
+        for (int v = 0; v < w; ++v) e = __builtin_fma(s->wa[v], e, s->wb[v]);
+        e = __builtin_fma(Ae, e, Be);                                          // e before the run
+#pragma unroll
+        for (int k = 0; k < ENV_R; ++k) {
+            if (i0 + k >= n) break;
+            if (c0 + i0 + k == 0) e = (double)dv[0];
+            else e = __builtin_fma(c.p, e, c.b0 * ((double)dv[k] + (double)(k ? dv[k - 1] : dm)));
+            s->e[i0 + k] = e;
+        }
+        __syncthreads();
+        if (t == 255) { s->carry = e; s->dcarry = dv[ENV_R - 1]; }           // read after the next chunk's first barrier
+        if (c0 + n > L - ysz) {                                                // workgroup-uniform
+            for (int i = t; i < n; i += 256) {
+                const int j = c0 + i - (L - ysz);
+                if (j < 0) continue;
+                const double ev = s->e[i];
+                const double g = ev > thresh ? exp10((thresh + (ev - thresh) / ratio - ev) / 20.0) : 1.0;
+                yb[j] = (float)((double)xb[c0 + i] * g);
+            }
+        }
+    }
+}
+// st_compressor (knobs_wc [B][3]) and the second launch of the feed's split form (d from the scratch, world knobs [B][4]): one workgroup per window
+__global__ void __launch_bounds__(256)
+compressor_env_kernel(const float* __restrict__ x, const float* __restrict__ db, const float* __restrict__ knobs_wc, const int kstride, const float sr,
+                      const int L, const int ysz, float* __restrict__ y)
+{
+    __shared__ EnvLds s;
+    const int b = blockIdx.x;
+    const float* kw = knobs_wc + (size_t)kstride * b;
+    env_compressor_window(x + (size_t)b * L, db ? db + (size_t)b * L : nullptr, y + (size_t)b * ysz, (double)kw[0], (double)kw[1],
+                          env_coef((double)kw[2], (double)sr), L, ysz, &s);
+}
+
 
 // ------------------------------------------------------------------------------ layer activations of one autoencoder (diagnostics)
 // nn_proc.py:77-126 with return_acts=True (what utils/viz.py:135 plots): the ten tensors the reference appends -- ELU outputs of the four
