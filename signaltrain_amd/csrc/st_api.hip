@@ -191,7 +191,7 @@ static int g_g16_dma = 0;    // bit 0 / bit 1: its analysis forward / synthesis 
 static int g_g16_abl = 0;    // TIMING ONLY (results invalid): analysis forward epilogue ablation, bit0 no mag/phs, bit1 no re/im, bit2 frame rows at 16-byte aligned (wrong) offsets (st_set_tuning(9680 + bits))
 static int g_g16_split = 0;  // k-slices of its weight-gradient GEMMs (0: by residency; st_set_tuning(9700 + n))
 static int g_nt128 = 1;      // fp32 synthesis frames / data-gradient GEMMs on the 128 x 128-tile NT kernel (st_gemm_tn.h); 0 = gemm_kernel<2, ...> (st_set_tuning(9950), diagnostics)
-static int g_tn128 = 1;      // weight-gradient GEMMs on the 128 x 128-tile kernel (st_gemm_tn.h) where it applies; 0 = gemm_kernel<3, ...> (st_set_tuning(9500), diagnostics)
+static int g_tn128 = 1;      // weight-gradient GEMMs on the 128 x 128-tile kernel (st_gemm_tn.h) where it applies; 0 = gemm_kernel<3, ...> (st_set_tuning(9500), diagnostics); 2 = its round-3 k-tile loop (st_set_tuning(9580))
 static int g_tn_bk = 32;     // its k-tile depth (st_set_tuning(9516 / 9532))
 static int g_tn_fm = 3;      // round 5: frame-major reduction order + per-tile-column row ranges (structural zeros skipped) in the 128 x 128 weight-gradient GEMMs: bit 0 synthesis
                              // (25 % of its reduction rows are cropped taps: 41.7 -> 37.0 us), bit 1 analysis (7.6 %: 113.8 -> 109.5 us)   (st_set_tuning(9540 + bits), diagnostics)
@@ -230,6 +230,7 @@ extern "C" int st_set_tuning(int bk)
 #endif
     if (bk >= 9600) { const int v = bk - 9600; if (v == 32 || v == 64) g_g16_bk = v; else g_g16 = v; return ST_OK; }
     if (bk >= 9560 && bk < 9576) { g_g16_crop = bk - 9560; return ST_OK; }
+    if (bk == 9580 || bk == 9581) { g_tn128 = bk == 9580 ? 2 : 1; return ST_OK; }      // 9580: the 128 x 128-tile weight-gradient kernel on its round-3 k-tile loop (A/B timing, bit-equality test); 9581: the pipelined loop (default)
     if (bk >= 9540 && bk < 9544) { g_tn_fm = bk - 9540; return ST_OK; }
     if (bk >= 9500) { const int v = bk - 9500; if (v == 16 || v == 32) g_tn_bk = v; else g_tn128 = v; return ST_OK; }
     if (bk >= 9400) { g_pl_bf16 = bk - 9400; return ST_OK; }
@@ -759,6 +760,9 @@ static TNFrameMajor tn_frame_major(const stg::TNOperand& ta, const stg::TNOperan
     f.trim = stg::frame_trim(live, B, H, Ntaps, pad, Ls);
     return f;
 }
+// g_tn128 == 2: the round-3 k-tile loop (st_set_tuning(9580)); otherwise the pipelined one (st_gemm_tn.h, round 7)
+#define ST_TN128(...) do { if (g_tn_bk == 16) { if (g_tn128 == 2) ST_TRY((stg::launch_tn128<16, false>(__VA_ARGS__))); else ST_TRY((stg::launch_tn128<16, true>(__VA_ARGS__))); } \
+                           else if (g_tn128 == 2) ST_TRY((stg::launch_tn128<32, false>(__VA_ARGS__))); else ST_TRY((stg::launch_tn128<32, true>(__VA_ARGS__))); } while (0)
 static int wgrad_tn128(const st_dims* d, const stg::TNOperand& ta, const stg::TNOperand& tb, const float* zeros, const stg::RowMap& map, int R,
                        float* ws, int ns, stm::NyqJob* nyq, void* stream, const stg::FrameTrim* trim)
 {
@@ -768,8 +772,7 @@ static int wgrad_tn128(const st_dims* d, const stg::TNOperand& ta, const stg::TN
     float* part = ws + (size_t)ns * KP * d->N;
     int P = 0;
     const unsigned c0 = (unsigned)(d->F - 1), c1 = (unsigned)(KP / 2 + d->F - 1);
-    if (g_tn_bk == 16) ST_TRY((stg::launch_tn128<16>(ta, tb, zeros, map, R, d->N, mh, (unsigned)(KP / 2), d->N, ws, d->N, (size_t)KP * d->N, ns, st_stream(stream), part, c0, c1, &P, trim)));
-    else ST_TRY((stg::launch_tn128<32>(ta, tb, zeros, map, R, d->N, mh, (unsigned)(KP / 2), d->N, ws, d->N, (size_t)KP * d->N, ns, st_stream(stream), part, c0, c1, &P, trim)));
+    ST_TN128(ta, tb, zeros, map, R, d->N, mh, (unsigned)(KP / 2), d->N, ws, d->N, (size_t)KP * d->N, ns, st_stream(stream), part, c0, c1, &P, trim);
     nyq->part = part; nyq->P = P; nyq->on = 1;
     return ST_OK;
 }
@@ -1718,10 +1721,8 @@ static int analysis_wgrad_half(const st_dims* d, const Layout& L, float* grads, 
         int P = 0;
         const TNFrameMajor fm = tn_frame_major(ta, tb, ma, d->B, d->H, N, N, d->L, (g_tn_fm & 2) != 0);
         // half 0 also forms the Nyquist partials of BOTH bases (its A origin is column 0: c0 = F - 1, c1 = KP / 2 + F - 1); half 1 has no Nyquist slice
-        if (g_tn_bk == 16) ST_TRY((stg::launch_tn128<16>(fm.a, fm.b, w.xp, fm.map, R, N / 2, mh, (unsigned)(KP / 2), N, w.wg + (size_t)m0 * N, N, (size_t)KP * N, ns, st_stream(stream),
-                                                          half ? nullptr : part, (unsigned)(F - 1), (unsigned)(KP / 2 + F - 1), &P, &fm.trim)));
-        else ST_TRY((stg::launch_tn128<32>(fm.a, fm.b, w.xp, fm.map, R, N / 2, mh, (unsigned)(KP / 2), N, w.wg + (size_t)m0 * N, N, (size_t)KP * N, ns, st_stream(stream),
-                                            half ? nullptr : part, (unsigned)(F - 1), (unsigned)(KP / 2 + F - 1), &P, &fm.trim)));
+        ST_TN128(fm.a, fm.b, w.xp, fm.map, R, N / 2, mh, (unsigned)(KP / 2), N, w.wg + (size_t)m0 * N, N, (size_t)KP * N, ns, st_stream(stream),
+                 half ? nullptr : part, (unsigned)(F - 1), (unsigned)(KP / 2 + F - 1), &P, &fm.trim);
         if (!half) { nyq_io->part = part; nyq_io->P = P; nyq_io->on = 1; }
     } else {
         ST_LAUNCHED("analysis_wgrad");

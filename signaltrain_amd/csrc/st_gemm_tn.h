@@ -22,6 +22,15 @@
 #pragma once
 #include "st_gemm.h"
 
+// Timing-only ablations of the round-3 k-tile loops of the two kernels below (results INVALID by construction): build a diagnostic library with
+// EXTRA=-DST_G128_ABLATE=<bits> (the Makefile never sets it) and select the TN kernel's round-3 loop with st_set_tuning(9580).  Compile-time for the reason given at
+// ST_GEMM_ABLATE (st_gemm.h).  bit 0: no barrier in the loop; bit 1: no fragment reads (the fragments are read once, before the loop); bit 2: no LDS
+// stores (the loaded registers are still waited for); bit 3: no global loads in the loop.  15 = the MFMAs and the loop's scalar code alone.
+#ifndef ST_G128_ABLATE
+#define ST_G128_ABLATE 0
+#endif
+#define ST_G128_KEEP4(v_) asm volatile("" :: "v"((v_)[0]), "v"((v_)[1]), "v"((v_)[2]), "v"((v_)[3]))
+
 namespace stg {
 
 struct TNJob {
@@ -91,8 +100,13 @@ __device__ __forceinline__ void nyq_partial(const TNJob& j, const int p)
     }
 }
 
-template <int BKT>
-__global__ void __launch_bounds__(256)
+// PIPE (round 7): the k-tile loop with the barrier and the first fragment reads off the wave's critical path (see the loop); false = the round-3 loop,
+// kept for A/B timing and the bit-equality test (st_set_tuning(9580)).  UNI (PIPE only, chosen on the host, see tn128_uniform): every k-tile lies inside ONE
+// outer index of the row map (frame-major order, inner count a multiple of BKT, k ranges that start on such a multiple), so (b, t) of a tile is wave-uniform.
+// Register budget: left to itself the compiler holds these kernels to 128 registers (four waves per SIMD, which the 64 KB of LDS rule out anyway) and, in
+// the pipelined loop, sends the staging registers through scratch; at most two waves per SIMD ever share one, so let it use 256.
+template <int BKT, bool PIPE = false, bool UNI = false>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2)))
 gemm_tn128_kernel(const TNJob j, float* __restrict__ out, const int ldo, const size_t slab, const int ksplit)
 {
     constexpr int TS = BKT * 128;                       // floats per operand tile
@@ -125,28 +139,30 @@ gemm_tn128_kernel(const TNJob j, float* __restrict__ out, const int ldo, const s
     const unsigned sa1 = 4u * j.SA1, sa2 = 4u * j.SA2, sb1 = 4u * j.SB1, sb2 = 4u * j.SB2;
     float4 ra[NP], rb[NP];
     auto ld = [&](const unsigned byte_off) { return *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(j.base) + byte_off); };
+    auto gload_pass = [&](const int kt, const int p) {
+        const int k = kt + kr + 8 * p;
+        const unsigned kc = (unsigned)(k < j.K ? k : j.K - 1);
+        const unsigned b = __umulhi(kc, j.magic);                                   // Tv >= 2 (host-checked): magic != 0
+        const unsigned t = (unsigned)j.t_lo + kc - __umul24(b, (unsigned)j.Tv);
+        const unsigned oa = __umul24(b, sa1) + __umul24(t, sa2) + la;
+        const unsigned ob = __umul24(b, sb1) + __umul24(t, sb2) + lb;
+        const unsigned live = (unsigned)((k - j.K) >> 31);       // all ones while k < K; a bit select (v_bfi), not a ?: the compiler turns into a branch
+        ra[p] = ld((oa & live) | (lz & ~live));                  // rows past the end of the reduction: the block of zeros (B's row is clamped: finite x 0)
+        rb[p] = ld(ob);
+    };
     auto gload = [&](const int kt) {
 #pragma unroll
-        for (int p = 0; p < NP; ++p) {
-            const int k = kt + kr + 8 * p;
-            const unsigned kc = (unsigned)(k < j.K ? k : j.K - 1);
-            const unsigned b = __umulhi(kc, j.magic);                                   // Tv >= 2 (host-checked): magic != 0
-            const unsigned t = (unsigned)j.t_lo + kc - __umul24(b, (unsigned)j.Tv);
-            const unsigned oa = __umul24(b, sa1) + __umul24(t, sa2) + la;
-            const unsigned ob = __umul24(b, sb1) + __umul24(t, sb2) + lb;
-            const unsigned live = (unsigned)((k - j.K) >> 31);       // all ones while k < K; a bit select (v_bfi), not a ?: the compiler turns into a branch
-            ra[p] = ld((oa & live) | (lz & ~live));                  // rows past the end of the reduction: the block of zeros (B's row is clamped: finite x 0)
-            rb[p] = ld(ob);
-        }
+        for (int p = 0; p < NP; ++p) gload_pass(kt, p);
     };
-    auto lstore = [&](const int buf) {
+    auto lstore_pass = [&](const int buf, const int p) {
         float* as = As + buf * TS + kr * 128 + 4 * c4;
         float* bs = Bs + buf * TS + kr * 128 + 4 * c4;
+        *reinterpret_cast<float4*>(as + p * 8 * 128) = ra[p];
+        *reinterpret_cast<float4*>(bs + p * 8 * 128) = rb[p];
+    };
+    auto lstore = [&](const int buf) {
 #pragma unroll
-        for (int p = 0; p < NP; ++p) {
-            *reinterpret_cast<float4*>(as + p * 8 * 128) = ra[p];
-            *reinterpret_cast<float4*>(bs + p * 8 * 128) = rb[p];
-        }
+        for (int p = 0; p < NP; ++p) lstore_pass(buf, p);
     };
 
     f32x16 acc[2][2];
@@ -158,17 +174,102 @@ gemm_tn128_kernel(const TNJob j, float* __restrict__ out, const int ldo, const s
             for (int i = 0; i < 16; ++i) acc[mi][nj][i] = 0.f;
 
     const int h = lane >> 5, l31 = lane & 31;
-    if (k_begin < k_end) {
+    if constexpr (PIPE) {
+        // Round 7.  At one wave per SIMD nothing else is resident to fill a hole, and the round-3 loop has two per k-tile: it ends with lstore / barrier
+        // and begins with fragment reads of the tile that barrier released (barrier skew, then an LDS round trip with four waves asking at once), and its
+        // eight ds_write_b128 issue after the last MFMA.  Here, with the same two LDS stages:
+        //   invariant at the top of tile i:  tile i complete in stage i & 1 AND its first fragment pair in registers; tile i + 1 in the staging registers
+        //   pairs 0 .. last - 1 (all but 8 MFMAs):  the stores of tile i + 1 into the other stage and the global loads of tile i + 2 among the first MFMAs,
+        //                                      the remaining fragment pairs of tile i one pair ahead as before;
+        //   ONE barrier, before the last pair's 8 MFMAs: every fragment of tile i has been read by then (its stage is next written in tile i + 1, behind
+        //   this barrier), the stores of tile i + 1 are complete, and the MFMAs that follow the barrier need nothing from it;
+        //   under those 8 MFMAs (512 cycles) the first fragment pair of tile i + 1 is read.
+        // No third stage is needed: a stage is written in the tile after its last read, and that read lies before the barrier in between.  The LDS request
+        // stays at 64 KB, so the Nyquist side workgroups still fit beside a GEMM workgroup.  The MFMAs per accumulator run in the same order: same bits.
+        // Tails: a k range of n tiles loads tiles min(i, n - 1) -- the last one is fetched (and stored, and its first fragments read) again instead of
+        // branching around the prefetch; n = 1 and n = 2 are the same code, an empty range skips the loop.
+        // Placement is by program order in chunks of one fragment pair (8 MFMAs) closed by a scheduling barrier: chunk p < NP holds the two stores of
+        // load pass p, chunk p + 1 the two loads that refill those registers (consumed 7 chunks = 56 MFMAs later).
+        constexpr int PAIRS = KS / 2;
+        static_assert(PAIRS % 2 == 0 && NP + 1 <= PAIRS - 1, "fragment buffers alternate by pair; stores and loads sit before the barrier");
+        const int ntiles = (k_end - k_begin + BKT - 1) / BKT;
+        if (ntiles > 0) {
+            const int k_last = k_begin + (ntiles - 1) * BKT;
+            unsigned ua[UNI ? NP : 1], ub[UNI ? NP : 1];
+            if constexpr (UNI) {
+#pragma unroll
+                for (int p = 0; p < NP; ++p) { ua[p] = la + (unsigned)(kr + 8 * p) * sa2; ub[p] = lb + (unsigned)(kr + 8 * p) * sb2; }
+            }
+            auto gl = [&](const int kt, const int p) {              // load pass p of the tile at kt
+                if constexpr (UNI) {
+                    // kt is workgroup-uniform and a multiple of BKT, which divides Tv: rows kt .. kt + BKT - 1 share b, their t is t0 + row (scalar ALU only)
+                    const unsigned b = __umulhi((unsigned)kt, j.magic), t0 = (unsigned)j.t_lo + (unsigned)kt - b * (unsigned)j.Tv;
+                    ra[p] = ld(b * sa1 + t0 * sa2 + ua[p]);
+                    rb[p] = ld(b * sb1 + t0 * sb2 + ub[p]);
+                } else gload_pass(kt, p);
+            };
+            const int a_off = h * 128 + wm * 64 + 2 * l31;          // k-step s reads row 2 s + h
+            const int b_off = h * 128 + wn * 64 + 2 * l31;
+            float2 fa[2][2], fb[2][2];
+            auto frag = [&](const int stage, const int pr, const int buf) {
+                const float* as = As + stage * TS + a_off;
+                const float* bs = Bs + stage * TS + b_off;
+#pragma unroll
+                for (int u = 0; u < 2; ++u) {
+                    fa[buf][u] = *reinterpret_cast<const float2*>(as + (2 * pr + u) * 256);
+                    fb[buf][u] = *reinterpret_cast<const float2*>(bs + (2 * pr + u) * 256);
+                }
+            };
+            auto mfma8 = [&](const int buf) {
+#pragma unroll
+                for (int u = 0; u < 2; ++u) {
+                    const float2 a = fa[buf][u], b = fb[buf][u];
+                    acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, b.x, acc[0][0], 0, 0, 0);
+                    acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, b.y, acc[0][1], 0, 0, 0);
+                    acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, b.x, acc[1][0], 0, 0, 0);
+                    acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, b.y, acc[1][1], 0, 0, 0);
+                }
+            };
+#pragma unroll
+            for (int p = 0; p < NP; ++p) gl(k_begin, p);
+            lstore(0);
+#pragma unroll
+            for (int p = 0; p < NP; ++p) gl(ntiles > 1 ? k_begin + BKT : k_begin, p);
+            __syncthreads();
+            frag(0, 0, 0);
+            int cur = 0;
+            for (int i = 0; i < ntiles; ++i) {
+                const int k2 = k_begin + (i + 2) * BKT, kn = k2 < k_last ? k2 : k_last;      // tile i + 2
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int pr = 0; pr < PAIRS - 1; ++pr) {
+                    frag(cur, pr + 1, (pr + 1) & 1);                // one pair ahead, double-buffered in registers
+                    if (pr < NP) lstore_pass(cur ^ 1, pr);          // tile i + 1 (the staging registers were loaded one tile ago)
+                    if (pr >= 1 && pr <= NP) gl(kn, pr - 1);
+                    mfma8(pr & 1);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+                __syncthreads();
+                frag(cur ^ 1, 0, 0);
+                mfma8(1);
+                __builtin_amdgcn_sched_barrier(0);
+                cur ^= 1;
+            }
+        }
+    } else if (k_begin < k_end) {
         gload(k_begin);
         lstore(0);
         __syncthreads();
         int cur = 0;
         const int a_off = h * 128 + wm * 64 + 2 * l31;          // k-step s reads row 2 s + h
         const int b_off = h * 128 + wn * 64 + 2 * l31;
+        float2 abl_f[4];                                        // ST_G128_ABLATE bit 1: stand-ins for the fragments, read once
+#pragma unroll
+        for (int u = 0; u < 4; ++u) abl_f[u] = (ST_G128_ABLATE & 2) ? *reinterpret_cast<const float2*>(As + a_off + u * 256) : make_float2(0.f, 0.f);
         for (int kt = k_begin; kt < k_end; kt += BKT) {
             // one basic block per k-tile (the last iteration re-loads its own tile instead of branching around the prefetch)
             const bool more = kt + BKT < k_end;
-            gload(more ? kt + BKT : kt);
+            if (!(ST_G128_ABLATE & 8)) gload(more ? kt + BKT : kt);
             __builtin_amdgcn_sched_barrier(0);
             const float* as = As + cur * TS + a_off;
             const float* bs = Bs + cur * TS + b_off;
@@ -179,6 +280,7 @@ gemm_tn128_kernel(const TNJob j, float* __restrict__ out, const int ldo, const s
             auto frag = [&](const int pr, const int buf) {
 #pragma unroll
                 for (int u = 0; u < 2; ++u) {
+                    if (ST_G128_ABLATE & 2) { fa[buf][u] = abl_f[(2 * buf + u) & 3]; fb[buf][u] = abl_f[(2 * buf + u + 1) & 3]; continue; }
                     fa[buf][u] = *reinterpret_cast<const float2*>(as + (2 * pr + u) * 256);
                     fb[buf][u] = *reinterpret_cast<const float2*>(bs + (2 * pr + u) * 256);
                 }
@@ -203,8 +305,12 @@ gemm_tn128_kernel(const TNJob j, float* __restrict__ out, const int ldo, const s
                 __builtin_amdgcn_sched_group_barrier(0x008, 8, 0);
             }
             __builtin_amdgcn_sched_barrier(0);
-            lstore(cur ^ 1);
-            __syncthreads();
+            if (!(ST_G128_ABLATE & 4)) lstore(cur ^ 1);
+            else {
+#pragma unroll
+                for (int p = 0; p < NP; ++p) { asm volatile("" :: "v"(ra[p].x), "v"(ra[p].y), "v"(ra[p].z), "v"(ra[p].w)); asm volatile("" :: "v"(rb[p].x), "v"(rb[p].y), "v"(rb[p].z), "v"(rb[p].w)); }
+            }
+            if (!(ST_G128_ABLATE & 1)) __syncthreads();
             cur ^= 1;
         }
     }
@@ -230,7 +336,16 @@ static inline bool tn128_fits(const TNOperand& A, const TNOperand& B, const floa
     const size_t lim = (size_t)1 << 30;
     return (size_t)(A.base - lo) + extentA < lim && (size_t)(B.base - lo) + extentB < lim && (size_t)(zeros - lo) + 128 < lim;
 }
-template <int BKT>
+// The wave-uniform address form (gemm_tn128_kernel UNI) applies when every k-tile lies inside one outer index of the row map: the inner count and the
+// reduction length are multiples of the tile depth (no row past K is ever touched), and so is the start of every k-slice (ksplit, and the trimmed
+// ranges fa * fB + z * per with per rounded to the tile depth).  True for both weight-gradient launches in the frame-major order when the batch is a
+// multiple of the tile depth; every other shape keeps the per-row split.
+static inline bool tn128_uniform(const RowMap& map, int K, int bkt, const FrameTrim* trim)
+{
+    if (map.Tv % bkt || K % bkt) return false;
+    return !(trim && trim->on) || trim->B % bkt == 0;
+}
+template <int BKT, bool PIPE = false>
 static inline int launch_tn128(const TNOperand& A, const TNOperand& B, const float* zeros, const RowMap& map, int K,
                                int M, int mh, unsigned mstride, int Nc, float* out, int ldo, size_t slab, int nsplit, hipStream_t s,
                                float* nyq_out = nullptr, unsigned nyq_c0 = 0, unsigned nyq_c1 = 0, int* nyq_P = nullptr, const FrameTrim* trim = nullptr)
@@ -245,12 +360,15 @@ static inline int launch_tn128(const TNOperand& A, const TNOperand& B, const flo
     int ksplit = K;
     if (nsplit > 1) ksplit = st_round_up((K + nsplit - 1) / nsplit, BKT);
     constexpr size_t lds = (size_t)4 * BKT * 128 * sizeof(float);
-    if (lds > 65536) { const int rc = ::ensure_dyn_lds((const void*)gemm_tn128_kernel<BKT>, "gemm_tn128_kernel"); if (rc) return rc; }
+    static_assert(lds <= 65536, "the Nyquist side workgroups share a CU with a GEMM workgroup: 2 x 64 KB of the 160");
     const int nz = nsplit > 1 ? nsplit : 1, tiles = (Nc / 128) * (M / 128);
     j.nsplit = nz; j.Nc = Nc; j.nyq_out = nyq_out; j.nyq_c0 = nyq_c0; j.nyq_c1 = nyq_c1;
     j.nyq_P = tiles < 64 ? tiles : 64; { const int W = K / 8 > 0 ? K / 8 : 1; if (j.nyq_P > W) j.nyq_P = W; }      // partials of >= 8 reduction rows
     if (nyq_P) *nyq_P = j.nyq_P;
-    hipLaunchKernelGGL((gemm_tn128_kernel<BKT>), dim3(Nc / 128, M / 128, nz + (nyq_out ? 1 : 0)), dim3(256), lds, s, j, out, ldo, slab, ksplit);
+    const dim3 grid(Nc / 128, M / 128, nz + (nyq_out ? 1 : 0));
+    if (!PIPE) hipLaunchKernelGGL((gemm_tn128_kernel<BKT>), grid, dim3(256), lds, s, j, out, ldo, slab, ksplit);
+    else if (tn128_uniform(map, K, BKT, trim)) hipLaunchKernelGGL((gemm_tn128_kernel<BKT, PIPE, PIPE>), grid, dim3(256), lds, s, j, out, ldo, slab, ksplit);
+    else hipLaunchKernelGGL((gemm_tn128_kernel<BKT, PIPE, false>), grid, dim3(256), lds, s, j, out, ldo, slab, ksplit);
     return 0;
 }
 
@@ -364,6 +482,9 @@ __device__ __forceinline__ void nt128_nyquist(const NTRows& ra, const NTRows& rb
     }
 }
 
+// Round 7: the pipelined k-tile loop of gemm_tn128_kernel was built for this kernel as well (barrier in mid-tile, the next tile's first fragment half read
+// under the last 32 MFMAs) and measured equal (33.98 against 33.54 us per launch at B = 256): the ablations put this kernel's exposed time in its global
+// loads (2.2 of 2.5 us per launch), not in its barrier or LDS traffic.  Removed; the loop below is the round-3 / round-5 one.
 __global__ void __launch_bounds__(256)
 gemm_nt128_kernel(const NTRows ra, const NTRows rb, const StoreSlab epi, const NTWork wk)
 {
@@ -421,9 +542,12 @@ gemm_nt128_kernel(const NTRows ra, const NTRows rb, const StoreSlab epi, const N
         int cur = 0;
         const int h = lane >> 5, l31 = lane & 31;
         const int a_off = (wm * 64 + l31) * LD + 16 * h, b_off = (wn * 64 + l31) * LD + 16 * h;
+        f32x4 abl_f[4];                                        // ST_G128_ABLATE bit 1: stand-ins for the fragments, read once
+#pragma unroll
+        for (int u = 0; u < 4; ++u) abl_f[u] = (ST_G128_ABLATE & 2) ? *reinterpret_cast<const f32x4*>(As + a_off + 4 * u) : f32x4{0.f, 0.f, 0.f, 0.f};
         for (int kt = k_begin; kt < k_end; kt += BKT) {
             const bool more = kt + BKT < k_end;
-            gload(more ? kt + BKT : kt);
+            if (!(ST_G128_ABLATE & 8)) gload(more ? kt + BKT : kt);
             __builtin_amdgcn_sched_barrier(0);
             const float* as = As + cur * TS + a_off;
             const float* bs = Bs + cur * TS + b_off;
@@ -435,6 +559,7 @@ gemm_nt128_kernel(const NTRows ra, const NTRows rb, const StoreSlab epi, const N
                 for (int x = 0; x < 2; ++x)
 #pragma unroll
                     for (int q = 0; q < 2; ++q) {
+                        if (ST_G128_ABLATE & 2) { fa[hf][x][q] = abl_f[(2 * x + q) & 3]; fb[hf][x][q] = abl_f[(2 * x + q + 1) & 3]; continue; }
                         fa[hf][x][q] = *reinterpret_cast<const f32x4*>(as + x * 32 * LD + 8 * hf + 4 * q);
                         fb[hf][x][q] = *reinterpret_cast<const f32x4*>(bs + x * 32 * LD + 8 * hf + 4 * q);
                     }
@@ -451,7 +576,11 @@ gemm_nt128_kernel(const NTRows ra, const NTRows rb, const StoreSlab epi, const N
                         acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
                         acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
                     }
-            lstore(cur ^ 1);
+            if (!(ST_G128_ABLATE & 4)) lstore(cur ^ 1);
+            else {
+#pragma unroll
+                for (int p = 0; p < NP; ++p) { ST_G128_KEEP4(va[p]); ST_G128_KEEP4(vb[p]); }
+            }
             // one wave per SIMD (see launch_nt128): nothing else hides LDS traffic, so it is placed by hand --
             // 8 reads | 32 MFMAs with the second half's 8 reads between them | 16 MFMAs | 16 MFMAs with the next tile's 8 ds_write_b128 between them
             // (the global loads behind those writes were issued ~48 MFMAs = 3000 cycles earlier)
@@ -462,7 +591,7 @@ gemm_nt128_kernel(const NTRows ra, const NTRows rb, const StoreSlab epi, const N
 #pragma unroll
             for (int i = 0; i < 8; ++i) { __builtin_amdgcn_sched_group_barrier(0x008, 2, 0); __builtin_amdgcn_sched_group_barrier(0x200, 1, 0); }
             __builtin_amdgcn_sched_barrier(0);
-            __syncthreads();
+            if (!(ST_G128_ABLATE & 1)) __syncthreads();
             cur ^= 1;
         }
     }
