@@ -254,6 +254,20 @@ int st_loss_backward(const st_dims* d, const float* params, float* grads, const 
                      const float* y_true, float* y_hat, float* mag, float* mag_hat, void* ws,
                      float* scalars, void* stream);
 
+/* One validation batch of train.py:28-80 on the device: forward, calc_loss with scale_by_freq (loss_functions.py:26-36) and mae
+ * (loss_functions.py:19-20).  The forward is the one st_train_step takes at this st_dims.prec (the 16-bit levels run the GEMMs on pre-rounded 16-bit
+ * operands, which st_model_fwd does not); nothing is kept for a backward -- the saved state of `ws` is gone afterwards -- no gradient is written, no
+ * mag / mag_hat copy is made, and there is no host synchronisation and no allocation.  st_dims.loss_scale and clip_all are ignored: the reported
+ * values never carry the loss scale.  y_hat[B,y] may be NULL; knobs may be NULL for K == 0.
+ * acc: 8 doubles on the device, updated by the last kernel of the call:
+ *   [0] running average beta * acc[0] + (1 - beta) * loss, formed in double as train.py:33 forms vl_avg (the caller seeds it: train.py carries
+ *       vl_avg from epoch to epoch)                        [1] this batch's loss        [2] its mean log-cosh      [3] its L1 term
+ *   [4] this batch's MAE (train.py:34 logs the last one)   [5] batches accumulated      [6], [7] running sums of loss and MAE
+ * The caller resets by writing acc.  [1..3] are formed exactly as st_finalize_scalars forms scalars[0..2]; the MAE partials (one per 256 samples, by the
+ * summation tree of st_ola_loss's loss partials, bits independent of pointer alignment) live in the workspace's d syn area: st_workspace_bytes is unchanged. */
+int st_eval_step(const st_dims* d, const float* params, const float* x, const float* knobs, const float* y_true,
+                 float* y_hat /* may be NULL */, void* ws, double* acc /* device, 8 doubles */, double beta, void* stream);
+
 /* Data-parallel split of st_loss_backward.  After p1 the gradients of the synthesis bases and both
  * autoencoders (grads[offs[2]..end)) are final: all-reduce them while p2 computes the analysis
  * weight gradient (rows [0,F) of tensors 0 and 1) and the loss scalars. */

@@ -19,6 +19,8 @@ if __name__ == "__main__":
                    "(one process per GPU); checked against WORLD_SIZE")
     p.add_argument('--device-feed', action='store_true', default=True, help="(default) generate every training minibatch on the GPU (st_synth_effect) and keep the validation set in HBM")
     p.add_argument('--host-feed', dest='device_feed', action='store_false', help="the reference's feed instead: a torch DataLoader with 10 CPU workers over the Dataset items")
+    p.add_argument('--device-eval', action='store_true', help="run the per-epoch validation pass on the device (st_eval_step: the training step's forward at --dtype, "
+                   "loss and MAE accumulated on the GPU, one read per epoch) instead of the host-side pass")
     p.add_argument('--resume-optimizer', action='store_true', help="restore Adam's moments (and, if the checkpoint belongs to this schedule, the position in the run) from --checkpoint")
     p.add_argument('-b', '--batch', type=int, help="batch size (per GPU); the reference's default.  On MI355X multiples of 256 windows (8192-sample window) fill the tile rounds of the analysis "
                                                         "forward: 379 k windows/s at 200, 418-426 k at 256, 477 k at 512 in fp32 (DESIGN.md section 5)", default=200)
@@ -64,6 +66,6 @@ if __name__ == "__main__":
     train.train(epochs=args.epochs, n_data_points=args.num, batch_size=args.batch, device=torch.device("cuda", local),
                 effect=effect, datapath=(args.path if args.effect == 'files' else None), sr=args.sr, scale_factor=args.scale, shrink_factor=args.shrink, apex_opt=args.apex,
                 target_type=args.target, lr_max=args.lrmax, in_checkpointname=args.checkpoint, compand=args.compand,
-                compute_dtype=args.dtype, device_feed=args.device_feed, resume_optimizer=args.resume_optimizer)
+                compute_dtype=args.dtype, device_feed=args.device_feed, resume_optimizer=args.resume_optimizer, device_eval=args.device_eval)
     if dist.is_initialized():
         dist.destroy_process_group()

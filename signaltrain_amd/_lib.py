@@ -98,6 +98,7 @@ SIGNATURES = {
     "st_model_bwd": (_i, [_D, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     "st_model_knob_grad": (_i, [_D, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     "st_loss_backward": (_i, [_D, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "st_eval_step": (_i, [_D, _p, _p, _p, _p, _p, _p, _p, C.c_double, _p]),
     "st_loss_backward_p1": (_i, [_D, _p, _p, _p, _p, _p, _p, _p]),
     "st_loss_backward_p2": (_i, [_D, _p, _p, _p, _p, _p]),
     "st_loss_backward_p2_staged": (_i, [_D, _p, _p, _p, _p, _p, _p]),

@@ -669,9 +669,13 @@ extern "C" int st_nt128_worklist(const st_dims* d, int which, int ncus, unsigned
     return wk.n;
 }
 
+// with_mae (the validation pass, st_eval_step): the kernels' MAE instantiations -- loss_partial then has room for a second array of st_ola_loss_partials() floats, the
+// |y - y_hat| partials, at stm::mae_partial_offset() -- and no d syn is written
 static int ola_loss_impl(const st_dims* d, const float* frs, const float* x, const float* y_true,
-                         float* y_hat, float* dsyn, int dsyn_pad, float* loss_partial, void* stream, unsigned short* dsyn16 = nullptr)
+                         float* y_hat, float* dsyn, int dsyn_pad, float* loss_partial, void* stream, unsigned short* dsyn16 = nullptr,
+                         bool with_mae = false)
 {
+    if (with_mae) ST_REQ(y_true && loss_partial && !dsyn, "ola_loss: the MAE partials come with a target and without d syn");
     const float inv = loss_scale_of(d) / ((float)d->B * (float)d->y);     // d loss / d y_hat, times the loss scale (train.py:134-135)
     {   // four samples per thread (round 5) where the geometry and the pointers allow 16-byte accesses: always inside the fused step
         const int ns = st_synth_frame_slabs(d), nslot = (d->y + 255) / 256;
@@ -682,16 +686,19 @@ static int ola_loss_impl(const st_dims* d, const float* frs, const float* x, con
             const dim3 grid((d->y / 4 + 255) / 256, d->B);
             const size_t slab = (size_t)d->B * d->OT * d->N;
             unsigned short* d16 = dsyn ? dsyn16 : nullptr; const int ht = dsyn16 ? gemm_ht(d->prec) : 0;
-#define ST_OLA4(NS_) hipLaunchKernelGGL((stm::ola_loss4_kernel<NS_>), grid, dim3(256), 0, st_stream(stream), frs, x, y_true, y_hat, dsyn, loss_partial, d->L, d->N, d->H, d->OT, d->y, inv, slab, dsyn_pad, nslot, d16, ht)
-            if (ns == 3) ST_OLA4(3); else if (ns == 2) ST_OLA4(2); else ST_OLA4(1);
+#define ST_OLA4(NS_, MAE_) hipLaunchKernelGGL((stm::ola_loss4_kernel<NS_, MAE_>), grid, dim3(256), 0, st_stream(stream), frs, x, y_true, y_hat, dsyn, loss_partial, d->L, d->N, d->H, d->OT, d->y, inv, slab, dsyn_pad, nslot, d16, ht)
+            if (with_mae) { if (ns == 3) ST_OLA4(3, true); else if (ns == 2) ST_OLA4(2, true); else ST_OLA4(1, true); }
+            else if (ns == 3) ST_OLA4(3, false); else if (ns == 2) ST_OLA4(2, false); else ST_OLA4(1, false);
 #undef ST_OLA4
             ST_LAUNCHED("ola_loss");
             return ST_OK;
         }
     }
-    hipLaunchKernelGGL(stm::ola_loss_kernel, dim3((d->y + 255) / 256, d->B), dim3(256), 0, st_stream(stream),
-                       frs, x, y_true, y_hat, dsyn, loss_partial, d->L, d->N, d->H, d->OT, d->y, inv,
-                       st_synth_frame_slabs(d), (size_t)d->B * d->OT * d->N, dsyn_pad, dsyn ? dsyn16 : nullptr, dsyn16 ? gemm_ht(d->prec) : 0);
+#define ST_OLA1(MAE_) hipLaunchKernelGGL(stm::ola_loss_kernel<MAE_>, dim3((d->y + 255) / 256, d->B), dim3(256), 0, st_stream(stream), \
+                       frs, x, y_true, y_hat, dsyn, loss_partial, d->L, d->N, d->H, d->OT, d->y, inv, \
+                       st_synth_frame_slabs(d), (size_t)d->B * d->OT * d->N, dsyn_pad, dsyn ? dsyn16 : nullptr, dsyn16 ? gemm_ht(d->prec) : 0)
+    if (with_mae) ST_OLA1(true); else ST_OLA1(false);
+#undef ST_OLA1
     ST_LAUNCHED("ola_loss");
     return ST_OK;
 }
@@ -1528,7 +1535,7 @@ static int wgrad16(const st_dims* d, const unsigned short* A, unsigned SA1, cons
 
 // ------------------------------------------------------------------------------ fused entry points
 static int forward_impl(const st_dims* d, const Layout& L, const float* params, const float* x, const float* knobs,
-                        const float* y_true, float* y_hat, float* mag, float* mag_hat, WS& w, bool save, void* stream)
+                        const float* y_true, float* y_hat, float* mag, float* mag_hat, WS& w, bool save, void* stream, float* eval_p = nullptr)
 {
     const float* Wr = params + L.offs[0]; const float* Wi = params + L.offs[1];
     const float* Sr = params + L.offs[2]; const float* Si = params + L.offs[3];
@@ -1589,7 +1596,7 @@ static int forward_impl(const st_dims* d, const Layout& L, const float* params, 
     if (planes) ST_TRY(synthesis_frames_planes(d, w, stream)); else
     ST_TRY(synthesis_frames_impl(d, w.AA, w.Sfold, w.SfoldT, w.frs, stream));
     ST_TRY(ola_loss_impl(d, w.frs, x, y_true, y_hat ? y_hat : w.y_hat, (save && y_true) ? w.dsyn : nullptr, d->N,
-                         y_true ? w.loss_p : nullptr, stream, w.g16 ? w.dsyn16 : nullptr));
+                         eval_p ? eval_p : y_true ? w.loss_p : nullptr, stream, w.g16 ? w.dsyn16 : nullptr, eval_p != nullptr));      // eval_p: loss + MAE partials (st_eval_step)
     const size_t nm = (size_t)d->B * d->T * d->F * sizeof(float), nh = (size_t)d->B * d->OT * d->F * sizeof(float);
     if (mag && hipMemcpyAsync(mag, w.mag, nm, hipMemcpyDeviceToDevice, st_stream(stream)) != hipSuccess) return st_fail(ST_ERR_LAUNCH, "copy mag");
     if (mag_hat && hipMemcpyAsync(mag_hat, w.mag_hat, nh, hipMemcpyDeviceToDevice, st_stream(stream)) != hipSuccess) return st_fail(ST_ERR_LAUNCH, "copy mag_hat");
@@ -1817,6 +1824,27 @@ extern "C" int st_loss_backward(const st_dims* d, const float* params, float* gr
     // grads carry the loss scale (if any); the published norm is that of the unscaled gradient
     ST_TRY(st_finalize_scalars(d, w.loss_p, w.reg_p, w.norm_a, w.norm_s, 1.0f / loss_scale_of(d), scalars, stream));
     return ST_OK;
+}
+
+// One validation batch of train.py:28-42: the forward of the training step at this st_dims.prec (16-bit levels: the pre-rounded operand GEMMs), nothing kept
+// for a backward, the log-cosh / MAE / L1 partials and one finalize that updates the caller's accumulator on the device.  The log-cosh and MAE partials
+// (2 * st_ola_loss_partials floats) take the place of d syn, which a forward without a backward never writes: the workspace does not grow.
+extern "C" int st_eval_step(const st_dims* d, const float* params, const float* x, const float* knobs, const float* y_true,
+                            float* y_hat, void* ws, double* acc, double beta, void* stream)
+{
+    Layout L; ST_TRY(make_layout(d, &L));
+    ST_REQ(params, "st_eval_step: null pointer (params)"); ST_REQ(x, "st_eval_step: null pointer (x)");
+    ST_REQ(knobs || d->K == 0, "st_eval_step: null pointer (knobs, K = %d)", d->K);
+    ST_REQ(y_true, "st_eval_step: null pointer (y_true)"); ST_REQ(ws, "st_eval_step: null pointer (ws)"); ST_REQ(acc, "st_eval_step: null pointer (acc)");
+    if (!knobs) knobs = params;
+    WS w; carve(d, ws, &w);
+    w.g16 = use_g16(d);
+    prof_mark("begin", stream);
+    float* const eval_p = w.dsyn;      // two arrays of B * ceil(y / 256) partials (the second at stm::mae_partial_offset) out of B * (y + 2N) floats
+    ST_TRY(forward_impl(d, L, params, x, knobs, y_true, y_hat, nullptr, nullptr, w, false, stream, eval_p));
+    const stm::FinArgs f = fin_args(d, eval_p, w.reg_p, nullptr, nullptr, 1.0f);
+    hipLaunchKernelGGL(stm::eval_finalize_kernel, dim3(1), dim3(256), 0, st_stream(stream), f, beta, acc);
+    ST_LAUNCHED("eval_finalize"); return ST_OK;
 }
 
 // Data-parallel split of st_loss_backward: after phase 1 the synthesis + autoencoder gradients

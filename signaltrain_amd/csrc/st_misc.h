@@ -60,6 +60,11 @@ zero_dead_frames_kernel(float* __restrict__ a0, float* __restrict__ a1, float* _
 // ---------------------------------------------------------------- overlap-add + residual + log-cosh
 // y_hat[b,j] = 2 * sum_t frs[b,t, N + j - H t] + x[b, L-y+j]     (cls_fe_dft.py:112-113, nn_proc.py:332,340)
 // loss partial = sum log cosh(y - y_hat) ; dsyn = 2 * (-tanh(y - y_hat)) * inv_count  (loss_functions.py:9-10)
+// MAE (the validation pass, st_eval_step): loss_partial has room for a second array of B * slots partials behind the first (at mae_partial_offset(): the next
+// multiple of four floats, so that both arrays take the same path through finalize_block's psum) and that one receives the sums of |y - y_hat|
+// (loss_functions.py:19-20), slot by slot through the tree of the log-cosh partials.  The training kernels are the MAE = false instantiations.
+__host__ __device__ __forceinline__ int mae_partial_offset(const int n_loss) { return (n_loss + 3) & ~3; }
+template <bool MAE = false>
 __global__ void __launch_bounds__(256)
 ola_loss_kernel(const float* __restrict__ frs, const float* __restrict__ x, const float* __restrict__ y_true,
                 float* __restrict__ y_hat, float* __restrict__ dsyn, float* __restrict__ loss_partial,
@@ -70,6 +75,7 @@ ola_loss_kernel(const float* __restrict__ frs, const float* __restrict__ x, cons
     const int b = blockIdx.y;
     const int j = blockIdx.x * 256 + threadIdx.x;
     float lc = 0.f;
+    [[maybe_unused]] float ma = 0.f;
     if (j < ysz) {
         int t0 = j / H + 1;                           // first frame with N + j - H t < N
         int t1 = (N + j) / H;                         // last frame with N + j - H t >= 0
@@ -89,16 +95,19 @@ ola_loss_kernel(const float* __restrict__ frs, const float* __restrict__ x, cons
         if (y_true) {
             const float dlt = y_true[(size_t)b * ysz + j] - out;
             const float a = fabsf(dlt);
+            if (MAE) ma = a;
             // log(cosh(d)) = log1p(2 sinh^2(d/2)): no cancellation for the small residuals of a trained model (the
             // a + log1p(e^-2a) - ln2 form loses ~1e-7 absolute per sample, i.e. 1e-3 of a 1e-4 mean); large |d|: overflow-free form
             if (a < 8.0f) { const float u = expm1f(0.5f * a); const float sh = 0.5f * (u + u / (u + 1.0f)); lc = log1pf(2.0f * sh * sh); }
             else lc = a + log1pf(__expf(-2.0f * a)) - 0.69314718056f;
-            const float ds = -2.0f * tanhf(dlt) * inv_count;
-            if (dsyn16) dsyn16[(size_t)b * (ysz + 2 * dsyn_pad) + dsyn_pad + j] = st_to_h16(ds, ht);
-            else if (dsyn) dsyn[(size_t)b * (ysz + 2 * dsyn_pad) + dsyn_pad + j] = ds;   // dsyn_pad > 0: padded layout for the framed loaders
+            if (!MAE) {      // the MAE instantiation writes no d syn
+                const float ds = -2.0f * tanhf(dlt) * inv_count;
+                if (dsyn16) dsyn16[(size_t)b * (ysz + 2 * dsyn_pad) + dsyn_pad + j] = st_to_h16(ds, ht);
+                else if (dsyn) dsyn[(size_t)b * (ysz + 2 * dsyn_pad) + dsyn_pad + j] = ds;   // dsyn_pad > 0: padded layout for the framed loaders
+            }
         }
     }
-    if ((dsyn || dsyn16) && dsyn_pad > 0) {      // zero margins of the padded gradient signal (2*pad floats per window)
+    if (!MAE && (dsyn || dsyn16) && dsyn_pad > 0) {      // zero margins of the padded gradient signal (2*pad floats per window)
         const size_t ro = (size_t)b * (ysz + 2 * dsyn_pad);
         for (int m = blockIdx.x * 256 + threadIdx.x; m < 2 * dsyn_pad; m += gridDim.x * 256) {
             if (dsyn16) dsyn16[ro + (m < dsyn_pad ? m : ysz + m)] = 0;
@@ -115,6 +124,17 @@ ola_loss_kernel(const float* __restrict__ frs, const float* __restrict__ x, cons
         __syncthreads();
         if (threadIdx.x == 0) loss_partial[blockIdx.y * gridDim.x + blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);      // levels 5 and 6
     }
+    if (MAE) {               // the same tree over |y - y_hat|
+        __shared__ float redm[4];
+        const int lane = threadIdx.x & 63, g = lane & ~3;
+        const float a0 = __shfl(ma, g), a1 = __shfl(ma, g + 1), a2 = __shfl(ma, g + 2), a3 = __shfl(ma, g + 3);
+        float q = ((a0 + a1) + a2) + a3;
+#pragma unroll
+        for (int o = 4; o < 64; o <<= 1) q += __shfl_xor(q, o);
+        if (lane == 0) redm[threadIdx.x >> 6] = q;
+        __syncthreads();
+        if (threadIdx.x == 0) loss_partial[mae_partial_offset(gridDim.y * gridDim.x) + blockIdx.y * gridDim.x + blockIdx.x] = (redm[0] + redm[1]) + (redm[2] + redm[3]);
+    }
 }
 
 // Round 5: the same, FOUR output samples per thread.  H, N, y (and with them every frame offset N + j - H t) are multiples of 4 for the reference's geometries, so the
@@ -125,7 +145,7 @@ ola_loss_kernel(const float* __restrict__ frs, const float* __restrict__ x, cons
 // pointers' alignment selected): slot s = samples [256 s, 256 s + 256) of the window, summed by ONE tree in both kernels -- quads ((l0 + l1) + l2) + l3 in sample order, then the
 // balanced binary tree over the 64 quad sums by quad index (xor butterfly, offsets 1, 2, 4, ..., 32; a + b == b + a, so every lane holds the same bits).  Here a wave's 64 lanes
 // hold exactly the 64 quads of one slot; the scalar kernel gathers a quad from four lanes, runs levels 1-4 inside each wave and levels 5-6 over its four waves.
-template <int NS>
+template <int NS, bool MAE = false>
 __global__ void __launch_bounds__(256)
 ola_loss4_kernel(const float* __restrict__ frs, const float* __restrict__ x, const float* __restrict__ y_true,
                  float* __restrict__ y_hat, float* __restrict__ dsyn, float* __restrict__ loss_partial,
@@ -135,6 +155,7 @@ ola_loss4_kernel(const float* __restrict__ frs, const float* __restrict__ x, con
     const int b = blockIdx.y;
     const int j = 4 * (blockIdx.x * 256 + threadIdx.x);
     float lc = 0.f;
+    [[maybe_unused]] float ma = 0.f;
     if (j < ysz) {
         const int t0 = j / H + 1;                     // first frame with N + j - H t < N  (the same for j .. j + 3: H is a multiple of 4)
         int t1 = (N + j) / H;                         // last frame with N + j - H t >= 0
@@ -171,16 +192,17 @@ ola_loss4_kernel(const float* __restrict__ frs, const float* __restrict__ x, con
             if (a < 8.0f) { const float u = expm1f(0.5f * a); const float sh = 0.5f * (u + u / (u + 1.0f)); l1 = log1pf(2.0f * sh * sh); }
             else l1 = a + log1pf(__expf(-2.0f * a)) - 0.69314718056f;
             lc += y_true ? l1 : 0.f;
-            ds[q] = -2.0f * tanhf(dlt) * inv_count;
+            if (MAE) ma += y_true ? a : 0.f;      // ((a0 + a1) + a2) + a3 in sample order, like lc
+            if (!MAE) ds[q] = -2.0f * tanhf(dlt) * inv_count;      // the MAE instantiations write no d syn
         }
         if (y_hat) *reinterpret_cast<float4*>(y_hat + (size_t)b * ysz + j) = make_float4(out[0], out[1], out[2], out[3]);
-        if (y_true) {
+        if (!MAE && y_true) {
             const size_t o = (size_t)b * (ysz + 2 * dsyn_pad) + dsyn_pad + j;
             if (dsyn16) *reinterpret_cast<uint2*>(dsyn16 + o) = st_to_h16x4(make_float4(ds[0], ds[1], ds[2], ds[3]), ht);
             else if (dsyn) *reinterpret_cast<float4*>(dsyn + o) = make_float4(ds[0], ds[1], ds[2], ds[3]);
         }
     }
-    if ((dsyn || dsyn16) && dsyn_pad > 0) {      // zero margins of the padded gradient signal (2*pad floats per window)
+    if (!MAE && (dsyn || dsyn16) && dsyn_pad > 0) {      // zero margins of the padded gradient signal (2*pad floats per window)
         const size_t ro = (size_t)b * (ysz + 2 * dsyn_pad);
         for (int m = blockIdx.x * 256 + threadIdx.x; m < 2 * dsyn_pad; m += gridDim.x * 256) {
             if (dsyn16) dsyn16[ro + (m < dsyn_pad ? m : ysz + m)] = 0;
@@ -193,6 +215,13 @@ ola_loss4_kernel(const float* __restrict__ frs, const float* __restrict__ x, con
         for (int o = 1; o < 64; o <<= 1) q += __shfl_xor(q, o);
         const int slot = 4 * blockIdx.x + (threadIdx.x >> 6);
         if ((threadIdx.x & 63) == 0 && slot < nslot) loss_partial[blockIdx.y * nslot + slot] = q;
+    }
+    if (MAE) {               // the second array behind loss_partial: the MAE partials, same slots, same tree (see ola_loss_kernel)
+        float q = ma;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) q += __shfl_xor(q, o);
+        const int slot = 4 * blockIdx.x + (threadIdx.x >> 6);
+        if ((threadIdx.x & 63) == 0 && slot < nslot) loss_partial[mae_partial_offset(gridDim.y * nslot) + blockIdx.y * nslot + slot] = q;
     }
 }
 
@@ -702,6 +731,27 @@ finalize_kernel(const FinArgs f, float* __restrict__ scalars)
     if (threadIdx.x == 0) {
         if (f.loss_partial) { scalars[1] = lc; scalars[2] = rg; scalars[0] = lc + rg; }
         if (f.norm_a || f.norm_s || f.norm_e) { scalars[3] = nrm; scalars[4] = coef; }
+    }
+}
+
+// The validation pass (train.py:28-42), last kernel of st_eval_step.  One block: the loss terms exactly as finalize_kernel forms scalars[0..2] (same
+// partial-sum order), the MAE from its partials (the array behind the loss partials, ola_loss_kernel<MAE>) by that order, then the accumulator in double:
+// acc[0] = beta * acc[0] + (1 - beta) * loss with each product and the sum rounded on its own, as the host forms vl_avg (train.py:33), acc[1..4] = this batch's loss, mean log-cosh, L1 term, MAE,
+// acc[5] = batches so far, acc[6], acc[7] = running sums of loss and MAE.
+__global__ void __launch_bounds__(256)
+eval_finalize_kernel(const FinArgs f, const double beta, double* __restrict__ acc)
+{
+    __shared__ float red[4];
+    float lc, rg, nrm, ma, t0, t1;
+    finalize_block(f, true, red, lc, rg, nrm);
+    FinArgs g = f; g.loss_partial = f.loss_partial + mae_partial_offset(f.n_loss); g.reg_partial = nullptr;
+    finalize_block(g, true, red, ma, t0, t1);
+    if (threadIdx.x == 0) {
+#pragma clang fp contract(off)      // lc + rg as finalize_kernel rounds it (contracted with lc's own product the sum lands one ulp off), the average as the host rounds it
+        const double loss = (double)(lc + rg), mae = (double)ma;
+        acc[0] = beta * acc[0] + (1.0 - beta) * loss;
+        acc[1] = loss; acc[2] = (double)lc; acc[3] = (double)rg; acc[4] = mae;
+        acc[5] += 1.0; acc[6] += loss; acc[7] += mae;
     }
 }
 

@@ -112,6 +112,7 @@ class StepEngine:
         nbytes = max(workspace_bytes_upto(self.lib, dims, self.max_batch), int(self.lib.st_workspace_bytes(C.byref(dmax))))
         self.ws = torch.zeros(nbytes, dtype=torch.uint8, device=self.device)
         self.scalars = torch.zeros(8, dtype=torch.float32, device=self.device)
+        self.eval_acc = torch.zeros(8, dtype=torch.float64, device=self.device)      # st_eval_step's accumulator (eval_step / eval_reset / eval_read)
         self.stage = None            # packed live analysis gradient rows (data parallel, allocated on first use)
         self.named = self.layout.views(self.params)
         self.named_grads = self.layout.views(self.grads)
@@ -343,6 +344,29 @@ class StepEngine:
                    _lib.ptr(self.scalars), float(lr), float(betas[0]), float(betas[1]), float(eps),
                    int(self.step_count), self._stream())
         return self.scalars
+
+    # ---------------------------------------------------------------- validation on the device
+    EVAL_FIELDS = ("vl_avg", "loss", "logcosh", "l1_term", "mae", "batches", "loss_sum", "mae_sum")
+
+    def eval_step(self, x, knobs, y, beta=0.98, want_y_hat=False):
+        """One validation batch (train.py:28-42) as one C call: the forward of train_step at this compute_dtype, calc_loss with scale_by_freq and mae,
+        accumulated into self.eval_acc on the device (st_eval_step in include/signaltrain_hip.h).  No host sync; read with eval_read().  Overwrites the
+        workspace's saved-for-backward state (a pending autograd backward recomputes its forward); parameters, gradients, moments and scalars are untouched."""
+        d, x, knobs, y = self._prep(x, knobs, y)
+        y_hat = torch.empty(d.B, d.y, dtype=torch.float32, device=self.device) if want_y_hat else None
+        self.generation += 1
+        self._call("st_eval_step", C.byref(d), _lib.ptr(self.params), _lib.ptr(x), _lib.ptr(knobs), _lib.ptr(y), _lib.ptr(y_hat),
+                   _lib.ptr(self.ws), C.c_void_p(self.eval_acc.data_ptr()), float(beta), self._stream())
+        return y_hat
+
+    def eval_reset(self, vl_avg=0.0):
+        """Start a validation pass: the running average is seeded with `vl_avg` (train.py carries it from epoch to epoch), everything else is zero."""
+        self.eval_acc.zero_()
+        self.eval_acc[0] = float(vl_avg)
+
+    def eval_read(self):
+        """The eight accumulator values (EVAL_FIELDS order) as Python floats: ONE device->host sync."""
+        return self.eval_acc.tolist()
 
     # ---------------------------------------------------------------- the step as one HIP graph
     def graph_capture(self, batch, lr_table, betas=(0.9, 0.999), eps=1e-8):

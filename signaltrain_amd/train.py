@@ -19,22 +19,37 @@ from .dp import DataParallel
 
 def eval_status_save(model, engine, effect, epoch, epochs, lr, mom, device, dataloader_val, logfilename, first_time,
                      beta, vl_avg, out_checkpointname, parallel, optimizer, data_point, smoothed_loss, y_size, sr,
-                     status_every, plot_every=10, cp_every=25, scale_by_freq=None, is_main=True):
-    """train.py:28-80: validation pass, log files, checkpoint cadence."""
+                     status_every, plot_every=10, cp_every=25, scale_by_freq=None, is_main=True, device_eval=False):
+    """train.py:28-80: validation pass, log files, checkpoint cadence.  device_eval: the pass runs as one engine.eval_step per batch (forward of the training
+    step at the engine's arithmetic, loss, MAE and the running average on the device) and ONE read of the accumulator after the last batch; the progress line
+    is then printed once per epoch, from that read."""
     val_batch_num, val_mae = 0, float("nan")
-    for x_val, y_val, knobs_val in dataloader_val:
-        val_batch_num += 1
-        x_c, y_c, k_c = x_val.to(device), y_val.to(device).float(), knobs_val.to(device)
-        y_hat, mag_val, mag_val_hat = engine.forward(x_c, k_c)
-        if scale_by_freq is None or scale_by_freq.shape != mag_val_hat.shape:
-            F = mag_val_hat.shape[-1]
-            scale_by_freq = torch.exp((7. / F) * torch.arange(0., F, device=device)).expand_as(mag_val_hat).float()
-        loss_val = loss_functions.calc_loss(y_hat, y_c, mag_val_hat, scale_by_freq=scale_by_freq)
-        vl_avg = beta * vl_avg + (1 - beta) * loss_val.item()
-        val_mae = loss_functions.mae(y_hat, y_c).item()
-        if 0 == val_batch_num % status_every and is_main:
-            print(f"\repoch {epoch+1}/{epochs}, time: {time.time()-first_time:.2f}: lr={lr:.2e},mom={mom:.3f} data_point {data_point}: "
-                  f"loss: {smoothed_loss:.3e} val_loss: {vl_avg:.3e}   ", end="")
+    if device_eval:
+        for x_val, y_val, knobs_val in dataloader_val:
+            if val_batch_num == 0:
+                engine.eval_reset(vl_avg)
+            val_batch_num += 1
+            engine.eval_step(x_val.to(device), knobs_val.to(device), y_val.to(device).float(), beta=beta)
+        if val_batch_num:               # no validation batch: no call, vl_avg as it was, MAE nan (as the host path below)
+            acc = engine.eval_read()
+            vl_avg, val_mae = acc[0], acc[4]
+            if is_main:
+                print(f"\repoch {epoch+1}/{epochs}, time: {time.time()-first_time:.2f}: lr={lr:.2e},mom={mom:.3f} data_point {data_point}: "
+                      f"loss: {smoothed_loss:.3e} val_loss: {vl_avg:.3e}   ", end="")
+    else:
+        for x_val, y_val, knobs_val in dataloader_val:
+            val_batch_num += 1
+            x_c, y_c, k_c = x_val.to(device), y_val.to(device).float(), knobs_val.to(device)
+            y_hat, mag_val, mag_val_hat = engine.forward(x_c, k_c)
+            if scale_by_freq is None or scale_by_freq.shape != mag_val_hat.shape:
+                F = mag_val_hat.shape[-1]
+                scale_by_freq = torch.exp((7. / F) * torch.arange(0., F, device=device)).expand_as(mag_val_hat).float()
+            loss_val = loss_functions.calc_loss(y_hat, y_c, mag_val_hat, scale_by_freq=scale_by_freq)
+            vl_avg = beta * vl_avg + (1 - beta) * loss_val.item()
+            val_mae = loss_functions.mae(y_hat, y_c).item()
+            if 0 == val_batch_num % status_every and is_main:
+                print(f"\repoch {epoch+1}/{epochs}, time: {time.time()-first_time:.2f}: lr={lr:.2e},mom={mom:.3f} data_point {data_point}: "
+                      f"loss: {smoothed_loss:.3e} val_loss: {vl_avg:.3e}   ", end="")
     if is_main:
         with open(logfilename, "a") as f:
             f.write(f"{epoch+1} {vl_avg:.3e}\n")
@@ -50,14 +65,14 @@ def eval_status_save(model, engine, effect, epoch, epochs, lr, mom, device, data
 
 def train_loop(model, engine, effect, device, epochs, batch_size, lr_sched, mom_sched, dataloader, dataloader_val,
                y_size, logfilename, out_checkpointname, plot_every=10, cp_every=25, sr=44100, lr_max=1e-4,
-               start_epoch=0, start_iter=0, lr_resume=None):
+               start_epoch=0, start_iter=0, lr_resume=None, device_eval=False):
     """train.py:84-164.  start_epoch / start_iter / lr_resume: position restored from a checkpoint (epoch counter, optimizer
     step count = position in the 1-cycle table, the learning rate that sat in the optimizer) -- the reference restarts all
     three at zero on resume (train.py:229 TODO)."""
     dp = DataParallel(engine)
     try:
         return _train_loop(dp, model, engine, effect, device, epochs, batch_size, lr_sched, mom_sched, dataloader, dataloader_val,
-                           y_size, logfilename, out_checkpointname, plot_every, cp_every, sr, lr_max, start_epoch, start_iter, lr_resume)
+                           y_size, logfilename, out_checkpointname, plot_every, cp_every, sr, lr_max, start_epoch, start_iter, lr_resume, device_eval)
     finally:
         dp.close()          # the library-owned RCCL communicator, its stream and events (before the caller destroys the process group)
 
@@ -73,7 +88,7 @@ def seed_data_streams(rank):
 
 
 def _train_loop(dp, model, engine, effect, device, epochs, batch_size, lr_sched, mom_sched, dataloader, dataloader_val,
-                y_size, logfilename, out_checkpointname, plot_every, cp_every, sr, lr_max, start_epoch, start_iter, lr_resume):
+                y_size, logfilename, out_checkpointname, plot_every, cp_every, sr, lr_max, start_epoch, start_iter, lr_resume, device_eval=False):
     dp.broadcast_parameters()
     is_main = (not dist.is_initialized()) or dist.get_rank() == 0
     iter_count, batch_num, status_every = int(start_iter), 0, 10
@@ -148,7 +163,7 @@ def _train_loop(dp, model, engine, effect, device, epochs, batch_size, lr_sched,
         t_train += t_last
         vl_avg = eval_status_save(model, engine, effect, epoch, epochs, lr_in_optimizer, 0.0, device, dataloader_val, logfilename,
                                   first_time, beta, vl_avg, out_checkpointname, False, opt, data_point, smoothed_loss, y_size, sr,
-                                  status_every, is_main=is_main)
+                                  status_every, is_main=is_main, device_eval=device_eval)
     if is_main:
         world = dist.get_world_size() if dist.is_initialized() else 1
         per_epoch = windows // max(epochs - int(start_epoch), 1)
@@ -160,7 +175,7 @@ def _train_loop(dp, model, engine, effect, device, epochs, batch_size, lr_sched,
 def train(effect=None, epochs=100, n_data_points=200000, batch_size=20, device=None, plot_every=10, cp_every=25, sr=44100,
           datapath=None, scale_factor=1, shrink_factor=4, apex_opt="O0", target_type="stream", lr_max=1e-4,
           in_checkpointname='modelcheckpoint.tar', compand=False, num_workers=10, device_feed=True, compute_dtype=None,
-          resume_optimizer=False):
+          resume_optimizer=False, device_eval=False):
     """train.py:167-278.  datapath: directory with Train/ and Val/ wav pairs (datasets.AudioFileDataSet, the reference's
     file feed, e.g. the LA2A set of BASELINE configs[3]; pass effect=audio.FileEffect(datapath)); compand: mu-law compand that dataset's audio (datasets.py:218-220).
     apex_opt: "O0" = fp32 (the parity path); "O1" / "O2" / "O3" = the reference's Apex mixed precision (train.py:254-255),
@@ -172,7 +187,9 @@ def train(effect=None, epochs=100, n_data_points=200000, batch_size=20, device=N
     below the step rate; printed when chosen); resume_optimizer: False (default, the reference's behaviour: train `epochs`
     more epochs from the loaded weights with a fresh optimizer and schedule -- its fine-tune workflow); True restores Adam's moments
     from the checkpoint (which the reference saves but never reads back, train.py:229) and, if the checkpoint belongs to THIS schedule
-    (its epoch counter is below `epochs` and its step count lies inside the 1-cycle table), also the position in the run."""
+    (its epoch counter is below `epochs` and its step count lies inside the 1-cycle table), also the position in the run;
+    device_eval: False (default) = the per-epoch validation pass on the host side (engine.forward + torch loss, two host syncs per batch); True = on the
+    device (engine.eval_step: the training step's forward at this compute_dtype, one accumulator read per epoch)."""
     if compute_dtype is None:
         compute_dtype = "f32" if str(apex_opt).upper() in ("O0", "NONE", "") else "f16_all"
     effect = audio.Compressor_4c() if effect is None else effect
@@ -268,5 +285,5 @@ def train(effect=None, epochs=100, n_data_points=200000, batch_size=20, device=N
     open(logfilename, "a").close()
     train_loop(model, engine, effect, device, epochs, batch_size, lr_sched, mom_sched, dataloader, dataloader_val,
                out_chunk_size, logfilename, "modelcheckpoint.tar", sr=sr, lr_max=lr_max,
-               start_epoch=start_epoch, start_iter=start_iter, lr_resume=lr_resume)
+               start_epoch=start_epoch, start_iter=start_iter, lr_resume=lr_resume, device_eval=device_eval)
     return model
