@@ -434,8 +434,16 @@ int st_model_knob_grad(const st_dims* d, const float* params, float* grads_scrat
  * Synthesis.forward (:174-179) = ConvTranspose1d(C -> 1, kernel KW, stride hop) with `crop` samples cut from both ends.
  * W is the [C][1][KW] Conv weight seen as [C][KW].  T = st_fe_frames(L, KW, hop, pad).  The *_bwd entries are the
  * autograd of the forward ones (weight, bias and input gradients).  ws: st_fe_ws_floats() floats (for synthesis pass
- * L = the output length + 2*crop - 2*pad equivalent, i.e. call it with the analysis geometry of the same model). */
+ * L = the output length (T - 1) * hop + KW - 2 * crop and pad = crop, i.e. call it with the analysis geometry of the same model).
+ * Every entry refuses a shape st_fe_supported() refuses with ST_ERR_ARG and a message that names the limit, before any launch; st_fe_ws_floats()
+ * then returns 0. */
 int st_fe_frames(int L, int KW, int hop, int pad);
+/* Host only (no device work): 1 if the front-end kernels may run this shape, else 0.  The rules: positive sizes, KW%16, C%16, hop%4, pad%4, L%4 and at least
+ * one frame (KW <= L + 2 pad); rows B * T and samples L + 2 pad + 2 KW below 2^24 (24-bit multiplies); B * L, B * (L + 2 pad + 2 KW), B * T * KW, B * T * C
+ * and C * KW below 2^30 elements (32-bit element offsets); and (B * T - 1) * T < 2^32, up to where the kernels' division of a row index r < B * T by T through
+ * a multiply-high with floor(2^32 / T) + 1 is exact (the same rule st_fm_div_exact states for the frame-major order).  The synthesis entries apply it with
+ * L = (T - 1) * hop + KW - 2 * crop and pad = crop. */
+int st_fe_supported(int B, int L, int C, int KW, int hop, int pad);
 size_t st_fe_ws_floats(int B, int L, int C, int KW, int hop, int pad);
 int st_fe_analysis_fwd(const float* x, int B, int L, const float* W, const float* bias, int C, int KW, int hop, int pad,
                        float* out, void* stream);

@@ -92,7 +92,7 @@ class _SynthesisFn(torch.autograd.Function):
         B, T, Cn = xf.shape; KW = W.shape[2]
         n = (T - 1) * hop + KW - 2 * crop
         g = g_wave.contiguous().float().reshape(B, n)
-        ws = torch.empty(lib.st_fe_ws_floats(B, n + 2 * crop, Cn, KW, hop, crop), device=xf.device)
+        ws = torch.empty(lib.st_fe_ws_floats(B, n, Cn, KW, hop, crop), device=xf.device)
         gW = torch.empty_like(W)
         gx = torch.empty_like(xf) if ctx.needs_input_grad[0] else None
         _lib.check(lib.st_fe_synthesis_bwd(_lib.ptr(xf), B, T, _lib.ptr(W), Cn, KW, hop, crop, _lib.ptr(g), _lib.ptr(ws), _lib.ptr(gW),

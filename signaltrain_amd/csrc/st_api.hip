@@ -119,6 +119,9 @@ static int check_dims(const st_dims* d)
     // multiplies: rows (B*T) < 2^24, the largest per-batch operands (B*T x KP spectra, B x (L + 2N) padded signals) < 2^30 elements
     ST_REQ((size_t)d->B * d->T < ((size_t)1 << 24) && (size_t)d->B * d->T * st_kp_of(d->F) < ((size_t)1 << 30) &&
            (size_t)d->B * ((size_t)d->L + 2 * (size_t)d->N) < ((size_t)1 << 30), "batch too large for 32-bit element offsets (B=%d)", d->B);
+    // ... and split a compact row r < B*T into (window, frame) with a multiply-high by floor(2^32 / Tv) + 1, Tv <= T (st_gemm.h RowMap::split): exact while
+    // r * T < 2^32; the largest row decides (st_fe_supported has the same rule for the generic front end)
+    ST_REQ(((unsigned long long)d->B * d->T - 1) * (unsigned long long)d->T < (1ull << 32), "row split inexact: (B*T - 1)*T must stay below 2^32 (B=%d T=%d)", d->B, d->T);
     return ST_OK;
 }
 
@@ -2094,15 +2097,51 @@ extern "C" int st_synth_comp4c(unsigned seed, unsigned long long first_window, i
 // ------------------------------------------------------------------------------ generic learned-basis front end (a15)
 // cls_fe_dct_bases.Analysis / Synthesis: Conv1d(1 -> C, k = KW, stride = hop, padding = pad, bias) and
 // ConvTranspose1d(C -> 1, k = KW, stride = hop) + crop, forward and backward, on the same framed GEMM family.
-static int fe_check(int B, int L, int C, int KW, int hop, int pad)
+// The one host-side gate of the family: the limit a shape violates, by name, or NULL where the kernels may run it.  Everything in 64-bit host arithmetic.
+//  - rows: the loaders index rows and padded signals with 24-bit multiplies (__umul24): B * T and L + 2 pad + 2 KW stay below 2^24;
+//  - elements: ldg128 shifts a 32-bit ELEMENT offset left by 2 in 32 bits, so every operand addressed that way stays below 2^30 elements;
+//  - the row split: RowMap::split divides a compact row r < B * T by T with a multiply-high by floor(2^32 / T) + 1, exact while r * T < 2^32.  The quotient
+//    fails first at r = T - 1 (mod T), so the largest row B * T - 1 decides.  A wrong quotient is a frame index of -1: an address, not a rounding error.
+static const char* fe_limit(int B, int L, int C, int KW, int hop, int pad)
 {
-    ST_REQ(B > 0 && L > 0 && C > 0 && KW > 0 && hop > 0 && pad >= 0, "front end: non-positive dimension");
-    ST_REQ(KW % 16 == 0 && C % 16 == 0 && hop % 4 == 0 && pad % 4 == 0 && L % 4 == 0, "front end: KW%%16, C%%16, hop%%4, pad%%4, L%%4 required");
+    if (!(B > 0 && L > 0 && C > 0 && KW > 0 && hop > 0 && pad >= 0)) return "non-positive dimension";
+    if (!(KW % 16 == 0 && C % 16 == 0 && hop % 4 == 0 && pad % 4 == 0 && L % 4 == 0)) return "KW%16, C%16, hop%4, pad%4, L%4 required";
+    const long long span = (long long)L + 2ll * pad;
+    if (KW > span) return "window longer than the padded signal (no frame)";
+    const long long T = (span - KW) / hop + 1, R = (long long)B * T, wide = span + 2ll * KW;
+    const long long r24 = 1ll << 24, e30 = 1ll << 30;
+    if (R >= r24) return "B*T rows leave the 24-bit row index";
+    if (wide >= r24) return "L + 2 pad + 2 KW leaves the 24-bit sample index";
+    if ((long long)B * L >= e30) return "B*L leaves the 32-bit element offsets (2^30 elements)";
+    if ((long long)B * wide >= e30) return "B*(L + 2 pad + 2 KW) leaves the 32-bit element offsets (2^30 elements)";
+    if (R * KW >= e30) return "B*T*KW leaves the 32-bit element offsets (2^30 elements)";
+    if (R * C >= e30) return "B*T*C leaves the 32-bit element offsets (2^30 elements)";
+    if ((long long)C * KW >= e30) return "C*KW leaves the 32-bit element offsets (2^30 elements)";
+    if (!fm_div_exact((int)(R - 1), (int)T)) return "row split inexact: (B*T - 1)*T must stay below 2^32";
+    return nullptr;
+}
+extern "C" int st_fe_supported(int B, int L, int C, int KW, int hop, int pad) { return fe_limit(B, L, C, KW, hop, pad) ? 0 : 1; }
+static int fe_check(const char* who, int B, int L, int C, int KW, int hop, int pad)
+{
+    const char* why = fe_limit(B, L, C, KW, hop, pad);
+    ST_REQ(!why, "%s: %s (B=%d L=%d C=%d KW=%d hop=%d pad=%d)", who, why, B, L, C, KW, hop, pad);
     return ST_OK;
+}
+// the synthesis entries take (B, T, C, KW, hop, crop): the same gate at the analysis geometry of the same model, L = the output length and pad = crop
+// (st_fe_frames(len, KW, hop, crop) is T again)
+static int fe_check_synth(const char* who, int B, int T, int C, int KW, int hop, int crop, int* len)
+{
+    ST_REQ(B > 0 && T > 0 && C > 0 && KW > 0 && hop > 0 && crop >= 0, "%s: non-positive dimension", who);
+    const long long n = ((long long)T - 1) * hop + KW - 2ll * crop;
+    ST_REQ(n > 0, "%s: nothing left after the crop", who);
+    ST_REQ(n < (1ll << 24), "%s: output length leaves the 24-bit sample index", who);
+    *len = (int)n;
+    return fe_check(who, B, (int)n, C, KW, hop, crop);      // len % 4 is the gate's L % 4
 }
 extern "C" int st_fe_frames(int L, int KW, int hop, int pad) { return (L + 2 * pad - KW) / hop + 1; }
 extern "C" size_t st_fe_ws_floats(int B, int L, int C, int KW, int hop, int pad)
 {
+    if (!st_fe_supported(B, L, C, KW, hop, pad)) return 0;
     const int T = st_fe_frames(L, KW, hop, pad);
     const size_t R = (size_t)B * T;
     // frames [R][KW] + padded gradient signal [B][L + 2 KW] + split-K slabs of the weight gradient
@@ -2111,9 +2150,8 @@ extern "C" size_t st_fe_ws_floats(int B, int L, int C, int KW, int hop, int pad)
 extern "C" int st_fe_analysis_fwd(const float* x, int B, int L, const float* W, const float* bias, int C, int KW, int hop, int pad,
                                   float* out, void* stream)
 {
-    ST_TRY(fe_check(B, L, C, KW, hop, pad)); ST_REQ(x && W && out, "st_fe_analysis_fwd: null pointer");
+    ST_TRY(fe_check("st_fe_analysis_fwd", B, L, C, KW, hop, pad)); ST_REQ(x && W && out, "st_fe_analysis_fwd: null pointer");
     const int T = st_fe_frames(L, KW, hop, pad), R = B * T;
-    ST_REQ(T > 0, "st_fe_analysis_fwd: window longer than the padded signal");
     stg::FramedNT<false> al{x, L, hop, pad, R, KW, 1.0f, stg::all_frames(T)};
     stg::PlainNT bl{W, C, KW, KW, stg::all_frames(1)};
     stg::BiasStore ep{out, bias, R, C, C};
@@ -2134,10 +2172,9 @@ static int fe_frames_ola(const float* xft, int B, int T, const float* W, int C, 
 extern "C" int st_fe_synthesis_fwd(const float* xft, int B, int T, const float* W, int C, int KW, int hop, int crop,
                                    float* ws, float* out, void* stream)
 {
-    ST_REQ(xft && W && ws && out && B > 0 && T > 0, "st_fe_synthesis_fwd: bad arguments");
-    ST_REQ(KW % 16 == 0 && C % 16 == 0 && hop % 4 == 0 && crop % 4 == 0, "st_fe_synthesis_fwd: KW%%16, C%%16, hop%%4, crop%%4 required");
-    const int len = (T - 1) * hop + KW - 2 * crop;
-    ST_REQ(len > 0, "st_fe_synthesis_fwd: nothing left after the crop");
+    int len = 0;
+    ST_TRY(fe_check_synth("st_fe_synthesis_fwd", B, T, C, KW, hop, crop, &len));
+    ST_REQ(xft && W && ws && out, "st_fe_synthesis_fwd: null pointer");
     ST_TRY(fe_frames_ola(xft, B, T, W, C, KW, hop, crop, len, ws, out, stream));
     ST_LAUNCHED("fe_synthesis_fwd"); return ST_OK;
 }
@@ -2173,7 +2210,7 @@ extern "C" int st_model_input_grad(const st_dims* d, const float* params, void* 
 extern "C" int st_fe_analysis_bwd(const float* x, int B, int L, const float* W, int C, int KW, int hop, int pad, const float* g_out,
                                   float* ws, float* gW, float* gbias, float* gx, void* stream)
 {
-    ST_TRY(fe_check(B, L, C, KW, hop, pad)); ST_REQ(x && W && g_out && ws && gW, "st_fe_analysis_bwd: null pointer");
+    ST_TRY(fe_check("st_fe_analysis_bwd", B, L, C, KW, hop, pad)); ST_REQ(x && W && g_out && ws && gW, "st_fe_analysis_bwd: null pointer");
     const int T = st_fe_frames(L, KW, hop, pad), R = B * T;
     const int ns = wgrad_split(R);
     float* slabs = ws;                                       // [ns][C][KW]
@@ -2194,10 +2231,10 @@ extern "C" int st_fe_analysis_bwd(const float* x, int B, int L, const float* W, 
 extern "C" int st_fe_synthesis_bwd(const float* xft, int B, int T, const float* W, int C, int KW, int hop, int crop, const float* g_wave,
                                    float* ws, float* gW, float* g_xft, void* stream)
 {
-    ST_REQ(xft && W && g_wave && ws && gW && B > 0 && T > 0, "st_fe_synthesis_bwd: bad arguments");
-    ST_REQ(KW % 16 == 0 && C % 16 == 0 && hop % 4 == 0 && crop % 4 == 0, "st_fe_synthesis_bwd: KW%%16, C%%16, hop%%4, crop%%4 required");
-    const int len = (T - 1) * hop + KW - 2 * crop, R = B * T;
-    ST_REQ(len > 0 && len % 4 == 0, "st_fe_synthesis_bwd: bad output length %d", len);
+    int len = 0;
+    ST_TRY(fe_check_synth("st_fe_synthesis_bwd", B, T, C, KW, hop, crop, &len));
+    ST_REQ(xft && W && g_wave && ws && gW, "st_fe_synthesis_bwd: null pointer");
+    const int R = B * T;
     const int ns = wgrad_split(R);
     float* slabs = ws;                                       // [ns][C][KW]
     float* gp = ws + (size_t)ns * C * KW;                    // padded gradient signal [B][crop + len + crop]: its frames are d(frames)

@@ -519,3 +519,152 @@ def test_one_workspace_serves_every_smaller_batch():
     brute = max(lib.st_workspace_bytes(C.byref(d.with_batch(b).with_arith(prec=p, clip_all=ca))) for b in range(1, 601) for p in _lib.PREC.values() for ca in (0, 1))
     assert lib.st_workspace_bytes_max(C.byref(d)) == brute == lib.st_workspace_bytes_max(C.byref(d.with_arith(prec=_lib.PREC["bf16_all"], clip_all=1)))
     assert lib.st_workspace_bytes_max(C.byref(d.with_batch(0))) == 0
+
+
+# ------------------------------------------------------------------------------ the host gate of the generic front end (st_fe_supported)
+FE_DIV_TABLE = [      # (B, L, C, KW, hop, pad): the two largest exact row splits of KW = 16, hop = 4 and the first inexact ones above them
+    (1, 262144, 16, 16, 4, 0), (16, 65536, 16, 16, 4, 0),      # R * T = 4 294 574 089 and 4 293 394 576: below 2^32
+    (2, 262144, 16, 16, 4, 0), (17, 65536, 16, 16, 4, 0),      # over: the last row's quotient is wrong
+]
+FE_ORDINARY = [(1, 64, 16, 16, 4, 0), (3, 256, 16, 16, 4, 16), (5, 1000, 112, 48, 20, 12), (7, 1204, 16, 64, 100, 0), (2, 400, 32, 64, 12, 128),
+               (9, 4096, 208, 144, 36, 72), (16, 1616, 32, 16, 8, 0), (3, 8192, 512, 1024, 256, 512), (16, 8192, 16, 16, 4, 8), (3, 8192, 1024, 2048, 1024, 1024),
+               (256, 8192, 1056, 1024, 384, 1024)]
+
+
+def fe_violations(B, L, C, KW, hop, pad):
+    """The limits of include/signaltrain_hip.h (st_fe_supported) in Python integers: the names of the violated ones."""
+    if min(B, L, C, KW, hop) <= 0 or pad < 0:
+        return ["non-positive"]
+    bad = [n for n, v, m in (("KW%16", KW, 16), ("C%16", C, 16), ("hop%4", hop, 4), ("pad%4", pad, 4), ("L%4", L, 4)) if v % m]
+    if bad:
+        return bad
+    if KW > L + 2 * pad:
+        return ["no frame"]
+    T = (L + 2 * pad - KW) // hop + 1
+    R, wide = B * T, L + 2 * pad + 2 * KW
+    lim = [("rows", R, 1 << 24), ("samples", wide, 1 << 24), ("B*L", B * L, 1 << 30), ("B*wide", B * wide, 1 << 30), ("R*KW", R * KW, 1 << 30),
+           ("R*C", R * C, 1 << 30), ("C*KW", C * KW, 1 << 30), ("split", (R - 1) * T, 1 << 32)]
+    return [n for n, v, m in lim if v >= m]
+
+
+def test_fe_gate_is_exactly_the_row_split_bound():
+    """RowMap::split (st_gemm.h) divides a compact row r < B * T by T with a multiply-high by floor(2^32 / T) + 1.  st_fe_supported says yes exactly where that is the
+    true quotient for every row (brute force on the rows next to every multiple of T, where it fails first), and at the two refused shapes the brute force really finds a
+    wrong quotient: without the gate the last row's frame index would be -1."""
+    lib = _lib.load()
+
+    def first_wrong(R, T):
+        magic = (1 << 32) // T + 1
+        for q in range(1, R // T + 1):
+            for r in (q * T - 1, q * T):
+                if r < R and (r * magic) >> 32 != r // T:
+                    return r
+        return None
+
+    for s in FE_DIV_TABLE + FE_ORDINARY:
+        B, L, C_, KW, hop, pad = s
+        T = lib.st_fe_frames(L, KW, hop, pad); R = B * T
+        wrong = first_wrong(R, T)
+        assert lib.st_fe_supported(*s) == (1 if wrong is None else 0), (s, wrong)
+        assert (wrong is None) == ((R - 1) * T < (1 << 32)), (s, wrong)
+    assert [lib.st_fe_supported(*s) for s in FE_DIV_TABLE] == [1, 1, 0, 0]
+    assert first_wrong(2 * 65533, 65533) == 2 * 65533 - 1 and first_wrong(17 * 16381, 16381) == 17 * 16381 - 1      # the last row, as recorded
+    # every compute entry and the workspace size refuse such a shape on the host, by name, before they look at a pointer
+    for s in FE_DIV_TABLE[2:]:
+        B, L, C_, KW, hop, pad = s
+        T = lib.st_fe_frames(L, KW, hop, pad)
+        assert lib.st_fe_ws_floats(*s) == 0
+        for rc in (lib.st_fe_analysis_fwd(None, B, L, None, None, C_, KW, hop, pad, None, None),
+                   lib.st_fe_analysis_bwd(None, B, L, None, C_, KW, hop, pad, None, None, None, None, None, None),
+                   lib.st_fe_synthesis_fwd(None, B, T, None, C_, KW, hop, pad, None, None, None),
+                   lib.st_fe_synthesis_bwd(None, B, T, None, C_, KW, hop, pad, None, None, None, None, None)):
+            assert rc == -1 and b"row split" in lib.st_last_error(), (s, rc, lib.st_last_error())
+
+
+FE_LIMIT_PAIRS = [      # (limit, a shape just inside it, a shape just outside it)
+    ("rows", (65535, 1036, 16, 16, 4, 0), (65536, 1036, 16, 16, 4, 0)),                          # T = 256: R = 2^24 - 256 | 2^24
+    ("samples", (1, (1 << 24) - 36, 16, 16, 512, 0), (1, (1 << 24) - 32, 16, 16, 512, 0)),      # L + 2 KW = 2^24 - 4 | 2^24
+    ("B*L", (1024, (1 << 20) - 36, 16, 16, 4096, 0), (1024, 1 << 20, 16, 16, 4096, 0)),        # B * L = 2^30 (then B * (L + 2 KW) is over as well)
+    ("B*wide", (1024, (1 << 20) - 36, 16, 16, 4096, 0), (1024, (1 << 20) - 32, 16, 16, 4096, 0)),      # B * L < 2^30 <= B * (L + 2 KW)
+    ("R*KW", (1, 163832, 16, 32768, 4, 0), (1, 163836, 16, 32768, 4, 0)),                       # T = 32767 | 32768 frames of 32768 taps
+    ("R*C", (1, 131080, 32768, 16, 4, 0), (1, 131084, 32768, 16, 4, 0)),                        # T = 32767 | 32768 frames of 32768 channels
+    ("C*KW", (1, 32768, 32752, 32768, 4, 0), (1, 32768, 32768, 32768, 4, 0)),
+    ("split", (1, 262144, 16, 16, 4, 0), (1, 262160, 16, 16, 4, 0)),                            # T = 65533 | 65537: T (T - 1) crosses 2^32
+    ("split", (16, 65536, 16, 16, 4, 0), (17, 65536, 16, 16, 4, 0)),
+    ("KW%16", (2, 256, 32, 48, 8, 8), (2, 256, 32, 40, 8, 8)),
+    ("C%16", (2, 256, 48, 32, 8, 8), (2, 256, 40, 32, 8, 8)),
+    ("hop%4", (2, 256, 32, 32, 12, 8), (2, 256, 32, 32, 10, 8)),
+    ("pad%4", (2, 256, 32, 32, 8, 12), (2, 256, 32, 32, 8, 10)),
+    ("L%4", (2, 260, 32, 32, 8, 8), (2, 258, 32, 32, 8, 8)),
+    ("no frame", (1, 64, 16, 80, 4, 8), (1, 64, 16, 96, 4, 8)),                                  # KW = | > L + 2 pad: T = 1 | 0
+    ("non-positive", (1, 64, 16, 16, 4, 0), (0, 64, 16, 16, 4, 0)),
+    ("non-positive", (1, 64, 16, 16, 4, 0), (1, 64, 16, 16, 4, -4)),
+    ("non-positive", (1, 64, 16, 16, 4, 0), (1, 64, 16, 16, 0, 0)),
+]
+
+
+def test_fe_gate_limits_one_shape_inside_and_one_outside_each():
+    """Every limit of st_fe_supported against integer arithmetic in Python: the shape just inside violates nothing and is accepted, the shape just outside violates
+    the named limit (and, except where one limit implies another, only that one) and is refused -- by the predicate, by the workspace size and, with a message, by a
+    compute entry that has not looked at a pointer yet.  A seeded random sweep around the limits then has predicate and Python agree shape by shape."""
+    lib = _lib.load()
+    implied = {"B*L": {"B*L", "B*wide"}}
+    for name, inside, outside in FE_LIMIT_PAIRS:
+        assert fe_violations(*inside) == [] and lib.st_fe_supported(*inside) == 1, (name, inside, fe_violations(*inside))
+        assert set(fe_violations(*outside)) == implied.get(name, {name}), (name, outside, fe_violations(*outside))
+        assert lib.st_fe_supported(*outside) == 0 and lib.st_fe_ws_floats(*outside) == 0, (name, outside)
+        B, L, C_, KW, hop, pad = outside
+        assert lib.st_fe_analysis_fwd(None, B, L, None, None, C_, KW, hop, pad, None, None) == -1 and len(lib.st_last_error()) > 20
+        assert b"null" not in lib.st_last_error(), lib.st_last_error()
+    rng = np.random.default_rng(11)
+    seen = {0: 0, 1: 0}
+    for _ in range(4000):
+        KW = 16 * int(rng.integers(1, 5)) if rng.random() < 0.8 else 16 * int(rng.integers(1, 4096))
+        C_ = 16 * int(rng.integers(1, 5)) if rng.random() < 0.8 else 16 * int(rng.integers(1, 4096))
+        hop = 4 * int(rng.integers(1, 2 ** int(rng.integers(1, 12))))
+        pad = 4 * int(rng.integers(0, 64))
+        L = 4 * int(rng.integers(1, 2 ** int(rng.integers(3, 23))))
+        B = int(rng.integers(1, 2 ** int(rng.integers(1, 18))))
+        s = (B, L, C_, KW, hop, pad)
+        ok = lib.st_fe_supported(*s)
+        assert ok == (0 if fe_violations(*s) else 1), (s, fe_violations(*s))
+        seen[ok] += 1
+    assert min(seen.values()) > 200, seen      # the sweep really reaches both sides
+
+
+def test_fe_workspace_size_is_zero_exactly_where_the_gate_refuses():
+    """st_fe_ws_floats is 0 exactly where st_fe_supported is 0 (like st_workspace_bytes on bad dims); where the shape is accepted it covers what st_fe_analysis_bwd
+    and st_fe_synthesis_bwd carve: ns slabs of the weight gradient, the frame buffer and the padded gradient signal, ns = clamp(B * T // 200, 1, 16)
+    (the tuning defaults frozen by test_tuning_defaults_are_frozen)."""
+    lib = _lib.load()
+    shapes = FE_DIV_TABLE + FE_ORDINARY + [s for _, a, b in FE_LIMIT_PAIRS for s in (a, b)]
+    for s in shapes:
+        B, L, C_, KW, hop, pad = s
+        n = lib.st_fe_ws_floats(*s)
+        assert (n == 0) == (lib.st_fe_supported(*s) == 0), s
+        if n:
+            T = (L + 2 * pad - KW) // hop + 1
+            assert T == lib.st_fe_frames(L, KW, hop, pad)
+            ns = min(max(B * T // 200, 1), 16)
+            assert n >= ns * C_ * KW + B * T * KW + B * (L + 2 * pad), (s, n)
+
+
+def test_model_dims_are_refused_past_the_row_split_bound():
+    """check_dims carries the same rule for the model's framed GEMMs: (B * T - 1) * T < 2^32 (their live-frame maps divide by Tv <= T).  No training geometry comes
+    near it -- every configuration of BASELINE.md and the largest admitted batches of test_dims_edge_cases_are_refused_with_a_message still report a layout."""
+    lib = _lib.load()
+    d = _lib.geometry(1, 4, 4, 1)
+    d.T = 65536
+    assert (d.B * d.T - 1) * d.T < (1 << 32) and lib.st_param_offsets(C.byref(d), None) > 0, lib.st_last_error()
+    d.T = 65537
+    assert (d.B * d.T - 1) * d.T >= (1 << 32) and d.B * d.T < (1 << 24) and d.B * d.T * lib.st_kp(d.F) < (1 << 30)      # no other limit is in the way
+    assert lib.st_param_offsets(C.byref(d), None) == -1 and b"row split" in lib.st_last_error()
+    assert lib.st_workspace_bytes(C.byref(d)) == 0
+    assert lib.st_analysis_fwd(C.byref(d), None, None, None, 0.5, None, None, None, None, None) < 0 and b"row split" in lib.st_last_error()
+    d.B, d.T = 3, 40000                                          # R = 120000 rows: 119999 * 40000 >= 2^32
+    assert d.B * d.T * lib.st_kp(d.F) < (1 << 30) and lib.st_param_offsets(C.byref(d), None) == -1 and b"row split" in lib.st_last_error()
+    for scale, scheme, batches in ((1, "lean", (32, 256, 1024, 2048)), (8, "lean", (64, 512)), (2, "legacy", (256,))):
+        for Bn in batches:
+            g = _lib.geometry(scale, 4, 4, Bn, scale_scheme=scheme)
+            assert (g.B * g.T - 1) * g.T < (1 << 32) // 100
+            assert lib.st_param_offsets(C.byref(g), None) > 0 and lib.st_workspace_bytes(C.byref(g)) > 0, (scale, scheme, Bn, lib.st_last_error())
