@@ -55,7 +55,18 @@ extern "C" {
 #define ST_PREC_F16_ALL 4
 #define ST_PREC_F32X3 5
 
-/* Geometry (nn_proc.py:357-385) and arithmetic of one call. */
+/* Geometry (nn_proc.py:357-385) and arithmetic of one call.
+ * The supported family is wider than what st_geometry produces (N = 1024, H = 384 and the legacy multiples); every entry refuses anything outside it
+ * with ST_ERR_ARG and a message in st_last_error() that names the rule, before any launch, and every size or count function below that takes an st_dims
+ * then returns 0 (st_param_offsets and st_workspace_offsets: -1):
+ *   - B, L, N, H, T, OT > 0, 0 <= K <= 16, F == N/2 + 1;
+ *   - N % 32 == 0, H % 4 == 0, L % 4 == 0, y % 4 == 0 (H > N, H == N and L < N are inside the family);
+ *   - y == (OT - 1) * H - N, 0 < y <= L, OT <= T;
+ *   - H * T >= L + N: frame t starts at sample H t - N, so T frames must reach the end of the signal.  The reference's Conv1d yields (L + N) / H + 1 frames
+ *     and its first Linear layer accepts no other count; here a larger T only adds all-padding frames (st_geometry's ceil(L/H) + ceil(N/H) does that for some
+ *     L) and the one frame that starts exactly at L may be left out, but a T that drops a frame overlapping the signal is refused;
+ *   - B * T < 2^24, B * T * KP < 2^30, B * (L + 2 N) < 2^30 (32-bit element offsets) and (B * T - 1) * T < 2^32 (the row split by a multiply-high).
+ * Sizes away from 1024 / 384 run the general kernels (no 128-row tiles below N % 256 == 0, no 16-bit operand pipeline below N % 128 == 0): correct, not tuned. */
 typedef struct st_dims {
     int B;   /* windows in this (per-GPU) minibatch                         */
     int L;   /* samples per input window  (8192*scale)                      */

@@ -350,7 +350,9 @@ def _ae_bwd(dout, v, knobs, P, prefix, mode, hs):
         # wide geometries (T > 32 or OT > 16: st_ae_wide.h) run layers 1 and 9 as GEMMs in which the bias gradient rides along as a row of ones,
         # i.e. it is the sum of the ROUNDED dA under AE_ROUND; everywhere else it is summed from the fp32 accumulators
         wide_gemm_layer = (T > 32 or OT > 16) and li in (0, len(AE_LAYERS) - 1)
-        grads[f"{prefix}.{name}.bias"] = (_ra(da2) if wide_gemm_layer else da2).sum(0)
+        # summed along the contiguous axis, where numpy adds pairwise: one after the other, B * F = 77 400 float32 rows (600 windows at 256 taps) drift by
+        # 1e-4 of the result, which is the oracle's own noise and not a property of the inputs
+        grads[f"{prefix}.{name}.bias"] = np.ascontiguousarray((_ra(da2) if wide_gemm_layer else da2).T).sum(1)
         dh = _ra(da) @ _ra(W)
         if name == "fnn_addknobs":
             # the knob columns of the concatenated input (nn_proc.py:92-93: knobs repeated over the rows of a window, then torch.cat):

@@ -85,14 +85,13 @@ class _AnalysisFn(torch.autograd.Function):
 
 
 def _relax(d):
-    """Standalone front/back-end calls only use part of st_dims; fill the rest consistently."""
+    """Standalone front/back-end calls only use part of st_dims; fill the rest consistently.  T is the caller's frame count and stays: the tensors are
+    sized by it.  A wave so short that the smallest output geometry has more frames than that (then y > L as well) is refused by name by the entry."""
     if d.OT < 3:
         d.OT = max(3, -(-d.N // d.H) + 1)
     d.y = (d.OT - 1) * d.H - d.N
     while d.y <= 0 or d.y % 4:
         d.OT += 1; d.y = (d.OT - 1) * d.H - d.N
-    if d.T < d.OT:
-        d.T = d.OT
     return d
 
 
@@ -116,7 +115,7 @@ class _SynthesisFn(torch.autograd.Function):
     def forward(ctx, real, imag, Sr, Si, N, H):
         lib = _lib.load()
         B, OT, F = real.shape
-        d = _dims(B, 4 * ((OT - 1) * H - N), N, H, OT, OT)
+        d = _dims(B, (OT - 1) * H - N, N, H, OT, OT)            # L = y: the synthesis side reads no input window, and T = OT frames then cover L (H T >= L + N)
         KP = lib.st_kp(F)
         AA = torch.zeros(B * OT, KP, device=real.device)
         AA[:, :F] = real.reshape(B * OT, F); AA[:, KP // 2:KP // 2 + F] = imag.reshape(B * OT, F)
@@ -135,7 +134,7 @@ class _SynthesisFn(torch.autograd.Function):
         lib = _lib.load()
         AA, Sfold = ctx.saved_tensors
         B, OT, F, N, H = ctx.geom
-        d = _dims(B, 4 * ((OT - 1) * H - N), N, H, OT, OT)
+        d = _dims(B, (OT - 1) * H - N, N, H, OT, OT)            # L = y: the synthesis side reads no input window, and T = OT frames then cover L (H T >= L + N)
         KP = lib.st_kp(F)
         dsyn = g_wave.contiguous().float()
         dAA = torch.zeros(lib.st_synth_slabs(C.byref(d)), B * OT, KP, device=AA.device)

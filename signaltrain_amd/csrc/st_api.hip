@@ -112,6 +112,11 @@ static int check_dims(const st_dims* d)
     ST_REQ(d->N % 32 == 0 && d->H % 4 == 0 && d->L % 4 == 0 && d->y % 4 == 0, "N%%32, H%%4, L%%4, y%%4 required");
     ST_REQ(d->y == (d->OT - 1) * d->H - d->N && d->y > 0 && d->y <= d->L, "y must equal (OT-1)*H-N");
     ST_REQ(d->OT <= d->T, "OT must be <= T");
+    // the reference's Conv1d (padding N, stride H) yields (L + N) / H + 1 frames and its first Linear layer refuses any other count; here frame t starts
+    // at sample H t - N, so a T with H T < L + N leaves out a frame that still overlaps the signal.  A larger T only adds all-padding frames (st_geometry
+    // emits that: ceil(L / H) + ceil(N / H) frames), a frame starting exactly at L is dead and may be omitted.
+    ST_REQ((long long)d->H * d->T >= (long long)d->L + d->N, "T too small: H*T >= L+N required, or a frame overlapping the signal is dropped (T=%d L=%d N=%d H=%d)",
+           d->T, d->L, d->N, d->H);
     ST_REQ(d->K <= 16, "at most 16 knobs");
     ST_REQ(d->prec >= ST_PREC_F32 && d->prec <= ST_PREC_F32X3, "st_dims.prec = %d is not an ST_PREC_* level", d->prec);
     ST_REQ(d->loss_scale >= 0.f && d->loss_scale <= 3.0e38f, "st_dims.loss_scale must be 0 (none) or a positive finite scale");
@@ -373,9 +378,10 @@ static int wgrad_split_tiles(int R, int M, int Nc)
 }
 static int synth_split(int R) { return R >= 4096 ? 1 : g_syn_split; }   // consumers (ola_loss_kernel, ae_bwd_kernel) sum at most 3 slabs
 
-extern "C" int st_ae_fwd_partials(const st_dims* d) { return ae_fwd_grid(d) * ae_fwd_nw(d); }
-extern "C" int st_ola_loss_partials(const st_dims* d) { return d->B * ((d->y + 255) / 256); }
-extern "C" int st_norm_partials(const st_dims* d) { return stm::norm_partial_count(d->F, d->N); }
+// (the host size functions answer 0 for dims outside the supported family, with the rule in st_last_error(): check_dims)
+extern "C" int st_ae_fwd_partials(const st_dims* d) { return check_dims(d) != ST_OK ? 0 : ae_fwd_grid(d) * ae_fwd_nw(d); }
+extern "C" int st_ola_loss_partials(const st_dims* d) { return check_dims(d) != ST_OK ? 0 : d->B * ((d->y + 255) / 256); }
+extern "C" int st_norm_partials(const st_dims* d) { return check_dims(d) != ST_OK ? 0 : stm::norm_partial_count(d->F, d->N); }
 // k-slices of the 128 x 128-tile weight-gradient GEMM (st_gemm_tn.h): as many as fill the CUs with one workgroup each, never slices
 // shorter than 64 reduction rows
 static int tn_split(int R, int N)
@@ -387,6 +393,7 @@ static int tn_split(int R, int N)
 }
 extern "C" size_t st_wgrad_ws_floats(const st_dims* d)
 {
+    if (check_dims(d) != ST_OK) return 0;
     int s = wgrad_split_tiles(d->B * d->T, st_kp_of(d->F), d->N);
     const int s2 = tn_split(d->B * d->T, d->N); if (s2 > s) s = s2;
     return (size_t)s * st_kp_of(d->F) * d->N + (size_t)64 * 2 * d->N;       // + the Nyquist partials of the 128 x 128-tile form
@@ -396,11 +403,11 @@ static size_t synth_wgrad_ws_floats(const st_dims* d) { return st_wgrad_ws_float
 // backward; with a buffer of their own the analysis weight-gradient GEMM (which reuses the first area) needs no communicator -> compute wait before it starts -- one
 // barrier packet (~6 us of bubble on this stack) less on the compute stream.
 static size_t synth_wgrad_ws_floats(const st_dims* d);      // = st_wgrad_ws_floats(d): every slab-count rule of the fp32 and 16-bit weight-gradient launches is capped by that area's size
-extern "C" int st_synth_slabs(const st_dims* d) { return synth_split(synth_live_rows(d)); }
+extern "C" int st_synth_slabs(const st_dims* d) { return check_dims(d) != ST_OK ? 0 : synth_split(synth_live_rows(d)); }
 // split-K slabs of the synthesis FRAMES GEMM (summed by ola_loss_kernel, which takes up to 6; the dgrad slabs are summed
 // inside ae_bwd_kernel where every extra slab costs 8 loads per row group, hence the separate, smaller count above)
 static int frames_split(int R) { return R >= 4096 ? 1 : g_frs_split; }
-extern "C" int st_synth_frame_slabs(const st_dims* d) { return frames_split(synth_live_rows(d)); }
+extern "C" int st_synth_frame_slabs(const st_dims* d) { return check_dims(d) != ST_OK ? 0 : frames_split(synth_live_rows(d)); }
 // Wide geometries (T > 32 or OT > 16) run the autoencoders as feature-major GEMMs (st_ae_wide.h) and need workspace
 // for the activations [features][B*FP]; the fused kernels of st_ae.h need none in forward.
 static bool ae_is_wide(const st_dims* d) { return d->T > 32 || d->OT > 16; }
@@ -1326,7 +1333,11 @@ extern "C" int st_workspace_offsets(const st_dims* d, int64_t* offs8)
 // The ten return_acts tensors of ONE autoencoder (nn_proc.py:77-126), [B][F][width] each, concatenated in `acts`
 // (widths 64, 32, 16, 16, 16 + K, 16, 16, 32, 64, OT; st_ae_acts_floats() floats).  v: [B][T][F] (mag or phs); ae: that autoencoder's
 // packed parameters (st_param_offsets order); sf != 0: the skip-filter output (magnitude net), else the bare ELU output (phase net).
-extern "C" size_t st_ae_acts_floats(const st_dims* d) { return (size_t)d->B * d->F * (64 + 32 + 16 + 16 + 16 + d->K + 16 + 16 + 32 + 64 + d->OT); }
+extern "C" size_t st_ae_acts_floats(const st_dims* d)
+{
+    if (check_dims(d) != ST_OK) return 0;
+    return (size_t)d->B * d->F * (64 + 32 + 16 + 16 + 16 + d->K + 16 + 16 + 32 + 64 + d->OT);
+}
 extern "C" int st_ae_acts(const st_dims* d, const float* v, const float* knobs, const float* ae, int sf, float* acts, void* stream)
 {
     Layout L; ST_TRY(make_layout(d, &L));

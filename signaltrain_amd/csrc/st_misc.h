@@ -1112,9 +1112,13 @@ ae_acts_kernel(const AeActsArgs a)
         for (int o = 0; o < outw[l]; ++o) {
             float s = bias[o];
             for (int i = 0; i < inw; ++i) s = __builtin_fmaf(W[o * inw + i], l == 0 ? a.v[((size_t)b * a.T + i) * a.F + f] : h[i], s);
-            z[o] = s > 0.f ? s : expm1f(s);            // ELU, alpha = 1
+            float e = s > 0.f ? s : expm1f(s);         // ELU, alpha = 1
+            if (l == 8) {                              // fnn_dec: OT outputs (any OT <= T, not bounded by the 80 of h / z) go straight out
+                if (a.sf) e *= a.v[((size_t)b * a.T + (a.T - a.OT + o)) * a.F + f];      // skip-filter (nn_proc.py:115)
+                a.out[9][(size_t)row * a.OT + o] = e;
+            } else z[o] = e;
         }
-        if (l == 8 && a.sf) for (int o = 0; o < a.OT; ++o) z[o] *= a.v[((size_t)b * a.T + (a.T - a.OT + o)) * a.F + f];      // skip-filter (nn_proc.py:115)
+        if (l == 8) break;
         const int slot = l < 4 ? l : l + 1;
         for (int o = 0; o < outw[l]; ++o) { h[o] = z[o]; a.out[slot][(size_t)row * outw[l] + o] = z[o]; }
         inw = outw[l];

@@ -65,7 +65,7 @@ class AsymAutoEncoder(nn.Module):
         x = x_input.contiguous().float(); kn = knobs.contiguous().float() if self._K else None      # K = 0: an empty tensor has no address; the C ABI takes NULL then
         B, T, F = x.shape
         d = _lib.st_dims(); d.B, d.N, d.F, d.T, d.OT, d.K, d.H = B, 2 * (F - 1), F, T, self._OT, self._K, 384
-        d.y = (d.OT - 1) * d.H - d.N; d.L = max(4 * d.y, 4)
+        d.y = (d.OT - 1) * d.H - d.N; d.L = d.y          # one autoencoder alone reads no waveform: L = y keeps H T >= L + N for every OT <= T
         offs, total = _lib.param_offsets(d)
         packed = torch.zeros(offs[22] - offs[4], device=x.device)
         k = 0
@@ -88,7 +88,7 @@ class AsymAutoEncoder(nn.Module):
         lib = _lib.load()
         B, T, F = x_input.shape
         d = _lib.st_dims(); d.B, d.N, d.F, d.T, d.OT, d.K, d.H = B, 2 * (F - 1), F, T, self._OT, self._K, 384
-        d.y = (d.OT - 1) * d.H - d.N; d.L = max(4 * d.y, 4)
+        d.y = (d.OT - 1) * d.H - d.N; d.L = d.y          # one autoencoder alone reads no waveform: L = y keeps H T >= L + N for every OT <= T
         offs, total = _lib.param_offsets(d)
         pg = offs[22] - offs[4]
         packed = torch.zeros(pg, device=x_input.device)

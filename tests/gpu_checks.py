@@ -30,9 +30,10 @@ def stream():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
-def make_case(B=3, seed=0, scale=1, shrink=4, K=4, pert=7, scheme="lean"):
-    """Seeded comp_4c-shaped inputs + 'learned' (perturbed) parameters, as fp32 numpy."""
-    geo = O.geometry(scale, shrink, scheme)
+def make_case(B=3, seed=0, scale=1, shrink=4, K=4, pert=7, scheme="lean", geo=None):
+    """Seeded comp_4c-shaped inputs + 'learned' (perturbed) parameters, as fp32 numpy.  geo: an explicit geometry (a dict with the keys O.geometry
+    returns) instead of the one (scale, shrink, scheme) give -- any (ft, hop, frame) sizes st_dims admits (tests/dims_table.py)."""
+    geo = O.geometry(scale, shrink, scheme) if geo is None else dict(geo)
     rng = np.random.default_rng(seed)
     X, Y, KN = O.synth_comp4c_batch(B, geo["L"], geo["y"], rng)
     if K != 4:
@@ -185,10 +186,10 @@ def phase_err(name, got, ref, mag, tol=TOL):
 
 
 # --------------------------------------------------------------------------------------------- stages
-def run_all(B=3, seed=0, K=4, verbose=False, scale=1, scheme="lean", shrink=4):
+def run_all(B=3, seed=0, K=4, verbose=False, scale=1, scheme="lean", shrink=4, geo=None):
     """Run every per-op entry point on oracle-provided inputs; returns list of result dicts."""
     lib = _lib.load()
-    geo, X, Y, KN, P = make_case(B, seed, K=K, scale=scale, scheme=scheme, shrink=shrink)
+    geo, X, Y, KN, P = make_case(B, seed, K=K, scale=scale, scheme=scheme, shrink=shrink, geo=geo)
     d = dims_of(geo, B, K)
     restore_oracle = follow_effective_arithmetic(d)
     try:
@@ -331,10 +332,10 @@ def _run_all(lib, geo, X, Y, KN, P, d, B, K, verbose):
     return res
 
 
-def run_fused(B=3, seed=1, K=4, steps=3, scale=1, scheme="lean", shrink=4, oracle_dtype="f64"):
+def run_fused(B=3, seed=1, K=4, steps=3, scale=1, scheme="lean", shrink=4, oracle_dtype="f64", geo=None):
     """Fused entry points: st_model_fwd, st_loss_backward, st_train_step x steps vs the oracle (float64 from the same fp32 inputs; oracle_dtype="f32":
     the oracle's forward / backward in float32 arithmetic instead -- the reference's own precision, tools/fuzz_ground_f32.py)."""
-    geo, X, Y, KN, P = make_case(B, seed, K=K, scale=scale, scheme=scheme, shrink=shrink)
+    geo, X, Y, KN, P = make_case(B, seed, K=K, scale=scale, scheme=scheme, shrink=shrink, geo=geo)
     d = dims_of(geo, B, K)
     restore_oracle = follow_effective_arithmetic(d)
     try:

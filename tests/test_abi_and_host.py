@@ -668,3 +668,103 @@ def test_model_dims_are_refused_past_the_row_split_bound():
             g = _lib.geometry(scale, 4, 4, Bn, scale_scheme=scheme)
             assert (g.B * g.T - 1) * g.T < (1 << 32) // 100
             assert lib.st_param_offsets(C.byref(g), None) > 0 and lib.st_workspace_bytes(C.byref(g)) > 0, (scale, scheme, Bn, lib.st_last_error())
+
+
+# ---------------------------------------------------------------------------------------------- the (ft, hop, frame) sizes of tests/test_gpu_dims_sweep.py
+def _dims_of_row(shape, B=3, K=4):
+    from tests import dims_table as D
+    g = D.geo_of(shape)
+    d = _lib.st_dims()
+    d.B, d.L, d.N, d.H, d.T, d.OT, d.F, d.K, d.y = B, g["L"], g["N"], g["H"], g["T"], g["OT"], g["F"], K, g["y"]
+    return d
+
+
+def _sweep_case_ids():
+    from tests import dims_table as D
+    return [f"{r}-B{b}-K{k}-seed{s}-{kind}" for r, b, k, s, kind in D.sweep_cases()]
+
+
+def _sweep_cases():
+    from tests import dims_table as D
+    return D.sweep_cases()
+
+
+@pytest.mark.parametrize("case", _sweep_cases(), ids=_sweep_case_ids())
+def test_sweep_inputs_leave_fp32_arithmetic_inside_a_quarter_of_the_tolerance(case):
+    """A GPU comparison at tolerance tau means something only if fp32 arithmetic itself is well inside tau on those inputs: for every (shape, batch, knobs,
+    seed) of the dims sweep, the oracle run in float32 agrees with its float64 run to tau / 4 on every tensor the sweep compares (y_hat, mag, mag_hat, the
+    loss at 1e-4; the 40 gradients at 1e-4 per-op and 2e-4 fused; the per-op intermediates of run_all; the L1 norm and, on the rolled inputs of both train
+    steps, the loss and the parameters of run_fused: dims_table.input_condition), with gpu_checks' scaling.  CPU only."""
+    from tests import dims_table as D
+    from tests import gpu_checks as G                        # make_case only (numpy); no GPU touched
+    row, B, K, seed, kind = case
+    geo = D.geo_of(row)
+    _, X, Y, KN, P = G.make_case(B, seed, K=K, geo=geo)
+    c = D.input_condition(geo, X, Y, KN, P, kind)
+    assert len(c) == {"per-op": 62, "fused": 49}[kind]
+    over = {k: v for k, v in c.items() if not v <= D.condition_bound(k, kind)}
+    assert not over, (case, over)
+
+
+def test_host_size_functions_at_every_sweep_row():
+    """Host only: layout and workspace arithmetic at the sizes st_geometry never produces -- positive sizes, parameter offsets aligned to 4 floats, the
+    forward state inside the workspace, and one workspace for every smaller batch no smaller than the exact one."""
+    from tests import dims_table as D
+    lib = _lib.load()
+    for row in D.ROWS:
+        for B, K in ((3, 4), (1, 0), (2, 16)):
+            d = _dims_of_row(row, B, K)
+            offs = (C.c_int64 * 40)()
+            total = lib.st_param_offsets(C.byref(d), offs)
+            assert total > 0 and all(o % 4 == 0 for o in offs) and list(offs) == sorted(set(offs)) and offs[39] < total, (row, lib.st_last_error())
+            from signaltrain_amd.engine import param_shapes
+            assert total >= sum(int(np.prod(s)) for s in param_shapes(d)) > total - 4 * 40
+            for prec in (0, 2, 4, 5):
+                d.prec = prec
+                nb = lib.st_workspace_bytes(C.byref(d))
+                assert nb > 0 and nb % 4 == 0 and lib.st_workspace_bytes_max(C.byref(d)) >= nb, (row, prec)
+                w8 = (C.c_int64 * 8)()
+                assert lib.st_workspace_offsets(C.byref(d), w8) == 0
+                KP = lib.st_kp(d.F)
+                sizes = [B * d.T * d.F] * 4 + [B * d.OT * d.F] * 2 + [B * d.OT * KP, B * d.y]
+                spans = sorted((o, o + n) for o, n in zip(w8, sizes))
+                assert spans[0][0] >= 0 and spans[-1][1] * 4 <= nb and all(a[1] <= b[0] for a, b in zip(spans, spans[1:])), (row, prec, spans)
+            d.prec = 0
+            assert lib.st_norm_partials(C.byref(d)) > 0 and lib.st_synth_slabs(C.byref(d)) > 0
+            assert lib.st_ola_loss_partials(C.byref(d)) == B * -(-d.y // 256)
+            assert lib.st_ae_acts_floats(C.byref(d)) == B * d.F * (272 + K + d.OT)
+
+
+def test_a_frame_count_that_drops_live_frames_is_refused_by_name():
+    """check_dims: H T >= L + N.  Frame t starts at H t - N; the reference's Conv1d has (L + N) // H + 1 of them and its first Linear layer raises on any other
+    count.  Here a larger T (all-padding frames: st_geometry emits it) and the omission of the one frame that starts exactly at L stay legal; a T that drops a
+    frame overlapping the signal comes back as -1 / 0 from every host size function, with the rule and the four numbers in st_last_error()."""
+    from tests import dims_table as D
+    lib = _lib.load()
+    for name, shape in D.REFUSED.items():
+        N, H, L, T, OT = shape
+        assert H * T < L + N
+        d = _dims_of_row(shape)
+        for fn, want in (("st_param_offsets", -1), ("st_workspace_bytes", 0), ("st_workspace_bytes_max", 0), ("st_norm_partials", 0), ("st_ola_loss_partials", 0),
+                         ("st_synth_slabs", 0), ("st_ae_acts_floats", 0), ("st_ae_fwd_ws_floats", 0), ("st_ae_bwd_ws_floats", 0), ("st_ae_fwd_partials", 0),
+                         ("st_synth_frame_slabs", 0), ("st_wgrad_ws_floats", 0), ("st_ae_kept_activation_bytes", 0), ("st_model_input_grad_ws_floats", 0)):
+            lib.st_workspace_bytes(C.byref(_dims_of_row("n256")))        # a good call in between: the message must come from THIS refusal
+            got = lib.st_param_offsets(C.byref(d), None) if fn == "st_param_offsets" else getattr(lib, fn)(C.byref(d))
+            msg = lib.st_last_error()
+            assert got == want and b"T too small" in msg, (name, fn, got, msg)
+            assert all(f"{k}={v}".encode() in msg for k, v in (("T", T), ("L", L), ("N", N), ("H", H))), msg
+        assert lib.st_workspace_offsets(C.byref(d), (C.c_int64 * 8)()) == -1
+        assert lib.st_analysis_fwd(C.byref(d), None, None, None, 0.5, None, None, None, None, None) == -1 and b"T too small" in lib.st_last_error()
+        d.T = -(-(L + N) // H)                                   # the smallest legal T
+        d.OT = min(d.OT, d.T); d.y = (d.OT - 1) * H - N
+        assert lib.st_param_offsets(C.byref(d), None) > 0, (name, lib.st_last_error())
+    # nothing st_geometry produces violates the rule: ceil(L / H) + ceil(N / H) >= (L + N) / H
+    for scale in (1, 2, 4, 8):
+        for shrink in (1, 2, 4, 8):
+            for scheme in ("lean", "legacy"):
+                g = _lib.geometry(scale, shrink, 4, 2, scale_scheme=scheme)
+                assert g.H * g.T >= g.L + g.N and lib.st_workspace_bytes(C.byref(g)) > 0, (scale, shrink, scheme, lib.st_last_error())
+    # the standalone modules build their own dims: one autoencoder alone at the 89 output frames of scale 4 / shrink 1
+    d = _lib.st_dims(); d.B, d.N, d.F, d.T, d.OT, d.K, d.H = 1, 1024, 513, 89, 89, 3, 384
+    d.y = (d.OT - 1) * d.H - d.N; d.L = d.y
+    assert lib.st_ae_acts_floats(C.byref(d)) == 513 * (272 + 3 + 89), lib.st_last_error()

@@ -507,3 +507,31 @@ def test_g14_edges(golden_dir, ci):
         assert np.abs(m[SAMPLE_ROWS] - g[pre + "rows_" + k]).max() <= tol, k
         assert np.abs(PROJ @ m - g[pre + "proj_" + k]).max() <= 1024 * tol, k
         assert abs(np.abs(m).sum() - float(g[pre + "l1_" + k])) <= 1e-4 * float(g[pre + "l1_" + k]), k
+
+
+@pytest.mark.parametrize("tag", ["c64", "c96"])
+def test_g16_other_ft_hop_and_frame_sizes(golden_dir, tag):
+    """Every other golden is at ft 1024 / hop 384 or a legacy multiple.  G16 (tools/capture_golden_sizes.py): the reference's AsymMPAEC built directly at
+    (ft, hop, L, T, OT, K) = (64, 24, 528, 25, 9, 3) and (96, 32, 640, 24, 8, 2), B = 2 -- whole tensors, no fingerprints: forward outputs, the loss and the
+    autograd gradients of all 40 tensors, at the tolerances of G3 / G4.  This is what pins the oracle at the sizes of tests/dims_table.py."""
+    g = load(golden_dir, "g16_other_sizes.npz")
+    N, H, L, T, OT, K = (int(v) for v in g["table"][list(g["cases"]).index(tag)])
+    y = (OT - 1) * H - N
+    geo = dict(L=L, out_chunk_intended=y, N=N, H=H, T=T, OT=OT, y=y, F=N // 2 + 1)
+    assert T == (L + N) // H + 1
+    assert list(g["param_names"]) == O.param_order()
+    P = {k: g[f"{tag}_p{i:02d}"] for i, k in enumerate(O.param_order())}
+    Gref = {k: g[f"{tag}_g{i:02d}"] for i, k in enumerate(O.param_order())}
+    assert [P[k].shape for k in O.param_order()[4:22:2]] == O.ae_layer_shapes(T, OT, K)
+    X, KN, Y = g[f"{tag}_x"], g[f"{tag}_knobs"], g[f"{tag}_y"]
+    assert X.shape == (2, L) and KN.shape == (2, K) and Y.shape == (2, y)
+    yh, mag, mag_hat = O.model_fwd(X, KN, P, geo)
+    close(yh, g[f"{tag}_y_hat"], 3e-6, "y_hat"); close(mag, g[f"{tag}_mag"], 3e-6, "mag"); close(mag_hat, g[f"{tag}_mag_hat"], 3e-6, "mag_hat")
+    loss, G, _ = O.model_loss_bwd(X.astype(np.float64), KN.astype(np.float64), Y.astype(np.float64), P, geo)
+    close(loss, g[f"{tag}_loss"], 3e-5, "loss")
+    for k in O.param_order():
+        assert G[k].shape == Gref[k].shape
+        close(G[k], Gref[k], 2e-5, k)
+    F = geo["F"]
+    for k in STFT_KEYS[:2]:
+        assert np.all(G[k][F:] == 0) and np.all(Gref[k][F:] == 0)
