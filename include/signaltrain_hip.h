@@ -91,11 +91,13 @@ int st_kp(int F);
 const char* st_last_error(void);
 int st_version(void);
 
-/* Diagnostic switches (process-wide; NEVER set by the product path): st_set_tuning(code) selects kernel variants kept for comparison
- * (codes: st_api.hip).  They are one readable state: st_get_tuning / st_tuning_defaults fill out[0..n) in a fixed order and return the
- * number of switches (out may be NULL), st_reset_tuning restores the shipped defaults; the test-suite asserts the state is at the
- * defaults after every test.  Timing-only ablations (results invalid) exist only in -DST_DIAG builds. */
-int st_set_tuning(int bk);
+/* Diagnostic switches (process-wide; NEVER set by the product path): st_set_tuning(code) selects a kernel variant that the test-suite keeps as
+ * an A/B reference or an agreement case.  ONE table in st_api.hip (k_tuning_codes) is the whole interface: it lists every accepted code with the
+ * switch it sets and the value it stores; any other code returns ST_ERR_ARG, names the code in st_last_error() and changes nothing.  The 20
+ * switches are one readable state: st_get_tuning / st_tuning_defaults fill out[0..n) in a fixed order and return the number of switches (out
+ * may be NULL), st_reset_tuning restores the shipped defaults; the test-suite asserts the state is at the defaults after every test.
+ * Timing-only ablations (results invalid) are not switches: they exist only as -D constants that the Makefile never sets. */
+int st_set_tuning(int code);
 int st_get_tuning(int* out, int n);
 int st_tuning_defaults(int* out, int n);
 int st_reset_tuning(void);
@@ -103,10 +105,9 @@ int st_reset_tuning(void);
  * wide autoencoder path -- T > 32 or OT > 16, e.g. the 65536-sample window -- ran fp32 Linear layers for odd batches; its weight-gradient GEMMs now take
  * 16-deep k-tiles when B * 528 is 16 mod 32).  Kept so that callers assert the arithmetic instead of assuming it (StepEngine.effective_dtype). */
 int st_effective_prec(const st_dims* d);
-/* Timing-only ablation switches for diagnostics (bit0: skip k-loop loads/stores, bit1: skip barriers, bit2: skip MFMAs);
- * results are INVALID when non-zero.  Never set by the product path. */
+/* The library has no run-time ablations (build one with EXTRA=-DST_GEMM_ABLATE=<bits>, -DST_AE_ABLATE=..., -DST_PL_ABLATE=..., -DST_G128_ABLATE=...):
+ * accepts 0, anything else is ST_ERR_ARG.  Kept for callers that pass an ablation argument through. */
 int st_set_debug(int v);
-int st_debug_read_stage_cycles(unsigned long long* out32);   /* diagnostics: s_memtime per stage of ae_bwd (st_set_debug(256)) */
 
 /* Optional per-kernel HIP-event profiling of the fused entry points (off by default; used by
  * bench.py's roofline leg outside the timed region).  st_profile_report fills buf with
@@ -223,7 +224,7 @@ size_t st_ae_bwd_ws_floats(const st_dims* d);
  * layers, the forward kernel KEEPS the post-ELU activations of both nets -- what the reference's autograd keeps (nn_proc.py:77-126) -- in the
  * autoencoder workspace behind the gradient partials, and the backward reads them instead of recomputing the forward chain.  Returns the bytes the
  * forward writes (and the backward reads back) per call: 2 nets x B * ceil(F / 16) row groups x 17 KB (294 MB at B = 256); 0 where the path is not
- * taken (16-bit autoencoder layers, wide geometries, st_set_tuning(8200)).  st_ae_bwd on its own (no forward in the same workspace) recomputes. */
+ * taken (16-bit autoencoder layers, wide geometries, the recompute switch g_ae_save = 0).  st_ae_bwd on its own (no forward in the same workspace) recomputes. */
 size_t st_ae_kept_activation_bytes(const st_dims* d);
 
 /* Backward of nn_proc.py:309-310: dG[B*T,KP] (d re | d im) from (re,im,dmag,dphs). */

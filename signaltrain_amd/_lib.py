@@ -45,7 +45,6 @@ SIGNATURES = {
     "st_reset_tuning": (_i, []),
     "st_effective_prec": (_i, [_D]),
     "st_set_debug": (_i, [_i]),
-    "st_debug_read_stage_cycles": (_i, [C.POINTER(C.c_uint64)]),
     "st_profile_enable": (_i, [_i]),
     "st_profile_report": (_i, [C.c_char_p, _i]),
     "st_geometry": (_i, [C.c_double, C.c_double, _i, _i, _i, _D]),

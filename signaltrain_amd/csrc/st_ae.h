@@ -628,14 +628,6 @@ ae_inner_fwd_kernel(const float* __restrict__ H1m, const float* __restrict__ H1p
 // dW/db (packed like the parameters): run-to-run identical bits; ae_grad_reduce_kernel sums the workgroups.
 constexpr int SP = 20;                 // scratch pitch (floats): 16 rows + 4, keeps rows 16-B aligned
 
-// Diagnostics only (st_set_debug bit 8): wave 0 of workgroup (0,0) accumulates s_memtime deltas per kernel stage.
-__device__ unsigned long long g_ae_stage_cycles[32];
-// Stage timers exist only in the TIMED instantiation.  They must not be a run-time branch of the production kernel:
-// a basic-block boundary between an MFMA chain and the first v_accvgpr_read of its result escapes the compiler's
-// MFMA->VALU hazard padding (measured: the last k-step of layer 5 missing from accumulator element 3), hence the
-// explicit wait states ahead of the branch in the TIMED build.
-#define ST_T(i_) do { if constexpr (TIMED) { __builtin_amdgcn_sched_barrier(0); asm volatile("s_nop 15\n\ts_nop 15"); __builtin_amdgcn_sched_barrier(0); if (timing) { const unsigned long long t1_ = __builtin_amdgcn_s_memtime(); if (lane == 0) g_ae_stage_cycles[i_] += t1_ - t0_; t0_ = __builtin_amdgcn_s_memtime(); } } } while (0)
-
 // ---------------------------------------------------------------------------------------------------------
 // Weight fragments in registers.  Left to itself the compiler issues each MFMA's LDS weight fetch just before
 // the MFMA (one s_waitcnt per MFMA: with one wave per SIMD the kernel was LDS-latency-bound).  These helpers burst-load
@@ -861,7 +853,7 @@ constexpr int ae_bwd_lds_floats(int nw) { return (CL::BWD_TOTAL + nw * AE_BWD_SC
 // ELU' needs only the OUTPUT of ELU).  A third of the kernel's MFMAs, the ELU transcendentals and the forward fragment reads go; with nothing left at the top
 // of a group to hide a memory round trip behind, EVERY per-group input is loaded one full group ahead and IN PLACE: right behind the last use of a register
 // set in this group, the same registers are refilled for the next one (no second buffer, no copies).
-template <int NW, bool TIMED, bool INNER = false, int BF = 0, int VAR = 1, bool SAVED = false>      // BF: 16-bit operands in all Linear-layer products (ST_PREC_*_ALL)
+template <int NW, bool INNER = false, int BF = 0, int VAR = 1, bool SAVED = false>      // BF: 16-bit operands in all Linear-layer products (ST_PREC_*_ALL)
 __global__ void __launch_bounds__(NW * 64, 1)
 ae_bwd_kernel(const float* __restrict__ mag, const float* __restrict__ phs, const float* __restrict__ knobs,
               const float* __restrict__ ae_m, const float* __restrict__ ae_p, const AEOffsets go, const int PG,
@@ -871,13 +863,11 @@ ae_bwd_kernel(const float* __restrict__ mag, const float* __restrict__ phs, cons
               const int B, const int T, const int OT, const int F, const int K, const int KP,
               const int to_lo, const int to_hi,      // live synthesis frames: dAA rows outside are treated as zero
               const int nslab, const size_t slab,     // dAA arrives as split-K slabs of the synthesis dgrad GEMM
-              const int dbg, const float* __restrict__ sv = nullptr)      // SAVED: the kept activations ([net][group][17 tiles][lane] float4)
+              const float* __restrict__ sv = nullptr)      // SAVED: the kept activations ([net][group][17 tiles][lane] float4)
 {
     static_assert(!SAVED || (!INNER && BF == 0), "the kept-activation backward exists for the fused fp32 geometries");
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int ae = blockIdx.y;
-    const bool timing = TIMED && (dbg & 256) && blockIdx.x == 0 && blockIdx.y == 0 && (threadIdx.x >> 6) == 0;
-    unsigned long long t0_ = timing ? __builtin_amdgcn_s_memtime() : 0ull;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int g = lane >> 4, c = lane & 15;
     float* lw = lds;                                   // forward images + biases, then the dgrad images (CL)
@@ -1004,7 +994,6 @@ ae_bwd_kernel(const float* __restrict__ mag, const float* __restrict__ phs, cons
     }
 
     for (; grp < ngroups; grp += gstride) {
-        ST_T(16);
         asm volatile("" ::: "memory");      // keep the (loop-invariant) LDS weight fetches inside the loop
         const int b = grp / gpw, f = (grp - b * gpw) * 16 + c;
         const bool fv = f < F;
@@ -1035,7 +1024,6 @@ ae_bwd_kernel(const float* __restrict__ mag, const float* __restrict__ phs, cons
         if constexpr (!INNER) load_v(gnext, vn);
         load_kn(gnext, knn, knTn);
 #endif
-        ST_T(0);
 
         // ------------------------------------------------------------------ forward recompute (D layout)
         // Rolling fragment prefetch: each stage first issues the LDS reads of the NEXT layer's fragments, then runs its own
@@ -1068,9 +1056,7 @@ ae_bwd_kernel(const float* __restrict__ mag, const float* __restrict__ phs, cons
             ST_FENCE();
             fwdD_fr<4, 2, BF>(fr1, lw + CL::B0, vr, h1, g);
         }
-        ST_T(1);
         f32x4 fr3[1 * 2]; frags_fwd<1, 2, CL::O2, BF>(fr3, lw + CL::A2, g, c); ST_FENCE(); fwdD_fr<2, 4, BF>(fr2, lw + CL::B1, h1, h2, g);
-        ST_T(2);
         f32x4 fr4[1 * 1]; frags_fwd<1, 1, CL::O3, BF>(fr4, lw + CL::A3, g, c); ST_FENCE(); fwdD_fr<1, 2, BF>(fr3, lw + CL::B2, h2, h3, g);
         f32x4 fr5[1 * 2]; frags_fwd<1, 2, CL::O4, BF>(fr5, lw + CL::A4, g, c); ST_FENCE(); fwdD_fr<1, 1, BF>(fr4, lw + CL::B3, h3, h4, g);
         f32x4 fr6[1 * 1]; frags_fwd<1, 1, CL::O5, BF>(fr6, lw + CL::A5, g, c); ST_FENCE();
@@ -1078,13 +1064,10 @@ ae_bwd_kernel(const float* __restrict__ mag, const float* __restrict__ phs, cons
             const f32x4 hk[2] = {h4[0], kn};                                 // knob features 16 + 4g + r
             fwdD_fr<1, 2, BF>(fr5, lw + CL::B4, hk, h5, g);
         }
-        ST_T(3);
         f32x4 fr7[2 * 1]; frags_fwd<2, 1, CL::O6, BF>(fr7, lw + CL::A6, g, c); ST_FENCE(); fwdD_fr<1, 1, BF>(fr6, lw + CL::B5, h5, h6, g);
         f32x4 fr8[4 * 2]; frags_fwd<4, 2, CL::O7, BF>(fr8, lw + CL::A7, g, c); ST_FENCE(); fwdD_fr<2, 1, BF>(fr7, lw + CL::B6, h6, h7, g);
-        ST_T(4);
         if constexpr (!INNER) frags_fwd<1, 4, CL::O8, BF>(fr9, lw + CL::A8, g, c);
         ST_FENCE(); fwdD_fr<4, 2, BF>(fr8, lw + CL::B7, h7, h8, g);
-        ST_T(5);
         }
         // ---- d out (D layout: t' = 4g + r), part A: everything that does not need e9 -- polar->rect backward of nn_proc.py:322-326 and
         // the L1 term of loss_functions.py:36 -- sits in the SAME scheduling region as the layer-9 MFMAs (one dependent chain of 16,
@@ -1120,7 +1103,6 @@ ae_bwd_kernel(const float* __restrict__ mag, const float* __restrict__ phs, cons
             }
             ST_FENCE();
         }
-        ST_T(6);
         // ---- d out, part B: ELU'(a9) and the skip / residual tails
         if constexpr (!INNER) {
 #pragma unroll
@@ -1169,27 +1151,22 @@ ae_bwd_kernel(const float* __restrict__ mag, const float* __restrict__ phs, cons
 #pragma unroll
             for (int ot = 0; ot < 4; ++ot) da8[ot] = dh8[ot];
             mul_elu_grad<4>(da8, h8); to_T<4>(XD, da8, daT8, g, c);
-            ST_T(7);
         } else {
             // layer 9 (64 -> OT): d a9 transposed through the wave's scratch
             f32x4 daT9[1], fd9[4 * 1];
             frags_dgrad<1, 4, CL::I8, BF>(fd9, lw + CL::G8, g, c);
             daT9[0] = *reinterpret_cast<const f32x4*>(Ys + c * SP + 4 * g);
-            ST_T(7);
             ST_BWD_STAGE(1, 4, fd9, da9, daT9, h8, hT8, da8, daT8, rW9, rb9, (frags_dgrad<4, 2, CL::I7, BF>(fd8, lw + CL::G7, g, c)))
             ST_REFILL(sv_load(svq, lane16, 12, s_h8));
         }
-        ST_T(8);
         // layer 8 (32 -> 64)
         tt_t hT7[2]; f32x4 da7[2], daT7[2], fd7[1 * 2];
         ST_BWD_STAGE(4, 2, fd8, da8, daT8, h7, hT7, da7, daT7, rW8, rb8, (frags_dgrad<2, 1, CL::I6, BF>(fd7, lw + CL::G6, g, c)))
         ST_REFILL(sv_load(svq, lane16, 10, s_h7));
-        ST_T(9);
         // layer 7 (16 -> 32)
         tt_t hT6[1]; f32x4 da6[1], daT6[1], fd6[1];
         ST_BWD_STAGE(2, 1, fd7, da7, daT7, h6, hT6, da6, daT6, rW7, rb7, (frags_dgrad<1, 1, CL::I5, BF>(fd6, lw + CL::G5, g, c)))
         ST_REFILL(sv_load(svq, lane16, 9, s_h6));
-        ST_T(10);
         // layer 6 (16 -> 16)
         tt_t hT5[1]; f32x4 da5[1], daT5[1], fd5[1];
         ST_BWD_STAGE(1, 1, fd6, da6, daT6, h5, hT5, da5, daT5, rW6, rb6, (frags_dgrad<1, 1, CL::I4, BF>(fd5, lw + CL::G4, g, c)))
@@ -1209,12 +1186,10 @@ ae_bwd_kernel(const float* __restrict__ mag, const float* __restrict__ phs, cons
         tt_t hT3[1]; f32x4 da3[1], daT3[1], fd3[2 * 1];
         ST_BWD_STAGE(1, 1, fd4, da4, daT4, h3, hT3, da3, daT3, rW4, rb4, (frags_dgrad<1, 2, CL::I2, BF>(fd3, lw + CL::G2, g, c)))
         ST_REFILL(sv_load(svq, lane16, 6, s_h3));
-        ST_T(11);
         // layer 3 (32 -> 16)
         tt_t hT2[2]; f32x4 da2[2], daT2[2], fd2[4 * 2];
         ST_BWD_STAGE(1, 2, fd3, da3, daT3, h2, hT2, da2, daT2, rW3, rb3, (frags_dgrad<2, 4, CL::I1, BF>(fd2, lw + CL::G1, g, c)))
         ST_REFILL(sv_load(svq, lane16, 4, s_h2));
-        ST_T(12);
         // layer 2 (64 -> 32)
         tt_t hT1[4]; f32x4 da1[4], daT1[4], fd1[2 * 4];
         if constexpr (INNER) {                     // dA1 goes back to memory for the layer-1 GEMMs
@@ -1231,7 +1206,6 @@ ae_bwd_kernel(const float* __restrict__ mag, const float* __restrict__ phs, cons
             ST_BWD_STAGE(2, 4, fd2, da2, daT2, h1, hT1, da1, daT1, rW2, rb2, (frags_dgrad<4, 2, CL::I0, BF>(fd1, lw + CL::G0, g, c)))
             ST_REFILL(sv_load(svq, lane16, 0, s_h1));
         }
-        ST_T(13);
         // layer 1 (T -> 64): input rows transposed through the wave's scratch
         f32x4 vT[2], dv[2];
         if constexpr (!INNER) {
@@ -1244,7 +1218,6 @@ ae_bwd_kernel(const float* __restrict__ mag, const float* __restrict__ phs, cons
 #undef ST_BWD_STAGE
 #undef ST_PIPE
 #undef ST_REFILL
-        ST_T(14);
         // Round 6: the NEXT group's input rows / knobs are taken over HERE, ahead of this group's stores.  Behind them (as until round 5) the wait for these
         // loads -- the memory counter is in-order and counts stores too -- also waited for the write acknowledgements of the stores just issued: one exposed
         // round trip per group, the "loads issue" stage that stayed at ~10 % of a group through rounds 2-5 whatever was done to the loads themselves.
@@ -1253,7 +1226,6 @@ ae_bwd_kernel(const float* __restrict__ mag, const float* __restrict__ phs, cons
             vr[0] = vn[0]; vr[1] = vn[1];
         }
         mask_kn(knn, knTn); kn = knn; knT = knTn;
-        ST_T(17);
         // ------------------------------------------------------------------ d input rows (+ skip / residual tails)
         if constexpr (!INNER) {
         // Materialise the accumulators in VGPRs HERE, in the block of the MFMAs that produce them: the stores below sit in
@@ -1282,7 +1254,6 @@ ae_bwd_kernel(const float* __restrict__ mag, const float* __restrict__ phs, cons
 #endif
             }
         }
-        ST_T(15);
     }
     // ---------------------------------------------------------------------- workgroup partial gradients
     // All LDS contents are dead now.  Every wave stores its accumulators into ITS OWN gradient image (dW_l as [o][INp] at

@@ -6,7 +6,7 @@
 // (column = b * FP + f, FP = roundup(F, 16) "virtual bins", pad columns hold zeros).  Then every layer of the MLP is a
 // plain 2-D GEMM on the one MFMA GEMM family (st_gemm.h), with the fusions moved into epilogues:
 //     forward   H_l  [OUT][R] = ELU( W_l [OUT][IN] . H_{l-1} [IN][R] + b_l )            (ActStore / OutStore for layer 9)
-//     dgrad     dA_{l-1}[IN][R] = ( W_l^T . dA_l ) * ELU'(H_{l-1})                        (DgradStore / DvStore for layer 1)
+//     dgrad     dA_{l-1}[IN][R] = ( W_l^T . dA_l ) * ELU'(H_{l-1})                        (layer 1: wide_dv_polar_kernel)
 //     wgrad     dW_l [OUT][IN] = dA_l [OUT][R] . H_{l-1}[IN][R]^T   (K = R, split-K slabs, summed in slab order)
 // The knobs (nn_proc.py:92-93, concatenated after the 16-wide code) are K extra ROWS of the layer-5 input, so layer 5
 // and its weight gradient need no special case.  Weight matrices whose row length is not a multiple of the k-tile
@@ -92,48 +92,8 @@ struct OutStore {          // layer 9 forward (nn_proc.py:113-117, :322): e = EL
     }
 };
 
-struct DgradStore {        // dA_{l-1} = (W_l^T dA_l) * ELU'(h_{l-1}), ELU' from the stored output: h > 0 ? 1 : h + 1
-    float* out; const float* H; int M, R;
-    __device__ void operator()(int m0, int n0, const f32x16 (&acc)[NJ]) const {
-        const int lane = threadIdx.x & 63;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            const int row = m0 + d_row(i, lane);
-            if (row < M) {
-#pragma unroll
-                for (int j = 0; j < NJ; ++j) {
-                    const int col = n0 + 32 * j + (lane & 31);
-                    if (col < R) { const size_t ix = (size_t)row * R + col; out[ix] = acc[j][i] * elu_grad_from_out(H[ix]); }
-                }
-            }
-        }
-    }
-};
-
-struct DvStore {           // gradient w.r.t. the AE input rows, written in the [B][T][F] layout of mag / phs (+ skip / residual tails)
-    float* dv; const float* tail; int T, OT, R, FP, F;
-    __device__ void operator()(int m0, int n0, const f32x16 (&acc)[NJ]) const {
-        const int lane = threadIdx.x & 63;
-        ColInfo ci[NJ]; col_info(ci, n0, lane, R, FP, F);
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            const int row = m0 + d_row(i, lane);
-            if (row < T) {
-#pragma unroll
-                for (int j = 0; j < NJ; ++j) {
-                    if (ci[j].real) {
-                        float v = acc[j][i];
-                        if (row >= T - OT) v += tail[(size_t)(row - (T - OT)) * R + ci[j].col];
-                        dv[((size_t)ci[j].b * T + row) * F + ci[j].f] = v;
-                    }
-                }
-            }
-        }
-    }
-};
-
 // ------------------------------------------------------------------------------------------------ layer-1 data gradient + polar backward
-// Round 3.  At the 65536-sample window the gradient w.r.t. the autoencoder inputs was two generic GEMMs with a scatter epilogue (DvStore:
+// Round 3.  At the 65536-sample window the gradient w.r.t. the autoencoder inputs was two generic GEMMs with a scatter epilogue (
 // 36 us each for 0.75 GFLOP) followed by the polar backward (29 us): dmag / dphs went out to HBM (46 MB) only to be read back.  One kernel now
 // walks 16-row groups like the fused autoencoder kernels: d a1 of both nets in D layout (16 + 16 dwords per lane from the feature-major
 // buffers), W1^T fragments from an LDS dgrad image, one 16-frame output tile at a time

@@ -173,101 +173,76 @@ static int num_cus()
     if (!n) { int dev = 0; (void)hipGetDevice(&dev); hipDeviceProp_t p; if (hipGetDeviceProperties(&p, dev) == hipSuccess) n = p.multiProcessorCount; if (n <= 0) n = 256; }
     return n;
 }
-static int g_dbg = 0;   // timing-only ablation switches (bench/diagnostics); results are invalid when non-zero
-extern "C" int st_set_debug(int v) { g_dbg = v; return ST_OK; }
-namespace sta { extern __device__ unsigned long long g_ae_stage_cycles[32]; }
-// Diagnostics: read (and clear) the per-stage s_memtime accumulators of ae_bwd_kernel (st_set_debug(256)).
-extern "C" int st_debug_read_stage_cycles(unsigned long long* out32);
-static int g_dp_inline = 1;  // st_dp_train_step: 1 = the last (exposed) exchange is issued in line on the compute stream (round 6), 0 = on the communicator stream between two hand-offs (st_set_tuning(8300 / 8301))
-static int g_ae_save = 1;    // fused geometries, fp32 autoencoder layers: 1 = the forward kernel keeps the activations and the backward reads them (round 6), 0 = the backward recomputes them (st_set_tuning(8200 / 8201))
-static int g_ae_split = -1;  // autoencoder backward of the fused geometries: 0 = the single kernel (st_set_tuning(8000)), 1 = the two kernels of st_ae_split.h (8001),
-                             // -1 = by precision (8002, default): fp32 -> single (179.5 us against 87.0 + 92.4 us at B = 256 -- equal: the fp32 MFMA holds the vector ALUs, a partner
+// The product library has no run-time ablations: a timing-only ablation exists only as a -D constant the Makefile never sets (ST_GEMM_ABLATE, ST_AE_ABLATE,
+// ST_PL_ABLATE, ST_G128_ABLATE).  The entry stays for callers that pass their --ablate argument through; it accepts 0 alone.
+extern "C" int st_set_debug(int v) { return v == 0 ? ST_OK : st_fail(ST_ERR_ARG, "st_set_debug(%d): the product library has no run-time ablations (build with -DST_*_ABLATE=bits)", v); }
+static int g_dp_inline = 1;  // st_dp_train_step: 1 = the last (exposed) exchange is issued in line on the compute stream (round 6), 0 = on the communicator stream between two hand-offs
+static int g_ae_save = 1;    // fused geometries, fp32 autoencoder layers: 1 = the forward kernel keeps the activations and the backward reads them (round 6), 0 = the backward recomputes them
+static int g_ae_split = -1;  // autoencoder backward of the fused geometries: 0 = the single kernel, 1 = the two kernels of st_ae_split.h,
+                             // -1 = by precision (default): fp32 -> single (179.5 us against 87.0 + 92.4 us at B = 256 -- equal: the fp32 MFMA holds the vector ALUs, a partner
                              // wave has nothing to overlap with -- and the split moves 66 MB more per step: h4 / d a4 / tails hand-over); 16-bit Linear layers -> split (the
                              // matrix pipe is then a separate unit and two waves per SIMD overlap it with the ELU / conversion / transpose work: 102 -> 48 + 44 us at
                              // B = 256, 354 -> 152 + 138 us at B = 1024, bf16_all)
-static int g_ae32 = 1;       // 16-bit autoencoder forward of the fused geometries on 32-row groups / v_mfma_f32_32x32x16 (st_ae32.h); 0 = the 16-row kernel of st_ae.h (st_set_tuning(8100 + n))
+static int g_ae32 = 1;       // 16-bit autoencoder forward of the fused geometries on 32-row groups / v_mfma_f32_32x32x16 (st_ae32.h); 0 = the 16-row kernel of st_ae.h
 static int g_pl_bf16 = 0;    // ST_PREC_BF16*: analysis / frames GEMMs on the plane kernel with ONE plane (bf16 copies of the bases, k-chunk-major).  MEASURED SLOWER at B = 256
-                             // (analysis 53.8 vs 49.8 us + 12 us for the copies): three MFMAs per 16-deep k-tile and barrier; needs a 64-deep tile   (st_set_tuning(9400 + n))
-static int g_wg_split = 0;   // ST_PREC_F32X3: weight-gradient GEMMs on the in-kernel three-plane split instead of the fp32 MFMA kernel (see ST_GEMM_WG)   (st_set_tuning(9300 + n))
-static int g_pl_dgrad = 0;   // ST_PREC_F32X3: synthesis data gradient on the plane kernel (measured slower than the fp32 MFMA kernel at B = 256: 57 vs 45 us)   (st_set_tuning(9200 + n))
+                             // (analysis 53.8 vs 49.8 us + 12 us for the copies): three MFMAs per 16-deep k-tile and barrier; needs a 64-deep tile
+static int g_wg_split = 0;   // ST_PREC_F32X3: weight-gradient GEMMs on the in-kernel three-plane split instead of the fp32 MFMA kernel (see ST_GEMM_WG)
+static int g_pl_dgrad = 0;   // ST_PREC_F32X3: synthesis data gradient on the plane kernel (measured slower than the fp32 MFMA kernel at B = 256: 57 vs 45 us)
 static int g_pl_shape = 3;   // analysis plane GEMM tile (ST_PREC_F32X3): 0 = 4 waves x (32 x 96) [91.9 us], 1 = 2 waves x (64 x 96) [117], 2 = 4 waves x (64 x 96) [112],
-                             // 3 = 8 waves x (32 x 96) = 256 x 96, one workgroup per CU: a quarter less L2 traffic at the same two waves per SIMD [88.1]   (st_set_tuning(9100 + n))
-static int g_g16 = 1;        // 16-bit configurations: the fused step's GEMMs on pre-rounded 16-bit operands (st_gemm16.h); 0 = gemm_half_kernel on fp32 operands (st_set_tuning(9600), diagnostics)
-static int g_g16_bk = 64;    // k-tile depth of its TN kernel (st_set_tuning(9632 / 9664))
-static int g_g16_dma = 0;    // bit 0 / bit 1: its analysis forward / synthesis data-gradient GEMM on the LDS-DMA kernel gemm16_nt256_kernel (st_set_tuning(9690 + bits)).  MEASURED EQUAL to
+                             // 3 = 8 waves x (32 x 96) = 256 x 96, one workgroup per CU: a quarter less L2 traffic at the same two waves per SIMD [88.1]
+static int g_g16 = 1;        // 16-bit configurations: the fused step's GEMMs on pre-rounded 16-bit operands (st_gemm16.h); 0 = gemm_half_kernel on fp32 operands
+static int g_g16_dma = 0;    // bit 0 / bit 1: its analysis forward / synthesis data-gradient GEMM on the LDS-DMA kernel gemm16_nt256_kernel.  MEASURED EQUAL to
                              // gemm16_nt_kernel (analysis forward, bf16, B = 256 / 1024: 34.2 / 138.6 us against 35.5 / 137.2): both deliver ~20 B/clk/CU from L2 to LDS, see st_gemm16.h
-static int g_g16_abl = 0;    // TIMING ONLY (results invalid): analysis forward epilogue ablation, bit0 no mag/phs, bit1 no re/im, bit2 frame rows at 16-byte aligned (wrong) offsets (st_set_tuning(9680 + bits))
-static int g_g16_split = 0;  // k-slices of its weight-gradient GEMMs (0: by residency; st_set_tuning(9700 + n))
-static int g_nt128 = 1;      // fp32 synthesis frames / data-gradient GEMMs on the 128 x 128-tile NT kernel (st_gemm_tn.h); 0 = gemm_kernel<2, ...> (st_set_tuning(9950), diagnostics)
-static int g_tn128 = 1;      // weight-gradient GEMMs on the 128 x 128-tile kernel (st_gemm_tn.h) where it applies; 0 = gemm_kernel<3, ...> (st_set_tuning(9500), diagnostics); 2 = its round-3 k-tile loop (st_set_tuning(9580))
-static int g_tn_bk = 32;     // its k-tile depth (st_set_tuning(9516 / 9532))
+static int g_nt128 = 1;      // fp32 synthesis frames / data-gradient GEMMs on the 128 x 128-tile NT kernel (st_gemm_tn.h); 0 = gemm_kernel<2, ...>
+static int g_tn128 = 1;      // weight-gradient GEMMs on the 128 x 128-tile kernel (st_gemm_tn.h) where it applies; 0 = gemm_kernel<3, ...>; 2 = its round-3 k-tile loop
 static int g_tn_fm = 3;      // round 5: frame-major reduction order + per-tile-column row ranges (structural zeros skipped) in the 128 x 128 weight-gradient GEMMs: bit 0 synthesis
-                             // (25 % of its reduction rows are cropped taps: 41.7 -> 37.0 us), bit 1 analysis (7.6 %: 113.8 -> 109.5 us)   (st_set_tuning(9540 + bits), diagnostics)
+                             // (25 % of its reduction rows are cropped taps: 41.7 -> 37.0 us), bit 1 analysis (7.6 %: 113.8 -> 109.5 us)
 static int g_g16_crop = 15;  // round 5, 16-bit operand pipeline: structural zeros skipped (frame-major rows): bit 0 frames GEMM (dead tile columns return), bit 1 data gradient (live taps per tile row),
-                             // bit 2 / bit 3 synthesis / analysis weight gradient (reduction rows per tile column)   (st_set_tuning(9560 + bits), diagnostics)
-static int g_frs_nt = 1;     // synthesis frames GEMM against the transposed fold (both operands K-contiguous); 0 = the k-major form (st_set_tuning(9000), diagnostics)
-static int g_xt = 0;       // 1: M/N-contiguous operands staged k-quad-major (st_gemm.h XT; st_set_tuning(7001), diagnostics).  MEASURED SLOWER at B=256 although
+                             // bit 2 / bit 3 synthesis / analysis weight gradient (reduction rows per tile column)
+static int g_frs_nt = 1;     // synthesis frames GEMM against the transposed fold (both operands K-contiguous); 0 = the k-major form
+static int g_xt = 0;       // 1: M/N-contiguous operands staged k-quad-major (st_gemm.h XT).  MEASURED SLOWER at B=256 although
                            // conflict-free with a third fewer LDS cycles: analysis wgrad 173 vs 145 us, synthesis frames 63 vs 60 us (16 more prefetch
                            // registers -> 4 instead of 4.5 waves per SIMD, and 16 v_mov per micro-tile): the k-major staging stays the default
 static const int NORM_E_PARTIALS = 32;     // |g| partials of the autoencoder gradient range (st_dims.clip_all) when they come from l1_partial_kernel
 static const int NORM_E_MAX = 4096;        // room for the per-block partials of the reducing kernels themselves (post_ae_kernel / wide_grad_finish_kernel)
-static int g_wide_pair = 1;  // wide geometries, 16-bit: the layer-1 / layer-9 GEMMs of the two autoencoders as ONE launch each (gemm_half_pair_kernel); 0 = two launches (st_set_tuning(9960 + n), diagnostics)
-static int g_wide_direct = 1; // wide geometries: the analysis epilogue writes the wide autoencoder path's feature-major input itself (no wide_in_kernel in the fused step); 0 = copy kernel (st_set_tuning(9970 + n), diagnostics)
-static int g_wide_dvp = 1;   // wide geometries: layer-1 data gradient (+ polar backward) as one fused kernel; 0 = two GEMMs + polar_bwd (st_set_tuning(9900), diagnostics)
-static int g_nt_mi = 0;     // fp32 NT x NT GEMMs with 64 x 96 wave tiles (MI = 2): 0 off; bit 0 analysis forward <4,16,2>, bit 1 <2,32,2>, bit 2 frames / dgrad <2,16,2>  (st_set_tuning(9800 + n), experiments)
+static int g_wide_direct = 1; // wide geometries: the analysis epilogue writes the wide autoencoder path's feature-major input itself (no wide_in_kernel in the fused step); 0 = copy kernel
 static int g_an_bk = 32;   // k-tile depth of the analysis forward GEMM (see ST_GEMM_AN)
 static int g_bk = 16;   // k-tile depth of the GEMM family (16: 36 KB LDS/WG -> 4 WGs/CU; 32: 64 KB -> 2 WGs/CU)
-static int g_wg_mode_set(int v);
-static int g_wsplit_max = 16, g_wsplit_div = 200, g_an_waves = 4, g_syn_split = 3, g_frs_split = 3, g_wide_fused = 1, g_wsplit_half = 0;      // frames: 3, 4 measured equal, 6 slower (only 66 k-tiles to split)
-extern "C" int st_set_tuning(int bk)
+static int g_wg_mode = 0;    // weight-gradient GEMMs: 0 = three waves share a 96 x 96 tile (32 x 96 strips), 2 = the same on the k-quad-major staging (see g_xt)
+// The diagnostic switches above as ONE readable state, in st_get_tuning's order, with their shipped defaults.  The product path never sets them;
+// tests/conftest.py asserts after every test that the state is back at the defaults (a wrong default can then not ship unnoticed, and a test cannot
+// leak a switch into the next one).
+#define ST_TUNING_LIST(X) X(g_ae_split, -1) X(g_ae_save, 1) X(g_dp_inline, 1) X(g_pl_bf16, 0) X(g_wg_split, 0) X(g_pl_dgrad, 0) X(g_pl_shape, 3) X(g_g16, 1) X(g_g16_dma, 0) \
+    X(g_nt128, 1) X(g_tn128, 1) X(g_frs_nt, 1) X(g_xt, 0) X(g_an_bk, 32) X(g_bk, 16) X(g_wg_mode, 0) X(g_ae32, 1) X(g_wide_direct, 1) X(g_tn_fm, 3) X(g_g16_crop, 15)
+// ... and the WHOLE interface that sets them: code first + i (0 <= i < count) stores value + i into *var (and into *also, where given).  A code that is not
+// listed here is an error and changes nothing.
+static const struct { int first, count; int* var; int value; int* also; } k_tuning_codes[] = {
+    {16, 1, &g_an_bk, 16, &g_bk}, {32, 1, &g_an_bk, 32, &g_bk},      // k-tile depth of the fp32 GEMM family
+    {100, 1, &g_wg_mode, 0, nullptr}, {102, 1, &g_wg_mode, 2, nullptr},
+    {7000, 2, &g_xt, 0, nullptr},
+    {8000, 2, &g_ae_split, 0, nullptr}, {8002, 1, &g_ae_split, -1, nullptr},      // single kernel / two kernels / by precision
+    {8100, 2, &g_ae32, 0, nullptr},
+    {8200, 2, &g_ae_save, 0, nullptr},
+    {8300, 2, &g_dp_inline, 0, nullptr},
+    {9000, 2, &g_frs_nt, 0, nullptr},
+    {9100, 1, &g_pl_shape, 0, nullptr}, {9103, 1, &g_pl_shape, 3, nullptr},
+    {9200, 2, &g_pl_dgrad, 0, nullptr},
+    {9300, 2, &g_wg_split, 0, nullptr},
+    {9400, 2, &g_pl_bf16, 0, nullptr},
+    {9500, 2, &g_tn128, 0, nullptr}, {9580, 1, &g_tn128, 2, nullptr}, {9581, 1, &g_tn128, 1, nullptr},      // 9580: its round-3 k-tile loop (A/B timing, bit-equality test)
+    {9540, 4, &g_tn_fm, 0, nullptr},
+    {9560, 16, &g_g16_crop, 0, nullptr},
+    {9600, 2, &g_g16, 0, nullptr},
+    {9690, 4, &g_g16_dma, 0, nullptr},
+    {9950, 2, &g_nt128, 0, nullptr},
+    {9970, 2, &g_wide_direct, 0, nullptr},
+};
+extern "C" int st_set_tuning(int code)
 {
-#ifdef ST_DIAG      // timing-only ablations (results INVALID by construction): compiled only into diagnostic builds (make EXTRA=-DST_DIAG), never into the product library
-    if (bk >= 96800 && bk < 96928) { g_g16_abl = bk - 96800; return ST_OK; }      // 16-bit analysis GEMM (bits 3..5: its k-loop)
-#else
-    if ((bk >= 96800 && bk < 96928) || (bk >= 9680 && bk < 9690)) return st_fail(ST_ERR_ARG, "st_set_tuning(%d): timing-only ablation, needs a -DST_DIAG build", bk);
-#endif
-    if (bk >= 9970 && bk < 9980) { g_wide_direct = bk - 9970; return ST_OK; }
-    if (bk >= 9960) { g_wide_pair = bk - 9960; return ST_OK; }
-    if (bk >= 9950 && bk < 9960) { g_nt128 = bk - 9950; return ST_OK; }
-    if (bk >= 9900) { g_wide_dvp = bk - 9900; return ST_OK; }
-    if (bk >= 9800) { g_nt_mi = bk - 9800; return ST_OK; }
-    if (bk >= 9700) { g_g16_split = bk - 9700; return ST_OK; }
-    if (bk >= 9690 && bk < 9700) { g_g16_dma = bk - 9690; return ST_OK; }
-#ifdef ST_DIAG
-    if (bk >= 9680 && bk < 9690) { g_g16_abl = bk - 9680; return ST_OK; }
-#endif
-    if (bk >= 9600) { const int v = bk - 9600; if (v == 32 || v == 64) g_g16_bk = v; else g_g16 = v; return ST_OK; }
-    if (bk >= 9560 && bk < 9576) { g_g16_crop = bk - 9560; return ST_OK; }
-    if (bk == 9580 || bk == 9581) { g_tn128 = bk == 9580 ? 2 : 1; return ST_OK; }      // 9580: the 128 x 128-tile weight-gradient kernel on its round-3 k-tile loop (A/B timing, bit-equality test); 9581: the pipelined loop (default)
-    if (bk >= 9540 && bk < 9544) { g_tn_fm = bk - 9540; return ST_OK; }
-    if (bk >= 9500) { const int v = bk - 9500; if (v == 16 || v == 32) g_tn_bk = v; else g_tn128 = v; return ST_OK; }
-    if (bk >= 9400) { g_pl_bf16 = bk - 9400; return ST_OK; }
-    if (bk >= 9300) { g_wg_split = bk - 9300; return ST_OK; }
-    if (bk >= 9200) { g_pl_dgrad = bk - 9200; return ST_OK; }
-    if (bk >= 9100) { g_pl_shape = bk - 9100; return ST_OK; }
-    if (bk >= 9000) { g_frs_nt = bk - 9000; return ST_OK; }
-    if (bk >= 8100 && bk < 8110) { g_ae32 = bk - 8100; return ST_OK; }           // 8100 / 8101: 16-bit autoencoder forward on 16-row / 32-row groups (st_ae32.h)
-    if (bk == 8300 || bk == 8301) { g_dp_inline = bk - 8300; return ST_OK; }      // last exchange of the data-parallel step: communicator stream / in line
-    if (bk == 8200 || bk == 8201) { g_ae_save = bk - 8200; return ST_OK; }      // autoencoder backward: recompute / read the kept activations
-    if (bk >= 8000) { g_ae_split = bk == 8002 ? -1 : bk - 8000; return ST_OK; }     // 8000 / 8001 / 8002: single-kernel / split autoencoder backward / by precision
-    if (bk >= 7000) { g_xt = bk - 7000; return ST_OK; }
-    if (bk >= 6000) { g_wsplit_half = bk - 6000; return ST_OK; }  // 6000 + n: split-K of the half (one-basis) analysis weight-gradient GEMMs of st_loss_backward_stage (0: as the full GEMM)
-    if (bk >= 5000) { g_wide_fused = bk - 5000; return ST_OK; }   // 5000 / 5001: wide AE path all-GEMM / fused inner layers
-    if (bk >= 4000) { g_frs_split = bk - 4000; return (g_frs_split >= 1 && g_frs_split <= 6) ? ST_OK : st_fail(ST_ERR_ARG, "frames split must be 1..6"); }
-    if (bk >= 3000) { g_syn_split = bk - 3000; return ST_OK; }    // 3000 + n: synthesis split-K (<= 3: consumers sum at most 3 slabs)
-    if (bk >= 2000) { g_an_waves = bk - 2000; return ST_OK; }     // 2000 + n: waves per workgroup of the analysis forward GEMM
-    if (bk >= 1000) { g_wsplit_div = bk - 1000; return ST_OK; }  // 1000 + n: rows per weight-gradient k-slice (diagnostics)
-    if (bk >= 200) { g_wsplit_max = bk - 200; return ST_OK; }      // 200 + n: cap of the weight-gradient split-K (diagnostics)
-    if (bk >= 100) return g_wg_mode_set(bk - 100);           // 100 / 101: weight-gradient tile mode (diagnostics)
-    if (bk != 16 && bk != 32) return st_fail(ST_ERR_ARG, "bk must be 16 or 32"); g_bk = bk; g_an_bk = bk; return ST_OK;
+    for (const auto& t : k_tuning_codes)
+        if (code >= t.first && code < t.first + t.count) { *t.var = t.value + (code - t.first); if (t.also) *t.also = *t.var; return ST_OK; }
+    return st_fail(ST_ERR_ARG, "st_set_tuning(%d): no such code", code);
 }
-// The diagnostic switches above as ONE readable state: st_get_tuning() reports them in a fixed order, st_reset_tuning() restores the shipped
-// defaults.  The product path never sets them; tests/conftest.py asserts after every test that the state is back at ST_TUNING_DEFAULTS
-// (a wrong default can then not ship unnoticed, and a test cannot leak a switch into the next one).
-#define ST_TUNING_LIST(X) X(g_dbg, 0) X(g_ae_split, -1) X(g_ae_save, 1) X(g_dp_inline, 1) X(g_pl_bf16, 0) X(g_wg_split, 0) X(g_pl_dgrad, 0) X(g_pl_shape, 3) X(g_g16, 1) X(g_g16_bk, 64) X(g_g16_dma, 0) \
-    X(g_g16_abl, 0) X(g_g16_split, 0) X(g_nt128, 1) X(g_tn128, 1) X(g_tn_bk, 32) X(g_frs_nt, 1) X(g_xt, 0) X(g_wide_pair, 1) X(g_wide_dvp, 1) X(g_nt_mi, 0) X(g_an_bk, 32) \
-    X(g_bk, 16) X(g_wsplit_max, 16) X(g_wsplit_div, 200) X(g_an_waves, 4) X(g_syn_split, 3) X(g_frs_split, 3) X(g_wide_fused, 1) X(g_wsplit_half, 0) X(g_wg_mode, 0) X(g_ae32, 1) X(g_wide_direct, 1) X(g_tn_fm, 3) X(g_g16_crop, 15)
-static int g_wg_mode = 0;
 extern "C" int st_get_tuning(int* out, int n)
 {
     int i = 0;
@@ -301,20 +276,17 @@ static inline float loss_scale_of(const st_dims* d) { return d->loss_scale > 0.f
 #define ST_GEMM_BK(BK_, W_, ...) do { const int ht_ = gemm_ht(d->prec); \
                               if (ht_ == 1) stg::launch_half<W_, 1>(__VA_ARGS__); else if (ht_ == 2) stg::launch_half<W_, 2>(__VA_ARGS__); \
                               else if (ht_ == 3) { ST_TRY((stg::launch_half<W_, 1, 3>(__VA_ARGS__))); } \
-                              else if (g_xt) { if ((BK_) == 16) stg::launch<W_, 16, 1, true>(__VA_ARGS__, g_dbg); else stg::launch<W_, 32, 1, true>(__VA_ARGS__, g_dbg); } \
-                              else if ((BK_) == 16) stg::launch<W_, 16>(__VA_ARGS__, g_dbg); else stg::launch<W_, 32>(__VA_ARGS__, g_dbg); } while (0)
+                              else if (g_xt) { if ((BK_) == 16) stg::launch<W_, 16, true>(__VA_ARGS__); else stg::launch<W_, 32, true>(__VA_ARGS__); } \
+                              else if ((BK_) == 16) stg::launch<W_, 16>(__VA_ARGS__); else stg::launch<W_, 32>(__VA_ARGS__); } while (0)
 #define ST_GEMM(W_, ...) ST_GEMM_BK(g_bk, W_, __VA_ARGS__)
 // the analysis forward GEMM (K = N = 1024, two 4-wave workgroups per CU either way) runs 5 % faster with 32-deep k-tiles
 // (half the barriers); every other GEMM of the step is faster with 16 (more workgroups per CU)
 #define ST_GEMM_AN(W_, ...) ST_GEMM_BK(g_an_bk, W_, __VA_ARGS__)
-// weight-gradient GEMMs: g_wg_mode 0 = three waves share a 96x96 tile (32x96 strips), 1 = one wave per 96x96 tile
-static int g_wg_mode_set(int v) { g_wg_mode = v; return ST_OK; }
 // ST_PREC_F32X3: the weight-gradient GEMMs reduce along the ROWS of both operands (k-major staging, 4x4 register transposes); their
 // in-kernel three-plane split measured slower than the fp32 MFMA kernel (176 vs 141 us, 62 vs 55 us at B = 256), so that precision
 // level keeps them on the fp32 kernel (st_set_tuning(9301) selects the split form).
-#define ST_GEMM_WG(...) do { if (g_wg_mode == 1 && gemm_ht(d->prec) == 0) stg::launch<1, 16, 3>(__VA_ARGS__, g_dbg); \
-                             else if (g_wg_mode == 2 && gemm_ht(d->prec) == 0) stg::launch<3, 16, 1, true>(__VA_ARGS__, g_dbg); \
-                             else if (gemm_ht(d->prec) == 3 && !g_wg_split) stg::launch<3, 16>(__VA_ARGS__, g_dbg); else ST_GEMM(3, __VA_ARGS__); } while (0)
+#define ST_GEMM_WG(...) do { if (g_wg_mode == 2 && gemm_ht(d->prec) == 0) stg::launch<3, 16, true>(__VA_ARGS__); \
+                             else if (gemm_ht(d->prec) == 3 && !g_wg_split) stg::launch<3, 16>(__VA_ARGS__); else ST_GEMM(3, __VA_ARGS__); } while (0)
 // Kernels with > 64 KB of dynamic LDS need the attribute once per (device, kernel); the result is checked (round 1 discarded
 // it behind non-atomic flags: a failure surfaced later as an opaque launch error).
 static int ensure_dyn_lds(const void* fn, const char* name)
@@ -364,7 +336,8 @@ static int ae_bwd_grid(const st_dims* d) { int groups = d->B * (st_kp_of(d->F) /
 // split-K factors.  fp32 MFMA tiles are long serial chains (48 MFMAs x 64 cycles per k-tile per wave), so a GEMM
 // needs >= ~2 waves per SIMD (2048 waves) to overlap its load/LDS phases; the small-M synthesis GEMMs and the
 // 121-tile weight-gradient GEMMs get there by splitting K and summing the slabs in the consumer kernel.
-static int wgrad_split(int R) { int s = R / g_wsplit_div; if (s < 1) s = 1; if (s > g_wsplit_max) s = g_wsplit_max; return s; }
+static const int WSPLIT_ROWS = 200, WSPLIT_MAX = 16;      // reduction rows per weight-gradient k-slice, and the cap of the slice count
+static int wgrad_split(int R) { int s = R / WSPLIT_ROWS; if (s < 1) s = 1; if (s > WSPLIT_MAX) s = WSPLIT_MAX; return s; }
 // ... and never more k-slices than keep all workgroups co-resident: the 3-wave weight-gradient workgroup (25 KB of LDS, 95 registers)
 // fits six to a CU, and a second, partly filled round costs more than the shorter k-chains save (measured sawtooth at B = 256,
 // 121 tiles: 10 / 12 / 16 slices -> 151 / 153 / 160 us incl. the slab reduce; 11, 13 -> 160, 169)
@@ -376,7 +349,7 @@ static int wgrad_split_tiles(int R, int M, int Nc)
     if (fit >= 2) fit &= ~1;                       // even slice counts: odd ones leave a ragged last slice (k-slices are multiples of 32 rows)
     return s < fit ? s : fit;
 }
-static int synth_split(int R) { return R >= 4096 ? 1 : g_syn_split; }   // consumers (ola_loss_kernel, ae_bwd_kernel) sum at most 3 slabs
+static int synth_split(int R) { return R >= 4096 ? 1 : 3; }   // consumers (ola_loss_kernel, ae_bwd_kernel) sum at most 3 slabs
 
 // (the host size functions answer 0 for dims outside the supported family, with the rule in st_last_error(): check_dims)
 extern "C" int st_ae_fwd_partials(const st_dims* d) { return check_dims(d) != ST_OK ? 0 : ae_fwd_grid(d) * ae_fwd_nw(d); }
@@ -398,15 +371,15 @@ extern "C" size_t st_wgrad_ws_floats(const st_dims* d)
     const int s2 = tn_split(d->B * d->T, d->N); if (s2 > s) s = s2;
     return (size_t)s * st_kp_of(d->F) * d->N + (size_t)64 * 2 * d->N;       // + the Nyquist partials of the 128 x 128-tile form
 }
-static size_t synth_wgrad_ws_floats(const st_dims* d) { return st_wgrad_ws_floats(d); }
 // Round 6: a second slab area for the SYNTHESIS weight gradient alone.  In the data-parallel step its slabs are summed on the communicator stream beside the autoencoder
 // backward; with a buffer of their own the analysis weight-gradient GEMM (which reuses the first area) needs no communicator -> compute wait before it starts -- one
-// barrier packet (~6 us of bubble on this stack) less on the compute stream.
-static size_t synth_wgrad_ws_floats(const st_dims* d);      // = st_wgrad_ws_floats(d): every slab-count rule of the fp32 and 16-bit weight-gradient launches is capped by that area's size
+// barrier packet (~6 us of bubble on this stack) less on the compute stream.  Same size as the first: every slab-count rule of the fp32 and 16-bit weight-gradient
+// launches is capped by that area's size.
+static size_t synth_wgrad_ws_floats(const st_dims* d) { return st_wgrad_ws_floats(d); }
 extern "C" int st_synth_slabs(const st_dims* d) { return check_dims(d) != ST_OK ? 0 : synth_split(synth_live_rows(d)); }
 // split-K slabs of the synthesis FRAMES GEMM (summed by ola_loss_kernel, which takes up to 6; the dgrad slabs are summed
 // inside ae_bwd_kernel where every extra slab costs 8 loads per row group, hence the separate, smaller count above)
-static int frames_split(int R) { return R >= 4096 ? 1 : g_frs_split; }
+static int frames_split(int R) { return R >= 4096 ? 1 : 3; }      // 3, 4 measured equal, 6 slower (only 66 k-tiles to split)
 extern "C" int st_synth_frame_slabs(const st_dims* d) { return check_dims(d) != ST_OK ? 0 : frames_split(synth_live_rows(d)); }
 // Wide geometries (T > 32 or OT > 16) run the autoencoders as feature-major GEMMs (st_ae_wide.h) and need workspace
 // for the activations [features][B*FP]; the fused kernels of st_ae.h need none in forward.
@@ -457,7 +430,7 @@ static int ae_split_grid(const st_dims* d) { int g = (ae_fwd_groups(d) + AE_SPLI
 // precisions keep the single kernel.
 // 16-bit operands in the split form were tried (decoder + encoder halves 49 + 45 us against 101 us for the single kernel, the step did not
 // move) and are NOT instantiated: the compiler emitted a cross-block MFMA-result hazard in the 16-bit encoder half (tools/check_mfma_hazards.py).
-static bool ae_use_split(const st_dims* d) { return (g_ae_split < 0 ? ae_ht(d->prec) != 0 : g_ae_split != 0) && !ae_is_wide(d) && !(g_dbg & 256); }
+static bool ae_use_split(const st_dims* d) { return (g_ae_split < 0 ? ae_ht(d->prec) != 0 : g_ae_split != 0) && !ae_is_wide(d); }
 // Round 6: kept activations of the fused fp32 autoencoders ([net][group][17 tiles][64 lanes] float4, st_ae.h): the workspace always has room for them where the
 // autoencoder layers run in fp32 (the tuning switch picks the kernels, not the size); they sit BEHIND the workgroup partials.
 static size_t ae_sv_floats(const st_dims* d) { return (!ae_is_wide(d) && ae_ht(d->prec) == 0) ? (size_t)2 * ae_fwd_groups(d) * sta::AE_SV_TILES * 256 : 0; }
@@ -500,11 +473,7 @@ static int analysis_fwd_impl(const st_dims* d, const float* sig, bool padded, co
     polar_wide_set(ep, pw);
     if (padded) {
         stg::FramedNT<true> al{sig, d->L, d->H, d->N, R, d->N, 1.0f, map};
-        if (gemm_ht(d->prec) == 0 && (g_nt_mi & 1)) stg::launch<4, 16, 2>(al, bl, ep, R, 2 * d->F, d->N, 1, st_stream(stream), g_dbg);
-        else if (gemm_ht(d->prec) == 0 && (g_nt_mi & 2)) stg::launch<2, 32, 2>(al, bl, ep, R, 2 * d->F, d->N, 1, st_stream(stream), g_dbg);
-        else if (g_an_waves == 2) ST_GEMM_AN(2, al, bl, ep, R, 2 * d->F, d->N, 1, st_stream(stream));
-        else if (g_an_waves == 3) ST_GEMM_AN(3, al, bl, ep, R, 2 * d->F, d->N, 1, st_stream(stream));
-        else ST_GEMM_AN(4, al, bl, ep, R, 2 * d->F, d->N, 1, st_stream(stream));
+        ST_GEMM_AN(4, al, bl, ep, R, 2 * d->F, d->N, 1, st_stream(stream));
     }
     else { stg::FramedNT<false> al{sig, d->L, d->H, d->N, R, d->N, in_scale, map}; ST_GEMM(4, al, bl, ep, R, 2 * d->F, d->N, 1, st_stream(stream)); }
     ST_LAUNCHED("analysis_fwd");
@@ -649,7 +618,6 @@ static int synthesis_frames_impl(const st_dims* d, const float* AA, const float*
             ST_TRY(stg::launch_nt128(ra, rb, es, wk, st_stream(stream)));
         }
         else if (R >= 4096) ST_GEMM(4, al, bt, ep, R, d->N, KP, 1, st_stream(stream));
-        else if (gemm_ht(d->prec) == 0 && (g_nt_mi & 4)) stg::launch<2, 16, 2>(al, bt, ep, R, d->N, KP, frames_split(R), st_stream(stream), g_dbg);
         else ST_GEMM(2, al, bt, ep, R, d->N, KP, frames_split(R), st_stream(stream));
     }
     else if (R >= 4096) ST_GEMM(4, al, bl, ep, R, d->N, KP, 1, st_stream(stream));
@@ -742,7 +710,6 @@ static int synthesis_dgrad_impl(const st_dims* d, const float* dsyn, bool padded
             ST_TRY(stg::launch_nt128(ra, rb, es, wk, st_stream(stream)));
         }
         else if (R >= 4096) ST_GEMM(4, al, bl, ep, R, KP, d->N, ns, st_stream(stream));
-        else if (gemm_ht(d->prec) == 0 && (g_nt_mi & 4)) stg::launch<2, 16, 2>(al, bl, ep, R, KP, d->N, ns, st_stream(stream), g_dbg);
         else ST_GEMM(2, al, bl, ep, R, KP, d->N, ns, st_stream(stream));
     } else {
         stg::FramedNT<false> al{dsyn, d->y, d->H, d->N, R, d->N, 1.0f, ms};
@@ -778,8 +745,7 @@ static TNFrameMajor tn_frame_major(const stg::TNOperand& ta, const stg::TNOperan
     return f;
 }
 // g_tn128 == 2: the round-3 k-tile loop (st_set_tuning(9580)); otherwise the pipelined one (st_gemm_tn.h, round 7)
-#define ST_TN128(...) do { if (g_tn_bk == 16) { if (g_tn128 == 2) ST_TRY((stg::launch_tn128<16, false>(__VA_ARGS__))); else ST_TRY((stg::launch_tn128<16, true>(__VA_ARGS__))); } \
-                           else if (g_tn128 == 2) ST_TRY((stg::launch_tn128<32, false>(__VA_ARGS__))); else ST_TRY((stg::launch_tn128<32, true>(__VA_ARGS__))); } while (0)
+#define ST_TN128(...) do { if (g_tn128 == 2) ST_TRY((stg::launch_tn128<32, false>(__VA_ARGS__))); else ST_TRY((stg::launch_tn128<32, true>(__VA_ARGS__))); } while (0)
 static int wgrad_tn128(const st_dims* d, const stg::TNOperand& ta, const stg::TNOperand& tb, const float* zeros, const stg::RowMap& map, int R,
                        float* ws, int ns, stm::NyqJob* nyq, void* stream, const stg::FrameTrim* trim)
 {
@@ -828,34 +794,29 @@ extern "C" int st_synthesis_wgrad(const st_dims* d, const float* AA, const float
 
 
 // ------------------------------------------------------------------------------ wide-geometry autoencoders (st_ae_wide.h)
-// BM = 64, k-tile 16 (every K below is a multiple of 16 or checked).  Level-2 precision: the 16-bit kernel (k-tile 32: W1 is padded to a multiple of 32
-// columns).  The weight-gradient GEMMs reduce over the R = B * 528 columns: a multiple of 32 for even batches; for ODD batches (R = 16 mod 32) they run
-// the same kernel on 16-deep k-tiles (round 5) -- until round 4 an odd batch dropped the whole wide path to fp32 layers (and said so: st_effective_prec),
-// the last place where the arithmetic of a call depended on its batch size.  wide_ht, a local of every user of ST_WGEMM: 0 fp32 / 1 bf16 / 2 fp16.
-static inline int wide_half_type(const st_dims* d, int R) { (void)R; return ae_ht(d->prec); }
 // The arithmetic a call REALLY runs.  Since round 5 that is the request for every geometry and batch; the entry stays so that callers (and the tests) can
 // keep asserting it instead of assuming it.
 extern "C" int st_effective_prec(const st_dims* d)
 {
     if (!d) return -1;
-    if (ae_is_wide(d) && ae_ht(d->prec) && wide_half_type(d, d->B * (st_kp_of(d->F) / 2)) == 0)
-        return d->prec == ST_PREC_BF16_ALL ? ST_PREC_BF16 : ST_PREC_F16;
     return d->prec;
 }
-#define ST_WGEMM(...) do { if (wide_ht == 1) stg::launch_half<2, 1>(__VA_ARGS__); else if (wide_ht == 2) stg::launch_half<2, 2>(__VA_ARGS__); \
-                           else stg::launch<2, 16>(__VA_ARGS__, g_dbg); } while (0)
+// BM = 64, k-tile 16 (every K below is a multiple of 16 or checked).  Level-2 precision: the 16-bit kernel (k-tile 32: W1 is padded to a multiple of 32
+// columns).  The weight-gradient GEMMs reduce over the R = B * 528 columns: a multiple of 32 for even batches; for ODD batches (R = 16 mod 32) they run
+// the same kernel on 16-deep k-tiles (round 5) -- until round 4 an odd batch dropped the whole wide path to fp32 layers (and said so: st_effective_prec),
+// the last place where the arithmetic of a call depended on its batch size.  wide_ht, a local of every user of ST_WGEMM_PAIR: 0 fp32 / 1 bf16 / 2 fp16.
 // the same GEMM for both autoencoders: ONE launch in the 16-bit configurations (gemm_half_pair_kernel), two on the fp32 kernel
 #define ST_WGEMM_PAIR(A0_, B0_, E0_, A1_, B1_, E1_, M_, N_, K_, NS_, S_) do { \
-        if (wide_ht == 1 && g_wide_pair) stg::launch_half_pair<2, 1>(A0_, B0_, E0_, A1_, B1_, E1_, M_, N_, K_, NS_, S_); \
-        else if (wide_ht == 2 && g_wide_pair) stg::launch_half_pair<2, 2>(A0_, B0_, E0_, A1_, B1_, E1_, M_, N_, K_, NS_, S_); \
-        else { ST_WGEMM(A0_, B0_, E0_, M_, N_, K_, NS_, S_); ST_WGEMM(A1_, B1_, E1_, M_, N_, K_, NS_, S_); } } while (0)
+        if (wide_ht == 1) stg::launch_half_pair<2, 1>(A0_, B0_, E0_, A1_, B1_, E1_, M_, N_, K_, NS_, S_); \
+        else if (wide_ht == 2) stg::launch_half_pair<2, 2>(A0_, B0_, E0_, A1_, B1_, E1_, M_, N_, K_, NS_, S_); \
+        else { stg::launch<2, 16>(A0_, B0_, E0_, M_, N_, K_, NS_, S_); stg::launch<2, 16>(A1_, B1_, E1_, M_, N_, K_, NS_, S_); } } while (0)
 static int ae_wide_fwd(const st_dims* d, const Layout& L, const float* mag, const float* phs, const float* knobs,
                        const float* ae_m, const float* ae_p, float* mag_hat, float* phs_hat, float* AA, float* reg_partial,
                        WideWS& w, void* stream, unsigned short* AA16, bool in_done)
 {
     hipStream_t s = st_stream(stream);
     const int FP = L.KP / 2, F = d->F, T = d->T, OT = d->OT, R = (int)w.R, Tp = w.Tp;
-    const int wide_ht = wide_half_type(d, R);
+    const int wide_ht = ae_ht(d->prec);
     ST_REQ(w.R * (size_t)(T > 64 ? T : 64) < ((size_t)1 << 30), "wide autoencoder path: batch too large (B=%d)", d->B);
     const stg::RowMap id = stg::all_frames(1);
     int out[9], in[9]; ae_shapes(d, out, in);
@@ -875,26 +836,14 @@ static int ae_wide_fwd(const st_dims* d, const Layout& L, const float* mag, cons
                            d->B, T, F, FP, d->K, n_copy, pj);
         ST_LAUNCHED("ae_wide_in");
     }
-    // layers 1..8: GEMM for layer 1 (K = T); layers 2..8 either one fused kernel for both nets (default) or seven more GEMMs
-    if (g_wide_fused) {
+    // layers 1..8: GEMM for layer 1 (K = T), layers 2..8 in one fused kernel for both nets
+    {
         stg::PlainNT al0{w.W1p[0], out[0], Tp, Tp, id}, al1{w.W1p[1], out[0], Tp, Tp, id};
         stg::PlainTN bl0{w.V[0], in[0], R, R, id}, bl1{w.V[1], in[0], R, R, id};
         stw::ActStore ep0{w.H[0][0], ae_m + L.go.b[0], out[0], R, FP, F}, ep1{w.H[1][0], ae_p + L.go.b[0], out[0], R, FP, F};
         ST_WGEMM_PAIR(al0, bl0, ep0, al1, bl1, ep1, out[0], R, Tp, 1, s);
     }
-    else for (int a = 0; a < 2; ++a) {
-        const float* ae = a ? ae_p : ae_m;
-        for (int l = 0; l < 8; ++l) {
-            const float* Wl = l == 0 ? w.W1p[a] : (l == 4 ? w.W5p[a] : ae + L.go.w[l]);
-            const int kp = l == 0 ? Tp : (l == 4 ? 32 : in[l]);                       // padded reduction length = row pitch of Wl
-            const float* Hin = l == 0 ? w.V[a] : w.H[a][l - 1];
-            stg::PlainNT al{Wl, out[l], kp, kp, id};
-            stg::PlainTN bl{Hin, in[l], R, R, id};
-            stw::ActStore ep{w.H[a][l], ae + L.go.b[l], out[l], R, FP, F};
-            ST_WGEMM(al, bl, ep, out[l], R, kp, 1, s);
-        }
-    }
-    if (g_wide_fused) {
+    {
         const size_t lds = (size_t)2 * sta::CL::FWD_TOTAL * sizeof(float);
 #define ST_AE_INNER_FWD_(NW_, HT_) do { ST_DYN_LDS((sta::ae_inner_fwd_kernel<NW_, HT_>)); \
             hipLaunchKernelGGL((sta::ae_inner_fwd_kernel<NW_, HT_>), dim3(ae_inner_grid(d)), dim3(NW_ * 64), lds, s, \
@@ -921,23 +870,8 @@ static int ae_wide_fwd(const st_dims* d, const Layout& L, const float* mag, cons
     return ST_OK;
 }
 
-// one weight-gradient GEMM of the wide path: dW_l (+ bias via the ones row) as split-K slabs of net a
-static void wide_wgrad(const st_dims* d, WideWS& w, int a, int l, const int* out, const int* in, hipStream_t s, const int wide_ht)
-{
-    const int R = (int)w.R;
-    const stg::RowMap id = stg::all_frames(1);
-    const float* Hin = l == 0 ? w.V[a] : w.H[a][l - 1];
-    stg::PlainNT al{w.DA[a][l], out[l], R, R, id};
-    stg::PlainNT bl{Hin, in[l] + 1, R, R, id};
-    stg::StoreC ep{w.slabs + (size_t)a * w.nsplit * w.SL + w.so[l], out[l], in[l] + 1, in[l] + 1, w.SL, id};
-    if (wide_ht && R % 32) {      // odd batch: the reduction length is 16 mod 32 -> 16-deep k-tiles of the same kernel
-        if (wide_ht == 1) stg::launch_half<2, 1, 1, 16>(al, bl, ep, out[l], in[l] + 1, R, w.nsplit, s); else stg::launch_half<2, 2, 1, 16>(al, bl, ep, out[l], in[l] + 1, R, w.nsplit, s);
-        return;
-    }
-    ST_WGEMM(al, bl, ep, out[l], in[l] + 1, R, w.nsplit, s);
-}
-
-// ... of both nets in one launch: net 1's slabs follow net 0's (slab z of the pair launch = net * nsplit + slice), so both epilogues share one origin
+// one weight-gradient GEMM of the wide path for both nets: dW_l (+ bias via the ones row) as split-K slabs.  In the one 16-bit launch net 1's slabs follow net 0's
+// (slab z of the pair launch = net * nsplit + slice), so both epilogues share one origin
 static void wide_wgrad_pair(const st_dims* d, WideWS& w, int l, const int* out, const int* in, hipStream_t s, const int wide_ht)
 {
     const int R = (int)w.R;
@@ -946,13 +880,10 @@ static void wide_wgrad_pair(const st_dims* d, WideWS& w, int l, const int* out, 
     stg::PlainNT bl0{l == 0 ? w.V[0] : w.H[0][l - 1], in[l] + 1, R, R, id}, bl1{l == 0 ? w.V[1] : w.H[1][l - 1], in[l] + 1, R, R, id};
     stg::StoreC ep0{w.slabs + w.so[l], out[l], in[l] + 1, in[l] + 1, w.SL, id};
     stg::StoreC ep1 = ep0;
-    if (!(g_wide_pair && wide_ht)) ep1.out = w.slabs + (size_t)w.nsplit * w.SL + w.so[l];      // two launches: each with its own z = 0 .. nsplit - 1
-    if (wide_ht && R % 32) {      // odd batch: 16-deep k-tiles (see wide_wgrad)
-        if (g_wide_pair) {
-            if (wide_ht == 1) stg::launch_half_pair<2, 1, 1, 16>(al0, bl0, ep0, al1, bl1, ep1, out[l], in[l] + 1, R, w.nsplit, s);
-            else stg::launch_half_pair<2, 2, 1, 16>(al0, bl0, ep0, al1, bl1, ep1, out[l], in[l] + 1, R, w.nsplit, s);
-        } else if (wide_ht == 1) { stg::launch_half<2, 1, 1, 16>(al0, bl0, ep0, out[l], in[l] + 1, R, w.nsplit, s); stg::launch_half<2, 1, 1, 16>(al1, bl1, ep1, out[l], in[l] + 1, R, w.nsplit, s); }
-        else { stg::launch_half<2, 2, 1, 16>(al0, bl0, ep0, out[l], in[l] + 1, R, w.nsplit, s); stg::launch_half<2, 2, 1, 16>(al1, bl1, ep1, out[l], in[l] + 1, R, w.nsplit, s); }
+    if (!wide_ht) ep1.out = w.slabs + (size_t)w.nsplit * w.SL + w.so[l];      // two launches: each with its own z = 0 .. nsplit - 1
+    if (wide_ht && R % 32) {      // odd batch: the reduction length is 16 mod 32 -> 16-deep k-tiles of the same kernel
+        if (wide_ht == 1) stg::launch_half_pair<2, 1, 1, 16>(al0, bl0, ep0, al1, bl1, ep1, out[l], in[l] + 1, R, w.nsplit, s);
+        else stg::launch_half_pair<2, 2, 1, 16>(al0, bl0, ep0, al1, bl1, ep1, out[l], in[l] + 1, R, w.nsplit, s);
         return;
     }
     ST_WGEMM_PAIR(al0, bl0, ep0, al1, bl1, ep1, out[l], in[l] + 1, R, w.nsplit, s);
@@ -963,12 +894,12 @@ struct PolarSink { const float* re; const float* im; const float* g_mag; float* 
 static int ae_wide_bwd(const st_dims* d, const Layout& L, const float* mag, const float* phs, const float* knobs,
                        const float* ae_m, const float* ae_p, const float* mag_hat, const float* phs_hat, const float* dAA,
                        const float* g_mag_hat, float reg_coef, float* dmag, float* dphs, WideWS& w, float* g_m, float* g_p,
-                       bool have_fwd, void* stream, const PolarSink* sink = nullptr, bool* sink_used = nullptr,
-                       const stw::SynReduce* syn = nullptr, bool* syn_done = nullptr, float* norm_e = nullptr, int* n_norm_e = nullptr)
+                       bool have_fwd, void* stream, const PolarSink* sink = nullptr,
+                       const stw::SynReduce* syn = nullptr, float* norm_e = nullptr, int* n_norm_e = nullptr)
 {
     hipStream_t s = st_stream(stream);
-    const int FP = L.KP / 2, F = d->F, T = d->T, OT = d->OT, R = (int)w.R, Tp = w.Tp;
-    const int wide_ht = wide_half_type(d, R);
+    const int FP = L.KP / 2, F = d->F, T = d->T, OT = d->OT, R = (int)w.R;
+    const int wide_ht = ae_ht(d->prec);
     const stg::RowMap id = stg::all_frames(1);
     int out[9], in[9]; ae_shapes(d, out, in);
     // forward state (activations + ELU outputs of layer 9): recomputed into the workspace unless the fused step's own
@@ -990,88 +921,64 @@ static int ae_wide_bwd(const st_dims* d, const Layout& L, const float* mag, cons
                            w.DA[0][8], w.DA[1][8], w.TL[0], w.TL[1], d->B, OT, F, FP, L.KP, ms.t_lo, ms.t_lo + ms.Tv - 1, grid, rows);
         ST_LAUNCHED("ae_wide_dout");
     }
-    // data gradient through W_l into dA_{l-1} (layer 5: only the 16 code columns; the knobs take no gradient)
-    auto dgrad = [&](int a, int l, bool plain) {
-        const float* ae = a ? ae_p : ae_m;
-        const float* Wl = l == 0 ? w.W1p[a] : (l == 4 ? w.W5p[a] : ae + L.go.w[l]);
-        const int pitch = l == 0 ? Tp : (l == 4 ? 32 : in[l]);
-        const int m = l == 0 ? T : (l == 4 ? 16 : in[l]);
-        stg::PlainTN al{Wl, out[l], pitch, m, id};
-        stg::PlainTN bl{w.DA[a][l], out[l], R, R, id};
-        if (l == 0) { stw::DvStore ep{a ? dphs : dmag, w.TL[a], T, OT, R, FP, F}; ST_WGEMM(al, bl, ep, T, R, out[l], 1, s); }
-        else if (plain) { stg::StoreC ep{w.DA[a][l - 1], m, R, R, 0, id}; ST_WGEMM(al, bl, ep, m, R, out[l], 1, s); }     // dH only: the fused kernel applies ELU'
-        else { stw::DgradStore ep{w.DA[a][l - 1], w.H[a][l - 1], m, R}; ST_WGEMM(al, bl, ep, m, R, out[l], 1, s); }
-    };
     stw::GradTab tab;
     for (int l = 0; l < 9; ++l) { tab.so[l] = w.so[l]; tab.out[l] = out[l]; tab.in[l] = in[l]; tab.gw[l] = L.go.w[l]; tab.gb[l] = L.go.b[l]; }
     tab.so[9] = w.so[9];
     int inner_parts = 0;
-    if (g_wide_fused) {
-        // layer 9 as GEMMs, layers 8..2 in one fused kernel (both nets), layer 1 as GEMMs
-        wide_wgrad_pair(d, w, 8, out, in, s, wide_ht);
-        {   // d H8 = W9^T d A9 of both nets (the fused kernel applies ELU')
-            stg::PlainTN al0{ae_m + L.go.w[8], out[8], in[8], in[8], id}, al1{ae_p + L.go.w[8], out[8], in[8], in[8], id};
-            stg::PlainTN bl0{w.DA[0][8], out[8], R, R, id}, bl1{w.DA[1][8], out[8], R, R, id};
-            stg::StoreC ep0{w.DA[0][7], in[8], R, R, 0, id}, ep1{w.DA[1][7], in[8], R, R, 0, id};
-            ST_WGEMM_PAIR(al0, bl0, ep0, al1, bl1, ep1, in[8], R, out[8], 1, s);
-        }
-        {
-            const size_t lds = (size_t)sta::ae_bwd_lds_floats(AE_BWD_NW) * sizeof(float);
-            const int grid = ae_bwd_grid(d);
-#define ST_AE_INNER_BWD(HT_) do { ST_DYN_LDS((sta::ae_bwd_kernel<AE_BWD_NW, false, true, HT_, 0>)); \
-                hipLaunchKernelGGL((sta::ae_bwd_kernel<AE_BWD_NW, false, true, HT_, 0>), dim3(grid, 2), dim3(AE_BWD_NW * 64), lds, s, \
-                                   (const float*)w.H[0][0], (const float*)w.H[1][0], knobs, ae_m, ae_p, L.go, L.PG, \
-                                   (const float*)w.DA[0][7], (const float*)w.DA[1][7], (const float*)nullptr, (const float*)nullptr, 0.f, 0.f, \
-                                   w.DA[0][0], w.DA[1][0], w.inner_ws, d->B, T, OT, F, d->K, L.KP, 0, 0, 1, (size_t)0, 0); } while (0)
-            switch (wide_ht) { case 1: ST_AE_INNER_BWD(1); break; case 2: ST_AE_INNER_BWD(2); break; default: ST_AE_INNER_BWD(0); }
+    // layer 9 as GEMMs, layers 8..2 in one fused kernel (both nets), layer 1 as GEMMs
+    wide_wgrad_pair(d, w, 8, out, in, s, wide_ht);
+    {   // d H8 = W9^T d A9 of both nets (the fused kernel applies ELU')
+        stg::PlainTN al0{ae_m + L.go.w[8], out[8], in[8], in[8], id}, al1{ae_p + L.go.w[8], out[8], in[8], in[8], id};
+        stg::PlainTN bl0{w.DA[0][8], out[8], R, R, id}, bl1{w.DA[1][8], out[8], R, R, id};
+        stg::StoreC ep0{w.DA[0][7], in[8], R, R, 0, id}, ep1{w.DA[1][7], in[8], R, R, 0, id};
+        ST_WGEMM_PAIR(al0, bl0, ep0, al1, bl1, ep1, in[8], R, out[8], 1, s);
+    }
+    {
+        const size_t lds = (size_t)sta::ae_bwd_lds_floats(AE_BWD_NW) * sizeof(float);
+        const int grid = ae_bwd_grid(d);
+#define ST_AE_INNER_BWD(HT_) do { ST_DYN_LDS((sta::ae_bwd_kernel<AE_BWD_NW, true, HT_, 0>)); \
+            hipLaunchKernelGGL((sta::ae_bwd_kernel<AE_BWD_NW, true, HT_, 0>), dim3(grid, 2), dim3(AE_BWD_NW * 64), lds, s, \
+                               (const float*)w.H[0][0], (const float*)w.H[1][0], knobs, ae_m, ae_p, L.go, L.PG, \
+                               (const float*)w.DA[0][7], (const float*)w.DA[1][7], (const float*)nullptr, (const float*)nullptr, 0.f, 0.f, \
+                               w.DA[0][0], w.DA[1][0], w.inner_ws, d->B, T, OT, F, d->K, L.KP, 0, 0, 1, (size_t)0); } while (0)
+        switch (wide_ht) { case 1: ST_AE_INNER_BWD(1); break; case 2: ST_AE_INNER_BWD(2); break; default: ST_AE_INNER_BWD(0); }
 #undef ST_AE_INNER_BWD
-            inner_parts = grid;                          // summed by the second role of wide_grad_finish_kernel below (was a launch of its own)
-        }
-        for (int l = 1; l < 8; ++l) tab.out[l] = 0;                 // the finish kernel only scatters layers 1 and 9
-        wide_wgrad_pair(d, w, 0, out, in, s, wide_ht);
-        if (!g_wide_dvp) for (int a = 0; a < 2; ++a) dgrad(a, 0, false);
-        if (norm_e && 2 * ((w.so[9] + 63) / 64 + (L.PG + 63) / 64) > NORM_E_MAX) norm_e = nullptr;
-        hipLaunchKernelGGL(stw::wide_grad_finish_kernel, dim3((w.so[9] + 63) / 64 + (L.PG + 63) / 64 + (syn ? st_norm_partials(d) : 0), 2), dim3(256), 0, s, w.slabs, w.nsplit, w.SL, tab, g_m, g_p,
-                           (w.so[9] + 63) / 64, (const float*)w.inner_ws, inner_parts, L.PG, syn ? *syn : stw::SynReduce{}, norm_e);
-        if (syn && syn_done) *syn_done = true;
-        if (norm_e && n_norm_e) *n_norm_e = 2 * ((w.so[9] + 63) / 64 + (L.PG + 63) / 64);
-        if (g_wide_dvp) {
-            stw::DvPolarArgs q;
-            q.DA1m = w.DA[0][0]; q.DA1p = w.DA[1][0]; q.TLm = w.TL[0]; q.TLp = w.TL[1]; q.W1m = ae_m + L.go.w[0]; q.W1p = ae_p + L.go.w[0];
-            q.re = sink ? sink->re : nullptr; q.im = sink ? sink->im : nullptr; q.g_mag = sink ? sink->g_mag : nullptr;
-            q.dG = sink ? sink->dG : nullptr; q.dG16 = sink ? sink->dG16 : nullptr;
-            q.dmag = sink ? nullptr : dmag; q.dphs = sink ? nullptr : dphs;          // fused step: d mag / d phs never leave the kernel
-            q.ht = gemm_ht(d->prec) <= 2 ? gemm_ht(d->prec) : 0; q.sat = gemm_ht(d->prec) == 2 ? 65504.0f : 0.0f;
-            q.B = d->B; q.T = T; q.OT = OT; q.F = F; q.FP = FP; q.KP = L.KP;
-            const int TP16 = (T + 15) / 16 * 16, groups = d->B * (FP / 16);
-            ST_REQ(TP16 <= 192, "wide autoencoder path: T = %d frames exceeds the layer-1 data-gradient kernel's 192", T);
-            const size_t lds = (size_t)2 * (wide_ht ? 32 : 64) * TP16 * sizeof(float);          // 16-bit images take half the room
-            int grid = ((groups + 7) / 8) * (TP16 / 16); if (grid > num_cus()) grid = num_cus();      // units of (8 adjacent groups, 16-frame tile), shared equally; one workgroup per CU
-                                                                                                      // (two or three per CU measured slower: 146.6 / 155.5 us against 141.1 for the whole
-                                                                                                      // wide backward -- every workgroup stages the layer-1 weights, ~10 us of dependent loads)
+        inner_parts = grid;                          // summed by the second role of wide_grad_finish_kernel below (was a launch of its own)
+    }
+    for (int l = 1; l < 8; ++l) tab.out[l] = 0;                 // the finish kernel only scatters layers 1 and 9
+    wide_wgrad_pair(d, w, 0, out, in, s, wide_ht);
+    if (norm_e && 2 * ((w.so[9] + 63) / 64 + (L.PG + 63) / 64) > NORM_E_MAX) norm_e = nullptr;
+    hipLaunchKernelGGL(stw::wide_grad_finish_kernel, dim3((w.so[9] + 63) / 64 + (L.PG + 63) / 64 + (syn ? st_norm_partials(d) : 0), 2), dim3(256), 0, s, w.slabs, w.nsplit, w.SL, tab, g_m, g_p,
+                       (w.so[9] + 63) / 64, (const float*)w.inner_ws, inner_parts, L.PG, syn ? *syn : stw::SynReduce{}, norm_e);
+    if (norm_e && n_norm_e) *n_norm_e = 2 * ((w.so[9] + 63) / 64 + (L.PG + 63) / 64);
+    {   // layer-1 data gradient + polar backward of both nets in one kernel
+        stw::DvPolarArgs q;
+        q.DA1m = w.DA[0][0]; q.DA1p = w.DA[1][0]; q.TLm = w.TL[0]; q.TLp = w.TL[1]; q.W1m = ae_m + L.go.w[0]; q.W1p = ae_p + L.go.w[0];
+        q.re = sink ? sink->re : nullptr; q.im = sink ? sink->im : nullptr; q.g_mag = sink ? sink->g_mag : nullptr;
+        q.dG = sink ? sink->dG : nullptr; q.dG16 = sink ? sink->dG16 : nullptr;
+        q.dmag = sink ? nullptr : dmag; q.dphs = sink ? nullptr : dphs;          // fused step: d mag / d phs never leave the kernel
+        q.ht = gemm_ht(d->prec) <= 2 ? gemm_ht(d->prec) : 0; q.sat = gemm_ht(d->prec) == 2 ? 65504.0f : 0.0f;
+        q.B = d->B; q.T = T; q.OT = OT; q.F = F; q.FP = FP; q.KP = L.KP;
+        const int TP16 = (T + 15) / 16 * 16, groups = d->B * (FP / 16);
+        ST_REQ(TP16 <= 192, "wide autoencoder path: T = %d frames exceeds the layer-1 data-gradient kernel's 192", T);
+        const size_t lds = (size_t)2 * (wide_ht ? 32 : 64) * TP16 * sizeof(float);          // 16-bit images take half the room
+        int grid = ((groups + 7) / 8) * (TP16 / 16); if (grid > num_cus()) grid = num_cus();      // units of (8 adjacent groups, 16-frame tile), shared equally; one workgroup per CU
+                                                                                                  // (two or three per CU measured slower: 146.6 / 155.5 us against 141.1 for the whole
+                                                                                                  // wide backward -- every workgroup stages the layer-1 weights, ~10 us of dependent loads)
 #define ST_DVP(HT_) do { ST_DYN_LDS((stw::wide_dv_polar_kernel<HT_>)); hipLaunchKernelGGL((stw::wide_dv_polar_kernel<HT_>), dim3(grid), dim3(512), lds, s, q); } while (0)
-            switch (wide_ht) { case 1: ST_DVP(1); break; case 2: ST_DVP(2); break; default: ST_DVP(0); }
+        switch (wide_ht) { case 1: ST_DVP(1); break; case 2: ST_DVP(2); break; default: ST_DVP(0); }
 #undef ST_DVP
-            if (sink_used) *sink_used = sink != nullptr;
-        }
-    } else {
-        for (int a = 0; a < 2; ++a) {
-            for (int l = 8; l >= 0; --l) { wide_wgrad(d, w, a, l, out, in, s, wide_ht); dgrad(a, l, false); }
-            hipLaunchKernelGGL(stw::wide_grad_finish_kernel, dim3((w.so[9] + 63) / 64, 1), dim3(256), 0, s,
-                               w.slabs + (size_t)a * w.nsplit * w.SL, w.nsplit, w.SL, tab, a ? g_p : g_m, a ? g_p : g_m);
-        }
     }
     ST_LAUNCHED("ae_wide_bwd");
     return ST_OK;
 }
-#undef ST_WGEMM
+#undef ST_WGEMM_PAIR
 
 static int ae_bwd_impl(const st_dims* d, const float* mag, const float* phs, const float* knobs,
                        const float* ae_m, const float* ae_p, const float* mag_hat, const float* phs_hat,
                        const float* dAA, const float* g_mag_hat, float reg_coef, float* dmag, float* dphs, float* ws,
                        float* g_m, float* g_p, bool have_fwd, void* stream, bool* defer_reduce = nullptr,
-                       const PolarSink* sink = nullptr, bool* sink_used = nullptr, const stw::SynReduce* syn = nullptr, bool* syn_done = nullptr,
-                       float* norm_e = nullptr, int* n_norm_e = nullptr)
+                       const PolarSink* sink = nullptr, const stw::SynReduce* syn = nullptr, float* norm_e = nullptr, int* n_norm_e = nullptr)
 {
     // defer_reduce: in -> the caller will sum the workgroup partials itself (post_ae_kernel, together with the polar backward);
     // out -> false if this geometry's path already reduced them (wide geometries)
@@ -1081,7 +988,7 @@ static int ae_bwd_impl(const st_dims* d, const float* mag, const float* phs, con
     if (ae_is_wide(d)) {
         if (defer_reduce) *defer_reduce = false;
         WideWS w; wide_carve(d, ws, &w);
-        return ae_wide_bwd(d, L, mag, phs, knobs, ae_m, ae_p, mag_hat, phs_hat, dAA, g_mag_hat, reg_coef, dmag, dphs, w, g_m, g_p, have_fwd, stream, sink, sink_used, syn, syn_done, norm_e, n_norm_e);
+        return ae_wide_bwd(d, L, mag, phs, knobs, ae_m, ae_p, mag_hat, phs_hat, dAA, g_mag_hat, reg_coef, dmag, dphs, w, g_m, g_p, have_fwd, stream, sink, syn, norm_e, n_norm_e);
     }
     const size_t lds = (size_t)sta::ae_bwd_lds_floats(AE_BWD_NW) * sizeof(float);
     static_assert((size_t)sta::ae_bwd_lds_floats(AE_BWD_NW) * sizeof(float) <= 160 * 1024, "ae_bwd LDS budget");
@@ -1116,32 +1023,27 @@ static int ae_bwd_impl(const st_dims* d, const float* mag, const float* phs, con
         hipLaunchKernelGGL(stm::ae_grad_reduce_kernel, dim3((L.PG + 63) / 64, 2), dim3(256), 0, st_stream(stream), parts, grid, L.PG, g_m, g_p);
         ST_LAUNCHED("ae_grad_reduce"); return ST_OK;
     }
-#define ST_AE_BWD_LAUNCH(TIMED_, HT_, VAR_) do { ST_DYN_LDS((sta::ae_bwd_kernel<AE_BWD_NW, TIMED_, false, HT_, VAR_>)); \
-    hipLaunchKernelGGL((sta::ae_bwd_kernel<AE_BWD_NW, TIMED_, false, HT_, VAR_>), dim3(grid, 2), dim3(AE_BWD_NW * 64), lds, st_stream(stream), \
+#define ST_AE_BWD_LAUNCH(HT_, VAR_) do { ST_DYN_LDS((sta::ae_bwd_kernel<AE_BWD_NW, false, HT_, VAR_>)); \
+    hipLaunchKernelGGL((sta::ae_bwd_kernel<AE_BWD_NW, false, HT_, VAR_>), dim3(grid, 2), dim3(AE_BWD_NW * 64), lds, st_stream(stream), \
                        mag, phs, knobs, ae_m, ae_p, L.go, L.PG, mag_hat, phs_hat, dAA, g_mag_hat, reg_coef, expfac, \
-                       dmag, dphs, parts, d->B, d->T, d->OT, d->F, d->K, L.KP, live.t_lo, live.t_lo + live.Tv - 1, st_synth_slabs(d), (size_t)d->B * d->OT * L.KP, g_dbg); } while (0)
+                       dmag, dphs, parts, d->B, d->T, d->OT, d->F, d->K, L.KP, live.t_lo, live.t_lo + live.Tv - 1, st_synth_slabs(d), (size_t)d->B * d->OT * L.KP); } while (0)
     // kernel variant: 1 = an upstream d/d mag_hat arrives (autograd entry), 2 = T - OT == 16 (tails already in registers), 0 = neither
     const int var = g_mag_hat ? 1 : (d->T - d->OT == 16 ? 2 : 0);
     if (have_fwd && ae_use_saved(d)) {               // round 6: the forward of this workspace kept the activations -- no recompute
         const float* sv = ae_sv_ptr(d, L, ws);
-#define ST_AE_BWD_SV(VAR_, TIMED_) do { ST_DYN_LDS((sta::ae_bwd_kernel<AE_BWD_NW, TIMED_, false, 0, VAR_, true>)); \
-        hipLaunchKernelGGL((sta::ae_bwd_kernel<AE_BWD_NW, TIMED_, false, 0, VAR_, true>), dim3(grid, 2), dim3(AE_BWD_NW * 64), lds, st_stream(stream), \
+#define ST_AE_BWD_SV(VAR_) do { ST_DYN_LDS((sta::ae_bwd_kernel<AE_BWD_NW, false, 0, VAR_, true>)); \
+        hipLaunchKernelGGL((sta::ae_bwd_kernel<AE_BWD_NW, false, 0, VAR_, true>), dim3(grid, 2), dim3(AE_BWD_NW * 64), lds, st_stream(stream), \
                        mag, phs, knobs, ae_m, ae_p, L.go, L.PG, mag_hat, phs_hat, dAA, g_mag_hat, reg_coef, expfac, \
-                       dmag, dphs, parts, d->B, d->T, d->OT, d->F, d->K, L.KP, live.t_lo, live.t_lo + live.Tv - 1, st_synth_slabs(d), (size_t)d->B * d->OT * L.KP, g_dbg, sv); } while (0)
-        if (g_dbg & 256) { ST_REQ(var == 2, "the stage-timer build covers the fp32 training step at T - OT == 16 only"); ST_AE_BWD_SV(2, true); }      // tools/ae_stage_times.py
-        else if (var == 1) ST_AE_BWD_SV(1, false); else if (var == 2) ST_AE_BWD_SV(2, false); else ST_AE_BWD_SV(0, false);
+                       dmag, dphs, parts, d->B, d->T, d->OT, d->F, d->K, L.KP, live.t_lo, live.t_lo + live.Tv - 1, st_synth_slabs(d), (size_t)d->B * d->OT * L.KP, sv); } while (0)
+        if (var == 1) ST_AE_BWD_SV(1); else if (var == 2) ST_AE_BWD_SV(2); else ST_AE_BWD_SV(0);
 #undef ST_AE_BWD_SV
         ST_LAUNCHED("ae_bwd");
         if (defer_reduce && *defer_reduce) return ST_OK;
         hipLaunchKernelGGL(stm::ae_grad_reduce_kernel, dim3((L.PG + 63) / 64, 2), dim3(256), 0, st_stream(stream), parts, grid, L.PG, g_m, g_p);
         ST_LAUNCHED("ae_grad_reduce"); return ST_OK;
     }
-#define ST_AE_BWD_VARS(HT_) do { if (var == 1) ST_AE_BWD_LAUNCH(false, HT_, 1); else if (var == 2) ST_AE_BWD_LAUNCH(false, HT_, 2); else ST_AE_BWD_LAUNCH(false, HT_, 0); } while (0)
-    if (g_dbg & 256) {                               // stage-timer build (tools/ae_stage_times.py): the default-geometry training variant
-        ST_REQ(var == 2 && ae_ht(d->prec) == 0, "the stage-timer build covers the fp32 training step at T - OT == 16 only");
-        ST_AE_BWD_LAUNCH(true, 0, 2);
-    }
-    else switch (ae_ht(d->prec)) { case 1: ST_AE_BWD_VARS(1); break; case 2: ST_AE_BWD_VARS(2); break; default: ST_AE_BWD_VARS(0); }
+#define ST_AE_BWD_VARS(HT_) do { if (var == 1) ST_AE_BWD_LAUNCH(HT_, 1); else if (var == 2) ST_AE_BWD_LAUNCH(HT_, 2); else ST_AE_BWD_LAUNCH(HT_, 0); } while (0)
+    switch (ae_ht(d->prec)) { case 1: ST_AE_BWD_VARS(1); break; case 2: ST_AE_BWD_VARS(2); break; default: ST_AE_BWD_VARS(0); }
 #undef ST_AE_BWD_VARS
 #undef ST_AE_BWD_LAUNCH
     ST_LAUNCHED("ae_bwd");
@@ -1188,7 +1090,7 @@ static int analysis_wgrad_impl(const st_dims* d, const float* dG, const float* s
             const double f = (double)w / ((double)rounds * cus);
             if (f > bf + 1e-9) { bf = f; best = c; }
         }
-        ns = (g_wsplit_half > 0 && g_wsplit_half < ns) ? g_wsplit_half : best;
+        ns = best;
     }
     const int M = half < 0 ? KP : KP / 2, m0 = half > 0 ? KP / 2 : 0;
     stm::NyqJob nyq{}; nyq.on = 0;
@@ -1267,14 +1169,6 @@ extern "C" int st_clip_adam(float* params, float* grads, float* m, float* v, int
                             void* stream)
 {
     return clip_adam_impl(params, grads, m, v, n_total, n_stft, const_cast<float*>(scalars), grad_scale, lr, beta1, beta2, eps, step, nullptr, stream);
-}
-
-extern "C" int st_debug_read_stage_cycles(unsigned long long* out32)
-{
-    unsigned long long z[32] = {0};
-    if (hipMemcpyFromSymbol(out32, HIP_SYMBOL(sta::g_ae_stage_cycles), sizeof(z)) != hipSuccess) return st_fail(ST_ERR_LAUNCH, "memcpyFromSymbol");
-    if (hipMemcpyToSymbol(HIP_SYMBOL(sta::g_ae_stage_cycles), z, sizeof(z)) != hipSuccess) return st_fail(ST_ERR_LAUNCH, "memcpyToSymbol");
-    return ST_OK;
 }
 
 // ------------------------------------------------------------------------------ workspace
@@ -1404,9 +1298,7 @@ static int analysis_fwd_planes(const st_dims* d, WS& w, float* re, float* im, fl
     stg::PolarStore ep{re, im, mag, phs, R, d->F, map};
     polar_wide_set(ep, pw);
     if (planes_of(d) == 1) ST_TRY((stg::launch_planes<4, 1>(al, bl, ep, R, 2 * d->F, d->N, 1, st_stream(stream))));
-    else if (g_pl_shape == 1) ST_TRY((stg::launch_planes<2, 3, 2>(al, bl, ep, R, 2 * d->F, d->N, 1, st_stream(stream))));
-    else if (g_pl_shape == 2) ST_TRY((stg::launch_planes<4, 3, 2>(al, bl, ep, R, 2 * d->F, d->N, 1, st_stream(stream))));
-    else if (g_pl_shape == 3) ST_TRY((stg::launch_planes<8, 3, 1>(al, bl, ep, R, 2 * d->F, d->N, 1, st_stream(stream))));
+    else if (g_pl_shape == 3) ST_TRY((stg::launch_planes<8, 3>(al, bl, ep, R, 2 * d->F, d->N, 1, st_stream(stream))));
     else ST_TRY((stg::launch_planes<4, 3>(al, bl, ep, R, 2 * d->F, d->N, 1, st_stream(stream))));
     ST_LAUNCHED("analysis_fwd");
     return ST_OK;
@@ -1456,19 +1348,16 @@ static int analysis_fwd16(const st_dims* d, WS& w, float* re, float* im, float* 
 {
     const stg::RowMap map = stg::live_frames(d->T, d->H, d->N, d->N, d->L);
     const int R = map.rows(d->B);
-    stg::Rows16 ra = stg::rows16(w.xp16, (unsigned)(d->L + 2 * d->N), (unsigned)d->H, map, R);
-    if (g_g16_abl & 4) ra.S2 &= ~7u;              // timing only: 16-byte aligned frame rows
+    const stg::Rows16 ra = stg::rows16(w.xp16, (unsigned)(d->L + 2 * d->N), (unsigned)d->H, map, R);
     const stg::Rows16 rb = stg::rows16_plain(w.W16, (unsigned)d->N, 2 * d->F);
     stg::PolarStore ep{re, im, mag, phs, R, d->F, map};
     polar_wide_set(ep, pw);
-    if (g_g16_abl & 1) ep.mag = ep.phs = nullptr;
-    if (g_g16_abl & 2) ep.re = ep.im = nullptr;
     if ((g_g16_dma & 1) && d->N % 64 == 0) {
-        if (gemm_ht(d->prec) == 2) ST_TRY((stg::launch16_nt256<2>(ra, rb, ep, R, 2 * d->F, d->N, 1, st_stream(stream), g_g16_abl >> 3)));
-        else ST_TRY((stg::launch16_nt256<1>(ra, rb, ep, R, 2 * d->F, d->N, 1, st_stream(stream), g_g16_abl >> 3)));
+        if (gemm_ht(d->prec) == 2) ST_TRY((stg::launch16_nt256<2>(ra, rb, ep, R, 2 * d->F, d->N, 1, st_stream(stream))));
+        else ST_TRY((stg::launch16_nt256<1>(ra, rb, ep, R, 2 * d->F, d->N, 1, st_stream(stream))));
     }
-    else if (gemm_ht(d->prec) == 2) ST_TRY((stg::launch16_nt<2>(ra, rb, ep, R, 2 * d->F, d->N, 1, st_stream(stream), g_g16_bk != 32)));
-    else ST_TRY((stg::launch16_nt<1>(ra, rb, ep, R, 2 * d->F, d->N, 1, st_stream(stream), g_g16_bk != 32)));
+    else if (gemm_ht(d->prec) == 2) ST_TRY((stg::launch16_nt<2>(ra, rb, ep, R, 2 * d->F, d->N, 1, st_stream(stream))));
+    else ST_TRY((stg::launch16_nt<1>(ra, rb, ep, R, 2 * d->F, d->N, 1, st_stream(stream))));
     ST_LAUNCHED("analysis_fwd"); return ST_OK;
 }
 static int synthesis_frames16(const st_dims* d, WS& w, void* stream)
@@ -1482,8 +1371,8 @@ static int synthesis_frames16(const st_dims* d, WS& w, void* stream)
     stg::StoreC ep{w.frs, R, d->N, d->N, (size_t)d->B * d->OT * d->N, crop ? stg::frame_major(ms, d->B) : ms};
     const stg::Crop16 cr{crop ? 1 : 0, d->B, d->H, d->N, d->N, d->y, ms.t_lo, R, 1};      // tile columns without a tap inside the crop (cls_fe_dft.py:113) are not computed: ola_loss_kernel never reads them
     const int ns = frames_split(R);
-    if (gemm_ht(d->prec) == 2) ST_TRY((stg::launch16_nt<2>(ra, rb, ep, R, d->N, KP, ns, st_stream(stream), true, &cr)));
-    else ST_TRY((stg::launch16_nt<1>(ra, rb, ep, R, d->N, KP, ns, st_stream(stream), true, &cr)));
+    if (gemm_ht(d->prec) == 2) ST_TRY((stg::launch16_nt<2>(ra, rb, ep, R, d->N, KP, ns, st_stream(stream), &cr)));
+    else ST_TRY((stg::launch16_nt<1>(ra, rb, ep, R, d->N, KP, ns, st_stream(stream), &cr)));
     ST_LAUNCHED("synthesis_frames"); return ST_OK;
 }
 static int synthesis_dgrad16(const st_dims* d, WS& w, void* stream)
@@ -1501,8 +1390,8 @@ static int synthesis_dgrad16(const st_dims* d, WS& w, void* stream)
         if (gemm_ht(d->prec) == 2) ST_TRY((stg::launch16_nt256<2>(ra, rb, ep, R, KP, d->N, ns, st_stream(stream))));
         else ST_TRY((stg::launch16_nt256<1>(ra, rb, ep, R, KP, d->N, ns, st_stream(stream))));
     }
-    else if (gemm_ht(d->prec) == 2) ST_TRY((stg::launch16_nt<2>(ra, rb, ep, R, KP, d->N, ns, st_stream(stream), true, &cr)));
-    else ST_TRY((stg::launch16_nt<1>(ra, rb, ep, R, KP, d->N, ns, st_stream(stream), true, &cr)));
+    else if (gemm_ht(d->prec) == 2) ST_TRY((stg::launch16_nt<2>(ra, rb, ep, R, KP, d->N, ns, st_stream(stream), &cr)));
+    else ST_TRY((stg::launch16_nt<1>(ra, rb, ep, R, KP, d->N, ns, st_stream(stream), &cr)));
     ST_LAUNCHED("synthesis_dgrad"); return ST_OK;
 }
 // k-slices of a 16-bit weight-gradient GEMM: about two workgroups per CU (their time is staging, not matrix work), never slices under
@@ -1510,7 +1399,7 @@ static int synthesis_dgrad16(const st_dims* d, WS& w, void* stream)
 static int g16_wsplit(const st_dims* d, int R)
 {
     const int KP = st_kp_of(d->F), tiles = ((KP + 127) / 128) * (d->N / 128);
-    int s = g_g16_split > 0 ? g_g16_split : (2 * num_cus()) / (tiles > 0 ? tiles : 1);
+    int s = (2 * num_cus()) / (tiles > 0 ? tiles : 1);
     const int cap = R / 128; if (s > cap) s = cap;
     const int room = (int)(st_wgrad_ws_floats(d) / ((size_t)KP * d->N)); if (s > room) s = room;
     return s < 1 ? 1 : s;
@@ -1542,8 +1431,7 @@ static int wgrad16(const st_dims* d, const unsigned short* A, unsigned SA1, cons
     }
     stg::StoreC ep{slabs + (size_t)m0 * d->N, M, d->N, d->N, (size_t)KP * d->N, stg::all_frames(1)};
     const int ht = gemm_ht(d->prec);
-    if (g_g16_bk == 32) { if (ht == 2) ST_TRY((stg::launch16_tn<2, 32>(j, ep, M, d->N, ns, st_stream(stream)))); else ST_TRY((stg::launch16_tn<1, 32>(j, ep, M, d->N, ns, st_stream(stream)))); }
-    else { if (ht == 2) ST_TRY((stg::launch16_tn<2, 64>(j, ep, M, d->N, ns, st_stream(stream)))); else ST_TRY((stg::launch16_tn<1, 64>(j, ep, M, d->N, ns, st_stream(stream)))); }
+    if (ht == 2) ST_TRY((stg::launch16_tn<2, 64>(j, ep, M, d->N, ns, st_stream(stream)))); else ST_TRY((stg::launch16_tn<1, 64>(j, ep, M, d->N, ns, st_stream(stream))));
     return ST_OK;
 }
 
@@ -1644,7 +1532,7 @@ static int backward_ae(const st_dims* d, const Layout& L, const float* params, f
                        const stm::NyqJob* syn_nyq = nullptr)
 {   // syn_slabs > 0: the synthesis weight-gradient slabs in w.wg are still to be summed (done by post_ae_kernel)
     const float* ae_m = params + L.offs[4]; const float* ae_p = params + L.offs[22];
-    bool deferred = true, sink_used = false, syn_done = false;
+    bool deferred = true;
     const PolarSink sink{w.re, w.im, g_mag, w.g16 ? nullptr : w.dG, w.g16 ? w.dG16 : nullptr};
     stw::SynReduce syn{};
     if (syn_slabs > 0 && ae_is_wide(d)) {              // wide geometries: the synthesis slab sum rides in the gradient-finish launch of the autoencoder backward
@@ -1652,25 +1540,9 @@ static int backward_ae(const st_dims* d, const Layout& L, const float* params, f
         syn.nyq = stm::NyqJob{}; syn.nyq.on = 0; if (syn_nyq) syn.nyq = *syn_nyq;
     }
     ST_TRY(ae_bwd_impl(d, w.mag, w.phs, knobs, ae_m, ae_p, w.mag_hat, w.phs_hat, w.dAA, g_mag_hat, reg_coef, w.dmag, w.dphs,
-                       w.aews, grads + L.offs[4], grads + L.offs[22], true, stream, &deferred, &sink, &sink_used, syn.wg ? &syn : nullptr, &syn_done,
+                       w.aews, grads + L.offs[4], grads + L.offs[22], true, stream, &deferred, &sink, syn.wg ? &syn : nullptr,
                        (d->clip_all && ae_is_wide(d)) ? w.norm_e : nullptr, &w.n_norm_e));      // the forward left its AE state in w.aews
-    if (syn.wg && !syn_done) {                         // the path taken had no launch to ride in (all-GEMM variant): the reduce as a launch of its own
-        hipLaunchKernelGGL(stm::wgrad_reduce_kernel, dim3(st_norm_partials(d)), dim3(256), 0, st_stream(stream),
-                           syn.wg, syn.nz, syn.gSr, syn.gSi, syn.norm_s, d->N, d->F, L.KP, 1, 0, 2 * d->F, (float*)nullptr, syn.nyq);
-        ST_LAUNCHED("synthesis_wgrad_reduce");
-    }
-    if (syn.wg) syn_slabs = 0;
-    if (sink_used) return ST_OK;                       // wide geometries: the polar backward ran inside wide_dv_polar_kernel
-    if (!deferred) {
-        ST_REQ(syn_slabs == 0, "internal: deferred synthesis slabs on a path without post_ae_kernel");
-        if (w.g16) {                       // wide geometries: the polar backward is its own launch; d G goes out in the GEMM operand type
-            const int R = d->B * d->T, KP = st_kp_of(d->F);
-            hipLaunchKernelGGL(stm::polar_bwd_kernel, dim3((KP / 2 + 255) / 256, R), dim3(256), 0, st_stream(stream),
-                               w.re, w.im, w.dmag, w.dphs, g_mag, (float*)nullptr, R, d->F, KP, gemm_ht(d->prec) == 2 ? 65504.0f : 0.0f, w.dG16, gemm_ht(d->prec));
-            ST_LAUNCHED("polar_bwd"); return ST_OK;
-        }
-        return st_polar_bwd(d, w.re, w.im, w.dmag, w.dphs, g_mag, w.dG, stream);
-    }
+    if (!deferred) return ST_OK;                       // wide geometries: the gradient-finish launch summed the partials (and the synthesis slabs), and the polar backward ran inside wide_dv_polar_kernel
     stm::PostAeArgs a;
     a.ws = w.aews + 2 * ae_h4_floats(d); a.nparts = ae_use_split(d) ? ae_split_grid(d) : ae_bwd_grid(d); a.PG = L.PG; a.g_m = grads + L.offs[4]; a.g_p = grads + L.offs[22];
     a.n_red_x = (L.PG + 63) / 64; a.n_red = 2 * a.n_red_x;
@@ -1731,7 +1603,7 @@ static int analysis_wgrad_half(const st_dims* d, const Layout& L, float* grads, 
     const stg::TNOperand ta{w.dG + m0, (unsigned)(d->T * KP), (unsigned)KP}, tb{w.xp, (unsigned)(d->L + 2 * d->N), (unsigned)d->H};
     if (w.g16) {
         const int tiles = ((KP / 2 + 127) / 128) * (N / 128);
-        ns = g_g16_split > 0 ? g_g16_split : (2 * num_cus()) / (tiles > 0 ? tiles : 1);
+        ns = (2 * num_cus()) / (tiles > 0 ? tiles : 1);
         if (ns > R / 128) ns = R / 128; if (ns > room) ns = room; if (ns < 1) ns = 1;
         ST_TRY(wgrad16(d, w.dG16, (unsigned)(d->T * KP), w.xp16, (unsigned)(d->L + 2 * d->N), ma, R, w.wg, ns, stream, m0, KP / 2, (g_g16_crop & 8) ? d->L : 0));
         if (!half) { *nyq_io = stm::NyqJob{}; nyq_io->on = 0; }
@@ -2166,7 +2038,7 @@ extern "C" int st_fe_analysis_fwd(const float* x, int B, int L, const float* W, 
     stg::FramedNT<false> al{x, L, hop, pad, R, KW, 1.0f, stg::all_frames(T)};
     stg::PlainNT bl{W, C, KW, KW, stg::all_frames(1)};
     stg::BiasStore ep{out, bias, R, C, C};
-    stg::launch<2, 16>(al, bl, ep, R, C, KW, 1, st_stream(stream), g_dbg);
+    stg::launch<2, 16>(al, bl, ep, R, C, KW, 1, st_stream(stream));
     ST_LAUNCHED("fe_analysis_fwd"); return ST_OK;
 }
 static int fe_frames_ola(const float* xft, int B, int T, const float* W, int C, int KW, int hop, int crop, int len,
@@ -2176,7 +2048,7 @@ static int fe_frames_ola(const float* xft, int B, int T, const float* W, int C, 
     stg::PlainNT al{xft, R, C, C, stg::all_frames(1)};
     stg::PlainTN bl{W, C, KW, KW, stg::all_frames(1)};
     stg::StoreC ep{frs, R, KW, KW, 0, stg::all_frames(1)};
-    stg::launch<2, 16>(al, bl, ep, R, KW, C, 1, st_stream(stream), g_dbg);
+    stg::launch<2, 16>(al, bl, ep, R, KW, C, 1, st_stream(stream));
     hipLaunchKernelGGL(stm::ola_crop_kernel, dim3((len + 255) / 256, B), dim3(256), 0, st_stream(stream), frs, out, T, KW, hop, crop, len);
     return ST_OK;
 }
@@ -2230,7 +2102,7 @@ extern "C" int st_fe_analysis_bwd(const float* x, int B, int L, const float* W, 
         stg::PlainTN al{g_out, R, C, C, stg::all_frames(1)};
         stg::FramedTN<false> bl{x, L, hop, pad, R, KW, 1.0f, stg::all_frames(T)};
         stg::StoreC ep{slabs, C, KW, KW, (size_t)C * KW, stg::all_frames(1)};
-        stg::launch<3, 16>(al, bl, ep, C, KW, R, ns, st_stream(stream), g_dbg);
+        stg::launch<3, 16>(al, bl, ep, C, KW, R, ns, st_stream(stream));
         const size_t n = (size_t)C * KW;
         hipLaunchKernelGGL(stm::sum_slabs_flat_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st_stream(stream), slabs, ns, n, gW);
     }
@@ -2254,13 +2126,13 @@ extern "C" int st_fe_synthesis_bwd(const float* xft, int B, int T, const float* 
         stg::FramedNT<true> al{gp, len, hop, crop, R, KW, 1.0f, stg::all_frames(T)};
         stg::PlainNT bl{W, C, KW, KW, stg::all_frames(1)};
         stg::StoreC ep{g_xft, R, C, C, 0, stg::all_frames(1)};
-        stg::launch<2, 16>(al, bl, ep, R, C, KW, 1, st_stream(stream), g_dbg);
+        stg::launch<2, 16>(al, bl, ep, R, C, KW, 1, st_stream(stream));
     }
     {
         stg::PlainTN al{xft, R, C, C, stg::all_frames(1)};
         stg::FramedTN<true> bl{gp, len, hop, crop, R, KW, 1.0f, stg::all_frames(T)};
         stg::StoreC ep{slabs, C, KW, KW, (size_t)C * KW, stg::all_frames(1)};
-        stg::launch<3, 16>(al, bl, ep, C, KW, R, ns, st_stream(stream), g_dbg);
+        stg::launch<3, 16>(al, bl, ep, C, KW, R, ns, st_stream(stream));
         const size_t n = (size_t)C * KW;
         hipLaunchKernelGGL(stm::sum_slabs_flat_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st_stream(stream), slabs, ns, n, gW);
     }
@@ -2474,17 +2346,17 @@ static int attr_prepare(const st_dims* d)
         ST_PREP3((sta::ae_inner_fwd_kernel<AE_FWD_NW, 0>), (sta::ae_inner_fwd_kernel<AE_FWD_NW, 1>), (sta::ae_inner_fwd_kernel<AE_FWD_NW, 2>));
         ST_PREP3((sta::ae_inner_fwd_kernel<9, 0>), (sta::ae_inner_fwd_kernel<9, 1>), (sta::ae_inner_fwd_kernel<9, 2>));
         ST_PREP3((sta::ae_inner_fwd_kernel<12, 0>), (sta::ae_inner_fwd_kernel<12, 1>), (sta::ae_inner_fwd_kernel<12, 2>));
-        ST_PREP3((sta::ae_bwd_kernel<AE_BWD_NW, false, true, 0, 0>), (sta::ae_bwd_kernel<AE_BWD_NW, false, true, 1, 0>), (sta::ae_bwd_kernel<AE_BWD_NW, false, true, 2, 0>));
+        ST_PREP3((sta::ae_bwd_kernel<AE_BWD_NW, true, 0, 0>), (sta::ae_bwd_kernel<AE_BWD_NW, true, 1, 0>), (sta::ae_bwd_kernel<AE_BWD_NW, true, 2, 0>));
         ST_PREP3((stw::wide_dv_polar_kernel<0>), (stw::wide_dv_polar_kernel<1>), (stw::wide_dv_polar_kernel<2>));
     } else {
         ST_PREP3((sta::ae_fwd_kernel<AE_FWD_NW, 0>), (sta::ae_fwd_kernel<AE_FWD_NW, 1>), (sta::ae_fwd_kernel<AE_FWD_NW, 2>));
         if (ht == 1) ST_DYN_LDS((sta::ae_fwd32_kernel<AE_FWD_NW, 1>)); else if (ht == 2) ST_DYN_LDS((sta::ae_fwd32_kernel<AE_FWD_NW, 2>));
         if (ht == 0) { ST_DYN_LDS((sta::ae_fwd_kernel<11, 0>)); ST_DYN_LDS((sta::ae_fwd_kernel<11, 0, true>)); ST_DYN_LDS((sta::ae_fwd_kernel<AE_FWD_NW, 0, true>));
-                       ST_DYN_LDS((sta::ae_bwd_kernel<AE_BWD_NW, false, false, 0, 0, true>)); ST_DYN_LDS((sta::ae_bwd_kernel<AE_BWD_NW, false, false, 0, 1, true>)); ST_DYN_LDS((sta::ae_bwd_kernel<AE_BWD_NW, false, false, 0, 2, true>)); }
+                       ST_DYN_LDS((sta::ae_bwd_kernel<AE_BWD_NW, false, 0, 0, true>)); ST_DYN_LDS((sta::ae_bwd_kernel<AE_BWD_NW, false, 0, 1, true>)); ST_DYN_LDS((sta::ae_bwd_kernel<AE_BWD_NW, false, 0, 2, true>)); }
         ST_PREP3((sta::ae_bwd_part_kernel<AE_SPLIT_NW, 1, 0, false>), (sta::ae_bwd_part_kernel<AE_SPLIT_NW, 1, 1, false>), (sta::ae_bwd_part_kernel<AE_SPLIT_NW, 1, 2, false>));
         ST_PREP3((sta::ae_bwd_part_kernel<AE_SPLIT_NW, 2, 0, false>), (sta::ae_bwd_part_kernel<AE_SPLIT_NW, 2, 1, false>), (sta::ae_bwd_part_kernel<AE_SPLIT_NW, 2, 2, false>));
-        if (d->T - d->OT == 16) ST_PREP3((sta::ae_bwd_kernel<AE_BWD_NW, false, false, 0, 2>), (sta::ae_bwd_kernel<AE_BWD_NW, false, false, 1, 2>), (sta::ae_bwd_kernel<AE_BWD_NW, false, false, 2, 2>));
-        else ST_PREP3((sta::ae_bwd_kernel<AE_BWD_NW, false, false, 0, 0>), (sta::ae_bwd_kernel<AE_BWD_NW, false, false, 1, 0>), (sta::ae_bwd_kernel<AE_BWD_NW, false, false, 2, 0>));
+        if (d->T - d->OT == 16) ST_PREP3((sta::ae_bwd_kernel<AE_BWD_NW, false, 0, 2>), (sta::ae_bwd_kernel<AE_BWD_NW, false, 1, 2>), (sta::ae_bwd_kernel<AE_BWD_NW, false, 2, 2>));
+        else ST_PREP3((sta::ae_bwd_kernel<AE_BWD_NW, false, 0, 0>), (sta::ae_bwd_kernel<AE_BWD_NW, false, 1, 0>), (sta::ae_bwd_kernel<AE_BWD_NW, false, 2, 0>));
     }
 #undef ST_PREP3
     if (g_nt128 && gemm_ht(d->prec) == 0) ST_DYN_LDS((stg::gemm_nt128_kernel));
@@ -2498,10 +2370,10 @@ static int attr_prepare(const st_dims* d)
         }
     }
     if (use_planes(d)) {        // the 4-wave plane GEMM carries 67 KB of LDS (st_gemm_planes.h)
-        ST_DYN_LDS((stg::gemm_planes_kernel<4, 3, 1, stg::FramedNT<true>, stg::ChunkP, stg::PolarStore>));
-        ST_DYN_LDS((stg::gemm_planes_kernel<8, 3, 1, stg::FramedNT<true>, stg::ChunkP, stg::PolarStore>));
-        ST_DYN_LDS((stg::gemm_planes_kernel<4, 3, 1, stg::PlainNT, stg::ChunkP, stg::StoreC>));
-        ST_DYN_LDS((stg::gemm_planes_kernel<4, 3, 1, stg::FramedNT<true>, stg::ChunkP, stg::StoreC>));
+        ST_DYN_LDS((stg::gemm_planes_kernel<4, 3, stg::FramedNT<true>, stg::ChunkP, stg::PolarStore>));
+        ST_DYN_LDS((stg::gemm_planes_kernel<8, 3, stg::FramedNT<true>, stg::ChunkP, stg::PolarStore>));
+        ST_DYN_LDS((stg::gemm_planes_kernel<4, 3, stg::PlainNT, stg::ChunkP, stg::StoreC>));
+        ST_DYN_LDS((stg::gemm_planes_kernel<4, 3, stg::FramedNT<true>, stg::ChunkP, stg::StoreC>));
     }
     (void)num_cus();
     return ST_OK;

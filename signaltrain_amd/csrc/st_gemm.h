@@ -381,19 +381,15 @@ template <class L, class = void> struct has_tn_params { static constexpr bool va
 template <class L> struct has_tn_params<L, decltype((void)L::kParams)> { static constexpr bool value = L::kParams; };
 
 // ------------------------------------------------------------------------------ kernel
-// The timing-only ablation switches are COMPILE-TIME (build with -DST_GEMM_ABLATE for tools/gemm_ablate*.py): as run-time
+// The timing-only ablation switches are COMPILE-TIME (build with EXTRA=-DST_GEMM_ABLATE=<bits>; the Makefile never sets it): as run-time
 // tests they split the k-loop body into several basic blocks, and the compiler then shuttled all 48 accumulator registers
 // between AGPRs and VGPRs on every iteration (96 extra instructions per 24 MFMAs).
-#ifdef ST_GEMM_ABLATE
-#define ST_DBG(bit_) (dbg & (bit_))
-#else
-#define ST_DBG(bit_) false
+// bit 0: skip loads / stores in the k-loop; bit 1: skip barriers; bit 2: skip MFMAs.  Results are invalid when non-zero.
+#ifndef ST_GEMM_ABLATE
+#define ST_GEMM_ABLATE 0
 #endif
-// BKT = k-tile depth (32: 64 KB LDS/WG, 2 WGs/CU; 16: 36 KB, 4 WGs/CU -- better for the small-M split-K GEMMs).
-// dbg: timing-only ablation switches (bit0 skip loads/stores in the k-loop, bit1 skip barriers, bit2 skip MFMAs).
-// MI = 32-row blocks per wave: MI = 1 is the 32 x 96 wave strip; WAVES_M = 1, MI = 3 lets ONE wave own a 96 x 96 tile
-// (9 accumulators): same global traffic per MFMA as three waves sharing the tile, half the LDS fragment reads (B is read
-// once instead of three times) and no cross-wave barrier stalls -- for the split-K weight-gradient GEMMs.
+#define ST_DBG(bit_) (ST_GEMM_ABLATE & (bit_))
+// BKT = k-tile depth (32: 64 KB LDS/WG, 2 WGs/CU; 16: 36 KB, 4 WGs/CU -- better for the small-M split-K GEMMs).  A wave owns a 32 x 96 strip.
 // XT: M/N-contiguous (TN-type) operands are transposed on the way into LDS -- a thread loads a 4(k) x 4(row) micro-tile as four
 // float4 and writes four k-quads -- into a K-QUAD-MAJOR tile  X[k / 4][row][k % 4]  (16-byte slots, no padding), so that the MFMA
 // fragments of such an operand are fetched exactly like those of a K-contiguous one: ds_read_b128 of 4 consecutive k, HK / 4 reads
@@ -407,11 +403,11 @@ template <class L> struct has_tn_params<L, decltype((void)L::kParams)> { static 
 // weight-gradient GEMM is SLOWER (173 vs 145 us) -- the kernel is not bound by its fragment reads.  Kept selectable
 // (st_set_tuning(7001)); the default stays k-major.
 __device__ __forceinline__ int xq_slot(const int row, const int q) { (void)q; return (row & ~3) | ((row + (row >> 3)) & 3); }
-template <int WAVES_M, int BKT, int MI, bool XT, class AL, class BL, class EPI>
+template <int WAVES_M, int BKT, bool XT, class AL, class BL, class EPI>
 __global__ void __launch_bounds__(WAVES_M * 64)
-gemm_kernel(const AL al, const BL bl, const EPI epi, const int K, const int ksplit, const int dbg)
+gemm_kernel(const AL al, const BL bl, const EPI epi, const int K, const int ksplit)
 {
-    constexpr int BM = 32 * WAVES_M * MI, NT = 64 * WAVES_M;
+    constexpr int BM = 32 * WAVES_M, NT = 64 * WAVES_M;
     constexpr int PKT = BKT + 4;                         // row pitch: 36 (BK 32) / 20 (BK 16) floats, both conflict-free for b128
     constexpr bool A_T = AL::kTN && XT, A_K = AL::kTN && !XT;       // transposed staging / k-major staging
     constexpr bool B_T = BL::kTN && XT, B_K = BL::kTN && !XT;
@@ -574,13 +570,11 @@ gemm_kernel(const AL al, const BL bl, const EPI epi, const int K, const int kspl
         }
     };
 
-    f32x16 acc[MI][NJ];
+    f32x16 acc[NJ];
 #pragma unroll
-    for (int mi = 0; mi < MI; ++mi)
+    for (int j = 0; j < NJ; ++j)
 #pragma unroll
-        for (int j = 0; j < NJ; ++j)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[mi][j][i] = 0.f;
+        for (int i = 0; i < 16; ++i) acc[j][i] = 0.f;
 
     if (k_begin < k_end) {
         gload(k_begin);
@@ -589,16 +583,13 @@ gemm_kernel(const AL al, const BL bl, const EPI epi, const int K, const int kspl
         int cur = 0;
         const int h = lane >> 5, l31 = lane & 31;
         // NT: lane reads HK consecutive floats of its row; TN: lane reads column l31 of rows HK*h .. HK*h+HK-1
-        const int a_off = A_T ? 0 : (A_K ? (HK * h) * LDA + wave * (32 * MI) + l31 : (wave * (32 * MI) + l31) * LDA + HK * h);
-        constexpr int A_MI = A_K ? 32 : 32 * LDA;              // LDS offset between the wave's 32-row blocks
+        const int a_off = A_T ? 0 : (A_K ? (HK * h) * LDA + wave * 32 + l31 : (wave * 32 + l31) * LDA + HK * h);
         const int b_off = B_T ? 0 : (B_K ? (HK * h) * LDB + l31 : l31 * LDB + HK * h);
         // k-quad-major operands: float offset of (row, k-quad HK/4 * h + q) -- per lane, fixed across k-tiles
-        int a_xq[A_T ? MI : 1][A_T ? HK / 4 : 1], b_xq[B_T ? NJ : 1][B_T ? HK / 4 : 1];
+        int a_xq[A_T ? HK / 4 : 1], b_xq[B_T ? NJ : 1][B_T ? HK / 4 : 1];
         if constexpr (A_T) {
 #pragma unroll
-            for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-                for (int q = 0; q < HK / 4; ++q) { const int kq = (HK / 4) * h + q; a_xq[mi][q] = (kq * BM + xq_slot((wave * MI + mi) * 32 + l31, kq)) * 4; }
+            for (int q = 0; q < HK / 4; ++q) { const int kq = (HK / 4) * h + q; a_xq[q] = (kq * BM + xq_slot(wave * 32 + l31, kq)) * 4; }
         }
         if constexpr (B_T) {
 #pragma unroll
@@ -616,15 +607,13 @@ gemm_kernel(const AL al, const BL bl, const EPI epi, const int K, const int kspl
             const float* as = As + cur * A_SZ + a_off;
             const float* bs = Bs + cur * B_SZ + b_off;
             if (!ST_DBG(4)) {
-                float af[MI][HK], bf[NJ][HK];
+                float af[HK], bf[NJ][HK];
                 if constexpr (!A_K) {
 #pragma unroll
-                    for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-                        for (int q = 0; q < HK / 4; ++q) {
-                            const float4 v = *reinterpret_cast<const float4*>(A_T ? as + a_xq[A_T ? mi : 0][A_T ? q : 0] : as + mi * A_MI + 4 * q);
-                            af[mi][4 * q] = v.x; af[mi][4 * q + 1] = v.y; af[mi][4 * q + 2] = v.z; af[mi][4 * q + 3] = v.w;
-                        }
+                    for (int q = 0; q < HK / 4; ++q) {
+                        const float4 v = *reinterpret_cast<const float4*>(A_T ? as + a_xq[A_T ? q : 0] : as + 4 * q);
+                        af[4 * q] = v.x; af[4 * q + 1] = v.y; af[4 * q + 2] = v.z; af[4 * q + 3] = v.w;
+                    }
                 }
                 if constexpr (!B_K) {
 #pragma unroll
@@ -637,25 +626,21 @@ gemm_kernel(const AL al, const BL bl, const EPI epi, const int K, const int kspl
                 }
 #pragma unroll
                 for (int kk = 0; kk < HK; ++kk) {
-                    float a[MI], b[NJ];
-#pragma unroll
-                    for (int mi = 0; mi < MI; ++mi) { if constexpr (A_K) a[mi] = as[kk * LDA + mi * A_MI]; else a[mi] = af[mi][kk]; }
+                    float a, b[NJ];
+                    if constexpr (A_K) a = as[kk * LDA]; else a = af[kk];
 #pragma unroll
                     for (int j = 0; j < NJ; ++j) { if constexpr (B_K) b[j] = bs[kk * LDB + 32 * j]; else b[j] = bf[j][kk]; }
 #pragma unroll
-                    for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-                        for (int j = 0; j < NJ; ++j)
-                            acc[mi][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[mi], b[j], acc[mi][j], 0, 0, 0);
+                    for (int j = 0; j < NJ; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b[j], acc[j], 0, 0, 0);
                 }
-                if constexpr (A_K && B_K && MI == 1) {
+                if constexpr (A_K && B_K) {
                     // k-major operands: one scalar A and NJ scalar B fragments per k-step.  Recipe: the LDS reads of step k+1 are
                     // issued before the MFMAs of step k (left alone the compiler emits ds_read / s_waitcnt / MFMA triplets).
                     __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
 #pragma unroll
                     for (int kk = 0; kk < HK; ++kk) {
                         __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
-                        __builtin_amdgcn_sched_group_barrier(0x008, MI * NJ, 0);
+                        __builtin_amdgcn_sched_group_barrier(0x008, NJ, 0);
                     }
                 }
             }
@@ -665,8 +650,7 @@ gemm_kernel(const AL al, const BL bl, const EPI epi, const int K, const int kspl
             cur ^= 1;
         }
     }
-#pragma unroll
-    for (int mi = 0; mi < MI; ++mi) epi(m_blk + (wave * MI + mi) * 32, n_blk, acc[mi]);
+    epi(m_blk + wave * 32, n_blk, acc);
 }
 
 // ------------------------------------------------------------------------------ mixed-precision variant
@@ -1065,16 +1049,15 @@ static inline int launch_half(const AL& al, const BL& bl, const EPI& epi, int M,
     return 0;
 }
 
-template <int WAVES_M, int BKT, int MI = 1, bool XT = false, class AL, class BL, class EPI>
-static inline void launch(const AL& al, const BL& bl, const EPI& epi, int M, int Nc, int K, int nsplit,
-                          hipStream_t s, int dbg = 0)
+template <int WAVES_M, int BKT, bool XT = false, class AL, class BL, class EPI>
+static inline void launch(const AL& al, const BL& bl, const EPI& epi, int M, int Nc, int K, int nsplit, hipStream_t s)
 {
-    constexpr int BM = 32 * WAVES_M * MI;
+    constexpr int BM = 32 * WAVES_M;
     int ksplit = K;
     if (nsplit > 1) ksplit = st_round_up((K + nsplit - 1) / nsplit, BK);
     // exactly nsplit z-slices: a slice that starts past K stores zeros, so consumers sum a fixed slab count
     dim3 grid((Nc + BN - 1) / BN, (M + BM - 1) / BM, nsplit > 1 ? nsplit : 1);
-    hipLaunchKernelGGL((gemm_kernel<WAVES_M, BKT, MI, XT, AL, BL, EPI>), grid, dim3(WAVES_M * 64), 0, s, al, bl, epi, K, ksplit, dbg);
+    hipLaunchKernelGGL((gemm_kernel<WAVES_M, BKT, XT, AL, BL, EPI>), grid, dim3(WAVES_M * 64), 0, s, al, bl, epi, K, ksplit);
 }
 
 }  // namespace stg

@@ -175,7 +175,7 @@ gemm16_nt_kernel(const Rows16 ra, const Rows16 rb, const EPI epi, const int K, c
 // K % 64 == 0 only (analysis forward: K = N; synthesis data gradient: K = N).
 template <int HT, class EPI>
 __global__ void __launch_bounds__(768)
-gemm16_nt256_kernel(const Rows16 ra, const Rows16 rb, const EPI epi, const int K, const int ksplit, const int dbg)
+gemm16_nt256_kernel(const Rows16 ra, const Rows16 rb, const EPI epi, const int K, const int ksplit)
 {
     typedef typename frag16<HT>::type frag_t;
     constexpr int A_BYTES = 256 * 128, B_BYTES = 128 * 128, STAGE = A_BYTES + B_BYTES, NST = 3;
@@ -188,7 +188,7 @@ gemm16_nt256_kernel(const Rows16 ra, const Rows16 rb, const EPI epi, const int K
     const int m_blk = tby * 256, n_blk = tbx * 128;
     const int k_begin = tbz * ksplit;
     const int k_end = (k_begin + ksplit < K) ? k_begin + ksplit : K;
-    const int nt = (dbg & 8) ? 1 : (k_end - k_begin) / 64;
+    const int nt = (k_end - k_begin) / 64;
     if (nt <= 0) {                                                          // a k-slice past K: zeros (consumers only)
         if (wave < 8) {
             f32x16 z[2];
@@ -234,7 +234,7 @@ gemm16_nt256_kernel(const Rows16 ra, const Rows16 rb, const EPI epi, const int K
         int stage = 0;
         for (int t = 0; t < nt; ++t) {
             // start of phase 2 t: group B fetched tile t - 1 during phase 2 t - 1 -> stage (t - 1) % 3 == (t + 2) % 3 is free
-            if (!(dbg & 1)) issue(t + 2, stage >= 1 ? stage - 1 : NST - 1);
+            issue(t + 2, stage >= 1 ? stage - 1 : NST - 1);
             asm volatile("s_waitcnt vmcnt(12)" ::: "memory");              // tile t + 1 (issued a whole tile ago) has landed: group A reads it in phase 2 t + 2
             __builtin_amdgcn_s_barrier();                                   // end of phase 2 t
             __builtin_amdgcn_s_barrier();                                   // end of phase 2 t + 1
@@ -417,11 +417,11 @@ gemm16_tn_kernel(const TN16Job j, const StoreC epi, const int ksplit)
 
 // ------------------------------------------------------------------------------ host side
 template <int HT, class EPI>
-static inline int launch16_nt(const Rows16& ra, const Rows16& rb, const EPI& epi, int M, int Nc, int K, int nsplit, hipStream_t s, bool allow64 = true, const Crop16* crop = nullptr)
+static inline int launch16_nt(const Rows16& ra, const Rows16& rb, const EPI& epi, int M, int Nc, int K, int nsplit, hipStream_t s, const Crop16* crop = nullptr)
 {
     dim3 grid((Nc + 127) / 128, (M + 127) / 128, nsplit > 1 ? nsplit : 1);
     Crop16 cr{}; cr.mode = 0; if (crop) cr = *crop; cr.nsplit = nsplit > 1 ? nsplit : 1;
-    const bool k64 = allow64 && K % 64 == 0 && (nsplit <= 1 || (K / 64) % nsplit == 0);
+    const bool k64 = K % 64 == 0 && (nsplit <= 1 || (K / 64) % nsplit == 0);
     if (k64) {
         int ksplit = K; if (nsplit > 1) ksplit = st_round_up((K + nsplit - 1) / nsplit, 64);
         constexpr size_t lds = (size_t)4 * 128 * (64 + 8) * sizeof(h16_t);
@@ -437,12 +437,12 @@ static inline int launch16_nt(const Rows16& ra, const Rows16& rb, const EPI& epi
 template <int HT, class EPI>
 static inline bool nt256_fits(int K, int nsplit) { return K % 64 == 0 && K / 64 >= (nsplit > 1 ? nsplit : 1); }
 template <int HT, class EPI>
-static inline int launch16_nt256(const Rows16& ra, const Rows16& rb, const EPI& epi, int M, int Nc, int K, int nsplit, hipStream_t s, int dbg = 0)
+static inline int launch16_nt256(const Rows16& ra, const Rows16& rb, const EPI& epi, int M, int Nc, int K, int nsplit, hipStream_t s)
 {
     int ksplit = K; if (nsplit > 1) ksplit = st_round_up((K + nsplit - 1) / nsplit, 64);
     constexpr size_t lds = (size_t)3 * (256 + 128) * 128;
     const int rc = ::ensure_dyn_lds((const void*)gemm16_nt256_kernel<HT, EPI>, "gemm16_nt256_kernel"); if (rc) return rc;
-    hipLaunchKernelGGL((gemm16_nt256_kernel<HT, EPI>), dim3((Nc + 127) / 128, (M + 255) / 256, nsplit > 1 ? nsplit : 1), dim3(768), lds, s, ra, rb, epi, K, ksplit, dbg);
+    hipLaunchKernelGGL((gemm16_nt256_kernel<HT, EPI>), dim3((Nc + 127) / 128, (M + 255) / 256, nsplit > 1 ? nsplit : 1), dim3(768), lds, s, ra, rb, epi, K, ksplit);
     return 0;
 }
 template <int HT, int BKH>

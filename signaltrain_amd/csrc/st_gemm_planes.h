@@ -117,16 +117,16 @@ struct Stager<L, ROWS, NT_, PL, true> {
 #ifndef ST_PL_ABLATE
 #define ST_PL_ABLATE 0
 #endif
-template <int WAVES_M, int PL, int MI, class AL, class BL, class EPI>
+template <int WAVES_M, int PL, class AL, class BL, class EPI>
 __global__ void __launch_bounds__(WAVES_M * 64)
 gemm_planes_kernel(const AL al, const BL bl, const EPI epi, const int K, const int ksplit)
 {
     static_assert(PL == 1 || PL == 3, "one bfloat16 plane (rounded operands) or the three-plane split");
     constexpr int BKP = 16, LD = BKP + 8;
-    constexpr int BM = 32 * MI * WAVES_M, NT = 64 * WAVES_M;      // a wave owns MI x NJ accumulator blocks: (32 MI) x 96
+    constexpr int BM = 32 * WAVES_M, NT = 64 * WAVES_M;      // a wave owns NJ accumulator blocks: 32 x 96
     constexpr int A_SZ = BM * LD + 16, B_SZ = BN * LD + 16;       // one plane of one buffer (+32 bytes: the three planes of a pre-split operand are written by ONE
                                                                   // ds_write_b128 -- 8-lane groups hold pieces of all three -- and must not share banks)
-    constexpr int NTERM = PL == 3 ? 6 : 1, NM = NTERM * NJ * MI;
+    constexpr int NTERM = PL == 3 ? 6 : 1, NM = NTERM * NJ;
     extern __shared__ __attribute__((aligned(16))) unsigned short plds[];        // [2][PL][A_SZ] | [2][PL][B_SZ] | 16-byte dump slot per thread
     unsigned short* const As = plds;
     unsigned short* const Bs = plds + 2 * PL * A_SZ;
@@ -142,13 +142,11 @@ gemm_planes_kernel(const AL al, const BL bl, const EPI epi, const int K, const i
     sa.init(al, m_blk, tid); sb.init(bl, n_blk, tid);
     constexpr int NSA = Stager<AL, BM, NT, PL>::NS, NSB = Stager<BL, BN, NT, PL>::NS, NS = NSA + NSB;
 
-    f32x16 acc[MI][NJ];
+    f32x16 acc[NJ];
 #pragma unroll
-    for (int mi = 0; mi < MI; ++mi)
+    for (int j = 0; j < NJ; ++j)
 #pragma unroll
-        for (int j = 0; j < NJ; ++j)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[mi][j][i] = 0.f;
+        for (int i = 0; i < 16; ++i) acc[j][i] = 0.f;
 
     if (k_begin < k_end) {
         sa.gload(al, k_begin, 0); sb.gload(bl, k_begin, 0);
@@ -160,9 +158,9 @@ gemm_planes_kernel(const AL al, const BL bl, const EPI epi, const int K, const i
         { const int k1 = k_begin + BKP < k_end ? k_begin + BKP : k_begin; sa.gload(al, k1, 1); sb.gload(bl, k1, 1); }     // tile 1 -> set 1
         __syncthreads();
         const int h = lane >> 5, l31 = lane & 31;
-        const int a_off = (wave * 32 * MI + l31) * LD + 8 * h;
+        const int a_off = (wave * 32 + l31) * LD + 8 * h;
         const int b_off = l31 * LD + 8 * h;
-        st_bf16x8 a[MI][PL], b[NJ][PL];
+        st_bf16x8 a[PL], b[NJ][PL];
         // one k-tile: tile `kt` sits in LDS buffer CUR; the registers of set 1 - CUR hold tile kt + 16 (staged now), set CUR receives tile kt + 32
         auto ktile = [&](const int kt, const int CUR) {
             const unsigned short* as = As + CUR * PL * A_SZ + a_off;
@@ -172,9 +170,7 @@ gemm_planes_kernel(const AL al, const BL bl, const EPI epi, const int K, const i
 #endif
             {
 #pragma unroll
-            for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-                for (int p = 0; p < PL; ++p) a[mi][p] = *reinterpret_cast<const st_bf16x8*>(as + p * A_SZ + 32 * mi * LD);
+            for (int p = 0; p < PL; ++p) a[p] = *reinterpret_cast<const st_bf16x8*>(as + p * A_SZ);
 #pragma unroll
             for (int j = 0; j < NJ; ++j)
 #pragma unroll
@@ -184,11 +180,11 @@ gemm_planes_kernel(const AL al, const BL bl, const EPI epi, const int K, const i
             constexpr int TA[6] = {0, 2, 1, 0, 1, 0}, TB[6] = {2, 0, 1, 1, 0, 0};      // smallest partial products first
 #pragma unroll
             for (int m = 0; m < NM; ++m) {
-                const int t = m / (NJ * MI), j = (m / MI) % NJ, mi = m % MI;
+                const int t = m / NJ, j = m % NJ;
 #if !(ST_PL_ABLATE & 16)
-                acc[mi][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[mi][PL == 3 ? TA[t] : 0], b[j][PL == 3 ? TB[t] : 0], acc[mi][j], 0, 0, 0);
+                acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[PL == 3 ? TA[t] : 0], b[j][PL == 3 ? TB[t] : 0], acc[j], 0, 0, 0);
 #else
-                acc[mi][j][0] += __builtin_bit_cast(float, (int)a[mi][0][0]) + __builtin_bit_cast(float, (int)b[j][0][0]);
+                acc[j][0] += __builtin_bit_cast(float, (int)a[0][0]) + __builtin_bit_cast(float, (int)b[j][0][0]);
 #endif
                 if (m == 0) {
                     // tile kt + 16 leaves its registers (past the end: stale data into a buffer that is not read again) ...
@@ -217,20 +213,19 @@ gemm_planes_kernel(const AL al, const BL bl, const EPI epi, const int K, const i
             if (kt + BKP < k_end) ktile(kt + BKP, 1);
         }
     }
-#pragma unroll
-    for (int mi = 0; mi < MI; ++mi) epi(m_blk + (wave * MI + mi) * 32, n_blk, acc[mi]);
+    epi(m_blk + wave * 32, n_blk, acc);
 }
 
-template <int WAVES_M, int PL, int MI = 1, class AL, class BL, class EPI>
+template <int WAVES_M, int PL, class AL, class BL, class EPI>
 static inline int launch_planes(const AL& al, const BL& bl, const EPI& epi, int M, int Nc, int K, int nsplit, hipStream_t s)
 {
-    constexpr int BM = 32 * MI * WAVES_M;
+    constexpr int BM = 32 * WAVES_M;
     constexpr size_t lds = ((size_t)2 * PL * ((BM + BN) * 24 + 32) + 8 * 64 * WAVES_M) * sizeof(unsigned short);
     int ksplit = K;
     if (nsplit > 1) ksplit = st_round_up((K + nsplit - 1) / nsplit, 16);
     dim3 grid((Nc + BN - 1) / BN, (M + BM - 1) / BM, nsplit > 1 ? nsplit : 1);
-    if (lds > 65536) { const int rc = ::ensure_dyn_lds((const void*)gemm_planes_kernel<WAVES_M, PL, MI, AL, BL, EPI>, "gemm_planes_kernel"); if (rc) return rc; }
-    hipLaunchKernelGGL((gemm_planes_kernel<WAVES_M, PL, MI, AL, BL, EPI>), grid, dim3(WAVES_M * 64), lds, s, al, bl, epi, K, ksplit);
+    if (lds > 65536) { const int rc = ::ensure_dyn_lds((const void*)gemm_planes_kernel<WAVES_M, PL, AL, BL, EPI>, "gemm_planes_kernel"); if (rc) return rc; }
+    hipLaunchKernelGGL((gemm_planes_kernel<WAVES_M, PL, AL, BL, EPI>), grid, dim3(WAVES_M * 64), lds, s, al, bl, epi, K, ksplit);
     return 0;
 }
 

@@ -232,17 +232,50 @@ int main(void)
 
 def test_tuning_defaults_are_frozen():
     """The shipped values of the library's diagnostic switches (ST_TUNING_LIST in st_api.hip), in st_get_tuning's order.  A changed default has to be
-    changed HERE as well -- it cannot ship unnoticed -- and tests/conftest.py asserts after every test that the live state equals these values."""
+    changed HERE as well -- it cannot ship unnoticed -- and tests/conftest.py asserts after every test that the live state equals these values.
+    The accepted codes are exactly those of the table k_tuning_codes: each moves one switch (16 / 32: two), everything else -- retired switches, retired
+    values of kept switches, arbitrary numbers -- is an error that names the code and changes nothing."""
     lib = _lib.load()
     n = lib.st_get_tuning(None, 0)
     cur, dflt = (C.c_int * n)(), (C.c_int * n)()
     assert lib.st_get_tuning(cur, n) == n and lib.st_tuning_defaults(dflt, n) == n
-    frozen = [0, -1, 1, 1, 0, 0, 0, 3, 1, 64, 0, 0, 0, 1, 1, 32, 1, 0, 1, 1, 0, 32, 16, 16, 200, 4, 3, 3, 1, 0, 0, 1, 1, 3, 15]
+    frozen = [-1, 1, 1, 0, 0, 0, 3, 1, 0, 1, 1, 1, 0, 32, 16, 0, 1, 1, 3, 15]
     assert list(dflt) == frozen and list(cur) == frozen
-    # a switch is visible in the state and reset restores it; timing-only ablations (invalid results) are not in the product build
-    assert lib.st_set_tuning(9500) == 0 and list((lib.st_get_tuning(cur, n), cur)[1]) != frozen
-    assert lib.st_reset_tuning() == 0 and list((lib.st_get_tuning(cur, n), cur)[1]) == frozen
-    assert lib.st_set_tuning(9681) != 0 and lib.st_set_tuning(96801) != 0 and b"ST_DIAG" in lib.st_last_error()
+
+    def state():
+        assert lib.st_get_tuning(cur, n) == n
+        return list(cur)
+    # a switch is visible in the state and reset restores it
+    assert lib.st_set_tuning(9500) == 0 and state() != frozen
+    assert lib.st_reset_tuning() == 0 and state() == frozen
+    # timing-only ablations (invalid results) are not in the product build: rejected, and the error names the offending code
+    assert lib.st_set_tuning(9681) != 0 and b"9681" in lib.st_last_error()
+    assert lib.st_set_tuning(96801) != 0 and b"96801" in lib.st_last_error()
+    # one code of each retired switch; arbitrary unknown codes; retired values of kept switches
+    rejected = [9800, 2002, 210, 1100, 6001, 3001, 4002, 9516, 9632, 9701, 5000, 9960, 9900, 9681, 96801] + [9999, 250, 99, 0, -1] + [9101, 9102, 101]
+    for code in rejected:
+        assert lib.st_set_tuning(code) != 0 and str(code).encode() in lib.st_last_error(), code
+        assert state() == frozen, code
+    # the table: switch index in st_get_tuning's order -> {code: stored value}
+    table = {0: {8000: 0, 8001: 1, 8002: -1}, 1: {8200: 0, 8201: 1}, 2: {8300: 0, 8301: 1}, 3: {9400: 0, 9401: 1}, 4: {9300: 0, 9301: 1}, 5: {9200: 0, 9201: 1},
+             6: {9100: 0, 9103: 3}, 7: {9600: 0, 9601: 1}, 8: {9690 + i: i for i in range(4)}, 9: {9950: 0, 9951: 1}, 10: {9500: 0, 9501: 1, 9580: 2, 9581: 1},
+             11: {9000: 0, 9001: 1}, 12: {7000: 0, 7001: 1}, 15: {100: 0, 102: 2}, 16: {8100: 0, 8101: 1}, 17: {9970: 0, 9971: 1},
+             18: {9540 + i: i for i in range(4)}, 19: {9560 + i: i for i in range(16)}}
+    try:
+        for idx, codes in table.items():
+            for code, val in codes.items():
+                want = list(frozen); want[idx] = val
+                assert lib.st_set_tuning(code) == 0 and state() == want, code
+                assert lib.st_reset_tuning() == 0 and state() == frozen
+        for bk in (16, 32):                                    # the k-tile depth sets the analysis GEMM's and the family's together
+            want = list(frozen); want[13] = want[14] = bk
+            assert lib.st_set_tuning(bk) == 0 and state() == want, bk
+            assert lib.st_reset_tuning() == 0 and state() == frozen
+        # no run-time ablations
+        assert lib.st_set_debug(0) == 0
+        assert lib.st_set_debug(256) != 0 and b"ablation" in lib.st_last_error() and state() == frozen
+    finally:
+        lib.st_reset_tuning()
 
 
 def test_kept_activation_bytes_follow_geometry_and_arithmetic():
