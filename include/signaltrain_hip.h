@@ -435,11 +435,27 @@ int st_model_input_grad(const st_dims* d, const float* params, void* ws, float* 
  * knobs tensor that requires grad -- nn_proc.py:92-93 repeats the settings over the rows of a window and concatenates them in front of
  * fnn_addknobs of both autoencoders (nn_proc.py:332-333).  g_knobs [B][K].  The exact, SLOW route: one forward + backward per window, whose
  * fnn_addknobs bias gradients are that window's row sums of d a5; the reference's training never asks for this gradient (knobs are data), so
- * the hot kernels carry nothing for it.  grads_scratch: st_param_offsets() floats, overwritten.  The saved-for-backward state of `ws` belongs
+ * the training step's kernels carry nothing for it (st_model_bwd_knobs below is the opt-in one-pass form).  grads_scratch: st_param_offsets() floats, overwritten.  The saved-for-backward state of `ws` belongs
  * to the last window afterwards: run st_model_fwd(save_for_backward = 1) again before st_model_bwd.  The per-window passes run in the arithmetic of
  * d->prec like the batch itself (round 5: a single window takes 16-bit layers on every geometry, st_effective_prec). */
 int st_model_knob_grad(const st_dims* d, const float* params, float* grads_scratch, const float* x, const float* knobs,
                        const float* g_y_hat, const float* g_mag_hat, const float* g_mag, void* ws, float* g_knobs, void* stream);
+
+/* The same gradient in ONE backward pass of the batch (opt-in; st_model_knob_grad above stays the exact reference route and the fallback).
+ * st_model_bwd_knobs is st_model_bwd -- same contract: asynchronous, no allocation, no host sync, same meaning of the upstream gradients, `grads`
+ * receives exactly what st_model_bwd writes, bit for bit -- and in the same pass g_knobs[B][K]: the autoencoder backward kernel that holds d a5 (the
+ * gradient at fnn_addknobs' pre-activation, fp32 also with 16-bit layers) also stores its column sums per 16-row group (a group never straddles a
+ * window) into `scratch` ([net][group][16] floats), and one small launch, one workgroup per window, sums a window's groups in ascending order
+ * (bit-repeatable) and applies the fp32 W5 of both nets.  Call it where st_model_bwd would be called, after st_model_fwd(save_for_backward = 1); the
+ * saved-for-backward state of `ws` is still that of the batch afterwards.  scratch: st_model_bwd_knobs_ws_floats(d) floats of the caller's, every
+ * element read is written by the same call (no clearing); st_workspace_bytes does not change.
+ * Refusals, before any launch, with the rule in st_last_error(): dims outside the family, a null pointer, K < 1 (ST_ERR_ARG); ST_ERR_UNSUPPORTED where
+ * a diagnostic switch away from its default (st_set_tuning 8000 / 8001 / 8200) routes the autoencoder backward to a kernel form that has no per-group
+ * output -- st_knob_grad_fused_supported (host only, no device work) then answers 0, as it does for K == 0 and for bad dims. */
+int    st_knob_grad_fused_supported(const st_dims* d);
+size_t st_model_bwd_knobs_ws_floats(const st_dims* d);      /* 2 nets x B x (KP/32) groups x 16 floats; 0 for bad dims */
+int    st_model_bwd_knobs(const st_dims* d, const float* params, float* grads, const float* x, const float* knobs,
+                          const float* g_y_hat, const float* g_mag_hat, const float* g_mag, void* ws, float* scratch, float* g_knobs, void* stream);
 
 /* ---- generic learned-basis front end: SURVEY.md row a15, signaltrain/cls_fe_dct_bases.py ------------------------------
  * Analysis.forward (:129-136)  = Conv1d(1 -> C, kernel KW, stride hop, padding pad, bias) transposed to [B][T][C];

@@ -97,6 +97,9 @@ SIGNATURES = {
     "st_model_fwd": (_i, [_D, _p, _p, _p, _p, _p, _p, _p, _i, _p]),
     "st_model_bwd": (_i, [_D, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     "st_model_knob_grad": (_i, [_D, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "st_knob_grad_fused_supported": (_i, [_D]),
+    "st_model_bwd_knobs_ws_floats": (C.c_size_t, [_D]),
+    "st_model_bwd_knobs": (_i, [_D, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     "st_loss_backward": (_i, [_D, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     "st_eval_step": (_i, [_D, _p, _p, _p, _p, _p, _p, _p, C.c_double, _p]),
     "st_loss_backward_p1": (_i, [_D, _p, _p, _p, _p, _p, _p, _p]),

@@ -837,6 +837,24 @@ __device__ __forceinline__ void db_flush(float* dst, float (&db)[OTL], const int
     }
 }
 
+// Column sums of one 16-row group's transposed tile (lane (g, c), reg r <-> row 4g + r, feature c) to dst[c]: the four registers first, then the four row
+// blocks g -- the order wgrad_regh + db_flush use for a bias gradient.  The cross-row steps are the two half-exchange VALU instructions of gfx950
+// (v_permlane16_swap: odd 16-lane rows of the first operand <-> even rows of the second; v_permlane32_swap: upper half <-> lower half) on two copies of the
+// value, not __shfl_xor: that is ds_bpermute, which would put two LDS-pipe round trips and a wait on the in-order LDS counter into a loop whose LDS traffic
+// (fragments, transposes) is prefetched a stage ahead, and needs two address registers in a kernel that sits at its register line.  Lanes g == 0 hold
+// (row0 + row1) + (row2 + row3) afterwards and store.
+__device__ __forceinline__ void group_colsum_store(float* __restrict__ dst, const f32x4& t, const int g, const int c)
+{
+    const float v = (t[0] + t[1]) + (t[2] + t[3]);
+    const unsigned u = __builtin_bit_cast(unsigned, v);
+    const auto p = __builtin_amdgcn_permlane16_swap(u, u, false, false);      // p[0]: rows {0, 0, 2, 2} of v; p[1]: rows {1, 1, 3, 3}
+    const float w = __builtin_bit_cast(float, (unsigned)p[0]) + __builtin_bit_cast(float, (unsigned)p[1]);
+    const unsigned x = __builtin_bit_cast(unsigned, w);
+    const auto q = __builtin_amdgcn_permlane32_swap(x, x, false, false);      // q[0]: lower half of w in both halves; q[1]: upper half
+    const float s = __builtin_bit_cast(float, (unsigned)q[0]) + __builtin_bit_cast(float, (unsigned)q[1]);
+    if (g == 0) dst[c] = s;
+}
+
 // INNER (wide geometries, st_ae_wide.h): only layers 2..8 -- layers 1 and 9 are feature-major GEMMs.  Pointer roles then:
 //   mag / phs         -> H1 [64][R] of the two nets (layer-1 outputs, R = B*FP columns)
 //   mag_hat / phs_hat -> dH8 [64][R] = W9^T dA9 (the kernel applies ELU'(h8) itself: h8 is recomputed)
@@ -853,7 +871,10 @@ constexpr int ae_bwd_lds_floats(int nw) { return (CL::BWD_TOTAL + nw * AE_BWD_SC
 // ELU' needs only the OUTPUT of ELU).  A third of the kernel's MFMAs, the ELU transcendentals and the forward fragment reads go; with nothing left at the top
 // of a group to hide a memory round trip behind, EVERY per-group input is loaded one full group ahead and IN PLACE: right behind the last use of a register
 // set in this group, the same registers are refilled for the next one (no second buffer, no copies).
-template <int NW, bool INNER = false, int BF = 0, int VAR = 1, bool SAVED = false>      // BF: 16-bit operands in all Linear-layer products (ST_PREC_*_ALL)
+// KG (st_model_bwd_knobs): the kernel also writes the per-group column sums of d a5 -- this group's share of the fnn_addknobs bias gradient rb5, taken
+// from the same unrounded fp32 daT5 -- to kg[net][group][16].  A group never straddles a window (ngroups = B * gpw), so the gpw rows of a window sum to
+// the bias gradient of that window alone, which is all d knobs needs (knob_grad_kernel, st_api.hip).  A compile-time flag: off, nothing is added.
+template <int NW, bool INNER = false, int BF = 0, int VAR = 1, bool SAVED = false, bool KG = false>      // BF: 16-bit operands in all Linear-layer products (ST_PREC_*_ALL)
 __global__ void __launch_bounds__(NW * 64, 1)
 ae_bwd_kernel(const float* __restrict__ mag, const float* __restrict__ phs, const float* __restrict__ knobs,
               const float* __restrict__ ae_m, const float* __restrict__ ae_p, const AEOffsets go, const int PG,
@@ -863,7 +884,8 @@ ae_bwd_kernel(const float* __restrict__ mag, const float* __restrict__ phs, cons
               const int B, const int T, const int OT, const int F, const int K, const int KP,
               const int to_lo, const int to_hi,      // live synthesis frames: dAA rows outside are treated as zero
               const int nslab, const size_t slab,     // dAA arrives as split-K slabs of the synthesis dgrad GEMM
-              const float* __restrict__ sv = nullptr)      // SAVED: the kept activations ([net][group][17 tiles][lane] float4)
+              const float* __restrict__ sv = nullptr,      // SAVED: the kept activations ([net][group][17 tiles][lane] float4)
+              float* __restrict__ kg = nullptr)            // KG: per-group column sums of d a5 ([net][group][16])
 {
     static_assert(!SAVED || (!INNER && BF == 0), "the kept-activation backward exists for the fused fp32 geometries");
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -1180,6 +1202,7 @@ ae_bwd_kernel(const float* __restrict__ mag, const float* __restrict__ phs, cons
             hT4k[0] = hT4[0];
             hT4k[1] = tt_splat<BF>(knT);                               // features 16 + c = knob c, every row
             wgrad_regh<1, 2, BF>(rW5, rb5, daT5, hT4k);
+            if constexpr (KG) group_colsum_store(kg + ((size_t)ae * ngroups + grp) * 16, daT5[0], g, c);      // grp: the group in hand, not the prefetched one
         }
         ST_REFILL(sv_load(svq, lane16, 7, s_h4));
         // layer 4 (16 -> 16)

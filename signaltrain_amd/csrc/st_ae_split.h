@@ -97,7 +97,8 @@ __device__ inline void ae_load_lds_tab(float* lds, const int total, const AETab 
 
 // grid (x: workgroups, y: net 0 = magnitude 'sf' / 1 = phase); NW = 8 waves = two per SIMD.  h4x / da4x: [net][group][lane] float4
 // exchange buffers (h4 in D layout as the forward kernel left it; d a4 likewise).  GM: an upstream d/d mag_hat arrives.
-template <int NW, int PART, int BF = 0, bool GM = false>
+// KG (decoder half only): also writes the per-group column sums of d a5 to kg[net][group][16] (see ae_bwd_kernel).
+template <int NW, int PART, int BF = 0, bool GM = false, bool KG = false>
 __global__ void __launch_bounds__(NW * 64)
 ae_bwd_part_kernel(const float* __restrict__ mag, const float* __restrict__ phs, const float* __restrict__ knobs,
                    const float* __restrict__ ae_m, const float* __restrict__ ae_p, const AEOffsets go, const int PG,
@@ -106,8 +107,9 @@ ae_bwd_part_kernel(const float* __restrict__ mag, const float* __restrict__ phs,
                    float* __restrict__ dmag, float* __restrict__ dphs, float* __restrict__ ws,
                    const float* __restrict__ h4x, float* __restrict__ da4x,
                    const int B, const int T, const int OT, const int F, const int K, const int KP,
-                   const int to_lo, const int to_hi, const int nslab, const size_t slab)
+                   const int to_lo, const int to_hi, const int nslab, const size_t slab, float* __restrict__ kg = nullptr)
 {
+    static_assert(!KG || PART == 1, "d a5 lives in the decoder half");
     static_assert(NW == 8, "the end-of-kernel reduction pairs waves w and w + 4");
     using P = CP<PART>;
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -258,6 +260,7 @@ ae_bwd_part_kernel(const float* __restrict__ mag, const float* __restrict__ phs,
                 hT4k[0] = hT4[0];
                 hT4k[1] = tt_splat<BF>(knT);
                 wgrad_regh<1, 2, BF>(rW5, rb5, daT5, hT4k);
+                if constexpr (KG) group_colsum_store(kg + ((size_t)ae * ngroups + grp) * 16, daT5[0], g, c);
             }
             {
                 float d0 = da4[0][0], d1 = da4[0][1], d2 = da4[0][2], d3 = da4[0][3];

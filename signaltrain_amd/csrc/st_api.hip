@@ -437,6 +437,17 @@ static size_t ae_sv_floats(const st_dims* d) { return (!ae_is_wide(d) && ae_ht(d
 static int ae_parts_max(const st_dims* d) { return ae_split_grid(d) > ae_bwd_grid(d) ? ae_split_grid(d) : ae_bwd_grid(d); }
 static bool ae_use_saved(const st_dims* d) { return g_ae_save && !ae_is_wide(d) && ae_ht(d->prec) == 0 && !ae_use_split(d); }
 static float* ae_sv_ptr(const st_dims* d, const Layout& L, float* aews) { return aews + 2 * ae_h4_floats(d) + (size_t)ae_parts_max(d) * 2 * L.PG; }
+// st_model_bwd_knobs: does the autoencoder backward this geometry / precision / tuning state routes to (behind a forward that kept its state) exist with the
+// per-group d a5 output?  Instantiated: the wide path's fused kernel, the kept-activation fp32 kernel and the 16-bit decoder half -- what the shipped
+// defaults reach.  A diagnostic switch away from its default (g_ae_split, g_ae_save) can route elsewhere.
+static const char* ae_kg_why(const st_dims* d)
+{
+    if (ae_is_wide(d)) return nullptr;
+    if (ae_use_split(d)) return ae_ht(d->prec) != 0 ? nullptr : "g_ae_split routes fp32 layers to the split kernels";
+    if (ae_ht(d->prec) != 0) return "g_ae_split routes 16-bit layers to the single kernel";
+    return ae_use_saved(d) ? nullptr : "g_ae_save is off: the recomputing fp32 kernel";
+}
+static bool ae_kg_route(const st_dims* d) { return ae_kg_why(d) == nullptr; }
 extern "C" size_t st_ae_fwd_ws_floats(const st_dims* d)
 {
     if (check_dims(d) != ST_OK) return 0;
@@ -895,8 +906,8 @@ static int ae_wide_bwd(const st_dims* d, const Layout& L, const float* mag, cons
                        const float* ae_m, const float* ae_p, const float* mag_hat, const float* phs_hat, const float* dAA,
                        const float* g_mag_hat, float reg_coef, float* dmag, float* dphs, WideWS& w, float* g_m, float* g_p,
                        bool have_fwd, void* stream, const PolarSink* sink = nullptr,
-                       const stw::SynReduce* syn = nullptr, float* norm_e = nullptr, int* n_norm_e = nullptr)
-{
+                       const stw::SynReduce* syn = nullptr, float* norm_e = nullptr, int* n_norm_e = nullptr, float* kg = nullptr)
+{   // kg (st_model_bwd_knobs): the fused kernel of layers 2..8 also writes the per-group column sums of d a5 there
     hipStream_t s = st_stream(stream);
     const int FP = L.KP / 2, F = d->F, T = d->T, OT = d->OT, R = (int)w.R;
     const int wide_ht = ae_ht(d->prec);
@@ -936,13 +947,15 @@ static int ae_wide_bwd(const st_dims* d, const Layout& L, const float* mag, cons
     {
         const size_t lds = (size_t)sta::ae_bwd_lds_floats(AE_BWD_NW) * sizeof(float);
         const int grid = ae_bwd_grid(d);
-#define ST_AE_INNER_BWD(HT_) do { ST_DYN_LDS((sta::ae_bwd_kernel<AE_BWD_NW, true, HT_, 0>)); \
-            hipLaunchKernelGGL((sta::ae_bwd_kernel<AE_BWD_NW, true, HT_, 0>), dim3(grid, 2), dim3(AE_BWD_NW * 64), lds, s, \
+#define ST_AE_INNER_BWD_K(HT_, KG_) do { ST_DYN_LDS((sta::ae_bwd_kernel<AE_BWD_NW, true, HT_, 0, false, KG_>)); \
+            hipLaunchKernelGGL((sta::ae_bwd_kernel<AE_BWD_NW, true, HT_, 0, false, KG_>), dim3(grid, 2), dim3(AE_BWD_NW * 64), lds, s, \
                                (const float*)w.H[0][0], (const float*)w.H[1][0], knobs, ae_m, ae_p, L.go, L.PG, \
                                (const float*)w.DA[0][7], (const float*)w.DA[1][7], (const float*)nullptr, (const float*)nullptr, 0.f, 0.f, \
-                               w.DA[0][0], w.DA[1][0], w.inner_ws, d->B, T, OT, F, d->K, L.KP, 0, 0, 1, (size_t)0); } while (0)
+                               w.DA[0][0], w.DA[1][0], w.inner_ws, d->B, T, OT, F, d->K, L.KP, 0, 0, 1, (size_t)0, (const float*)nullptr, kg); } while (0)
+#define ST_AE_INNER_BWD(HT_) do { if (kg) ST_AE_INNER_BWD_K(HT_, true); else ST_AE_INNER_BWD_K(HT_, false); } while (0)
         switch (wide_ht) { case 1: ST_AE_INNER_BWD(1); break; case 2: ST_AE_INNER_BWD(2); break; default: ST_AE_INNER_BWD(0); }
 #undef ST_AE_INNER_BWD
+#undef ST_AE_INNER_BWD_K
         inner_parts = grid;                          // summed by the second role of wide_grad_finish_kernel below (was a launch of its own)
     }
     for (int l = 1; l < 8; ++l) tab.out[l] = 0;                 // the finish kernel only scatters layers 1 and 9
@@ -978,8 +991,11 @@ static int ae_bwd_impl(const st_dims* d, const float* mag, const float* phs, con
                        const float* ae_m, const float* ae_p, const float* mag_hat, const float* phs_hat,
                        const float* dAA, const float* g_mag_hat, float reg_coef, float* dmag, float* dphs, float* ws,
                        float* g_m, float* g_p, bool have_fwd, void* stream, bool* defer_reduce = nullptr,
-                       const PolarSink* sink = nullptr, const stw::SynReduce* syn = nullptr, float* norm_e = nullptr, int* n_norm_e = nullptr)
+                       const PolarSink* sink = nullptr, const stw::SynReduce* syn = nullptr, float* norm_e = nullptr, int* n_norm_e = nullptr,
+                       float* kg = nullptr)
 {
+    // kg (st_model_bwd_knobs): the kernel that holds d a5 also writes its per-group column sums there ([net][group][16]); only the instantiations the shipped
+    // tuning defaults reach exist in that form (ae_kg_route)
     // defer_reduce: in -> the caller will sum the workgroup partials itself (post_ae_kernel, together with the polar backward);
     // out -> false if this geometry's path already reduced them (wide geometries)
     Layout L; ST_TRY(make_layout(d, &L));
@@ -988,8 +1004,9 @@ static int ae_bwd_impl(const st_dims* d, const float* mag, const float* phs, con
     if (ae_is_wide(d)) {
         if (defer_reduce) *defer_reduce = false;
         WideWS w; wide_carve(d, ws, &w);
-        return ae_wide_bwd(d, L, mag, phs, knobs, ae_m, ae_p, mag_hat, phs_hat, dAA, g_mag_hat, reg_coef, dmag, dphs, w, g_m, g_p, have_fwd, stream, sink, syn, norm_e, n_norm_e);
+        return ae_wide_bwd(d, L, mag, phs, knobs, ae_m, ae_p, mag_hat, phs_hat, dAA, g_mag_hat, reg_coef, dmag, dphs, w, g_m, g_p, have_fwd, stream, sink, syn, norm_e, n_norm_e, kg);
     }
+    if (kg && !(ae_kg_route(d) && have_fwd)) return st_fail(ST_ERR_UNSUPPORTED, "st_ae_bwd: no per-group d a5 output on this autoencoder backward route (%s)", ae_kg_why(d));
     const size_t lds = (size_t)sta::ae_bwd_lds_floats(AE_BWD_NW) * sizeof(float);
     static_assert((size_t)sta::ae_bwd_lds_floats(AE_BWD_NW) * sizeof(float) <= 160 * 1024, "ae_bwd LDS budget");
     ST_REQ((size_t)st_synth_slabs(d) * d->B * d->OT * L.KP < ((size_t)1 << 30) && (size_t)d->B * d->T * L.KP < ((size_t)1 << 30),
@@ -1009,16 +1026,22 @@ static int ae_bwd_impl(const st_dims* d, const float* mag, const float* phs, con
         }
         grid = ae_split_grid(d);
         static_assert((size_t)sta::ae_split_lds_floats<1>(AE_SPLIT_NW) * sizeof(float) <= 160 * 1024 && (size_t)sta::ae_split_lds_floats<2>(AE_SPLIT_NW) * sizeof(float) <= 160 * 1024, "split ae_bwd LDS budget");
-#define ST_AE_PART(PART_, HT_, GM_) do { ST_DYN_LDS((sta::ae_bwd_part_kernel<AE_SPLIT_NW, PART_, HT_, GM_>)); \
-        hipLaunchKernelGGL((sta::ae_bwd_part_kernel<AE_SPLIT_NW, PART_, HT_, GM_>), dim3(grid, 2), dim3(AE_SPLIT_NW * 64), \
+#define ST_AE_PART_K(PART_, HT_, GM_, KG_) do { ST_DYN_LDS((sta::ae_bwd_part_kernel<AE_SPLIT_NW, PART_, HT_, GM_, KG_>)); \
+        hipLaunchKernelGGL((sta::ae_bwd_part_kernel<AE_SPLIT_NW, PART_, HT_, GM_, KG_>), dim3(grid, 2), dim3(AE_SPLIT_NW * 64), \
                            (size_t)sta::ae_split_lds_floats<PART_>(AE_SPLIT_NW) * sizeof(float), st_stream(stream), \
                            mag, phs, knobs, ae_m, ae_p, L.go, L.PG, mag_hat, phs_hat, dAA, g_mag_hat, reg_coef, expfac, dmag, dphs, parts, \
                            (const float*)h4x, da4x, d->B, d->T, d->OT, d->F, d->K, L.KP, live.t_lo, live.t_lo + live.Tv - 1, st_synth_slabs(d), \
-                           (size_t)d->B * d->OT * L.KP); } while (0)
+                           (size_t)d->B * d->OT * L.KP, kg); } while (0)
+#define ST_AE_PART(PART_, HT_, GM_) ST_AE_PART_K(PART_, HT_, GM_, false)
 #define ST_AE_PARTS(HT_) do { if (g_mag_hat) ST_AE_PART(1, HT_, true); else ST_AE_PART(1, HT_, false); ST_LAUNCHED("ae_bwd_dec"); ST_AE_PART(2, HT_, false); ST_LAUNCHED("ae_bwd_enc"); } while (0)
+#define ST_AE_PARTS_KG(HT_) do { if (g_mag_hat) ST_AE_PART_K(1, HT_, true, true); else ST_AE_PART_K(1, HT_, false, true); ST_LAUNCHED("ae_bwd_dec"); ST_AE_PART(2, HT_, false); ST_LAUNCHED("ae_bwd_enc"); } while (0)
+        if (kg) { if (ae_ht(d->prec) == 1) ST_AE_PARTS_KG(1); else ST_AE_PARTS_KG(2); }      // 16-bit layers only (ae_kg_route)
+        else
         switch (ae_ht(d->prec)) { case 1: ST_AE_PARTS(1); break; case 2: ST_AE_PARTS(2); break; default: ST_AE_PARTS(0); }
+#undef ST_AE_PARTS_KG
 #undef ST_AE_PARTS
 #undef ST_AE_PART
+#undef ST_AE_PART_K
         if (defer_reduce && *defer_reduce) return ST_OK;
         hipLaunchKernelGGL(stm::ae_grad_reduce_kernel, dim3((L.PG + 63) / 64, 2), dim3(256), 0, st_stream(stream), parts, grid, L.PG, g_m, g_p);
         ST_LAUNCHED("ae_grad_reduce"); return ST_OK;
@@ -1031,12 +1054,14 @@ static int ae_bwd_impl(const st_dims* d, const float* mag, const float* phs, con
     const int var = g_mag_hat ? 1 : (d->T - d->OT == 16 ? 2 : 0);
     if (have_fwd && ae_use_saved(d)) {               // round 6: the forward of this workspace kept the activations -- no recompute
         const float* sv = ae_sv_ptr(d, L, ws);
-#define ST_AE_BWD_SV(VAR_) do { ST_DYN_LDS((sta::ae_bwd_kernel<AE_BWD_NW, false, 0, VAR_, true>)); \
-        hipLaunchKernelGGL((sta::ae_bwd_kernel<AE_BWD_NW, false, 0, VAR_, true>), dim3(grid, 2), dim3(AE_BWD_NW * 64), lds, st_stream(stream), \
+#define ST_AE_BWD_SV_K(VAR_, KG_) do { ST_DYN_LDS((sta::ae_bwd_kernel<AE_BWD_NW, false, 0, VAR_, true, KG_>)); \
+        hipLaunchKernelGGL((sta::ae_bwd_kernel<AE_BWD_NW, false, 0, VAR_, true, KG_>), dim3(grid, 2), dim3(AE_BWD_NW * 64), lds, st_stream(stream), \
                        mag, phs, knobs, ae_m, ae_p, L.go, L.PG, mag_hat, phs_hat, dAA, g_mag_hat, reg_coef, expfac, \
-                       dmag, dphs, parts, d->B, d->T, d->OT, d->F, d->K, L.KP, live.t_lo, live.t_lo + live.Tv - 1, st_synth_slabs(d), (size_t)d->B * d->OT * L.KP, sv); } while (0)
+                       dmag, dphs, parts, d->B, d->T, d->OT, d->F, d->K, L.KP, live.t_lo, live.t_lo + live.Tv - 1, st_synth_slabs(d), (size_t)d->B * d->OT * L.KP, sv, kg); } while (0)
+#define ST_AE_BWD_SV(VAR_) do { if (kg) ST_AE_BWD_SV_K(VAR_, true); else ST_AE_BWD_SV_K(VAR_, false); } while (0)
         if (var == 1) ST_AE_BWD_SV(1); else if (var == 2) ST_AE_BWD_SV(2); else ST_AE_BWD_SV(0);
 #undef ST_AE_BWD_SV
+#undef ST_AE_BWD_SV_K
         ST_LAUNCHED("ae_bwd");
         if (defer_reduce && *defer_reduce) return ST_OK;
         hipLaunchKernelGGL(stm::ae_grad_reduce_kernel, dim3((L.PG + 63) / 64, 2), dim3(256), 0, st_stream(stream), parts, grid, L.PG, g_m, g_p);
@@ -1529,7 +1554,7 @@ static int backward_syn(const st_dims* d, const Layout& L, float* grads, WS& w, 
 }
 static int backward_ae(const st_dims* d, const Layout& L, const float* params, float* grads,
                        const float* knobs, const float* g_mag_hat, const float* g_mag, float reg_coef, WS& w, void* stream, int syn_slabs = 0,
-                       const stm::NyqJob* syn_nyq = nullptr)
+                       const stm::NyqJob* syn_nyq = nullptr, float* kg = nullptr)
 {   // syn_slabs > 0: the synthesis weight-gradient slabs in w.wg are still to be summed (done by post_ae_kernel)
     const float* ae_m = params + L.offs[4]; const float* ae_p = params + L.offs[22];
     bool deferred = true;
@@ -1541,7 +1566,7 @@ static int backward_ae(const st_dims* d, const Layout& L, const float* params, f
     }
     ST_TRY(ae_bwd_impl(d, w.mag, w.phs, knobs, ae_m, ae_p, w.mag_hat, w.phs_hat, w.dAA, g_mag_hat, reg_coef, w.dmag, w.dphs,
                        w.aews, grads + L.offs[4], grads + L.offs[22], true, stream, &deferred, &sink, syn.wg ? &syn : nullptr,
-                       (d->clip_all && ae_is_wide(d)) ? w.norm_e : nullptr, &w.n_norm_e));      // the forward left its AE state in w.aews
+                       (d->clip_all && ae_is_wide(d)) ? w.norm_e : nullptr, &w.n_norm_e, kg));      // the forward left its AE state in w.aews
     if (!deferred) return ST_OK;                       // wide geometries: the gradient-finish launch summed the partials (and the synthesis slabs), and the polar backward ran inside wide_dv_polar_kernel
     stm::PostAeArgs a;
     a.ws = w.aews + 2 * ae_h4_floats(d); a.nparts = ae_use_split(d) ? ae_split_grid(d) : ae_bwd_grid(d); a.PG = L.PG; a.g_m = grads + L.offs[4]; a.g_p = grads + L.offs[22];
@@ -1565,11 +1590,11 @@ static int backward_ae(const st_dims* d, const Layout& L, const float* params, f
     return ST_OK;
 }
 static int backward_p1(const st_dims* d, const Layout& L, const float* params, float* grads,
-                       const float* knobs, const float* g_mag_hat, const float* g_mag, float reg_coef, WS& w, void* stream)
+                       const float* knobs, const float* g_mag_hat, const float* g_mag, float reg_coef, WS& w, void* stream, float* kg = nullptr)
 {
     int syn_slabs = 0; stm::NyqJob syn_nyq{}; syn_nyq.on = 0;
     ST_TRY(backward_syn(d, L, grads, w, stream, &syn_slabs, &syn_nyq));      // the slab sum rides in a later launch: post_ae_kernel (fused geometries) / wide_grad_finish_kernel (wide ones)
-    return backward_ae(d, L, params, grads, knobs, g_mag_hat, g_mag, reg_coef, w, stream, syn_slabs, &syn_nyq);
+    return backward_ae(d, L, params, grads, knobs, g_mag_hat, g_mag, reg_coef, w, stream, syn_slabs, &syn_nyq, kg);
 }
 static int backward_p2(const st_dims* d, const Layout& L, float* grads, const float* x, WS& w, void* stream, float* stage = nullptr, int stage_bf16 = 0)
 {
@@ -1629,9 +1654,9 @@ static int analysis_wgrad_half(const st_dims* d, const Layout& L, float* grads, 
     return ST_OK;
 }
 static int backward_impl(const st_dims* d, const Layout& L, const float* params, float* grads, const float* x,
-                         const float* knobs, const float* g_mag_hat, const float* g_mag, float reg_coef, WS& w, void* stream)
+                         const float* knobs, const float* g_mag_hat, const float* g_mag, float reg_coef, WS& w, void* stream, float* kg = nullptr)
 {
-    ST_TRY(backward_p1(d, L, params, grads, knobs, g_mag_hat, g_mag, reg_coef, w, stream));
+    ST_TRY(backward_p1(d, L, params, grads, knobs, g_mag_hat, g_mag, reg_coef, w, stream, kg));
     return backward_p2(d, L, grads, x, w, stream);
 }
 
@@ -1664,14 +1689,25 @@ extern "C" int st_model_bwd(const st_dims* d, const float* params, float* grads,
 // gradient (knobs are data), so the hot kernels carry no per-window reduction for it.  grads_scratch: L.total floats, overwritten; the saved-for-backward
 // state of `ws` afterwards belongs to the LAST window -- run the forward again before st_model_bwd.  At geometries where a single window cannot take
 // the requested 16-bit arithmetic (st_effective_prec: the wide autoencoder path, odd batch) these passes run the autoencoder layers in fp32.
+// One workgroup (64 threads) per window: workgroup w reads ng rows of 16 floats of either net from gbm / gbp + w * ng * 16 and sums them in ascending row
+// order (bit-repeatable), then the 16 x K multiply-adds with the fp32 W5 of both nets -> out[w][K].  ng = 1, one workgroup: the rows ARE the two bias
+// gradients (st_model_knob_grad); ng = groups per window: the per-group column sums of d a5 the backward kernels wrote (st_model_bwd_knobs).
 __global__ void knob_grad_kernel(const float* __restrict__ Wm, const float* __restrict__ gbm, const float* __restrict__ Wp, const float* __restrict__ gbp,
-                                 const int K, float* __restrict__ out)
+                                 const int K, float* __restrict__ out, const int ng)
 {
+    __shared__ float gb[32];
     const int k = threadIdx.x;
+    if (k < 32) {
+        const float* p = (k < 16 ? gbm : gbp) + (size_t)blockIdx.x * ng * 16 + (k & 15);
+        float a = p[0];
+        for (int j = 1; j < ng; ++j) a += p[j * 16];
+        gb[k] = a;
+    }
+    __syncthreads();
     if (k >= K) return;
     float s = 0.f, t = 0.f;
-    for (int o = 0; o < 16; ++o) { s += Wm[o * (16 + K) + 16 + k] * gbm[o]; t += Wp[o * (16 + K) + 16 + k] * gbp[o]; }
-    out[k] = s + t;
+    for (int o = 0; o < 16; ++o) { s += Wm[o * (16 + K) + 16 + k] * gb[o]; t += Wp[o * (16 + K) + 16 + k] * gb[16 + o]; }
+    out[(size_t)blockIdx.x * K + k] = s + t;
 }
 extern "C" int st_model_knob_grad(const st_dims* d, const float* params, float* grads_scratch, const float* x, const float* knobs,
                                   const float* g_y_hat, const float* g_mag_hat, const float* g_mag, void* ws, float* g_knobs, void* stream)
@@ -1688,8 +1724,41 @@ extern "C" int st_model_knob_grad(const st_dims* d, const float* params, float* 
         ST_TRY(st_model_bwd(&d1, params, grads_scratch, xb, kb, g_y_hat + (size_t)b * d->y, g_mag_hat ? g_mag_hat + (size_t)b * d->OT * d->F : nullptr,
                             g_mag ? g_mag + (size_t)b * d->T * d->F : nullptr, ws, stream));
         hipLaunchKernelGGL(knob_grad_kernel, dim3(1), dim3(64), 0, st_stream(stream), params + w5, grads_scratch + b5, params + w5 + L1.PG, grads_scratch + b5 + L1.PG,
-                           d->K, g_knobs + (size_t)b * d->K);
+                           d->K, g_knobs + (size_t)b * d->K, 1);
     }
+    ST_LAUNCHED("knob_grad");
+    return ST_OK;
+}
+
+// The same gradient in ONE backward pass of the batch: the autoencoder backward kernels also write the per-group column sums of d a5 (16 floats per 16-row
+// group; a group never straddles a window) into the caller's scratch, and one small launch -- one workgroup per window -- sums a window's groups in
+// ascending order and applies W5.  Every scratch element that launch reads was written by this call: no clearing.
+extern "C" int st_knob_grad_fused_supported(const st_dims* d)
+{
+    if (check_dims(d) != ST_OK) return 0;
+    if (d->K < 1) { (void)st_fail(ST_ERR_ARG, "st_model_bwd_knobs: K = %d (a model without knobs has no knob gradient)", d->K); return 0; }
+    if (!ae_kg_route(d)) { (void)st_fail(ST_ERR_UNSUPPORTED, "st_model_bwd_knobs: no per-group d a5 output on this autoencoder backward route (%s)", ae_kg_why(d)); return 0; }
+    return 1;
+}
+extern "C" size_t st_model_bwd_knobs_ws_floats(const st_dims* d)
+{
+    if (check_dims(d) != ST_OK) return 0;
+    return (size_t)2 * ae_fwd_groups(d) * 16;
+}
+extern "C" int st_model_bwd_knobs(const st_dims* d, const float* params, float* grads, const float* x, const float* knobs,
+                                  const float* g_y_hat, const float* g_mag_hat, const float* g_mag, void* ws, float* scratch, float* g_knobs, void* stream)
+{
+    Layout L; ST_TRY(make_layout(d, &L));
+    ST_REQ(params && grads && x && knobs && g_y_hat && ws && scratch && g_knobs, "st_model_bwd_knobs: null pointer");
+    ST_REQ(d->K >= 1, "st_model_bwd_knobs: K = %d (a model without knobs has no knob gradient)", d->K);
+    if (!ae_kg_route(d)) return st_fail(ST_ERR_UNSUPPORTED, "st_model_bwd_knobs: no per-group d a5 output on this autoencoder backward route (%s)", ae_kg_why(d));
+    WS w; carve(d, ws, &w);
+    ST_TRY(pad_scale(g_y_hat, w.dsyn, d->B, d->y, d->N, 2.0f, stream));     // as st_model_bwd
+    ST_TRY(backward_impl(d, L, params, grads, x, knobs, g_mag_hat, g_mag, 0.0f, w, stream, scratch));
+    const size_t w5 = (size_t)L.offs[4] + (size_t)L.go.w[4];
+    const int gpw = L.KP / 32;
+    hipLaunchKernelGGL(knob_grad_kernel, dim3(d->B), dim3(64), 0, st_stream(stream), params + w5, (const float*)scratch, params + w5 + L.PG,
+                       (const float*)scratch + (size_t)ae_fwd_groups(d) * 16, d->K, g_knobs, gpw);
     ST_LAUNCHED("knob_grad");
     return ST_OK;
 }

@@ -256,6 +256,29 @@ class StepEngine:
                    _lib.ptr(knobs), _lib.ptr(g_y_hat), _lib.ptr(g_mag_hat), _lib.ptr(g_mag), _lib.ptr(self.ws), self._stream())
         return self.grads
 
+    def knob_grad_fused_supported(self, B):
+        """Whether backward_with_knob_grad() runs a batch of B windows at this engine's arithmetic (st_knob_grad_fused_supported: host arithmetic only).
+        False for a model without knobs and where a diagnostic switch routes the autoencoder backward to a kernel form without the per-group output."""
+        return bool(self.lib.st_knob_grad_fused_supported(C.byref(self._dims(int(B)))))
+
+    def backward_with_knob_grad(self, x, knobs, g_y_hat, g_mag_hat=None, g_mag=None):
+        """backward() and, in the same pass, d / d knobs [B, K] (st_model_bwd_knobs): returns (self.grads, g_knobs).  After forward(save_for_backward=True),
+        like backward(); self.grads receives exactly what backward() writes and the workspace still holds the batch's state afterwards (knob_grad(), the
+        exact per-window route, leaves the last window's).  Raises where knob_grad_fused_supported(B) is False."""
+        if self.dims.K == 0:               # no knobs, no knob gradient: the plain backward and an empty [B, 0] tensor, without a st_model_bwd_knobs call
+            return self.backward(x, knobs, g_y_hat, g_mag_hat, g_mag), torch.empty(x.shape[0], 0, dtype=torch.float32, device=self.device)
+        d, x, knobs, _ = self._prep(x, knobs)
+        d.loss_scale = 0.0
+        f = lambda t: None if t is None else t.to(device=self.device, dtype=torch.float32).contiguous()
+        g_y_hat, g_mag_hat, g_mag = f(g_y_hat), f(g_mag_hat), f(g_mag)
+        need = int(self.lib.st_model_bwd_knobs_ws_floats(C.byref(d)))
+        if getattr(self, "_knob_groups", None) is None or self._knob_groups.numel() < need:
+            self._knob_groups = torch.empty(need, dtype=torch.float32, device=self.device)      # per-group column sums of d a5; never cleared (written before read)
+        out = torch.empty(d.B, d.K, dtype=torch.float32, device=self.device)
+        self._call("st_model_bwd_knobs", C.byref(d), _lib.ptr(self.params), _lib.ptr(self.grads), _lib.ptr(x), _lib.ptr(knobs),
+                   _lib.ptr(g_y_hat), _lib.ptr(g_mag_hat), _lib.ptr(g_mag), _lib.ptr(self.ws), _lib.ptr(self._knob_groups), _lib.ptr(out), self._stream())
+        return self.grads, out
+
     def input_grad(self, x, g_y_hat):
         """d loss / d x of the whole model (right after backward() on the same batch): half the conv-transpose of the analysis output
         gradient (nn_proc.py:307 feeds x/2) plus the skip connection's share on the last y samples (nn_proc.py:340)."""

@@ -133,13 +133,20 @@ class _STModelFn(torch.autograd.Function):
         if g_y is None:
             g_y = torch.zeros(x.shape[0], eng.dims.y, device=x.device)
         gk = None
-        if ctx.needs_input_grad[2]:
-            # knobs that require grad (nn_proc.py:92-93 under autograd): the exact per-window route of st_model_knob_grad -- slow (one forward + backward
-            # per window: the reference's training never asks for it), and it leaves the LAST window's state in the workspace
-            gk = eng.knob_grad(x, knobs, g_y, g_mh, g_mag)
-        if gk is not None or eng is not ctx.engine or eng.generation != ctx.generation:
-            eng.forward(x, knobs, save_for_backward=True)          # the workspace was reused since this graph's forward: rebuild its state
-        eng.backward(x, knobs, g_y, g_mh, g_mag)
+        if ctx.needs_input_grad[2] and getattr(ctx.model, "knob_grad_route", "exact") == "fused" and eng.knob_grad_fused_supported(x.shape[0]):
+            # opt-in (st_model.knob_grad_route = "fused"): the knob gradient out of the ONE backward pass of the batch (st_model_bwd_knobs) -- no per-window
+            # passes and, unless the workspace was reused since this graph's forward, no second forward
+            if eng is not ctx.engine or eng.generation != ctx.generation:
+                eng.forward(x, knobs, save_for_backward=True)
+            _, gk = eng.backward_with_knob_grad(x, knobs, g_y, g_mh, g_mag)
+        else:
+            if ctx.needs_input_grad[2]:
+                # knobs that require grad (nn_proc.py:92-93 under autograd): the exact per-window route of st_model_knob_grad -- slow (one forward + backward
+                # per window: the reference's training never asks for it), and it leaves the LAST window's state in the workspace
+                gk = eng.knob_grad(x, knobs, g_y, g_mh, g_mag)
+            if gk is not None or eng is not ctx.engine or eng.generation != ctx.generation:
+                eng.forward(x, knobs, save_for_backward=True)          # the workspace was reused since this graph's forward: rebuild its state
+            eng.backward(x, knobs, g_y, g_mh, g_mag)
         gx = eng.input_grad(x, g_y) if ctx.needs_input_grad[1] else None     # something trainable upstream of the model
         # one flat clone, then per-parameter views of it: autograd accumulates into .grad, so the engine's gradient buffer
         # (overwritten by the next backward) must not be handed out itself
@@ -164,6 +171,7 @@ class AsymMPAEC(nn.Module):
         self.aenc = AsymAutoEncoder(T=expected_time_frames, R=decomposition_rank, K=n_knobs, OT=self.output_tf)
         self.phs_aenc = AsymAutoEncoder(T=expected_time_frames, R=decomposition_rank, K=n_knobs, OT=self.output_tf)
         self._engine = None
+        self.knob_grad_route = "exact"       # st_model.knob_grad_route
 
     def reinitialize(self):
         self.aenc.initialize(); self.phs_aenc.initialize()
@@ -268,6 +276,22 @@ class st_model(nn.Module):
 
     def clip_grad_norm_(self):
         self.mpaec.clip_grad_norm_()
+
+    KNOB_GRAD_ROUTES = ("exact", "fused")
+
+    @property
+    def knob_grad_route(self):
+        """How a knobs tensor that requires grad gets its gradient.  "exact" (default): st_model_knob_grad, one forward + backward per window -- the route
+        every parity test of this gradient pins.  "fused": st_model_bwd_knobs, out of the one backward pass of the batch (same tolerance against the
+        reference's autograd, not the same bits: the rows of a window are summed in another order); batches the library does not run that way
+        (StepEngine.knob_grad_fused_supported) take the exact route."""
+        return self.mpaec.knob_grad_route
+
+    @knob_grad_route.setter
+    def knob_grad_route(self, route):
+        if route not in self.KNOB_GRAD_ROUTES:
+            raise ValueError(f"knob_grad_route must be one of {self.KNOB_GRAD_ROUTES}")
+        self.mpaec.knob_grad_route = route
 
     def set_compute_dtype(self, dtype):
         """Arithmetic of the accelerated path: 'f32' (default) | 'f32x3' | 'bf16' | 'bf16_all' | 'f16' | 'f16_all' (see AsymMPAEC.set_compute_dtype)."""
