@@ -226,6 +226,12 @@ size_t st_ae_bwd_ws_floats(const st_dims* d);
  * forward writes (and the backward reads back) per call: 2 nets x B * ceil(F / 16) row groups x 17 KB (294 MB at B = 256); 0 where the path is not
  * taken (16-bit autoencoder layers, wide geometries, the recompute switch g_ae_save = 0).  st_ae_bwd on its own (no forward in the same workspace) recomputes. */
 size_t st_ae_kept_activation_bytes(const st_dims* d);
+/* Round 10.  On the same configurations every fused forward (training step, st_model_fwd, st_eval_step) also leaves the autoencoders' LDS weight images --
+ * both nets' forward and data-gradient fragment images with their zero padding, and the per-bin frequency weights of the L1 term -- at the head of the
+ * autoencoder workspace, in the h4 / d a4 exchange areas that only the split backward uses (no size changes): its first launch builds them once, and the
+ * autoencoder kernels copy them into LDS instead of rebuilding them in each of their 512 workgroups.  A part that does not fit there (the backward's below
+ * 38 row groups, the forward's below 20 at the default geometry) is built in the kernel as before, as in st_ae_fwd / st_ae_bwd on their own and in the
+ * whole step under st_set_tuning(8202) (the A/B reference of tests/test_gpu_ae_weight_images.py: identical bits). */
 
 /* Backward of nn_proc.py:309-310: dG[B*T,KP] (d re | d im) from (re,im,dmag,dphs). */
 int st_polar_bwd(const st_dims* d, const float* re, const float* im, const float* dmag, const float* dphs,

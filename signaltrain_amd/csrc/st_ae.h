@@ -32,6 +32,8 @@ constexpr int NL = 9;
 // Timing-only ablation build of ae_bwd_kernel (tools/ae_ablate.sh; results are INVALID when non-zero; never set in the product build):
 // 1 no d-out global loads | 2 no dv stores | 4 no weight-gradient MFMAs | 8 ELU without the transcendental | 16 no LDS transposes |
 // 32 no forward-recompute MFMAs | 64 no next-group prefetch loads
+// Round 10, ae_fwd_kernel and ae_bwd_kernel: 128 no prologue work -- the LDS images are zero-filled only: no parameter loads, no scatter, no ready-made image copy,
+// no frequency-weight table | 256 no partial-gradient tail of ae_bwd (the accumulators are only kept alive)
 #ifndef ST_AE_ABLATE
 #define ST_AE_ABLATE 0
 #endif
@@ -88,8 +90,9 @@ constexpr int ae_max_elems(int l) { return l == 0 ? 64 * 32 : l == 1 ? 32 * 64 :
 template <int NT>
 struct AEParamRegs { float v[NL][(64 * 32 + NT - 1) / NT]; float bv[NL]; };      // one thread's share of an autoencoder's parameters
 
+// (__host__ too, with ae_params_scatter and ae_img_build: tests/test_ae_weight_images_host.py runs the scatter and its inverse on the CPU)
 template <int NT>
-__device__ __forceinline__ void ae_params_issue(AEParamRegs<NT>& r, const float* __restrict__ ae, const AEOffsets& go,
+__host__ __device__ __forceinline__ void ae_params_issue(AEParamRegs<NT>& r, const float* __restrict__ ae, const AEOffsets& go,
                                                 const int T, const int OT, const int K, const int tid, const int l0, const int l1)
 {
     const int out[NL] = {64, 32, 16, 16, 16, 16, 32, 64, OT};
@@ -118,7 +121,7 @@ template <int BF> __device__ __forceinline__ float st_half_to_float(const unsign
     else return __uint_as_float((unsigned)b << 16);
 }
 template <int NT, int BF = 0>
-__device__ __forceinline__ void ae_params_scatter(float* lds, const AEParamRegs<NT>& r, const int T, const int OT, const int K,
+__host__ __device__ __forceinline__ void ae_params_scatter(float* lds, const AEParamRegs<NT>& r, const int T, const int OT, const int K,
                                                   const int tid, const int l0, const int l1, const bool dgrad_images)
 {
     const int out[NL] = {64, 32, 16, 16, 16, 16, 32, 64, OT};
@@ -155,18 +158,25 @@ template <int NT, int BF = 0>
 __device__ inline void ae_load_lds(float* lds, const float* __restrict__ ae, const AEOffsets& go, const int T, const int OT, const int K,
                                    const int tid, const int l0, const int l1, const bool dgrad_images)
 {
+    const int total = dgrad_images ? CL::BWD_TOTAL : CL::FWD_TOTAL;
+#if ST_AE_ABLATE & 128
+    for (int e = tid; e < total; e += NT) lds[e] = 0.f;
+#else
     AEParamRegs<NT> r;
     ae_params_issue<NT>(r, ae, go, T, OT, K, tid, l0, l1);
-    const int total = dgrad_images ? CL::BWD_TOTAL : CL::FWD_TOTAL;
     for (int e = tid; e < total; e += NT) lds[e] = 0.f;
     __syncthreads();
     ae_params_scatter<NT, BF>(lds, r, T, OT, K, tid, l0, l1, dgrad_images);
+#endif
 }
 // ... or both (forward kernels: two forward images CL::FWD_TOTAL floats apart), still one round trip.
 template <int NT, int BF = 0>
 __device__ inline void ae_load_lds2(float* lds, const float* __restrict__ ae_m, const float* __restrict__ ae_p, const AEOffsets& go,
                                     const int T, const int OT, const int K, const int tid, const int l0, const int l1)
 {
+#if ST_AE_ABLATE & 128
+    for (int e = tid; e < 2 * CL::FWD_TOTAL; e += NT) lds[e] = 0.f;
+#else
     AEParamRegs<NT> rm, rp;
     ae_params_issue<NT>(rm, ae_m, go, T, OT, K, tid, l0, l1);
     ae_params_issue<NT>(rp, ae_p, go, T, OT, K, tid, l0, l1);
@@ -174,6 +184,56 @@ __device__ inline void ae_load_lds2(float* lds, const float* __restrict__ ae_m, 
     __syncthreads();
     ae_params_scatter<NT, BF>(lds, rm, T, OT, K, tid, l0, l1, false);
     ae_params_scatter<NT, BF>(lds + CL::FWD_TOTAL, rp, T, OT, K, tid, l0, l1, false);
+#endif
+}
+
+// Round 10: READY-MADE images (fused fp32 geometries).  The images above are the same for every workgroup of the forward and the backward kernel of a step, and
+// the parameters do not change between prep_kernel and the end of ae_bwd: prep_kernel builds them ONCE per step into the workspace (ae_img_build, one float per
+// thread, gathered -- every float is written, the zero padding included) and the kernels' prologue becomes a linear 16-byte copy: no zero fill, no AEParamRegs,
+// no division per element, one barrier.  Layout (floats):
+//     [forward image + biases, net 0: CL::FWD_TOTAL][the same, net 1][wtab: FP frequency weights][dgrad images, net 0: AE_IMG_DG][dgrad images, net 1]
+// i.e. the first 2 * FWD_TOTAL + FP floats ARE the forward kernel's LDS contents, and a net's dgrad block is the backward kernel's LDS at CL::G0.
+constexpr int AE_IMG_DG = CL::BWD_TOTAL - CL::FWD_TOTAL;
+__host__ __device__ constexpr int ae_img_fwd_floats(const int FP) { return 2 * CL::FWD_TOTAL + FP; }                  // what the forward kernel copies
+__host__ __device__ constexpr int ae_img_floats(const int FP) { return ae_img_fwd_floats(FP) + 2 * AE_IMG_DG; }       // ... and the backward's dgrad blocks behind it
+struct AEImgJob { const float* ae[2]; float* img; AEOffsets go; int T, OT, K, F, FP; float expfac; int n, n_blk; };      // the first n floats are built (the forward's part or all); n_blk = 0: no job
+// exp(expfac * bin): the frequency weight of the L1 term (train.py:115-117); one definition for the table builders and the in-kernel form
+__host__ __device__ __forceinline__ float ae_freq_weight(const float expfac, const int f) { return expf(expfac * (float)f); }
+// Float p of the image block: the inverse of ae_params_scatter's positions (OUTp, INp are powers of two).
+__host__ __device__ __forceinline__ void ae_img_build(const AEImgJob& j, const int p)
+{
+    if (p >= j.n) return;
+    const int out[NL] = {64, 32, 16, 16, 16, 16, 32, 64, j.OT};
+    const int in[NL] = {j.T, 64, 32, 16, 16 + j.K, 16, 16, 32, 64};
+    const int outp[NL] = {CL::O0, CL::O1, CL::O2, CL::O3, CL::O4, CL::O5, CL::O6, CL::O7, CL::O8};
+    const int inp[NL] = {CL::I0, CL::I1, CL::I2, CL::I3, CL::I4, CL::I5, CL::I6, CL::I7, CL::I8};
+    const int ao[NL + 1] = {CL::A0, CL::A1, CL::A2, CL::A3, CL::A4, CL::A5, CL::A6, CL::A7, CL::A8, CL::AEND};
+    const int bo[NL + 1] = {CL::B0, CL::B1, CL::B2, CL::B3, CL::B4, CL::B5, CL::B6, CL::B7, CL::B8, CL::FWD_TOTAL};
+    float v = 0.f;
+    const int q0 = p - 2 * CL::FWD_TOTAL;
+    if (q0 >= 0 && q0 < j.FP) v = q0 < j.F ? ae_freq_weight(j.expfac, q0) : 0.f;
+    else {
+        const bool dg = q0 >= 0;
+        const int net = dg ? (q0 - j.FP >= AE_IMG_DG) : (p >= CL::FWD_TOTAL);
+        const int q = dg ? q0 - j.FP - net * AE_IMG_DG : p - net * CL::FWD_TOTAL;      // position inside the net's forward block / dgrad block
+        const float* __restrict__ ae = j.ae[net];
+        if (!dg && q >= CL::AEND) {                                                      // biases
+#pragma unroll
+            for (int l = 0; l < NL; ++l)
+                if (q >= bo[l] && q < bo[l + 1]) { const int o = q - bo[l]; if (o < out[l]) v = ae[j.go.b[l] + o]; }
+        } else {
+#pragma unroll
+            for (int l = 0; l < NL; ++l)
+                if (q >= ao[l] && q < ao[l + 1]) {
+                    const int s = (q - ao[l]) >> 2, lo = (q - ao[l]) & 3;
+                    // forward image: slot (i >> 2) * OUTp + o, element i & 3;  dgrad image: slot (o >> 2) * INp + i, element o & 3
+                    const int o = dg ? ((s / inp[l]) << 2) + lo : s % outp[l];
+                    const int i = dg ? s % inp[l] : ((s / outp[l]) << 2) + lo;
+                    if (o < out[l] && i < in[l]) v = ae[j.go.w[l] + o * in[l] + i];
+                }
+        }
+    }
+    j.img[p] = v;
 }
 
 #define ST_MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
@@ -453,22 +513,39 @@ ae_fwd_kernel(const float* __restrict__ mag, const float* __restrict__ phs, cons
                                                       // the split backward (st_ae_split.h); mag_hat == NULL: h4 only (no other output is written)
               unsigned short* __restrict__ AA16 = nullptr, const int aa_ht = 0,      // 16-bit GEMM configurations (st_gemm16.h): the spectra go out rounded to
                                                       // the operand type (1 bf16 / 2 fp16) INSTEAD of fp32 -- their only consumers are the two synthesis GEMMs
-              float* __restrict__ sv = nullptr)       // SV: the kept activations of both nets (layout above)
+              float* __restrict__ sv = nullptr,       // SV: the kept activations of both nets (layout above)
+              const float* __restrict__ img = nullptr)      // fp32 only: the ready-made images + frequency-weight table prep_kernel built (ae_img_build); NULL = built here
 {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int g = lane >> 4, c = lane & 15;
     const float* const lw[2] = {lds, lds + CL::FWD_TOTAL};
-    ae_load_lds2<NW * 64, BF>(lds, ae_m, ae_p, go, T, OT, K, tid, 0, NL);
-    __syncthreads();
-
     const int FP = KP / 2, gpw = FP / 16;              // groups per window
+    // frequency weights of the L1 term, one per bin (the table sits behind the two forward images; the host sizes the LDS request for it)
+    float* const wtab = lds + 2 * CL::FWD_TOTAL;
+    const bool ready = BF == 0 && !(ST_AE_ABLATE & 128) && img != nullptr;      // workgroup-uniform
+    if (ready) {
+        // the table's FP / 4 quads ride behind the image loads and in front of the image stores: still one memory round trip
+        constexpr int N4 = 2 * CL::FWD_TOTAL / 4, U = (N4 + NW * 64 - 1) / (NW * 64);
+        f32x4 v[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) { const int e = tid + u * NW * 64; v[u] = reinterpret_cast<const f32x4*>(img)[e < N4 ? e : 0]; }
+        for (int i = tid; i < FP / 4; i += NW * 64) reinterpret_cast<f32x4*>(wtab)[i] = reinterpret_cast<const f32x4*>(img + 2 * CL::FWD_TOTAL)[i];
+#pragma unroll
+        for (int u = 0; u < U; ++u) { const int e = tid + u * NW * 64; if (e < N4) reinterpret_cast<f32x4*>(lds)[e] = v[u]; }
+    } else {
+        ae_load_lds2<NW * 64, BF>(lds, ae_m, ae_p, go, T, OT, K, tid, 0, NL);
+        __syncthreads();
+#if ST_AE_ABLATE & 128
+        for (int i = tid; i < FP; i += NW * 64) wtab[i] = 0.f;
+#else
+        for (int i = tid; i < FP; i += NW * 64) wtab[i] = i < F ? ae_freq_weight(expfac, i) : 0.f;
+#endif
+    }
+
     const int ngroups = B * gpw;
     const int KQ = (K + 3) / 4;
     float reg = 0.f;
-    // frequency weights of the L1 term, one per bin (the table sits behind the two forward images; the host sizes the LDS request for it)
-    float* const wtab = lds + 2 * CL::FWD_TOTAL;
-    for (int i = tid; i < FP; i += NW * 64) wtab[i] = i < F ? expf(expfac * (float)i) : 0.f;
     unsigned toF[4], toK[4];
 #pragma unroll
     for (int r = 0; r < 4; ++r) { toF[r] = ST_MUL24(4 * g + r, F); toK[r] = ST_MUL24(4 * g + r, KP); }
@@ -874,7 +951,9 @@ constexpr int ae_bwd_lds_floats(int nw) { return (CL::BWD_TOTAL + nw * AE_BWD_SC
 // KG (st_model_bwd_knobs): the kernel also writes the per-group column sums of d a5 -- this group's share of the fnn_addknobs bias gradient rb5, taken
 // from the same unrounded fp32 daT5 -- to kg[net][group][16].  A group never straddles a window (ngroups = B * gpw), so the gpw rows of a window sum to
 // the bias gradient of that window alone, which is all d knobs needs (knob_grad_kernel, st_api.hip).  A compile-time flag: off, nothing is added.
-template <int NW, bool INNER = false, int BF = 0, int VAR = 1, bool SAVED = false, bool KG = false>      // BF: 16-bit operands in all Linear-layer products (ST_PREC_*_ALL)
+// IMG (round 10; SAVED only): the dgrad images and the frequency-weight table arrive ready-made from prep_kernel (ae_img_build): the prologue is a linear copy, and the
+// weight of the L1 term is read from the table (the kept-activation kernel never touches the forward images: the table lies in their place).
+template <int NW, bool INNER = false, int BF = 0, int VAR = 1, bool SAVED = false, bool KG = false, bool IMG = false>      // BF: 16-bit operands in all Linear-layer products (ST_PREC_*_ALL)
 __global__ void __launch_bounds__(NW * 64, 1)
 ae_bwd_kernel(const float* __restrict__ mag, const float* __restrict__ phs, const float* __restrict__ knobs,
               const float* __restrict__ ae_m, const float* __restrict__ ae_p, const AEOffsets go, const int PG,
@@ -885,9 +964,11 @@ ae_bwd_kernel(const float* __restrict__ mag, const float* __restrict__ phs, cons
               const int to_lo, const int to_hi,      // live synthesis frames: dAA rows outside are treated as zero
               const int nslab, const size_t slab,     // dAA arrives as split-K slabs of the synthesis dgrad GEMM
               const float* __restrict__ sv = nullptr,      // SAVED: the kept activations ([net][group][17 tiles][lane] float4)
-              float* __restrict__ kg = nullptr)            // KG: per-group column sums of d a5 ([net][group][16])
+              float* __restrict__ kg = nullptr,            // KG: per-group column sums of d a5 ([net][group][16])
+              const float* __restrict__ img = nullptr)     // IMG: the image block of this step (layout at ae_img_floats)
 {
     static_assert(!SAVED || (!INNER && BF == 0), "the kept-activation backward exists for the fused fp32 geometries");
+    static_assert(!IMG || SAVED, "ready-made images: the kept-activation backward only");
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int ae = blockIdx.y;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -899,6 +980,17 @@ ae_bwd_kernel(const float* __restrict__ mag, const float* __restrict__ phs, cons
     float* Ts = Ys + 16 * SP;
     float* XH = Ts + 16 * SP;                          // transposes of activations
     float* XD = XH + 4 * 320;                          // transposes of activation gradients
+    if constexpr (IMG && !(ST_AE_ABLATE & 128)) {
+        const int FPi = KP / 2;                        // the host passes an image block only where FP <= CL::FWD_TOTAL
+        const float* const dg = img + 2 * CL::FWD_TOTAL + FPi + ae * AE_IMG_DG;
+        constexpr int N4 = AE_IMG_DG / 4, U = (N4 + NW * 64 - 1) / (NW * 64);
+        f32x4 v[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) { const int e = tid + u * NW * 64; v[u] = reinterpret_cast<const f32x4*>(dg)[e < N4 ? e : 0]; }
+        for (int i = tid; i < FPi / 4; i += NW * 64) reinterpret_cast<f32x4*>(lds)[i] = reinterpret_cast<const f32x4*>(img + 2 * CL::FWD_TOTAL)[i];
+#pragma unroll
+        for (int u = 0; u < U; ++u) { const int e = tid + u * NW * 64; if (e < N4) reinterpret_cast<f32x4*>(lds + CL::G0)[e] = v[u]; }
+    } else
     ae_load_lds<NW * 64, BF>(lw, ae ? ae_p : ae_m, go, INNER ? 16 : T, INNER ? 16 : OT, K, tid, INNER ? 1 : 0, INNER ? 8 : NL, true);
     __syncthreads();
 
@@ -1098,7 +1190,9 @@ ae_bwd_kernel(const float* __restrict__ mag, const float* __restrict__ phs, cons
         float dxA[4], mtA[4];
         if constexpr (!INNER) {
             ST_FENCE();
-            const float wf = fv ? expf(expfac * (float)f) : 0.f;
+            float wf;
+            if constexpr (IMG && !(ST_AE_ABLATE & 128)) wf = fv ? lds[f] : 0.f;      // the table ae_img_build wrote: the same expf of the same argument
+            else wf = fv ? ae_freq_weight(expfac, f) : 0.f;
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 // Branch-free on purpose: with the loads' only uses inside an `if (fv && to < OT)` block the compiler SANK ten
@@ -1283,6 +1377,17 @@ ae_bwd_kernel(const float* __restrict__ mag, const float* __restrict__ phs, cons
     // CL::A_l, db_l at CL::B_l, images CL::FWD_TOTAL floats apart), all four in parallel, and the store pass below sums the
     // images in a fixed order ((0 + 1) + (2 + 3)): run-to-run identical bits without the serialised wave-by-wave
     // read-modify-write flush the first versions used (three extra barrier-separated LDS passes).
+#if ST_AE_ABLATE & 256
+    {   // timing only: no flush, no store pass -- the accumulators are merely kept alive (as VGPR reads: up to 161 accumulator-file moves stay in the figure)
+#define ST_KT(x, A, Bq) { _Pragma("unroll") for (int a_ = 0; a_ < A; ++a_) _Pragma("unroll") for (int b_ = 0; b_ < Bq; ++b_) _Pragma("unroll") for (int r_ = 0; r_ < 4; ++r_) asm volatile("" :: "v"(x[a_][b_][r_])); }
+#define ST_KB(x, A) { _Pragma("unroll") for (int a_ = 0; a_ < A; ++a_) asm volatile("" :: "v"(x[a_])); }
+        ST_KT(rW1, 4, 2) ST_KT(rW2, 2, 4) ST_KT(rW3, 1, 2) ST_KT(rW4, 1, 1) ST_KT(rW5, 1, 2) ST_KT(rW6, 1, 1) ST_KT(rW7, 2, 1) ST_KT(rW8, 4, 2) ST_KT(rW9, 1, 4)
+        ST_KB(rb1, 4) ST_KB(rb2, 2) ST_KB(rb3, 1) ST_KB(rb4, 1) ST_KB(rb5, 1) ST_KB(rb6, 1) ST_KB(rb7, 2) ST_KB(rb8, 4) ST_KB(rb9, 1)
+#undef ST_KT
+#undef ST_KB
+        return;
+    }
+#endif
     __syncthreads();
     static_assert(NW == 4, "the store pass sums exactly four per-wave images");
     float* dwl = lds + wave * CL::FWD_TOTAL;

@@ -177,7 +177,8 @@ static int num_cus()
 // ST_PL_ABLATE, ST_G128_ABLATE).  The entry stays for callers that pass their --ablate argument through; it accepts 0 alone.
 extern "C" int st_set_debug(int v) { return v == 0 ? ST_OK : st_fail(ST_ERR_ARG, "st_set_debug(%d): the product library has no run-time ablations (build with -DST_*_ABLATE=bits)", v); }
 static int g_dp_inline = 1;  // st_dp_train_step: 1 = the last (exposed) exchange is issued in line on the compute stream (round 6), 0 = on the communicator stream between two hand-offs
-static int g_ae_save = 1;    // fused geometries, fp32 autoencoder layers: 1 = the forward kernel keeps the activations and the backward reads them (round 6), 0 = the backward recomputes them
+static int g_ae_save = 1;    // fused geometries, fp32 autoencoder layers: 1 = the forward kernel keeps the activations and the backward reads them (round 6), 0 = the backward recomputes them;
+                             // 2 = as 1, with the LDS weight images built inside the kernels instead of once per step by prep_kernel (round 10: A/B timing, bit-equality tests)
 static int g_ae_split = -1;  // autoencoder backward of the fused geometries: 0 = the single kernel, 1 = the two kernels of st_ae_split.h,
                              // -1 = by precision (default): fp32 -> single (179.5 us against 87.0 + 92.4 us at B = 256 -- equal: the fp32 MFMA holds the vector ALUs, a partner
                              // wave has nothing to overlap with -- and the split moves 66 MB more per step: h4 / d a4 / tails hand-over); 16-bit Linear layers -> split (the
@@ -222,7 +223,7 @@ static const struct { int first, count; int* var; int value; int* also; } k_tuni
     {7000, 2, &g_xt, 0, nullptr},
     {8000, 2, &g_ae_split, 0, nullptr}, {8002, 1, &g_ae_split, -1, nullptr},      // single kernel / two kernels / by precision
     {8100, 2, &g_ae32, 0, nullptr},
-    {8200, 2, &g_ae_save, 0, nullptr},
+    {8200, 3, &g_ae_save, 0, nullptr},      // 8202: kept activations, in-kernel weight images
     {8300, 2, &g_dp_inline, 0, nullptr},
     {9000, 2, &g_frs_nt, 0, nullptr},
     {9100, 1, &g_pl_shape, 0, nullptr}, {9103, 1, &g_pl_shape, 3, nullptr},
@@ -437,6 +438,20 @@ static size_t ae_sv_floats(const st_dims* d) { return (!ae_is_wide(d) && ae_ht(d
 static int ae_parts_max(const st_dims* d) { return ae_split_grid(d) > ae_bwd_grid(d) ? ae_split_grid(d) : ae_bwd_grid(d); }
 static bool ae_use_saved(const st_dims* d) { return g_ae_save && !ae_is_wide(d) && ae_ht(d->prec) == 0 && !ae_use_split(d); }
 static float* ae_sv_ptr(const st_dims* d, const Layout& L, float* aews) { return aews + 2 * ae_h4_floats(d) + (size_t)ae_parts_max(d) * 2 * L.PG; }
+// Round 10: the ready-made LDS weight images of both nets + the frequency-weight table (st_ae.h ae_img_floats), written by prep_kernel in front of every fused forward and
+// read by the prologues of ae_fwd_kernel and of the kept-activation ae_bwd_kernel.  They need no workspace of their own: with fp32 layers on the single-kernel backward
+// nothing uses the h4 / d a4 exchange areas at the head of the autoencoder workspace (they connect the forward to the SPLIT backward), 1024 floats per row group, and the
+// images lie there -- as much of them as fits: the forward's part (both forward images + the table) from 20 groups (at the default geometry: B >= 1 ), the backward's
+// data-gradient images behind it from 38 (B >= 2).  A kernel whose part does not fit (tiny batches of tiny geometries) builds its images itself, as do all other paths.
+static int ae_img_level(const st_dims* d)      // 0: no ready-made images, 1: the forward's part, 2: the backward's too
+{
+    if (g_ae_save == 2 || ae_is_wide(d) || ae_ht(d->prec) != 0 || ae_use_split(d)) return 0;
+    const int FP = st_kp_of(d->F) / 2;
+    const size_t room = 2 * ae_h4_floats(d);
+    if (FP > sta::CL::FWD_TOTAL || room < (size_t)sta::ae_img_fwd_floats(FP)) return 0;      // FP <= FWD_TOTAL: the backward kernel keeps its copy of the table in the place of the forward images
+    return room >= (size_t)sta::ae_img_floats(FP) ? 2 : 1;
+}
+static float* ae_img_ptr(float* aews) { return aews; }
 // st_model_bwd_knobs: does the autoencoder backward this geometry / precision / tuning state routes to (behind a forward that kept its state) exist with the
 // per-group d a5 output?  Instantiated: the wide path's fused kernel, the kept-activation fp32 kernel and the 16-bit decoder half -- what the shipped
 // defaults reach.  A diagnostic switch away from its default (g_ae_split, g_ae_save) can route elsewhere.
@@ -511,7 +526,7 @@ static int pad_scale(const float* in, float* out, int B, int Ls, int pad, float 
 // AA16 != NULL (fused step of the 16-bit GEMM configurations): the spectra are written rounded to the operand type, not as fp32
 static int ae_fwd_impl(const st_dims* d, const float* mag, const float* phs, const float* knobs,
                        const float* ae_m, const float* ae_p, float* mag_hat, float* phs_hat, float* AA,
-                       float* reg_partial, float* ws, void* stream, unsigned short* AA16 = nullptr, bool wide_in_done = false, float* sv = nullptr);
+                       float* reg_partial, float* ws, void* stream, unsigned short* AA16 = nullptr, bool wide_in_done = false, float* sv = nullptr, const float* img = nullptr);
 extern "C" int st_ae_fwd(const st_dims* d, const float* mag, const float* phs, const float* knobs,
                          const float* ae_m, const float* ae_p, float* mag_hat, float* phs_hat, float* AA,
                          float* reg_partial, float* ws, void* stream)
@@ -520,8 +535,9 @@ extern "C" int st_ae_fwd(const st_dims* d, const float* mag, const float* phs, c
 }
 static int ae_fwd_impl(const st_dims* d, const float* mag, const float* phs, const float* knobs,
                        const float* ae_m, const float* ae_p, float* mag_hat, float* phs_hat, float* AA,
-                       float* reg_partial, float* ws, void* stream, unsigned short* AA16, bool wide_in_done, float* sv)
+                       float* reg_partial, float* ws, void* stream, unsigned short* AA16, bool wide_in_done, float* sv, const float* img)
 {      // sv != NULL (fused fp32 geometries, training step): the activations are kept for the backward (ae_sv_floats)
+       // img != NULL (fused step, fp32 layers): prep_kernel built the weight images of this step (ae_img_level); the per-op entry builds them in the kernel
     Layout L; ST_TRY(make_layout(d, &L));
     const int aa_ht = AA16 ? gemm_ht(d->prec) : 0;
     ST_REQ(mag && phs && (knobs || d->K == 0) && ae_m && ae_p && ((mag_hat && phs_hat && AA) || (!mag_hat && !phs_hat && !AA && ws)), "st_ae_fwd: null pointer");
@@ -539,7 +555,7 @@ static int ae_fwd_impl(const st_dims* d, const float* mag, const float* phs, con
 #define ST_AE_FWD_LAUNCH(HT_) do { ST_DYN_LDS((sta::ae_fwd_kernel<AE_FWD_NW, HT_>)); \
         hipLaunchKernelGGL((sta::ae_fwd_kernel<AE_FWD_NW, HT_>), dim3(ae_fwd_grid(d)), dim3(AE_FWD_NW * 64), lds, st_stream(stream), \
                            mag, phs, knobs, ae_m, ae_p, L.go, mag_hat, phs_hat, AA, reg_partial, \
-                           d->B, d->T, d->OT, d->F, d->K, L.KP, expfac, ws, AA16, aa_ht); } while (0)
+                           d->B, d->T, d->OT, d->F, d->K, L.KP, expfac, ws, AA16, aa_ht, (float*)nullptr, HT_ == 0 ? img : nullptr); } while (0)
     const bool use32 = g_ae32 && ae_ht(d->prec) != 0 && L.KP / 2 <= 17 * 32 && AE_FWD_NW == 8;
 #define ST_AE_FWD32_LAUNCH(HT_) do { ST_DYN_LDS((sta::ae_fwd32_kernel<AE_FWD_NW, HT_>)); \
         hipLaunchKernelGGL((sta::ae_fwd32_kernel<AE_FWD_NW, HT_>), dim3(ae_fwd_grid(d)), dim3(AE_FWD_NW * 64), (size_t)sta::ae32_lds_floats(L.KP / 2) * sizeof(float), st_stream(stream), \
@@ -553,13 +569,13 @@ static int ae_fwd_impl(const st_dims* d, const float* mag, const float* phs, con
             ST_REQ(mag_hat, "st_ae_fwd: internal: kept activations on a code-only pass");
 #define ST_AE_FWD_SV(NW_) do { ST_DYN_LDS((sta::ae_fwd_kernel<NW_, 0, true>)); \
             hipLaunchKernelGGL((sta::ae_fwd_kernel<NW_, 0, true>), dim3(ae_fwd_grid(d)), dim3(NW_ * 64), lds, st_stream(stream), \
-                               mag, phs, knobs, ae_m, ae_p, L.go, mag_hat, phs_hat, AA, reg_partial, d->B, d->T, d->OT, d->F, d->K, L.KP, expfac, ws, AA16, aa_ht, sv); } while (0)
+                               mag, phs, knobs, ae_m, ae_p, L.go, mag_hat, phs_hat, AA, reg_partial, d->B, d->T, d->OT, d->F, d->K, L.KP, expfac, ws, AA16, aa_ht, sv, img); } while (0)
             if (ae_fwd_nw(d) == 11) ST_AE_FWD_SV(11); else ST_AE_FWD_SV(AE_FWD_NW);
 #undef ST_AE_FWD_SV
         } else if (ae_fwd_nw(d) == 11) {
             ST_DYN_LDS((sta::ae_fwd_kernel<11, 0>));
             hipLaunchKernelGGL((sta::ae_fwd_kernel<11, 0>), dim3(ae_fwd_grid(d)), dim3(11 * 64), lds, st_stream(stream),
-                               mag, phs, knobs, ae_m, ae_p, L.go, mag_hat, phs_hat, AA, reg_partial, d->B, d->T, d->OT, d->F, d->K, L.KP, expfac, ws, AA16, aa_ht);
+                               mag, phs, knobs, ae_m, ae_p, L.go, mag_hat, phs_hat, AA, reg_partial, d->B, d->T, d->OT, d->F, d->K, L.KP, expfac, ws, AA16, aa_ht, (float*)nullptr, img);
         } else ST_AE_FWD_LAUNCH(0);
     }
 #undef ST_AE_FWD_LAUNCH
@@ -992,8 +1008,9 @@ static int ae_bwd_impl(const st_dims* d, const float* mag, const float* phs, con
                        const float* dAA, const float* g_mag_hat, float reg_coef, float* dmag, float* dphs, float* ws,
                        float* g_m, float* g_p, bool have_fwd, void* stream, bool* defer_reduce = nullptr,
                        const PolarSink* sink = nullptr, const stw::SynReduce* syn = nullptr, float* norm_e = nullptr, int* n_norm_e = nullptr,
-                       float* kg = nullptr)
+                       float* kg = nullptr, bool have_img = false)
 {
+    // have_img: the forward of this workspace was a fused one whose prep_kernel left the weight images there (ae_img_ptr)
     // kg (st_model_bwd_knobs): the kernel that holds d a5 also writes its per-group column sums there ([net][group][16]); only the instantiations the shipped
     // tuning defaults reach exist in that form (ae_kg_route)
     // defer_reduce: in -> the caller will sum the workgroup partials itself (post_ae_kernel, together with the polar backward);
@@ -1054,11 +1071,13 @@ static int ae_bwd_impl(const st_dims* d, const float* mag, const float* phs, con
     const int var = g_mag_hat ? 1 : (d->T - d->OT == 16 ? 2 : 0);
     if (have_fwd && ae_use_saved(d)) {               // round 6: the forward of this workspace kept the activations -- no recompute
         const float* sv = ae_sv_ptr(d, L, ws);
-#define ST_AE_BWD_SV_K(VAR_, KG_) do { ST_DYN_LDS((sta::ae_bwd_kernel<AE_BWD_NW, false, 0, VAR_, true, KG_>)); \
-        hipLaunchKernelGGL((sta::ae_bwd_kernel<AE_BWD_NW, false, 0, VAR_, true, KG_>), dim3(grid, 2), dim3(AE_BWD_NW * 64), lds, st_stream(stream), \
+        const float* img = (have_img && ae_img_level(d) == 2) ? ae_img_ptr(ws) : nullptr;
+#define ST_AE_BWD_SV_K(VAR_, KG_, IMG_) do { ST_DYN_LDS((sta::ae_bwd_kernel<AE_BWD_NW, false, 0, VAR_, true, KG_, IMG_>)); \
+        hipLaunchKernelGGL((sta::ae_bwd_kernel<AE_BWD_NW, false, 0, VAR_, true, KG_, IMG_>), dim3(grid, 2), dim3(AE_BWD_NW * 64), lds, st_stream(stream), \
                        mag, phs, knobs, ae_m, ae_p, L.go, L.PG, mag_hat, phs_hat, dAA, g_mag_hat, reg_coef, expfac, \
-                       dmag, dphs, parts, d->B, d->T, d->OT, d->F, d->K, L.KP, live.t_lo, live.t_lo + live.Tv - 1, st_synth_slabs(d), (size_t)d->B * d->OT * L.KP, sv, kg); } while (0)
-#define ST_AE_BWD_SV(VAR_) do { if (kg) ST_AE_BWD_SV_K(VAR_, true); else ST_AE_BWD_SV_K(VAR_, false); } while (0)
+                       dmag, dphs, parts, d->B, d->T, d->OT, d->F, d->K, L.KP, live.t_lo, live.t_lo + live.Tv - 1, st_synth_slabs(d), (size_t)d->B * d->OT * L.KP, sv, kg, img); } while (0)
+#define ST_AE_BWD_SV(VAR_) do { if (img) { if (kg) ST_AE_BWD_SV_K(VAR_, true, true); else ST_AE_BWD_SV_K(VAR_, false, true); } \
+                                else { if (kg) ST_AE_BWD_SV_K(VAR_, true, false); else ST_AE_BWD_SV_K(VAR_, false, false); } } while (0)
         if (var == 1) ST_AE_BWD_SV(1); else if (var == 2) ST_AE_BWD_SV(2); else ST_AE_BWD_SV(0);
 #undef ST_AE_BWD_SV
 #undef ST_AE_BWD_SV_K
@@ -1502,7 +1521,13 @@ static int forward_impl(const st_dims* d, const Layout& L, const float* params, 
             a.wd.n_vpad = (int)(((size_t)d->B * d->T * (FP - d->F) + 255) / 256); if (a.wd.n_vpad < 1) a.wd.n_vpad = 1;
             a.wd.n_kn = (int)(((size_t)d->K * d->B * (FP / 4) + 255) / 256);
         }
-        hipLaunchKernelGGL(stm::prep_kernel, dim3(a.n_pad + a.n_fold + n_dead + a.wd.n_vpad + a.wd.n_kn + a.wd.n_pj + a.n_w16), dim3(256), 0, st_stream(stream), a);
+        a.ai = sta::AEImgJob{}; a.ai.n_blk = 0;
+        if (ae_img_level(d)) {      // round 10: the autoencoders' LDS weight images, once per step instead of once per workgroup of ae_fwd / ae_bwd
+            a.ai.ae[0] = ae_m; a.ai.ae[1] = ae_p; a.ai.img = ae_img_ptr(w.aews); a.ai.go = L.go;
+            a.ai.T = d->T; a.ai.OT = d->OT; a.ai.K = d->K; a.ai.F = d->F; a.ai.FP = L.KP / 2; a.ai.expfac = (float)(7.0 / d->F);
+            a.ai.n = ae_img_level(d) == 2 ? sta::ae_img_floats(L.KP / 2) : sta::ae_img_fwd_floats(L.KP / 2); a.ai.n_blk = (a.ai.n + 255) / 256;
+        }
+        hipLaunchKernelGGL(stm::prep_kernel, dim3(a.n_pad + a.n_fold + n_dead + a.wd.n_vpad + a.wd.n_kn + a.wd.n_pj + a.ai.n_blk + a.n_w16), dim3(256), 0, st_stream(stream), a);
         ST_LAUNCHED("prep");
     }
     const bool planes = use_planes(d) && !w.g16;
@@ -1518,7 +1543,8 @@ static int forward_impl(const st_dims* d, const Layout& L, const float* params, 
     float* sv = nullptr;
     if (save && ae_use_saved(d)) { Layout Ls; ST_TRY(make_layout(d, &Ls)); sv = ae_sv_ptr(d, Ls, w.aews); }      // round 6: the activations stay for the backward
     ST_TRY(ae_fwd_impl(d, w.mag, w.phs, knobs, ae_m, ae_p, w.mag_hat, w.phs_hat, w.AA, w.reg_p,
-                       (ae_is_wide(d) || (save && ae_use_split(d))) ? w.aews : nullptr, stream, w.g16 ? w.AA16 : nullptr, wide_direct, sv));     // fused geometries: the code h4 is kept for the split backward
+                       (ae_is_wide(d) || (save && ae_use_split(d))) ? w.aews : nullptr, stream, w.g16 ? w.AA16 : nullptr, wide_direct, sv,
+                       ae_img_level(d) ? ae_img_ptr(w.aews) : nullptr));     // fused geometries: the code h4 is kept for the split backward
     if (w.g16) ST_TRY(synthesis_frames16(d, w, stream)); else
     if (planes) ST_TRY(synthesis_frames_planes(d, w, stream)); else
     ST_TRY(synthesis_frames_impl(d, w.AA, w.Sfold, w.SfoldT, w.frs, stream));
@@ -1566,7 +1592,7 @@ static int backward_ae(const st_dims* d, const Layout& L, const float* params, f
     }
     ST_TRY(ae_bwd_impl(d, w.mag, w.phs, knobs, ae_m, ae_p, w.mag_hat, w.phs_hat, w.dAA, g_mag_hat, reg_coef, w.dmag, w.dphs,
                        w.aews, grads + L.offs[4], grads + L.offs[22], true, stream, &deferred, &sink, syn.wg ? &syn : nullptr,
-                       (d->clip_all && ae_is_wide(d)) ? w.norm_e : nullptr, &w.n_norm_e, kg));      // the forward left its AE state in w.aews
+                       (d->clip_all && ae_is_wide(d)) ? w.norm_e : nullptr, &w.n_norm_e, kg, true));      // the forward left its AE state in w.aews
     if (!deferred) return ST_OK;                       // wide geometries: the gradient-finish launch summed the partials (and the synthesis slabs), and the polar backward ran inside wide_dv_polar_kernel
     stm::PostAeArgs a;
     a.ws = w.aews + 2 * ae_h4_floats(d); a.nparts = ae_use_split(d) ? ae_split_grid(d) : ae_bwd_grid(d); a.PG = L.PG; a.g_m = grads + L.offs[4]; a.g_p = grads + L.offs[22];
@@ -2421,7 +2447,9 @@ static int attr_prepare(const st_dims* d)
         ST_PREP3((sta::ae_fwd_kernel<AE_FWD_NW, 0>), (sta::ae_fwd_kernel<AE_FWD_NW, 1>), (sta::ae_fwd_kernel<AE_FWD_NW, 2>));
         if (ht == 1) ST_DYN_LDS((sta::ae_fwd32_kernel<AE_FWD_NW, 1>)); else if (ht == 2) ST_DYN_LDS((sta::ae_fwd32_kernel<AE_FWD_NW, 2>));
         if (ht == 0) { ST_DYN_LDS((sta::ae_fwd_kernel<11, 0>)); ST_DYN_LDS((sta::ae_fwd_kernel<11, 0, true>)); ST_DYN_LDS((sta::ae_fwd_kernel<AE_FWD_NW, 0, true>));
-                       ST_DYN_LDS((sta::ae_bwd_kernel<AE_BWD_NW, false, 0, 0, true>)); ST_DYN_LDS((sta::ae_bwd_kernel<AE_BWD_NW, false, 0, 1, true>)); ST_DYN_LDS((sta::ae_bwd_kernel<AE_BWD_NW, false, 0, 2, true>)); }
+                       ST_DYN_LDS((sta::ae_bwd_kernel<AE_BWD_NW, false, 0, 0, true>)); ST_DYN_LDS((sta::ae_bwd_kernel<AE_BWD_NW, false, 0, 1, true>)); ST_DYN_LDS((sta::ae_bwd_kernel<AE_BWD_NW, false, 0, 2, true>));
+                       ST_DYN_LDS((sta::ae_bwd_kernel<AE_BWD_NW, false, 0, 0, true, false, true>)); ST_DYN_LDS((sta::ae_bwd_kernel<AE_BWD_NW, false, 0, 1, true, false, true>));
+                       ST_DYN_LDS((sta::ae_bwd_kernel<AE_BWD_NW, false, 0, 2, true, false, true>)); }
         ST_PREP3((sta::ae_bwd_part_kernel<AE_SPLIT_NW, 1, 0, false>), (sta::ae_bwd_part_kernel<AE_SPLIT_NW, 1, 1, false>), (sta::ae_bwd_part_kernel<AE_SPLIT_NW, 1, 2, false>));
         ST_PREP3((sta::ae_bwd_part_kernel<AE_SPLIT_NW, 2, 0, false>), (sta::ae_bwd_part_kernel<AE_SPLIT_NW, 2, 1, false>), (sta::ae_bwd_part_kernel<AE_SPLIT_NW, 2, 2, false>));
         if (d->T - d->OT == 16) ST_PREP3((sta::ae_bwd_kernel<AE_BWD_NW, false, 0, 2>), (sta::ae_bwd_kernel<AE_BWD_NW, false, 1, 2>), (sta::ae_bwd_kernel<AE_BWD_NW, false, 2, 2>));

@@ -1,6 +1,7 @@
 // st_misc.h -- HBM-bound helper kernels of the SignalTrain step (gfx950).
 #pragma once
 #include "st_common.h"
+#include "st_ae.h"
 
 namespace stm {
 
@@ -282,6 +283,7 @@ struct PrepArgs {
     // and n_w16 more blocks write the F used rows of the analysis bases as rows (bin, re | im) interleaved: W16[2 bin + part][N]
     int ht; unsigned short *xp16, *Sfold16, *SfoldT16, *W16; const float* Wr; const float* Wi; int n_w16, n_dead;
     PrepWide wd;
+    sta::AEImgJob ai;      // round 10, fused fp32 autoencoders: the LDS weight images of both nets + the frequency-weight table, built once per step (st_ae.h ae_img_build)
 };
 // 32 x 32 tile of the folded synthesis bases, written twice: Sfold [KP][N] (rows k: the K-contiguous operand of the synthesis data-gradient
 // GEMM) and its transpose SfoldT [N][KP] (rows n: the K-contiguous operand of the synthesis FRAMES GEMM, which otherwise has to take
@@ -362,8 +364,10 @@ prep_kernel(const PrepArgs a)
     }
     else if (blk < a.n_pad + a.n_fold + a.n_dead + a.wd.n_vpad + a.wd.n_kn + a.wd.n_pj)
         pad_rows4_block(a.wd.pj, blk - a.n_pad - a.n_fold - a.n_dead - a.wd.n_vpad - a.wd.n_kn);
+    else if (blk < a.n_pad + a.n_fold + a.n_dead + a.wd.n_vpad + a.wd.n_kn + a.wd.n_pj + a.ai.n_blk)
+        sta::ae_img_build(a.ai, (blk - a.n_pad - a.n_fold - a.n_dead - a.wd.n_vpad - a.wd.n_kn - a.wd.n_pj) * 256 + (int)threadIdx.x);
     else {                                           // analysis bases, 4 taps per thread
-        const size_t i4 = (size_t)(blk - a.n_pad - a.n_fold - a.n_dead - a.wd.n_vpad - a.wd.n_kn - a.wd.n_pj) * 256 + threadIdx.x, n4 = a.N / 4;
+        const size_t i4 = (size_t)(blk - a.n_pad - a.n_fold - a.n_dead - a.wd.n_vpad - a.wd.n_kn - a.wd.n_pj - a.ai.n_blk) * 256 + threadIdx.x, n4 = a.N / 4;
         if (i4 < (size_t)2 * a.F * n4) {
             const int jrow = (int)(i4 / n4), c = (int)(i4 - (size_t)jrow * n4);
             const float4 v = reinterpret_cast<const float4*>(((jrow & 1) ? a.Wi : a.Wr) + (size_t)(jrow >> 1) * a.N)[c];
