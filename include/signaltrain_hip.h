@@ -429,6 +429,23 @@ int st_synth_effect(int effect, unsigned seed, unsigned long long first_window, 
                     const float* knob_lo, const float* knob_hi, int augment, int chooser, const float* pink_in,
                     float* x, float* y, float* knobs, float* scratch, void* stream);
 
+/* One training minibatch of RECORDED input / target pairs cut out of device-resident audio in ONE launch (st_feed_files.h; replaces
+ * AudioFileDataSet.get_single_chunk, datasets.py:225-253).  pool_x / pool_y hold all files concatenated (float32, or the int16 of the wav
+ * files: fmt), file f at samples [file_off[f], file_off[f] + file_len[f]).  Window b of the call is window w = first_window + b of the stream
+ * `seed`, a function of (seed, w) only, with integer draws (the law is written out in st_feed_files.h; datasets.file_feed_draw replicates it):
+ * a file uniformly over the files, a start uniformly in [0, len - L), and with `augment` one polarity flip of the pair.
+ *   x [B][L] = the window of pool_x, y [B][ysz] = the last ysz samples of the same span of pool_y (NULL: not made),
+ *   knobs [B][K] = the file's row of file_knobs [nfiles][K] (normalised settings; K == 0: both NULL), meta [B][3] = (file, start, flipped), or NULL.
+ * ST_PCM_S16 samples convert as (float)((double)s / 32767.0): a window out of the int16 pool equals the one out of the float32 pool bit for bit.
+ * min_len: the smallest file length, pool_samples: the pool's length (host values).  Refused before any launch (ST_ERR_ARG, the rule in
+ * st_last_error()): a null required pointer; B, L, ysz, nfiles <= 0; ysz > L; L % 4 or ysz % 4; K outside [0, 16]; file_knobs == NULL with K > 0
+ * (or not NULL with K == 0); an unknown fmt; min_len <= L; pool_samples < min_len.  No address outside the pools is formed even from wrong tables. */
+enum { ST_PCM_F32 = 0, ST_PCM_S16 = 1 };
+int st_file_feed(unsigned seed, unsigned long long first_window, int B, int L, int ysz, int K, int fmt,
+                 const void* pool_x, const void* pool_y, const long long* file_off, const long long* file_len, int nfiles,
+                 long long min_len, long long pool_samples, const float* file_knobs, int augment,
+                 float* x, float* y, float* knobs, long long* meta, void* stream);
+
 /* Gradient of the loss w.r.t. the (halved) input waveform, for callers with something trainable upstream of the model (the reference's
  * autograd provides it; nn_proc.py:307, cls_fe_dft.py:55-56).  Call right after st_model_bwd on the SAME workspace:
  *   gxh[b][n] = conv-transpose of the analysis output gradient with both bases, cropped by the Conv1d padding   [B][L]

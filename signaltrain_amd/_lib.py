@@ -65,6 +65,7 @@ SIGNATURES = {
     "st_synth_effect_scratch_floats": (C.c_size_t, [_i, _i, _i]),
     "st_synth_effect": (_i, [_i, C.c_uint, C.c_ulonglong, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float),
                              C.c_int, C.c_int, _p, _p, _p, _p, _p, _p]),
+    "st_file_feed": (_i, [C.c_uint, C.c_ulonglong, _i, _i, _i, _i, _i, _p, _p, _p, _p, _i, C.c_longlong, C.c_longlong, _p, _i, _p, _p, _p, _p, _p]),
     "st_fe_frames": (_i, [C.c_int] * 4),
     "st_fe_ws_floats": (C.c_size_t, [C.c_int] * 6),
     "st_fe_supported": (_i, [C.c_int] * 6),
@@ -126,6 +127,8 @@ SIGNATURES = {
 
 # effect ids of st_synth_effect (include/signaltrain_hip.h ST_FX_*)
 FX_COMP4C, FX_COMP = 0, 1
+# sample formats of st_file_feed's audio pools (include/signaltrain_hip.h ST_PCM_*)
+PCM_F32, PCM_S16 = 0, 1
 
 # st_dims.prec levels (include/signaltrain_hip.h ST_PREC_*) by the names the Python surface uses
 PREC = {"f32": 0, "bf16": 1, "bf16_all": 2, "f16": 3, "f16_all": 4, "f32x3": 5}

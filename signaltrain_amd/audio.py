@@ -219,10 +219,11 @@ def mu_decompand(y, mu=32):
     return np.sign(y) / mu * ((1 + mu) ** np.abs(y) - 1)
 
 
-def read_audio_file(filename, sr=44100, mono=True, norm=False, dtype=np.float32, **_ignored):
+def read_audio_file(filename, sr=44100, mono=True, norm=False, dtype=np.float32, info=None, **_ignored):
     """audio.py:207-255: a wav file as float in [-1, 1] (int16 / 32767), first channel if `mono`.  A file at another sample rate is resampled to
     `sr` with a polyphase filter (scipy.signal.resample_poly; the reference calls librosa.resample there -- another low-pass design, so such
-    files agree with the reference's to the filters' pass-band ripple, not bit for bit)."""
+    files agree with the reference's to the filters' pass-band ripple, not bit for bit).  info: an optional dict that receives what the
+    returned samples are -- "int16" (the file holds 16-bit PCM) and "exact" (they are still s / 32767 of it: neither resampled nor normalised)."""
     from scipy.io import wavfile
     import warnings
     with warnings.catch_warnings():
@@ -230,7 +231,10 @@ def read_audio_file(filename, sr=44100, mono=True, norm=False, dtype=np.float32,
         read_sr, signal = wavfile.read(filename)
     if mono and signal.ndim > 1:
         signal = signal[:, 0]
-    if signal.dtype == np.int16:
+    was_int16 = signal.dtype == np.int16
+    if info is not None:
+        info["int16"], info["exact"] = bool(was_int16), bool(was_int16 and read_sr == int(sr) and not norm)
+    if was_int16:
         signal = np.array(signal / 32767.0, dtype=dtype)
     signal = signal.astype(dtype, copy=False)
     if read_sr != int(sr):

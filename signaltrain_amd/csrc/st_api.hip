@@ -20,6 +20,7 @@
 #include "st_ae32.h"
 #include "st_dp.h"
 #include "st_feed.h"
+#include "st_feed_files.h"
 
 // ------------------------------------------------------------------------------ errors
 static thread_local char g_err[512] = "";
@@ -2070,6 +2071,41 @@ extern "C" int st_synth_comp4c(unsigned seed, unsigned long long first_window, i
 {
     ST_REQ(K == 4, "st_synth_comp4c: bad sizes (B=%d L=%d ysz=%d K=%d)", B, L, ysz, K);
     return st_synth_effect(ST_FX_COMP4C, seed, first_window, B, L, ysz, K, sr, knob_lo, knob_hi, augment, chooser, pink_in, x, y, knobs, scratch, stream);
+}
+
+// The feed of recorded input / target pairs (st_feed_files.h): B windows cut out of the device-resident audio pool in one launch.
+extern "C" int st_file_feed(unsigned seed, unsigned long long first_window, int B, int L, int ysz, int K, int fmt,
+                            const void* pool_x, const void* pool_y, const long long* file_off, const long long* file_len, int nfiles,
+                            long long min_len, long long pool_samples, const float* file_knobs, int augment,
+                            float* x, float* y, float* knobs, long long* meta, void* stream)
+{
+    ST_REQ(pool_x && file_off && file_len && x, "st_file_feed: null pointer (pool_x, file_off, file_len and x are required)");
+    ST_REQ(!y || pool_y, "st_file_feed: null pointer (pool_y is required when y is asked for)");
+    ST_REQ(B > 0 && L > 0 && ysz > 0 && nfiles > 0, "st_file_feed: bad sizes: B, L, ysz and nfiles must be positive (B=%d L=%d ysz=%d nfiles=%d)", B, L, ysz, nfiles);
+    ST_REQ(ysz <= L, "st_file_feed: ysz = %d exceeds L = %d (the target is the last ysz samples of the window)", ysz, L);
+    ST_REQ(L % 4 == 0 && ysz % 4 == 0, "st_file_feed: L = %d and ysz = %d must be multiples of 4 (the st_dims rule: 16-byte rows)", L, ysz);
+    ST_REQ(K >= 0 && K <= 16, "st_file_feed: K = %d knobs is outside [0, 16]", K);
+    ST_REQ(K == 0 || (file_knobs && knobs), "st_file_feed: null pointer (file_knobs and knobs are required when K = %d > 0)", K);
+    ST_REQ(K > 0 || !file_knobs, "st_file_feed: file_knobs must be NULL when K = 0");
+    ST_REQ(fmt == ST_PCM_F32 || fmt == ST_PCM_S16, "st_file_feed: fmt = %d is not an ST_PCM_* id (ST_PCM_F32 = 0, ST_PCM_S16 = 1)", fmt);
+    ST_REQ(min_len > (long long)L, "st_file_feed: min_len = %lld: every file must be longer than the window L = %d", min_len, L);
+    ST_REQ(pool_samples >= min_len, "st_file_feed: pool_samples = %lld is below min_len = %lld", pool_samples, min_len);
+    stf::FileFeedArgs a;
+    a.pool_x = pool_x; a.pool_y = pool_y; a.file_off = file_off; a.file_len = file_len; a.file_knobs = file_knobs;
+    a.pool_samples = pool_samples; a.seed = seed; a.L = L; a.ysz = ysz; a.K = K; a.nfiles = nfiles; a.augment = augment ? 1 : 0;
+    a.nsx = (L + stf::FILE_SEG - 1) / stf::FILE_SEG;
+    const int nsy = y ? (ysz + stf::FILE_SEG - 1) / stf::FILE_SEG : 0;
+    const int SUB = 32768;                                   // windows per launch: gridDim.y stays below 65536
+    for (int b0 = 0; b0 < B; b0 += SUB) {
+        const int nb = B - b0 < SUB ? B - b0 : SUB;
+        a.first = first_window + (unsigned long long)b0;
+        a.x = x + (size_t)b0 * L; a.y = y ? y + (size_t)b0 * ysz : nullptr; a.knobs = knobs ? knobs + (size_t)b0 * K : nullptr;
+        a.meta = meta ? meta + (size_t)b0 * 3 : nullptr;
+        if (fmt == ST_PCM_S16) hipLaunchKernelGGL(stf::file_feed_kernel<short>, dim3(a.nsx + nsy, nb), dim3(256), 0, st_stream(stream), a);
+        else hipLaunchKernelGGL(stf::file_feed_kernel<float>, dim3(a.nsx + nsy, nb), dim3(256), 0, st_stream(stream), a);
+        ST_LAUNCHED(fmt == ST_PCM_S16 ? "file_feed_s16" : "file_feed_f32");
+    }
+    return ST_OK;
 }
 
 // ------------------------------------------------------------------------------ generic learned-basis front end (a15)

@@ -29,6 +29,7 @@ __device__ __forceinline__ unsigned mix32(unsigned x)
 __device__ __forceinline__ float u01(const unsigned h) { return (float)(h >> 8) * (1.0f / 16777216.0f); }      // [0, 1)
 struct Draw {              // sequential scalar draws of one window (every thread evaluates the same sequence)
     unsigned key, ctr;
+    __device__ unsigned h() { return mix32(key + 0x9E3779B9u * (++ctr)); }      // the next 32-bit hash itself (integer draws: st_feed_files.h)
     __device__ float u() { return u01(mix32(key + 0x9E3779B9u * (++ctr))); }
     __device__ float sign() { return u() < 0.5f ? -1.f : 1.f; }
     __device__ int randint(int lo, int hi) { const int v = lo + (int)(u() * (float)(hi - lo)); return v < hi ? v : hi - 1; }      // [lo, hi)

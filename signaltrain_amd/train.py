@@ -182,8 +182,8 @@ def train(effect=None, epochs=100, n_data_points=200000, batch_size=20, device=N
     here float16 operands with fp32 accumulation, a loss scale and the L1 clip over all parameters (train.py:133-136) --
     compute_dtype "f16_all".  Extra keywords (not in the reference): compute_dtype overrides the arithmetic ("f32", "bf16",
     "bf16_all", "f16", "f16_all"; bf16 is the MI355X-native choice and needs no loss scale); device_feed: True (default) = the synthetic task's minibatches are
-    generated on the GPU (csrc/st_feed.h; "recycle": one device-resident training set re-sampled each epoch) and file datasets gather their windows on the
-    device; False = the reference's feed, a torch DataLoader with `num_workers` CPU workers over the Dataset's __getitem__ (two to three orders of magnitude
+    generated on the GPU (csrc/st_feed.h; "recycle": one device-resident training set re-sampled each epoch) and file datasets cut their windows out of the
+    device-resident audio (datasets.DeviceFileLoader, csrc/st_feed_files.h; target_type="chunk" re-runs an effect that has go_device on the device); False = the reference's feed, a torch DataLoader with `num_workers` CPU workers over the Dataset's __getitem__ (two to three orders of magnitude
     below the step rate; printed when chosen); resume_optimizer: False (default, the reference's behaviour: train `epochs`
     more epochs from the loaded weights with a fresh optimizer and schedule -- its fine-tune workflow); True restores Adam's moments
     from the checkpoint (which the reference saves but never reads back, train.py:229) and, if the checkpoint belongs to THIS schedule
@@ -222,7 +222,10 @@ def train(effect=None, epochs=100, n_data_points=200000, batch_size=20, device=N
                                             rerun=(target_type != "stream"), augment=True, preload=True, compand=compand)
         dataset_val = datasets.AudioFileDataSet(chunk_size, effect, sr=sr, datapoints=n_data_points // 4, path=datapath + "/Val/", y_size=out_chunk_size,
                                                 rerun=(target_type != "stream"), augment=False, compand=compand)
-        if device_feed and target_type == "stream":
+        if device_feed and device.type == "cuda" and (target_type == "stream" or hasattr(effect, "go_device")):
+            # one st_file_feed launch per chunk of minibatches, on a side stream beside the steps; target_type="chunk": the effect re-run on the device
+            dataloader, dataloader_val = datasets.DeviceFileLoader(dataset, batch_size, device), datasets.DeviceFileLoader(dataset_val, batch_size, device)
+        elif device_feed and target_type == "stream":
             class _FileLoader:
                 def __init__(self_inner, ds): self_inner.ds = ds
                 def __iter__(self_inner): return self_inner.ds.device_batches(batch_size, device)
