@@ -7,6 +7,7 @@
 #include <math.h>
 #include <mutex>
 #include <set>
+#include <type_traits>
 #include <utility>
 #include "st_common.h"
 #include "st_gemm.h"
@@ -138,9 +139,8 @@ static void ae_shapes(const st_dims* d, int* out, int* in)
     memcpy(out, o, sizeof(o)); memcpy(in, i, sizeof(i));
 }
 
-extern "C" int64_t st_param_offsets(const st_dims* d, int64_t* offs)
+static int64_t param_offsets(const st_dims* d, int64_t* offs)
 {
-    if (check_dims(d) != ST_OK) return -1;
     int64_t off = 0; int n = 0;
     auto put = [&](int64_t sz) { if (offs) offs[n] = off; ++n; off += (sz + 3) / 4 * 4; };
     for (int s = 0; s < 4; ++s) put((int64_t)d->N * d->N);
@@ -149,6 +149,7 @@ extern "C" int64_t st_param_offsets(const st_dims* d, int64_t* offs)
         for (int l = 0; l < 9; ++l) { put((int64_t)out[l] * in[l]); put(out[l]); }
     return off;
 }
+extern "C" int64_t st_param_offsets(const st_dims* d, int64_t* offs) { return check_dims(d) != ST_OK ? -1 : param_offsets(d, offs); }
 
 struct Layout {            // everything derived from dims that the host side needs
     int64_t offs[40]; int64_t total; int64_t n_stft; int PG; sta::AEOffsets go; int KP;
@@ -156,7 +157,7 @@ struct Layout {            // everything derived from dims that the host side ne
 static int make_layout(const st_dims* d, Layout* L)
 {
     ST_TRY(check_dims(d));
-    L->total = st_param_offsets(d, L->offs);
+    L->total = param_offsets(d, L->offs);
     L->n_stft = L->offs[4];
     L->PG = (int)(L->offs[22] - L->offs[4]);
     for (int l = 0; l < 9; ++l) {
@@ -274,6 +275,11 @@ extern "C" int st_reset_tuning(void)
 static inline int gemm_ht(int prec) { return (prec == ST_PREC_BF16 || prec == ST_PREC_BF16_ALL) ? 1 : ((prec == ST_PREC_F16 || prec == ST_PREC_F16_ALL) ? 2 : (prec == ST_PREC_F32X3 ? 3 : 0)); }
 static inline int ae_ht(int prec) { return prec == ST_PREC_BF16_ALL ? 1 : (prec == ST_PREC_F16_ALL ? 2 : 0); }
 static inline float loss_scale_of(const st_dims* d) { return d->loss_scale > 0.f ? d->loss_scale : 1.0f; }
+// The model's constants, each in ONE place: the L1 regulariser's weight of loss_functions.py:36 per element of mag_hat (reg_scale_of), the same times the loss scale
+// as the backward kernels take it (reg_coef_of: (loss scale * c) / elements, in this order -- the fused tests compare bits), and the slope of its frequency weights
+static inline float reg_scale_of(const st_dims* d) { return (float)(2e-5 / 10.0) / ((float)d->B * (float)d->OT * (float)d->F); }
+static inline float reg_coef_of(const st_dims* d) { return loss_scale_of(d) * (float)(2e-5 / 10.0) / ((float)d->B * (float)d->OT * (float)d->F); }
+static inline float expfac_of(const st_dims* d) { return (float)(7.0 / d->F); }
 // every ST_GEMM* user has `d` (const st_dims*) in scope
 #define ST_GEMM_BK(BK_, W_, ...) do { const int ht_ = gemm_ht(d->prec); \
                               if (ht_ == 1) stg::launch_half<W_, 1>(__VA_ARGS__); else if (ht_ == 2) stg::launch_half<W_, 2>(__VA_ARGS__); \
@@ -302,8 +308,27 @@ static int ensure_dyn_lds(const void* fn, const char* name)
     done.insert({dev, fn});
     return ST_OK;
 }
-#define ST_DYN_LDS(kernel_) ST_TRY(ensure_dyn_lds(reinterpret_cast<const void*>(&kernel_), #kernel_))
+// One launch of a kernel that may need more than 64 KB of dynamic LDS: the attribute (once per device and kernel), then the launch.  The arguments convert to
+// the kernel's parameter types as in a plain call; ST_LAUNCHED("name") follows the launch, or the group of launches that shares one mark.
+template <class... P, class... A>
+static int launch_lds(const char* name, void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t s, A&&... args)
+{
+    static_assert(sizeof...(P) == sizeof...(A), "launch_lds: argument count");
+    ST_TRY(ensure_dyn_lds(reinterpret_cast<const void*>(kernel), name));
+    hipLaunchKernelGGL(kernel, grid, block, lds, s, static_cast<P>(args)...);
+    return ST_OK;
+}
+// From a run-time value to a template argument: f is a generic lambda that receives the value as a std::integral_constant (HT() is a constant expression) and is
+// instantiated once per member of the set -- so a family that exists for a subset only is dispatched over that subset.  Each returns what f returns.
+template <int V> using ic = std::integral_constant<int, V>;
+template <class F> static inline auto with_ht(int ht, F&& f) { return ht == 1 ? f(ic<1>{}) : ht == 2 ? f(ic<2>{}) : f(ic<0>{}); }      // 0 fp32 / 1 bfloat16 / 2 float16
+template <class F> static inline auto with_ht16(int ht, F&& f) { return ht == 2 ? f(ic<2>{}) : f(ic<1>{}); }                          // the two 16-bit levels
+template <class F> static inline auto with_bool(bool b, F&& f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
+template <class F> static inline auto with_var(int var, F&& f) { return with_ht(var, f); }                                        // ae_bwd_kernel's VAR: 0 / 1 / 2 as well (see ae_bwd_body)
+template <class F> static inline auto with_slabs(int ns, F&& f) { return ns == 3 ? f(ic<3>{}) : ns == 2 ? f(ic<2>{}) : f(ic<1>{}); }   // 1..3 split-K slabs
 static const int AE_FWD_NW = 8, AE_BWD_NW = 4;
+template <class F> static inline auto with_fwd_nw(int nw, F&& f) { return nw == 11 ? f(ic<11>{}) : f(ic<AE_FWD_NW>{}); }                             // ae_fwd_nw: {8, 11}
+template <class F> static inline auto with_inner_nw(int nw, F&& f) { return nw == 9 ? f(ic<9>{}) : nw == 12 ? f(ic<12>{}) : f(ic<AE_FWD_NW>{}); }   // ae_inner_nw: {8, 9, 12}
 static int synth_live_rows(const st_dims* d);
 static bool ae_is_wide(const st_dims* d);
 // Waves per workgroup of the fused forward kernel: 8, or 11 where that removes the tail round.  A wave walks whole 16-row groups,
@@ -352,11 +377,16 @@ static int wgrad_split_tiles(int R, int M, int Nc)
     return s < fit ? s : fit;
 }
 static int synth_split(int R) { return R >= 4096 ? 1 : 3; }   // consumers (ola_loss_kernel, ae_bwd_kernel) sum at most 3 slabs
+static int dgrad_slabs(int R) { return synth_split(R); }      // split-K slabs of the synthesis data-gradient GEMM over R live rows
 
+// Sizes for internal code, which holds checked dims; the extern "C" functions of these names ask check_dims first
 // (the host size functions answer 0 for dims outside the supported family, with the rule in st_last_error(): check_dims)
-extern "C" int st_ae_fwd_partials(const st_dims* d) { return check_dims(d) != ST_OK ? 0 : ae_fwd_grid(d) * ae_fwd_nw(d); }
-extern "C" int st_ola_loss_partials(const st_dims* d) { return check_dims(d) != ST_OK ? 0 : d->B * ((d->y + 255) / 256); }
-extern "C" int st_norm_partials(const st_dims* d) { return check_dims(d) != ST_OK ? 0 : stm::norm_partial_count(d->F, d->N); }
+static int ae_fwd_partials(const st_dims* d) { return ae_fwd_grid(d) * ae_fwd_nw(d); }
+static int ola_loss_partials(const st_dims* d) { return d->B * ((d->y + 255) / 256); }
+static int norm_partials(const st_dims* d) { return stm::norm_partial_count(d->F, d->N); }
+extern "C" int st_ae_fwd_partials(const st_dims* d) { return check_dims(d) != ST_OK ? 0 : ae_fwd_partials(d); }
+extern "C" int st_ola_loss_partials(const st_dims* d) { return check_dims(d) != ST_OK ? 0 : ola_loss_partials(d); }
+extern "C" int st_norm_partials(const st_dims* d) { return check_dims(d) != ST_OK ? 0 : norm_partials(d); }
 // k-slices of the 128 x 128-tile weight-gradient GEMM (st_gemm_tn.h): as many as fill the CUs with one workgroup each, never slices
 // shorter than 64 reduction rows
 static int tn_split(int R, int N)
@@ -366,23 +396,25 @@ static int tn_split(int R, int N)
     const int cap = R / 64; if (s > cap) s = cap;
     return s < 1 ? 1 : s;
 }
-extern "C" size_t st_wgrad_ws_floats(const st_dims* d)
+static size_t wgrad_ws_floats(const st_dims* d)
 {
-    if (check_dims(d) != ST_OK) return 0;
     int s = wgrad_split_tiles(d->B * d->T, st_kp_of(d->F), d->N);
     const int s2 = tn_split(d->B * d->T, d->N); if (s2 > s) s = s2;
     return (size_t)s * st_kp_of(d->F) * d->N + (size_t)64 * 2 * d->N;       // + the Nyquist partials of the 128 x 128-tile form
 }
+extern "C" size_t st_wgrad_ws_floats(const st_dims* d) { return check_dims(d) != ST_OK ? 0 : wgrad_ws_floats(d); }
 // Round 6: a second slab area for the SYNTHESIS weight gradient alone.  In the data-parallel step its slabs are summed on the communicator stream beside the autoencoder
 // backward; with a buffer of their own the analysis weight-gradient GEMM (which reuses the first area) needs no communicator -> compute wait before it starts -- one
 // barrier packet (~6 us of bubble on this stack) less on the compute stream.  Same size as the first: every slab-count rule of the fp32 and 16-bit weight-gradient
 // launches is capped by that area's size.
-static size_t synth_wgrad_ws_floats(const st_dims* d) { return st_wgrad_ws_floats(d); }
-extern "C" int st_synth_slabs(const st_dims* d) { return check_dims(d) != ST_OK ? 0 : synth_split(synth_live_rows(d)); }
+static size_t synth_wgrad_ws_floats(const st_dims* d) { return wgrad_ws_floats(d); }
+static int synth_slabs(const st_dims* d) { return dgrad_slabs(synth_live_rows(d)); }
+extern "C" int st_synth_slabs(const st_dims* d) { return check_dims(d) != ST_OK ? 0 : synth_slabs(d); }
 // split-K slabs of the synthesis FRAMES GEMM (summed by ola_loss_kernel, which takes up to 6; the dgrad slabs are summed
 // inside ae_bwd_kernel where every extra slab costs 8 loads per row group, hence the separate, smaller count above)
 static int frames_split(int R) { return R >= 4096 ? 1 : 3; }      // 3, 4 measured equal, 6 slower (only 66 k-tiles to split)
-extern "C" int st_synth_frame_slabs(const st_dims* d) { return check_dims(d) != ST_OK ? 0 : frames_split(synth_live_rows(d)); }
+static int frame_slabs(const st_dims* d) { return frames_split(synth_live_rows(d)); }
+extern "C" int st_synth_frame_slabs(const st_dims* d) { return check_dims(d) != ST_OK ? 0 : frame_slabs(d); }
 // Wide geometries (T > 32 or OT > 16) run the autoencoders as feature-major GEMMs (st_ae_wide.h) and need workspace
 // for the activations [features][B*FP]; the fused kernels of st_ae.h need none in forward.
 static bool ae_is_wide(const st_dims* d) { return d->T > 32 || d->OT > 16; }
@@ -392,7 +424,7 @@ struct WideWS {
     // every layer-input buffer (V, H[.][j]) has ONE extra row (index = that layer's IN) of ones: bias gradient via the wgrad GEMM
     size_t fwd_floats, floats; int Tp, nsplit; size_t R, SL; int so[10];
 };
-static void wide_carve(const st_dims* d, float* base, WideWS* w)
+static void wide_carve(const st_dims* d, const Layout& L, float* base, WideWS* w)
 {
     const int FP = st_kp_of(d->F) / 2;
     const size_t R = (size_t)d->B * FP;
@@ -418,7 +450,7 @@ static void wide_carve(const st_dims* d, float* base, WideWS* w)
         w->TL[a] = take((size_t)d->OT * R);
     }
     w->slabs = take((size_t)2 * w->nsplit * w->SL);
-    { Layout L; if (make_layout(d, &L) == ST_OK) w->inner_ws = take((size_t)ae_bwd_grid(d) * 2 * L.PG); else w->inner_ws = nullptr; }
+    w->inner_ws = take((size_t)ae_bwd_grid(d) * 2 * L.PG);
     w->floats = off;
 }
 // Fused geometries: the autoencoder workspace is [h4 exchange | d a4 exchange | workgroup gradient partials]; the first two are the
@@ -466,21 +498,21 @@ static const char* ae_kg_why(const st_dims* d)
 static bool ae_kg_route(const st_dims* d) { return ae_kg_why(d) == nullptr; }
 extern "C" size_t st_ae_fwd_ws_floats(const st_dims* d)
 {
-    if (check_dims(d) != ST_OK) return 0;
+    Layout L; if (make_layout(d, &L) != ST_OK) return 0;
     if (!ae_is_wide(d)) return ae_h4_floats(d);             // optional for the forward alone (ws may be NULL: h4 is then not kept)
-    WideWS w; wide_carve(d, nullptr, &w); return w.fwd_floats;
+    WideWS w; wide_carve(d, L, nullptr, &w); return w.fwd_floats;
 }
 extern "C" size_t st_ae_kept_activation_bytes(const st_dims* d)
 {
     if (check_dims(d) != ST_OK || !ae_use_saved(d)) return 0;
     return ae_sv_floats(d) * sizeof(float);
 }
-extern "C" size_t st_ae_bwd_ws_floats(const st_dims* d)
+static size_t ae_bwd_ws_floats(const st_dims* d, const Layout& L)
 {
-    Layout L; if (make_layout(d, &L) != ST_OK) return 0;
-    if (ae_is_wide(d)) { WideWS w; wide_carve(d, nullptr, &w); return w.floats; }
+    if (ae_is_wide(d)) { WideWS w; wide_carve(d, L, nullptr, &w); return w.floats; }
     return 2 * ae_h4_floats(d) + (size_t)ae_parts_max(d) * 2 * L.PG + ae_sv_floats(d);
 }
+extern "C" size_t st_ae_bwd_ws_floats(const st_dims* d) { Layout L; return make_layout(d, &L) != ST_OK ? 0 : ae_bwd_ws_floats(d, L); }
 static int ae_wide_fwd(const st_dims* d, const Layout& L, const float* mag, const float* phs, const float* knobs,
                        const float* ae_m, const float* ae_p, float* mag_hat, float* phs_hat, float* AA, float* reg_partial,
                        WideWS& w, void* stream, unsigned short* AA16 = nullptr, bool in_done = false);
@@ -525,63 +557,53 @@ static int pad_scale(const float* in, float* out, int B, int Ls, int pad, float 
 }
 
 // AA16 != NULL (fused step of the 16-bit GEMM configurations): the spectra are written rounded to the operand type, not as fp32
-static int ae_fwd_impl(const st_dims* d, const float* mag, const float* phs, const float* knobs,
+static int ae_fwd_body(const st_dims* d, const Layout& L, const float* mag, const float* phs, const float* knobs,
                        const float* ae_m, const float* ae_p, float* mag_hat, float* phs_hat, float* AA,
-                       float* reg_partial, float* ws, void* stream, unsigned short* AA16 = nullptr, bool wide_in_done = false, float* sv = nullptr, const float* img = nullptr);
-extern "C" int st_ae_fwd(const st_dims* d, const float* mag, const float* phs, const float* knobs,
-                         const float* ae_m, const float* ae_p, float* mag_hat, float* phs_hat, float* AA,
-                         float* reg_partial, float* ws, void* stream)
-{
-    return ae_fwd_impl(d, mag, phs, knobs, ae_m, ae_p, mag_hat, phs_hat, AA, reg_partial, ws, stream);
-}
-static int ae_fwd_impl(const st_dims* d, const float* mag, const float* phs, const float* knobs,
-                       const float* ae_m, const float* ae_p, float* mag_hat, float* phs_hat, float* AA,
-                       float* reg_partial, float* ws, void* stream, unsigned short* AA16, bool wide_in_done, float* sv, const float* img)
+                       float* reg_partial, float* ws, void* stream, unsigned short* AA16 = nullptr, bool wide_in_done = false, float* sv = nullptr, const float* img = nullptr)
 {      // sv != NULL (fused fp32 geometries, training step): the activations are kept for the backward (ae_sv_floats)
        // img != NULL (fused step, fp32 layers): prep_kernel built the weight images of this step (ae_img_level); the per-op entry builds them in the kernel
-    Layout L; ST_TRY(make_layout(d, &L));
     const int aa_ht = AA16 ? gemm_ht(d->prec) : 0;
     ST_REQ(mag && phs && (knobs || d->K == 0) && ae_m && ae_p && ((mag_hat && phs_hat && AA) || (!mag_hat && !phs_hat && !AA && ws)), "st_ae_fwd: null pointer");
     if (!knobs) knobs = ae_m;      // K == 0: the kernels issue one clamped, masked load of knobs[0] -- any resident float will do
     if (ae_is_wide(d)) {
         ST_REQ(mag_hat, "st_ae_fwd: the code-only pass exists for the fused geometries only");
         ST_REQ(ws, "st_ae_fwd: this geometry (T=%d, OT=%d) needs st_ae_fwd_ws_floats() floats of workspace", d->T, d->OT);
-        WideWS w; wide_carve(d, ws, &w);
+        WideWS w; wide_carve(d, L, ws, &w);
         return ae_wide_fwd(d, L, mag, phs, knobs, ae_m, ae_p, mag_hat, phs_hat, AA, reg_partial, w, stream, AA16, wide_in_done);
     }
     ST_REQ((size_t)d->B * d->T * d->F < ((size_t)1 << 30) && (size_t)d->B * d->OT * L.KP < ((size_t)1 << 30),
            "st_ae_fwd: batch too large for the kernel's 32-bit element offsets (B=%d)", d->B);
     const size_t lds = ((size_t)2 * sta::CL::FWD_TOTAL + (size_t)(L.KP / 2)) * sizeof(float);      // two forward images + the per-bin frequency weights
-    const float expfac = (float)(7.0 / d->F);
-#define ST_AE_FWD_LAUNCH(HT_) do { ST_DYN_LDS((sta::ae_fwd_kernel<AE_FWD_NW, HT_>)); \
-        hipLaunchKernelGGL((sta::ae_fwd_kernel<AE_FWD_NW, HT_>), dim3(ae_fwd_grid(d)), dim3(AE_FWD_NW * 64), lds, st_stream(stream), \
-                           mag, phs, knobs, ae_m, ae_p, L.go, mag_hat, phs_hat, AA, reg_partial, \
-                           d->B, d->T, d->OT, d->F, d->K, L.KP, expfac, ws, AA16, aa_ht, (float*)nullptr, HT_ == 0 ? img : nullptr); } while (0)
-    const bool use32 = g_ae32 && ae_ht(d->prec) != 0 && L.KP / 2 <= 17 * 32 && AE_FWD_NW == 8;
-#define ST_AE_FWD32_LAUNCH(HT_) do { ST_DYN_LDS((sta::ae_fwd32_kernel<AE_FWD_NW, HT_>)); \
-        hipLaunchKernelGGL((sta::ae_fwd32_kernel<AE_FWD_NW, HT_>), dim3(ae_fwd_grid(d)), dim3(AE_FWD_NW * 64), (size_t)sta::ae32_lds_floats(L.KP / 2) * sizeof(float), st_stream(stream), \
-                           mag, phs, knobs, ae_m, ae_p, L.go, mag_hat, phs_hat, AA, reg_partial, \
-                           d->B, d->T, d->OT, d->F, d->K, L.KP, expfac, ws, AA16, aa_ht); } while (0)
-    switch (ae_ht(d->prec)) {
-    case 1: if (use32) ST_AE_FWD32_LAUNCH(1); else ST_AE_FWD_LAUNCH(1); break;
-    case 2: if (use32) ST_AE_FWD32_LAUNCH(2); else ST_AE_FWD_LAUNCH(2); break;
-    default:
-        if (sv) {
-            ST_REQ(mag_hat, "st_ae_fwd: internal: kept activations on a code-only pass");
-#define ST_AE_FWD_SV(NW_) do { ST_DYN_LDS((sta::ae_fwd_kernel<NW_, 0, true>)); \
-            hipLaunchKernelGGL((sta::ae_fwd_kernel<NW_, 0, true>), dim3(ae_fwd_grid(d)), dim3(NW_ * 64), lds, st_stream(stream), \
-                               mag, phs, knobs, ae_m, ae_p, L.go, mag_hat, phs_hat, AA, reg_partial, d->B, d->T, d->OT, d->F, d->K, L.KP, expfac, ws, AA16, aa_ht, sv, img); } while (0)
-            if (ae_fwd_nw(d) == 11) ST_AE_FWD_SV(11); else ST_AE_FWD_SV(AE_FWD_NW);
-#undef ST_AE_FWD_SV
-        } else if (ae_fwd_nw(d) == 11) {
-            ST_DYN_LDS((sta::ae_fwd_kernel<11, 0>));
-            hipLaunchKernelGGL((sta::ae_fwd_kernel<11, 0>), dim3(ae_fwd_grid(d)), dim3(11 * 64), lds, st_stream(stream),
-                               mag, phs, knobs, ae_m, ae_p, L.go, mag_hat, phs_hat, AA, reg_partial, d->B, d->T, d->OT, d->F, d->K, L.KP, expfac, ws, AA16, aa_ht, (float*)nullptr, img);
-        } else ST_AE_FWD_LAUNCH(0);
-    }
-#undef ST_AE_FWD_LAUNCH
-#undef ST_AE_FWD32_LAUNCH
+    const float expfac = expfac_of(d);
+    const int ht = ae_ht(d->prec);
+    const dim3 grid(ae_fwd_grid(d));
+    hipStream_t s = st_stream(stream);
+    const bool use32 = g_ae32 && ht != 0 && L.KP / 2 <= 17 * 32 && AE_FWD_NW == 8;
+    if (use32)                      // 16-bit layers only: 32-row groups (st_ae32.h)
+        ST_TRY(with_ht16(ht, [&](auto HT) {
+            return launch_lds("ae_fwd32_kernel", sta::ae_fwd32_kernel<AE_FWD_NW, HT()>, grid, dim3(AE_FWD_NW * 64), (size_t)sta::ae32_lds_floats(L.KP / 2) * sizeof(float), s,
+                              mag, phs, knobs, ae_m, ae_p, L.go, mag_hat, phs_hat, AA, reg_partial, d->B, d->T, d->OT, d->F, d->K, L.KP, expfac, ws, AA16, aa_ht); }));
+    else if (ht != 0)               // ... on 16-row groups: no kept activations, no ready-made images
+        ST_TRY(with_ht16(ht, [&](auto HT) {
+            return launch_lds("ae_fwd_kernel", sta::ae_fwd_kernel<AE_FWD_NW, HT()>, grid, dim3(AE_FWD_NW * 64), lds, s,
+                              mag, phs, knobs, ae_m, ae_p, L.go, mag_hat, phs_hat, AA, reg_partial, d->B, d->T, d->OT, d->F, d->K, L.KP, expfac, ws, AA16, aa_ht, nullptr, nullptr); }));
+    else if (sv) {                  // fp32 layers: 8 or 11 waves (ae_fwd_nw), with or without the kept activations
+        ST_REQ(mag_hat, "st_ae_fwd: internal: kept activations on a code-only pass");
+        ST_TRY(with_fwd_nw(ae_fwd_nw(d), [&](auto NW) {
+            return launch_lds("ae_fwd_kernel", sta::ae_fwd_kernel<NW(), 0, true>, grid, dim3(NW() * 64), lds, s,
+                              mag, phs, knobs, ae_m, ae_p, L.go, mag_hat, phs_hat, AA, reg_partial, d->B, d->T, d->OT, d->F, d->K, L.KP, expfac, ws, AA16, aa_ht, sv, img); }));
+    } else
+        ST_TRY(with_fwd_nw(ae_fwd_nw(d), [&](auto NW) {
+            return launch_lds("ae_fwd_kernel", sta::ae_fwd_kernel<NW(), 0>, grid, dim3(NW() * 64), lds, s,
+                              mag, phs, knobs, ae_m, ae_p, L.go, mag_hat, phs_hat, AA, reg_partial, d->B, d->T, d->OT, d->F, d->K, L.KP, expfac, ws, AA16, aa_ht, nullptr, img); }));
     ST_LAUNCHED("ae_fwd"); return ST_OK;
+}
+extern "C" int st_ae_fwd(const st_dims* d, const float* mag, const float* phs, const float* knobs,
+                         const float* ae_m, const float* ae_p, float* mag_hat, float* phs_hat, float* AA,
+                         float* reg_partial, float* ws, void* stream)
+{
+    Layout L; ST_TRY(make_layout(d, &L));
+    return ae_fwd_body(d, L, mag, phs, knobs, ae_m, ae_p, mag_hat, phs_hat, AA, reg_partial, ws, stream);
 }
 
 extern "C" int st_synth_fold(const st_dims* d, const float* Sr, const float* Si, float* Sfold, void* stream)
@@ -667,7 +689,7 @@ extern "C" int st_nt128_worklist(const st_dims* d, int which, int ncus, unsigned
     if (ncus <= 0) ncus = num_cus();
     stg::NTWork wk; wk.n = 0;
     if (!use_nt128(d, R, which ? KP : d->N, ncus)) return 0;
-    const bool ok = which ? stg::ntw_dgrad(wk, ms, d->B, d->H, d->N, d->N, d->y, d->F, KP, R >= 4096 ? 1 : synth_split(R), ncus)
+    const bool ok = which ? stg::ntw_dgrad(wk, ms, d->B, d->H, d->N, d->N, d->y, d->F, KP, dgrad_slabs(R), ncus)
                           : stg::ntw_frames(wk, ms, d->B, d->H, d->N, d->N, d->y, KP, frames_split(R), ncus);
     if (!ok) return 0;
     head6[0] = wk.nslabs; head6[1] = wk.col_h; head6[2] = wk.col_stride; head6[3] = d->B; head6[4] = wk.kunit; head6[5] = wk.kt_total;
@@ -684,7 +706,7 @@ static int ola_loss_impl(const st_dims* d, const float* frs, const float* x, con
     if (with_mae) ST_REQ(y_true && loss_partial && !dsyn, "ola_loss: the MAE partials come with a target and without d syn");
     const float inv = loss_scale_of(d) / ((float)d->B * (float)d->y);     // d loss / d y_hat, times the loss scale (train.py:134-135)
     {   // four samples per thread (round 5) where the geometry and the pointers allow 16-byte accesses: always inside the fused step
-        const int ns = st_synth_frame_slabs(d), nslot = (d->y + 255) / 256;
+        const int ns = frame_slabs(d), nslot = (d->y + 255) / 256;
         auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
         const bool ok4 = d->H % 4 == 0 && d->N % 4 == 0 && d->y % 4 == 0 && d->L % 4 == 0 && dsyn_pad % 4 == 0 && ns >= 1 && ns <= 3 && (d->N + d->H - 1) / d->H <= 3 &&
                          al16(frs) && al16(x) && al16(y_true) && al16(y_hat) && al16(dsyn) && al16(dsyn16) && ((size_t)d->B * d->OT * d->N) % 4 == 0;
@@ -692,19 +714,16 @@ static int ola_loss_impl(const st_dims* d, const float* frs, const float* x, con
             const dim3 grid((d->y / 4 + 255) / 256, d->B);
             const size_t slab = (size_t)d->B * d->OT * d->N;
             unsigned short* d16 = dsyn ? dsyn16 : nullptr; const int ht = dsyn16 ? gemm_ht(d->prec) : 0;
-#define ST_OLA4(NS_, MAE_) hipLaunchKernelGGL((stm::ola_loss4_kernel<NS_, MAE_>), grid, dim3(256), 0, st_stream(stream), frs, x, y_true, y_hat, dsyn, loss_partial, d->L, d->N, d->H, d->OT, d->y, inv, slab, dsyn_pad, nslot, d16, ht)
-            if (with_mae) { if (ns == 3) ST_OLA4(3, true); else if (ns == 2) ST_OLA4(2, true); else ST_OLA4(1, true); }
-            else if (ns == 3) ST_OLA4(3, false); else if (ns == 2) ST_OLA4(2, false); else ST_OLA4(1, false);
-#undef ST_OLA4
+            with_bool(with_mae, [&](auto MAE) { with_slabs(ns, [&](auto NS) {
+                hipLaunchKernelGGL((stm::ola_loss4_kernel<NS(), MAE()>), grid, dim3(256), 0, st_stream(stream), frs, x, y_true, y_hat, dsyn, loss_partial, d->L, d->N, d->H, d->OT, d->y, inv, slab, dsyn_pad, nslot, d16, ht); }); });
             ST_LAUNCHED("ola_loss");
             return ST_OK;
         }
     }
-#define ST_OLA1(MAE_) hipLaunchKernelGGL(stm::ola_loss_kernel<MAE_>, dim3((d->y + 255) / 256, d->B), dim3(256), 0, st_stream(stream), \
-                       frs, x, y_true, y_hat, dsyn, loss_partial, d->L, d->N, d->H, d->OT, d->y, inv, \
-                       st_synth_frame_slabs(d), (size_t)d->B * d->OT * d->N, dsyn_pad, dsyn ? dsyn16 : nullptr, dsyn16 ? gemm_ht(d->prec) : 0)
-    if (with_mae) ST_OLA1(true); else ST_OLA1(false);
-#undef ST_OLA1
+    with_bool(with_mae, [&](auto MAE) {
+        hipLaunchKernelGGL(stm::ola_loss_kernel<MAE()>, dim3((d->y + 255) / 256, d->B), dim3(256), 0, st_stream(stream),
+                           frs, x, y_true, y_hat, dsyn, loss_partial, d->L, d->N, d->H, d->OT, d->y, inv,
+                           frame_slabs(d), (size_t)d->B * d->OT * d->N, dsyn_pad, dsyn ? dsyn16 : nullptr, dsyn16 ? gemm_ht(d->prec) : 0); });
     ST_LAUNCHED("ola_loss");
     return ST_OK;
 }
@@ -725,7 +744,7 @@ static int synthesis_dgrad_impl(const st_dims* d, const float* dsyn, bool padded
     // dAA holds st_synth_slabs() split-K slabs [B*OT, KP]; st_ae_bwd sums them
     stg::PlainNT bl{Sfold, KP, d->N, d->N, stg::all_frames(1)};
     stg::StoreC ep{dAA, R, KP, KP, (size_t)d->B * d->OT * KP, ms};
-    const int ns = R >= 4096 ? 1 : synth_split(R);
+    const int ns = dgrad_slabs(R);
     if (padded) {
         stg::FramedNT<true> al{dsyn, d->y, d->H, d->N, R, d->N, 1.0f, ms};
         stg::NTWork wk;
@@ -808,7 +827,7 @@ static int synthesis_wgrad_impl(const st_dims* d, const float* AA, const float* 
     }
     ST_LAUNCHED("synthesis_wgrad");
     if (defer_slabs) { *defer_slabs = ns; if (defer_nyq) *defer_nyq = nyq; return ST_OK; }
-    hipLaunchKernelGGL(stm::wgrad_reduce_kernel, dim3(st_norm_partials(d)), dim3(256), 0, st_stream(stream),
+    hipLaunchKernelGGL(stm::wgrad_reduce_kernel, dim3(norm_partials(d)), dim3(256), 0, st_stream(stream),
                        ws, ns, gSr, gSi, norm_partial, d->N, d->F, KP, 1, 0, 2 * d->F, (float*)nullptr, nyq);
     ST_LAUNCHED("synthesis_wgrad_reduce");
     return ST_OK;
@@ -832,12 +851,28 @@ extern "C" int st_effective_prec(const st_dims* d)
 // BM = 64, k-tile 16 (every K below is a multiple of 16 or checked).  Level-2 precision: the 16-bit kernel (k-tile 32: W1 is padded to a multiple of 32
 // columns).  The weight-gradient GEMMs reduce over the R = B * 528 columns: a multiple of 32 for even batches; for ODD batches (R = 16 mod 32) they run
 // the same kernel on 16-deep k-tiles (round 5) -- until round 4 an odd batch dropped the whole wide path to fp32 layers (and said so: st_effective_prec),
-// the last place where the arithmetic of a call depended on its batch size.  wide_ht, a local of every user of ST_WGEMM_PAIR: 0 fp32 / 1 bf16 / 2 fp16.
+// the last place where the arithmetic of a call depended on its batch size.  wide_ht, the first argument of wgemm_pair: 0 fp32 / 1 bf16 / 2 fp16.
 // the same GEMM for both autoencoders: ONE launch in the 16-bit configurations (gemm_half_pair_kernel), two on the fp32 kernel
-#define ST_WGEMM_PAIR(A0_, B0_, E0_, A1_, B1_, E1_, M_, N_, K_, NS_, S_) do { \
-        if (wide_ht == 1) stg::launch_half_pair<2, 1>(A0_, B0_, E0_, A1_, B1_, E1_, M_, N_, K_, NS_, S_); \
-        else if (wide_ht == 2) stg::launch_half_pair<2, 2>(A0_, B0_, E0_, A1_, B1_, E1_, M_, N_, K_, NS_, S_); \
-        else { stg::launch<2, 16>(A0_, B0_, E0_, M_, N_, K_, NS_, S_); stg::launch<2, 16>(A1_, B1_, E1_, M_, N_, K_, NS_, S_); } } while (0)
+template <class AL, class BL, class EPI>
+static void wgemm_pair(int wide_ht, const AL& a0, const BL& b0, const EPI& e0, const AL& a1, const BL& b1, const EPI& e1, int M, int Nc, int K, int ns, hipStream_t s)
+{
+    if (wide_ht) with_ht16(wide_ht, [&](auto HT) { stg::launch_half_pair<2, HT()>(a0, b0, e0, a1, b1, e1, M, Nc, K, ns, s); });
+    else { stg::launch<2, 16>(a0, b0, e0, M, Nc, K, ns, s); stg::launch<2, 16>(a1, b1, e1, M, Nc, K, ns, s); }
+}
+// The four pad jobs of the wide path's side work (stw::PadJobs): W1 of either net padded to Tp columns, W5 to 32.  Returns their block count.
+static int fill_pad_jobs(stw::PadJobs& pj, const st_dims* d, const Layout& L, const float* ae_m, const float* ae_p, const WideWS& w)
+{
+    int blk = 0;
+    for (int a = 0; a < 2; ++a) {
+        const float* ae = a ? ae_p : ae_m;
+        pj.src[2 * a] = ae + L.go.w[0]; pj.dst[2 * a] = w.W1p[a]; pj.rows[2 * a] = 64; pj.cols[2 * a] = d->T; pj.pitch[2 * a] = w.Tp;
+        pj.blk0[2 * a] = blk; blk += (64 * w.Tp + 255) / 256;
+        pj.src[2 * a + 1] = ae + L.go.w[4]; pj.dst[2 * a + 1] = w.W5p[a]; pj.rows[2 * a + 1] = 16; pj.cols[2 * a + 1] = 16 + d->K; pj.pitch[2 * a + 1] = 32;
+        pj.blk0[2 * a + 1] = blk; blk += 2;
+    }
+    pj.blk0[4] = blk;
+    return blk;
+}
 static int ae_wide_fwd(const st_dims* d, const Layout& L, const float* mag, const float* phs, const float* knobs,
                        const float* ae_m, const float* ae_p, float* mag_hat, float* phs_hat, float* AA, float* reg_partial,
                        WideWS& w, void* stream, unsigned short* AA16, bool in_done)
@@ -849,15 +884,7 @@ static int ae_wide_fwd(const st_dims* d, const Layout& L, const float* mag, cons
     const stg::RowMap id = stg::all_frames(1);
     int out[9], in[9]; ae_shapes(d, out, in);
     if (!in_done) {      // the fused step's analysis GEMM wrote V itself and prep_kernel did the side jobs (round 4); the per-op entry copies here
-        stw::PadJobs pj; int blk = 0;
-        for (int a = 0; a < 2; ++a) {
-            const float* ae = a ? ae_p : ae_m;
-            pj.src[2 * a] = ae + L.go.w[0]; pj.dst[2 * a] = w.W1p[a]; pj.rows[2 * a] = 64; pj.cols[2 * a] = T; pj.pitch[2 * a] = Tp;
-            pj.blk0[2 * a] = blk; blk += (64 * Tp + 255) / 256;
-            pj.src[2 * a + 1] = ae + L.go.w[4]; pj.dst[2 * a + 1] = w.W5p[a]; pj.rows[2 * a + 1] = 16; pj.cols[2 * a + 1] = 16 + d->K; pj.pitch[2 * a + 1] = 32;
-            pj.blk0[2 * a + 1] = blk; blk += 2;
-        }
-        pj.blk0[4] = blk;
+        stw::PadJobs pj; const int blk = fill_pad_jobs(pj, d, L, ae_m, ae_p, w);
         ST_REQ(FP % 4 == 0 && (size_t)(T + d->K) * d->B * (FP / 4) < ((size_t)1 << 31), "wide autoencoder path: batch too large (B=%d)", d->B);
         const int n_copy = (int)(((size_t)(T + d->K) * d->B * (FP / 4) + 255) / 256);
         hipLaunchKernelGGL(stw::wide_in_kernel, dim3(n_copy + blk), dim3(256), 0, s, mag, phs, knobs, w.V[0], w.V[1], w.H[0][3], w.H[1][3],
@@ -869,30 +896,25 @@ static int ae_wide_fwd(const st_dims* d, const Layout& L, const float* mag, cons
         stg::PlainNT al0{w.W1p[0], out[0], Tp, Tp, id}, al1{w.W1p[1], out[0], Tp, Tp, id};
         stg::PlainTN bl0{w.V[0], in[0], R, R, id}, bl1{w.V[1], in[0], R, R, id};
         stw::ActStore ep0{w.H[0][0], ae_m + L.go.b[0], out[0], R, FP, F}, ep1{w.H[1][0], ae_p + L.go.b[0], out[0], R, FP, F};
-        ST_WGEMM_PAIR(al0, bl0, ep0, al1, bl1, ep1, out[0], R, Tp, 1, s);
+        wgemm_pair(wide_ht, al0, bl0, ep0, al1, bl1, ep1, out[0], R, Tp, 1, s);
     }
     {
         const size_t lds = (size_t)2 * sta::CL::FWD_TOTAL * sizeof(float);
-#define ST_AE_INNER_FWD_(NW_, HT_) do { ST_DYN_LDS((sta::ae_inner_fwd_kernel<NW_, HT_>)); \
-            hipLaunchKernelGGL((sta::ae_inner_fwd_kernel<NW_, HT_>), dim3(ae_inner_grid(d)), dim3(NW_ * 64), lds, s, \
-                               w.H[0][0], w.H[1][0], knobs, ae_m, ae_p, L.go, w.H[0][7], w.H[1][7], d->B, F, d->K, L.KP); } while (0)
-#define ST_AE_INNER_FWD(HT_) do { const int nw_ = ae_inner_nw(d); if (nw_ == 9) ST_AE_INNER_FWD_(9, HT_); else if (nw_ == 12) ST_AE_INNER_FWD_(12, HT_); else ST_AE_INNER_FWD_(AE_FWD_NW, HT_); } while (0)
-        switch (wide_ht) { case 1: ST_AE_INNER_FWD(1); break; case 2: ST_AE_INNER_FWD(2); break; default: ST_AE_INNER_FWD(0); }
-#undef ST_AE_INNER_FWD
-#undef ST_AE_INNER_FWD_
+        ST_TRY(with_ht(wide_ht, [&](auto HT) { return with_inner_nw(ae_inner_nw(d), [&](auto NW) {
+            return launch_lds("ae_inner_fwd_kernel", sta::ae_inner_fwd_kernel<NW(), HT()>, dim3(ae_inner_grid(d)), dim3(NW() * 64), lds, s,
+                              w.H[0][0], w.H[1][0], knobs, ae_m, ae_p, L.go, w.H[0][7], w.H[1][7], d->B, F, d->K, L.KP); }); }));
     }
     {
         stg::PlainNT al0{ae_m + L.go.w[8], OT, 64, 64, id}, al1{ae_p + L.go.w[8], OT, 64, 64, id};
         stg::PlainTN bl0{w.H[0][7], 64, R, R, id}, bl1{w.H[1][7], 64, R, R, id};
         stw::OutStore ep0{w.E9[0], mag_hat, w.V[0] + (size_t)(T - OT) * R, ae_m + L.go.b[8], OT, R, FP, F, 0};
         stw::OutStore ep1{w.E9[1], phs_hat, w.V[1] + (size_t)(T - OT) * R, ae_p + L.go.b[8], OT, R, FP, F, 1};
-        ST_WGEMM_PAIR(al0, bl0, ep0, al1, bl1, ep1, OT, R, 64, 1, s);
+        wgemm_pair(wide_ht, al0, bl0, ep0, al1, bl1, ep1, OT, R, 64, 1, s);
     }
     ST_LAUNCHED("ae_wide_fwd");
     if (AA) {
-        const float expfac = (float)(7.0 / d->F);
-        hipLaunchKernelGGL(stw::wide_polar_out_kernel, dim3(st_ae_fwd_partials(d)), dim3(256), 0, s, mag_hat, phs_hat, AA, reg_partial,
-                           d->B, OT, F, FP, L.KP, expfac, AA16, AA16 ? gemm_ht(d->prec) : 0);
+        hipLaunchKernelGGL(stw::wide_polar_out_kernel, dim3(ae_fwd_partials(d)), dim3(256), 0, s, mag_hat, phs_hat, AA, reg_partial,
+                           d->B, OT, F, FP, L.KP, expfac_of(d), AA16, AA16 ? gemm_ht(d->prec) : 0);
         ST_LAUNCHED("ae_wide_polar_out");
     }
     return ST_OK;
@@ -910,11 +932,10 @@ static void wide_wgrad_pair(const st_dims* d, WideWS& w, int l, const int* out, 
     stg::StoreC ep1 = ep0;
     if (!wide_ht) ep1.out = w.slabs + (size_t)w.nsplit * w.SL + w.so[l];      // two launches: each with its own z = 0 .. nsplit - 1
     if (wide_ht && R % 32) {      // odd batch: the reduction length is 16 mod 32 -> 16-deep k-tiles of the same kernel
-        if (wide_ht == 1) stg::launch_half_pair<2, 1, 1, 16>(al0, bl0, ep0, al1, bl1, ep1, out[l], in[l] + 1, R, w.nsplit, s);
-        else stg::launch_half_pair<2, 2, 1, 16>(al0, bl0, ep0, al1, bl1, ep1, out[l], in[l] + 1, R, w.nsplit, s);
+        with_ht16(wide_ht, [&](auto HT) { stg::launch_half_pair<2, HT(), 1, 16>(al0, bl0, ep0, al1, bl1, ep1, out[l], in[l] + 1, R, w.nsplit, s); });
         return;
     }
-    ST_WGEMM_PAIR(al0, bl0, ep0, al1, bl1, ep1, out[l], in[l] + 1, R, w.nsplit, s);
+    wgemm_pair(wide_ht, al0, bl0, ep0, al1, bl1, ep1, out[l], in[l] + 1, R, w.nsplit, s);
 }
 
 // Where the gradient w.r.t. the autoencoder inputs goes on the fused path: straight through the polar backward into d G (wide_dv_polar_kernel)
@@ -938,13 +959,13 @@ static int ae_wide_bwd(const st_dims* d, const Layout& L, const float* mag, cons
         rows.p[9 * a] = w.V[a] + (size_t)in[0] * R;
         for (int j = 0; j < 8; ++j) rows.p[9 * a + 1 + j] = w.H[a][j] + (size_t)in[j + 1] * R;
     }
-    const float expfac = (float)(7.0 / d->F);
+    const float expfac = expfac_of(d);
     const stg::RowMap ms = synth_live(d);
     {
         const size_t n = (size_t)d->B * OT * FP;
         ST_REQ(n < ((size_t)1 << 30), "wide autoencoder path: batch too large (B=%d)", d->B);
         int grid = (int)((n + 255) / 256); if (grid > 8192) grid = 8192;
-        hipLaunchKernelGGL(stw::wide_dout_kernel, dim3(grid + 18 * d->B), dim3(256), 0, s, dAA, st_synth_slabs(d), (size_t)d->B * OT * L.KP,
+        hipLaunchKernelGGL(stw::wide_dout_kernel, dim3(grid + 18 * d->B), dim3(256), 0, s, dAA, synth_slabs(d), (size_t)d->B * OT * L.KP,
                            mag_hat, phs_hat, w.E9[0], w.E9[1], w.V[0] + (size_t)(T - OT) * R, g_mag_hat, reg_coef, expfac,
                            w.DA[0][8], w.DA[1][8], w.TL[0], w.TL[1], d->B, OT, F, FP, L.KP, ms.t_lo, ms.t_lo + ms.Tv - 1, grid, rows);
         ST_LAUNCHED("ae_wide_dout");
@@ -959,26 +980,21 @@ static int ae_wide_bwd(const st_dims* d, const Layout& L, const float* mag, cons
         stg::PlainTN al0{ae_m + L.go.w[8], out[8], in[8], in[8], id}, al1{ae_p + L.go.w[8], out[8], in[8], in[8], id};
         stg::PlainTN bl0{w.DA[0][8], out[8], R, R, id}, bl1{w.DA[1][8], out[8], R, R, id};
         stg::StoreC ep0{w.DA[0][7], in[8], R, R, 0, id}, ep1{w.DA[1][7], in[8], R, R, 0, id};
-        ST_WGEMM_PAIR(al0, bl0, ep0, al1, bl1, ep1, in[8], R, out[8], 1, s);
+        wgemm_pair(wide_ht, al0, bl0, ep0, al1, bl1, ep1, in[8], R, out[8], 1, s);
     }
     {
         const size_t lds = (size_t)sta::ae_bwd_lds_floats(AE_BWD_NW) * sizeof(float);
         const int grid = ae_bwd_grid(d);
-#define ST_AE_INNER_BWD_K(HT_, KG_) do { ST_DYN_LDS((sta::ae_bwd_kernel<AE_BWD_NW, true, HT_, 0, false, KG_>)); \
-            hipLaunchKernelGGL((sta::ae_bwd_kernel<AE_BWD_NW, true, HT_, 0, false, KG_>), dim3(grid, 2), dim3(AE_BWD_NW * 64), lds, s, \
-                               (const float*)w.H[0][0], (const float*)w.H[1][0], knobs, ae_m, ae_p, L.go, L.PG, \
-                               (const float*)w.DA[0][7], (const float*)w.DA[1][7], (const float*)nullptr, (const float*)nullptr, 0.f, 0.f, \
-                               w.DA[0][0], w.DA[1][0], w.inner_ws, d->B, T, OT, F, d->K, L.KP, 0, 0, 1, (size_t)0, (const float*)nullptr, kg); } while (0)
-#define ST_AE_INNER_BWD(HT_) do { if (kg) ST_AE_INNER_BWD_K(HT_, true); else ST_AE_INNER_BWD_K(HT_, false); } while (0)
-        switch (wide_ht) { case 1: ST_AE_INNER_BWD(1); break; case 2: ST_AE_INNER_BWD(2); break; default: ST_AE_INNER_BWD(0); }
-#undef ST_AE_INNER_BWD
-#undef ST_AE_INNER_BWD_K
+        ST_TRY(with_ht(wide_ht, [&](auto HT) { return with_bool(kg != nullptr, [&](auto KG) {
+            return launch_lds("ae_bwd_kernel", sta::ae_bwd_kernel<AE_BWD_NW, true, HT(), 0, false, KG()>, dim3(grid, 2), dim3(AE_BWD_NW * 64), lds, s,
+                              w.H[0][0], w.H[1][0], knobs, ae_m, ae_p, L.go, L.PG, w.DA[0][7], w.DA[1][7], nullptr, nullptr, 0.f, 0.f,
+                              w.DA[0][0], w.DA[1][0], w.inner_ws, d->B, T, OT, F, d->K, L.KP, 0, 0, 1, (size_t)0, nullptr, kg, nullptr); }); }));
         inner_parts = grid;                          // summed by the second role of wide_grad_finish_kernel below (was a launch of its own)
     }
     for (int l = 1; l < 8; ++l) tab.out[l] = 0;                 // the finish kernel only scatters layers 1 and 9
     wide_wgrad_pair(d, w, 0, out, in, s, wide_ht);
     if (norm_e && 2 * ((w.so[9] + 63) / 64 + (L.PG + 63) / 64) > NORM_E_MAX) norm_e = nullptr;
-    hipLaunchKernelGGL(stw::wide_grad_finish_kernel, dim3((w.so[9] + 63) / 64 + (L.PG + 63) / 64 + (syn ? st_norm_partials(d) : 0), 2), dim3(256), 0, s, w.slabs, w.nsplit, w.SL, tab, g_m, g_p,
+    hipLaunchKernelGGL(stw::wide_grad_finish_kernel, dim3((w.so[9] + 63) / 64 + (L.PG + 63) / 64 + (syn ? norm_partials(d) : 0), 2), dim3(256), 0, s, w.slabs, w.nsplit, w.SL, tab, g_m, g_p,
                        (w.so[9] + 63) / 64, (const float*)w.inner_ws, inner_parts, L.PG, syn ? *syn : stw::SynReduce{}, norm_e);
     if (norm_e && n_norm_e) *n_norm_e = 2 * ((w.so[9] + 63) / 64 + (L.PG + 63) / 64);
     {   // layer-1 data gradient + polar backward of both nets in one kernel
@@ -995,16 +1011,13 @@ static int ae_wide_bwd(const st_dims* d, const Layout& L, const float* mag, cons
         int grid = ((groups + 7) / 8) * (TP16 / 16); if (grid > num_cus()) grid = num_cus();      // units of (8 adjacent groups, 16-frame tile), shared equally; one workgroup per CU
                                                                                                   // (two or three per CU measured slower: 146.6 / 155.5 us against 141.1 for the whole
                                                                                                   // wide backward -- every workgroup stages the layer-1 weights, ~10 us of dependent loads)
-#define ST_DVP(HT_) do { ST_DYN_LDS((stw::wide_dv_polar_kernel<HT_>)); hipLaunchKernelGGL((stw::wide_dv_polar_kernel<HT_>), dim3(grid), dim3(512), lds, s, q); } while (0)
-        switch (wide_ht) { case 1: ST_DVP(1); break; case 2: ST_DVP(2); break; default: ST_DVP(0); }
-#undef ST_DVP
+        ST_TRY(with_ht(wide_ht, [&](auto HT) { return launch_lds("wide_dv_polar_kernel", stw::wide_dv_polar_kernel<HT()>, dim3(grid), dim3(512), lds, s, q); }));
     }
     ST_LAUNCHED("ae_wide_bwd");
     return ST_OK;
 }
-#undef ST_WGEMM_PAIR
 
-static int ae_bwd_impl(const st_dims* d, const float* mag, const float* phs, const float* knobs,
+static int ae_bwd_body(const st_dims* d, const Layout& L, const float* mag, const float* phs, const float* knobs,
                        const float* ae_m, const float* ae_p, const float* mag_hat, const float* phs_hat,
                        const float* dAA, const float* g_mag_hat, float reg_coef, float* dmag, float* dphs, float* ws,
                        float* g_m, float* g_p, bool have_fwd, void* stream, bool* defer_reduce = nullptr,
@@ -1016,85 +1029,67 @@ static int ae_bwd_impl(const st_dims* d, const float* mag, const float* phs, con
     // tuning defaults reach exist in that form (ae_kg_route)
     // defer_reduce: in -> the caller will sum the workgroup partials itself (post_ae_kernel, together with the polar backward);
     // out -> false if this geometry's path already reduced them (wide geometries)
-    Layout L; ST_TRY(make_layout(d, &L));
     ST_REQ(mag && phs && (knobs || d->K == 0) && ae_m && ae_p && mag_hat && phs_hat && dAA && dmag && dphs && ws && g_m && g_p, "st_ae_bwd: null pointer");
     if (!knobs) knobs = ae_m;
     if (ae_is_wide(d)) {
         if (defer_reduce) *defer_reduce = false;
-        WideWS w; wide_carve(d, ws, &w);
+        WideWS w; wide_carve(d, L, ws, &w);
         return ae_wide_bwd(d, L, mag, phs, knobs, ae_m, ae_p, mag_hat, phs_hat, dAA, g_mag_hat, reg_coef, dmag, dphs, w, g_m, g_p, have_fwd, stream, sink, syn, norm_e, n_norm_e, kg);
     }
     if (kg && !(ae_kg_route(d) && have_fwd)) return st_fail(ST_ERR_UNSUPPORTED, "st_ae_bwd: no per-group d a5 output on this autoencoder backward route (%s)", ae_kg_why(d));
     const size_t lds = (size_t)sta::ae_bwd_lds_floats(AE_BWD_NW) * sizeof(float);
     static_assert((size_t)sta::ae_bwd_lds_floats(AE_BWD_NW) * sizeof(float) <= 160 * 1024, "ae_bwd LDS budget");
-    ST_REQ((size_t)st_synth_slabs(d) * d->B * d->OT * L.KP < ((size_t)1 << 30) && (size_t)d->B * d->T * L.KP < ((size_t)1 << 30),
+    ST_REQ((size_t)synth_slabs(d) * d->B * d->OT * L.KP < ((size_t)1 << 30) && (size_t)d->B * d->T * L.KP < ((size_t)1 << 30),
            "st_ae_bwd: batch too large for the kernel's 32-bit element offsets (B=%d)", d->B);
-    const float expfac = (float)(7.0 / d->F);
+    const float expfac = expfac_of(d);
     const stg::RowMap live = synth_live(d);
+    const int t_hi = live.t_lo + live.Tv - 1, nsl = synth_slabs(d);
+    const size_t slab = (size_t)d->B * d->OT * L.KP;
+    hipStream_t s = st_stream(stream);
     float* h4x = ws;                                      // workspace: [h4 | d a4 | workgroup partials] (st_ae_bwd_ws_floats)
     float* da4x = ws + ae_h4_floats(d);
     float* parts = ws + 2 * ae_h4_floats(d);
     int grid = ae_bwd_grid(d);
+    const int ht = ae_ht(d->prec);
     if (ae_use_split(d)) {
         // two kernels at two waves per SIMD (st_ae_split.h): decoder half (layers 5..9, from the code h4 the forward kernel kept),
         // then encoder half (layers 1..4, from d a4 and the tails the first one left)
-        if (!have_fwd) {                                   // per-op entry without a preceding forward in this workspace: code-only forward pass
-            st_dims dd = *d; dd.prec = d->prec;
-            ST_TRY(st_ae_fwd(&dd, mag, phs, knobs, ae_m, ae_p, nullptr, nullptr, nullptr, nullptr, h4x, stream));
-        }
+        if (!have_fwd)                                     // per-op entry without a preceding forward in this workspace: code-only forward pass
+            ST_TRY(ae_fwd_body(d, L, mag, phs, knobs, ae_m, ae_p, nullptr, nullptr, nullptr, nullptr, h4x, stream));
         grid = ae_split_grid(d);
         static_assert((size_t)sta::ae_split_lds_floats<1>(AE_SPLIT_NW) * sizeof(float) <= 160 * 1024 && (size_t)sta::ae_split_lds_floats<2>(AE_SPLIT_NW) * sizeof(float) <= 160 * 1024, "split ae_bwd LDS budget");
-#define ST_AE_PART_K(PART_, HT_, GM_, KG_) do { ST_DYN_LDS((sta::ae_bwd_part_kernel<AE_SPLIT_NW, PART_, HT_, GM_, KG_>)); \
-        hipLaunchKernelGGL((sta::ae_bwd_part_kernel<AE_SPLIT_NW, PART_, HT_, GM_, KG_>), dim3(grid, 2), dim3(AE_SPLIT_NW * 64), \
-                           (size_t)sta::ae_split_lds_floats<PART_>(AE_SPLIT_NW) * sizeof(float), st_stream(stream), \
-                           mag, phs, knobs, ae_m, ae_p, L.go, L.PG, mag_hat, phs_hat, dAA, g_mag_hat, reg_coef, expfac, dmag, dphs, parts, \
-                           (const float*)h4x, da4x, d->B, d->T, d->OT, d->F, d->K, L.KP, live.t_lo, live.t_lo + live.Tv - 1, st_synth_slabs(d), \
-                           (size_t)d->B * d->OT * L.KP, kg); } while (0)
-#define ST_AE_PART(PART_, HT_, GM_) ST_AE_PART_K(PART_, HT_, GM_, false)
-#define ST_AE_PARTS(HT_) do { if (g_mag_hat) ST_AE_PART(1, HT_, true); else ST_AE_PART(1, HT_, false); ST_LAUNCHED("ae_bwd_dec"); ST_AE_PART(2, HT_, false); ST_LAUNCHED("ae_bwd_enc"); } while (0)
-#define ST_AE_PARTS_KG(HT_) do { if (g_mag_hat) ST_AE_PART_K(1, HT_, true, true); else ST_AE_PART_K(1, HT_, false, true); ST_LAUNCHED("ae_bwd_dec"); ST_AE_PART(2, HT_, false); ST_LAUNCHED("ae_bwd_enc"); } while (0)
-        if (kg) { if (ae_ht(d->prec) == 1) ST_AE_PARTS_KG(1); else ST_AE_PARTS_KG(2); }      // 16-bit layers only (ae_kg_route)
-        else
-        switch (ae_ht(d->prec)) { case 1: ST_AE_PARTS(1); break; case 2: ST_AE_PARTS(2); break; default: ST_AE_PARTS(0); }
-#undef ST_AE_PARTS_KG
-#undef ST_AE_PARTS
-#undef ST_AE_PART
-#undef ST_AE_PART_K
-        if (defer_reduce && *defer_reduce) return ST_OK;
-        hipLaunchKernelGGL(stm::ae_grad_reduce_kernel, dim3((L.PG + 63) / 64, 2), dim3(256), 0, st_stream(stream), parts, grid, L.PG, g_m, g_p);
-        ST_LAUNCHED("ae_grad_reduce"); return ST_OK;
-    }
-#define ST_AE_BWD_LAUNCH(HT_, VAR_) do { ST_DYN_LDS((sta::ae_bwd_kernel<AE_BWD_NW, false, HT_, VAR_>)); \
-    hipLaunchKernelGGL((sta::ae_bwd_kernel<AE_BWD_NW, false, HT_, VAR_>), dim3(grid, 2), dim3(AE_BWD_NW * 64), lds, st_stream(stream), \
-                       mag, phs, knobs, ae_m, ae_p, L.go, L.PG, mag_hat, phs_hat, dAA, g_mag_hat, reg_coef, expfac, \
-                       dmag, dphs, parts, d->B, d->T, d->OT, d->F, d->K, L.KP, live.t_lo, live.t_lo + live.Tv - 1, st_synth_slabs(d), (size_t)d->B * d->OT * L.KP); } while (0)
-    // kernel variant: 1 = an upstream d/d mag_hat arrives (autograd entry), 2 = T - OT == 16 (tails already in registers), 0 = neither
-    const int var = g_mag_hat ? 1 : (d->T - d->OT == 16 ? 2 : 0);
-    if (have_fwd && ae_use_saved(d)) {               // round 6: the forward of this workspace kept the activations -- no recompute
-        const float* sv = ae_sv_ptr(d, L, ws);
-        const float* img = (have_img && ae_img_level(d) == 2) ? ae_img_ptr(ws) : nullptr;
-#define ST_AE_BWD_SV_K(VAR_, KG_, IMG_) do { ST_DYN_LDS((sta::ae_bwd_kernel<AE_BWD_NW, false, 0, VAR_, true, KG_, IMG_>)); \
-        hipLaunchKernelGGL((sta::ae_bwd_kernel<AE_BWD_NW, false, 0, VAR_, true, KG_, IMG_>), dim3(grid, 2), dim3(AE_BWD_NW * 64), lds, st_stream(stream), \
-                       mag, phs, knobs, ae_m, ae_p, L.go, L.PG, mag_hat, phs_hat, dAA, g_mag_hat, reg_coef, expfac, \
-                       dmag, dphs, parts, d->B, d->T, d->OT, d->F, d->K, L.KP, live.t_lo, live.t_lo + live.Tv - 1, st_synth_slabs(d), (size_t)d->B * d->OT * L.KP, sv, kg, img); } while (0)
-#define ST_AE_BWD_SV(VAR_) do { if (img) { if (kg) ST_AE_BWD_SV_K(VAR_, true, true); else ST_AE_BWD_SV_K(VAR_, false, true); } \
-                                else { if (kg) ST_AE_BWD_SV_K(VAR_, true, false); else ST_AE_BWD_SV_K(VAR_, false, false); } } while (0)
-        if (var == 1) ST_AE_BWD_SV(1); else if (var == 2) ST_AE_BWD_SV(2); else ST_AE_BWD_SV(0);
-#undef ST_AE_BWD_SV
-#undef ST_AE_BWD_SV_K
+        auto part = [&](auto PART, auto HT, auto GM, auto KG) {
+            return launch_lds("ae_bwd_part_kernel", sta::ae_bwd_part_kernel<AE_SPLIT_NW, PART(), HT(), GM(), KG()>, dim3(grid, 2), dim3(AE_SPLIT_NW * 64),
+                              (size_t)sta::ae_split_lds_floats<PART()>(AE_SPLIT_NW) * sizeof(float), s,
+                              mag, phs, knobs, ae_m, ae_p, L.go, L.PG, mag_hat, phs_hat, dAA, g_mag_hat, reg_coef, expfac, dmag, dphs, parts,
+                              h4x, da4x, d->B, d->T, d->OT, d->F, d->K, L.KP, live.t_lo, t_hi, nsl, slab, kg); };
+        auto halves = [&](auto HT, auto KG) -> int {      // KG: the decoder half (it holds d a5) also writes the per-group sums
+            ST_TRY(with_bool(g_mag_hat != nullptr, [&](auto GM) { return part(ic<1>{}, HT, GM, KG); }));
+            ST_LAUNCHED("ae_bwd_dec");
+            ST_TRY(part(ic<2>{}, HT, std::false_type{}, std::false_type{}));
+            ST_LAUNCHED("ae_bwd_enc");
+            return ST_OK; };
+        if (kg) ST_TRY(with_ht16(ht, [&](auto HT) { return halves(HT, std::true_type{}); }));      // 16-bit layers only (ae_kg_route)
+        else ST_TRY(with_ht(ht, [&](auto HT) { return halves(HT, std::false_type{}); }));
+    } else {
+        // kernel variant: 1 = an upstream d/d mag_hat arrives (autograd entry), 2 = T - OT == 16 (tails already in registers), 0 = neither
+        const int var = g_mag_hat ? 1 : (d->T - d->OT == 16 ? 2 : 0);
+        if (have_fwd && ae_use_saved(d)) {               // round 6: the forward of this workspace kept the activations -- no recompute (fp32 layers only)
+            const float* sv = ae_sv_ptr(d, L, ws);
+            const float* img = (have_img && ae_img_level(d) == 2) ? ae_img_ptr(ws) : nullptr;
+            ST_TRY(with_var(var, [&](auto VAR) { return with_bool(kg != nullptr, [&](auto KG) { return with_bool(img != nullptr, [&](auto IMG) {
+                return launch_lds("ae_bwd_kernel", sta::ae_bwd_kernel<AE_BWD_NW, false, 0, VAR(), true, KG(), IMG()>, dim3(grid, 2), dim3(AE_BWD_NW * 64), lds, s,
+                                  mag, phs, knobs, ae_m, ae_p, L.go, L.PG, mag_hat, phs_hat, dAA, g_mag_hat, reg_coef, expfac,
+                                  dmag, dphs, parts, d->B, d->T, d->OT, d->F, d->K, L.KP, live.t_lo, t_hi, nsl, slab, sv, kg, img); }); }); }));
+        } else
+            ST_TRY(with_ht(ht, [&](auto HT) { return with_var(var, [&](auto VAR) {
+                return launch_lds("ae_bwd_kernel", sta::ae_bwd_kernel<AE_BWD_NW, false, HT(), VAR()>, dim3(grid, 2), dim3(AE_BWD_NW * 64), lds, s,
+                                  mag, phs, knobs, ae_m, ae_p, L.go, L.PG, mag_hat, phs_hat, dAA, g_mag_hat, reg_coef, expfac,
+                                  dmag, dphs, parts, d->B, d->T, d->OT, d->F, d->K, L.KP, live.t_lo, t_hi, nsl, slab, nullptr, nullptr, nullptr); }); }));
         ST_LAUNCHED("ae_bwd");
-        if (defer_reduce && *defer_reduce) return ST_OK;
-        hipLaunchKernelGGL(stm::ae_grad_reduce_kernel, dim3((L.PG + 63) / 64, 2), dim3(256), 0, st_stream(stream), parts, grid, L.PG, g_m, g_p);
-        ST_LAUNCHED("ae_grad_reduce"); return ST_OK;
     }
-#define ST_AE_BWD_VARS(HT_) do { if (var == 1) ST_AE_BWD_LAUNCH(HT_, 1); else if (var == 2) ST_AE_BWD_LAUNCH(HT_, 2); else ST_AE_BWD_LAUNCH(HT_, 0); } while (0)
-    switch (ae_ht(d->prec)) { case 1: ST_AE_BWD_VARS(1); break; case 2: ST_AE_BWD_VARS(2); break; default: ST_AE_BWD_VARS(0); }
-#undef ST_AE_BWD_VARS
-#undef ST_AE_BWD_LAUNCH
-    ST_LAUNCHED("ae_bwd");
     if (defer_reduce && *defer_reduce) return ST_OK;
-    hipLaunchKernelGGL(stm::ae_grad_reduce_kernel, dim3((L.PG + 63) / 64, 2), dim3(256), 0, st_stream(stream),
-                       parts, grid, L.PG, g_m, g_p);
+    hipLaunchKernelGGL(stm::ae_grad_reduce_kernel, dim3((L.PG + 63) / 64, 2), dim3(256), 0, s, parts, grid, L.PG, g_m, g_p);
     ST_LAUNCHED("ae_grad_reduce"); return ST_OK;
 }
 extern "C" int st_ae_bwd(const st_dims* d, const float* mag, const float* phs, const float* knobs,
@@ -1102,7 +1097,8 @@ extern "C" int st_ae_bwd(const st_dims* d, const float* mag, const float* phs, c
                          const float* dAA, const float* g_mag_hat, float reg_coef, float* dmag, float* dphs, float* ws,
                          float* g_m, float* g_p, void* stream)
 {
-    return ae_bwd_impl(d, mag, phs, knobs, ae_m, ae_p, mag_hat, phs_hat, dAA, g_mag_hat, reg_coef, dmag, dphs, ws, g_m, g_p, false, stream);
+    Layout L; ST_TRY(make_layout(d, &L));
+    return ae_bwd_body(d, L, mag, phs, knobs, ae_m, ae_p, mag_hat, phs_hat, dAA, g_mag_hat, reg_coef, dmag, dphs, ws, g_m, g_p, false, stream);
 }
 
 extern "C" int st_polar_bwd(const st_dims* d, const float* re, const float* im, const float* dmag, const float* dphs,
@@ -1165,23 +1161,26 @@ extern "C" int st_analysis_wgrad(const st_dims* d, const float* dG, const float*
     return analysis_wgrad_impl(d, dG, x, false, in_scale, ws, gWr, gWi, norm_partial, stream);
 }
 
-extern "C" int st_finalize_scalars(const st_dims* d, const float* loss_partial, const float* reg_partial,
-                                   const float* norm_a, const float* norm_s, float inv_world, float* scalars, void* stream)
-{
-    ST_TRY(check_dims(d)); ST_REQ(scalars, "st_finalize_scalars: null pointer");
-    const float inv_y = 1.0f / ((float)d->B * (float)d->y);
-    const float reg_scale = (float)(2e-5 / 10.0) / ((float)d->B * (float)d->OT * (float)d->F);   // loss_functions.py:36
-    const stm::FinArgs f{loss_partial, st_ola_loss_partials(d), reg_partial, st_ae_fwd_partials(d),
-                         norm_a, st_norm_partials(d), norm_s, st_norm_partials(d), inv_y, reg_scale, inv_world, nullptr, 0};
-    hipLaunchKernelGGL(stm::finalize_kernel, dim3(1), dim3(256), 0, st_stream(stream), f, scalars);
-    ST_LAUNCHED("finalize_scalars"); return ST_OK;
-}
 static stm::FinArgs fin_args(const st_dims* d, const float* loss_partial, const float* reg_partial, const float* norm_a, const float* norm_s, float norm_scale)
 {
     const float inv_y = 1.0f / ((float)d->B * (float)d->y);
-    const float reg_scale = (float)(2e-5 / 10.0) / ((float)d->B * (float)d->OT * (float)d->F);   // loss_functions.py:36
-    return stm::FinArgs{loss_partial, st_ola_loss_partials(d), reg_partial, st_ae_fwd_partials(d),
-                        norm_a, st_norm_partials(d), norm_s, norm_s ? st_norm_partials(d) : 0, inv_y, reg_scale, norm_scale, nullptr, 0};
+    return stm::FinArgs{loss_partial, ola_loss_partials(d), reg_partial, ae_fwd_partials(d),
+                        norm_a, norm_partials(d), norm_s, norm_s ? norm_partials(d) : 0, inv_y, reg_scale_of(d), norm_scale, nullptr, 0};
+}
+static int finalize_scalars(const st_dims* d, const float* loss_partial, const float* reg_partial,
+                            const float* norm_a, const float* norm_s, float inv_world, float* scalars, void* stream)
+{
+    ST_REQ(scalars, "st_finalize_scalars: null pointer");
+    stm::FinArgs f = fin_args(d, loss_partial, reg_partial, norm_a, norm_s, inv_world);
+    f.n_ns = norm_partials(d);      // counted whether or not norm_s is given, as this entry always has
+    hipLaunchKernelGGL(stm::finalize_kernel, dim3(1), dim3(256), 0, st_stream(stream), f, scalars);
+    ST_LAUNCHED("finalize_scalars"); return ST_OK;
+}
+extern "C" int st_finalize_scalars(const st_dims* d, const float* loss_partial, const float* reg_partial,
+                                   const float* norm_a, const float* norm_s, float inv_world, float* scalars, void* stream)
+{
+    ST_TRY(check_dims(d));
+    return finalize_scalars(d, loss_partial, reg_partial, norm_a, norm_s, inv_world, scalars, stream);
 }
 
 // fin != nullptr: the clip coefficient (and, if fin->loss_partial, the loss scalars) are derived inside the kernel from
@@ -1228,26 +1227,26 @@ struct WS {
     // bases as rows (bin, re | im) [2F][N], the folded synthesis bases [KP][N] and [N][KP], the spectra, the padded d syn, d G
     unsigned short *xp16, *W16, *Sfold16, *SfoldT16, *AA16, *dsyn16, *dG16;
     int n_norm_e;      // > 0: the autoencoder backward of this call left that many |g| partials of its gradients in norm_e (clip_all needs no l1_partial launch)
-    bool g16;          // this call runs the 16-bit operand pipeline (set by the entry point after carve(): use_g16(); the autograd entries and the
+    bool g16;          // this call runs the 16-bit operand pipeline (call_begin's g16 argument and use_g16(); the autograd entries and the
                        // four-stage schedule keep fp32 operands + gemm_half_kernel)
     size_t bytes;
 };
-static void carve(const st_dims* d, void* base, WS* w)
+static void carve(const st_dims* d, const Layout& L, void* base, WS* w)
 {
     const size_t RT = (size_t)d->B * d->T, RO = (size_t)d->B * d->OT, F = d->F, KP = st_kp_of(d->F), N = d->N;
     size_t off = 0;
     auto take = [&](size_t n) { float* p = base ? reinterpret_cast<float*>(base) + off : nullptr; off += (n + 63) / 64 * 64; return p; };
     w->re = take(RT * F); w->im = take(RT * F); w->mag = take(RT * F); w->phs = take(RT * F);
     w->mag_hat = take(RO * F); w->phs_hat = take(RO * F);
-    const size_t nsl = st_synth_slabs(d), nfs = st_synth_frame_slabs(d);
+    const size_t nsl = synth_slabs(d), nfs = frame_slabs(d);
     w->AA = take(RO * KP); w->dAA = take(nsl * RO * KP);
     w->Sfold = take(KP * N); w->SfoldT = take(KP * N); w->frs = take(nfs * RO * N);
     w->y_hat = take((size_t)d->B * d->y); w->dsyn = take((size_t)d->B * (d->y + 2 * d->N));   // dsyn padded [B][N + y + N]
     w->xp = take((size_t)d->B * (d->L + 2 * d->N));                                               // x/2 padded  [B][N + L + N]
     w->dmag = take(RT * F); w->dphs = take(RT * F); w->dG = take(RT * KP);
-    w->wg = take(st_wgrad_ws_floats(d)); w->aews = take(st_ae_bwd_ws_floats(d));
-    w->loss_p = take(st_ola_loss_partials(d)); w->reg_p = take(st_ae_fwd_partials(d));
-    w->norm_a = take(st_norm_partials(d)); w->norm_s = take(st_norm_partials(d)); w->norm_e = take(NORM_E_MAX); w->n_norm_e = 0;
+    w->wg = take(wgrad_ws_floats(d)); w->aews = take(ae_bwd_ws_floats(d, L));
+    w->loss_p = take(ola_loss_partials(d)); w->reg_p = take(ae_fwd_partials(d));
+    w->norm_a = take(norm_partials(d)); w->norm_s = take(norm_partials(d)); w->norm_e = take(NORM_E_MAX); w->n_norm_e = 0;
     auto take16 = [&](size_t n) { return reinterpret_cast<unsigned short*>(take((n + 1) / 2)); };      // always sized for three planes: 19 MB
     w->pl_W = take16((size_t)3 * 2 * F * N); w->pl_Sfold = take16((size_t)3 * KP * N); w->pl_SfoldT = take16((size_t)3 * KP * N);
     // (+ 256: the 128-wide tiles of the TN kernel read up to 96 elements past the last row of an M/N-contiguous operand; masked outputs)
@@ -1262,8 +1261,8 @@ static void carve(const st_dims* d, void* base, WS* w)
 // For diagnostics (st_model.forward(return_acts=True), nn_proc.py:311-338): the caller views its own buffer, nothing is copied.
 extern "C" int st_workspace_offsets(const st_dims* d, int64_t* offs8)
 {
-    ST_TRY(check_dims(d)); ST_REQ(offs8, "st_workspace_offsets: null pointer");
-    WS w; carve(d, reinterpret_cast<void*>(sizeof(float)), &w);       // a non-null dummy base: pointer differences are the offsets
+    Layout L; ST_TRY(make_layout(d, &L)); ST_REQ(offs8, "st_workspace_offsets: null pointer");
+    WS w; carve(d, L, reinterpret_cast<void*>(sizeof(float)), &w);       // a non-null dummy base: pointer differences are the offsets
     float* base = reinterpret_cast<float*>(sizeof(float));
     float* p[8] = {w.re, w.im, w.mag, w.phs, w.mag_hat, w.phs_hat, w.AA, w.y_hat};
     for (int i = 0; i < 8; ++i) offs8[i] = (int64_t)(p[i] - base);
@@ -1293,20 +1292,20 @@ extern "C" int st_ae_acts(const st_dims* d, const float* v, const float* knobs, 
 }
 extern "C" size_t st_workspace_bytes(const st_dims* d)
 {
-    if (check_dims(d) != ST_OK) return 0;
-    WS w; carve(d, nullptr, &w); return w.bytes;
+    Layout L; if (make_layout(d, &L) != ST_OK) return 0;
+    WS w; carve(d, L, nullptr, &w); return w.bytes;
 }
 // ONE workspace for every batch 1 .. d->B at every arithmetic level and clip scope: the exact size above is monotonic in none of them (header).
 extern "C" size_t st_workspace_bytes_max(const st_dims* d)
 {
-    if (check_dims(d) != ST_OK) return 0;
+    Layout L; if (make_layout(d, &L) != ST_OK) return 0;      // the layout depends on neither batch, precision nor clip scope
     size_t best = 0;
     st_dims q = *d;
     for (int b = 1; b <= d->B; ++b)
         for (int prec = ST_PREC_F32; prec <= ST_PREC_F32X3; ++prec)
             for (int ca = 0; ca < 2; ++ca) {
                 q.B = b; q.prec = prec; q.clip_all = ca;
-                WS w; carve(&q, nullptr, &w);
+                WS w; carve(&q, L, nullptr, &w);
                 if (w.bytes > best) best = w.bytes;
             }
     return best;
@@ -1318,6 +1317,7 @@ extern "C" size_t st_workspace_bytes_max(const st_dims* d)
 // their GEMM stages them.  The weight-gradient GEMMs (reduction along the rows of both operands) keep the fp32 MFMA kernel.
 static bool use_planes(const st_dims* d) { return (gemm_ht(d->prec) == 3 || (gemm_ht(d->prec) == 1 && g_pl_bf16)) && d->N % 16 == 0 && st_kp_of(d->F) % 16 == 0; }
 static int planes_of(const st_dims* d) { return gemm_ht(d->prec) == 3 ? 3 : 1; }
+template <class F> static inline auto with_planes(int pl, F&& f) { return pl == 1 ? f(ic<1>{}) : f(ic<3>{}); }
 static int planes_prepare(const st_dims* d, const float* Wr, const float* Wi, WS& w, void* stream)
 {
     const int KP = st_kp_of(d->F);
@@ -1329,8 +1329,7 @@ static int planes_prepare(const st_dims* d, const float* Wr, const float* Wi, WS
     unsigned blk = 0;
     for (int j = 0; j < 3; ++j) { a.blk0[j] = blk; blk += (unsigned)(((size_t)a.job[j].rows * (a.job[j].K / 4) + 255) / 256); }
     a.blk0[3] = blk; a.blk0[4] = blk;
-    if (planes_of(d) == 3) hipLaunchKernelGGL(stg::wplanes_kernel<3>, dim3(blk), dim3(256), 0, st_stream(stream), a);
-    else hipLaunchKernelGGL(stg::wplanes_kernel<1>, dim3(blk), dim3(256), 0, st_stream(stream), a);
+    with_planes(planes_of(d), [&](auto PL) { hipLaunchKernelGGL(stg::wplanes_kernel<PL()>, dim3(blk), dim3(256), 0, st_stream(stream), a); });
     ST_LAUNCHED("planes");
     return ST_OK;
 }
@@ -1356,12 +1355,9 @@ static int synthesis_frames_planes(const st_dims* d, WS& w, void* stream)
     stg::PlainNT al{w.AA, R, KP, KP, ms};
     stg::ChunkP bt{w.pl_SfoldT, d->N};
     stg::StoreC ep{w.frs, R, d->N, d->N, (size_t)d->B * d->OT * d->N, ms};
-    if (planes_of(d) == 1) {
-        if (R >= 4096) ST_TRY((stg::launch_planes<4, 1>(al, bt, ep, R, d->N, KP, 1, st_stream(stream))));
-        else ST_TRY((stg::launch_planes<2, 1>(al, bt, ep, R, d->N, KP, frames_split(R), st_stream(stream))));
-    }
-    else if (R >= 4096) ST_TRY((stg::launch_planes<4, 3>(al, bt, ep, R, d->N, KP, 1, st_stream(stream))));
-    else ST_TRY((stg::launch_planes<2, 3>(al, bt, ep, R, d->N, KP, frames_split(R), st_stream(stream))));
+    ST_TRY(with_planes(planes_of(d), [&](auto PL) {
+        return R >= 4096 ? stg::launch_planes<4, PL()>(al, bt, ep, R, d->N, KP, 1, st_stream(stream))
+                         : stg::launch_planes<2, PL()>(al, bt, ep, R, d->N, KP, frames_split(R), st_stream(stream)); }));
     ST_LAUNCHED("synthesis_frames"); return ST_OK;
 }
 static int synthesis_dgrad_planes(const st_dims* d, WS& w, void* stream)
@@ -1372,13 +1368,10 @@ static int synthesis_dgrad_planes(const st_dims* d, WS& w, void* stream)
     stg::FramedNT<true> al{w.dsyn, d->y, d->H, d->N, R, d->N, 1.0f, ms};
     stg::ChunkP bl{w.pl_Sfold, KP};
     stg::StoreC ep{w.dAA, R, KP, KP, (size_t)d->B * d->OT * KP, ms};
-    const int ns = R >= 4096 ? 1 : synth_split(R);
-    if (planes_of(d) == 1) {
-        if (R >= 4096) ST_TRY((stg::launch_planes<4, 1>(al, bl, ep, R, KP, d->N, ns, st_stream(stream))));
-        else ST_TRY((stg::launch_planes<2, 1>(al, bl, ep, R, KP, d->N, ns, st_stream(stream))));
-    }
-    else if (R >= 4096) ST_TRY((stg::launch_planes<4, 3>(al, bl, ep, R, KP, d->N, ns, st_stream(stream))));
-    else ST_TRY((stg::launch_planes<2, 3>(al, bl, ep, R, KP, d->N, ns, st_stream(stream))));
+    const int ns = dgrad_slabs(R);
+    ST_TRY(with_planes(planes_of(d), [&](auto PL) {
+        return R >= 4096 ? stg::launch_planes<4, PL()>(al, bl, ep, R, KP, d->N, ns, st_stream(stream))
+                         : stg::launch_planes<2, PL()>(al, bl, ep, R, KP, d->N, ns, st_stream(stream)); }));
     ST_LAUNCHED("synthesis_dgrad"); return ST_OK;
 }
 
@@ -1388,7 +1381,6 @@ static bool use_g16(const st_dims* d)
     const int ht = gemm_ht(d->prec);
     return g_g16 && (ht == 1 || ht == 2) && !g_pl_bf16 && d->N % 128 == 0 && num_cus() > 0;
 }
-#define ST_G16(CALL_) do { if (gemm_ht(d->prec) == 2) ST_TRY((stg::CALL_<2>)); else ST_TRY((stg::CALL_<1>)); } while (0)
 static int analysis_fwd16(const st_dims* d, WS& w, float* re, float* im, float* mag, float* phs, void* stream, const PolarWide* pw = nullptr)
 {
     const stg::RowMap map = stg::live_frames(d->T, d->H, d->N, d->N, d->L);
@@ -1397,12 +1389,9 @@ static int analysis_fwd16(const st_dims* d, WS& w, float* re, float* im, float* 
     const stg::Rows16 rb = stg::rows16_plain(w.W16, (unsigned)d->N, 2 * d->F);
     stg::PolarStore ep{re, im, mag, phs, R, d->F, map};
     polar_wide_set(ep, pw);
-    if ((g_g16_dma & 1) && d->N % 64 == 0) {
-        if (gemm_ht(d->prec) == 2) ST_TRY((stg::launch16_nt256<2>(ra, rb, ep, R, 2 * d->F, d->N, 1, st_stream(stream))));
-        else ST_TRY((stg::launch16_nt256<1>(ra, rb, ep, R, 2 * d->F, d->N, 1, st_stream(stream))));
-    }
-    else if (gemm_ht(d->prec) == 2) ST_TRY((stg::launch16_nt<2>(ra, rb, ep, R, 2 * d->F, d->N, 1, st_stream(stream))));
-    else ST_TRY((stg::launch16_nt<1>(ra, rb, ep, R, 2 * d->F, d->N, 1, st_stream(stream))));
+    ST_TRY(with_ht16(gemm_ht(d->prec), [&](auto HT) {
+        return ((g_g16_dma & 1) && d->N % 64 == 0) ? stg::launch16_nt256<HT()>(ra, rb, ep, R, 2 * d->F, d->N, 1, st_stream(stream))
+                                                   : stg::launch16_nt<HT()>(ra, rb, ep, R, 2 * d->F, d->N, 1, st_stream(stream)); }));
     ST_LAUNCHED("analysis_fwd"); return ST_OK;
 }
 static int synthesis_frames16(const st_dims* d, WS& w, void* stream)
@@ -1416,8 +1405,7 @@ static int synthesis_frames16(const st_dims* d, WS& w, void* stream)
     stg::StoreC ep{w.frs, R, d->N, d->N, (size_t)d->B * d->OT * d->N, crop ? stg::frame_major(ms, d->B) : ms};
     const stg::Crop16 cr{crop ? 1 : 0, d->B, d->H, d->N, d->N, d->y, ms.t_lo, R, 1};      // tile columns without a tap inside the crop (cls_fe_dft.py:113) are not computed: ola_loss_kernel never reads them
     const int ns = frames_split(R);
-    if (gemm_ht(d->prec) == 2) ST_TRY((stg::launch16_nt<2>(ra, rb, ep, R, d->N, KP, ns, st_stream(stream), &cr)));
-    else ST_TRY((stg::launch16_nt<1>(ra, rb, ep, R, d->N, KP, ns, st_stream(stream), &cr)));
+    ST_TRY(with_ht16(gemm_ht(d->prec), [&](auto HT) { return stg::launch16_nt<HT()>(ra, rb, ep, R, d->N, KP, ns, st_stream(stream), &cr); }));
     ST_LAUNCHED("synthesis_frames"); return ST_OK;
 }
 static int synthesis_dgrad16(const st_dims* d, WS& w, void* stream)
@@ -1430,13 +1418,10 @@ static int synthesis_dgrad16(const st_dims* d, WS& w, void* stream)
     const stg::Rows16 rb = stg::rows16_plain(w.Sfold16, (unsigned)d->N, KP);
     stg::StoreC ep{w.dAA, R, KP, KP, (size_t)d->B * d->OT * KP, crop ? stg::frame_major(ms, d->B) : ms};
     const stg::Crop16 cr{crop ? 2 : 0, d->B, d->H, d->N, d->N, d->y, ms.t_lo, R, 1};      // per tile row only the taps that lie inside d syn: the rest of the padded copy is zeros
-    const int ns = R >= 4096 ? 1 : synth_split(R);
-    if ((g_g16_dma & 2) && d->N % 64 == 0 && d->N / 64 >= ns) {
-        if (gemm_ht(d->prec) == 2) ST_TRY((stg::launch16_nt256<2>(ra, rb, ep, R, KP, d->N, ns, st_stream(stream))));
-        else ST_TRY((stg::launch16_nt256<1>(ra, rb, ep, R, KP, d->N, ns, st_stream(stream))));
-    }
-    else if (gemm_ht(d->prec) == 2) ST_TRY((stg::launch16_nt<2>(ra, rb, ep, R, KP, d->N, ns, st_stream(stream), &cr)));
-    else ST_TRY((stg::launch16_nt<1>(ra, rb, ep, R, KP, d->N, ns, st_stream(stream), &cr)));
+    const int ns = dgrad_slabs(R);
+    ST_TRY(with_ht16(gemm_ht(d->prec), [&](auto HT) {
+        return ((g_g16_dma & 2) && d->N % 64 == 0 && d->N / 64 >= ns) ? stg::launch16_nt256<HT()>(ra, rb, ep, R, KP, d->N, ns, st_stream(stream))
+                                                                      : stg::launch16_nt<HT()>(ra, rb, ep, R, KP, d->N, ns, st_stream(stream), &cr); }));
     ST_LAUNCHED("synthesis_dgrad"); return ST_OK;
 }
 // k-slices of a 16-bit weight-gradient GEMM: about two workgroups per CU (their time is staging, not matrix work), never slices under
@@ -1446,7 +1431,7 @@ static int g16_wsplit(const st_dims* d, int R)
     const int KP = st_kp_of(d->F), tiles = ((KP + 127) / 128) * (d->N / 128);
     int s = (2 * num_cus()) / (tiles > 0 ? tiles : 1);
     const int cap = R / 128; if (s > cap) s = cap;
-    const int room = (int)(st_wgrad_ws_floats(d) / ((size_t)KP * d->N)); if (s > room) s = room;
+    const int room = (int)(wgrad_ws_floats(d) / ((size_t)KP * d->N)); if (s > room) s = room;
     return s < 1 ? 1 : s;
 }
 // A: [rows (b, t)][KP] 16-bit (d G or the spectra), B: frames of a padded 16-bit signal whose first N elements are zero (the block of zeros)
@@ -1475,21 +1460,34 @@ static int wgrad16(const st_dims* d, const unsigned short* A, unsigned SA1, cons
         for (int i = 0; i < 64; ++i) { j.fa[i] = ft.fa[i]; j.fb[i] = ft.fb[i]; }
     }
     stg::StoreC ep{slabs + (size_t)m0 * d->N, M, d->N, d->N, (size_t)KP * d->N, stg::all_frames(1)};
-    const int ht = gemm_ht(d->prec);
-    if (ht == 2) ST_TRY((stg::launch16_tn<2, 64>(j, ep, M, d->N, ns, st_stream(stream)))); else ST_TRY((stg::launch16_tn<1, 64>(j, ep, M, d->N, ns, st_stream(stream))));
-    return ST_OK;
+    return with_ht16(gemm_ht(d->prec), [&](auto HT) { return stg::launch16_tn<HT(), 64>(j, ep, M, d->N, ns, st_stream(stream)); });
 }
 
 // ------------------------------------------------------------------------------ fused entry points
-static int forward_impl(const st_dims* d, const Layout& L, const float* params, const float* x, const float* knobs,
-                        const float* y_true, float* y_hat, float* mag, float* mag_hat, WS& w, bool save, void* stream, float* eval_p = nullptr)
+// What a fused entry derives from its arguments before its first launch, handed down in one piece.  call_begin validates the dims (and nothing else: every
+// entry keeps its own pointer checks, after it), lays out the parameters, carves the workspace and lets knobs fall back to any resident float where K == 0.
+// g16 is each entry's own choice: the training and validation entries ask for the 16-bit operand pipeline (taken where use_g16() admits the precision),
+// the autograd entries and the four-stage schedule do not and keep fp32 operands + gemm_half_kernel.
+struct Call { const st_dims* d; Layout L; WS w; const float* knobs; void* stream; };
+static const bool G16_PIPELINE = true, FP32_OPERANDS = false;
+static int call_begin(Call* c, const st_dims* d, const float* params, const float* knobs, void* ws, void* stream, bool g16)
 {
+    ST_TRY(make_layout(d, &c->L));
+    c->d = d; c->knobs = knobs ? knobs : params; c->stream = stream;
+    carve(d, c->L, ws, &c->w);
+    c->w.g16 = g16 && use_g16(d);
+    return ST_OK;
+}
+static int forward_impl(Call& c, const float* params, const float* x, const float* y_true, float* y_hat, float* mag, float* mag_hat, bool save, float* eval_p = nullptr)
+{
+    const st_dims* d = c.d; const Layout& L = c.L; WS& w = c.w; void* stream = c.stream;
+    const float* knobs = c.knobs;
     const float* Wr = params + L.offs[0]; const float* Wi = params + L.offs[1];
     const float* Sr = params + L.offs[2]; const float* Si = params + L.offs[3];
     const float* ae_m = params + L.offs[4]; const float* ae_p = params + L.offs[22];
     // wide geometries (round 4): the analysis epilogue writes mag / phs straight into the wide autoencoder path's feature-major input
     const bool wide_direct = ae_is_wide(d) && g_wide_direct && (size_t)d->B * (L.KP / 2) * (size_t)(d->T > 64 ? d->T : 64) < ((size_t)1 << 30);
-    WideWS ww; if (wide_direct) wide_carve(d, w.aews, &ww);
+    WideWS ww; if (wide_direct) wide_carve(d, L, w.aews, &ww);
     PolarWide pwide{nullptr, nullptr, 0, 0u};
     if (wide_direct) pwide = PolarWide{ww.V[0], ww.V[1], L.KP / 2, (unsigned)ww.R};
     // saved-for-backward state always lives in the workspace; user-visible outputs are copies
@@ -1507,25 +1505,17 @@ static int forward_impl(const st_dims* d, const Layout& L, const float* params, 
         if (a.ht) a.n_w16 = (int)(((size_t)2 * d->F * (d->N / 4) + 255) / 256);
         a.wd = stm::PrepWide{}; a.wd.n_vpad = a.wd.n_kn = a.wd.n_pj = 0;
         if (wide_direct) {       // wide geometries: the side jobs of the feature-major input (see stm::PrepWide)
-            const int FP = L.KP / 2, Tp = ww.Tp;
+            const int FP = L.KP / 2;
             a.wd.Vm = ww.V[0]; a.wd.Vp = ww.V[1]; a.wd.FP = FP; a.wd.B = d->B; a.wd.R = (unsigned)ww.R;
             a.wd.H4Km = ww.H[0][3]; a.wd.H4Kp = ww.H[1][3]; a.wd.knobs = knobs; a.wd.K = d->K;
-            int blk = 0;
-            for (int n = 0; n < 2; ++n) {
-                const float* ae = n ? ae_p : ae_m;
-                a.wd.pj.src[2 * n] = ae + L.go.w[0]; a.wd.pj.dst[2 * n] = ww.W1p[n]; a.wd.pj.rows[2 * n] = 64; a.wd.pj.cols[2 * n] = d->T; a.wd.pj.pitch[2 * n] = Tp;
-                a.wd.pj.blk0[2 * n] = blk; blk += (64 * Tp + 255) / 256;
-                a.wd.pj.src[2 * n + 1] = ae + L.go.w[4]; a.wd.pj.dst[2 * n + 1] = ww.W5p[n]; a.wd.pj.rows[2 * n + 1] = 16; a.wd.pj.cols[2 * n + 1] = 16 + d->K; a.wd.pj.pitch[2 * n + 1] = 32;
-                a.wd.pj.blk0[2 * n + 1] = blk; blk += 2;
-            }
-            a.wd.pj.blk0[4] = blk; a.wd.n_pj = blk;
+            a.wd.n_pj = fill_pad_jobs(a.wd.pj, d, L, ae_m, ae_p, ww);
             a.wd.n_vpad = (int)(((size_t)d->B * d->T * (FP - d->F) + 255) / 256); if (a.wd.n_vpad < 1) a.wd.n_vpad = 1;
             a.wd.n_kn = (int)(((size_t)d->K * d->B * (FP / 4) + 255) / 256);
         }
         a.ai = sta::AEImgJob{}; a.ai.n_blk = 0;
         if (ae_img_level(d)) {      // round 10: the autoencoders' LDS weight images, once per step instead of once per workgroup of ae_fwd / ae_bwd
             a.ai.ae[0] = ae_m; a.ai.ae[1] = ae_p; a.ai.img = ae_img_ptr(w.aews); a.ai.go = L.go;
-            a.ai.T = d->T; a.ai.OT = d->OT; a.ai.K = d->K; a.ai.F = d->F; a.ai.FP = L.KP / 2; a.ai.expfac = (float)(7.0 / d->F);
+            a.ai.T = d->T; a.ai.OT = d->OT; a.ai.K = d->K; a.ai.F = d->F; a.ai.FP = L.KP / 2; a.ai.expfac = expfac_of(d);
             a.ai.n = ae_img_level(d) == 2 ? sta::ae_img_floats(L.KP / 2) : sta::ae_img_fwd_floats(L.KP / 2); a.ai.n_blk = (a.ai.n + 255) / 256;
         }
         hipLaunchKernelGGL(stm::prep_kernel, dim3(a.n_pad + a.n_fold + n_dead + a.wd.n_vpad + a.wd.n_kn + a.wd.n_pj + a.ai.n_blk + a.n_w16), dim3(256), 0, st_stream(stream), a);
@@ -1541,9 +1531,8 @@ static int forward_impl(const st_dims* d, const Layout& L, const float* params, 
         ST_TRY(analysis_fwd_planes(d, w, save ? w.re : nullptr, save ? w.im : nullptr, pmag, pphs, stream, &pwide));
     } else
     ST_TRY(analysis_fwd_impl(d, w.xp, true, Wr, Wi, 1.0f, save ? w.re : nullptr, save ? w.im : nullptr, pmag, pphs, stream, true, &pwide));
-    float* sv = nullptr;
-    if (save && ae_use_saved(d)) { Layout Ls; ST_TRY(make_layout(d, &Ls)); sv = ae_sv_ptr(d, Ls, w.aews); }      // round 6: the activations stay for the backward
-    ST_TRY(ae_fwd_impl(d, w.mag, w.phs, knobs, ae_m, ae_p, w.mag_hat, w.phs_hat, w.AA, w.reg_p,
+    float* const sv = (save && ae_use_saved(d)) ? ae_sv_ptr(d, L, w.aews) : nullptr;      // round 6: the activations stay for the backward
+    ST_TRY(ae_fwd_body(d, L, w.mag, w.phs, knobs, ae_m, ae_p, w.mag_hat, w.phs_hat, w.AA, w.reg_p,
                        (ae_is_wide(d) || (save && ae_use_split(d))) ? w.aews : nullptr, stream, w.g16 ? w.AA16 : nullptr, wide_direct, sv,
                        ae_img_level(d) ? ae_img_ptr(w.aews) : nullptr));     // fused geometries: the code h4 is kept for the split backward
     if (w.g16) ST_TRY(synthesis_frames16(d, w, stream)); else
@@ -1560,29 +1549,52 @@ static int forward_impl(const st_dims* d, const Layout& L, const float* params, 
 // backward of everything behind d syn (workspace holds the forward state): autograd of train.py:138.
 // phase 1 = synthesis dgrad/wgrad + autoencoders + polar backward (fills grads[n_stft/2 ..));
 // phase 2 = analysis weight gradient (fills rows [0,F) of the first two tensors).
-static int backward_syn(const st_dims* d, const Layout& L, float* grads, WS& w, void* stream, int* defer_slabs = nullptr, stm::NyqJob* defer_nyq = nullptr)
+// The weight-gradient GEMM of the 16-bit operand pipeline and the sum of its slabs.  synth: the synthesis bases (A = the spectra, B = the padded d syn), else the
+// analysis bases (A = d G, B = the padded input); half = -1 the whole tensor, 0 / 1 one basis of the analysis pair (analysis_wgrad_half: twice the k-slices on half
+// the tiles).  defer_slabs: the caller sums the slabs itself and receives their count.  No Nyquist job on this path.
+static int wgrad16_and_reduce(Call& c, float* grads, bool synth, int half, float* stage, int stage_bf16, int* defer_slabs = nullptr)
 {
+    const st_dims* d = c.d; const Layout& L = c.L; WS& w = c.w; void* stream = c.stream;
+    const int KP = L.KP, F = d->F, N = d->N;
+    const stg::RowMap map = synth ? synth_live(d) : stg::live_frames(d->T, d->H, d->N, d->N, d->L);
+    const int R = map.rows(d->B);
+    int ns = g16_wsplit(d, R);
+    if (half >= 0) {
+        const int room = (int)((wgrad_ws_floats(d) - (size_t)64 * 2 * N) / ((size_t)KP * N));      // slabs the workspace holds (the Nyquist partials sit behind them)
+        const int tiles = ((KP / 2 + 127) / 128) * (N / 128);
+        ns = (2 * num_cus()) / (tiles > 0 ? tiles : 1);
+        if (ns > R / 128) ns = R / 128; if (ns > room) ns = room; if (ns < 1) ns = 1;
+    }
+    if (synth) ST_TRY(wgrad16(d, w.AA16, (unsigned)(d->OT * KP), w.dsyn16, (unsigned)(d->y + 2 * N), map, R, w.wg, ns, stream, 0, -1, (g_g16_crop & 4) ? d->y : 0));
+    else ST_TRY(wgrad16(d, w.dG16, (unsigned)(d->T * KP), w.xp16, (unsigned)(d->L + 2 * N), map, R, w.wg, ns, stream, half > 0 ? KP / 2 : 0, half < 0 ? -1 : KP / 2, (g_g16_crop & 8) ? d->L : 0));
+    ST_LAUNCHED(synth ? "synthesis_wgrad" : "analysis_wgrad");
+    if (defer_slabs) { *defer_slabs = ns; return ST_OK; }
+    stm::NyqJob nq{}; nq.on = 0;
+    float* const g0 = grads + L.offs[synth ? 2 : 0]; float* const g1 = grads + L.offs[synth ? 3 : 1];
+    const int per = stm::nyq_blocks(N) / 2;
+    if (half < 0) hipLaunchKernelGGL(stm::wgrad_reduce_kernel, dim3(norm_partials(d)), dim3(256), 0, st_stream(stream),
+                                     w.wg, ns, g0, g1, synth ? w.norm_s : w.norm_a, N, F, KP, synth ? 1 : 0, 0, 2 * F, stage, nq, 0, stage_bf16);
+    else hipLaunchKernelGGL(stm::wgrad_reduce_kernel, dim3(F + per), dim3(256), 0, st_stream(stream),
+                            w.wg, ns, g0, g1, w.norm_a, N, F, KP, 0, half * F, F, stage, nq, half * per, stage_bf16);
+    ST_LAUNCHED(synth ? "synthesis_wgrad_reduce" : "analysis_wgrad_reduce");
+    return ST_OK;
+}
+static int backward_syn(Call& c, float* grads, int* defer_slabs = nullptr, stm::NyqJob* defer_nyq = nullptr)
+{
+    const st_dims* d = c.d; const Layout& L = c.L; WS& w = c.w; void* stream = c.stream;
     if (w.g16) {
         ST_TRY(synthesis_dgrad16(d, w, stream));
-        const stg::RowMap ms = synth_live(d);
-        const int R = ms.rows(d->B), KP = st_kp_of(d->F), ns = g16_wsplit(d, R);
-        ST_TRY(wgrad16(d, w.AA16, (unsigned)(d->OT * KP), w.dsyn16, (unsigned)(d->y + 2 * d->N), ms, R, w.wg, ns, stream, 0, -1, (g_g16_crop & 4) ? d->y : 0));
-        ST_LAUNCHED("synthesis_wgrad");
-        if (defer_slabs) { *defer_slabs = ns; if (defer_nyq) { *defer_nyq = stm::NyqJob{}; defer_nyq->on = 0; } return ST_OK; }
-        stm::NyqJob nq{}; nq.on = 0;
-        hipLaunchKernelGGL(stm::wgrad_reduce_kernel, dim3(st_norm_partials(d)), dim3(256), 0, st_stream(stream),
-                           w.wg, ns, grads + L.offs[2], grads + L.offs[3], w.norm_s, d->N, d->F, KP, 1, 0, 2 * d->F, (float*)nullptr, nq);
-        ST_LAUNCHED("synthesis_wgrad_reduce");
-        return ST_OK;
+        if (defer_slabs && defer_nyq) { *defer_nyq = stm::NyqJob{}; defer_nyq->on = 0; }
+        return wgrad16_and_reduce(c, grads, true, -1, nullptr, 0, defer_slabs);
     }
     if (use_planes(d) && g_pl_dgrad) ST_TRY(synthesis_dgrad_planes(d, w, stream)); else
     ST_TRY(synthesis_dgrad_impl(d, w.dsyn, true, w.Sfold, w.dAA, stream));
     return synthesis_wgrad_impl(d, w.AA, w.dsyn, true, w.wg, grads + L.offs[2], grads + L.offs[3], w.norm_s, stream, defer_slabs, defer_nyq);
 }
-static int backward_ae(const st_dims* d, const Layout& L, const float* params, float* grads,
-                       const float* knobs, const float* g_mag_hat, const float* g_mag, float reg_coef, WS& w, void* stream, int syn_slabs = 0,
+static int backward_ae(Call& c, const float* params, float* grads, const float* g_mag_hat, const float* g_mag, float reg_coef, int syn_slabs = 0,
                        const stm::NyqJob* syn_nyq = nullptr, float* kg = nullptr)
 {   // syn_slabs > 0: the synthesis weight-gradient slabs in w.wg are still to be summed (done by post_ae_kernel)
+    const st_dims* d = c.d; const Layout& L = c.L; WS& w = c.w; void* stream = c.stream;
     const float* ae_m = params + L.offs[4]; const float* ae_p = params + L.offs[22];
     bool deferred = true;
     const PolarSink sink{w.re, w.im, g_mag, w.g16 ? nullptr : w.dG, w.g16 ? w.dG16 : nullptr};
@@ -1591,7 +1603,7 @@ static int backward_ae(const st_dims* d, const Layout& L, const float* params, f
         syn.wg = w.wg; syn.nz = syn_slabs; syn.gSr = grads + L.offs[2]; syn.gSi = grads + L.offs[3]; syn.norm_s = w.norm_s; syn.N = d->N; syn.F = d->F; syn.KP = L.KP;
         syn.nyq = stm::NyqJob{}; syn.nyq.on = 0; if (syn_nyq) syn.nyq = *syn_nyq;
     }
-    ST_TRY(ae_bwd_impl(d, w.mag, w.phs, knobs, ae_m, ae_p, w.mag_hat, w.phs_hat, w.dAA, g_mag_hat, reg_coef, w.dmag, w.dphs,
+    ST_TRY(ae_bwd_body(d, L, w.mag, w.phs, c.knobs, ae_m, ae_p, w.mag_hat, w.phs_hat, w.dAA, g_mag_hat, reg_coef, w.dmag, w.dphs,
                        w.aews, grads + L.offs[4], grads + L.offs[22], true, stream, &deferred, &sink, syn.wg ? &syn : nullptr,
                        (d->clip_all && ae_is_wide(d)) ? w.norm_e : nullptr, &w.n_norm_e, kg, true));      // the forward left its AE state in w.aews
     if (!deferred) return ST_OK;                       // wide geometries: the gradient-finish launch summed the partials (and the synthesis slabs), and the polar backward ran inside wide_dv_polar_kernel
@@ -1612,54 +1624,41 @@ static int backward_ae(const st_dims* d, const Layout& L, const float* params, f
     if (w.g16) { a.dG16 = w.dG16; a.ht = gemm_ht(d->prec); a.dG = nullptr; }      // the analysis weight-gradient GEMM is the only consumer on this path
     a.norm_e = nullptr;
     if (d->clip_all && a.n_red <= NORM_E_MAX) { a.norm_e = w.norm_e; w.n_norm_e = a.n_red; }
-    hipLaunchKernelGGL(stm::post_ae_kernel, dim3(a.n_red + a.n_polar + (syn_slabs > 0 ? st_norm_partials(d) : 0)), dim3(256), 0, st_stream(stream), a);
+    hipLaunchKernelGGL(stm::post_ae_kernel, dim3(a.n_red + a.n_polar + (syn_slabs > 0 ? norm_partials(d) : 0)), dim3(256), 0, st_stream(stream), a);
     ST_LAUNCHED("post_ae");
     return ST_OK;
 }
-static int backward_p1(const st_dims* d, const Layout& L, const float* params, float* grads,
-                       const float* knobs, const float* g_mag_hat, const float* g_mag, float reg_coef, WS& w, void* stream, float* kg = nullptr)
+static int backward_p1(Call& c, const float* params, float* grads, const float* g_mag_hat, const float* g_mag, float reg_coef, float* kg = nullptr)
 {
     int syn_slabs = 0; stm::NyqJob syn_nyq{}; syn_nyq.on = 0;
-    ST_TRY(backward_syn(d, L, grads, w, stream, &syn_slabs, &syn_nyq));      // the slab sum rides in a later launch: post_ae_kernel (fused geometries) / wide_grad_finish_kernel (wide ones)
-    return backward_ae(d, L, params, grads, knobs, g_mag_hat, g_mag, reg_coef, w, stream, syn_slabs, &syn_nyq, kg);
+    ST_TRY(backward_syn(c, grads, &syn_slabs, &syn_nyq));      // the slab sum rides in a later launch: post_ae_kernel (fused geometries) / wide_grad_finish_kernel (wide ones)
+    return backward_ae(c, params, grads, g_mag_hat, g_mag, reg_coef, syn_slabs, &syn_nyq, kg);
 }
-static int backward_p2(const st_dims* d, const Layout& L, float* grads, const float* x, WS& w, void* stream, float* stage = nullptr, int stage_bf16 = 0)
+static int backward_p2(Call& c, float* grads, float* stage = nullptr, int stage_bf16 = 0)
 {
-    (void)x;
-    if (w.g16) {
-        const stg::RowMap ma = stg::live_frames(d->T, d->H, d->N, d->N, d->L);
-        const int R = ma.rows(d->B), KP = st_kp_of(d->F), ns = g16_wsplit(d, R);
-        ST_TRY(wgrad16(d, w.dG16, (unsigned)(d->T * KP), w.xp16, (unsigned)(d->L + 2 * d->N), ma, R, w.wg, ns, stream, 0, -1, (g_g16_crop & 8) ? d->L : 0));
-        ST_LAUNCHED("analysis_wgrad");
-        stm::NyqJob nq{}; nq.on = 0;
-        hipLaunchKernelGGL(stm::wgrad_reduce_kernel, dim3(st_norm_partials(d)), dim3(256), 0, st_stream(stream),
-                           w.wg, ns, grads + L.offs[0], grads + L.offs[1], w.norm_a, d->N, d->F, KP, 0, 0, 2 * d->F, stage, nq, 0, stage_bf16);
-        ST_LAUNCHED("analysis_wgrad_reduce");
-        return ST_OK;
-    }
-    return analysis_wgrad_impl(d, w.dG, w.xp, true, 1.0f, w.wg, grads + L.offs[0], grads + L.offs[1], w.norm_a, stream, -1, stage, stage_bf16);
+    if (c.w.g16) return wgrad16_and_reduce(c, grads, false, -1, stage, stage_bf16);
+    return analysis_wgrad_impl(c.d, c.w.dG, c.w.xp, true, 1.0f, c.w.wg, grads + c.L.offs[0], grads + c.L.offs[1], c.w.norm_a, c.stream, -1, stage, stage_bf16);
 }
 // ONE basis (half 0 = real, 1 = imaginary) of the analysis weight gradient -- its GEMM over that basis' rows and its slab reduce (gradient rows, packed
 // stage rows [half * F, half * F + F)) -- so that the data-parallel exchange of the first basis runs under the GEMM of the second (st_dp_train_step,
 // exchange flag 2): only F * N values (2.1 MB; 1.05 MB bf16-packed) stay exposed behind the last GEMM of the step.  Each half fills the chip with twice
 // the k-slices of the whole-tensor launch (half the tiles), so the two launches together do the work of the one.  nyq_io carries the Nyquist partials'
 // description (128 x 128-tile form: formed for BOTH bases by the first launch) from half 0 to half 1.
-static int analysis_wgrad_half(const st_dims* d, const Layout& L, float* grads, WS& w, int half, float* stage, int stage_bf16, stm::NyqJob* nyq_io, void* stream)
+static int analysis_wgrad_half(Call& c, float* grads, int half, float* stage, int stage_bf16, stm::NyqJob* nyq_io)
 {
+    const st_dims* d = c.d; const Layout& L = c.L; WS& w = c.w; void* stream = c.stream;
     const int KP = st_kp_of(d->F), F = d->F, N = d->N, m0 = half ? KP / 2 : 0;
     const stg::RowMap ma = stg::live_frames(d->T, d->H, d->N, d->N, d->L);
     const int R = ma.rows(d->B);
-    const int room = (int)((st_wgrad_ws_floats(d) - (size_t)64 * 2 * N) / ((size_t)KP * N));      // slabs the workspace holds (the Nyquist partials sit behind them)
+    const int room = (int)((wgrad_ws_floats(d) - (size_t)64 * 2 * N) / ((size_t)KP * N));      // slabs the workspace holds (the Nyquist partials sit behind them)
     const int per = stm::nyq_blocks(N) / 2;
     int ns;
     const stg::TNOperand ta{w.dG + m0, (unsigned)(d->T * KP), (unsigned)KP}, tb{w.xp, (unsigned)(d->L + 2 * d->N), (unsigned)d->H};
     if (w.g16) {
-        const int tiles = ((KP / 2 + 127) / 128) * (N / 128);
-        ns = (2 * num_cus()) / (tiles > 0 ? tiles : 1);
-        if (ns > R / 128) ns = R / 128; if (ns > room) ns = room; if (ns < 1) ns = 1;
-        ST_TRY(wgrad16(d, w.dG16, (unsigned)(d->T * KP), w.xp16, (unsigned)(d->L + 2 * d->N), ma, R, w.wg, ns, stream, m0, KP / 2, (g_g16_crop & 8) ? d->L : 0));
         if (!half) { *nyq_io = stm::NyqJob{}; nyq_io->on = 0; }
-    } else if (use_tn128(d, true) && stg::tn128_fits(ta, tb, w.xp, ma, N / 2, N, (size_t)d->B * d->T * KP, (size_t)d->B * (d->L + 2 * d->N))) {
+        return wgrad16_and_reduce(c, grads, false, half, stage, stage_bf16);
+    }
+    if (use_tn128(d, true) && stg::tn128_fits(ta, tb, w.xp, ma, N / 2, N, (size_t)d->B * d->T * KP, (size_t)d->B * (d->L + 2 * d->N))) {
         const int mh = (N / 2) / 128, tiles = mh * (N / 128);
         ns = num_cus() / (tiles > 0 ? tiles : 1); if (ns > 16) ns = 16; if (ns > R / 64) ns = R / 64; if (ns > room) ns = room; if (ns < 1) ns = 1;
         float* part = w.wg + (size_t)room * KP * N;
@@ -1680,32 +1679,27 @@ static int analysis_wgrad_half(const st_dims* d, const Layout& L, float* grads, 
     ST_LAUNCHED("analysis_wgrad_reduce");
     return ST_OK;
 }
-static int backward_impl(const st_dims* d, const Layout& L, const float* params, float* grads, const float* x,
-                         const float* knobs, const float* g_mag_hat, const float* g_mag, float reg_coef, WS& w, void* stream, float* kg = nullptr)
+static int backward_impl(Call& c, const float* params, float* grads, const float* g_mag_hat, const float* g_mag, float reg_coef, float* kg = nullptr)
 {
-    ST_TRY(backward_p1(d, L, params, grads, knobs, g_mag_hat, g_mag, reg_coef, w, stream, kg));
-    return backward_p2(d, L, grads, x, w, stream);
+    ST_TRY(backward_p1(c, params, grads, g_mag_hat, g_mag, reg_coef, kg));
+    return backward_p2(c, grads);
 }
 
 extern "C" int st_model_fwd(const st_dims* d, const float* params, const float* x, const float* knobs,
                             float* y_hat, float* mag, float* mag_hat, void* ws, int save_for_backward, void* stream)
 {
-    Layout L; ST_TRY(make_layout(d, &L));
+    Call c; ST_TRY(call_begin(&c, d, params, knobs, ws, stream, FP32_OPERANDS));
     ST_REQ(params && x && (knobs || d->K == 0) && ws, "st_model_fwd: null pointer");
-    if (!knobs) knobs = params;
-    WS w; carve(d, ws, &w);
-    return forward_impl(d, L, params, x, knobs, nullptr, y_hat, mag, mag_hat, w, save_for_backward != 0, stream);
+    return forward_impl(c, params, x, nullptr, y_hat, mag, mag_hat, save_for_backward != 0);
 }
 
 extern "C" int st_model_bwd(const st_dims* d, const float* params, float* grads, const float* x, const float* knobs,
                             const float* g_y_hat, const float* g_mag_hat, const float* g_mag, void* ws, void* stream)
 {
-    Layout L; ST_TRY(make_layout(d, &L));
+    Call c; ST_TRY(call_begin(&c, d, params, knobs, ws, stream, FP32_OPERANDS));
     ST_REQ(params && grads && x && (knobs || d->K == 0) && g_y_hat && ws, "st_model_bwd: null pointer");
-    if (!knobs) knobs = params;
-    WS w; carve(d, ws, &w);
-    ST_TRY(pad_scale(g_y_hat, w.dsyn, d->B, d->y, d->N, 2.0f, stream));     // dsyn = 2 * g_y_hat, padded for the framed loaders
-    return backward_impl(d, L, params, grads, x, knobs, g_mag_hat, g_mag, 0.0f, w, stream);
+    ST_TRY(pad_scale(g_y_hat, c.w.dsyn, d->B, d->y, d->N, 2.0f, stream));     // dsyn = 2 * g_y_hat, padded for the framed loaders
+    return backward_impl(c, params, grads, g_mag_hat, g_mag, 0.0f);
 }
 
 // d (anything downstream) / d knobs for arbitrary upstream gradients -- what autograd hands to a knobs tensor that requires grad (nn_proc.py:92-93: the
@@ -1775,13 +1769,13 @@ extern "C" size_t st_model_bwd_knobs_ws_floats(const st_dims* d)
 extern "C" int st_model_bwd_knobs(const st_dims* d, const float* params, float* grads, const float* x, const float* knobs,
                                   const float* g_y_hat, const float* g_mag_hat, const float* g_mag, void* ws, float* scratch, float* g_knobs, void* stream)
 {
-    Layout L; ST_TRY(make_layout(d, &L));
+    Call c; ST_TRY(call_begin(&c, d, params, knobs, ws, stream, FP32_OPERANDS));
+    const Layout& L = c.L;
     ST_REQ(params && grads && x && knobs && g_y_hat && ws && scratch && g_knobs, "st_model_bwd_knobs: null pointer");
     ST_REQ(d->K >= 1, "st_model_bwd_knobs: K = %d (a model without knobs has no knob gradient)", d->K);
     if (!ae_kg_route(d)) return st_fail(ST_ERR_UNSUPPORTED, "st_model_bwd_knobs: no per-group d a5 output on this autoencoder backward route (%s)", ae_kg_why(d));
-    WS w; carve(d, ws, &w);
-    ST_TRY(pad_scale(g_y_hat, w.dsyn, d->B, d->y, d->N, 2.0f, stream));     // as st_model_bwd
-    ST_TRY(backward_impl(d, L, params, grads, x, knobs, g_mag_hat, g_mag, 0.0f, w, stream, scratch));
+    ST_TRY(pad_scale(g_y_hat, c.w.dsyn, d->B, d->y, d->N, 2.0f, stream));     // as st_model_bwd
+    ST_TRY(backward_impl(c, params, grads, g_mag_hat, g_mag, 0.0f, scratch));
     const size_t w5 = (size_t)L.offs[4] + (size_t)L.go.w[4];
     const int gpw = L.KP / 32;
     hipLaunchKernelGGL(knob_grad_kernel, dim3(d->B), dim3(64), 0, st_stream(stream), params + w5, (const float*)scratch, params + w5 + L.PG,
@@ -1794,18 +1788,13 @@ extern "C" int st_loss_backward(const st_dims* d, const float* params, float* gr
                                 const float* y_true, float* y_hat, float* mag, float* mag_hat, void* ws,
                                 float* scalars, void* stream)
 {
-    Layout L; ST_TRY(make_layout(d, &L));
+    Call c; ST_TRY(call_begin(&c, d, params, knobs, ws, stream, G16_PIPELINE));
     ST_REQ(params && grads && x && (knobs || d->K == 0) && y_true && ws && scalars, "st_loss_backward: null pointer");
-    if (!knobs) knobs = params;
-    WS w; carve(d, ws, &w);
-    w.g16 = use_g16(d);
     prof_mark("begin", stream);
-    ST_TRY(forward_impl(d, L, params, x, knobs, y_true, y_hat, mag, mag_hat, w, true, stream));
-    const float reg_coef = loss_scale_of(d) * (float)(2e-5 / 10.0) / ((float)d->B * (float)d->OT * (float)d->F);   // loss_functions.py:36
-    ST_TRY(backward_impl(d, L, params, grads, x, knobs, nullptr, nullptr, reg_coef, w, stream));
+    ST_TRY(forward_impl(c, params, x, y_true, y_hat, mag, mag_hat, true));
+    ST_TRY(backward_impl(c, params, grads, nullptr, nullptr, reg_coef_of(d)));
     // grads carry the loss scale (if any); the published norm is that of the unscaled gradient
-    ST_TRY(st_finalize_scalars(d, w.loss_p, w.reg_p, w.norm_a, w.norm_s, 1.0f / loss_scale_of(d), scalars, stream));
-    return ST_OK;
+    return finalize_scalars(d, c.w.loss_p, c.w.reg_p, c.w.norm_a, c.w.norm_s, 1.0f / loss_scale_of(d), scalars, stream);
 }
 
 // One validation batch of train.py:28-42: the forward of the training step at this st_dims.prec (16-bit levels: the pre-rounded operand GEMMs), nothing kept
@@ -1814,17 +1803,14 @@ extern "C" int st_loss_backward(const st_dims* d, const float* params, float* gr
 extern "C" int st_eval_step(const st_dims* d, const float* params, const float* x, const float* knobs, const float* y_true,
                             float* y_hat, void* ws, double* acc, double beta, void* stream)
 {
-    Layout L; ST_TRY(make_layout(d, &L));
+    Call c; ST_TRY(call_begin(&c, d, params, knobs, ws, stream, G16_PIPELINE));
     ST_REQ(params, "st_eval_step: null pointer (params)"); ST_REQ(x, "st_eval_step: null pointer (x)");
     ST_REQ(knobs || d->K == 0, "st_eval_step: null pointer (knobs, K = %d)", d->K);
     ST_REQ(y_true, "st_eval_step: null pointer (y_true)"); ST_REQ(ws, "st_eval_step: null pointer (ws)"); ST_REQ(acc, "st_eval_step: null pointer (acc)");
-    if (!knobs) knobs = params;
-    WS w; carve(d, ws, &w);
-    w.g16 = use_g16(d);
     prof_mark("begin", stream);
-    float* const eval_p = w.dsyn;      // two arrays of B * ceil(y / 256) partials (the second at stm::mae_partial_offset) out of B * (y + 2N) floats
-    ST_TRY(forward_impl(d, L, params, x, knobs, y_true, y_hat, nullptr, nullptr, w, false, stream, eval_p));
-    const stm::FinArgs f = fin_args(d, eval_p, w.reg_p, nullptr, nullptr, 1.0f);
+    float* const eval_p = c.w.dsyn;      // two arrays of B * ceil(y / 256) partials (the second at stm::mae_partial_offset) out of B * (y + 2N) floats
+    ST_TRY(forward_impl(c, params, x, y_true, y_hat, nullptr, nullptr, false, eval_p));
+    const stm::FinArgs f = fin_args(d, eval_p, c.w.reg_p, nullptr, nullptr, 1.0f);
     hipLaunchKernelGGL(stm::eval_finalize_kernel, dim3(1), dim3(256), 0, st_stream(stream), f, beta, acc);
     ST_LAUNCHED("eval_finalize"); return ST_OK;
 }
@@ -1834,24 +1820,18 @@ extern "C" int st_eval_step(const st_dims* d, const float* params, const float* 
 extern "C" int st_loss_backward_p1(const st_dims* d, const float* params, float* grads, const float* x, const float* knobs,
                                    const float* y_true, void* ws, void* stream)
 {
-    Layout L; ST_TRY(make_layout(d, &L));
+    Call c; ST_TRY(call_begin(&c, d, params, knobs, ws, stream, G16_PIPELINE));
     ST_REQ(params && grads && x && (knobs || d->K == 0) && y_true && ws, "st_loss_backward_p1: null pointer");
-    if (!knobs) knobs = params;
-    WS w; carve(d, ws, &w);
-    w.g16 = use_g16(d);
     prof_mark("begin", stream);
-    ST_TRY(forward_impl(d, L, params, x, knobs, y_true, nullptr, nullptr, nullptr, w, true, stream));
-    const float reg_coef = loss_scale_of(d) * (float)(2e-5 / 10.0) / ((float)d->B * (float)d->OT * (float)d->F);
-    return backward_p1(d, L, params, grads, knobs, nullptr, nullptr, reg_coef, w, stream);
+    ST_TRY(forward_impl(c, params, x, y_true, nullptr, nullptr, nullptr, true));
+    return backward_p1(c, params, grads, nullptr, nullptr, reg_coef_of(d));
 }
 extern "C" int st_loss_backward_p2(const st_dims* d, float* grads, const float* x, void* ws, float* scalars, void* stream)
 {
-    Layout L; ST_TRY(make_layout(d, &L));
+    Call c; ST_TRY(call_begin(&c, d, nullptr, nullptr, ws, stream, G16_PIPELINE));
     ST_REQ(grads && x && ws && scalars, "st_loss_backward_p2: null pointer");
-    WS w; carve(d, ws, &w);
-    w.g16 = use_g16(d);
-    ST_TRY(backward_p2(d, L, grads, x, w, stream));
-    return st_finalize_scalars(d, w.loss_p, w.reg_p, w.norm_a, w.norm_s, 1.0f / loss_scale_of(d), scalars, stream);
+    ST_TRY(backward_p2(c, grads));
+    return finalize_scalars(d, c.w.loss_p, c.w.reg_p, c.w.norm_a, c.w.norm_s, 1.0f / loss_scale_of(d), scalars, stream);
 }
 
 // As st_loss_backward_p2, and the 2F live rows of the two analysis gradients are ALSO written packed into `stage` [2F][N]:
@@ -1859,12 +1839,10 @@ extern "C" int st_loss_backward_p2(const st_dims* d, float* grads, const float* 
 // first tensor (st_unstage_analysis copies the reduced rows back).
 extern "C" int st_loss_backward_p2_staged(const st_dims* d, float* grads, float* stage, const float* x, void* ws, float* scalars, void* stream)
 {
-    Layout L; ST_TRY(make_layout(d, &L));
+    Call c; ST_TRY(call_begin(&c, d, nullptr, nullptr, ws, stream, G16_PIPELINE));
     ST_REQ(grads && stage && x && ws && scalars, "st_loss_backward_p2_staged: null pointer");
-    WS w; carve(d, ws, &w);
-    w.g16 = use_g16(d);
     (void)scalars;      // the loss scalars are published by st_dp_clip_adam (no single-block finalize between this GEMM and the all-reduce)
-    return backward_p2(d, L, grads, x, w, stream, stage);
+    return backward_p2(c, grads, stage);
 }
 extern "C" int st_unstage_analysis(const st_dims* d, float* grads, const float* stage, void* stream)
 {
@@ -1886,49 +1864,35 @@ extern "C" int st_unstage_analysis(const st_dims* d, float* grads, const float* 
 extern "C" int st_loss_backward_stage(const st_dims* d, const float* params, float* grads, const float* x, const float* knobs,
                                       const float* y_true, void* ws, float* scalars, int stage, void* stream)
 {
-    Layout L; ST_TRY(make_layout(d, &L));
+    Call c; ST_TRY(call_begin(&c, d, params, knobs, ws, stream, FP32_OPERANDS));
+    const Layout& L = c.L; WS& w = c.w;
     ST_REQ(params && grads && x && (knobs || d->K == 0) && y_true && ws && scalars, "st_loss_backward_stage: null pointer");
-    if (!knobs) knobs = params;
     ST_REQ(stage >= 0 && stage < 4, "st_loss_backward_stage: stage %d not in 0..3", stage);
-    WS w; carve(d, ws, &w);
-    const float reg_coef = loss_scale_of(d) * (float)(2e-5 / 10.0) / ((float)d->B * (float)d->OT * (float)d->F);
     switch (stage) {
     case 0:
         prof_mark("begin", stream);
-        ST_TRY(forward_impl(d, L, params, x, knobs, y_true, nullptr, nullptr, nullptr, w, true, stream));
-        return backward_syn(d, L, grads, w, stream);
+        ST_TRY(forward_impl(c, params, x, y_true, nullptr, nullptr, nullptr, true));
+        return backward_syn(c, grads);
     case 1:
-        return backward_ae(d, L, params, grads, knobs, nullptr, nullptr, reg_coef, w, stream);
+        return backward_ae(c, params, grads, nullptr, nullptr, reg_coef_of(d));
     case 2:
         return analysis_wgrad_impl(d, w.dG, w.xp, true, 1.0f, w.wg, grads + L.offs[0], grads + L.offs[1], w.norm_a, stream, 0);
     default:
         ST_TRY(analysis_wgrad_impl(d, w.dG, w.xp, true, 1.0f, w.wg, grads + L.offs[0], grads + L.offs[1], w.norm_a, stream, 1));
-        return st_finalize_scalars(d, w.loss_p, w.reg_p, w.norm_a, w.norm_s, 1.0f / loss_scale_of(d), scalars, stream);
+        return finalize_scalars(d, w.loss_p, w.reg_p, w.norm_a, w.norm_s, 1.0f / loss_scale_of(d), scalars, stream);
     }
 }
 
 static int train_step_impl(const st_dims* d, float* params, float* grads, float* m, float* v, const float* x,
                            const float* knobs, const float* y_true, void* ws, float* scalars,
-                           float lr, float beta1, float beta2, float eps, int step, void* stream, bool dev_hyper);
-extern "C" int st_train_step(const st_dims* d, float* params, float* grads, float* m, float* v, const float* x,
-                             const float* knobs, const float* y_true, void* ws, float* scalars,
-                             float lr, float beta1, float beta2, float eps, int step, void* stream)
-{
-    return train_step_impl(d, params, grads, m, v, x, knobs, y_true, ws, scalars, lr, beta1, beta2, eps, step, stream, false);
-}
-static int train_step_impl(const st_dims* d, float* params, float* grads, float* m, float* v, const float* x,
-                           const float* knobs, const float* y_true, void* ws, float* scalars,
                            float lr, float beta1, float beta2, float eps, int step, void* stream, bool dev_hyper)
 {
-    Layout L; ST_TRY(make_layout(d, &L));
+    Call c; ST_TRY(call_begin(&c, d, params, knobs, ws, stream, G16_PIPELINE));
+    const Layout& L = c.L; WS& w = c.w;
     ST_REQ(params && grads && x && (knobs || d->K == 0) && y_true && ws && scalars, "st_train_step: null pointer");
-    if (!knobs) knobs = params;
-    WS w; carve(d, ws, &w);
-    w.g16 = use_g16(d);
     prof_mark("begin", stream);
-    ST_TRY(forward_impl(d, L, params, x, knobs, y_true, nullptr, nullptr, nullptr, w, true, stream));
-    const float reg_coef = loss_scale_of(d) * (float)(2e-5 / 10.0) / ((float)d->B * (float)d->OT * (float)d->F);   // loss_functions.py:36
-    ST_TRY(backward_impl(d, L, params, grads, x, knobs, nullptr, nullptr, reg_coef, w, stream));
+    ST_TRY(forward_impl(c, params, x, y_true, nullptr, nullptr, nullptr, true));
+    ST_TRY(backward_impl(c, params, grads, nullptr, nullptr, reg_coef_of(d)));
     // loss scalars + clip coefficient inside the optimizer kernel (st_loss_backward + st_clip_adam minus one launch)
     const float inv_s = 1.0f / loss_scale_of(d);            // the gradients carry the loss scale: unscale inside the optimizer
     stm::FinArgs f = fin_args(d, w.loss_p, w.reg_p, w.norm_a, w.norm_s, inv_s);
@@ -1943,17 +1907,22 @@ static int train_step_impl(const st_dims* d, float* params, float* grads, float*
     }
     return clip_adam_impl(params, grads, m, v, L.total, d->clip_all ? L.total : L.n_stft, scalars, inv_s, lr, beta1, beta2, eps, step, &f, stream, dev_hyper);
 }
+extern "C" int st_train_step(const st_dims* d, float* params, float* grads, float* m, float* v, const float* x,
+                             const float* knobs, const float* y_true, void* ws, float* scalars,
+                             float lr, float beta1, float beta2, float eps, int step, void* stream)
+{
+    return train_step_impl(d, params, grads, m, v, x, knobs, y_true, ws, scalars, lr, beta1, beta2, eps, step, stream, false);
+}
 
 extern "C" int st_dp_clip_adam(const st_dims* d, float* params, float* grads, float* m, float* v, void* ws,
                                float* scalars, float grad_scale, float lr, float beta1, float beta2, float eps,
                                int step, void* stream)
 {
-    Layout L; ST_TRY(make_layout(d, &L));
+    Call c; ST_TRY(call_begin(&c, d, nullptr, nullptr, ws, stream, G16_PIPELINE));
+    const Layout& L = c.L; WS& w = c.w;
     ST_REQ(params && grads && m && v && ws && scalars, "st_dp_clip_adam: null pointer");
-    WS w; carve(d, ws, &w);
-    w.g16 = use_g16(d);
     // L1 norm of the all-reduced, 1/world-scaled STFT gradient: identical on every rank, no second collective
-    const int np = st_norm_partials(d);
+    const int np = norm_partials(d);
     const int64_t n_clip = d->clip_all ? L.total : L.n_stft;
     const float gs = grad_scale / loss_scale_of(d);          // 1/world and the loss scale leave the gradient together
     hipLaunchKernelGGL(stm::l1_partial_kernel, dim3(np), dim3(256), 0, st_stream(stream),
@@ -2213,7 +2182,7 @@ extern "C" int st_model_input_grad(const st_dims* d, const float* params, void* 
     Layout L; ST_TRY(make_layout(d, &L));
     ST_REQ(params && ws && scratch && gxh, "st_model_input_grad: null pointer");
     ST_REQ(d->L % 4 == 0 && d->H % 4 == 0, "st_model_input_grad: L %% 4 and hop %% 4 required");
-    WS w; carve(d, ws, &w);
+    WS w; carve(d, L, ws, &w);
     float* Wc = scratch; float* frs = scratch + (size_t)L.KP * d->N;
     hipLaunchKernelGGL(wcat_kernel, dim3(L.KP), dim3(256), 0, st_stream(stream), params + L.offs[0], params + L.offs[1], Wc, d->F, d->N, L.KP);
     ST_TRY(fe_frames_ola(w.dG, d->B, d->T, Wc, L.KP, d->N, d->H, d->N, d->L, frs, gxh, stream));
@@ -2373,10 +2342,10 @@ extern "C" int st_dp_train_step(st_dp* p, const st_dims* d, float* params, float
 {
     if (!p || (p->world == 1 && !(force_exchange & 1)))
         return st_train_step(d, params, grads, m, v, x, knobs, y_true, ws, scalars, lr, beta1, beta2, eps, step, stream);
-    Layout L; ST_TRY(make_layout(d, &L));
+    Call c; ST_TRY(call_begin(&c, d, params, knobs, ws, stream, G16_PIPELINE));
+    const Layout& L = c.L; WS& w = c.w;
     ST_REQ(stage, "st_dp_train_step: null staging buffer");
     ST_REQ(params && grads && x && (knobs || d->K == 0) && y_true && ws, "st_dp_train_step: null pointer");
-    if (!knobs) knobs = params;
     const float gs = (1.0f / (float)p->world) / loss_scale_of(d);          // 1/world and the loss scale leave the gradient together
     // force_exchange is a bit set: 1 = run the exchange even with one rank; 2 = split the LAST exchange by basis (real rows under the GEMM of the imaginary
     // ones: 2.1 MB exposed instead of 4.2); 4 = that exchange on bfloat16 values (only where the autoencoder layers already run in 16 bits: *_ALL)
@@ -2389,18 +2358,15 @@ extern "C" int st_dp_train_step(st_dp* p, const st_dims* d, float* params, float
     //                                (round 3 ran it in line: a 9 us launch on the critical path that the single-GPU step folds into post_ae_kernel);
     //   autoencoders (67 KB)      -- after the autoencoder backward;
     //   analysis bases            -- the 2F live rows, packed (4.2 MB), after the last GEMM of the step: the exposed one (split / packed: see the flags).
-    WS w; carve(d, ws, &w);
-    w.g16 = use_g16(d);
     {
         prof_mark("begin", stream);
-        ST_TRY(forward_impl(d, L, params, x, knobs, y_true, nullptr, nullptr, nullptr, w, true, stream));
-        const float reg_coef = loss_scale_of(d) * (float)(2e-5 / 10.0) / ((float)d->B * (float)d->OT * (float)d->F);
+        ST_TRY(forward_impl(c, params, x, y_true, nullptr, nullptr, nullptr, true));
         int syn_slabs = 0; stm::NyqJob syn_nyq{}; syn_nyq.on = 0;
         float* const wg_main = w.wg;
         if (g_dp_inline) w.wg = w.wg2;                                                  // round 6: the synthesis slabs in their own area (no wait before the analysis GEMM reuses the first)
-        ST_TRY(backward_syn(d, L, grads, w, stream, &syn_slabs, &syn_nyq));             // GEMMs only; the slabs are summed on the communicator stream
+        ST_TRY(backward_syn(c, grads, &syn_slabs, &syn_nyq));                           // GEMMs only; the slabs are summed on the communicator stream
         ST_TRY(dp_fork(p, stream));
-        hipLaunchKernelGGL(stm::wgrad_reduce_kernel, dim3(st_norm_partials(d)), dim3(256), 0, p->cs,
+        hipLaunchKernelGGL(stm::wgrad_reduce_kernel, dim3(norm_partials(d)), dim3(256), 0, p->cs,
                            w.wg, syn_slabs, grads + L.offs[2], grads + L.offs[3], w.norm_s, d->N, d->F, L.KP, 1, 0, 2 * d->F, (float*)nullptr, syn_nyq);
         w.wg = wg_main;
         if (!g_dp_inline) ST_HIP(hipEventRecord(p->wgfree, p->cs), "event record");     // the analysis weight-gradient GEMM reuses the slab buffer
@@ -2408,8 +2374,8 @@ extern "C" int st_dp_train_step(st_dp* p, const st_dims* d, float* params, float
         // The clip norm is that of the REDUCED, 1/world-scaled gradient.  The two ranges whose exchange is hidden get their |g| partials on the communicator
         // stream right behind their collective (hidden as well); only the analysis rows' share is formed after the exposed collective, in the pass that
         // copies them back (unstage_l1_kernel).  Same kernels, same order, same data on every rank: the norm is bit-identical across ranks.
-        hipLaunchKernelGGL(stm::l1_partial_kernel, dim3(st_norm_partials(d)), dim3(256), 0, p->cs, grads + L.offs[2], L.offs[4] - L.offs[2], gs, w.norm_s);
-        ST_TRY(backward_ae(d, L, params, grads, knobs, nullptr, nullptr, reg_coef, w, stream, 0, nullptr));
+        hipLaunchKernelGGL(stm::l1_partial_kernel, dim3(norm_partials(d)), dim3(256), 0, p->cs, grads + L.offs[2], L.offs[4] - L.offs[2], gs, w.norm_s);
+        ST_TRY(backward_ae(c, params, grads, nullptr, nullptr, reg_coef_of(d), 0, nullptr));
         ST_TRY(st_dp_allreduce(p, grads + L.offs[4], L.total - L.offs[4], stream));
         if (d->clip_all) hipLaunchKernelGGL(stm::l1_partial_kernel, dim3(NORM_E_PARTIALS), dim3(256), 0, p->cs, grads + L.n_stft, L.total - L.n_stft, gs, w.norm_e);
         if (!g_dp_inline) ST_HIP(hipStreamWaitEvent(st_stream(stream), p->wgfree, 0), "stream wait");
@@ -2422,18 +2388,18 @@ extern "C" int st_dp_train_step(st_dp* p, const st_dims* d, float* params, float
         // rank as a 21 us hole in front of the optimizer kernel) become ONE join that is recorded HERE, behind the last hidden collective, and has fired long
         // before the GEMM below ends.  RCCL serialises the collectives of one communicator in issue order across streams; every rank issues the same order.
         ST_HIP(hipEventRecord(p->done, p->cs), "event record");
-        ST_TRY(backward_p2(d, L, grads, x, w, stream, stage, pack16));
+        ST_TRY(backward_p2(c, grads, stage, pack16));
         ST_HIP(hipStreamWaitEvent(st_stream(stream), p->done, 0), "stream wait");
         ST_NCCL(p, p->AllReduce(stage, stage, (size_t)(2 * half_n), pack16 ? ncclBfloat16 : ncclFloat32, ncclSum, p->comm, st_stream(stream)), "ncclAllReduce");
         last_in_line = true;
     } else if (!split_last) {
-        ST_TRY(backward_p2(d, L, grads, x, w, stream, stage, pack16));
+        ST_TRY(backward_p2(c, grads, stage, pack16));
         ST_TRY(dp_fork(p, stream));
         ST_TRY(dp_allreduce_on_cs(p, stage, 2 * half_n, pack16 ? ncclBfloat16 : ncclFloat32));
     } else {
         stm::NyqJob nyq{}; nyq.on = 0;
         for (int h = 0; h < 2; ++h) {
-            ST_TRY(analysis_wgrad_half(d, L, grads, w, h, stage, pack16, &nyq, stream));
+            ST_TRY(analysis_wgrad_half(c, grads, h, stage, pack16, &nyq));
             void* part = pack16 ? (void*)(reinterpret_cast<unsigned short*>(stage) + (size_t)h * half_n) : (void*)(stage + (size_t)h * half_n);
             if (h == 1 && g_dp_inline) {        // the second half's exchange is the exposed one: in line, behind the join recorded when the first half's was issued
                 ST_HIP(hipStreamWaitEvent(st_stream(stream), p->done, 0), "stream wait");
@@ -2448,7 +2414,7 @@ extern "C" int st_dp_train_step(st_dp* p, const st_dims* d, float* params, float
     }
     if (!last_in_line) ST_TRY(st_dp_sync(p, stream));
     {
-        const int np = st_norm_partials(d);
+        const int np = norm_partials(d);
         hipLaunchKernelGGL(stm::unstage_l1_kernel, dim3(2 * d->F), dim3(256), 0, st_stream(stream), stage, grads + L.offs[0], grads + L.offs[1], d->F, d->N, gs, w.norm_a, np, pack16);
         ST_LAUNCHED("unstage_l1");
         stm::FinArgs f = fin_args(d, w.loss_p, w.reg_p, w.norm_a, w.norm_s, 1.0f);
@@ -2471,42 +2437,39 @@ static int attr_prepare(const st_dims* d)
 {
     // hipFuncSetAttribute is not a capturable call: make sure every >64 KB-LDS kernel this geometry / precision uses has its
     // attribute before the capture starts (ensure_dyn_lds is then a table hit inside the captured calls)
+    auto prep = [](auto* kernel, const char* name) { return ensure_dyn_lds(reinterpret_cast<const void*>(kernel), name); };
     const int ht = ae_ht(d->prec);
-#define ST_PREP3(K0_, K1_, K2_) do { if (ht == 1) ST_DYN_LDS(K1_); else if (ht == 2) ST_DYN_LDS(K2_); else ST_DYN_LDS(K0_); } while (0)
-    if (ae_is_wide(d)) {
-        ST_PREP3((sta::ae_inner_fwd_kernel<AE_FWD_NW, 0>), (sta::ae_inner_fwd_kernel<AE_FWD_NW, 1>), (sta::ae_inner_fwd_kernel<AE_FWD_NW, 2>));
-        ST_PREP3((sta::ae_inner_fwd_kernel<9, 0>), (sta::ae_inner_fwd_kernel<9, 1>), (sta::ae_inner_fwd_kernel<9, 2>));
-        ST_PREP3((sta::ae_inner_fwd_kernel<12, 0>), (sta::ae_inner_fwd_kernel<12, 1>), (sta::ae_inner_fwd_kernel<12, 2>));
-        ST_PREP3((sta::ae_bwd_kernel<AE_BWD_NW, true, 0, 0>), (sta::ae_bwd_kernel<AE_BWD_NW, true, 1, 0>), (sta::ae_bwd_kernel<AE_BWD_NW, true, 2, 0>));
-        ST_PREP3((stw::wide_dv_polar_kernel<0>), (stw::wide_dv_polar_kernel<1>), (stw::wide_dv_polar_kernel<2>));
-    } else {
-        ST_PREP3((sta::ae_fwd_kernel<AE_FWD_NW, 0>), (sta::ae_fwd_kernel<AE_FWD_NW, 1>), (sta::ae_fwd_kernel<AE_FWD_NW, 2>));
-        if (ht == 1) ST_DYN_LDS((sta::ae_fwd32_kernel<AE_FWD_NW, 1>)); else if (ht == 2) ST_DYN_LDS((sta::ae_fwd32_kernel<AE_FWD_NW, 2>));
-        if (ht == 0) { ST_DYN_LDS((sta::ae_fwd_kernel<11, 0>)); ST_DYN_LDS((sta::ae_fwd_kernel<11, 0, true>)); ST_DYN_LDS((sta::ae_fwd_kernel<AE_FWD_NW, 0, true>));
-                       ST_DYN_LDS((sta::ae_bwd_kernel<AE_BWD_NW, false, 0, 0, true>)); ST_DYN_LDS((sta::ae_bwd_kernel<AE_BWD_NW, false, 0, 1, true>)); ST_DYN_LDS((sta::ae_bwd_kernel<AE_BWD_NW, false, 0, 2, true>));
-                       ST_DYN_LDS((sta::ae_bwd_kernel<AE_BWD_NW, false, 0, 0, true, false, true>)); ST_DYN_LDS((sta::ae_bwd_kernel<AE_BWD_NW, false, 0, 1, true, false, true>));
-                       ST_DYN_LDS((sta::ae_bwd_kernel<AE_BWD_NW, false, 0, 2, true, false, true>)); }
-        ST_PREP3((sta::ae_bwd_part_kernel<AE_SPLIT_NW, 1, 0, false>), (sta::ae_bwd_part_kernel<AE_SPLIT_NW, 1, 1, false>), (sta::ae_bwd_part_kernel<AE_SPLIT_NW, 1, 2, false>));
-        ST_PREP3((sta::ae_bwd_part_kernel<AE_SPLIT_NW, 2, 0, false>), (sta::ae_bwd_part_kernel<AE_SPLIT_NW, 2, 1, false>), (sta::ae_bwd_part_kernel<AE_SPLIT_NW, 2, 2, false>));
-        if (d->T - d->OT == 16) ST_PREP3((sta::ae_bwd_kernel<AE_BWD_NW, false, 0, 2>), (sta::ae_bwd_kernel<AE_BWD_NW, false, 1, 2>), (sta::ae_bwd_kernel<AE_BWD_NW, false, 2, 2>));
-        else ST_PREP3((sta::ae_bwd_kernel<AE_BWD_NW, false, 0, 0>), (sta::ae_bwd_kernel<AE_BWD_NW, false, 1, 0>), (sta::ae_bwd_kernel<AE_BWD_NW, false, 2, 0>));
-    }
-#undef ST_PREP3
-    if (g_nt128 && gemm_ht(d->prec) == 0) ST_DYN_LDS((stg::gemm_nt128_kernel));
-    if (use_g16(d)) {           // st_gemm16.h: 72 / 80 KB of LDS with 64-deep k-tiles
-        if (gemm_ht(d->prec) == 2) {
-            ST_DYN_LDS((stg::gemm16_nt256_kernel<2, stg::PolarStore>)); ST_DYN_LDS((stg::gemm16_nt256_kernel<2, stg::StoreC>));
-            ST_DYN_LDS((stg::gemm16_nt_kernel<2, 64, stg::PolarStore>)); ST_DYN_LDS((stg::gemm16_nt_kernel<2, 64, stg::StoreC>)); ST_DYN_LDS((stg::gemm16_tn_kernel<2, 64>));
-        } else {
-            ST_DYN_LDS((stg::gemm16_nt256_kernel<1, stg::PolarStore>)); ST_DYN_LDS((stg::gemm16_nt256_kernel<1, stg::StoreC>));
-            ST_DYN_LDS((stg::gemm16_nt_kernel<1, 64, stg::PolarStore>)); ST_DYN_LDS((stg::gemm16_nt_kernel<1, 64, stg::StoreC>)); ST_DYN_LDS((stg::gemm16_tn_kernel<1, 64>));
+    if (ae_is_wide(d))
+        ST_TRY(with_ht(ht, [&](auto HT) -> int {
+            ST_TRY(prep(sta::ae_inner_fwd_kernel<AE_FWD_NW, HT()>, "ae_inner_fwd_kernel")); ST_TRY(prep(sta::ae_inner_fwd_kernel<9, HT()>, "ae_inner_fwd_kernel"));
+            ST_TRY(prep(sta::ae_inner_fwd_kernel<12, HT()>, "ae_inner_fwd_kernel"));
+            ST_TRY(prep(sta::ae_bwd_kernel<AE_BWD_NW, true, HT(), 0>, "ae_bwd_kernel"));
+            return prep(stw::wide_dv_polar_kernel<HT()>, "wide_dv_polar_kernel"); }));
+    else {
+        ST_TRY(with_ht(ht, [&](auto HT) -> int {
+            ST_TRY(prep(sta::ae_fwd_kernel<AE_FWD_NW, HT()>, "ae_fwd_kernel"));
+            ST_TRY(prep(sta::ae_bwd_part_kernel<AE_SPLIT_NW, 1, HT(), false>, "ae_bwd_part_kernel")); ST_TRY(prep(sta::ae_bwd_part_kernel<AE_SPLIT_NW, 2, HT(), false>, "ae_bwd_part_kernel"));
+            return d->T - d->OT == 16 ? prep(sta::ae_bwd_kernel<AE_BWD_NW, false, HT(), 2>, "ae_bwd_kernel") : prep(sta::ae_bwd_kernel<AE_BWD_NW, false, HT(), 0>, "ae_bwd_kernel"); }));
+        if (ht != 0) ST_TRY(with_ht16(ht, [&](auto HT) { return prep(sta::ae_fwd32_kernel<AE_FWD_NW, HT()>, "ae_fwd32_kernel"); }));
+        else {      // fp32 layers: the 11-wave forward, the kept-activation forms of both, with and without the ready-made images
+            ST_TRY(prep(sta::ae_fwd_kernel<11, 0>, "ae_fwd_kernel")); ST_TRY(prep(sta::ae_fwd_kernel<11, 0, true>, "ae_fwd_kernel")); ST_TRY(prep(sta::ae_fwd_kernel<AE_FWD_NW, 0, true>, "ae_fwd_kernel"));
+            for (int var = 0; var < 3; ++var)
+                ST_TRY(with_var(var, [&](auto VAR) -> int {
+                    ST_TRY(prep(sta::ae_bwd_kernel<AE_BWD_NW, false, 0, VAR(), true>, "ae_bwd_kernel"));
+                    return prep(sta::ae_bwd_kernel<AE_BWD_NW, false, 0, VAR(), true, false, true>, "ae_bwd_kernel"); }));
         }
     }
+    if (g_nt128 && gemm_ht(d->prec) == 0) ST_TRY(prep(stg::gemm_nt128_kernel, "gemm_nt128_kernel"));
+    if (use_g16(d))             // st_gemm16.h: 72 / 80 KB of LDS with 64-deep k-tiles
+        ST_TRY(with_ht16(gemm_ht(d->prec), [&](auto HT) -> int {
+            ST_TRY(prep(stg::gemm16_nt256_kernel<HT(), stg::PolarStore>, "gemm16_nt256_kernel")); ST_TRY(prep(stg::gemm16_nt256_kernel<HT(), stg::StoreC>, "gemm16_nt256_kernel"));
+            ST_TRY(prep(stg::gemm16_nt_kernel<HT(), 64, stg::PolarStore>, "gemm16_nt_kernel")); ST_TRY(prep(stg::gemm16_nt_kernel<HT(), 64, stg::StoreC>, "gemm16_nt_kernel"));
+            return prep(stg::gemm16_tn_kernel<HT(), 64>, "gemm16_tn_kernel"); }));
     if (use_planes(d)) {        // the 4-wave plane GEMM carries 67 KB of LDS (st_gemm_planes.h)
-        ST_DYN_LDS((stg::gemm_planes_kernel<4, 3, stg::FramedNT<true>, stg::ChunkP, stg::PolarStore>));
-        ST_DYN_LDS((stg::gemm_planes_kernel<8, 3, stg::FramedNT<true>, stg::ChunkP, stg::PolarStore>));
-        ST_DYN_LDS((stg::gemm_planes_kernel<4, 3, stg::PlainNT, stg::ChunkP, stg::StoreC>));
-        ST_DYN_LDS((stg::gemm_planes_kernel<4, 3, stg::FramedNT<true>, stg::ChunkP, stg::StoreC>));
+        ST_TRY(prep(stg::gemm_planes_kernel<4, 3, stg::FramedNT<true>, stg::ChunkP, stg::PolarStore>, "gemm_planes_kernel"));
+        ST_TRY(prep(stg::gemm_planes_kernel<8, 3, stg::FramedNT<true>, stg::ChunkP, stg::PolarStore>, "gemm_planes_kernel"));
+        ST_TRY(prep(stg::gemm_planes_kernel<4, 3, stg::PlainNT, stg::ChunkP, stg::StoreC>, "gemm_planes_kernel"));
+        ST_TRY(prep(stg::gemm_planes_kernel<4, 3, stg::FramedNT<true>, stg::ChunkP, stg::StoreC>, "gemm_planes_kernel"));
     }
     (void)num_cus();
     return ST_OK;
@@ -2516,9 +2479,8 @@ extern "C" int st_graph_create(const st_dims* d, float* params, float* grads, fl
                                const float* knobs, const float* y_true, void* ws, float* scalars,
                                const float* lr_table, int n_lr, float beta1, float beta2, float eps, void* stream, st_graph** out)
 {
-    Layout L; ST_TRY(make_layout(d, &L));
+    ST_TRY(check_dims(d));
     ST_REQ(params && grads && m && v && x && (knobs || d->K == 0) && y_true && ws && scalars && lr_table && n_lr > 0 && out, "st_graph_create: bad arguments");
-    if (!knobs) knobs = params;
     ST_REQ(!g_prof, "st_graph_create: switch the event profiling off first (event records would be captured)");
     ST_TRY(attr_prepare(d));
     hipStream_t s = st_stream(stream);
