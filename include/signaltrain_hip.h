@@ -397,6 +397,23 @@ int st_compressor_4c(const float* x, const float* knobs_wc, float sr, int B, int
  * below the threshold).  The envelope is a linear recurrence and runs as a parallel scan in one workgroup per window.
  *   x [B][L] fp32, knobs_wc [B][3] = (threshold dB, ratio, attack / release s) in WORLD coordinates, y [B][ysz] = the last ysz samples. */
 int st_compressor(const float* x, const float* knobs_wc, float sr, int B, int L, int ysz, float* y, void* stream);
+/* audio.LowPass (signaltrain/audio.py:610-625): scipy's butter(3, cutoff / (sr / 2)) low-pass run by lfilter from a zero state.  The
+ * recurrence is linear, so the window is a parallel scan in one workgroup per window -- over the three MODES of the filter (parallel form
+ * d + sum r_k / (1 - p_k z^-1) with the poles and residues in closed form from K = tan(pi cutoff / sr)), not over lfilter's direct-form state,
+ * whose maps are too ill-conditioned to compose near z = 1 (st_filter.h).  float64 states, y rounded to fp32; within 1e-5 of
+ * max(1e-3, max |y|) of scipy's float64 lfilter (measured: 3.5e-7; scipy itself is 7.5e-8 away from a long-double run at 10 Hz).
+ *   x [B][L] fp32, knobs_wc [B][1] = the cutoff in Hz (WORLD coordinates), y [B][ysz] = the last ysz samples of the filtered window.
+ * Asynchronous, no allocation.  Refused before any launch (ST_ERR_ARG, the rule in st_last_error()): a null pointer; B, L, ysz <= 0; ysz > L;
+ * sr <= 0; L % 4.  The cutoff is device data and cannot be checked on the host: a cutoff that is not inside (0, sr / 2), or is NaN, makes that
+ * row of y all NaN and nothing else. */
+int st_lowpass(const float* x, const float* knobs_wc, float sr, int B, int L, int ysz, float* y, void* stream);
+/* The input of audio.Denoise (signaltrain/audio.py:558-571: the clean signal is the target, the noisy one the input) for callers that bring
+ * their own clean windows:  x_noisy[b][n] = x[b][n] + knobs_wc[b] * (2 u - 1),  u = value n of per-sample stream 11 of window
+ * first_window + b of the stream `seed` (the counter-based generator of st_synth_effect), the noise formed and added in float32.  The same
+ * stream as ST_FX_DENOISE's: identical bits for the same (seed, window, clean x, strength).
+ *   x, x_noisy [B][L] fp32 (x_noisy may alias x), knobs_wc [B][1] = the strength (WORLD coordinates).
+ * Asynchronous, no allocation.  Refused before any launch (ST_ERR_ARG, the rule in st_last_error()): a null pointer; B, L <= 0; L % 4. */
+int st_denoise_input(unsigned seed, unsigned long long first_window, const float* x, const float* knobs_wc, int B, int L, float* x_noisy, void* stream);
 /* One training minibatch of the synthetic comp_4c task made on the device in ONE launch (st_feed.h; replaces
  * SynthAudioDataSet.gen_single_chunk, datasets.py:312-334, over audio.synth_input_sample, audio.py:296-334, chooser set
  * {0,1,2,4,6,7}, and compressor_4controls): per window the test signal, knobs = Beta(0.8, 0.8) - 0.5 (audio.py:20-21,
@@ -422,8 +439,18 @@ int st_synth_comp4c(unsigned seed, unsigned long long first_window, int B, int L
  *                 for K == 4 the window stream is st_synth_comp4c's, bit for bit;
  *   ST_FX_COMP    the envelope compressor of st_compressor, K == 3 (threshold, ratio, attack / release s); with scratch (and L % 64 == 0)
  *                 the generator leaves the dB signal there and a second launch runs the envelope scan.
- * Every window is a function of (seed, window index) only; knobs [B][K].  Wrong ids and knob counts are refused before any launch. */
-enum { ST_FX_COMP4C = 0, ST_FX_COMP = 1 };
+ *   ST_FX_LOWPASS the low-pass of st_lowpass, K == 1 (cutoff Hz): x is the clean window, y the last ysz samples of the filtered one.  The filter is
+ *                 odd in x, so the polarity flip is the compressors'.  knob_lo[0] / knob_hi[0] must satisfy 0 < lo <= hi < sr / 2;
+ *   ST_FX_DENOISE audio.Denoise (audio.py:558-571), K == 1 (strength): y is the last ysz samples of the CLEAN window and x leaves with the noise
+ *                 of st_denoise_input added (the same bits for the same seed, window, clean x and strength).  0 <= lo <= hi is required.
+ * The window's draws do not depend on the effect: all four knob draws are made whatever K is, so the clean signal of window w of the stream `seed`
+ * is, bit for bit, the x ST_FX_COMP4C produces for the same (seed, w, chooser, augment).  ST_FX_LOWPASS and ST_FX_DENOISE have no second-launch
+ * form: st_synth_effect_scratch_floats answers for them only what the 1/f noise of windows beyond 8192 samples needs (0 up to 8192 samples,
+ * where scratch may be NULL).  Their world knob is lo + (knob + 0.5) * (hi - lo) in float32 with every step rounded (what Effect.knobs_wc gives
+ * in float32): st_lowpass / st_denoise_input on the feed's x (clean x) and that knob reproduce the feed's y (x) bit for bit.
+ * Every window is a function of (seed, window index) only; knobs [B][K].  Wrong ids, knob counts and (for the two one-knob effects, whose ranges
+ * are host arrays) knob ranges are refused before any launch (ST_ERR_ARG, the rule in st_last_error()). */
+enum { ST_FX_COMP4C = 0, ST_FX_COMP = 1, ST_FX_LOWPASS = 2, ST_FX_DENOISE = 3 };
 size_t st_synth_effect_scratch_floats(int effect, int B, int L);
 int st_synth_effect(int effect, unsigned seed, unsigned long long first_window, int B, int L, int ysz, int K, float sr,
                     const float* knob_lo, const float* knob_hi, int augment, int chooser, const float* pink_in,

@@ -59,6 +59,8 @@ SIGNATURES = {
     "st_ae_acts": (_i, [_D, _p, _p, _p, _i, _p, _p]),
     "st_compressor_4c": (_i, [_p, _p, C.c_float, C.c_int, C.c_int, C.c_int, _p, _p]),
     "st_compressor": (_i, [_p, _p, C.c_float, C.c_int, C.c_int, C.c_int, _p, _p]),
+    "st_lowpass": (_i, [_p, _p, C.c_float, C.c_int, C.c_int, C.c_int, _p, _p]),
+    "st_denoise_input": (_i, [C.c_uint, C.c_ulonglong, _p, _p, C.c_int, C.c_int, _p, _p]),
     "st_synth_comp4c_scratch_floats": (C.c_size_t, [_i, _i]),
     "st_synth_comp4c": (_i, [C.c_uint, C.c_ulonglong, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float),
                              C.c_int, C.c_int, _p, _p, _p, _p, _p, _p]),
@@ -126,7 +128,7 @@ SIGNATURES = {
 }
 
 # effect ids of st_synth_effect (include/signaltrain_hip.h ST_FX_*)
-FX_COMP4C, FX_COMP = 0, 1
+FX_COMP4C, FX_COMP, FX_LOWPASS, FX_DENOISE = 0, 1, 2, 3
 # sample formats of st_file_feed's audio pools (include/signaltrain_hip.h ST_PCM_*)
 PCM_F32, PCM_S16 = 0, 1
 

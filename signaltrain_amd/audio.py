@@ -1,7 +1,8 @@
 """Effects and audio files -- the parts of signaltrain/audio.py the training driver needs: the Effect classes (:449-537, knob names / ranges,
 normalised <-> world knob coordinates), the compressor target effects (compressor_4controls :380-426: on the GPU through st_compressor_4c /
 st_synth_effect, on the host through the gcc-built helper for file datasets; compressor :349-371: st_compressor / st_synth_effect, and a
-numpy / scipy restatement on the host), wav reading / writing (:207-262) and file-defined effects
+numpy / scipy restatement on the host), LowPass (:610-625: st_lowpass / st_synth_effect, scipy on the host) and Denoise (:558-571: the noisy signal
+is the input, st_denoise_input / st_synth_effect), wav reading / writing (:207-262) and file-defined effects
 (:624-670).  The synthetic test signals themselves are generated on the GPU (csrc/st_feed.h, audio_device.py); their numpy restatement lives
 on the checker side (oracle/host_audio.py)."""
 import ctypes as C
@@ -67,6 +68,14 @@ def compressor(x, thresh=-24.0, ratio=2.0, attackrel=0.045, sr=44100.0):
     return (x * np.power(10.0, (out - e) / 20)).astype(np.float32)
 
 
+def lowpass(x, cutoff, sr=44100.0, order=3):
+    """audio.py:618-625 (the `lowpass` effect): scipy's Butterworth low-pass at cutoff / (sr / 2) of Nyquist run by lfilter from a zero state, as
+    the reference calls them, in float64; the result rounded to float32 (the training target's type).  The device form is st_lowpass."""
+    from scipy.signal import butter, lfilter
+    b, a = butter(order, float(cutoff) / (0.5 * float(sr)), btype='low', analog=False)
+    return lfilter(b, a, np.asarray(x, dtype=np.float32)).astype(np.float32)
+
+
 def _device_effect(fn, effect, x, kw, y_size):
     """y [B, y_size] of the library's effect `fn` (st_compressor_4c / st_compressor) on device tensors x [B, L] with world-coordinate knobs kw [B, K]."""
     import ctypes as C
@@ -84,8 +93,10 @@ def _device_effect(fn, effect, x, kw, y_size):
 
 class Effect:
     """audio.py:449-480.  feed_fx: the st_synth_effect id (_lib.FX_*) of the library's fused device feed for this effect, None if there is none;
-    feed_ranges(): the four (low, high) knob rows that feed takes (knobs past len(knob_ranges) are fixed at their low end)."""
+    feed_ranges(): the four (low, high) knob rows that feed takes (knobs past len(knob_ranges) are fixed at their low end);
+    makes_input: the effect makes the item's input itself (Denoise) -- its go_device returns (y, x_new) and takes seed=, the noise stream."""
     feed_fx = None
+    makes_input = False
 
     def __init__(self, sr=44100.0, dtype=np.float32):
         self.name = 'Generic Effect'; self.knob_names = ['knob']
@@ -159,6 +170,62 @@ class Compressor_4c(Effect):
         if x.device.type != "cuda":
             raise RuntimeError("Compressor_4c.go_device needs ROCm device tensors")
         return _device_effect("st_compressor_4c", self, x, _knobs_wc_device(self.knob_ranges, knobs_nn, x.device), y_size)
+
+
+class LowPass(Effect):
+    """audio.py:610-625: a third-order Butterworth low-pass with the cutoff (Hz) as its knob."""
+    feed_fx = 2                                   # _lib.FX_LOWPASS
+
+    def __init__(self, **kwargs):
+        super().__init__(**kwargs)
+        self.name = 'LowPass'
+        self.knob_names = ['cutoff']
+        self.knob_ranges = np.array([[10, 2000]])
+
+    def go_wc(self, x, knobs_w, order=3):
+        return lowpass(x, knobs_w[0], sr=self.sr, order=order), x
+
+    def go_device(self, x, knobs_nn, y_size=None):
+        """Batched effect on the GPU (st_lowpass): x [B,L] and knobs_nn [B,1] in [-.5,.5] as device tensors -> y [B,y_size]
+        (the last y_size samples).  No CPU fallback."""
+        if x.device.type != "cuda":
+            raise RuntimeError("LowPass.go_device needs ROCm device tensors")
+        return _device_effect("st_lowpass", self, x, _knobs_wc_device(self.knob_ranges, knobs_nn, x.device), y_size)
+
+
+class Denoise(Effect):
+    """audio.py:558-571: uniform noise of amplitude `strength` is added to the signal and the pair is swapped -- the clean signal is the target,
+    the noisy one the input (is_inverse), so the model learns to remove noise by a tunable amount.  go / go_wc / go_device return
+    (target, input) like every effect; here the input is NOT the x that came in."""
+    feed_fx = 3                                   # _lib.FX_DENOISE
+    makes_input = True
+
+    def __init__(self, **kwargs):
+        super().__init__(**kwargs)
+        self.name = 'Denoise'
+        self.knob_names = ['strength']
+        self.knob_ranges = np.array([[0.0, 0.5]])
+        self.is_inverse = True
+
+    def go_wc(self, x, knobs_w):
+        return x, x + (knobs_w[0] * (2 * np.random.random(x.shape[0]) - 1)).astype(x.dtype, copy=False)
+
+    def go_device(self, x, knobs_nn, y_size=None, seed=None, first_window=0):
+        """(y, x_noisy) on the GPU: y [B,y_size] = the last y_size samples of the clean x [B,L], x_noisy [B,L] = x plus the noise of
+        st_denoise_input at strength knobs_wc(knobs_nn [B,1]), rows = windows first_window ... of the noise stream `seed` (None: drawn from
+        numpy's global generator, so it follows np.random.seed of the run).  No CPU fallback."""
+        import torch
+        from . import _lib
+        if x.device.type != "cuda":
+            raise RuntimeError("Denoise.go_device needs ROCm device tensors")
+        x = x.to(torch.float32).contiguous(); B, L = x.shape
+        kw = _knobs_wc_device(self.knob_ranges, knobs_nn, x.device)
+        seed = int(np.random.randint(0, 2 ** 31 - 1)) if seed is None else int(seed)
+        xn = torch.empty_like(x)
+        with torch.cuda.device(x.device):
+            _lib.check(_lib.load().st_denoise_input(seed, int(first_window), _lib.ptr(x), _lib.ptr(kw), B, L, _lib.ptr(xn),
+                                                    C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)), "st_denoise_input")
+        return x[:, L - (L if y_size is None else int(y_size)):].contiguous(), xn
 
 
 class Compressor_4c_Large(Compressor_4c):

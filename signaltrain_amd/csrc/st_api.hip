@@ -1950,15 +1950,36 @@ extern "C" int st_compressor(const float* x, const float* knobs_wc, float sr, in
     ST_LAUNCHED("compressor_env"); return ST_OK;
 }
 
+// audio.LowPass (audio.py:610-625): the third-order Butterworth low-pass as a scan over the filter's modes (st_filter.h), one workgroup per window
+extern "C" int st_lowpass(const float* x, const float* knobs_wc, float sr, int B, int L, int ysz, float* y, void* stream)
+{
+    ST_REQ(x && knobs_wc && y, "st_lowpass: null pointer");
+    ST_REQ(B > 0 && L > 0 && ysz > 0 && ysz <= L && sr > 0.f, "st_lowpass: bad sizes (B=%d L=%d ysz=%d): 0 < ysz <= L and sr > 0 are required", B, L, ysz);
+    ST_REQ(L % 4 == 0, "st_lowpass: L = %d is not a multiple of 4", L);
+    hipLaunchKernelGGL(stm::lowpass_kernel, dim3(B), dim3(256), 0, st_stream(stream), x, knobs_wc, sr, L, ysz, y);
+    ST_LAUNCHED("lowpass"); return ST_OK;
+}
+// audio.Denoise's input (audio.py:571) for clean windows the caller brings: the noise stream of the feed (stf::denoise_add)
+extern "C" int st_denoise_input(unsigned seed, unsigned long long first_window, const float* x, const float* knobs_wc, int B, int L, float* x_noisy, void* stream)
+{
+    ST_REQ(x && knobs_wc && x_noisy, "st_denoise_input: null pointer");
+    ST_REQ(B > 0 && L > 0, "st_denoise_input: bad sizes (B=%d L=%d)", B, L);
+    ST_REQ(L % 4 == 0, "st_denoise_input: L = %d is not a multiple of 4", L);
+    const int chunks = (L / 4 + 255) / 256;
+    hipLaunchKernelGGL(stf::denoise_input_kernel, dim3(B, chunks < 65535 ? chunks : 65535), dim3(256), 0, st_stream(stream), seed, first_window, x, knobs_wc, L, x_noisy);
+    ST_LAUNCHED("denoise_input"); return ST_OK;
+}
+
 // scratch of st_synth_effect for the full-featured path: [gain curve (ST_FX_COMP: dB signal) B * L | world knobs 4 B] and, for power-of-two windows beyond the in-LDS FFT
 // (8192 < L <= 65536), [1/f noise B * L | per-window peaks | four-step FFT buffer 2 * min(B, 1024) * L]
 static const int FEED_FFT_SUB = 1024;      // windows per pass-1 / pass-2 launch pair of the long-window noise (a launch pair costs ~50 us whatever its size: few, large ones)
 static bool feed_long_fft(int L) { return L > stf::FFT_MAX && (L & (L - 1)) == 0 && L / stf::PL_N1 <= 256; }
-static bool feed_effect_ok(int effect) { return effect == ST_FX_COMP4C || effect == ST_FX_COMP; }
+static bool feed_effect_ok(int effect) { return effect == ST_FX_COMP4C || effect == ST_FX_COMP || effect == ST_FX_LOWPASS || effect == ST_FX_DENOISE; }
+static bool feed_effect_splits(int effect) { return effect == ST_FX_COMP4C || effect == ST_FX_COMP; }      // has a lane-per-window / second-launch form through the scratch
 extern "C" size_t st_synth_effect_scratch_floats(int effect, int B, int L)
 {
     if (!feed_effect_ok(effect) || B <= 0 || L <= 0) return 0;
-    size_t n = (size_t)B * (L + 4);      // both effects: [gain curve or dB signal B * L | world knobs 4 B]
+    size_t n = feed_effect_splits(effect) ? (size_t)B * (L + 4) : 0;      // the compressors: [gain curve or dB signal B * L | world knobs 4 B]; ST_FX_LOWPASS / ST_FX_DENOISE: only the long windows' noise
     if (feed_long_fft(L)) n += (size_t)B * L + (size_t)st_round_up(B, 64) + (size_t)2 * (B < FEED_FFT_SUB ? B : FEED_FFT_SUB) * L;
     return n;
 }
@@ -1977,15 +1998,22 @@ static int feed_launch(const stf::FeedArgs& a, int B, size_t lds, void* stream)
         }
     }
     hipLaunchKernelGGL(stf::synth_feed_kernel<FX>, dim3(B), dim3(256), lds, st_stream(stream), a);
-    ST_LAUNCHED(FX == ST_FX_COMP ? "synth_comp" : "synth_comp4c"); return ST_OK;
+    ST_LAUNCHED(FX == ST_FX_COMP ? "synth_comp" : FX == ST_FX_LOWPASS ? "synth_lowpass" : FX == ST_FX_DENOISE ? "synth_denoise" : "synth_comp4c"); return ST_OK;
 }
 extern "C" int st_synth_effect(int effect, unsigned seed, unsigned long long first_window, int B, int L, int ysz, int K, float sr,
                                const float* knob_lo, const float* knob_hi, int augment, int chooser, const float* pink_in,
                                float* x, float* y, float* knobs, float* scratch, void* stream)
 {
-    ST_REQ(feed_effect_ok(effect), "st_synth_effect: effect %d is not an ST_FX_* id (ST_FX_COMP4C = 0, ST_FX_COMP = 1)", effect);
+    ST_REQ(feed_effect_ok(effect), "st_synth_effect: effect %d is not an ST_FX_* id (ST_FX_COMP4C = 0, ST_FX_COMP = 1, ST_FX_LOWPASS = 2, ST_FX_DENOISE = 3)", effect);
     ST_REQ(effect != ST_FX_COMP4C || (K >= 1 && K <= 4), "st_synth_effect: ST_FX_COMP4C takes 1 to 4 knobs, not K=%d", K);
     ST_REQ(effect != ST_FX_COMP || K == 3, "st_synth_effect: ST_FX_COMP takes 3 knobs (threshold, ratio, attack/release), not K=%d", K);
+    ST_REQ(effect != ST_FX_LOWPASS || K == 1, "st_synth_effect: ST_FX_LOWPASS takes 1 knob (cutoff Hz), not K=%d", K);
+    ST_REQ(effect != ST_FX_DENOISE || K == 1, "st_synth_effect: ST_FX_DENOISE takes 1 knob (strength), not K=%d", K);
+    // the one-knob effects' ranges (host arrays): checked as soon as they are there, before the device pointers
+    ST_REQ(effect != ST_FX_LOWPASS || !knob_lo || !knob_hi || (knob_lo[0] > 0.f && knob_lo[0] <= knob_hi[0] && knob_hi[0] < 0.5f * sr),
+           "st_synth_effect: ST_FX_LOWPASS needs a cutoff range with 0 < lo <= hi < sr / 2 (lo=%g hi=%g sr=%g)", knob_lo[0], knob_hi[0], sr);
+    ST_REQ(effect != ST_FX_DENOISE || !knob_lo || !knob_hi || (knob_lo[0] >= 0.f && knob_lo[0] <= knob_hi[0]),
+           "st_synth_effect: ST_FX_DENOISE needs a strength range with 0 <= lo <= hi (lo=%g hi=%g)", knob_lo[0], knob_hi[0]);
     ST_REQ(x && y && knobs && knob_lo && knob_hi, "st_synth_effect: null pointer");
     ST_REQ(B > 0 && L > 0 && ysz > 0 && ysz <= L && sr > 0.f, "st_synth_effect: bad sizes (B=%d L=%d ysz=%d K=%d)", B, L, ysz, K);
     ST_REQ(chooser == -1 || chooser == 0 || chooser == 1 || chooser == 2 || chooser == 4 || chooser == 6 || chooser == 7 || chooser == 100, "st_synth_effect: signal family %d is not built (the compressor's set is 0,1,2,4,6,7)", chooser);
@@ -1997,11 +2025,11 @@ extern "C" int st_synth_effect(int effect, unsigned seed, unsigned long long fir
     a.x = x; a.y = y; a.knobs = knobs; a.pink_in = pink_in; a.pink_peak = nullptr; a.seed = seed; a.first = first_window;
     a.L = L; a.ysz = ysz; a.K = K; a.sr = sr; a.augment = augment; a.chooser = chooser;
     for (int k = 0; k < 4; ++k) { a.lo[k] = knob_lo[k]; a.hi[k] = knob_hi[k]; }
-    const bool split = scratch && L % 64 == 0;
+    const bool split = scratch && L % 64 == 0 && feed_effect_splits(effect);
     a.gc = split ? scratch : nullptr; a.kw = split ? scratch + (size_t)B * L : nullptr;
     if (long_fft) {
         // the window's 1/f noise by the library's own four-step inverse FFT (st_feed.h pink_long_pass1 / 2), 1024 windows at a time through the FFT buffer
-        float* pink = scratch + (size_t)B * (L + 4);
+        float* pink = scratch + (feed_effect_splits(effect) ? (size_t)B * (L + 4) : 0);
         float* peak = pink + (size_t)B * L;
         float2* fbuf = reinterpret_cast<float2*>(peak + st_round_up(B, 64));
         const int N2 = L / stf::PL_N1;
@@ -2016,7 +2044,10 @@ extern "C" int st_synth_effect(int effect, unsigned seed, unsigned long long fir
     }
     // dynamic LDS: the in-LDS FFT's buffer, else the in-kernel effect's (compressor_window's float[COMP_CH] holds the envelope scan's EnvLds as well)
     static_assert(sizeof(stm::EnvLds) <= (size_t)stm::COMP_CH * sizeof(float), "the envelope scan's LDS must fit the in-kernel effect's buffer");
+    static_assert(sizeof(stm::LpLds) <= (size_t)stm::COMP_CH * sizeof(float), "the low-pass scan's LDS must fit the in-kernel effect's buffer");
     const size_t lds = a.pink_in ? (split ? 0 : (size_t)stm::COMP_CH * sizeof(float)) : (size_t)stf::FFT_MAX * sizeof(float2);
+    if (effect == ST_FX_LOWPASS) return feed_launch<ST_FX_LOWPASS>(a, B, lds, stream);
+    if (effect == ST_FX_DENOISE) return feed_launch<ST_FX_DENOISE>(a, B, lds, stream);
     if (effect == ST_FX_COMP) {
         ST_TRY(feed_launch<ST_FX_COMP>(a, B, lds, stream));
         if (split) {

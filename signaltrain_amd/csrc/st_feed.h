@@ -12,12 +12,15 @@
 //   effect the 4-control compressor on the finished window (stm::compressor_window: parallel gain computer, sequential attack / release
 //          smoother in one lane, parallel apply) -> the last ysz samples; or (ST_FX_COMP) the envelope compressor of audio.py:349-371, whose
 //          linear envelope runs as a parallel scan (stm::env_compressor_window).  1 <= K <= 4 knobs: the ones past K are fixed at their low end.
+//          ST_FX_LOWPASS (audio.py:610-625): the third-order Butterworth low-pass as a scan over the filter's modes (stm::lowpass_window, st_filter.h).
+//          ST_FX_DENOISE (audio.py:558-571): the target is the clean window's tail and x leaves with strength * (2u - 1) added (denoise_add).
 // Output contract: x [B][L], y [B][ysz], knobs [B][K] in [-0.5, 0.5] (float32), as the reference's collated batch (train.py:104-120 casts y to float).
 // Parity is DISTRIBUTIONAL (another generator than numpy's): tests compare per-family peak ranges, the even symmetry and 1/f slope of the noise,
 // the box structure, the Beta(0.8, 0.8) law, and the compressor against golden G9 through the same device function.
 #pragma once
 #include "st_common.h"
 #include "st_misc.h"
+#include "st_filter.h"
 
 namespace stf {
 
@@ -46,6 +49,23 @@ struct Draw {              // sequential scalar draws of one window (every threa
 // per-sample streams: value n of stream s of the window
 __device__ __forceinline__ float su01(const unsigned key, const unsigned s, const unsigned n) { return u01(mix32(mix32(key ^ (0xA511E9B3u * (s + 1u))) + 0x9E3779B9u * n)); }
 
+// The Denoise effect's input (audio.py:571): clean sample v of index n of the window `key` plus strength * (2u - 1), u = value n of stream 11 of the
+// window (streams 3, 5 and 7 belong to the signals).  The noise is formed and added in float32, each step rounded on its own, as the reference
+// casts its noise to float32 before the sum: contraction is switched off here (HIP's __fmul_rn / __fadd_rn are plain operators and would be fused
+// into one FMA with a single rounding), so x - clean is the float32 noise to one rounding of the sum, in the feed and in st_denoise_input alike.
+__device__ __forceinline__ float denoise_add(const unsigned key, const unsigned n, const float strength, const float v)
+{
+#pragma clang fp contract(off)
+    const float noise = strength * (2.f * su01(key, 11u, n) - 1.f);
+    return v + noise;
+}
+// Effect.knobs_wc in float32 with every step rounded (what torch gives for float32 tensors): lo + (knob + 0.5) * (hi - lo)
+__device__ __forceinline__ float world_knob_f32(const float lo, const float hi, const float kn)
+{
+#pragma clang fp contract(off)
+    const float t = (kn + 0.5f) * (hi - lo);
+    return lo + t;
+}
 struct FeedArgs {
     float* x; float* y; float* knobs;       // outputs
     const float* pink_in;                   // [B][L] 1/f noise for windows longer than the in-kernel FFT handles (else NULL): unit-peak from the caller, or
@@ -106,6 +126,21 @@ __device__ __forceinline__ int feed_family(Draw& d, const int chooser)
 __device__ __forceinline__ unsigned feed_key(const unsigned seed, const unsigned long long w)
 {
     return mix32(seed ^ mix32((unsigned)w + 1u) ^ mix32((unsigned)(w >> 32) + 0x51ED27u));
+}
+// st_denoise_input: x_noisy [B][L] = denoise_add of x [B][L] (may be the same buffer: each sample is read and written by one thread)
+__global__ void __launch_bounds__(256)
+denoise_input_kernel(const unsigned seed, const unsigned long long first, const float* x, const float* __restrict__ knobs_wc, const int L, float* x_noisy)
+{
+    const int b = blockIdx.x;
+    const unsigned key = feed_key(seed, first + (unsigned long long)b);
+    const float sgth = knobs_wc[b];
+    for (int n4 = blockIdx.y * 256 + threadIdx.x; n4 < L / 4; n4 += gridDim.y * 256) {
+        const size_t o = (size_t)b * L + 4 * (size_t)n4;
+        const unsigned n = 4u * (unsigned)n4;
+        float4 v = *reinterpret_cast<const float4*>(x + o);
+        v = make_float4(denoise_add(key, n, sgth, v.x), denoise_add(key, n + 1u, sgth, v.y), denoise_add(key, n + 2u, sgth, v.z), denoise_add(key, n + 3u, sgth, v.w));
+        *reinterpret_cast<float4*>(x_noisy + o) = v;
+    }
 }
 // G independent in-place inverse FFTs of length n = 2^logn in LDS (a[g * n + i], input stored bit-reversed), 256 threads; tw[k] = e^{2 pi i k / n}, k < n / 2
 __device__ __forceinline__ void ifft_batch_lds(float2* a, const float2* tw, const int n, const int logn, const int G)
@@ -214,6 +249,8 @@ synth_feed_kernel(const FeedArgs a)
     float kn[4], kw[4];
     for (int k = 0; k < 4; ++k) { kn[k] = d.beta(0.8f) - 0.5f; kw[k] = a.lo[k] + (kn[k] + 0.5f) * (a.hi[k] - a.lo[k]); }
     for (int k = a.K; k < 4; ++k) kw[k] = a.lo[k];                   // K < 4: the remaining knobs are fixed settings (all four are drawn: one stream for every K)
+    if (FX == ST_FX_LOWPASS || FX == ST_FX_DENOISE)                  // the one knob as float32 Effect.knobs_wc gives it, every step rounded: st_lowpass / st_denoise_input
+        kw[0] = world_knob_f32(a.lo[0], a.hi[0], kn[0]);                                             // on (x, these knobs) reproduce the feed bit for bit
     // randsine (audio.py:96-104)
     const int s_n = d.randint(1, 3);
     float s_amp[2], s_frq[2], s_t0[2];
@@ -292,7 +329,17 @@ synth_feed_kernel(const FeedArgs a)
                 if (pin) { pk = *reinterpret_cast<const float4*>(pin + n); if (a.pink_peak) { pk.x *= inv_peak; pk.y *= inv_peak; pk.z *= inv_peak; pk.w *= inv_peak; } }
                 else pk = make_float4(fa[n].x * inv_peak, fa[n + 1].x * inv_peak, fa[n + 2].x * inv_peak, fa[n + 3].x * inv_peak);
             }
-            const float4 v = make_float4(sample(n, pk.x), sample(n + 1, pk.y), sample(n + 2, pk.z), sample(n + 3, pk.w));
+            float4 v = make_float4(sample(n, pk.x), sample(n + 1, pk.y), sample(n + 2, pk.z), sample(n + 3, pk.w));
+            if (FX == ST_FX_DENOISE) {                               // the target is the clean tail, the input leaves with the noise on it
+                float* __restrict__ yb = a.y + (size_t)b * a.ysz;
+                const int j = n - (L - a.ysz);
+                if (j >= 0) yb[j] = v.x;
+                if (j + 1 >= 0) yb[j + 1] = v.y;
+                if (j + 2 >= 0) yb[j + 2] = v.z;
+                if (j + 3 >= 0) yb[j + 3] = v.w;
+                v = make_float4(denoise_add(key, (unsigned)n, kw[0], v.x), denoise_add(key, (unsigned)n + 1u, kw[0], v.y),
+                                denoise_add(key, (unsigned)n + 2u, kw[0], v.z), denoise_add(key, (unsigned)n + 3u, kw[0], v.w));
+            }
             *reinterpret_cast<float4*>(xb + n) = v;
             if (gcb) {
                 if (FX == ST_FX_COMP) *reinterpret_cast<float4*>(gcb + n) = make_float4(stm::env_db(v.x), stm::env_db(v.y), stm::env_db(v.z), stm::env_db(v.w));
@@ -303,18 +350,27 @@ synth_feed_kernel(const FeedArgs a)
     } else {
         for (int n = threadIdx.x; n < L; n += 256) {
             const float pk = want_pink ? (pin ? (a.pink_peak ? pin[n] * inv_peak : pin[n]) : fa[n].x * inv_peak) : 0.f;
-            const float v = sample(n, pk);
+            float v = sample(n, pk);
+            if (FX == ST_FX_DENOISE) {
+                if (n >= L - a.ysz) a.y[(size_t)b * a.ysz + n - (L - a.ysz)] = v;
+                v = denoise_add(key, (unsigned)n, kw[0], v);
+            }
             xb[n] = v;
             if (gcb) gcb[n] = FX == ST_FX_COMP ? stm::env_db(v) : stm::comp_gain_curve(v, (double)kw[0], (double)kw[1]);
         }
     }
     if (threadIdx.x == 0) { for (int k = 0; k < 4; ++k) if (k < a.K) a.knobs[(size_t)b * a.K + k] = kn[k]; }
+    if (FX == ST_FX_DENOISE) return;
     if (a.gc) {                                                      // workgroup-uniform: the effect finishes in the next launches (comp_smooth_kernel +
         if (threadIdx.x == 0) { for (int k = 0; k < 4; ++k) a.kw[(size_t)b * 4 + k] = kw[k]; }      // comp_apply_kernel, or compressor_env_kernel)
         return;
     }
     __threadfence_block();
     __syncthreads();                                                 // the window is complete (and the FFT buffer is dead)
+    if (FX == ST_FX_LOWPASS) {                                       // the Butterworth low-pass (audio.py:610-625), a scan over the filter's modes
+        stm::lowpass_window(xb, a.y + (size_t)b * a.ysz, stm::lowpass_coef((double)kw[0], (double)a.sr), L, a.ysz, reinterpret_cast<stm::LpLds*>(feed_lds));
+        return;
+    }
     if (FX == ST_FX_COMP) {                                          // the envelope compressor (audio.py:349-371), a scan over the window
         stm::env_compressor_window(xb, nullptr, a.y + (size_t)b * a.ysz, (double)kw[0], (double)kw[1], stm::env_coef((double)kw[2], (double)a.sr),
                                    L, a.ysz, reinterpret_cast<stm::EnvLds*>(feed_lds));
