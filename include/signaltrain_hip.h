@@ -245,7 +245,8 @@ size_t st_wgrad_ws_floats(const st_dims* d);
 int st_norm_partials(const st_dims* d);
 
 /* nn_proc.py:299-302 L1 clip (STFT tensors = first 4 tensors of the flat buffer) fused with
- * torch.optim.Adam.step (train.py:147).  scalars: device float[8] written by st_finalize_scalars. */
+ * torch.optim.Adam.step (train.py:147).  scalars: device float[8] written by st_finalize_scalars.
+ * st_clip_adam refuses, before any launch: a NULL pointer, n_total <= 0, n_stft < 0, either not a multiple of 4, n_stft > n_total, step < 1. */
 int st_finalize_scalars(const st_dims* d, const float* loss_partial, const float* reg_partial,
                         const float* norm_partial_a, const float* norm_partial_s, float inv_world,
                         float* scalars /* [0]=loss [1]=logcosh [2]=reg [3]=l1norm [4]=clip_coef [5]=overflow */, void* stream);

@@ -1190,7 +1190,11 @@ static int clip_adam_impl(float* params, float* grads, float* m, float* v, int64
                           const stm::FinArgs* fin, void* stream, bool dev_hyper = false)
 {
     ST_REQ(params && grads && m && v && scalars, "st_clip_adam: null pointer");
-    ST_REQ(n_total % 4 == 0 && n_stft % 4 == 0 && n_stft <= n_total && step >= 1, "st_clip_adam: bad sizes/step");
+    ST_REQ(n_total > 0, "st_clip_adam: n_total must be positive (an empty range would be a zero-block launch)");
+    ST_REQ(n_stft >= 0, "st_clip_adam: n_stft must not be negative");
+    ST_REQ(n_total % 4 == 0 && n_stft % 4 == 0, "st_clip_adam: n_total and n_stft must be multiples of 4");
+    ST_REQ(n_stft <= n_total, "st_clip_adam: n_stft exceeds n_total");
+    ST_REQ(step >= 1, "st_clip_adam: step must be at least 1");
     const double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);
     const float neg_step = (float)(-(double)lr / bc1);
     const float bc2s = (float)sqrt(bc2);
