@@ -23,6 +23,14 @@
 // windows (knobs are wave-uniform) and the pad columns of the AA matrix get written as zeros.
 // These kernels cover T <= 32, OT <= 16, K <= 16 (every padded dimension fixed at compile time); wider geometries run
 // layers 1 and 9 as GEMMs (st_ae_wide.h) around the INNER forms below.
+//
+// Where the shapes and offsets live.  The nine layers are written down ONCE, below: ae_outp / ae_inp (padded OUTp x INp, compile time) and AEShape (the
+// run-time out x in of the packed tensors, from T, OT, K; st_api.hip, st_ae32.h and ae_acts_kernel read it too).  AELayout<L0, L1> is the one prefix sum that
+// places the forward images, biases and dgrad images of a layer range in LDS: CL is the full layout [0, 9), the split backward's CP<1> / CP<2>
+// (st_ae_split.h) are [4, 9) and [0, 4); their named constants (CL::A3, CP<1>::B4, ...) are aliases of it and AETab is the same offsets as data.  Everything
+// around the inner loops takes a layout as an AETab: ae_params_scatter (parameters -> images), ae_load_nets (the prologue: issue, zero-fill, barrier, scatter;
+// ae_load_lds / ae_load_lds2 / ae_load_lds_tab are calls of it), ae_img_build (the same positions, gathered) and ae_partials_store (the backward kernels'
+// tail).  A layer shape, a padding rule or an image offset changes in that one place; tests/test_ae_weight_images_host.py holds its own typed-out copy.
 #pragma once
 #include "st_common.h"
 
@@ -61,21 +69,47 @@ __device__ __forceinline__ GroupWalk fwd_group_walk(const int ngroups, const int
     return GroupWalk{wave * G + b, ngroups, G * NW};
 }
 
-// Compile-time LDS layout (floats).  Padded shapes OUTp x INp per layer:
+// THE layer table.  Padded shapes OUTp x INp (compile time: they size the LDS images and the MFMA tile loops) ...
 //   l = 0: 64 x 32 (IN = T)   1: 32 x 64   2: 16 x 32   3: 16 x 16   4: 16 x 32 (IN = 16 + K)   5: 16 x 16   6: 32 x 16
 //   7: 64 x 32   8: 16 x 64 (OUT = OT)
-struct CL {
-    static constexpr int O0 = 64, O1 = 32, O2 = 16, O3 = 16, O4 = 16, O5 = 16, O6 = 32, O7 = 64, O8 = 16;
-    static constexpr int I0 = 32, I1 = 64, I2 = 32, I3 = 16, I4 = 32, I5 = 16, I6 = 16, I7 = 32, I8 = 64;
-    // forward images
-    static constexpr int A0 = 0, A1 = A0 + O0 * I0, A2 = A1 + O1 * I1, A3 = A2 + O2 * I2, A4 = A3 + O3 * I3, A5 = A4 + O4 * I4,
-                         A6 = A5 + O5 * I5, A7 = A6 + O6 * I6, A8 = A7 + O7 * I7, AEND = A8 + O8 * I8;
-    // biases
-    static constexpr int B0 = AEND, B1 = B0 + O0, B2 = B1 + O1, B3 = B2 + O2, B4 = B3 + O3, B5 = B4 + O4, B6 = B5 + O5,
-                         B7 = B6 + O6, B8 = B7 + O7, FWD_TOTAL = B8 + O8;          // what the forward kernels keep per autoencoder
-    // dgrad images (backward kernel only)
-    static constexpr int G0 = FWD_TOTAL, G1 = G0 + O0 * I0, G2 = G1 + O1 * I1, G3 = G2 + O2 * I2, G4 = G3 + O3 * I3, G5 = G4 + O4 * I4,
-                         G6 = G5 + O5 * I5, G7 = G6 + O6 * I6, G8 = G7 + O7 * I7, BWD_TOTAL = G8 + O8 * I8;
+__host__ __device__ constexpr int ae_outp(const int l) { constexpr int v[NL] = {64, 32, 16, 16, 16, 16, 32, 64, 16}; return v[l]; }
+__host__ __device__ constexpr int ae_inp(const int l) { constexpr int v[NL] = {32, 64, 32, 16, 32, 16, 16, 32, 64}; return v[l]; }
+// ... and the run-time shapes out(l) x in(l) of the packed tensors (nn_proc.py:28-126): the padded ones but for OT, T and the K knobs appended to the
+// code.  Host and device; every kernel and st_api.hip read them here.
+struct AEShape {
+    int T, OT, K;
+    __host__ __device__ constexpr int out(const int l) const { return l == NL - 1 ? OT : ae_outp(l); }
+    __host__ __device__ constexpr int in(const int l) const { return l == 0 ? T : l == 4 ? 16 + K : ae_inp(l); }
+};
+
+// LDS layout (floats) of the layers [L0, L1): [forward images][biases][dgrad images], each layer by layer -- ONE prefix sum over the table.
+// ao / bo / gi: offset of layer l's forward image / bias / dgrad image (0 outside the range); AETab: the same as data, for the routines below.
+struct AETab { int ao[NL], bo[NL], gi[NL], fwd_end, total; };
+template <int L0_, int L1_> struct AELayout {
+    static constexpr int L0 = L0_, L1 = L1_;
+    __host__ __device__ static constexpr int wsum(const int l) { int s = 0; for (int k = L0; k < l; ++k) s += ae_outp(k) * ae_inp(k); return s; }
+    __host__ __device__ static constexpr int bsum(const int l) { int s = 0; for (int k = L0; k < l; ++k) s += ae_outp(k); return s; }
+    __host__ __device__ static constexpr bool has(const int l) { return l >= L0 && l < L1; }
+    __host__ __device__ static constexpr int ao(const int l) { return has(l) ? wsum(l) : 0; }
+    __host__ __device__ static constexpr int bo(const int l) { return has(l) ? wsum(L1) + bsum(l) : 0; }
+    __host__ __device__ static constexpr int gi(const int l) { return has(l) ? wsum(L1) + bsum(L1) + wsum(l) : 0; }
+    __host__ __device__ static constexpr AETab tab()
+    {
+        AETab t{};
+        for (int l = 0; l < NL; ++l) { t.ao[l] = ao(l); t.bo[l] = bo(l); t.gi[l] = gi(l); }
+        t.fwd_end = wsum(L1) + bsum(L1); t.total = t.fwd_end + wsum(L1);
+        return t;
+    }
+};
+// The full layout, with the names the kernels read.  FWD_TOTAL: what the forward kernels keep per autoencoder; the dgrad images are the backward kernel's.
+struct CL : AELayout<0, NL> {
+    static constexpr int O0 = ae_outp(0), O1 = ae_outp(1), O2 = ae_outp(2), O3 = ae_outp(3), O4 = ae_outp(4), O5 = ae_outp(5), O6 = ae_outp(6), O7 = ae_outp(7), O8 = ae_outp(8);
+    static constexpr int I0 = ae_inp(0), I1 = ae_inp(1), I2 = ae_inp(2), I3 = ae_inp(3), I4 = ae_inp(4), I5 = ae_inp(5), I6 = ae_inp(6), I7 = ae_inp(7), I8 = ae_inp(8);
+    static constexpr int A0 = ao(0), A1 = ao(1), A2 = ao(2), A3 = ao(3), A4 = ao(4), A5 = ao(5), A6 = ao(6), A7 = ao(7), A8 = ao(8), AEND = wsum(NL);
+    static constexpr int B0 = bo(0), B1 = bo(1), B2 = bo(2), B3 = bo(3), B4 = bo(4), B5 = bo(5), B6 = bo(6), B7 = bo(7), B8 = bo(8), FWD_TOTAL = tab().fwd_end;
+    static constexpr int G0 = gi(0), G1 = gi(1), G2 = gi(2), G3 = gi(3), G4 = gi(4), G5 = gi(5), G6 = gi(6), G7 = gi(7), G8 = gi(8), BWD_TOTAL = tab().total;
+    static_assert(A3 == 4608 && A8 == 8192 && AEND == 9216 && B0 == 9216 && B8 == 9472 && FWD_TOTAL == 9488 && G0 == 9488 && G8 == 17680 && BWD_TOTAL == 18704,
+                  "the LDS offsets the kernels and the ready-made image block were laid out with");
     static_assert(FWD_TOTAL % 4 == 0 && BWD_TOTAL % 4 == 0, "16-byte aligned regions");
 };
 
@@ -85,26 +119,24 @@ struct CL {
 // trips -- ~15 us of a workgroup's life before its first MFMA, at one wave per SIMD nothing hides that.)  The LDS zero-fill
 // runs while the loads are in flight, then the values are scattered to their image positions.  Layers [l0, l1) only (the
 // wide path keeps 1..7).  The caller synchronises afterwards.
-constexpr int ae_max_elems(int l) { return l == 0 ? 64 * 32 : l == 1 ? 32 * 64 : l == 2 ? 16 * 32 : l == 3 ? 16 * 16 : l == 4 ? 16 * 32 :
-                                           l == 5 ? 16 * 16 : l == 6 ? 32 * 16 : l == 7 ? 64 * 32 : 16 * 64; }
+constexpr int ae_max_elems(int l) { return ae_outp(l) * ae_inp(l); }
 template <int NT>
 struct AEParamRegs { float v[NL][(64 * 32 + NT - 1) / NT]; float bv[NL]; };      // one thread's share of an autoencoder's parameters
 
-// (__host__ too, with ae_params_scatter and ae_img_build: tests/test_ae_weight_images_host.py runs the scatter and its inverse on the CPU)
+// (__host__ too, with ae_params_scatter, ae_partials_store and ae_img_build: tests/test_ae_weight_images_host.py runs them on the CPU)
 template <int NT>
 __host__ __device__ __forceinline__ void ae_params_issue(AEParamRegs<NT>& r, const float* __restrict__ ae, const AEOffsets& go,
                                                 const int T, const int OT, const int K, const int tid, const int l0, const int l1)
 {
-    const int out[NL] = {64, 32, 16, 16, 16, 16, 32, 64, OT};
-    const int in[NL] = {T, 64, 32, 16, 16 + K, 16, 16, 32, 64};
+    const AEShape sh{T, OT, K};
 #pragma unroll
     for (int l = 0; l < NL; ++l) {
         const bool on = l >= l0 && l < l1;
-        const int n = on ? out[l] * in[l] : 0;
+        const int n = on ? sh.out(l) * sh.in(l) : 0;
         const float* src = ae + go.w[l];
 #pragma unroll
         for (int u = 0; u < (ae_max_elems(l) + NT - 1) / NT; ++u) { const int e = tid + u * NT; r.v[l][u] = src[e < n ? e : 0]; }
-        r.bv[l] = ae[go.b[l] + (tid < out[l] ? tid : 0)];
+        r.bv[l] = ae[go.b[l] + (tid < sh.out(l) ? tid : 0)];
     }
 }
 // BF != 0 (16-bit operand kernels): the weight images are written ALREADY ROUNDED to bfloat16 / float16, packed into the first half of
@@ -120,21 +152,16 @@ template <int BF> __device__ __forceinline__ float st_half_to_float(const unsign
     if constexpr (BF == 2) { union { unsigned short u; _Float16 h; } p; p.u = b; return (float)p.h; }
     else return __uint_as_float((unsigned)b << 16);
 }
+// The scatter into the images of the layout `tab` (any AELayout<...>::tab(); the layers [l0, l1) must lie inside it).
 template <int NT, int BF = 0>
-__host__ __device__ __forceinline__ void ae_params_scatter(float* lds, const AEParamRegs<NT>& r, const int T, const int OT, const int K,
+__host__ __device__ __forceinline__ void ae_params_scatter(float* lds, const AETab& tab, const AEParamRegs<NT>& r, const int T, const int OT, const int K,
                                                   const int tid, const int l0, const int l1, const bool dgrad_images)
 {
-    const int out[NL] = {64, 32, 16, 16, 16, 16, 32, 64, OT};
-    const int in[NL] = {T, 64, 32, 16, 16 + K, 16, 16, 32, 64};
-    const int outp[NL] = {CL::O0, CL::O1, CL::O2, CL::O3, CL::O4, CL::O5, CL::O6, CL::O7, CL::O8};
-    const int inp[NL] = {CL::I0, CL::I1, CL::I2, CL::I3, CL::I4, CL::I5, CL::I6, CL::I7, CL::I8};
-    const int ao[NL] = {CL::A0, CL::A1, CL::A2, CL::A3, CL::A4, CL::A5, CL::A6, CL::A7, CL::A8};
-    const int bo[NL] = {CL::B0, CL::B1, CL::B2, CL::B3, CL::B4, CL::B5, CL::B6, CL::B7, CL::B8};
-    const int gi[NL] = {CL::G0, CL::G1, CL::G2, CL::G3, CL::G4, CL::G5, CL::G6, CL::G7, CL::G8};
+    const AEShape sh{T, OT, K};
 #pragma unroll
     for (int l = 0; l < NL; ++l) {
         const bool on = l >= l0 && l < l1;
-        const int IN = in[l], n = on ? out[l] * IN : 0, OP = outp[l], IP = inp[l];
+        const int IN = sh.in(l), n = on ? sh.out(l) * IN : 0, OP = ae_outp(l), IP = ae_inp(l);
 #pragma unroll
         for (int u = 0; u < (ae_max_elems(l) + NT - 1) / NT; ++u) {
             const int e = tid + u * NT;
@@ -142,49 +169,77 @@ __host__ __device__ __forceinline__ void ae_params_scatter(float* lds, const AEP
                 const int o = e / IN, i = e - o * IN;
                 if constexpr (BF) {
                     const unsigned short hb = st_half_bits<BF>(r.v[l][u]);
-                    reinterpret_cast<unsigned short*>(lds + ao[l])[(((i >> 2) * OP + o) << 2) + (i & 3)] = hb;
-                    if (dgrad_images) reinterpret_cast<unsigned short*>(lds + gi[l])[(((o >> 2) * IP + i) << 2) + (o & 3)] = hb;
+                    reinterpret_cast<unsigned short*>(lds + tab.ao[l])[(((i >> 2) * OP + o) << 2) + (i & 3)] = hb;
+                    if (dgrad_images) reinterpret_cast<unsigned short*>(lds + tab.gi[l])[(((o >> 2) * IP + i) << 2) + (o & 3)] = hb;
                 } else {
-                lds[ao[l] + (((i >> 2) * OP + o) << 2) + (i & 3)] = r.v[l][u];
-                if (dgrad_images) lds[gi[l] + (((o >> 2) * IP + i) << 2) + (o & 3)] = r.v[l][u];
+                lds[tab.ao[l] + (((i >> 2) * OP + o) << 2) + (i & 3)] = r.v[l][u];
+                if (dgrad_images) lds[tab.gi[l] + (((o >> 2) * IP + i) << 2) + (o & 3)] = r.v[l][u];
                 }
             }
         }
-        if (on && tid < out[l]) lds[bo[l] + tid] = r.bv[l];
+        if (on && tid < sh.out(l)) lds[tab.bo[l] + tid] = r.bv[l];
     }
+}
+// The load sequence, once: NN nets (one block of `tab` each, back to back) -- issue every load, zero-fill, barrier, scatter.  ablatable: a build with
+// ST_AE_ABLATE & 128 only zero-fills (ae_fwd_kernel / ae_bwd_kernel; the split kernels always load).
+template <int NT, int BF, int NN>
+__device__ __forceinline__ void ae_load_nets(float* lds, const AETab& tab, const float* const (&ae)[NN], const AEOffsets& go, const int T, const int OT, const int K,
+                                             const int tid, const int l0, const int l1, const bool dgrad_images, const bool ablatable)
+{
+    const int per = dgrad_images ? tab.total : tab.fwd_end;
+    if ((ST_AE_ABLATE & 128) && ablatable) { for (int e = tid; e < NN * per; e += NT) lds[e] = 0.f; return; }
+    AEParamRegs<NT> r[NN];
+#pragma unroll
+    for (int a = 0; a < NN; ++a) ae_params_issue<NT>(r[a], ae[a], go, T, OT, K, tid, l0, l1);
+    for (int e = tid; e < NN * per; e += NT) lds[e] = 0.f;
+    __syncthreads();
+#pragma unroll
+    for (int a = 0; a < NN; ++a) ae_params_scatter<NT, BF>(lds + a * per, tab, r[a], T, OT, K, tid, l0, l1, dgrad_images);
 }
 // One autoencoder (backward kernel: forward + dgrad images) ...
 template <int NT, int BF = 0>
 __device__ inline void ae_load_lds(float* lds, const float* __restrict__ ae, const AEOffsets& go, const int T, const int OT, const int K,
                                    const int tid, const int l0, const int l1, const bool dgrad_images)
 {
-    const int total = dgrad_images ? CL::BWD_TOTAL : CL::FWD_TOTAL;
-#if ST_AE_ABLATE & 128
-    for (int e = tid; e < total; e += NT) lds[e] = 0.f;
-#else
-    AEParamRegs<NT> r;
-    ae_params_issue<NT>(r, ae, go, T, OT, K, tid, l0, l1);
-    for (int e = tid; e < total; e += NT) lds[e] = 0.f;
-    __syncthreads();
-    ae_params_scatter<NT, BF>(lds, r, T, OT, K, tid, l0, l1, dgrad_images);
-#endif
+    const float* const nets[1] = {ae};
+    ae_load_nets<NT, BF, 1>(lds, CL::tab(), nets, go, T, OT, K, tid, l0, l1, dgrad_images, true);
 }
 // ... or both (forward kernels: two forward images CL::FWD_TOTAL floats apart), still one round trip.
 template <int NT, int BF = 0>
 __device__ inline void ae_load_lds2(float* lds, const float* __restrict__ ae_m, const float* __restrict__ ae_p, const AEOffsets& go,
                                     const int T, const int OT, const int K, const int tid, const int l0, const int l1)
 {
-#if ST_AE_ABLATE & 128
-    for (int e = tid; e < 2 * CL::FWD_TOTAL; e += NT) lds[e] = 0.f;
-#else
-    AEParamRegs<NT> rm, rp;
-    ae_params_issue<NT>(rm, ae_m, go, T, OT, K, tid, l0, l1);
-    ae_params_issue<NT>(rp, ae_p, go, T, OT, K, tid, l0, l1);
-    for (int e = tid; e < 2 * CL::FWD_TOTAL; e += NT) lds[e] = 0.f;
-    __syncthreads();
-    ae_params_scatter<NT, BF>(lds, rm, T, OT, K, tid, l0, l1, false);
-    ae_params_scatter<NT, BF>(lds + CL::FWD_TOTAL, rp, T, OT, K, tid, l0, l1, false);
-#endif
+    const float* const nets[2] = {ae_m, ae_p};
+    ae_load_nets<NT, BF, 2>(lds, CL::tab(), nets, go, T, OT, K, tid, l0, l1, false, true);
+}
+
+// The store pass of the backward kernels: the packed partial gradient of a workgroup (layout of the parameter block) from four per-wave gradient images
+// `stride` floats apart in LDS (dW_l as [o][INp] at tab.ao[l], db_l at tab.bo[l]), summed in the fixed order (0 + 1) + (2 + 3), for the layers [l0, l1);
+// bit l of have_mask clear: the layer's partial is written as zeros.  One unrolled pass: every layer's elements per thread are compile-time bounded, so the LDS
+// reads batch up and the index arithmetic folds (the first version zeroed the whole block, synchronised, then ran nine run-time loops with a run-time
+// division per element: 14-22 us per launch).
+template <int NT>
+__host__ __device__ __forceinline__ void ae_partials_store(float* base, const float* lds, const int stride, const AETab& tab, const AEOffsets& go,
+                                                           const int PG, const int T, const int OT, const int K, const int tid, const int l0, const int l1,
+                                                           const unsigned have_mask)
+{
+    auto sum4 = [&](int idx) { return (lds[idx] + lds[stride + idx]) + (lds[2 * stride + idx] + lds[3 * stride + idx]); };
+    const AEShape sh{T, OT, K};
+#pragma unroll
+    for (int l = 0; l < NL; ++l) {
+        if (l < l0 || l >= l1) continue;
+        const bool have = (have_mask >> l) & 1;
+        const int IN = sh.in(l), n = sh.out(l) * IN;
+#pragma unroll
+        for (int u = 0; u < (ae_max_elems(l) + NT - 1) / NT; ++u) {
+            const int e = tid + u * NT;
+            if (e < n) { const int o = e / IN, i = e - o * IN; base[go.w[l] + e] = have ? sum4(tab.ao[l] + o * ae_inp(l) + i) : 0.f; }
+        }
+        if (tid < sh.out(l)) base[go.b[l] + tid] = have ? sum4(tab.bo[l] + tid) : 0.f;
+        // alignment pads behind the weight and the bias tensor
+        { const int p0 = go.w[l] + n, np = go.b[l] - p0; if (tid < np) base[p0 + tid] = 0.f; }
+        { const int p0 = go.b[l] + sh.out(l), np = (l + 1 < NL ? go.w[l + 1] : PG) - p0; if (tid < np) base[p0 + tid] = 0.f; }
+    }
 }
 
 // Round 10: READY-MADE images (fused fp32 geometries).  The images above are the same for every workgroup of the forward and the backward kernel of a step, and
@@ -203,12 +258,8 @@ __host__ __device__ __forceinline__ float ae_freq_weight(const float expfac, con
 __host__ __device__ __forceinline__ void ae_img_build(const AEImgJob& j, const int p)
 {
     if (p >= j.n) return;
-    const int out[NL] = {64, 32, 16, 16, 16, 16, 32, 64, j.OT};
-    const int in[NL] = {j.T, 64, 32, 16, 16 + j.K, 16, 16, 32, 64};
-    const int outp[NL] = {CL::O0, CL::O1, CL::O2, CL::O3, CL::O4, CL::O5, CL::O6, CL::O7, CL::O8};
-    const int inp[NL] = {CL::I0, CL::I1, CL::I2, CL::I3, CL::I4, CL::I5, CL::I6, CL::I7, CL::I8};
-    const int ao[NL + 1] = {CL::A0, CL::A1, CL::A2, CL::A3, CL::A4, CL::A5, CL::A6, CL::A7, CL::A8, CL::AEND};
-    const int bo[NL + 1] = {CL::B0, CL::B1, CL::B2, CL::B3, CL::B4, CL::B5, CL::B6, CL::B7, CL::B8, CL::FWD_TOTAL};
+    const AEShape sh{j.T, j.OT, j.K};
+    constexpr AETab tab = CL::tab();
     float v = 0.f;
     const int q0 = p - 2 * CL::FWD_TOTAL;
     if (q0 >= 0 && q0 < j.FP) v = q0 < j.F ? ae_freq_weight(j.expfac, q0) : 0.f;
@@ -220,16 +271,16 @@ __host__ __device__ __forceinline__ void ae_img_build(const AEImgJob& j, const i
         if (!dg && q >= CL::AEND) {                                                      // biases
 #pragma unroll
             for (int l = 0; l < NL; ++l)
-                if (q >= bo[l] && q < bo[l + 1]) { const int o = q - bo[l]; if (o < out[l]) v = ae[j.go.b[l] + o]; }
+                if (q >= tab.bo[l] && q < tab.bo[l] + ae_outp(l)) { const int o = q - tab.bo[l]; if (o < sh.out(l)) v = ae[j.go.b[l] + o]; }
         } else {
 #pragma unroll
             for (int l = 0; l < NL; ++l)
-                if (q >= ao[l] && q < ao[l + 1]) {
-                    const int s = (q - ao[l]) >> 2, lo = (q - ao[l]) & 3;
+                if (q >= tab.ao[l] && q < tab.ao[l] + ae_max_elems(l)) {
+                    const int s = (q - tab.ao[l]) >> 2, lo = (q - tab.ao[l]) & 3;
                     // forward image: slot (i >> 2) * OUTp + o, element i & 3;  dgrad image: slot (o >> 2) * INp + i, element o & 3
-                    const int o = dg ? ((s / inp[l]) << 2) + lo : s % outp[l];
-                    const int i = dg ? s % inp[l] : ((s / outp[l]) << 2) + lo;
-                    if (o < out[l] && i < in[l]) v = ae[j.go.w[l] + o * in[l] + i];
+                    const int o = dg ? ((s / ae_inp(l)) << 2) + lo : s % ae_outp(l);
+                    const int i = dg ? s % ae_inp(l) : ((s / ae_outp(l)) << 2) + lo;
+                    if (o < sh.out(l) && i < sh.in(l)) v = ae[j.go.w[l] + o * sh.in(l) + i];
                 }
         }
     }
@@ -1401,31 +1452,9 @@ ae_bwd_kernel(const float* __restrict__ mag, const float* __restrict__ phs, cons
     db_flush<1, true>(dwl + CL::B4, rb5, g, c); db_flush<1, true>(dwl + CL::B5, rb6, g, c); db_flush<2, true>(dwl + CL::B6, rb7, g, c);
     db_flush<4, true>(dwl + CL::B7, rb8, g, c);
     __syncthreads();
-    auto sum4 = [&](int idx) { return (lds[idx] + lds[CL::FWD_TOTAL + idx]) + (lds[2 * CL::FWD_TOTAL + idx] + lds[3 * CL::FWD_TOTAL + idx]); };
-    // Packed partial gradient of this workgroup (layout of the parameter block).  One unrolled pass: every layer's elements per
-    // thread are compile-time bounded, so the LDS reads batch up and the index arithmetic folds (the first version zeroed the
-    // whole block, synchronised, then ran nine run-time loops with a run-time division per element: 14-22 us per launch).
-    float* base = ws + ((size_t)blockIdx.x * 2 + ae) * PG;
-    const int out[NL] = {64, 32, 16, 16, 16, 16, 32, 64, OT};
-    const int in[NL] = {T, 64, 32, 16, 16 + K, 16, 16, 32, 64};
-    const int inp[NL] = {CL::I0, CL::I1, CL::I2, CL::I3, CL::I4, CL::I5, CL::I6, CL::I7, CL::I8};
-    const int ao[NL] = {CL::A0, CL::A1, CL::A2, CL::A3, CL::A4, CL::A5, CL::A6, CL::A7, CL::A8};
-    const int bo[NL] = {CL::B0, CL::B1, CL::B2, CL::B3, CL::B4, CL::B5, CL::B6, CL::B7, CL::B8};
-    constexpr int NT = NW * 64;
-#pragma unroll
-    for (int l = 0; l < NL; ++l) {
-        const bool have = !INNER || (l >= 1 && l < 8);                  // INNER: layers 1 and 9 come from the GEMM path, their partials stay zero
-        const int IN = in[l], n = out[l] * IN;
-#pragma unroll
-        for (int u = 0; u < (ae_max_elems(l) + NT - 1) / NT; ++u) {
-            const int e = tid + u * NT;
-            if (e < n) { const int o = e / IN, i = e - o * IN; base[go.w[l] + e] = have ? sum4(ao[l] + o * inp[l] + i) : 0.f; }
-        }
-        if (tid < out[l]) base[go.b[l] + tid] = have ? sum4(bo[l] + tid) : 0.f;
-        // alignment pads behind the weight and the bias tensor
-        { const int p0 = go.w[l] + n, np = go.b[l] - p0; if (tid < np) base[p0 + tid] = 0.f; }
-        { const int p0 = go.b[l] + out[l], np = (l + 1 < NL ? go.w[l + 1] : PG) - p0; if (tid < np) base[p0 + tid] = 0.f; }
-    }
+    // INNER: layers 1 and 9 come from the GEMM path, their partials stay zero
+    ae_partials_store<NW * 64>(ws + ((size_t)blockIdx.x * 2 + ae) * PG, lds, CL::FWD_TOTAL, CL::tab(), go, PG, T, OT, K, tid, 0, NL,
+                               INNER ? 0x0FEu : 0x1FFu);
 }
 
 }  // namespace sta

@@ -41,8 +41,7 @@ template <int NT, int BF>
 __device__ __forceinline__ void ae32_load(float* lds, const float* __restrict__ ae, const AEOffsets& go, const int T, const int OT, const int K, const int tid)
 {
     static_assert(NT == 512, "one tile = 512 values = one value per thread");
-    const int out[NL] = {64, 32, 16, 16, 16, 16, 32, 64, OT};
-    const int in[NL] = {T, 64, 32, 16, 16 + K, 16, 16, 32, 64};
+    const AEShape sh{T, OT, K};
     const int mt_[NL] = {CL32::MT0, CL32::MT1, CL32::MT2, CL32::MT3, CL32::MT4, CL32::MT5, CL32::MT6, CL32::MT7, CL32::MT8};
     const int ks_[NL] = {CL32::KS0, CL32::KS1, CL32::KS2, CL32::KS3, CL32::KS4, CL32::KS5, CL32::KS6, CL32::KS7, CL32::KS8};
     const int lane = tid >> 3, j = tid & 7, h = lane >> 5, m = lane & 31;
@@ -56,20 +55,20 @@ __device__ __forceinline__ void ae32_load(float* lds, const float* __restrict__ 
 #pragma unroll
             for (int ks = 0; ks < ks_[l]; ++ks, ++t) {
                 const int o = 32 * mt + m, i = 16 * ks + sf;
-                const bool ok = o < out[l] && i < in[l];
-                v[t] = ae[go.w[l] + (ok ? o * in[l] + i : 0)];
+                const bool ok = o < sh.out(l) && i < sh.in(l);
+                v[t] = ae[go.w[l] + (ok ? o * sh.in(l) + i : 0)];
                 v[t] = ok ? v[t] : 0.f;
             }
     float bv[NL];
 #pragma unroll
-    for (int l = 0; l < NL; ++l) bv[l] = ae[go.b[l] + (tid < out[l] ? tid : 0)];
+    for (int l = 0; l < NL; ++l) bv[l] = ae[go.b[l] + (tid < sh.out(l) ? tid : 0)];
     unsigned short* tl = reinterpret_cast<unsigned short*>(lds);
 #pragma unroll
     for (t = 0; t < CL32::NTILES; ++t) tl[t * 512 + tid] = st_half_bits<BF>(v[t]);
     const int bo[NL] = {CL32::B0, CL32::B1, CL32::B2, CL32::B3, CL32::B4, CL32::B5, CL32::B6, CL32::B7, CL32::B8};
     const int bw[NL] = {64, 32, 32, 32, 32, 32, 32, 64, 32};
 #pragma unroll
-    for (int l = 0; l < NL; ++l) if (tid < bw[l]) lds[bo[l] + tid] = tid < out[l] ? bv[l] : 0.f;
+    for (int l = 0; l < NL; ++l) if (tid < bw[l]) lds[bo[l] + tid] = tid < sh.out(l) ? bv[l] : 0.f;
 }
 
 template <int BF> struct frag32 { typedef stg::st_bf16x8 type; };

@@ -19,24 +19,19 @@
 
 namespace sta {
 
-// Compact LDS layouts: forward images, biases and dgrad images of the layers of one half only.
-struct AETab { int ao[NL], bo[NL], gi[NL]; };
+// Compact LDS layouts: forward images, biases and dgrad images of the layers of one half only (AELayout, st_ae.h).
 template <int PART> struct CP;
-template <> struct CP<1> {                 // layers l = 4..8  (fnn_addknobs, fnn_dec4, fnn_dec3, fnn_dec2, fnn_dec)
-    static constexpr int L0 = 4, L1 = 9;
-    static constexpr int A4 = 0, A5 = A4 + CL::O4 * CL::I4, A6 = A5 + CL::O5 * CL::I5, A7 = A6 + CL::O6 * CL::I6, A8 = A7 + CL::O7 * CL::I7, AEND = A8 + CL::O8 * CL::I8;
-    static constexpr int B4 = AEND, B5 = B4 + CL::O4, B6 = B5 + CL::O5, B7 = B6 + CL::O6, B8 = B7 + CL::O7, FWD_END = B8 + CL::O8;
-    static constexpr int G4 = FWD_END, G5 = G4 + CL::O4 * CL::I4, G6 = G5 + CL::O5 * CL::I5, G7 = G6 + CL::O6 * CL::I6, G8 = G7 + CL::O7 * CL::I7, TOTAL = G8 + CL::O8 * CL::I8;
+template <> struct CP<1> : AELayout<4, 9> {                 // layers l = 4..8  (fnn_addknobs, fnn_dec4, fnn_dec3, fnn_dec2, fnn_dec)
+    static constexpr int A4 = ao(4), A5 = ao(5), A6 = ao(6), A7 = ao(7), A8 = ao(8), B4 = bo(4), B5 = bo(5), B6 = bo(6), B7 = bo(7), B8 = bo(8);
+    static constexpr int G4 = gi(4), G5 = gi(5), G6 = gi(6), G7 = gi(7), G8 = gi(8), FWD_END = tab().fwd_end, TOTAL = tab().total;
     static constexpr int SCR = 16 * SP + 2 * 4 * 320;          // per wave: Y rows + two 4-tile transpose scratches
-    __device__ static AETab tab() { return AETab{{0, 0, 0, 0, A4, A5, A6, A7, A8}, {0, 0, 0, 0, B4, B5, B6, B7, B8}, {0, 0, 0, 0, G4, G5, G6, G7, G8}}; }
+    static_assert(A4 == 0 && A8 == 3328 && B4 == 4352 && B8 == 4480 && FWD_END == 4496 && G4 == 4496 && G8 == 7824 && TOTAL == 8848, "the offsets the decoder half was laid out with");
 };
-template <> struct CP<2> {                 // layers l = 0..3  (fnn_enc, fnn_enc2, fnn_enc3, fnn_enc4)
-    static constexpr int L0 = 0, L1 = 4;
-    static constexpr int A0 = 0, A1 = A0 + CL::O0 * CL::I0, A2 = A1 + CL::O1 * CL::I1, A3 = A2 + CL::O2 * CL::I2, AEND = A3 + CL::O3 * CL::I3;
-    static constexpr int B0 = AEND, B1 = B0 + CL::O0, B2 = B1 + CL::O1, B3 = B2 + CL::O2, FWD_END = B3 + CL::O3;
-    static constexpr int G0 = FWD_END, G1 = G0 + CL::O0 * CL::I0, G2 = G1 + CL::O1 * CL::I1, G3 = G2 + CL::O2 * CL::I2, TOTAL = G3 + CL::O3 * CL::I3;
+template <> struct CP<2> : AELayout<0, 4> {                 // layers l = 0..3  (fnn_enc, fnn_enc2, fnn_enc3, fnn_enc4)
+    static constexpr int A0 = ao(0), A1 = ao(1), A2 = ao(2), A3 = ao(3), B0 = bo(0), B1 = bo(1), B2 = bo(2), B3 = bo(3);
+    static constexpr int G0 = gi(0), G1 = gi(1), G2 = gi(2), G3 = gi(3), FWD_END = tab().fwd_end, TOTAL = tab().total;
     static constexpr int SCR = 32 * SP + 2 * 4 * 320;          // per wave: V rows + two 4-tile transpose scratches
-    __device__ static AETab tab() { return AETab{{A0, A1, A2, A3, 0, 0, 0, 0, 0}, {B0, B1, B2, B3, 0, 0, 0, 0, 0}, {G0, G1, G2, G3, 0, 0, 0, 0, 0}}; }
+    static_assert(A0 == 0 && A3 == 4608 && B0 == 4864 && B3 == 4976 && FWD_END == 4992 && G0 == 4992 && G3 == 9600 && TOTAL == 9856, "the offsets the encoder half was laid out with");
 };
 // dynamic LDS of a split kernel (floats): images + per-wave scratch during the loop; four gradient images (waves w and w + 4 share one) at the end
 template <int PART> constexpr int ae_split_lds_floats(int nw)
@@ -46,38 +41,11 @@ template <int PART> constexpr int ae_split_lds_floats(int nw)
 
 // Parameters of layers [l0, l1) into the compact images of `tab` (cf. ae_load_lds).
 template <int NT, int BF = 0>
-__device__ inline void ae_load_lds_tab(float* lds, const int total, const AETab tab, const float* __restrict__ ae, const AEOffsets& go,
+__device__ inline void ae_load_lds_tab(float* lds, const AETab tab, const float* __restrict__ ae, const AEOffsets& go,
                                        const int T, const int OT, const int K, const int tid, const int l0, const int l1)
 {
-    AEParamRegs<NT> r;
-    ae_params_issue<NT>(r, ae, go, T, OT, K, tid, l0, l1);
-    for (int e = tid; e < total; e += NT) lds[e] = 0.f;
-    __syncthreads();
-    const int out[NL] = {64, 32, 16, 16, 16, 16, 32, 64, OT};
-    const int in[NL] = {T, 64, 32, 16, 16 + K, 16, 16, 32, 64};
-    const int outp[NL] = {CL::O0, CL::O1, CL::O2, CL::O3, CL::O4, CL::O5, CL::O6, CL::O7, CL::O8};
-    const int inp[NL] = {CL::I0, CL::I1, CL::I2, CL::I3, CL::I4, CL::I5, CL::I6, CL::I7, CL::I8};
-#pragma unroll
-    for (int l = 0; l < NL; ++l) {
-        const bool on = l >= l0 && l < l1;
-        const int IN = in[l], n = on ? out[l] * IN : 0, OP = outp[l], IP = inp[l];
-#pragma unroll
-        for (int u = 0; u < (ae_max_elems(l) + NT - 1) / NT; ++u) {
-            const int e = tid + u * NT;
-            if (e < n) {
-                const int o = e / IN, i = e - o * IN;
-                if constexpr (BF) {                       // 16-bit images, packed into the first half of each region (ae_params_scatter)
-                    const unsigned short hb = st_half_bits<BF>(r.v[l][u]);
-                    reinterpret_cast<unsigned short*>(lds + tab.ao[l])[(((i >> 2) * OP + o) << 2) + (i & 3)] = hb;
-                    reinterpret_cast<unsigned short*>(lds + tab.gi[l])[(((o >> 2) * IP + i) << 2) + (o & 3)] = hb;
-                } else {
-                lds[tab.ao[l] + (((i >> 2) * OP + o) << 2) + (i & 3)] = r.v[l][u];
-                lds[tab.gi[l] + (((o >> 2) * IP + i) << 2) + (o & 3)] = r.v[l][u];
-                }
-            }
-        }
-        if (on && tid < out[l]) lds[tab.bo[l] + tid] = r.bv[l];
-    }
+    const float* const nets[1] = {ae};
+    ae_load_nets<NT, BF, 1>(lds, tab, nets, go, T, OT, K, tid, l0, l1, true, false);
 }
 
 // Scheduling recipe of one backward stage (see ae_bwd_kernel): data-gradient MFMAs first, then one weight-gradient MFMA per pair of
@@ -121,7 +89,7 @@ ae_bwd_part_kernel(const float* __restrict__ mag, const float* __restrict__ phs,
     float* S0 = scr;                                          // PART 1: Y rows (d a9 transposed); PART 2: V rows (input rows transposed)
     float* XH = scr + (PART == 1 ? 16 : 32) * SP;
     float* XD = XH + 4 * 320;
-    ae_load_lds_tab<NW * 64, BF>(lw, P::TOTAL, P::tab(), ae ? ae_p : ae_m, go, T, OT, K, tid, P::L0, P::L1);
+    ae_load_lds_tab<NW * 64, BF>(lw, P::tab(), ae ? ae_p : ae_m, go, T, OT, K, tid, P::L0, P::L1);
     __syncthreads();
 
     const float* vin = ae ? phs : mag;
@@ -413,26 +381,7 @@ ae_bwd_part_kernel(const float* __restrict__ mag, const float* __restrict__ phs,
 #undef ST_ZT
 #undef ST_ZB
     // ---- packed partial gradient of this workgroup for the layers of this half (layout of the parameter block; cf. ae_bwd_kernel)
-    auto sum4 = [&](int idx) { return (lds[idx] + lds[P::FWD_END + idx]) + (lds[2 * P::FWD_END + idx] + lds[3 * P::FWD_END + idx]); };
-    float* base = ws + ((size_t)blockIdx.x * 2 + ae) * PG;
-    const int out[NL] = {64, 32, 16, 16, 16, 16, 32, 64, OT};
-    const int in[NL] = {T, 64, 32, 16, 16 + K, 16, 16, 32, 64};
-    const int inp[NL] = {CL::I0, CL::I1, CL::I2, CL::I3, CL::I4, CL::I5, CL::I6, CL::I7, CL::I8};
-    const AETab tab = P::tab();
-    constexpr int NT = NW * 64;
-#pragma unroll
-    for (int l = 0; l < NL; ++l) {
-        if (l < P::L0 || l >= P::L1) continue;
-        const int IN = in[l], n = out[l] * IN;
-#pragma unroll
-        for (int u = 0; u < (ae_max_elems(l) + NT - 1) / NT; ++u) {
-            const int e = tid + u * NT;
-            if (e < n) { const int o = e / IN, i = e - o * IN; base[go.w[l] + e] = sum4(tab.ao[l] + o * inp[l] + i); }
-        }
-        if (tid < out[l]) base[go.b[l] + tid] = sum4(tab.bo[l] + tid);
-        { const int p0 = go.w[l] + n, np = go.b[l] - p0; if (tid < np) base[p0 + tid] = 0.f; }
-        { const int p0 = go.b[l] + out[l], np = (l + 1 < NL ? go.w[l + 1] : PG) - p0; if (tid < np) base[p0 + tid] = 0.f; }
-    }
+    ae_partials_store<NW * 64>(ws + ((size_t)blockIdx.x * 2 + ae) * PG, lds, P::FWD_END, P::tab(), go, PG, T, OT, K, tid, P::L0, P::L1, 0x1FFu);
 }
 #undef ST_BWD_STAGE2
 #undef ST_PIPE2

@@ -134,9 +134,8 @@ static int check_dims(const st_dims* d)
 
 static void ae_shapes(const st_dims* d, int* out, int* in)
 {
-    const int o[9] = {64, 32, 16, 16, 16, 16, 32, 64, d->OT};
-    const int i[9] = {d->T, 64, 32, 16, 16 + d->K, 16, 16, 32, 64};
-    memcpy(out, o, sizeof(o)); memcpy(in, i, sizeof(i));
+    const sta::AEShape sh{d->T, d->OT, d->K};      // the layer table of st_ae.h
+    for (int l = 0; l < sta::NL; ++l) { out[l] = sh.out(l); in[l] = sh.in(l); }
 }
 
 static int64_t param_offsets(const st_dims* d, int64_t* offs)
@@ -428,9 +427,7 @@ static void wide_carve(const st_dims* d, const Layout& L, float* base, WideWS* w
 {
     const int FP = st_kp_of(d->F) / 2;
     const size_t R = (size_t)d->B * FP;
-    const int hrows[8] = {64, 32, 16, 16 + d->K, 16, 16, 32, 64};
-    const int drows[9] = {64, 32, 16, 16, 16, 16, 32, 64, d->OT};
-    int out[9], in[9]; ae_shapes(d, out, in);
+    int out[9], in[9]; ae_shapes(d, out, in);      // H[.][j] is the input of layer j + 1, DA[.][l] the output gradient of layer l
     w->R = R; w->Tp = st_round_up(d->T, 32);      // 32: k-tile of the bf16 GEMM kernel (level-2 precision)
     { long ns = (long)(R / 128); w->nsplit = (int)(ns < 1 ? 1 : (ns > 256 ? 256 : ns)); }   // wgrad K = R: short k-chains on many workgroups
     w->so[0] = 0;
@@ -441,12 +438,12 @@ static void wide_carve(const st_dims* d, const Layout& L, float* base, WideWS* w
     for (int a = 0; a < 2; ++a) {
         w->W1p[a] = take((size_t)64 * w->Tp); w->W5p[a] = take(16 * 32);
         w->V[a] = take((size_t)(d->T + 1) * R);
-        for (int j = 0; j < 8; ++j) w->H[a][j] = take((size_t)(hrows[j] + 1) * R);
+        for (int j = 0; j < 8; ++j) w->H[a][j] = take((size_t)(in[j + 1] + 1) * R);
         w->E9[a] = take((size_t)d->OT * R);
     }
     w->fwd_floats = off;
     for (int a = 0; a < 2; ++a) {
-        for (int l = 0; l < 9; ++l) w->DA[a][l] = take((size_t)drows[l] * R);
+        for (int l = 0; l < 9; ++l) w->DA[a][l] = take((size_t)out[l] * R);
         w->TL[a] = take((size_t)d->OT * R);
     }
     w->slabs = take((size_t)2 * w->nsplit * w->SL);
@@ -1288,7 +1285,8 @@ extern "C" int st_ae_acts(const st_dims* d, const float* v, const float* knobs, 
     stm::AeActsArgs a;
     a.v = v; a.knobs = knobs; a.ae = ae; a.B = d->B; a.T = d->T; a.OT = d->OT; a.F = d->F; a.K = d->K; a.sf = sf;
     for (int l = 0; l < 9; ++l) { a.w_off[l] = L.go.w[l]; a.b_off[l] = L.go.b[l]; }
-    const int widths[10] = {64, 32, 16, 16, 16 + d->K, 16, 16, 32, 64, d->OT};
+    int out[9], in[9], widths[10]; ae_shapes(d, out, in);
+    for (int i = 0; i < 10; ++i) widths[i] = i < 4 ? out[i] : i == 4 ? in[4] : out[i - 1];      // layer outputs, with [z ; knobs] (the input of layer 4) between
     size_t off = 0;
     for (int i = 0; i < 10; ++i) { a.out[i] = acts + off; off += (size_t)d->B * d->F * widths[i]; }
     hipLaunchKernelGGL(stm::ae_acts_kernel, dim3((d->B * d->F + 63) / 64), dim3(64), 0, st_stream(stream), a);

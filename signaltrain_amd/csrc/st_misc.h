@@ -1103,7 +1103,9 @@ ae_acts_kernel(const AeActsArgs a)
     if (row >= a.B * a.F) return;
     const int b = row / a.F, f = row - b * a.F;
     float h[64 + 16], z[64 + 16];                      // widths <= 64 (+ K <= 16 knobs)
-    const int outw[9] = {64, 32, 16, 16, 16, 16, 32, 64, a.OT};
+    const sta::AEShape sh{a.T, a.OT, a.K};
+    int outw[9];                                       // the layer table as an array: the layer loop below is a run-time loop
+    for (int l = 0; l < 9; ++l) outw[l] = sh.out(l);
     int inw = a.T;
     // layer 1 reads the T input frames of this row straight from [B][T][F]
     for (int l = 0; l < 9; ++l) {
