@@ -456,6 +456,20 @@ size_t st_synth_effect_scratch_floats(int effect, int B, int L);
 int st_synth_effect(int effect, unsigned seed, unsigned long long first_window, int B, int L, int ysz, int K, float sr,
                     const float* knob_lo, const float* knob_hi, int augment, int chooser, const float* pink_in,
                     float* x, float* y, float* knobs, float* scratch, void* stream);
+/* st_synth_effect over a caller-chosen set of signal families: all twelve of audio.synth_input_sample (audio.py:296-334) are built -- beyond the
+ * compressor's set 3 (triangle + 1/f noise), 5 (spikes + normal noise), 8 (ampexpstepup from -30 dB), 9 (frequency sweep), 10 (box + white + 1/f
+ * noise) and 11 (scaled 1/f noise); the datasets of the reference use e.g. {0,1,3,4,6,10,2,7,9} and {1,3,5,6,7} (datasets.py:317-320).
+ *   family_mask   bit f allows family f, f in 0..11.  With ST_FAMILIES_COMPRESSOR the call IS st_synth_effect: the same kernel, the same bits.
+ *   chooser       -1: per window a uniform member of the set (the draw law is written out in st_feed.h; datasets.synth_feed_draw replicates the
+ *                 part of it the new families use); 0..11 force one family whatever the mask holds, 100 is the bare 1/f noise (tests).
+ * The other arguments, the effects, the scratch and the long-window rules are st_synth_effect's; a window stays a function of (seed, window index,
+ * family set) only, and its knobs, polarity and the signals of the compressor's families do not depend on the set.  Refused before any launch
+ * (ST_ERR_ARG, the rule in st_last_error()): an empty mask; bits >= 12; a forced family outside 0..11 / 100 -- the superposition of two signals
+ * (chooser >= 12 in the reference, which none of its datasets draws) is not built -- and everything st_synth_effect refuses. */
+enum { ST_FAMILIES_COMPRESSOR = 0xD7, ST_FAMILIES_ALL = 0xFFF };
+int st_synth_effect_families(int effect, unsigned family_mask, unsigned seed, unsigned long long first_window, int B, int L, int ysz, int K, float sr,
+                             const float* knob_lo, const float* knob_hi, int augment, int chooser, const float* pink_in,
+                             float* x, float* y, float* knobs, float* scratch, void* stream);
 
 /* One training minibatch of RECORDED input / target pairs cut out of device-resident audio in ONE launch (st_feed_files.h; replaces
  * AudioFileDataSet.get_single_chunk, datasets.py:225-253).  pool_x / pool_y hold all files concatenated (float32, or the int16 of the wav

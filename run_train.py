@@ -24,6 +24,9 @@ if __name__ == "__main__":
     p.add_argument('--resume-optimizer', action='store_true', help="restore Adam's moments (and, if the checkpoint belongs to this schedule, the position in the run) from --checkpoint")
     p.add_argument('-b', '--batch', type=int, help="batch size (per GPU); the reference's default.  On MI355X multiples of 256 windows (8192-sample window) fill the tile rounds of the analysis "
                                                         "forward: 379 k windows/s at 200, 418-426 k at 256, 477 k at 512 in fp32 (DESIGN.md section 5)", default=200)
+    p.add_argument('--choosers', default=None, type=lambda s: [int(v) for v in s.split(',')],
+                   help="signal families of the synthetic task (audio.synth_input_sample's 0..11), comma-separated, e.g. 0,1,3,4,6,10,2,7,9; "
+                        "default: the effect's own set, else the compressor's 0,1,2,4,6,7")
     p.add_argument('--checkpoint', help='name of checkpoint .tar file to start from', default='modelcheckpoint.tar')
     p.add_argument('-c', '--compand', help='mu-law compand the audio of a file dataset (datasets.py:218-220)', action='store_true')
     p.add_argument('--effect', help="effect to learn, the reference's keys (run_train.py:55-80): comp_4c | comp_large | comp | comp_t | comp_one | files are built here "
@@ -66,6 +69,6 @@ if __name__ == "__main__":
     train.train(epochs=args.epochs, n_data_points=args.num, batch_size=args.batch, device=torch.device("cuda", local),
                 effect=effect, datapath=(args.path if args.effect == 'files' else None), sr=args.sr, scale_factor=args.scale, shrink_factor=args.shrink, apex_opt=args.apex,
                 target_type=args.target, lr_max=args.lrmax, in_checkpointname=args.checkpoint, compand=args.compand,
-                compute_dtype=args.dtype, device_feed=args.device_feed, resume_optimizer=args.resume_optimizer, device_eval=args.device_eval)
+                compute_dtype=args.dtype, device_feed=args.device_feed, resume_optimizer=args.resume_optimizer, device_eval=args.device_eval, choosers=args.choosers)
     if dist.is_initialized():
         dist.destroy_process_group()

@@ -67,6 +67,8 @@ SIGNATURES = {
     "st_synth_effect_scratch_floats": (C.c_size_t, [_i, _i, _i]),
     "st_synth_effect": (_i, [_i, C.c_uint, C.c_ulonglong, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float),
                              C.c_int, C.c_int, _p, _p, _p, _p, _p, _p]),
+    "st_synth_effect_families": (_i, [_i, C.c_uint, C.c_uint, C.c_ulonglong, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.POINTER(C.c_float),
+                                      C.POINTER(C.c_float), C.c_int, C.c_int, _p, _p, _p, _p, _p, _p]),
     "st_file_feed": (_i, [C.c_uint, C.c_ulonglong, _i, _i, _i, _i, _i, _p, _p, _p, _p, _i, C.c_longlong, C.c_longlong, _p, _i, _p, _p, _p, _p, _p]),
     "st_fe_frames": (_i, [C.c_int] * 4),
     "st_fe_ws_floats": (C.c_size_t, [C.c_int] * 6),
@@ -129,6 +131,18 @@ SIGNATURES = {
 
 # effect ids of st_synth_effect (include/signaltrain_hip.h ST_FX_*)
 FX_COMP4C, FX_COMP, FX_LOWPASS, FX_DENOISE = 0, 1, 2, 3
+# signal-family sets of st_synth_effect_families (ST_FAMILIES_*): bit f allows family f
+FAMILIES_COMPRESSOR, FAMILIES_ALL = 0xD7, 0xFFF
+
+
+def family_mask(choosers):
+    """The family_mask of st_synth_effect_families for an iterable of family numbers (None: the compressor's set)."""
+    if choosers is None:
+        return FAMILIES_COMPRESSOR
+    fams = sorted({int(c) for c in choosers})
+    if not fams or fams[0] < 0 or fams[-1] > 11:
+        raise ValueError(f"signaltrain_amd: choosers = {list(choosers)!r}: a non-empty set of signal families out of 0..11 (the superposition, 12 and up, is not built)")
+    return sum(1 << f for f in fams)
 # sample formats of st_file_feed's audio pools (include/signaltrain_hip.h ST_PCM_*)
 PCM_F32, PCM_S16 = 0, 1
 

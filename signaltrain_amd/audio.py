@@ -94,9 +94,12 @@ def _device_effect(fn, effect, x, kw, y_size):
 class Effect:
     """audio.py:449-480.  feed_fx: the st_synth_effect id (_lib.FX_*) of the library's fused device feed for this effect, None if there is none;
     feed_ranges(): the four (low, high) knob rows that feed takes (knobs past len(knob_ranges) are fixed at their low end);
-    makes_input: the effect makes the item's input itself (Denoise) -- its go_device returns (y, x_new) and takes seed=, the noise stream."""
+    makes_input: the effect makes the item's input itself (Denoise) -- its go_device returns (y, x_new) and takes seed=, the noise stream;
+    feed_choosers: the signal families (audio.synth_input_sample's 0..11) a synthetic dataset of this effect draws from when it is given none;
+    None = the compressor's set {0,1,2,4,6,7} (datasets.py:317)."""
     feed_fx = None
     makes_input = False
+    feed_choosers = None
 
     def __init__(self, sr=44100.0, dtype=np.float32):
         self.name = 'Generic Effect'; self.knob_names = ['knob']

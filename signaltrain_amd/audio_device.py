@@ -1,7 +1,7 @@
 """Device-side synthetic test signals for the comp_4c task -- SURVEY.md 8(f)-1, the rest of the GPU data feed.
 
-signaltrain/audio.py:85-196 and :296-334 (`synth_input_sample` and the generators it calls for the compressor's chooser set
-{0, 1, 2, 4, 6, 7}, datasets.py:317) restated as BATCHED device computations: every window of a minibatch draws its own
+signaltrain/audio.py:85-196 and :296-334 (`synth_input_sample` and the generators it calls: all twelve signal families; the default
+set is the compressor's, {0, 1, 2, 4, 6, 7}, datasets.py:317, whose draw sequence is what it always was) restated as BATCHED device computations: every window of a minibatch draws its own
 chooser, tone count, amplitudes, frequencies, onsets ... from a device `torch.Generator` (no host RNG, no host loop), the
 waveforms are evaluated elementwise over [B, L] and normalised per window exactly as `normish` / `pinknoise` do.  The 1/f noise
 keeps the reference's construction -- an inverse real FFT of a REAL spectrum `(2 u - 1) / sqrt(k + 1)` (so it is an even
@@ -90,9 +90,63 @@ def pluck(t, B, gen, freq_range=(50.0, 6400.0)):
     return _normish(y * expdecay(t, B, gen), gen)
 
 
+def triangle(t, B, gen, pink):
+    """audio.py:188-196: ramp up, then down, zero outside, plus 1/f noise; not normalised."""
+    dev, tl = t.device, float(t[-1])
+    height = (0.4 * _u(gen, B, 1, device=dev) + 0.4) * _sign(gen, B, 1, device=dev)
+    width = _u(gen, B, 1, device=dev) / 4 * tl
+    t0 = 2 * width + 0.4 * _u(gen, B, 1, device=dev) * tl
+    tt = t[None, :]
+    x = height * (1 - (tt - t0).abs() / width.clamp_min(1e-30))
+    x = torch.where((tt < t0 - width) | (tt > t0 + width), torch.zeros_like(x), x)
+    return x + (0.1 * _u(gen, B, 1, device=dev) + 0.02) * pink
+
+
+def spikes(t, B, gen, n_spikes=50):
+    """audio.py:175-186: fifty three-sample spikes, each written over what is there (index int(int(u n - 2) + t[-1]), -1 wraps), plus normal noise."""
+    dev, n, tl = t.device, t.shape[0], float(t[-1])
+    x = torch.zeros(B, n, device=dev)
+    for _ in range(n_spikes):
+        loc = torch.trunc(torch.trunc(_u(gen, B, 1, device=dev).double() * n - 2) + tl).long()
+        h = (2 * _u(gen, B, 1, device=dev) - 1) * 0.7
+        x.scatter_(1, loc % n, h); x.scatter_(1, (loc + 1) % n, h / 2); x.scatter_(1, (loc - 1) % n, h / 2)
+    return x + 0.1 * _u(gen, B, 1, device=dev) * torch.randn(B, n, generator=gen, device=dev)
+
+
+def ampexpstepup(t, B, gen, start_dB=-30, freq_range=(400.0, 5000.0)):
+    """audio.py:149-161: a tone under an envelope that rises in integer dB steps (env = 10^(dB / 10), as the reference has it), then normish."""
+    dev, n = t.device, t.shape[0]
+    i = torch.arange(n, device=dev, dtype=torch.int64)
+    env_dB = start_dB + torch.div(-start_dB * i, max(n - 1, 1), rounding_mode="floor")      # == floor(linspace(start_dB, 0, n))
+    freq = freq_range[0] + (freq_range[1] - freq_range[0]) * _u(gen, B, 1, device=dev)
+    y = torch.pow(10.0, env_dB.double() / 10)[None, :] * torch.sin(freq.double() * t.double()[None, :])
+    return _normish(y.float(), gen)
+
+
+def sweep(t, B, gen):
+    """audio.py:164-173 with the draws of :323-325: exponential sweep f_low -> f_high (the constant in front is 20, not f_low), for one window
+    in three with the amplitude rising too, then normish."""
+    dev, tl = t.device, float(t[-1])
+    f_low = torch.randint(20, 1000, (B, 1), generator=gen, device=dev).double()
+    f_high = torch.randint(1000, 20000, (B, 1), generator=gen, device=dev).double()
+    amp_too = torch.randint(0, 3, (B, 1), generator=gen, device=dev) == 2
+    lnfr = torch.log(f_high / f_low)
+    amp = 0.9 * _u(gen, B, 1, device=dev).double()
+    g = torch.exp(t.double()[None, :] / tl * lnfr)
+    y = amp * torch.sin(20 * 2 * math.pi * tl / lnfr * (g - 1))
+    return _normish(torch.where(amp_too, y * g, y).float(), gen)
+
+
+EXTENDED_CHOOSERS = (3, 5, 8, 9, 10, 11)
+
+
 def synth_input_batch(B, chunk_size, sr, gen, device, choosers=COMPRESSOR_CHOOSERS, chooser=None):
     """B windows of audio.synth_input_sample (audio.py:296-334): x [B, chunk_size] float32 on `device`, and the chooser drawn
-    for each window.  chooser: force one signal family for every window (tests)."""
+    for each window, uniformly over `choosers` (families 0..11; the superposition is not built).  chooser: force one signal family
+    for every window (tests).  The families beyond the compressor's set draw only when one of them can come out."""
+    asked = tuple(choosers) if chooser is None else (int(chooser),)
+    if not asked or any(int(k) != k or not 0 <= k <= 11 for k in asked):
+        raise NotImplementedError(f"audio_device.synth_input_batch: signal families are 0..11 (the superposition, 12 and up, is not built), not {asked}")
     t = torch.arange(chunk_size, device=device, dtype=torch.float32) / float(sr)
     n = chunk_size
     if chooser is None:
@@ -109,11 +163,13 @@ def synth_input_batch(B, chunk_size, sr, gen, device, choosers=COMPRESSOR_CHOOSE
     y = torch.where(c == 4, bx, y)
     y = torch.where(c == 6, bx * white, y)
     y = torch.where(c == 7, plk + (0.3 * _u(gen, B, 1, device=device) + 0.1) * pink, y)
-    known = torch.zeros_like(c, dtype=torch.bool)
-    for k in (0, 1, 2, 4, 6, 7):
-        known |= c == k
-    if not bool(known.all()):
-        raise NotImplementedError("audio_device.synth_input_batch: only the compressor's chooser set {0,1,2,4,6,7} is built")
+    if any(k in EXTENDED_CHOOSERS for k in asked):
+        y = torch.where(c == 3, triangle(t, B, gen, pink), y)
+        y = torch.where(c == 5, spikes(t, B, gen), y)
+        y = torch.where(c == 8, ampexpstepup(t, B, gen), y)
+        y = torch.where(c == 9, sweep(t, B, gen), y)
+        y = torch.where(c == 10, bx + 0.2 * _u(gen, B, 1, device=device) * white + 0.2 * _u(gen, B, 1, device=device) * pink, y)
+        y = torch.where(c == 11, (0.6 * _u(gen, B, 1, device=device) + 0.2) * pink, y)
     # audio.py:333: random polarity + 1e-8 of uniform noise (keeps log10 away from exact zeros downstream)
     return y * _sign(gen, B, 1, device=device) + _u(gen, B, n, device=device) * 1e-8, pick
 

@@ -1986,7 +1986,7 @@ extern "C" size_t st_synth_effect_scratch_floats(int effect, int B, int L)
     return n;
 }
 extern "C" size_t st_synth_comp4c_scratch_floats(int B, int L) { return st_synth_effect_scratch_floats(ST_FX_COMP4C, B, L); }
-template <int FX>
+template <int FX, bool EXT>
 static int feed_launch(const stf::FeedArgs& a, int B, size_t lds, void* stream)
 {
     if (lds >= 65536) {      // exactly 64 KB of dynamic LDS beside a few static bytes: ask for it explicitly (the 160 KB request of ensure_dyn_lds is refused for a kernel with static LDS)
@@ -1994,38 +1994,46 @@ static int feed_launch(const stf::FeedArgs& a, int B, size_t lds, void* stream)
         int dev = 0; (void)hipGetDevice(&dev);
         std::lock_guard<std::mutex> lk(mu);
         if (!done.count(dev)) {
-            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&stf::synth_feed_kernel<FX>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&stf::synth_feed_kernel<FX, EXT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
             if (e != hipSuccess) return st_fail(ST_ERR_LAUNCH, "hipFuncSetAttribute(synth_feed_kernel, %zu B dynamic LDS): %s", lds, hipGetErrorString(e));
             done.insert(dev);
         }
     }
-    hipLaunchKernelGGL(stf::synth_feed_kernel<FX>, dim3(B), dim3(256), lds, st_stream(stream), a);
+    hipLaunchKernelGGL((stf::synth_feed_kernel<FX, EXT>), dim3(B), dim3(256), lds, st_stream(stream), a);
     ST_LAUNCHED(FX == ST_FX_COMP ? "synth_comp" : FX == ST_FX_LOWPASS ? "synth_lowpass" : FX == ST_FX_DENOISE ? "synth_denoise" : "synth_comp4c"); return ST_OK;
 }
-extern "C" int st_synth_effect(int effect, unsigned seed, unsigned long long first_window, int B, int L, int ysz, int K, float sr,
-                               const float* knob_lo, const float* knob_hi, int augment, int chooser, const float* pink_in,
-                               float* x, float* y, float* knobs, float* scratch, void* stream)
+template <int FX>
+static int feed_launch_fx(bool ext, const stf::FeedArgs& a, int B, size_t lds, void* stream)
 {
-    ST_REQ(feed_effect_ok(effect), "st_synth_effect: effect %d is not an ST_FX_* id (ST_FX_COMP4C = 0, ST_FX_COMP = 1, ST_FX_LOWPASS = 2, ST_FX_DENOISE = 3)", effect);
-    ST_REQ(effect != ST_FX_COMP4C || (K >= 1 && K <= 4), "st_synth_effect: ST_FX_COMP4C takes 1 to 4 knobs, not K=%d", K);
-    ST_REQ(effect != ST_FX_COMP || K == 3, "st_synth_effect: ST_FX_COMP takes 3 knobs (threshold, ratio, attack/release), not K=%d", K);
-    ST_REQ(effect != ST_FX_LOWPASS || K == 1, "st_synth_effect: ST_FX_LOWPASS takes 1 knob (cutoff Hz), not K=%d", K);
-    ST_REQ(effect != ST_FX_DENOISE || K == 1, "st_synth_effect: ST_FX_DENOISE takes 1 knob (strength), not K=%d", K);
+    return ext ? feed_launch<FX, true>(a, B, lds, stream) : feed_launch<FX, false>(a, B, lds, stream);
+}
+// st_synth_effect (families = the compressor's set, today's family rule) and st_synth_effect_families (who names the entry in the messages)
+static int synth_effect_run(const char* who, int effect, unsigned families, bool any_family, unsigned seed, unsigned long long first_window, int B, int L, int ysz,
+                            int K, float sr, const float* knob_lo, const float* knob_hi, int augment, int chooser, const float* pink_in,
+                            float* x, float* y, float* knobs, float* scratch, void* stream)
+{
+    ST_REQ(feed_effect_ok(effect), "%s: effect %d is not an ST_FX_* id (ST_FX_COMP4C = 0, ST_FX_COMP = 1, ST_FX_LOWPASS = 2, ST_FX_DENOISE = 3)", who, effect);
+    ST_REQ(effect != ST_FX_COMP4C || (K >= 1 && K <= 4), "%s: ST_FX_COMP4C takes 1 to 4 knobs, not K=%d", who, K);
+    ST_REQ(effect != ST_FX_COMP || K == 3, "%s: ST_FX_COMP takes 3 knobs (threshold, ratio, attack/release), not K=%d", who, K);
+    ST_REQ(effect != ST_FX_LOWPASS || K == 1, "%s: ST_FX_LOWPASS takes 1 knob (cutoff Hz), not K=%d", who, K);
+    ST_REQ(effect != ST_FX_DENOISE || K == 1, "%s: ST_FX_DENOISE takes 1 knob (strength), not K=%d", who, K);
     // the one-knob effects' ranges (host arrays): checked as soon as they are there, before the device pointers
     ST_REQ(effect != ST_FX_LOWPASS || !knob_lo || !knob_hi || (knob_lo[0] > 0.f && knob_lo[0] <= knob_hi[0] && knob_hi[0] < 0.5f * sr),
-           "st_synth_effect: ST_FX_LOWPASS needs a cutoff range with 0 < lo <= hi < sr / 2 (lo=%g hi=%g sr=%g)", knob_lo[0], knob_hi[0], sr);
+           "%s: ST_FX_LOWPASS needs a cutoff range with 0 < lo <= hi < sr / 2 (lo=%g hi=%g sr=%g)", who, knob_lo[0], knob_hi[0], sr);
     ST_REQ(effect != ST_FX_DENOISE || !knob_lo || !knob_hi || (knob_lo[0] >= 0.f && knob_lo[0] <= knob_hi[0]),
-           "st_synth_effect: ST_FX_DENOISE needs a strength range with 0 <= lo <= hi (lo=%g hi=%g)", knob_lo[0], knob_hi[0]);
-    ST_REQ(x && y && knobs && knob_lo && knob_hi, "st_synth_effect: null pointer");
-    ST_REQ(B > 0 && L > 0 && ysz > 0 && ysz <= L && sr > 0.f, "st_synth_effect: bad sizes (B=%d L=%d ysz=%d K=%d)", B, L, ysz, K);
-    ST_REQ(chooser == -1 || chooser == 0 || chooser == 1 || chooser == 2 || chooser == 4 || chooser == 6 || chooser == 7 || chooser == 100, "st_synth_effect: signal family %d is not built (the compressor's set is 0,1,2,4,6,7)", chooser);
+           "%s: ST_FX_DENOISE needs a strength range with 0 <= lo <= hi (lo=%g hi=%g)", who, knob_lo[0], knob_hi[0]);
+    ST_REQ(x && y && knobs && knob_lo && knob_hi, "%s: null pointer", who);
+    ST_REQ(B > 0 && L > 0 && ysz > 0 && ysz <= L && sr > 0.f, "%s: bad sizes (B=%d L=%d ysz=%d K=%d)", who, B, L, ysz, K);
+    ST_REQ(any_family || chooser == -1 || chooser == 0 || chooser == 1 || chooser == 2 || chooser == 4 || chooser == 6 || chooser == 7 || chooser == 100, "%s: signal family %d is not built (the compressor's set is 0,1,2,4,6,7)", who, chooser);
+    // the kernel it always was unless a family beyond the compressor's set can come out
+    const bool ext = chooser >= 0 ? (chooser != 100 && !((stf::FAMILIES_COMPRESSOR >> chooser) & 1u)) : families != stf::FAMILIES_COMPRESSOR;
     const bool fft_ok = L <= stf::FFT_MAX && (L & (L - 1)) == 0;
     const bool long_fft = !fft_ok && !pink_in && scratch && feed_long_fft(L);      // scratch is then st_synth_effect_scratch_floats(effect, B, L) floats (contract)
-    ST_REQ(fft_ok || pink_in || long_fft, "st_synth_effect: a %d-sample window needs either the 1/f noise from the caller (pink_in) or -- powers of two up to 65536 -- "
-           "st_synth_effect_scratch_floats() floats of scratch for the library's own transform", L);
+    ST_REQ(fft_ok || pink_in || long_fft, "%s: a %d-sample window needs either the 1/f noise from the caller (pink_in) or -- powers of two up to 65536 -- "
+           "st_synth_effect_scratch_floats() floats of scratch for the library's own transform", who, L);
     stf::FeedArgs a;
     a.x = x; a.y = y; a.knobs = knobs; a.pink_in = pink_in; a.pink_peak = nullptr; a.seed = seed; a.first = first_window;
-    a.L = L; a.ysz = ysz; a.K = K; a.sr = sr; a.augment = augment; a.chooser = chooser;
+    a.L = L; a.ysz = ysz; a.K = K; a.sr = sr; a.augment = augment; a.chooser = chooser; a.families = families;
     for (int k = 0; k < 4; ++k) { a.lo[k] = knob_lo[k]; a.hi[k] = knob_hi[k]; }
     const bool split = scratch && L % 64 == 0 && feed_effect_splits(effect);
     a.gc = split ? scratch : nullptr; a.kw = split ? scratch + (size_t)B * L : nullptr;
@@ -2037,8 +2045,8 @@ extern "C" int st_synth_effect(int effect, unsigned seed, unsigned long long fir
         const int N2 = L / stf::PL_N1;
         for (int b0 = 0; b0 < B; b0 += FEED_FFT_SUB) {
             const int nb = B - b0 < FEED_FFT_SUB ? B - b0 : FEED_FFT_SUB;
-            hipLaunchKernelGGL(stf::pink_long_pass1_kernel, dim3(stf::PL_N1 / stf::PL_G, nb), dim3(256), 0, st_stream(stream), seed, first_window + (unsigned long long)b0, L, chooser, fbuf, peak + b0);
-            hipLaunchKernelGGL(stf::pink_long_pass2_kernel, dim3(N2 / stf::PL_G, nb), dim3(256), 0, st_stream(stream), seed, first_window + (unsigned long long)b0, L, chooser,
+            hipLaunchKernelGGL(stf::pink_long_pass1_kernel, dim3(stf::PL_N1 / stf::PL_G, nb), dim3(256), 0, st_stream(stream), seed, first_window + (unsigned long long)b0, L, chooser, families, fbuf, peak + b0);
+            hipLaunchKernelGGL(stf::pink_long_pass2_kernel, dim3(N2 / stf::PL_G, nb), dim3(256), 0, st_stream(stream), seed, first_window + (unsigned long long)b0, L, chooser, families,
                                (const float2*)fbuf, pink + (size_t)b0 * L, peak + b0);
         }
         ST_LAUNCHED("pink_long");
@@ -2048,17 +2056,17 @@ extern "C" int st_synth_effect(int effect, unsigned seed, unsigned long long fir
     static_assert(sizeof(stm::EnvLds) <= (size_t)stm::COMP_CH * sizeof(float), "the envelope scan's LDS must fit the in-kernel effect's buffer");
     static_assert(sizeof(stm::LpLds) <= (size_t)stm::COMP_CH * sizeof(float), "the low-pass scan's LDS must fit the in-kernel effect's buffer");
     const size_t lds = a.pink_in ? (split ? 0 : (size_t)stm::COMP_CH * sizeof(float)) : (size_t)stf::FFT_MAX * sizeof(float2);
-    if (effect == ST_FX_LOWPASS) return feed_launch<ST_FX_LOWPASS>(a, B, lds, stream);
-    if (effect == ST_FX_DENOISE) return feed_launch<ST_FX_DENOISE>(a, B, lds, stream);
+    if (effect == ST_FX_LOWPASS) return feed_launch_fx<ST_FX_LOWPASS>(ext, a, B, lds, stream);
+    if (effect == ST_FX_DENOISE) return feed_launch_fx<ST_FX_DENOISE>(ext, a, B, lds, stream);
     if (effect == ST_FX_COMP) {
-        ST_TRY(feed_launch<ST_FX_COMP>(a, B, lds, stream));
+        ST_TRY(feed_launch_fx<ST_FX_COMP>(ext, a, B, lds, stream));
         if (split) {
             hipLaunchKernelGGL(stm::compressor_env_kernel, dim3(B), dim3(256), 0, st_stream(stream), x, a.gc, a.kw, 4, sr, L, ysz, y);
             ST_LAUNCHED("compressor_env");
         }
         return ST_OK;
     }
-    ST_TRY(feed_launch<ST_FX_COMP4C>(a, B, lds, stream));
+    ST_TRY(feed_launch_fx<ST_FX_COMP4C>(ext, a, B, lds, stream));
     if (split) {
         hipLaunchKernelGGL(stm::comp_smooth_kernel, dim3((B + 63) / 64), dim3(64), 0, st_stream(stream), a.gc, a.kw, sr, B, L);
         ST_LAUNCHED("comp_smooth");
@@ -2066,6 +2074,26 @@ extern "C" int st_synth_effect(int effect, unsigned seed, unsigned long long fir
         ST_LAUNCHED("comp_apply");
     }
     return ST_OK;
+}
+extern "C" int st_synth_effect(int effect, unsigned seed, unsigned long long first_window, int B, int L, int ysz, int K, float sr,
+                               const float* knob_lo, const float* knob_hi, int augment, int chooser, const float* pink_in,
+                               float* x, float* y, float* knobs, float* scratch, void* stream)
+{
+    return synth_effect_run("st_synth_effect", effect, stf::FAMILIES_COMPRESSOR, false, seed, first_window, B, L, ysz, K, sr, knob_lo, knob_hi, augment, chooser, pink_in,
+                            x, y, knobs, scratch, stream);
+}
+// The same feed over a caller-chosen set of signal families (all twelve of audio.synth_input_sample are built; the superposition is not)
+extern "C" int st_synth_effect_families(int effect, unsigned family_mask, unsigned seed, unsigned long long first_window, int B, int L, int ysz, int K, float sr,
+                                        const float* knob_lo, const float* knob_hi, int augment, int chooser, const float* pink_in,
+                                        float* x, float* y, float* knobs, float* scratch, void* stream)
+{
+    ST_REQ(family_mask != 0u, "st_synth_effect_families: family_mask is empty (bit f allows signal family f, f in 0..11; ST_FAMILIES_COMPRESSOR = 0xD7)");
+    ST_REQ((family_mask & ~stf::FAMILIES_ALL) == 0u, "st_synth_effect_families: family_mask 0x%X has bits past family 11 (the superposition, chooser >= 12, is not built)", family_mask);
+    ST_REQ(chooser == -1 || chooser == 100 || chooser < 12, "st_synth_effect_families: the superposition of two signals (chooser %d >= 12) is not built; "
+           "a forced family is 0..11, or 100 for the bare 1/f noise, or -1 to draw from family_mask", chooser);
+    ST_REQ(chooser >= -1, "st_synth_effect_families: forced family %d: 0..11, or 100 for the bare 1/f noise, or -1 to draw from family_mask", chooser);
+    return synth_effect_run("st_synth_effect_families", effect, family_mask, true, seed, first_window, B, L, ysz, K, sr, knob_lo, knob_hi, augment, chooser, pink_in,
+                            x, y, knobs, scratch, stream);
 }
 extern "C" int st_synth_comp4c(unsigned seed, unsigned long long first_window, int B, int L, int ysz, int K, float sr,
                                const float* knob_lo, const float* knob_hi, int augment, int chooser, const float* pink_in,

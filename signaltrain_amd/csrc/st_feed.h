@@ -17,6 +17,29 @@
 // Output contract: x [B][L], y [B][ysz], knobs [B][K] in [-0.5, 0.5] (float32), as the reference's collated batch (train.py:104-120 casts y to float).
 // Parity is DISTRIBUTIONAL (another generator than numpy's): tests compare per-family peak ranges, the even symmetry and 1/f slope of the noise,
 // the box structure, the Beta(0.8, 0.8) law, and the compressor against golden G9 through the same device function.
+//
+// Signal families (audio.py:296-334).  0 sine, 1 noisy sine, 2 pluck, 4 box, 6 noisy box, 7 noisy pluck are the compressor's set (datasets.py:317) and
+// the kernel it always was (synth_feed_kernel<FX, false>).  synth_feed_kernel<FX, true> adds 3 triangle + 1/f noise, 5 spikes + normal noise,
+// 8 ampexpstepup(start_dB = -30), 9 sweep, 10 box + white + 1/f noise, 11 scaled 1/f noise -- with the reference's oddities kept: the spike index is
+// int(int(u L - 2) + t[-1]) (two truncations toward zero, index -1 wraps), later spikes overwrite earlier ones, triangle and spikes are not
+// peak-normalised, env = 10^(env_dB / 10) in family 8 (env_dB = -30 + (30 n) / (L - 1) in integers == floor(linspace(-30, 0, L))), the sweep's
+// constant is 20 whatever f_low is.  The superposition (chooser >= 12) is not built.
+//
+// THE SECOND DRAW SEQUENCE.  The first sequence (Draw, below: family of the compressor's set, knobs, randsine, pluck, box, normish gain, noise
+// amounts, polarity) is unchanged, so the compressor-set stream keeps its bits; it has rejection loops on __powf and therefore no exact host replica.
+// Everything the families 3, 5, 8, 9, 10, 11 and a custom family set add is drawn from a second, loop-free sequence that datasets.synth_feed_draw
+// replicates exactly on the host:   key2 = mix32(key ^ 0x2545F491),   h_i = mix32(key2 + 0x9E3779B9 i),   u_i = (h_i >> 8) / 2^24 (float32),
+// below(h, n) = (h * n) >> 32 (64-bit product).  Every window has every draw, at a fixed index i, in float32 with each step rounded on its own:
+//    1  family        member number below(h_1, |set|) of the set in ascending order -- unless the set is {0,1,2,4,6,7}: then the first sequence's law
+//    2  tri height    (0.4 u + 0.4) * sign,   3  sign = h_3 >> 31 ? +1 : -1,   4  tri half-width u / 4 * tl,   5  tri t0 = 2 width + 0.4 u tl,
+//    6  tri 1/f amount 0.1 u + 0.02          (tl = float32(L - 1) / sr, the last time value;  t_n = float32(n) / sr)
+//    7  spikes' normal-noise amount 0.1 u
+//    8  step frequency 400 + 4600 u (rad/s, as the reference uses it)
+//    9  sweep f_low = 20 + below(h, 980),  10  f_high = 1000 + below(h, 19000),  11  amp_too = below(h, 3) == 2,  12  sweep amplitude 0.9 u
+//   13  family 10 white amount 0.2 u,  14  family 10 1/f amount 0.2 u,  15  family 11 1/f amount 0.6 u + 0.2
+//   32 + 2 j, 33 + 2 j  (j < 50)  spike j: position int(int(u L - 2) + tl) in float64, height (2 u - 1) * 0.7
+// Box (family 10), normish gain (8, 9) and the polarity come from the first sequence.  Per-sample streams: 3 white noise, 5 the 1e-8 noise, 7 the 1/f
+// spectrum, 11 Denoise, 13 and 17 the Box-Muller pair of family 5: z_n = sqrt(-2 ln(1 - u13_n)) cos(2 pi u17_n).
 #pragma once
 #include "st_common.h"
 #include "st_misc.h"
@@ -49,6 +72,44 @@ struct Draw {              // sequential scalar draws of one window (every threa
 // per-sample streams: value n of stream s of the window
 __device__ __forceinline__ float su01(const unsigned key, const unsigned s, const unsigned n) { return u01(mix32(mix32(key ^ (0xA511E9B3u * (s + 1u))) + 0x9E3779B9u * n)); }
 
+// ---- the second draw sequence (law: top of this file)
+constexpr unsigned FAMILIES_COMPRESSOR = 0xD7u, FAMILIES_ALL = 0xFFFu;      // bit f = family f
+constexpr int N_SPIKES = 50, SPIKE_MAP_BITS = 65536;
+__device__ __forceinline__ unsigned feed_key2(const unsigned key) { return mix32(key ^ 0x2545F491u); }
+__device__ __forceinline__ unsigned h2(const unsigned key2, const unsigned i) { return mix32(key2 + 0x9E3779B9u * i); }
+__device__ __forceinline__ int below(const unsigned h, const int n) { return (int)(((unsigned long long)h * (unsigned long long)(unsigned)n) >> 32); }
+struct ExtDraws { float tl, tri_h, tri_w, tri_t0, tri_amp, sp_amp, st_frq, sw_amp, c_white10, c_pink10, c_pink11; int sw_flo, sw_fhi, sw_too; };
+__device__ __forceinline__ ExtDraws ext_draws(const unsigned key2, const int L, const float sr)
+{
+#pragma clang fp contract(off)
+    ExtDraws e;
+    e.tl = (float)(L - 1) / sr;
+    const float th = 0.4f * u01(h2(key2, 2u)) + 0.4f;
+    e.tri_h = th * ((h2(key2, 3u) >> 31) ? 1.f : -1.f);
+    e.tri_w = u01(h2(key2, 4u)) / 4.f * e.tl;
+    const float tc = 0.4f * u01(h2(key2, 5u)) * e.tl;
+    e.tri_t0 = 2.f * e.tri_w + tc;
+    e.tri_amp = 0.1f * u01(h2(key2, 6u)) + 0.02f;
+    e.sp_amp = 0.1f * u01(h2(key2, 7u));
+    e.st_frq = 400.f + 4600.f * u01(h2(key2, 8u));
+    e.sw_flo = 20 + below(h2(key2, 9u), 980); e.sw_fhi = 1000 + below(h2(key2, 10u), 19000); e.sw_too = below(h2(key2, 11u), 3) == 2;
+    e.sw_amp = 0.9f * u01(h2(key2, 12u));
+    e.c_white10 = 0.2f * u01(h2(key2, 13u)); e.c_pink10 = 0.2f * u01(h2(key2, 14u));
+    e.c_pink11 = 0.6f * u01(h2(key2, 15u)) + 0.2f;
+    return e;
+}
+// spike j of the window: position (audio.py:178, in float64; an index outside the window wraps, as numpy's -1 does) and height
+__device__ __forceinline__ void ext_spike(const unsigned key2, const int j, const int L, const float tl, int* loc, float* height)
+{
+#pragma clang fp contract(off)
+    const int i0 = (int)((double)u01(h2(key2, 32u + 2u * (unsigned)j)) * (double)L - 2.0);
+    const int i1 = (int)((double)i0 + (double)tl);
+    *loc = ((i1 % L) + L) % L;
+    const float c = 2.f * u01(h2(key2, 33u + 2u * (unsigned)j)) - 1.f;
+    *height = c * 0.7f;
+}
+__device__ __forceinline__ bool family_wants_pink(const int ch) { return ch == 1 || ch == 7 || ch == 100 || ch == 3 || ch == 10 || ch == 11; }
+
 // The Denoise effect's input (audio.py:571): clean sample v of index n of the window `key` plus strength * (2u - 1), u = value n of stream 11 of the
 // window (streams 3, 5 and 7 belong to the signals).  The noise is formed and added in float32, each step rounded on its own, as the reference
 // casts its noise to float32 before the sum: contraction is switched off here (HIP's __fmul_rn / __fadd_rn are plain operators and would be fused
@@ -76,7 +137,8 @@ struct FeedArgs {
     int augment;
     float* gc; float* kw;                   // optional scratch [B][L] + [B][4]: the generator leaves the gain curve (ST_FX_COMP: the dB signal) and the world-coordinate knobs there and
                                             // stm::comp_smooth_apply_kernel finishes the effect (lane per window); NULL: the effect runs inside this kernel
-    int chooser;                            // -1: drawn per window from {0, 1, 2, 4, 6, 7}; else forced (tests); 100 = the bare 1/f noise (tests)
+    int chooser;                            // -1: drawn per window from `families`; else forced (tests); 100 = the bare 1/f noise (tests)
+    unsigned families;                      // bit f allows family f (synth_feed_kernel<FX, true>; the <FX, false> kernel draws from {0, 1, 2, 4, 6, 7})
 };
 constexpr int FFT_MAX = 8192;
 
@@ -115,13 +177,17 @@ __device__ __forceinline__ float block_max(float v, float* red)
 //           same per-window reproducibility as the in-LDS transform of the short windows), N2-point transform over k2 in LDS, twiddle, -> scr[n2][k1];
 //   pass 2  (n2 fixed, eight n2 per workgroup): 256-point transform over k1 of a contiguous 2 KB row, real part -> pink[N2 n1 + n2], |.| peak -> peak[b]
 //           (atomicMax on the bits of a non-negative float); the generator kernel divides by the peak when it mixes the noise in.
-// Only windows whose family uses the noise (chooser 1, 7; 100 in tests) do any work: a third of the training stream.  Round 3 took this noise from
+// Only windows whose family uses the noise (chooser 1, 7 and -- of a wider family set -- 3, 10, 11; 100 in tests) do any work: a third of the compressor's stream.  Round 3 took this noise from
 // torch.fft (rocFFT) driven by a stateful torch.Generator: 2 ms of full-width GPU time per 2048 windows and not reproducible per window index.
 constexpr int PL_N1 = 256, PL_G = 16;      // 16 transforms per workgroup: 128-byte segments in pass 1's transposed store, 64-byte ones in pass 2's
-__device__ __forceinline__ int feed_family(Draw& d, const int chooser)
+__device__ __forceinline__ int feed_family(Draw& d, const int chooser, const unsigned families = FAMILIES_COMPRESSOR)
 {
-    const int ci = d.randint(0, 6);
-    return chooser >= 0 ? chooser : (ci < 3 ? ci : (ci == 3 ? 4 : (ci == 4 ? 6 : 7)));
+    const int ci = d.randint(0, 6);                                     // drawn whatever the set is: the first sequence does not move
+    if (chooser >= 0) return chooser;
+    if (families == FAMILIES_COMPRESSOR) return ci < 3 ? ci : (ci == 3 ? 4 : (ci == 4 ? 6 : 7));
+    unsigned m = families;                                              // draw 1 of the second sequence: a uniform member of the set, ascending
+    for (int i = below(h2(feed_key2(d.key), 1u), __popc(families)); i > 0; --i) m &= m - 1u;
+    return __ffs(m) - 1;
 }
 __device__ __forceinline__ unsigned feed_key(const unsigned seed, const unsigned long long w)
 {
@@ -166,7 +232,8 @@ __device__ __forceinline__ void twiddle_table(float2* tw, const int n)
     for (int k = threadIdx.x; k < n / 2; k += 256) { float sn, cs; sincospif(2.0f * (float)k / (float)n, &sn, &cs); tw[k] = make_float2(cs, sn); }
 }
 __global__ void __launch_bounds__(256)
-pink_long_pass1_kernel(const unsigned seed, const unsigned long long first, const int L, const int chooser, float2* __restrict__ scr, float* __restrict__ peak)
+pink_long_pass1_kernel(const unsigned seed, const unsigned long long first, const int L, const int chooser, const unsigned families,
+                       float2* __restrict__ scr, float* __restrict__ peak)
 {
     __shared__ float2 lds[PL_G * 256];
     __shared__ float2 tw[128];
@@ -174,8 +241,8 @@ pink_long_pass1_kernel(const unsigned seed, const unsigned long long first, cons
     const unsigned long long w = first + (unsigned long long)b;
     Draw d{feed_key(seed, w), 0u};
     const unsigned key = d.key;
-    const int ch = feed_family(d, chooser);
-    if (!(ch == 1 || ch == 7 || ch == 100)) return;                     // workgroup-uniform
+    const int ch = feed_family(d, chooser, families);
+    if (!family_wants_pink(ch)) return;                                 // workgroup-uniform
     if (blockIdx.x == 0 && threadIdx.x == 0) peak[b] = 0.f;
     int logn = 0; while ((1 << logn) < N2) ++logn;
     twiddle_table(tw, N2);
@@ -198,7 +265,7 @@ pink_long_pass1_kernel(const unsigned seed, const unsigned long long first, cons
     }
 }
 __global__ void __launch_bounds__(256)
-pink_long_pass2_kernel(const unsigned seed, const unsigned long long first, const int L, const int chooser, const float2* __restrict__ scr,
+pink_long_pass2_kernel(const unsigned seed, const unsigned long long first, const int L, const int chooser, const unsigned families, const float2* __restrict__ scr,
                        float* __restrict__ pink, float* __restrict__ peak)
 {
     __shared__ float2 lds[PL_G * PL_N1];
@@ -207,8 +274,8 @@ pink_long_pass2_kernel(const unsigned seed, const unsigned long long first, cons
     const int b = blockIdx.y, N2 = L / PL_N1;
     const unsigned long long w = first + (unsigned long long)b;
     Draw d{feed_key(seed, w), 0u};
-    const int ch = feed_family(d, chooser);
-    if (!(ch == 1 || ch == 7 || ch == 100)) return;
+    const int ch = feed_family(d, chooser, families);
+    if (!family_wants_pink(ch)) return;
     twiddle_table(tw, PL_N1);
     const int n2_0 = blockIdx.x * PL_G;
     const float2* in = scr + (size_t)b * L + (size_t)n2_0 * PL_N1;
@@ -230,14 +297,19 @@ pink_long_pass2_kernel(const unsigned seed, const unsigned long long first, cons
     if (threadIdx.x == 0) atomicMax(reinterpret_cast<unsigned*>(peak + b), __float_as_uint(m));
 }
 
-// the effect a feed launch applies (include/signaltrain_hip.h ST_FX_*): a template parameter, so the comp_4c instantiation is the kernel it always was
-template <int FX>
+// the effect a feed launch applies (include/signaltrain_hip.h ST_FX_*): a template parameter, so the comp_4c instantiation is the kernel it always was.
+// EXT: the families beyond the compressor's set and the family set of a.families (the second draw sequence); false = the kernel it always was.
+template <int FX, bool EXT>
 __global__ void __launch_bounds__(256)
 synth_feed_kernel(const FeedArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) float feed_lds[];      // float2[FFT_MAX] (pink) -- later float[COMP_CH] (compressor)
     __shared__ float red[4];
     __shared__ float carry;
+    __shared__ int sp_loc[EXT ? N_SPIKES : 1];                            // family 5: the spikes' positions and heights
+    __shared__ float sp_h[EXT ? N_SPIKES : 1];
+    __shared__ unsigned sp_map[EXT ? SPIKE_MAP_BITS / 32 : 1];            // bit (n mod 65536): some spike touches sample n -- 150 of the window's samples look further
+    __shared__ double env_tab[EXT ? 32 : 1];                              // family 8: 10^(dB / 10), dB = -30 .. 0
     const int b = blockIdx.x, L = a.L;
     const unsigned long long w = a.first + (unsigned long long)b;
     Draw d{feed_key(a.seed, w), 0u};
@@ -245,7 +317,7 @@ synth_feed_kernel(const FeedArgs a)
     const float dt = 1.0f / a.sr, tl = (float)(L - 1) * dt;
 
     // ---- the window's parameters (datasets.py:317, audio.py:296-334)
-    const int ch = feed_family(d, a.chooser);      // {0, 1, 2, 4, 6, 7}
+    const int ch = EXT ? feed_family(d, a.chooser, a.families) : feed_family(d, a.chooser);      // {0, 1, 2, 4, 6, 7} unless EXT
     float kn[4], kw[4];
     for (int k = 0; k < 4; ++k) { kn[k] = d.beta(0.8f) - 0.5f; kw[k] = a.lo[k] + (kn[k] + 0.5f) * (a.hi[k] - a.lo[k]); }
     for (int k = a.K; k < 4; ++k) kw[k] = a.lo[k];                   // K < 4: the remaining knobs are fixed settings (all four are drawn: one stream for every K)
@@ -268,7 +340,59 @@ synth_feed_kernel(const FeedArgs a)
     const float c_pink1 = 0.2f * d.u(), c_white1 = 0.2f * d.u(), c_pink7 = 0.3f * d.u() + 0.1f;
     float pol = d.sign();
     if (a.augment) pol *= d.sign();                                  // datasets.py:27-29: the effect is odd in x, so flipping the pair == flipping x first
-    const bool want_pink = ch == 1 || ch == 7 || ch == 100;
+    const bool want_pink = EXT ? family_wants_pink(ch) : (ch == 1 || ch == 7 || ch == 100);
+    // ---- the families beyond the compressor's set: parameters from the second sequence, values in float64 where float32 would not carry the phase
+    // (the sweep reaches 2.7e4 rad at the 65536-sample window, the step tone 7e3 rad: an ulp of a float32 phase is 2e-3 rad there)
+    ExtDraws e = {};
+    double sw_c = 0.0, sw_r = 0.0;
+    if (EXT) {
+        const unsigned key2 = feed_key2(key);
+        e = ext_draws(key2, L, a.sr);
+        const double lnfr = log((double)e.sw_fhi / (double)e.sw_flo), tmax = fmax((double)e.tl, 1e-30);
+        sw_c = 20.0 * 2.0 * 3.14159265358979323846 * tmax / lnfr; sw_r = lnfr / tmax;
+        if (ch == 5) {                                               // workgroup-uniform
+            for (int i = threadIdx.x; i < SPIKE_MAP_BITS / 32; i += 256) sp_map[i] = 0u;
+            __syncthreads();
+            if (threadIdx.x < N_SPIKES) {
+                ext_spike(key2, (int)threadIdx.x, L, e.tl, &sp_loc[threadIdx.x], &sp_h[threadIdx.x]);
+                for (int dl = -1; dl <= 1; ++dl) {
+                    const unsigned m = (unsigned)((sp_loc[threadIdx.x] + dl + L) % L) & (unsigned)(SPIKE_MAP_BITS - 1);
+                    atomicOr(&sp_map[m >> 5], 1u << (m & 31u));
+                }
+            }
+            __syncthreads();
+        }
+        if (ch == 8) {
+            if (threadIdx.x <= 30) env_tab[threadIdx.x] = exp(0.1 * 2.30258509299404568402 * (double)((int)threadIdx.x - 30));
+            __syncthreads();
+        }
+    }
+    const int Lm1 = L > 1 ? L - 1 : 1;
+    auto tq = [&](const int n) { return (float)n / a.sr; };          // the reference's float32 time value, correctly rounded
+    auto stepv = [&](const int n) {                                  // ampexpstepup (audio.py:149-161) before normish
+        const int up = L <= (1 << 26) ? (int)((30u * (unsigned)n) / (unsigned)Lm1) : (int)((30ll * (long long)n) / (long long)Lm1);      // 0 .. 30
+        return (float)(env_tab[up] * sin((double)e.st_frq * (double)tq(n)));
+    };
+    auto sweepv = [&](const int n) {                                 // sweep (audio.py:164-173) before normish
+        const double g = exp(sw_r * (double)tq(n));
+        const double y = (double)e.sw_amp * sin(sw_c * (g - 1.0));
+        return (float)(e.sw_too ? y * g : y);
+    };
+    auto triv = [&](const int n) {                                   // triangle (audio.py:188-194) without its noise
+        const float t = tq(n);
+        return (t < e.tri_t0 - e.tri_w || t > e.tri_t0 + e.tri_w) ? 0.f : e.tri_h * (1.f - fabsf(t - e.tri_t0) / fmaxf(e.tri_w, 1e-30f));
+    };
+    auto spikev = [&](const int n) {                                 // spikes (audio.py:175-186): the last spike that touches the sample wins
+        float v = 0.f;
+        const unsigned m = (unsigned)n & (unsigned)(SPIKE_MAP_BITS - 1);
+        if ((sp_map[m >> 5] >> (m & 31u)) & 1u) for (int j = N_SPIKES - 1; j >= 0; --j) {
+            const int dl = n - sp_loc[j];
+            if (dl == 0) { v = sp_h[j]; break; }
+            if (dl == 1 || dl == -1 || dl == L - 1 || dl == 1 - L) { v = 0.5f * sp_h[j]; break; }
+        }
+        const float z = sqrtf(-2.f * logf(1.f - su01(key, 13u, (unsigned)n))) * cospif(2.f * su01(key, 17u, (unsigned)n));
+        return v + e.sp_amp * z;
+    };
 
     // ---- 1/f noise (audio.py:85-94)
     float2* fa = reinterpret_cast<float2*>(feed_lds);
@@ -301,6 +425,11 @@ synth_feed_kernel(const FeedArgs a)
         for (int n = threadIdx.x; n < L; n += 256) { const float t = (float)n * dt; m = fmaxf(m, fabsf((ch == 0 || ch == 1) ? sine(t) : plk(t))); }
         scale = nrm_u / fmaxf(block_max(m, red), 1e-30f);
     }
+    if (EXT && (ch == 8 || ch == 9)) {
+        float m = 0.f;
+        for (int n = threadIdx.x; n < L; n += 256) m = fmaxf(m, fabsf(ch == 8 ? stepv(n) : sweepv(n)));
+        scale = nrm_u / fmaxf(block_max(m, red), 1e-30f);
+    }
     // ---- pass 2: the window -- four consecutive samples per thread and trip (16-byte loads of the long-window noise, 16-byte stores), and with the
     // lane-per-window form of the effect the static gain curve of each sample right away, from the value in registers.  (Round 3 wrote the window and
     // then re-read it sample by sample in a third loop: without __restrict__ every trip's load waited for the previous trip's store -- 256 dependent
@@ -318,6 +447,12 @@ synth_feed_kernel(const FeedArgs a)
         else if (ch == 4) v = boxv(n);
         else if (ch == 6) v = boxv(n) * (2.f * su01(key, 3u, (unsigned)n) - 1.f);
         else if (ch == 100) v = pk;
+        else if (EXT && ch == 3) v = triv(n) + e.tri_amp * pk;
+        else if (EXT && ch == 5) v = spikev(n);
+        else if (EXT && ch == 8) v = stepv(n) * scale;
+        else if (EXT && ch == 9) v = sweepv(n) * scale;
+        else if (EXT && ch == 10) v = boxv(n) + e.c_white10 * (2.f * su01(key, 3u, (unsigned)n) - 1.f) + e.c_pink10 * pk;
+        else if (EXT && ch == 11) v = e.c_pink11 * pk;
         else v = plk(t) * scale + c_pink7 * pk;
         return ch == 100 ? v : v * pol + su01(key, 5u, (unsigned)n) * 1e-8f;       // audio.py:333
     };

@@ -175,7 +175,7 @@ def _train_loop(dp, model, engine, effect, device, epochs, batch_size, lr_sched,
 def train(effect=None, epochs=100, n_data_points=200000, batch_size=20, device=None, plot_every=10, cp_every=25, sr=44100,
           datapath=None, scale_factor=1, shrink_factor=4, apex_opt="O0", target_type="stream", lr_max=1e-4,
           in_checkpointname='modelcheckpoint.tar', compand=False, num_workers=10, device_feed=True, compute_dtype=None,
-          resume_optimizer=False, device_eval=False):
+          resume_optimizer=False, device_eval=False, choosers=None):
     """train.py:167-278.  datapath: directory with Train/ and Val/ wav pairs (datasets.AudioFileDataSet, the reference's
     file feed, e.g. the LA2A set of BASELINE configs[3]; pass effect=audio.FileEffect(datapath)); compand: mu-law compand that dataset's audio (datasets.py:218-220).
     apex_opt: "O0" = fp32 (the parity path); "O1" / "O2" / "O3" = the reference's Apex mixed precision (train.py:254-255),
@@ -189,7 +189,9 @@ def train(effect=None, epochs=100, n_data_points=200000, batch_size=20, device=N
     from the checkpoint (which the reference saves but never reads back, train.py:229) and, if the checkpoint belongs to THIS schedule
     (its epoch counter is below `epochs` and its step count lies inside the 1-cycle table), also the position in the run;
     device_eval: False (default) = the per-epoch validation pass on the host side (engine.forward + torch loss, two host syncs per batch); True = on the
-    device (engine.eval_step: the training step's forward at this compute_dtype, one accumulator read per epoch)."""
+    device (engine.eval_step: the training step's forward at this compute_dtype, one accumulator read per epoch);
+    choosers: the signal families (audio.synth_input_sample's 0..11) the synthetic task's training and validation windows are drawn from, e.g. the
+    reference's [0,1,3,4,6,10,2,7,9] or [1,3,5,6,7] (datasets.py:317-320); None = the effect's feed_choosers, else the compressor's {0,1,2,4,6,7}."""
     if compute_dtype is None:
         compute_dtype = "f32" if str(apex_opt).upper() in ("O0", "NONE", "") else "f16_all"
     effect = audio.Compressor_4c() if effect is None else effect
@@ -240,14 +242,15 @@ def train(effect=None, epochs=100, n_data_points=200000, batch_size=20, device=N
         # generated up front and re-sampled by index each epoch (the reference's recycle=True mode); device_feed=False: the reference's CPU-worker
         # DataLoader (~100 windows/s per core against 3-8 x 10^5 per second for the step).
         # Validation: the reference's recycled set (train.py:237-238), resident in HBM.
-        dataset = datasets.SynthAudioDataSet(chunk_size, effect, sr=sr, datapoints=n_data_points, y_size=out_chunk_size, augment=True)
+        dataset = datasets.SynthAudioDataSet(chunk_size, effect, sr=sr, datapoints=n_data_points, y_size=out_chunk_size, augment=True, choosers=choosers)
         t0 = time.time()
         if not device_feed:
             # the reference's own feed (train.py:233-248): CPU workers behind a DataLoader, items from SynthAudioDataSet.__getitem__
             print(f"device_feed=False: training minibatches come from {num_workers} CPU DataLoader workers (reference-style feed; expect ~10^2-10^3 windows/s)")
             dataloader = DataLoader(dataset, batch_size=batch_size, num_workers=num_workers, shuffle=True, worker_init_fn=datasets.worker_init, drop_last=True)
         elif device_feed == "recycle":
-            dev_ds = datasets.DeviceRecycledDataSet(chunk_size, effect, sr=sr, datapoints=n_data_points, y_size=out_chunk_size, augment=True, device=device)
+            dev_ds = datasets.DeviceRecycledDataSet(chunk_size, effect, sr=sr, datapoints=n_data_points, y_size=out_chunk_size, augment=True, device=device,
+                                                    choosers=choosers)
 
             class _DevLoader:                      # iterable with the DataLoader's per-epoch semantics
                 def __iter__(self_inner):
@@ -258,7 +261,8 @@ def train(effect=None, epochs=100, n_data_points=200000, batch_size=20, device=N
             dataloader = _DevLoader()
         else:
             dataloader = datasets.DeviceSynthLoader(dataset, batch_size, device)
-        val_ds = datasets.DeviceRecycledDataSet(chunk_size, effect, sr=sr, datapoints=n_data_points // 4, y_size=out_chunk_size, augment=False, device=device)
+        val_ds = datasets.DeviceRecycledDataSet(chunk_size, effect, sr=sr, datapoints=n_data_points // 4, y_size=out_chunk_size, augment=False, device=device,
+                                                choosers=choosers)
 
         class _ValLoader:
             def __iter__(self_inner):
