@@ -408,6 +408,18 @@ int st_compressor(const float* x, const float* knobs_wc, float sr, int B, int L,
  * sr <= 0; L % 4.  The cutoff is device data and cannot be checked on the host: a cutoff that is not inside (0, sr / 2), or is NaN, makes that
  * row of y all NaN and nothing else. */
 int st_lowpass(const float* x, const float* knobs_wc, float sr, int B, int L, int ysz, float* y, void* stream);
+/* audio.Echo (signaltrain/audio.py:539-547 over echo(), :430-443): y = x plus rint(echoes) delayed copies of it, copy i delayed by i * delay samples
+ * and scaled by ratio^i.  A fractional delay is the reference's two-tap interpolation: with dl = i * delay in float64, D = floor(dl), diff = dl - D,
+ *   y[n] += (float)pow(ratio, i) * ((float)(1 - diff) * x[n - D] + (float)diff * x[n - D - 1]),   x[m] = 0 for m < 0,
+ * in float32 with every product and sum rounded on its own -- what numpy computes on a float32 window (audio.echo is the host restatement, bit for
+ * bit the reference's under numpy 2).  No recurrence: one workgroup per (window, 2048 samples of the tail), reads of the window through L2.
+ *   x [B][L] fp32, knobs_wc [B][3] = (delay in samples, ratio, echoes) in WORLD coordinates, y [B][ysz] = the last ysz samples.  sr is accepted
+ *   (the signature is st_lowpass's and st_compressor_4c's) and not used.  Any L: a delayed read is unaligned anyway.
+ * Asynchronous, no allocation.  Refused before any launch (ST_ERR_ARG, the rule in st_last_error()): a null pointer; B, L, ysz <= 0; ysz > L.  The
+ * knobs are device data and cannot be checked on the host: a delay that is not a finite number >= 1 (the reference raises at 0), rint(echoes)
+ * (half to even) outside 0 .. ST_ECHO_MAX, or a NaN knob makes that row of y all NaN and nothing else. */
+enum { ST_ECHO_MAX = 8 };
+int st_echo(const float* x, const float* knobs_wc, float sr, int B, int L, int ysz, float* y, void* stream);
 /* The input of audio.Denoise (signaltrain/audio.py:558-571: the clean signal is the target, the noisy one the input) for callers that bring
  * their own clean windows:  x_noisy[b][n] = x[b][n] + knobs_wc[b] * (2 u - 1),  u = value n of per-sample stream 11 of window
  * first_window + b of the stream `seed` (the counter-based generator of st_synth_effect), the noise formed and added in float32.  The same
@@ -444,14 +456,24 @@ int st_synth_comp4c(unsigned seed, unsigned long long first_window, int B, int L
  *                 odd in x, so the polarity flip is the compressors'.  knob_lo[0] / knob_hi[0] must satisfy 0 < lo <= hi < sr / 2;
  *   ST_FX_DENOISE audio.Denoise (audio.py:558-571), K == 1 (strength): y is the last ysz samples of the CLEAN window and x leaves with the noise
  *                 of st_denoise_input added (the same bits for the same seed, window, clean x and strength).  0 <= lo <= hi is required.
+ *   ST_FX_ECHO    audio.Echo (audio.py:539-547), K == 3 (delay in samples, ratio, echoes): x is the clean window, y the last ysz samples of st_echo's
+ *                 result.  All three world knobs are float32 Effect.knobs_wc with every step rounded; the delay and the echo count are then rounded to
+ *                 integers, half to even, as Echo.go_wc does: st_echo on the feed's x and those knobs reproduces the feed's y bit for bit.  The ranges
+ *                 must satisfy rint(lo) >= 1 and lo <= hi (delay), finite lo <= hi (ratio), 0 <= rint(lo), rint(hi) <= ST_ECHO_MAX and lo <= hi (echoes).
+ *   ST_FX_DECOMP4C audio.DeCompressor_4c (audio.py:573-583), the inverse problem of ST_FX_COMP4C with its knobs and ranges (1 <= K <= 4): y is the last
+ *                 ysz samples of the CLEAN window and x leaves as compressor_4controls of the clean window over all L samples -- bit for bit
+ *                 st_compressor_4c(clean x, the window's world knobs, ysz = L), and its tail ST_FX_COMP4C's y.  With scratch (ST_FX_COMP4C's size, and
+ *                 L % 64 == 0) the attack / release stage runs one lane per window and a third launch applies the gain over the whole of x; the two forms
+ *                 agree bit for bit.
+ * Both are odd in x like the others, so the polarity flip of the pair stays where it is.
  * The window's draws do not depend on the effect: all four knob draws are made whatever K is, so the clean signal of window w of the stream `seed`
- * is, bit for bit, the x ST_FX_COMP4C produces for the same (seed, w, chooser, augment).  ST_FX_LOWPASS and ST_FX_DENOISE have no second-launch
+ * is, bit for bit, the x ST_FX_COMP4C produces for the same (seed, w, chooser, augment).  ST_FX_LOWPASS, ST_FX_DENOISE and ST_FX_ECHO have no second-launch
  * form: st_synth_effect_scratch_floats answers for them only what the 1/f noise of windows beyond 8192 samples needs (0 up to 8192 samples,
  * where scratch may be NULL).  Their world knob is lo + (knob + 0.5) * (hi - lo) in float32 with every step rounded (what Effect.knobs_wc gives
  * in float32): st_lowpass / st_denoise_input on the feed's x (clean x) and that knob reproduce the feed's y (x) bit for bit.
- * Every window is a function of (seed, window index) only; knobs [B][K].  Wrong ids, knob counts and (for the two one-knob effects, whose ranges
+ * Every window is a function of (seed, window index) only; knobs [B][K].  Wrong ids, knob counts and (for the two one-knob effects and ST_FX_ECHO; the ranges
  * are host arrays) knob ranges are refused before any launch (ST_ERR_ARG, the rule in st_last_error()). */
-enum { ST_FX_COMP4C = 0, ST_FX_COMP = 1, ST_FX_LOWPASS = 2, ST_FX_DENOISE = 3 };
+enum { ST_FX_COMP4C = 0, ST_FX_COMP = 1, ST_FX_LOWPASS = 2, ST_FX_DENOISE = 3, ST_FX_ECHO = 4, ST_FX_DECOMP4C = 5 };
 size_t st_synth_effect_scratch_floats(int effect, int B, int L);
 int st_synth_effect(int effect, unsigned seed, unsigned long long first_window, int B, int L, int ysz, int K, float sr,
                     const float* knob_lo, const float* knob_hi, int augment, int chooser, const float* pink_in,

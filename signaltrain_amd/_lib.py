@@ -60,6 +60,7 @@ SIGNATURES = {
     "st_compressor_4c": (_i, [_p, _p, C.c_float, C.c_int, C.c_int, C.c_int, _p, _p]),
     "st_compressor": (_i, [_p, _p, C.c_float, C.c_int, C.c_int, C.c_int, _p, _p]),
     "st_lowpass": (_i, [_p, _p, C.c_float, C.c_int, C.c_int, C.c_int, _p, _p]),
+    "st_echo": (_i, [_p, _p, C.c_float, C.c_int, C.c_int, C.c_int, _p, _p]),
     "st_denoise_input": (_i, [C.c_uint, C.c_ulonglong, _p, _p, C.c_int, C.c_int, _p, _p]),
     "st_synth_comp4c_scratch_floats": (C.c_size_t, [_i, _i]),
     "st_synth_comp4c": (_i, [C.c_uint, C.c_ulonglong, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float),
@@ -130,7 +131,8 @@ SIGNATURES = {
 }
 
 # effect ids of st_synth_effect (include/signaltrain_hip.h ST_FX_*)
-FX_COMP4C, FX_COMP, FX_LOWPASS, FX_DENOISE = 0, 1, 2, 3
+FX_COMP4C, FX_COMP, FX_LOWPASS, FX_DENOISE, FX_ECHO, FX_DECOMP4C = 0, 1, 2, 3, 4, 5
+ECHO_MAX = 8                      # ST_ECHO_MAX: the most echoes st_echo adds
 # signal-family sets of st_synth_effect_families (ST_FAMILIES_*): bit f allows family f
 FAMILIES_COMPRESSOR, FAMILIES_ALL = 0xD7, 0xFFF
 

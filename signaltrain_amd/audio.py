@@ -2,7 +2,8 @@
 normalised <-> world knob coordinates), the compressor target effects (compressor_4controls :380-426: on the GPU through st_compressor_4c /
 st_synth_effect, on the host through the gcc-built helper for file datasets; compressor :349-371: st_compressor / st_synth_effect, and a
 numpy / scipy restatement on the host), LowPass (:610-625: st_lowpass / st_synth_effect, scipy on the host) and Denoise (:558-571: the noisy signal
-is the input, st_denoise_input / st_synth_effect), wav reading / writing (:207-262) and file-defined effects
+is the input, st_denoise_input / st_synth_effect), Echo (:539-547 over echo() :430-443: st_echo / st_synth_effect, a float32 numpy restatement on
+the host) and DeCompressor_4c (:573-583: the compressed signal is the input, st_compressor_4c / st_synth_effect), wav reading / writing (:207-262) and file-defined effects
 (:624-670).  The synthetic test signals themselves are generated on the GPU (csrc/st_feed.h, audio_device.py); their numpy restatement lives
 on the checker side (oracle/host_audio.py)."""
 import ctypes as C
@@ -76,6 +77,29 @@ def lowpass(x, cutoff, sr=44100.0, order=3):
     return lfilter(b, a, np.asarray(x, dtype=np.float32)).astype(np.float32)
 
 
+def echo(x, delay_samples=1487, ratio=0.6, echoes=1):
+    """audio.py:430-443 (the `echo` effect) on a float32 window: np.round(echoes) copies of x are added to it, copy i delayed by i * delay_samples and
+    scaled by ratio ** i; a fractional delay is a two-tap interpolation between the neighbouring whole delays.  The delay length and the power are
+    Python floats (float64); the window stays float32 and every product and sum is rounded on its own, which is what the reference's expression
+    gives under numpy 2 (Python-float weights on a float32 array) -- bit for bit, tests/golden/g18_echo_decomp.npz.  A delay below one sample is
+    refused (the reference raises on its empty slice there).  The device form is st_echo."""
+    x = np.asarray(x, dtype=np.float32)
+    delay = float(delay_samples)
+    if not (1.0 <= delay < np.inf):
+        raise ValueError(f"echo: delay_samples = {delay_samples!r}: a finite delay of at least one sample is required")
+    L = len(x)
+    y = x.copy()
+    for i in range(1, int(np.round(echoes)) + 1):
+        dl = i * delay
+        D = int(np.floor(dl)); diff = dl - D
+        a = np.zeros(L, dtype=np.float32); b = np.zeros(L, dtype=np.float32)      # x shifted by D and D + 1 samples, zeros in front
+        if D < L: a[D:] = x[:L - D]
+        if D + 1 < L: b[D + 1:] = x[:L - D - 1]
+        xd = np.float32(1 - diff) * a + np.float32(diff) * b
+        y = y + np.float32(pow(float(ratio), i)) * xd
+    return y
+
+
 def _device_effect(fn, effect, x, kw, y_size):
     """y [B, y_size] of the library's effect `fn` (st_compressor_4c / st_compressor) on device tensors x [B, L] with world-coordinate knobs kw [B, K]."""
     import ctypes as C
@@ -96,7 +120,9 @@ class Effect:
     feed_ranges(): the four (low, high) knob rows that feed takes (knobs past len(knob_ranges) are fixed at their low end);
     makes_input: the effect makes the item's input itself (Denoise) -- its go_device returns (y, x_new) and takes seed=, the noise stream;
     feed_choosers: the signal families (audio.synth_input_sample's 0..11) a synthetic dataset of this effect draws from when it is given none;
-    None = the compressor's set {0,1,2,4,6,7} (datasets.py:317)."""
+    None = the compressor's set {0,1,2,4,6,7} (datasets.py:317).
+    Of the reference's eleven effects two are not built: PitchShifter (:549-556) is a call into librosa, which this project does not depend on, and
+    TimeAlign (:585-607) ignores its input and synthesises a hard-coded 4096-sample window, so it fits none of the window sizes train.train uses."""
     feed_fx = None
     makes_input = False
     feed_choosers = None
@@ -229,6 +255,59 @@ class Denoise(Effect):
             _lib.check(_lib.load().st_denoise_input(seed, int(first_window), _lib.ptr(x), _lib.ptr(kw), B, L, _lib.ptr(xn),
                                                     C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)), "st_denoise_input")
         return x[:, L - (L if y_size is None else int(y_size)):].contiguous(), xn
+
+
+class Echo(Effect):
+    """audio.py:539-547: echoes of the signal -- delay in samples, attenuation ratio per echo and the number of echoes (a switch: it is rounded, and
+    so is the delay).  Its signal families are the reference's set "for echo" (datasets.py:320)."""
+    feed_fx = 4                                   # _lib.FX_ECHO
+    feed_choosers = (1, 3, 5, 6, 7)
+
+    def __init__(self, **kwargs):
+        super().__init__(**kwargs)
+        self.name = 'Echo'
+        self.knob_names = ['delay_samples', 'ratio', 'echoes']
+        self.knob_ranges = np.array([[400, 400], [0.4, 1.0], [2, 2]])
+
+    def go_wc(self, x, knobs_w):
+        return echo(x, delay_samples=int(np.round(knobs_w[0])), ratio=knobs_w[1], echoes=int(np.round(knobs_w[2]))), x
+
+    def go_device(self, x, knobs_nn, y_size=None):
+        """Batched effect on the GPU (st_echo): x [B,L] and knobs_nn [B,3] in [-.5,.5] as device tensors -> y [B,y_size] (the last y_size
+        samples); the delay and the echo count are rounded (half to even) as go_wc rounds them.  No CPU fallback."""
+        if x.device.type != "cuda":
+            raise RuntimeError("Echo.go_device needs ROCm device tensors")
+        kw = _knobs_wc_device(self.knob_ranges, knobs_nn, x.device)
+        kw[:, 0] = kw[:, 0].round(); kw[:, 2] = kw[:, 2].round()
+        return _device_effect("st_echo", self, x, kw, y_size)
+
+
+class DeCompressor_4c(Effect):
+    """audio.py:573-583: the inverse problem of Compressor_4c, with its knobs -- the compressed signal is the input and the clean one the target
+    (is_inverse).  go / go_wc / go_device return (target, input) like every effect; the input is NOT the x that came in (makes_input)."""
+    feed_fx = 5                                   # _lib.FX_DECOMP4C
+    makes_input = True
+
+    def __init__(self, **kwargs):
+        super().__init__(**kwargs)
+        sub_effect = Compressor_4c(**kwargs)
+        self.name = 'DeCompressor_4c'
+        self.knob_names = sub_effect.knob_names
+        self.knob_ranges = sub_effect.knob_ranges
+        self.is_inverse = True
+
+    def go_wc(self, x, knobs_w):
+        return x, compressor_4controls(x, thresh=knobs_w[0], ratio=knobs_w[1], attackTime=knobs_w[2], releaseTime=knobs_w[3], sr=self.sr)
+
+    def go_device(self, x, knobs_nn, y_size=None, seed=None):
+        """(y, x_compressed) on the GPU: y [B,y_size] = the last y_size samples of the clean x [B,L], x_compressed [B,L] = st_compressor_4c of the
+        whole window at knobs_wc(knobs_nn [B,4]).  seed is what every makes_input effect is handed (Denoise's noise stream) and is not used.
+        No CPU fallback."""
+        if x.device.type != "cuda":
+            raise RuntimeError("DeCompressor_4c.go_device needs ROCm device tensors")
+        B, L = x.shape
+        xc = _device_effect("st_compressor_4c", self, x, _knobs_wc_device(self.knob_ranges, knobs_nn, x.device), L)
+        return x[:, L - (L if y_size is None else int(y_size)):].to(xc.dtype).contiguous(), xc
 
 
 class Compressor_4c_Large(Compressor_4c):

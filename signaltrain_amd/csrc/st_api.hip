@@ -1961,6 +1961,21 @@ extern "C" int st_lowpass(const float* x, const float* knobs_wc, float sr, int B
     hipLaunchKernelGGL(stm::lowpass_kernel, dim3(B), dim3(256), 0, st_stream(stream), x, knobs_wc, sr, L, ysz, y);
     ST_LAUNCHED("lowpass"); return ST_OK;
 }
+// audio.Echo (audio.py:430-443, :539-547): delayed, attenuated copies of the window added to it (st_echo.h); sr is not used
+extern "C" int st_echo(const float* x, const float* knobs_wc, float sr, int B, int L, int ysz, float* y, void* stream)
+{
+    (void)sr;
+    ST_REQ(x && knobs_wc && y, "st_echo: null pointer");
+    ST_REQ(B > 0 && L > 0 && ysz > 0 && ysz <= L, "st_echo: bad sizes (B=%d L=%d ysz=%d): B > 0 and 0 < ysz <= L are required", B, L, ysz);
+    const int ECHO_SUB = 32768;                              // windows per launch: the grid stays far below 2^31 workgroups
+    const int tiles = (ysz + 2047) / 2048;                   // eight 256-sample trips per workgroup: the taps' float64 powers are worked out once for them
+    for (int b0 = 0; b0 < B; b0 += ECHO_SUB) {
+        const int nb = B - b0 < ECHO_SUB ? B - b0 : ECHO_SUB;
+        hipLaunchKernelGGL(stm::echo_kernel, dim3(nb, tiles < 65535 ? tiles : 65535), dim3(256), 0, st_stream(stream),
+                           x + (size_t)b0 * L, knobs_wc + (size_t)b0 * 3, L, ysz, y + (size_t)b0 * ysz);
+    }
+    ST_LAUNCHED("echo"); return ST_OK;
+}
 // audio.Denoise's input (audio.py:571) for clean windows the caller brings: the noise stream of the feed (stf::denoise_add)
 extern "C" int st_denoise_input(unsigned seed, unsigned long long first_window, const float* x, const float* knobs_wc, int B, int L, float* x_noisy, void* stream)
 {
@@ -1976,12 +1991,12 @@ extern "C" int st_denoise_input(unsigned seed, unsigned long long first_window, 
 // (8192 < L <= 65536), [1/f noise B * L | per-window peaks | four-step FFT buffer 2 * min(B, 1024) * L]
 static const int FEED_FFT_SUB = 1024;      // windows per pass-1 / pass-2 launch pair of the long-window noise (a launch pair costs ~50 us whatever its size: few, large ones)
 static bool feed_long_fft(int L) { return L > stf::FFT_MAX && (L & (L - 1)) == 0 && L / stf::PL_N1 <= 256; }
-static bool feed_effect_ok(int effect) { return effect == ST_FX_COMP4C || effect == ST_FX_COMP || effect == ST_FX_LOWPASS || effect == ST_FX_DENOISE; }
-static bool feed_effect_splits(int effect) { return effect == ST_FX_COMP4C || effect == ST_FX_COMP; }      // has a lane-per-window / second-launch form through the scratch
+static bool feed_effect_ok(int effect) { return effect >= ST_FX_COMP4C && effect <= ST_FX_DECOMP4C; }
+static bool feed_effect_splits(int effect) { return effect == ST_FX_COMP4C || effect == ST_FX_COMP || effect == ST_FX_DECOMP4C; }      // has a lane-per-window / second-launch form through the scratch
 extern "C" size_t st_synth_effect_scratch_floats(int effect, int B, int L)
 {
     if (!feed_effect_ok(effect) || B <= 0 || L <= 0) return 0;
-    size_t n = feed_effect_splits(effect) ? (size_t)B * (L + 4) : 0;      // the compressors: [gain curve or dB signal B * L | world knobs 4 B]; ST_FX_LOWPASS / ST_FX_DENOISE: only the long windows' noise
+    size_t n = feed_effect_splits(effect) ? (size_t)B * (L + 4) : 0;      // the compressors: [gain curve or dB signal B * L | world knobs 4 B]; ST_FX_LOWPASS / ST_FX_DENOISE / ST_FX_ECHO: only the long windows' noise
     if (feed_long_fft(L)) n += (size_t)B * L + (size_t)st_round_up(B, 64) + (size_t)2 * (B < FEED_FFT_SUB ? B : FEED_FFT_SUB) * L;
     return n;
 }
@@ -2000,7 +2015,8 @@ static int feed_launch(const stf::FeedArgs& a, int B, size_t lds, void* stream)
         }
     }
     hipLaunchKernelGGL((stf::synth_feed_kernel<FX, EXT>), dim3(B), dim3(256), lds, st_stream(stream), a);
-    ST_LAUNCHED(FX == ST_FX_COMP ? "synth_comp" : FX == ST_FX_LOWPASS ? "synth_lowpass" : FX == ST_FX_DENOISE ? "synth_denoise" : "synth_comp4c"); return ST_OK;
+    ST_LAUNCHED(FX == ST_FX_COMP ? "synth_comp" : FX == ST_FX_LOWPASS ? "synth_lowpass" : FX == ST_FX_DENOISE ? "synth_denoise" : FX == ST_FX_ECHO ? "synth_echo" :
+                FX == ST_FX_DECOMP4C ? "synth_decomp4c" : "synth_comp4c"); return ST_OK;
 }
 template <int FX>
 static int feed_launch_fx(bool ext, const stf::FeedArgs& a, int B, size_t lds, void* stream)
@@ -2012,16 +2028,26 @@ static int synth_effect_run(const char* who, int effect, unsigned families, bool
                             int K, float sr, const float* knob_lo, const float* knob_hi, int augment, int chooser, const float* pink_in,
                             float* x, float* y, float* knobs, float* scratch, void* stream)
 {
-    ST_REQ(feed_effect_ok(effect), "%s: effect %d is not an ST_FX_* id (ST_FX_COMP4C = 0, ST_FX_COMP = 1, ST_FX_LOWPASS = 2, ST_FX_DENOISE = 3)", who, effect);
+    ST_REQ(feed_effect_ok(effect), "%s: effect %d is not an ST_FX_* id (ST_FX_COMP4C = 0, ST_FX_COMP = 1, ST_FX_LOWPASS = 2, ST_FX_DENOISE = 3, ST_FX_ECHO = 4, ST_FX_DECOMP4C = 5)", who, effect);
     ST_REQ(effect != ST_FX_COMP4C || (K >= 1 && K <= 4), "%s: ST_FX_COMP4C takes 1 to 4 knobs, not K=%d", who, K);
     ST_REQ(effect != ST_FX_COMP || K == 3, "%s: ST_FX_COMP takes 3 knobs (threshold, ratio, attack/release), not K=%d", who, K);
     ST_REQ(effect != ST_FX_LOWPASS || K == 1, "%s: ST_FX_LOWPASS takes 1 knob (cutoff Hz), not K=%d", who, K);
     ST_REQ(effect != ST_FX_DENOISE || K == 1, "%s: ST_FX_DENOISE takes 1 knob (strength), not K=%d", who, K);
-    // the one-knob effects' ranges (host arrays): checked as soon as they are there, before the device pointers
+    ST_REQ(effect != ST_FX_ECHO || K == 3, "%s: ST_FX_ECHO takes 3 knobs (delay in samples, ratio, echoes), not K=%d", who, K);
+    ST_REQ(effect != ST_FX_DECOMP4C || (K >= 1 && K <= 4), "%s: ST_FX_DECOMP4C takes 1 to 4 knobs, not K=%d", who, K);
+    // the one-knob effects' and the echo's ranges (host arrays): checked as soon as they are there, before the device pointers
     ST_REQ(effect != ST_FX_LOWPASS || !knob_lo || !knob_hi || (knob_lo[0] > 0.f && knob_lo[0] <= knob_hi[0] && knob_hi[0] < 0.5f * sr),
            "%s: ST_FX_LOWPASS needs a cutoff range with 0 < lo <= hi < sr / 2 (lo=%g hi=%g sr=%g)", who, knob_lo[0], knob_hi[0], sr);
     ST_REQ(effect != ST_FX_DENOISE || !knob_lo || !knob_hi || (knob_lo[0] >= 0.f && knob_lo[0] <= knob_hi[0]),
            "%s: ST_FX_DENOISE needs a strength range with 0 <= lo <= hi (lo=%g hi=%g)", who, knob_lo[0], knob_hi[0]);
+    if (effect == ST_FX_ECHO && knob_lo && knob_hi) {      // the delay and the echo count are rounded half to even (Echo.go_wc), so the rounded ends decide
+        ST_REQ(rintf(knob_lo[0]) >= 1.f && knob_lo[0] <= knob_hi[0] && knob_hi[0] <= 3.402823466e38f,
+               "%s: ST_FX_ECHO needs a delay range with 1 <= rint(lo), lo <= hi, finite (lo=%g hi=%g)", who, knob_lo[0], knob_hi[0]);
+        ST_REQ(fabsf(knob_lo[1]) <= 3.402823466e38f && fabsf(knob_hi[1]) <= 3.402823466e38f && knob_lo[1] <= knob_hi[1],
+               "%s: ST_FX_ECHO needs a finite ratio range with lo <= hi (lo=%g hi=%g)", who, knob_lo[1], knob_hi[1]);
+        ST_REQ(rintf(knob_lo[2]) >= 0.f && rintf(knob_hi[2]) <= (float)ST_ECHO_MAX && knob_lo[2] <= knob_hi[2],
+               "%s: ST_FX_ECHO needs an echoes range with 0 <= rint(lo), rint(hi) <= ST_ECHO_MAX = %d, lo <= hi (lo=%g hi=%g)", who, (int)ST_ECHO_MAX, knob_lo[2], knob_hi[2]);
+    }
     ST_REQ(x && y && knobs && knob_lo && knob_hi, "%s: null pointer", who);
     ST_REQ(B > 0 && L > 0 && ysz > 0 && ysz <= L && sr > 0.f, "%s: bad sizes (B=%d L=%d ysz=%d K=%d)", who, B, L, ysz, K);
     ST_REQ(any_family || chooser == -1 || chooser == 0 || chooser == 1 || chooser == 2 || chooser == 4 || chooser == 6 || chooser == 7 || chooser == 100, "%s: signal family %d is not built (the compressor's set is 0,1,2,4,6,7)", who, chooser);
@@ -2055,9 +2081,21 @@ static int synth_effect_run(const char* who, int effect, unsigned families, bool
     // dynamic LDS: the in-LDS FFT's buffer, else the in-kernel effect's (compressor_window's float[COMP_CH] holds the envelope scan's EnvLds as well)
     static_assert(sizeof(stm::EnvLds) <= (size_t)stm::COMP_CH * sizeof(float), "the envelope scan's LDS must fit the in-kernel effect's buffer");
     static_assert(sizeof(stm::LpLds) <= (size_t)stm::COMP_CH * sizeof(float), "the low-pass scan's LDS must fit the in-kernel effect's buffer");
+    static_assert(sizeof(stm::EchoLds) <= (size_t)stm::COMP_CH * sizeof(float), "the echo's taps must fit the in-kernel effect's buffer");
     const size_t lds = a.pink_in ? (split ? 0 : (size_t)stm::COMP_CH * sizeof(float)) : (size_t)stf::FFT_MAX * sizeof(float2);
     if (effect == ST_FX_LOWPASS) return feed_launch_fx<ST_FX_LOWPASS>(ext, a, B, lds, stream);
     if (effect == ST_FX_DENOISE) return feed_launch_fx<ST_FX_DENOISE>(ext, a, B, lds, stream);
+    if (effect == ST_FX_ECHO) return feed_launch_fx<ST_FX_ECHO>(ext, a, B, lds, stream);
+    if (effect == ST_FX_DECOMP4C) {
+        ST_TRY(feed_launch_fx<ST_FX_DECOMP4C>(ext, a, B, lds, stream));
+        if (split) {      // the target, the clean tail, is out; the window in x becomes the compressed one
+            hipLaunchKernelGGL(stm::comp_smooth_kernel, dim3((B + 63) / 64), dim3(64), 0, st_stream(stream), a.gc, a.kw, sr, B, L);
+            ST_LAUNCHED("comp_smooth");
+            hipLaunchKernelGGL(stm::comp_apply_inplace_kernel, dim3((L + 2047) / 2048 < 65535 ? (L + 2047) / 2048 : 65535, B), dim3(256), 0, st_stream(stream), x, a.gc, L);
+            ST_LAUNCHED("comp_apply_inplace");
+        }
+        return ST_OK;
+    }
     if (effect == ST_FX_COMP) {
         ST_TRY(feed_launch_fx<ST_FX_COMP>(ext, a, B, lds, stream));
         if (split) {

@@ -14,6 +14,8 @@
 //          linear envelope runs as a parallel scan (stm::env_compressor_window).  1 <= K <= 4 knobs: the ones past K are fixed at their low end.
 //          ST_FX_LOWPASS (audio.py:610-625): the third-order Butterworth low-pass as a scan over the filter's modes (stm::lowpass_window, st_filter.h).
 //          ST_FX_DENOISE (audio.py:558-571): the target is the clean window's tail and x leaves with strength * (2u - 1) added (denoise_add).
+//          ST_FX_ECHO (audio.py:430-443, :539-547): delayed copies of the finished window added to its tail (stm::echo_window, st_echo.h).
+//          ST_FX_DECOMP4C (audio.py:573-583): the target is the clean window's tail and x leaves as the 4-control compressor of the whole window.
 // Output contract: x [B][L], y [B][ysz], knobs [B][K] in [-0.5, 0.5] (float32), as the reference's collated batch (train.py:104-120 casts y to float).
 // Parity is DISTRIBUTIONAL (another generator than numpy's): tests compare per-family peak ranges, the even symmetry and 1/f slope of the noise,
 // the box structure, the Beta(0.8, 0.8) law, and the compressor against golden G9 through the same device function.
@@ -44,6 +46,7 @@
 #include "st_common.h"
 #include "st_misc.h"
 #include "st_filter.h"
+#include "st_echo.h"
 
 namespace stf {
 
@@ -137,6 +140,7 @@ struct FeedArgs {
     int augment;
     float* gc; float* kw;                   // optional scratch [B][L] + [B][4]: the generator leaves the gain curve (ST_FX_COMP: the dB signal) and the world-coordinate knobs there and
                                             // stm::comp_smooth_apply_kernel finishes the effect (lane per window); NULL: the effect runs inside this kernel
+                                            // (ST_FX_DECOMP4C: comp_smooth_kernel, then comp_apply_inplace_kernel over the whole of x)
     int chooser;                            // -1: drawn per window from `families`; else forced (tests); 100 = the bare 1/f noise (tests)
     unsigned families;                      // bit f allows family f (synth_feed_kernel<FX, true>; the <FX, false> kernel draws from {0, 1, 2, 4, 6, 7})
 };
@@ -323,6 +327,11 @@ synth_feed_kernel(const FeedArgs a)
     for (int k = a.K; k < 4; ++k) kw[k] = a.lo[k];                   // K < 4: the remaining knobs are fixed settings (all four are drawn: one stream for every K)
     if (FX == ST_FX_LOWPASS || FX == ST_FX_DENOISE)                  // the one knob as float32 Effect.knobs_wc gives it, every step rounded: st_lowpass / st_denoise_input
         kw[0] = world_knob_f32(a.lo[0], a.hi[0], kn[0]);                                             // on (x, these knobs) reproduce the feed bit for bit
+    if (FX == ST_FX_ECHO) {                                          // Echo.go_wc (audio.py:547): float32 world knobs, the delay and the echo count rounded half to even;
+        kw[0] = rintf(world_knob_f32(a.lo[0], a.hi[0], kn[0]));      // st_echo on (x, these knobs) reproduces the feed bit for bit
+        kw[1] = world_knob_f32(a.lo[1], a.hi[1], kn[1]);
+        kw[2] = rintf(world_knob_f32(a.lo[2], a.hi[2], kn[2]));
+    }
     // randsine (audio.py:96-104)
     const int s_n = d.randint(1, 3);
     float s_amp[2], s_frq[2], s_t0[2];
@@ -465,13 +474,15 @@ synth_feed_kernel(const FeedArgs a)
                 else pk = make_float4(fa[n].x * inv_peak, fa[n + 1].x * inv_peak, fa[n + 2].x * inv_peak, fa[n + 3].x * inv_peak);
             }
             float4 v = make_float4(sample(n, pk.x), sample(n + 1, pk.y), sample(n + 2, pk.z), sample(n + 3, pk.w));
-            if (FX == ST_FX_DENOISE) {                               // the target is the clean tail, the input leaves with the noise on it
+            if (FX == ST_FX_DENOISE || FX == ST_FX_DECOMP4C) {       // the target is the clean tail ...
                 float* __restrict__ yb = a.y + (size_t)b * a.ysz;
                 const int j = n - (L - a.ysz);
                 if (j >= 0) yb[j] = v.x;
                 if (j + 1 >= 0) yb[j + 1] = v.y;
                 if (j + 2 >= 0) yb[j + 2] = v.z;
                 if (j + 3 >= 0) yb[j + 3] = v.w;
+            }
+            if (FX == ST_FX_DENOISE) {                               // ... and the input leaves with the noise on it
                 v = make_float4(denoise_add(key, (unsigned)n, kw[0], v.x), denoise_add(key, (unsigned)n + 1u, kw[0], v.y),
                                 denoise_add(key, (unsigned)n + 2u, kw[0], v.z), denoise_add(key, (unsigned)n + 3u, kw[0], v.w));
             }
@@ -486,10 +497,8 @@ synth_feed_kernel(const FeedArgs a)
         for (int n = threadIdx.x; n < L; n += 256) {
             const float pk = want_pink ? (pin ? (a.pink_peak ? pin[n] * inv_peak : pin[n]) : fa[n].x * inv_peak) : 0.f;
             float v = sample(n, pk);
-            if (FX == ST_FX_DENOISE) {
-                if (n >= L - a.ysz) a.y[(size_t)b * a.ysz + n - (L - a.ysz)] = v;
-                v = denoise_add(key, (unsigned)n, kw[0], v);
-            }
+            if ((FX == ST_FX_DENOISE || FX == ST_FX_DECOMP4C) && n >= L - a.ysz) a.y[(size_t)b * a.ysz + n - (L - a.ysz)] = v;
+            if (FX == ST_FX_DENOISE) v = denoise_add(key, (unsigned)n, kw[0], v);
             xb[n] = v;
             if (gcb) gcb[n] = FX == ST_FX_COMP ? stm::env_db(v) : stm::comp_gain_curve(v, (double)kw[0], (double)kw[1]);
         }
@@ -506,6 +515,10 @@ synth_feed_kernel(const FeedArgs a)
         stm::lowpass_window(xb, a.y + (size_t)b * a.ysz, stm::lowpass_coef((double)kw[0], (double)a.sr), L, a.ysz, reinterpret_cast<stm::LpLds*>(feed_lds));
         return;
     }
+    if (FX == ST_FX_ECHO) {                                          // the echo (audio.py:430-443): reads of the finished window, no recurrence
+        stm::echo_window(xb, a.y + (size_t)b * a.ysz, kw[0], kw[1], kw[2], L, a.ysz, 0, 256, reinterpret_cast<stm::EchoLds*>(feed_lds));
+        return;
+    }
     if (FX == ST_FX_COMP) {                                          // the envelope compressor (audio.py:349-371), a scan over the window
         stm::env_compressor_window(xb, nullptr, a.y + (size_t)b * a.ysz, (double)kw[0], (double)kw[1], stm::env_coef((double)kw[2], (double)a.sr),
                                    L, a.ysz, reinterpret_cast<stm::EnvLds*>(feed_lds));
@@ -513,6 +526,10 @@ synth_feed_kernel(const FeedArgs a)
     }
     // ---- the effect (audio.py:380-426) on the finished window, inside this workgroup
     const double alphaA = exp(-log(9.0) / ((double)a.sr * (double)kw[2])), alphaR = exp(-log(9.0) / ((double)a.sr * (double)kw[3]));
+    if (FX == ST_FX_DECOMP4C) {                                      // the compressed window is the item's input (audio.py:573-583): over the whole of x, in place
+        stm::compressor_window_inplace(xb, (double)kw[0], (double)kw[1], alphaA, alphaR, L, feed_lds, &carry);
+        return;
+    }
     stm::compressor_window(xb, a.y + (size_t)b * a.ysz, (double)kw[0], (double)kw[1], alphaA, alphaR, L, a.ysz, feed_lds, &carry);
 }
 

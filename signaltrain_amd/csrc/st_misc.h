@@ -869,10 +869,12 @@ __device__ __forceinline__ float comp_gain_curve(const float xv, const double th
 // dB -> linear (audio.py:421): np.power(10.0, lin_A / 20) on a float32 array
 __device__ __forceinline__ float comp_db_to_lin(const float g) { return exp10f(g / 20.0f); }
 constexpr int COMP_CH = 8192;
-// one window; g: LDS float[COMP_CH], carry: LDS float.  Called by every thread of a 256-thread workgroup.
+// one window; g: LDS float[COMP_CH], carry: LDS float.  Called by every thread of a 256-thread workgroup.  XP / YP: the window's and the result's pointer
+// types -- __restrict__-qualified in compressor_window, plain in compressor_window_inplace, where the two are one buffer.
+template <typename XP, typename YP>
 __device__ __forceinline__ void
-compressor_window(const float* __restrict__ xb, float* __restrict__ yb, const double thresh, const double ratio, const double alphaA, const double alphaR,
-                  const int L, const int ysz, float* __restrict__ g, float* __restrict__ carry_p)
+compressor_window_body(XP xb, YP yb, const double thresh, const double ratio, const double alphaA, const double alphaR,
+                       const int L, const int ysz, float* __restrict__ g, float* __restrict__ carry_p)
 {
     if (threadIdx.x == 0) *carry_p = 0.f;
     for (int c0 = 0; c0 < L; c0 += COMP_CH) {
@@ -913,6 +915,20 @@ compressor_window(const float* __restrict__ xb, float* __restrict__ yb, const do
         }
         __syncthreads();
     }
+}
+__device__ __forceinline__ void
+compressor_window(const float* __restrict__ xb, float* __restrict__ yb, const double thresh, const double ratio, const double alphaA, const double alphaR,
+                  const int L, const int ysz, float* __restrict__ g, float* __restrict__ carry_p)
+{
+    compressor_window_body<const float* __restrict__, float* __restrict__>(xb, yb, thresh, ratio, alphaA, alphaR, L, ysz, g, carry_p);
+}
+// The whole compressed window written over the window itself (ST_FX_DECOMP4C: the compressed signal is the item's input).  Sound because a chunk's
+// samples are read into the gain curve and applied by the thread that reads them, and no later chunk looks back; the pointers carry no __restrict__.
+__device__ __forceinline__ void
+compressor_window_inplace(float* xyb, const double thresh, const double ratio, const double alphaA, const double alphaR, const int L,
+                          float* __restrict__ g, float* __restrict__ carry_p)
+{
+    compressor_window_body<const float*, float*>(xyb, xyb, thresh, ratio, alphaA, alphaR, L, L, g, carry_p);
 }
 // The same effect with the sequential stage turned sideways: ONE LANE PER WINDOW, 64 windows per wave.  In compressor_window the attack /
 // release recurrence runs in one lane while the other 255 threads of the workgroup (and its LDS) wait -- 8192 dependent float64 steps, ~240 us
@@ -982,6 +998,13 @@ comp_apply_kernel(const float* __restrict__ x, const float* __restrict__ g, cons
     if (j >= ysz) return;
     const size_t i = (size_t)b * L + (L - ysz) + j;
     y[(size_t)b * ysz + j] = comp_db_to_lin(g[i]) * x[i];
+}
+// ... over the whole window, in place (ST_FX_DECOMP4C's second-launch form): x[b][n] *= 10^(g[b][n] / 20).  Each sample is read and written by one thread.
+__global__ void __launch_bounds__(256)
+comp_apply_inplace_kernel(float* x, const float* __restrict__ g, const int L)
+{
+    const size_t r = (size_t)blockIdx.y * L;
+    for (int n = blockIdx.x * 256 + threadIdx.x; n < L; n += gridDim.x * 256) x[r + n] = comp_db_to_lin(g[r + n]) * x[r + n];
 }
 __global__ void __launch_bounds__(256)
 compressor_4c_kernel(const float* __restrict__ x, const float* __restrict__ knobs_wc, float sr, int L, int ysz, float* __restrict__ y)

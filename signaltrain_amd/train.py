@@ -238,7 +238,7 @@ def train(effect=None, epochs=100, n_data_points=200000, batch_size=20, device=N
             dataloader_val = DataLoader(dataset_val, batch_size=batch_size, num_workers=num_workers, shuffle=False, drop_last=True)
     else:
         # synthetic effect: every training minibatch is generated ON the GPU (one st_synth_effect call per minibatch for the effects
-        # with a fused feed: the compressors, LowPass, Denoise), as the reference's non-recycled dataset does on its CPU workers (train.py:233-248); device_feed="recycle": one dataset
+        # with a fused feed: the compressors, LowPass, Denoise, Echo, DeCompressor_4c), as the reference's non-recycled dataset does on its CPU workers (train.py:233-248); device_feed="recycle": one dataset
         # generated up front and re-sampled by index each epoch (the reference's recycle=True mode); device_feed=False: the reference's CPU-worker
         # DataLoader (~100 windows/s per core against 3-8 x 10^5 per second for the step).
         # Validation: the reference's recycled set (train.py:237-238), resident in HBM.
