@@ -510,6 +510,30 @@ int st_file_feed(unsigned seed, unsigned long long first_window, int B, int L, i
                  long long min_len, long long pool_samples, const float* file_knobs, int augment,
                  float* x, float* y, float* knobs, long long* meta, void* stream);
 
+/* One training minibatch of RECORDED input through a LIVE effect (st_feed_live.h): per window a span of st_file_feed's audio pool (pool_x, file_off,
+ * file_len, nfiles, min_len, pool_samples and fmt as there; no target pool), knobs drawn for that window, and the effect `effect` (an ST_FX_* id; K, knob_lo /
+ * knob_hi, sr, ysz as st_synth_effect) applied on the spot.  Window b of the call is window w = first_window + b of the stream `seed`; its four scalar
+ * draws -- the law is written out in st_feed_live.h, datasets.live_feed_draw replicates it -- decide
+ *   synthetic  with probability synth_prob (0: never, 1: always): the row is then, bit for bit, row w of st_synth_effect_families(effect, family_mask, seed, ...);
+ *   file, start, flipped   else: x = +-pool_x[file_off[file] + start .. + L) (minus where `augment` and flipped; no 1e-8 noise, no random polarity),
+ *              knobs = Beta(0.8, 0.8) - 0.5 per window, y / x by the effect as in st_synth_effect (ST_FX_DENOISE, ST_FX_DECOMP4C: y is the clean tail and x
+ *              leaves with the noise on it / compressed), so the library's effect entries on (x, world knobs) reproduce the row.
+ * x [B][L], y [B][ysz], knobs [B][K]; meta [B][4] = (synthetic, file, start, flipped) of every window, or NULL.  Every row is a function of (seed, w) and
+ * the pool only, whatever the batching and the other rows.  scratch: st_live_feed_scratch_floats(effect, B, L, synth_prob) floats, or NULL.  With it
+ * (and L % 64 == 0) the compressor effects run their sequential stage through the scratch, as st_synth_effect does, with the same bits as without:
+ * [gain curve or dB signal B * L | world knobs 4 B] are left there.  With synth_prob == 0 no synthetic kernel is launched and no window length needs a
+ * scratch; with synth_prob > 0 the scratch is st_synth_effect_scratch_floats(effect, B, L) and windows beyond 8192 samples require it.
+ * Refused before any launch (ST_ERR_ARG, the rule in st_last_error()): everything st_synth_effect refuses about the effect, K, the knob ranges and the
+ * sizes; everything st_file_feed refuses about the pool (fmt, nfiles, min_len <= L, pool_samples < min_len, null tables, L % 4, ysz % 4); synth_prob outside
+ * [0, 1] or NaN; and with synth_prob > 0 what st_synth_effect_families refuses about family_mask.  No address outside the pool is formed even from wrong tables. */
+size_t st_live_feed_scratch_floats(int effect, int B, int L, float synth_prob);
+int st_live_feed(int effect, unsigned family_mask, float synth_prob, unsigned seed, unsigned long long first_window,
+                 int B, int L, int ysz, int K, float sr, const float* knob_lo, const float* knob_hi, int augment,
+                 int fmt, const void* pool_x, const long long* file_off, const long long* file_len, int nfiles,
+                 long long min_len, long long pool_samples,
+                 float* x, float* y, float* knobs, long long* meta /* [B][4] kind, file, start, flipped; may be NULL */,
+                 float* scratch, void* stream);
+
 /* Gradient of the loss w.r.t. the (halved) input waveform, for callers with something trainable upstream of the model (the reference's
  * autograd provides it; nn_proc.py:307, cls_fe_dft.py:55-56).  Call right after st_model_bwd on the SAME workspace:
  *   gxh[b][n] = conv-transpose of the analysis output gradient with both bases, cropped by the Conv1d padding   [B][L]

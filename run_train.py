@@ -32,6 +32,9 @@ if __name__ == "__main__":
     p.add_argument('--effect', help="effect to learn, the reference's keys (run_train.py:55-80): comp_4c | comp_large | comp | comp_t | comp_one | files are built here "
                    "(comp_4c_large is kept as an alias of comp_large); the reference's other keys are named in the error message", default='comp_4c')
     p.add_argument('--epochs', type=int, default=1000)
+    p.add_argument('--inpath', metavar='DIR', default=None, help="directory with Train/ and Val/ folders of recorded INPUT audio (*.wav, names without 'target'): train on "
+                   "windows of it through the live --effect with knobs drawn per window (st_live_feed), instead of synthetic signals")
+    p.add_argument('--synthprob', metavar='P', type=float, default=0.0, help="with --inpath: the share of windows that are synthetic test signals instead, 0 to 1")
     p.add_argument('--lrmax', type=float, help="maximum learning rate", default=1e-4)
     p.add_argument('-n', '--num', type=int, help='number of data points per epoch', default=200000)
     p.add_argument('--path', help='dataset directory with Train/, Val/ wav pairs and effect_info.ini (use with --effect files)', default=None)
@@ -51,6 +54,12 @@ if __name__ == "__main__":
         raise SystemExit(f"Effect option '{args.effect}' is not yet added (available: {', '.join(k for k in EFFECTS if k != 'comp_4c_large')})")       # run_train.py:79-80
     if args.target not in ("chunk", "stream"):
         raise SystemExit(f"Error, invalid target type: {args.target}")                # run_train.py:90-92
+    if not 0.0 <= args.synthprob <= 1.0:
+        raise SystemExit(f"--synthprob {args.synthprob}: a probability, 0 to 1")
+    if args.synthprob and args.inpath is None:
+        raise SystemExit(f"--synthprob {args.synthprob} mixes synthetic windows into recorded input: give --inpath DIR as well")
+    if args.inpath is not None and args.effect == 'files':
+        raise SystemExit("--inpath runs a live effect on recorded input; --effect files trains on recorded input / target pairs (--path): give one")
 
     import torch.distributed as dist
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -69,6 +78,7 @@ if __name__ == "__main__":
     train.train(epochs=args.epochs, n_data_points=args.num, batch_size=args.batch, device=torch.device("cuda", local),
                 effect=effect, datapath=(args.path if args.effect == 'files' else None), sr=args.sr, scale_factor=args.scale, shrink_factor=args.shrink, apex_opt=args.apex,
                 target_type=args.target, lr_max=args.lrmax, in_checkpointname=args.checkpoint, compand=args.compand,
-                compute_dtype=args.dtype, device_feed=args.device_feed, resume_optimizer=args.resume_optimizer, device_eval=args.device_eval, choosers=args.choosers)
+                compute_dtype=args.dtype, device_feed=args.device_feed, resume_optimizer=args.resume_optimizer, device_eval=args.device_eval, choosers=args.choosers,
+                input_path=args.inpath, synth_prob=args.synthprob)
     if dist.is_initialized():
         dist.destroy_process_group()

@@ -22,6 +22,7 @@
 #include "st_dp.h"
 #include "st_feed.h"
 #include "st_feed_files.h"
+#include "st_feed_live.h"
 
 // ------------------------------------------------------------------------------ errors
 static thread_local char g_err[512] = "";
@@ -2023,10 +2024,8 @@ static int feed_launch_fx(bool ext, const stf::FeedArgs& a, int B, size_t lds, v
 {
     return ext ? feed_launch<FX, true>(a, B, lds, stream) : feed_launch<FX, false>(a, B, lds, stream);
 }
-// st_synth_effect (families = the compressor's set, today's family rule) and st_synth_effect_families (who names the entry in the messages)
-static int synth_effect_run(const char* who, int effect, unsigned families, bool any_family, unsigned seed, unsigned long long first_window, int B, int L, int ysz,
-                            int K, float sr, const float* knob_lo, const float* knob_hi, int augment, int chooser, const float* pink_in,
-                            float* x, float* y, float* knobs, float* scratch, void* stream)
+// what every feed refuses about the effect, its knob count and (host arrays, checked as soon as they are there) its knob ranges
+static int feed_effect_check(const char* who, int effect, int K, float sr, const float* knob_lo, const float* knob_hi)
 {
     ST_REQ(feed_effect_ok(effect), "%s: effect %d is not an ST_FX_* id (ST_FX_COMP4C = 0, ST_FX_COMP = 1, ST_FX_LOWPASS = 2, ST_FX_DENOISE = 3, ST_FX_ECHO = 4, ST_FX_DECOMP4C = 5)", who, effect);
     ST_REQ(effect != ST_FX_COMP4C || (K >= 1 && K <= 4), "%s: ST_FX_COMP4C takes 1 to 4 knobs, not K=%d", who, K);
@@ -2048,6 +2047,34 @@ static int synth_effect_run(const char* who, int effect, unsigned families, bool
         ST_REQ(rintf(knob_lo[2]) >= 0.f && rintf(knob_hi[2]) <= (float)ST_ECHO_MAX && knob_lo[2] <= knob_hi[2],
                "%s: ST_FX_ECHO needs an echoes range with 0 <= rint(lo), rint(hi) <= ST_ECHO_MAX = %d, lo <= hi (lo=%g hi=%g)", who, (int)ST_ECHO_MAX, knob_lo[2], knob_hi[2]);
     }
+    return ST_OK;
+}
+// the second launches of the compressors' form through the scratch (gc [B][L] gain curve or dB signal, kw [B][4] world knobs): once per row, comp_smooth_kernel works in place
+static int feed_effect_finish(int effect, int B, int L, int ysz, float sr, float* x, float* y, float* gc, const float* kw, void* stream)
+{
+    if (effect == ST_FX_DECOMP4C) {      // the target, the clean tail, is out; the window in x becomes the compressed one
+        hipLaunchKernelGGL(stm::comp_smooth_kernel, dim3((B + 63) / 64), dim3(64), 0, st_stream(stream), gc, kw, sr, B, L);
+        ST_LAUNCHED("comp_smooth");
+        hipLaunchKernelGGL(stm::comp_apply_inplace_kernel, dim3((L + 2047) / 2048 < 65535 ? (L + 2047) / 2048 : 65535, B), dim3(256), 0, st_stream(stream), x, gc, L);
+        ST_LAUNCHED("comp_apply_inplace");
+    } else if (effect == ST_FX_COMP) {
+        hipLaunchKernelGGL(stm::compressor_env_kernel, dim3(B), dim3(256), 0, st_stream(stream), x, gc, kw, 4, sr, L, ysz, y);
+        ST_LAUNCHED("compressor_env");
+    } else if (effect == ST_FX_COMP4C) {
+        hipLaunchKernelGGL(stm::comp_smooth_kernel, dim3((B + 63) / 64), dim3(64), 0, st_stream(stream), gc, kw, sr, B, L);
+        ST_LAUNCHED("comp_smooth");
+        hipLaunchKernelGGL(stm::comp_apply_kernel, dim3((ysz + 255) / 256, B), dim3(256), 0, st_stream(stream), x, gc, L, ysz, y);
+        ST_LAUNCHED("comp_apply");
+    }
+    return ST_OK;
+}
+// st_synth_effect (families = the compressor's set, today's family rule) and st_synth_effect_families (who names the entry in the messages).
+// finish = false (st_live_feed): the generator only -- the caller runs feed_effect_finish after it has replaced rows
+static int synth_effect_run(const char* who, int effect, unsigned families, bool any_family, unsigned seed, unsigned long long first_window, int B, int L, int ysz,
+                            int K, float sr, const float* knob_lo, const float* knob_hi, int augment, int chooser, const float* pink_in,
+                            float* x, float* y, float* knobs, float* scratch, void* stream, bool finish = true)
+{
+    ST_TRY(feed_effect_check(who, effect, K, sr, knob_lo, knob_hi));
     ST_REQ(x && y && knobs && knob_lo && knob_hi, "%s: null pointer", who);
     ST_REQ(B > 0 && L > 0 && ysz > 0 && ysz <= L && sr > 0.f, "%s: bad sizes (B=%d L=%d ysz=%d K=%d)", who, B, L, ysz, K);
     ST_REQ(any_family || chooser == -1 || chooser == 0 || chooser == 1 || chooser == 2 || chooser == 4 || chooser == 6 || chooser == 7 || chooser == 100, "%s: signal family %d is not built (the compressor's set is 0,1,2,4,6,7)", who, chooser);
@@ -2086,32 +2113,10 @@ static int synth_effect_run(const char* who, int effect, unsigned families, bool
     if (effect == ST_FX_LOWPASS) return feed_launch_fx<ST_FX_LOWPASS>(ext, a, B, lds, stream);
     if (effect == ST_FX_DENOISE) return feed_launch_fx<ST_FX_DENOISE>(ext, a, B, lds, stream);
     if (effect == ST_FX_ECHO) return feed_launch_fx<ST_FX_ECHO>(ext, a, B, lds, stream);
-    if (effect == ST_FX_DECOMP4C) {
-        ST_TRY(feed_launch_fx<ST_FX_DECOMP4C>(ext, a, B, lds, stream));
-        if (split) {      // the target, the clean tail, is out; the window in x becomes the compressed one
-            hipLaunchKernelGGL(stm::comp_smooth_kernel, dim3((B + 63) / 64), dim3(64), 0, st_stream(stream), a.gc, a.kw, sr, B, L);
-            ST_LAUNCHED("comp_smooth");
-            hipLaunchKernelGGL(stm::comp_apply_inplace_kernel, dim3((L + 2047) / 2048 < 65535 ? (L + 2047) / 2048 : 65535, B), dim3(256), 0, st_stream(stream), x, a.gc, L);
-            ST_LAUNCHED("comp_apply_inplace");
-        }
-        return ST_OK;
-    }
-    if (effect == ST_FX_COMP) {
-        ST_TRY(feed_launch_fx<ST_FX_COMP>(ext, a, B, lds, stream));
-        if (split) {
-            hipLaunchKernelGGL(stm::compressor_env_kernel, dim3(B), dim3(256), 0, st_stream(stream), x, a.gc, a.kw, 4, sr, L, ysz, y);
-            ST_LAUNCHED("compressor_env");
-        }
-        return ST_OK;
-    }
-    ST_TRY(feed_launch_fx<ST_FX_COMP4C>(ext, a, B, lds, stream));
-    if (split) {
-        hipLaunchKernelGGL(stm::comp_smooth_kernel, dim3((B + 63) / 64), dim3(64), 0, st_stream(stream), a.gc, a.kw, sr, B, L);
-        ST_LAUNCHED("comp_smooth");
-        hipLaunchKernelGGL(stm::comp_apply_kernel, dim3((ysz + 255) / 256, B), dim3(256), 0, st_stream(stream), x, a.gc, L, ysz, y);
-        ST_LAUNCHED("comp_apply");
-    }
-    return ST_OK;
+    if (effect == ST_FX_DECOMP4C) ST_TRY(feed_launch_fx<ST_FX_DECOMP4C>(ext, a, B, lds, stream));
+    else if (effect == ST_FX_COMP) ST_TRY(feed_launch_fx<ST_FX_COMP>(ext, a, B, lds, stream));
+    else ST_TRY(feed_launch_fx<ST_FX_COMP4C>(ext, a, B, lds, stream));
+    return split && finish ? feed_effect_finish(effect, B, L, ysz, sr, x, y, a.gc, a.kw, stream) : ST_OK;
 }
 extern "C" int st_synth_effect(int effect, unsigned seed, unsigned long long first_window, int B, int L, int ysz, int K, float sr,
                                const float* knob_lo, const float* knob_hi, int augment, int chooser, const float* pink_in,
@@ -2120,13 +2125,18 @@ extern "C" int st_synth_effect(int effect, unsigned seed, unsigned long long fir
     return synth_effect_run("st_synth_effect", effect, stf::FAMILIES_COMPRESSOR, false, seed, first_window, B, L, ysz, K, sr, knob_lo, knob_hi, augment, chooser, pink_in,
                             x, y, knobs, scratch, stream);
 }
+static int family_mask_check(const char* who, unsigned family_mask)
+{
+    ST_REQ(family_mask != 0u, "%s: family_mask is empty (bit f allows signal family f, f in 0..11; ST_FAMILIES_COMPRESSOR = 0xD7)", who);
+    ST_REQ((family_mask & ~stf::FAMILIES_ALL) == 0u, "%s: family_mask 0x%X has bits past family 11 (the superposition, chooser >= 12, is not built)", who, family_mask);
+    return ST_OK;
+}
 // The same feed over a caller-chosen set of signal families (all twelve of audio.synth_input_sample are built; the superposition is not)
 extern "C" int st_synth_effect_families(int effect, unsigned family_mask, unsigned seed, unsigned long long first_window, int B, int L, int ysz, int K, float sr,
                                         const float* knob_lo, const float* knob_hi, int augment, int chooser, const float* pink_in,
                                         float* x, float* y, float* knobs, float* scratch, void* stream)
 {
-    ST_REQ(family_mask != 0u, "st_synth_effect_families: family_mask is empty (bit f allows signal family f, f in 0..11; ST_FAMILIES_COMPRESSOR = 0xD7)");
-    ST_REQ((family_mask & ~stf::FAMILIES_ALL) == 0u, "st_synth_effect_families: family_mask 0x%X has bits past family 11 (the superposition, chooser >= 12, is not built)", family_mask);
+    ST_TRY(family_mask_check("st_synth_effect_families", family_mask));
     ST_REQ(chooser == -1 || chooser == 100 || chooser < 12, "st_synth_effect_families: the superposition of two signals (chooser %d >= 12) is not built; "
            "a forced family is 0..11, or 100 for the bare 1/f noise, or -1 to draw from family_mask", chooser);
     ST_REQ(chooser >= -1, "st_synth_effect_families: forced family %d: 0..11, or 100 for the bare 1/f noise, or -1 to draw from family_mask", chooser);
@@ -2174,6 +2184,66 @@ extern "C" int st_file_feed(unsigned seed, unsigned long long first_window, int 
         ST_LAUNCHED(fmt == ST_PCM_S16 ? "file_feed_s16" : "file_feed_f32");
     }
     return ST_OK;
+}
+
+// The feed of recorded input through a live effect (st_feed_live.h): per window a span of the audio pool, fresh knobs and the effect on the spot; a
+// share synth_prob of the windows are st_synth_effect_families' instead.
+extern "C" size_t st_live_feed_scratch_floats(int effect, int B, int L, float synth_prob)
+{
+    if (synth_prob > 0.f) return st_synth_effect_scratch_floats(effect, B, L);      // the synthetic rows' generator shares the scratch
+    if (!feed_effect_ok(effect) || B <= 0 || L <= 0) return 0;
+    return feed_effect_splits(effect) ? (size_t)B * (L + 4) : 0;
+}
+template <int FX>
+static int live_launch(int fmt, const stf::LiveFeedArgs& a, int B, size_t lds, void* stream)
+{
+    if (fmt == ST_PCM_S16) hipLaunchKernelGGL((stf::live_feed_kernel<FX, short>), dim3(B), dim3(256), lds, st_stream(stream), a);
+    else hipLaunchKernelGGL((stf::live_feed_kernel<FX, float>), dim3(B), dim3(256), lds, st_stream(stream), a);
+    ST_LAUNCHED(fmt == ST_PCM_S16 ? "live_feed_s16" : "live_feed_f32"); return ST_OK;
+}
+extern "C" int st_live_feed(int effect, unsigned family_mask, float synth_prob, unsigned seed, unsigned long long first_window,
+                            int B, int L, int ysz, int K, float sr, const float* knob_lo, const float* knob_hi, int augment,
+                            int fmt, const void* pool_x, const long long* file_off, const long long* file_len, int nfiles,
+                            long long min_len, long long pool_samples,
+                            float* x, float* y, float* knobs, long long* meta, float* scratch, void* stream)
+{
+    const char* who = "st_live_feed";
+    ST_REQ(knob_lo && knob_hi, "st_live_feed: null pointer (knob_lo and knob_hi, four host floats each, are required)");
+    ST_TRY(feed_effect_check(who, effect, K, sr, knob_lo, knob_hi));
+    ST_REQ(B > 0 && L > 0 && ysz > 0 && nfiles > 0, "st_live_feed: bad sizes: B, L, ysz and nfiles must be positive (B=%d L=%d ysz=%d nfiles=%d)", B, L, ysz, nfiles);
+    ST_REQ(ysz <= L, "st_live_feed: ysz = %d exceeds L = %d (the target is the last ysz samples of the window)", ysz, L);
+    ST_REQ(L % 4 == 0 && ysz % 4 == 0, "st_live_feed: L = %d and ysz = %d must be multiples of 4 (the st_dims rule: 16-byte rows)", L, ysz);
+    ST_REQ(sr > 0.f, "st_live_feed: sr = %g must be positive", sr);
+    ST_REQ(synth_prob >= 0.f && synth_prob <= 1.f, "st_live_feed: synth_prob = %g is not a probability in [0, 1]", synth_prob);      // refuses NaN as well
+    ST_REQ(fmt == ST_PCM_F32 || fmt == ST_PCM_S16, "st_live_feed: fmt = %d is not an ST_PCM_* id (ST_PCM_F32 = 0, ST_PCM_S16 = 1)", fmt);
+    ST_REQ(min_len > (long long)L, "st_live_feed: min_len = %lld: every file must be longer than the window L = %d", min_len, L);
+    ST_REQ(pool_samples >= min_len, "st_live_feed: pool_samples = %lld is below min_len = %lld", pool_samples, min_len);
+    ST_REQ(pool_x && file_off && file_len, "st_live_feed: null pointer (pool_x, file_off and file_len are required)");
+    ST_REQ(x && y && knobs, "st_live_feed: null pointer (x, y and knobs are required)");
+    if (synth_prob > 0.f) ST_TRY(family_mask_check(who, family_mask));
+    const bool split = scratch && L % 64 == 0 && feed_effect_splits(effect);
+    float* gc = split ? scratch : nullptr; float* kw = split ? scratch + (size_t)B * L : nullptr;
+    // synthetic rows: the generator of st_synth_effect_families over the whole batch (its checks, the long windows' scratch contract among them, come before its
+    // first launch); the recorded rows are overwritten below and the scratch form's second launches run once, after both
+    if (synth_prob > 0.f)
+        ST_TRY(synth_effect_run(who, effect, family_mask, true, seed, first_window, B, L, ysz, K, sr, knob_lo, knob_hi, augment, -1, nullptr, x, y, knobs, scratch, stream, false));
+    if (synth_prob < 1.f || meta) {
+        stf::LiveFeedArgs a;
+        a.pool = pool_x; a.file_off = file_off; a.file_len = file_len; a.x = x; a.y = y; a.knobs = knobs; a.meta = meta; a.gc = gc; a.kw = kw;
+        a.pool_samples = pool_samples; a.seed = seed; a.first = first_window; a.L = L; a.ysz = ysz; a.K = K; a.nfiles = nfiles; a.augment = augment ? 1 : 0;
+        a.sr = sr; a.synth_prob = synth_prob;
+        for (int k = 0; k < 4; ++k) { a.lo[k] = knob_lo[k]; a.hi[k] = knob_hi[k]; }
+        const size_t lds = split || effect == ST_FX_DENOISE ? 0 : (size_t)stm::COMP_CH * sizeof(float);      // the in-workgroup effect's buffer (synth_effect_run's static_asserts)
+        switch (effect) {
+        case ST_FX_COMP: ST_TRY(live_launch<ST_FX_COMP>(fmt, a, B, lds, stream)); break;
+        case ST_FX_LOWPASS: ST_TRY(live_launch<ST_FX_LOWPASS>(fmt, a, B, lds, stream)); break;
+        case ST_FX_DENOISE: ST_TRY(live_launch<ST_FX_DENOISE>(fmt, a, B, lds, stream)); break;
+        case ST_FX_ECHO: ST_TRY(live_launch<ST_FX_ECHO>(fmt, a, B, lds, stream)); break;
+        case ST_FX_DECOMP4C: ST_TRY(live_launch<ST_FX_DECOMP4C>(fmt, a, B, lds, stream)); break;
+        default: ST_TRY(live_launch<ST_FX_COMP4C>(fmt, a, B, lds, stream)); break;
+        }
+    }
+    return split ? feed_effect_finish(effect, B, L, ysz, sr, x, y, gc, kw, stream) : ST_OK;
 }
 
 // ------------------------------------------------------------------------------ generic learned-basis front end (a15)
