@@ -534,6 +534,35 @@ int st_live_feed(int effect, unsigned family_mask, float synth_prob, unsigned se
                  float* x, float* y, float* knobs, long long* meta /* [B][4] kind, file, start, flipped; may be NULL */,
                  float* scratch, void* stream);
 
+/* st_live_feed with the effect's HISTORY: the streamed target (st_feed_stream.h, where the law is written out).  Every argument of st_live_feed keeps its
+ * meaning and every window its draws, knobs, world knobs and meta.  For a recorded window the effect runs over up to `preroll` samples of the window's own
+ * file in front of it, the pre-roll, and only the window and the effect's tail leave:
+ *   R  = min(preroll, start & ~3)      (start: meta[2]; preroll % 4 == 0; at most three samples at a file's head stay out of the history)
+ *   xe = +-pool_x[file_off[file] + start - R .. + R + L)   (the flip covers the whole span),   x = xe[R:]
+ *   y  = the last ysz samples of st_compressor_4c / st_compressor / st_lowpass / st_echo on (xe, the window's world knobs), bit for bit;
+ *   ST_FX_DENOISE: st_live_feed's row (no state; the noise index is relative to the window);  ST_FX_DECOMP4C: y is the clean tail, x the last L samples of
+ *   st_compressor_4c(xe).
+ * With a pre-roll that reaches the head of the file, y is the streamed render of the file at the window's knob setting.  A synthetic row (synth_prob > 0) has
+ * no history: st_live_feed's row.  A recorded row depends on (seed, w), the pool and preroll only.
+ * How a state forgets its start: the 4-control compressor's gain in dB contracts by max(alphaA, alphaR)^n, alpha = exp(-ln 9 / (sr T)), so n ~ 7.6 T sr samples
+ * bring a difference down to 2^-24 of its start (T = 1 s at 44.1 kHz, Comp_Just_Thresh's release: 335 000 samples).  ST_LIVE_PREROLL_MAX = 2^22 samples is
+ * twelve times that (95 s at 44.1 kHz) and keeps preroll + L, every row index, inside 32 bits.
+ * preroll == 0: the call IS st_live_feed (same launches, same scratch contract, same size).  preroll > 0: scratch is REQUIRED,
+ * st_live_feed_stream_scratch_floats(effect, B, L, preroll, synth_prob) floats, and on return holds, with P = round_up(preroll + L, 64):
+ *   [ world knobs [B][4] (recorded rows) | R per row as int32, -1 for a synthetic row, round_up(B, 4) words |
+ *     B * P floats (not for ST_FX_DENOISE), rows right-aligned: ST_FX_COMP / LOWPASS / ECHO the float image of xe, ST_FX_COMP4C / DECOMP4C its gain curve,
+ *     smoothed over the samples that were applied | st_live_feed's scratch, st_live_feed_scratch_floats(effect, B, L, synth_prob) floats, when synth_prob > 0 ]
+ * Refused before any launch (ST_ERR_ARG, the rule in st_last_error()): everything st_live_feed refuses; preroll < 0; preroll % 4 != 0; preroll >
+ * ST_LIVE_PREROLL_MAX; a NULL scratch with preroll > 0; preroll + L >= 2^31 - 64 or B * P >= 2^40 elements (the offsets are 64-bit, a row index 32-bit).
+ * The size function returns 0 for such arguments.  Asynchronous, no allocation, no host sync. */
+enum { ST_LIVE_PREROLL_MAX = 1 << 22 };
+size_t st_live_feed_stream_scratch_floats(int effect, int B, int L, int preroll, float synth_prob);
+int st_live_feed_stream(int effect, unsigned family_mask, float synth_prob, int preroll, unsigned seed, unsigned long long first_window,
+                        int B, int L, int ysz, int K, float sr, const float* knob_lo, const float* knob_hi, int augment,
+                        int fmt, const void* pool_x, const long long* file_off, const long long* file_len, int nfiles,
+                        long long min_len, long long pool_samples,
+                        float* x, float* y, float* knobs, long long* meta, float* scratch, void* stream);
+
 /* Gradient of the loss w.r.t. the (halved) input waveform, for callers with something trainable upstream of the model (the reference's
  * autograd provides it; nn_proc.py:307, cls_fe_dft.py:55-56).  Call right after st_model_bwd on the SAME workspace:
  *   gxh[b][n] = conv-transpose of the analysis output gradient with both bases, cropped by the Conv1d padding   [B][L]

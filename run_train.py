@@ -35,6 +35,8 @@ if __name__ == "__main__":
     p.add_argument('--inpath', metavar='DIR', default=None, help="directory with Train/ and Val/ folders of recorded INPUT audio (*.wav, names without 'target'): train on "
                    "windows of it through the live --effect with knobs drawn per window (st_live_feed), instead of synthetic signals")
     p.add_argument('--synthprob', metavar='P', type=float, default=0.0, help="with --inpath: the share of windows that are synthetic test signals instead, 0 to 1")
+    p.add_argument('--preroll', metavar='N', type=int, default=0, help="with --inpath: samples of its own file the effect runs over in front of every recorded window, so "
+                   "that the target carries the effect's state (the streamed target; a multiple of 4; 0 = the effect starts at zero state in every window)")
     p.add_argument('--lrmax', type=float, help="maximum learning rate", default=1e-4)
     p.add_argument('-n', '--num', type=int, help='number of data points per epoch', default=200000)
     p.add_argument('--path', help='dataset directory with Train/, Val/ wav pairs and effect_info.ini (use with --effect files)', default=None)
@@ -58,6 +60,10 @@ if __name__ == "__main__":
         raise SystemExit(f"--synthprob {args.synthprob}: a probability, 0 to 1")
     if args.synthprob and args.inpath is None:
         raise SystemExit(f"--synthprob {args.synthprob} mixes synthetic windows into recorded input: give --inpath DIR as well")
+    if args.preroll < 0 or args.preroll % 4:
+        raise SystemExit(f"--preroll {args.preroll}: a non-negative multiple of 4 samples")
+    if args.preroll and args.inpath is None:
+        raise SystemExit(f"--preroll {args.preroll} is the effect's history in front of windows of recorded input: give --inpath DIR as well")
     if args.inpath is not None and args.effect == 'files':
         raise SystemExit("--inpath runs a live effect on recorded input; --effect files trains on recorded input / target pairs (--path): give one")
 
@@ -79,6 +85,6 @@ if __name__ == "__main__":
                 effect=effect, datapath=(args.path if args.effect == 'files' else None), sr=args.sr, scale_factor=args.scale, shrink_factor=args.shrink, apex_opt=args.apex,
                 target_type=args.target, lr_max=args.lrmax, in_checkpointname=args.checkpoint, compand=args.compand,
                 compute_dtype=args.dtype, device_feed=args.device_feed, resume_optimizer=args.resume_optimizer, device_eval=args.device_eval, choosers=args.choosers,
-                input_path=args.inpath, synth_prob=args.synthprob)
+                input_path=args.inpath, synth_prob=args.synthprob, preroll=args.preroll)
     if dist.is_initialized():
         dist.destroy_process_group()

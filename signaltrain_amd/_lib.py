@@ -74,6 +74,9 @@ SIGNATURES = {
     "st_live_feed_scratch_floats": (C.c_size_t, [_i, _i, _i, C.c_float]),
     "st_live_feed": (_i, [_i, C.c_uint, C.c_float, C.c_uint, C.c_ulonglong, _i, _i, _i, _i, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float), _i,
                           _i, _p, _p, _p, _i, C.c_longlong, C.c_longlong, _p, _p, _p, _p, _p, _p]),
+    "st_live_feed_stream_scratch_floats": (C.c_size_t, [_i, _i, _i, _i, C.c_float]),
+    "st_live_feed_stream": (_i, [_i, C.c_uint, C.c_float, _i, C.c_uint, C.c_ulonglong, _i, _i, _i, _i, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float), _i,
+                                 _i, _p, _p, _p, _i, C.c_longlong, C.c_longlong, _p, _p, _p, _p, _p, _p]),
     "st_fe_frames": (_i, [C.c_int] * 4),
     "st_fe_ws_floats": (C.c_size_t, [C.c_int] * 6),
     "st_fe_supported": (_i, [C.c_int] * 6),

@@ -23,6 +23,7 @@
 #include "st_feed.h"
 #include "st_feed_files.h"
 #include "st_feed_live.h"
+#include "st_feed_stream.h"
 
 // ------------------------------------------------------------------------------ errors
 static thread_local char g_err[512] = "";
@@ -2201,6 +2202,26 @@ static int live_launch(int fmt, const stf::LiveFeedArgs& a, int B, size_t lds, v
     else hipLaunchKernelGGL((stf::live_feed_kernel<FX, float>), dim3(B), dim3(256), lds, st_stream(stream), a);
     ST_LAUNCHED(fmt == ST_PCM_S16 ? "live_feed_s16" : "live_feed_f32"); return ST_OK;
 }
+// what st_live_feed and st_live_feed_stream refuse alike, before any launch
+static int live_feed_check(const char* who, int effect, unsigned family_mask, float synth_prob, int B, int L, int ysz, int K, float sr, const float* knob_lo, const float* knob_hi,
+                           int fmt, const void* pool_x, const long long* file_off, const long long* file_len, int nfiles, long long min_len, long long pool_samples,
+                           const float* x, const float* y, const float* knobs)
+{
+    ST_REQ(knob_lo && knob_hi, "%s: null pointer (knob_lo and knob_hi, four host floats each, are required)", who);
+    ST_TRY(feed_effect_check(who, effect, K, sr, knob_lo, knob_hi));
+    ST_REQ(B > 0 && L > 0 && ysz > 0 && nfiles > 0, "%s: bad sizes: B, L, ysz and nfiles must be positive (B=%d L=%d ysz=%d nfiles=%d)", who, B, L, ysz, nfiles);
+    ST_REQ(ysz <= L, "%s: ysz = %d exceeds L = %d (the target is the last ysz samples of the window)", who, ysz, L);
+    ST_REQ(L % 4 == 0 && ysz % 4 == 0, "%s: L = %d and ysz = %d must be multiples of 4 (the st_dims rule: 16-byte rows)", who, L, ysz);
+    ST_REQ(sr > 0.f, "%s: sr = %g must be positive", who, sr);
+    ST_REQ(synth_prob >= 0.f && synth_prob <= 1.f, "%s: synth_prob = %g is not a probability in [0, 1]", who, synth_prob);      // refuses NaN as well
+    ST_REQ(fmt == ST_PCM_F32 || fmt == ST_PCM_S16, "%s: fmt = %d is not an ST_PCM_* id (ST_PCM_F32 = 0, ST_PCM_S16 = 1)", who, fmt);
+    ST_REQ(min_len > (long long)L, "%s: min_len = %lld: every file must be longer than the window L = %d", who, min_len, L);
+    ST_REQ(pool_samples >= min_len, "%s: pool_samples = %lld is below min_len = %lld", who, pool_samples, min_len);
+    ST_REQ(pool_x && file_off && file_len, "%s: null pointer (pool_x, file_off and file_len are required)", who);
+    ST_REQ(x && y && knobs, "%s: null pointer (x, y and knobs are required)", who);
+    if (synth_prob > 0.f) ST_TRY(family_mask_check(who, family_mask));
+    return ST_OK;
+}
 extern "C" int st_live_feed(int effect, unsigned family_mask, float synth_prob, unsigned seed, unsigned long long first_window,
                             int B, int L, int ysz, int K, float sr, const float* knob_lo, const float* knob_hi, int augment,
                             int fmt, const void* pool_x, const long long* file_off, const long long* file_len, int nfiles,
@@ -2208,19 +2229,7 @@ extern "C" int st_live_feed(int effect, unsigned family_mask, float synth_prob, 
                             float* x, float* y, float* knobs, long long* meta, float* scratch, void* stream)
 {
     const char* who = "st_live_feed";
-    ST_REQ(knob_lo && knob_hi, "st_live_feed: null pointer (knob_lo and knob_hi, four host floats each, are required)");
-    ST_TRY(feed_effect_check(who, effect, K, sr, knob_lo, knob_hi));
-    ST_REQ(B > 0 && L > 0 && ysz > 0 && nfiles > 0, "st_live_feed: bad sizes: B, L, ysz and nfiles must be positive (B=%d L=%d ysz=%d nfiles=%d)", B, L, ysz, nfiles);
-    ST_REQ(ysz <= L, "st_live_feed: ysz = %d exceeds L = %d (the target is the last ysz samples of the window)", ysz, L);
-    ST_REQ(L % 4 == 0 && ysz % 4 == 0, "st_live_feed: L = %d and ysz = %d must be multiples of 4 (the st_dims rule: 16-byte rows)", L, ysz);
-    ST_REQ(sr > 0.f, "st_live_feed: sr = %g must be positive", sr);
-    ST_REQ(synth_prob >= 0.f && synth_prob <= 1.f, "st_live_feed: synth_prob = %g is not a probability in [0, 1]", synth_prob);      // refuses NaN as well
-    ST_REQ(fmt == ST_PCM_F32 || fmt == ST_PCM_S16, "st_live_feed: fmt = %d is not an ST_PCM_* id (ST_PCM_F32 = 0, ST_PCM_S16 = 1)", fmt);
-    ST_REQ(min_len > (long long)L, "st_live_feed: min_len = %lld: every file must be longer than the window L = %d", min_len, L);
-    ST_REQ(pool_samples >= min_len, "st_live_feed: pool_samples = %lld is below min_len = %lld", pool_samples, min_len);
-    ST_REQ(pool_x && file_off && file_len, "st_live_feed: null pointer (pool_x, file_off and file_len are required)");
-    ST_REQ(x && y && knobs, "st_live_feed: null pointer (x, y and knobs are required)");
-    if (synth_prob > 0.f) ST_TRY(family_mask_check(who, family_mask));
+    ST_TRY(live_feed_check(who, effect, family_mask, synth_prob, B, L, ysz, K, sr, knob_lo, knob_hi, fmt, pool_x, file_off, file_len, nfiles, min_len, pool_samples, x, y, knobs));
     const bool split = scratch && L % 64 == 0 && feed_effect_splits(effect);
     float* gc = split ? scratch : nullptr; float* kw = split ? scratch + (size_t)B * L : nullptr;
     // synthetic rows: the generator of st_synth_effect_families over the whole batch (its checks, the long windows' scratch contract among them, come before its
@@ -2244,6 +2253,96 @@ extern "C" int st_live_feed(int effect, unsigned family_mask, float synth_prob, 
         }
     }
     return split ? feed_effect_finish(effect, B, L, ysz, sr, x, y, gc, kw, stream) : ST_OK;
+}
+
+// st_live_feed with the effect's history (st_feed_stream.h).  Scratch of the pre-roll form, P = round_up(preroll + L, 64):
+// [world knobs 4 B | R per row (int32; -1: synthetic) round_up(B, 4) | B * P rows, right-aligned (not ST_FX_DENOISE) | st_live_feed's scratch (synth_prob > 0)]
+static const char* stream_limit(int B, int L, int preroll)
+{
+    if (preroll < 0) return "preroll is negative";
+    if (preroll % 4 != 0) return "preroll is not a multiple of 4 (the history keeps the 4-sample rule of the rows)";
+    if (preroll > (int)ST_LIVE_PREROLL_MAX) return "preroll exceeds ST_LIVE_PREROLL_MAX = 4194304 samples";
+    const long long P = ((long long)preroll + (long long)(L > 0 ? L : 0) + 63) / 64 * 64;
+    if (P >= 0x7fffffffLL - 64) return "preroll + L leaves the 32-bit row index (preroll + L < 2^31 - 64 is required)";
+    if ((long long)(B > 0 ? B : 0) * P >= (1ll << 40)) return "B * (preroll + L) leaves the offset arithmetic (below 2^40 elements is required)";
+    return nullptr;
+}
+static int stream_pitch(int L, int preroll) { return (int)(((long long)preroll + L + 63) / 64 * 64); }
+extern "C" size_t st_live_feed_stream_scratch_floats(int effect, int B, int L, int preroll, float synth_prob)
+{
+    if (preroll == 0) return st_live_feed_scratch_floats(effect, B, L, synth_prob);
+    if (!feed_effect_ok(effect) || B <= 0 || L <= 0 || L % 4 != 0 || stream_limit(B, L, preroll)) return 0;
+    size_t n = (size_t)4 * B + (size_t)st_round_up(B, 4);
+    if (effect != ST_FX_DENOISE) n += (size_t)B * stream_pitch(L, preroll);
+    return n + (synth_prob > 0.f ? st_live_feed_scratch_floats(effect, B, L, synth_prob) : 0);
+}
+template <int FX>
+static int stream_launch(int fmt, const stf::StreamFeedArgs& a, int B, size_t lds, void* stream)
+{
+    if (fmt == ST_PCM_S16) hipLaunchKernelGGL((stf::stream_feed_kernel<FX, short>), dim3(B), dim3(256), lds, st_stream(stream), a);
+    else hipLaunchKernelGGL((stf::stream_feed_kernel<FX, float>), dim3(B), dim3(256), lds, st_stream(stream), a);
+    ST_LAUNCHED(fmt == ST_PCM_S16 ? "stream_feed_s16" : "stream_feed_f32"); return ST_OK;
+}
+extern "C" int st_live_feed_stream(int effect, unsigned family_mask, float synth_prob, int preroll, unsigned seed, unsigned long long first_window,
+                                   int B, int L, int ysz, int K, float sr, const float* knob_lo, const float* knob_hi, int augment,
+                                   int fmt, const void* pool_x, const long long* file_off, const long long* file_len, int nfiles,
+                                   long long min_len, long long pool_samples,
+                                   float* x, float* y, float* knobs, long long* meta, float* scratch, void* stream)
+{
+    const char* who = "st_live_feed_stream";
+    if (preroll == 0)      // today's feed: the same launches, the same scratch contract
+        return st_live_feed(effect, family_mask, synth_prob, seed, first_window, B, L, ysz, K, sr, knob_lo, knob_hi, augment, fmt, pool_x, file_off, file_len, nfiles,
+                            min_len, pool_samples, x, y, knobs, meta, scratch, stream);
+    const char* why = stream_limit(B, L, preroll);
+    ST_REQ(!why, "%s: %s (preroll=%d B=%d L=%d)", who, why, preroll, B, L);
+    ST_REQ(scratch, "%s: null pointer (scratch, st_live_feed_stream_scratch_floats() floats, is required with preroll = %d > 0)", who, preroll);
+    ST_TRY(live_feed_check(who, effect, family_mask, synth_prob, B, L, ysz, K, sr, knob_lo, knob_hi, fmt, pool_x, file_off, file_len, nfiles, min_len, pool_samples, x, y, knobs));
+    const int P = stream_pitch(L, preroll);
+    const bool gain = effect == ST_FX_COMP4C || effect == ST_FX_DECOMP4C;
+    stf::StreamFeedArgs s;
+    s.kw = scratch; s.rr = reinterpret_cast<int*>(scratch + (size_t)4 * B);
+    float* rest = scratch + (size_t)4 * B + (size_t)st_round_up(B, 4);
+    s.buf = effect == ST_FX_DENOISE ? nullptr : rest;
+    if (effect != ST_FX_DENOISE) rest += (size_t)B * P;
+    s.P = P; s.preroll = preroll;
+    // synthetic rows: the generator of st_synth_effect_families over the whole batch and, where it left the compressors' chain to second launches, that chain at
+    // pitch L over its own part of the scratch -- all before the recorded rows are written, so no row passes an in-place stage twice
+    if (synth_prob > 0.f) {
+        float* scr_l = st_live_feed_scratch_floats(effect, B, L, synth_prob) ? rest : nullptr;
+        ST_TRY(synth_effect_run(who, effect, family_mask, true, seed, first_window, B, L, ysz, K, sr, knob_lo, knob_hi, augment, -1, nullptr, x, y, knobs, scr_l, stream, false));
+        if (scr_l && L % 64 == 0 && feed_effect_splits(effect)) ST_TRY(feed_effect_finish(effect, B, L, ysz, sr, x, y, scr_l, scr_l + (size_t)B * L, stream));
+    }
+    stf::LiveFeedArgs& a = s.live;
+    a.pool = pool_x; a.file_off = file_off; a.file_len = file_len; a.x = x; a.y = y; a.knobs = knobs; a.meta = meta; a.gc = nullptr; a.kw = nullptr;
+    a.pool_samples = pool_samples; a.seed = seed; a.first = first_window; a.L = L; a.ysz = ysz; a.K = K; a.nfiles = nfiles; a.augment = augment ? 1 : 0;
+    a.sr = sr; a.synth_prob = synth_prob;
+    for (int k = 0; k < 4; ++k) { a.lo[k] = knob_lo[k]; a.hi[k] = knob_hi[k]; }
+    const size_t lds = gain || effect == ST_FX_DENOISE ? 0 : (size_t)stm::COMP_CH * sizeof(float);      // the in-workgroup effect's buffer (synth_effect_run's static_asserts)
+    switch (effect) {
+    case ST_FX_COMP: ST_TRY(stream_launch<ST_FX_COMP>(fmt, s, B, lds, stream)); break;
+    case ST_FX_LOWPASS: ST_TRY(stream_launch<ST_FX_LOWPASS>(fmt, s, B, lds, stream)); break;
+    case ST_FX_DENOISE: ST_TRY(stream_launch<ST_FX_DENOISE>(fmt, s, B, lds, stream)); break;
+    case ST_FX_ECHO: ST_TRY(stream_launch<ST_FX_ECHO>(fmt, s, B, lds, stream)); break;
+    case ST_FX_DECOMP4C: ST_TRY(stream_launch<ST_FX_DECOMP4C>(fmt, s, B, lds, stream)); break;
+    default: ST_TRY(stream_launch<ST_FX_COMP4C>(fmt, s, B, lds, stream)); break;
+    }
+    if (!gain) return ST_OK;
+    // the recorded rows' chain at pitch P: history tiles advance the state, only the tiles the apply kernel reads are stored
+    const int keep0 = (P - (effect == ST_FX_DECOMP4C ? L : ysz)) & ~63;
+    hipLaunchKernelGGL(stf::stream_smooth_kernel, dim3((B + 63) / 64), dim3(64), 0, st_stream(stream), s.buf, (const float*)s.kw, (const int*)s.rr, sr, B, L, P, keep0);
+    ST_LAUNCHED("stream_smooth");
+    const int SUB = 32768;                                   // windows per launch: gridDim.y stays below 65536
+    for (int b0 = 0; b0 < B; b0 += SUB) {
+        const int nb = B - b0 < SUB ? B - b0 : SUB;
+        if (effect == ST_FX_DECOMP4C)
+            hipLaunchKernelGGL(stf::stream_apply_inplace_kernel, dim3((L + 2047) / 2048 < 65535 ? (L + 2047) / 2048 : 65535, nb), dim3(256), 0, st_stream(stream),
+                               x + (size_t)b0 * L, (const float*)s.buf + (size_t)b0 * P, (const int*)s.rr + b0, L, P);
+        else
+            hipLaunchKernelGGL(stf::stream_apply_kernel, dim3((ysz + 255) / 256, nb), dim3(256), 0, st_stream(stream),
+                               (const float*)x + (size_t)b0 * L, (const float*)s.buf + (size_t)b0 * P, (const int*)s.rr + b0, L, P, ysz, y + (size_t)b0 * ysz);
+    }
+    ST_LAUNCHED(effect == ST_FX_DECOMP4C ? "stream_apply_inplace" : "stream_apply");
+    return ST_OK;
 }
 
 // ------------------------------------------------------------------------------ generic learned-basis front end (a15)

@@ -175,7 +175,7 @@ def _train_loop(dp, model, engine, effect, device, epochs, batch_size, lr_sched,
 def train(effect=None, epochs=100, n_data_points=200000, batch_size=20, device=None, plot_every=10, cp_every=25, sr=44100,
           datapath=None, scale_factor=1, shrink_factor=4, apex_opt="O0", target_type="stream", lr_max=1e-4,
           in_checkpointname='modelcheckpoint.tar', compand=False, num_workers=10, device_feed=True, compute_dtype=None,
-          resume_optimizer=False, device_eval=False, choosers=None, input_path=None, synth_prob=0.0):
+          resume_optimizer=False, device_eval=False, choosers=None, input_path=None, synth_prob=0.0, preroll=0):
     """train.py:167-278.  datapath: directory with Train/ and Val/ wav pairs (datasets.AudioFileDataSet, the reference's
     file feed, e.g. the LA2A set of BASELINE configs[3]; pass effect=audio.FileEffect(datapath)); compand: mu-law compand that dataset's audio (datasets.py:218-220).
     apex_opt: "O0" = fp32 (the parity path); "O1" / "O2" / "O3" = the reference's Apex mixed precision (train.py:254-255),
@@ -195,13 +195,18 @@ def train(effect=None, epochs=100, n_data_points=200000, batch_size=20, device=N
     input_path: directory with Train/ and Val/ folders of recorded INPUT audio (*.wav, names without "target"): the windows are spans of it, the knobs are
     drawn per window and `effect` runs live (datasets.AudioInputDataSet; on the device one st_live_feed call per chunk of minibatches, csrc/st_feed_live.h);
     the validation set, n_data_points // 4 windows of Val/, is made once and kept in HBM.  Not together with datapath, whose targets are recordings.
-    synth_prob: with input_path, the share of windows that are synthetic test signals of `choosers` instead (the reference's unused `synthprob`)."""
+    synth_prob: with input_path, the share of windows that are synthetic test signals of `choosers` instead (the reference's unused `synthprob`);
+    preroll: with input_path, the samples of its own file the effect runs over in front of every recorded window, training and validation, so that the
+    target carries the effect's state (the reference's streamed target; st_live_feed_stream, csrc/st_feed_stream.h); a multiple of 4, 0 (default) = the
+    effect starts from its zero state at the head of each window.  target_type belongs to datapath and is not read with input_path."""
     if input_path is not None and datapath is not None:
         raise ValueError("train(): input_path (recorded input through the live effect) and datapath (recorded input / target pairs) are two different feeds: give one")
     if input_path is None and synth_prob:
         raise ValueError(f"train(): synth_prob = {synth_prob} mixes synthetic windows into recorded input and needs input_path; without one every window is synthetic")
     if not 0.0 <= float(synth_prob) <= 1.0:
         raise ValueError(f"train(): synth_prob = {synth_prob} is not a probability in [0, 1]")
+    if input_path is None and preroll:
+        raise ValueError(f"train(): preroll = {preroll} is the effect's history in front of windows of recorded input and needs input_path")
     if compute_dtype is None:
         compute_dtype = "f32" if str(apex_opt).upper() in ("O0", "NONE", "") else "f16_all"
     effect = audio.Compressor_4c() if effect is None else effect
@@ -250,9 +255,9 @@ def train(effect=None, epochs=100, n_data_points=200000, batch_size=20, device=N
         # recorded input through the live effect: spans of the device-resident audio, knobs per window, the effect on the spot (one st_live_feed call per
         # chunk of minibatches, on a side stream beside the steps).  Validation: n_data_points // 4 windows of Val/ made once and kept in HBM.
         dataset = datasets.AudioInputDataSet(chunk_size, effect, sr=sr, path=input_path + "/Train/", datapoints=n_data_points, y_size=out_chunk_size, augment=True,
-                                             synth_prob=synth_prob, choosers=choosers, compand=compand)
+                                             synth_prob=synth_prob, choosers=choosers, compand=compand, preroll=preroll)
         dataset_val = datasets.AudioInputDataSet(chunk_size, effect, sr=sr, path=input_path + "/Val/", datapoints=n_data_points // 4, y_size=out_chunk_size,
-                                                 augment=False, synth_prob=synth_prob, choosers=choosers, compand=compand)
+                                                 augment=False, synth_prob=synth_prob, choosers=choosers, compand=compand, preroll=preroll)
         if device_feed and device.type == "cuda":
             dataloader = datasets.DeviceLiveLoader(dataset, batch_size, device)
             live_val = datasets.DeviceRecycledDataSet(chunk_size, effect, sr=sr, datapoints=n_data_points // 4, y_size=out_chunk_size, augment=False, device=device,
