@@ -316,6 +316,46 @@ int st_train_step(const st_dims* d, float* params, float* grads, float* m, float
                   const float* knobs, const float* y_true, void* ws, float* scalars,
                   float lr, float beta1, float beta2, float eps, int step, void* stream);
 
+/* ---- the step with frozen parameter groups ------------------------------------------------------------------------------
+ * st_train_step for a model some of whose parameters have requires_grad = False (the reference's nn_proc.freeze_layers, nn_proc.py:17-26, and the
+ * st_model.freeze() it sketches for the two STFT bases, :395-401), with torch's semantics under clip_grad_norm_ + torch.optim.Adam (train.py:131-151).
+ * The 40 tensors form four groups, frozen or trainable as a whole; `trainable` is the OR of the trainable ones. */
+#define ST_GROUP_ANALYSIS  1   /* params[offs[0],  offs[2])   dft_analysis  real | imag  */
+#define ST_GROUP_SYNTHESIS 2   /* params[offs[2],  offs[4])   dft_synthesis real | imag  */
+#define ST_GROUP_AE_MAG    4   /* params[offs[4],  offs[22])  aenc                        */
+#define ST_GROUP_AE_PHS    8   /* params[offs[22], total)     phs_aenc                    */
+#define ST_GROUP_ALL      15
+
+/* stages of one step, as st_step_groups_stages() reports them */
+#define ST_STAGE_SYN_DGRAD  1
+#define ST_STAGE_SYN_WGRAD  2
+#define ST_STAGE_AE_BWD     4
+#define ST_STAGE_AE_DINPUT  8   /* d mag / d phs out of the autoencoder backward + the polar backward */
+#define ST_STAGE_ANA_WGRAD 16
+
+/* The backward stages a step with this mask launches (host arithmetic, no state; < 0 for a mask outside 1..15):
+ *   SYN_WGRAD  iff SYNTHESIS is trainable;   AE_BWD iff any of AE_MAG, AE_PHS, ANALYSIS is;   SYN_DGRAD iff AE_BWD;
+ *   AE_DINPUT and ANA_WGRAD  iff ANALYSIS is trainable.
+ * A stage outside the set issues NO launch: neither its GEMM, nor its slab reduce, nor its share of the launch behind the autoencoder backward.  The
+ * autoencoder backward, when it runs, runs both nets.  Without AE_DINPUT the fused geometries' autoencoder backward is the instantiation that forms no
+ * input gradient (csrc/st_ae.h, NOIN); the split 16-bit backward and the wide path keep forming it, and nothing reads it.  The polar backward runs on no route. */
+int st_step_groups_stages(int trainable);
+
+/* Forward, loss and st_dims.prec handling are st_train_step's at every level and geometry.  Frozen groups: their ranges of params, m and v are not
+ * written (bit for bit as the caller left them, whatever they hold -- they are not read either); what their ranges of grads hold afterwards is
+ * unspecified.  The L1 clip norm runs over the TRAINABLE tensors of the clip scope (the four STFT tensors, or everything with st_dims.clip_all); with
+ * none the norm is 0 and the coefficient 1, as clip_grad_norm_ over parameters without gradients.  scalars[3], [4] report exactly that norm and
+ * coefficient; scalars[0..2] and [5] are as in st_train_step, and the overflow skip of the f16 levels holds back every trainable group at once.
+ * step[g] (g = 0..3, order of the bits): the Adam step number of group g, >= 1 for a trainable group, ignored for a frozen one -- torch's
+ * per-parameter state['step']: a group unfrozen after k steps takes its bias corrections from step 1 while the others are at k + 1.
+ * ST_ERR_ARG before any launch: trainable outside 1..15, a trainable group with step[g] < 1, a null pointer.  trainable == ST_GROUP_ALL with four
+ * equal steps IS st_train_step with that step (same launches, same bits).  Not for the captured step or the data-parallel step. */
+int st_train_step_groups(const st_dims* d, float* params, float* grads, float* m, float* v,
+                         const float* x, const float* knobs, const float* y_true, void* ws, float* scalars,
+                         float lr, float beta1, float beta2, float eps,
+                         const int step[4],   /* Adam step number per group, order of the bits above */
+                         int trainable, void* stream);
+
 /* After an external all-reduce of `grads` (data parallel): recompute the L1 norm of the reduced, scaled gradient (over the
  * STFT tensors, or over everything with st_dims.clip_all), clip and Adam.  grad_scale = 1/world (the loss scale of
  * st_dims.loss_scale, if any, is removed here as well). */

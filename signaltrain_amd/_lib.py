@@ -120,6 +120,8 @@ SIGNATURES = {
     "st_unstage_analysis": (_i, [_D, _p, _p, _p]),
     "st_loss_backward_stage": (_i, [_D, _p, _p, _p, _p, _p, _p, _p, _i, _p]),
     "st_train_step": (_i, [_D, _p, _p, _p, _p, _p, _p, _p, _p, _p, _f, _f, _f, _f, _i, _p]),
+    "st_step_groups_stages": (_i, [_i]),
+    "st_train_step_groups": (_i, [_D, _p, _p, _p, _p, _p, _p, _p, _p, _p, _f, _f, _f, _f, C.POINTER(C.c_int), _i, _p]),
     "st_dp_clip_adam": (_i, [_D, _p, _p, _p, _p, _p, _p, _f, _f, _f, _f, _f, _i, _p]),
     "st_graph_create": (_i, [_D, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _f, _f, _f, _p, C.POINTER(_p)]),
     "st_graph_launch": (_i, [_p, _p]),
@@ -153,6 +155,12 @@ def family_mask(choosers):
     return sum(1 << f for f in fams)
 # sample formats of st_file_feed's audio pools (include/signaltrain_hip.h ST_PCM_*)
 PCM_F32, PCM_S16 = 0, 1
+
+# parameter groups of st_train_step_groups (ST_GROUP_*) by the names train.train(freeze=...) takes, and the stages st_step_groups_stages reports (ST_STAGE_*)
+GROUPS = {"analysis": 1, "synthesis": 2, "aenc": 4, "phs_aenc": 8}
+GROUP_SETS = dict(GROUPS, frontend=3)
+GROUP_ALL = 15
+STAGE_SYN_DGRAD, STAGE_SYN_WGRAD, STAGE_AE_BWD, STAGE_AE_DINPUT, STAGE_ANA_WGRAD = 1, 2, 4, 8, 16
 
 # st_dims.prec levels (include/signaltrain_hip.h ST_PREC_*) by the names the Python surface uses
 PREC = {"f32": 0, "bf16": 1, "bf16_all": 2, "f16": 3, "f16_all": 4, "f32x3": 5}

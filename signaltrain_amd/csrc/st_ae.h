@@ -1004,7 +1004,12 @@ constexpr int ae_bwd_lds_floats(int nw) { return (CL::BWD_TOTAL + nw * AE_BWD_SC
 // the bias gradient of that window alone, which is all d knobs needs (knob_grad_kernel, st_api.hip).  A compile-time flag: off, nothing is added.
 // IMG (round 10; SAVED only): the dgrad images and the frequency-weight table arrive ready-made from prep_kernel (ae_img_build): the prologue is a linear copy, and the
 // weight of the L1 term is read from the table (the kept-activation kernel never touches the forward images: the table lies in their place).
-template <int NW, bool INNER = false, int BF = 0, int VAR = 1, bool SAVED = false, bool KG = false, bool IMG = false>      // BF: 16-bit operands in all Linear-layer products (ST_PREC_*_ALL)
+// NOIN (st_train_step_groups with the analysis bases frozen; fused geometries only): nothing downstream reads d mag / d phs, so the layer-1 data-gradient
+// product, the fetch of its weight fragments, the transposed skip / residual tails it is summed with and the dmag / dphs stores are compiled out.  The
+// weight and bias gradient accumulation of all nine layers is the same instruction sequence on the same operands: the partials come out bit for bit as
+// with the flag off.  Off in every other instantiation.  The split 16-bit backward (st_ae_split.h) and the wide path (st_ae_wide.h) have no such form:
+// they keep computing the input gradient, and the step just does not consume it (the polar backward, their only consumer, is not launched).
+template <int NW, bool INNER = false, int BF = 0, int VAR = 1, bool SAVED = false, bool KG = false, bool IMG = false, bool NOIN = false>      // BF: 16-bit operands in all Linear-layer products (ST_PREC_*_ALL)
 __global__ void __launch_bounds__(NW * 64, 1)
 ae_bwd_kernel(const float* __restrict__ mag, const float* __restrict__ phs, const float* __restrict__ knobs,
               const float* __restrict__ ae_m, const float* __restrict__ ae_p, const AEOffsets go, const int PG,
@@ -1020,6 +1025,7 @@ ae_bwd_kernel(const float* __restrict__ mag, const float* __restrict__ phs, cons
 {
     static_assert(!SAVED || (!INNER && BF == 0), "the kept-activation backward exists for the fused fp32 geometries");
     static_assert(!IMG || SAVED, "ready-made images: the kept-activation backward only");
+    static_assert(!NOIN || !INNER, "the form without the input gradient exists for the fused geometries");
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int ae = blockIdx.y;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -1280,7 +1286,7 @@ ae_bwd_kernel(const float* __restrict__ mag, const float* __restrict__ phs, cons
                 const float d9 = dxA[r] * mtA[r] * eg;             // dxA is already zero outside the valid rows / frames
                 const float tail = dxA[r] * e1;
                 da9[0][r] = d9;
-                Ts[to * SP + c] = tail;
+                if constexpr (!NOIN) Ts[to * SP + c] = tail;
                 Ys[to * SP + c] = d9;                      // [feature t'][row c] -> read back transposed below
             }
         }
@@ -1371,7 +1377,8 @@ ae_bwd_kernel(const float* __restrict__ mag, const float* __restrict__ phs, cons
             ST_FENCE();
             wgrad_regh<2, 4, BF>(rW2, rb2, daT2, hT1);
         } else {
-            ST_BWD_STAGE(2, 4, fd2, da2, daT2, h1, hT1, da1, daT1, rW2, rb2, (frags_dgrad<4, 2, CL::I0, BF>(fd1, lw + CL::G0, g, c)))
+            auto next1 = [&]() { if constexpr (!NOIN) frags_dgrad<4, 2, CL::I0, BF>(fd1, lw + CL::G0, g, c); };
+            ST_BWD_STAGE(2, 4, fd2, da2, daT2, h1, hT1, da1, daT1, rW2, rb2, next1())
             ST_REFILL(sv_load(svq, lane16, 0, s_h1));
         }
         // layer 1 (T -> 64): input rows transposed through the wave's scratch
@@ -1380,7 +1387,7 @@ ae_bwd_kernel(const float* __restrict__ mag, const float* __restrict__ phs, cons
 #pragma unroll
             for (int it = 0; it < 2; ++it) vT[it] = *reinterpret_cast<const f32x4*>(Vs + (16 * it + c) * SP + 4 * g);
             ST_FENCE();
-            dgradD_fr<4, 2, BF>(fd1, da1, dv);
+            if constexpr (!NOIN) dgradD_fr<4, 2, BF>(fd1, da1, dv);
             wgrad_reg<4, 2, BF>(rW1, rb1, daT1, vT);
         }
 #undef ST_BWD_STAGE
@@ -1395,7 +1402,7 @@ ae_bwd_kernel(const float* __restrict__ mag, const float* __restrict__ phs, cons
         }
         mask_kn(knn, knTn); kn = knn; knT = knTn;
         // ------------------------------------------------------------------ d input rows (+ skip / residual tails)
-        if constexpr (!INNER) {
+        if constexpr (!INNER && !NOIN) {
         // Materialise the accumulators in VGPRs HERE, in the block of the MFMAs that produce them: the stores below sit in
         // conditional blocks, and an accumulator first read behind a skipped block would be read before the MFMA has
         // finished (the hazard class tools/check_mfma_hazards.py scans for).

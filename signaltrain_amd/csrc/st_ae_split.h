@@ -14,6 +14,9 @@
 // arithmetic, summation orders inside a wave and the fixed-order reduction of the per-wave gradient images are as in
 // ae_bwd_kernel, so the result is run-to-run bit-identical as before (the order in which rows reach a given accumulator changes,
 // hence results differ from the single-kernel form by fp32 reassociation only).
+//
+// Frozen analysis bases (st_train_step_groups without ST_STAGE_AE_DINPUT): these two kernels have no form without the input gradient -- the encoder half
+// still writes d mag / d phs, and the step simply does not read them (post_ae_kernel runs without its polar blocks).  ae_bwd_kernel has one (NOIN).
 #pragma once
 #include "st_ae.h"
 

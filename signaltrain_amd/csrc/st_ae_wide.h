@@ -11,6 +11,9 @@
 // The knobs (nn_proc.py:92-93, concatenated after the 16-wide code) are K extra ROWS of the layer-5 input, so layer 5
 // and its weight gradient need no special case.  Weight matrices whose row length is not a multiple of the k-tile
 // (W_1: T, W_5: 16 + K) are re-packed zero-padded once per call (pad_rows_kernel).
+//
+// Frozen analysis bases (st_train_step_groups without ST_STAGE_AE_DINPUT): the layer-1 data gradient + polar backward launch (wide_dv_polar_kernel) is
+// left out; the fused inner kernel of layers 2..8 keeps forming dA_1, which the layer-1 WEIGHT gradient needs anyway.
 #pragma once
 #include "st_common.h"
 #include "st_gemm.h"

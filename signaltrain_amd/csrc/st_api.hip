@@ -943,8 +943,9 @@ static int ae_wide_bwd(const st_dims* d, const Layout& L, const float* mag, cons
                        const float* ae_m, const float* ae_p, const float* mag_hat, const float* phs_hat, const float* dAA,
                        const float* g_mag_hat, float reg_coef, float* dmag, float* dphs, WideWS& w, float* g_m, float* g_p,
                        bool have_fwd, void* stream, const PolarSink* sink = nullptr,
-                       const stw::SynReduce* syn = nullptr, float* norm_e = nullptr, int* n_norm_e = nullptr, float* kg = nullptr)
-{   // kg (st_model_bwd_knobs): the fused kernel of layers 2..8 also writes the per-group column sums of d a5 there
+                       const stw::SynReduce* syn = nullptr, float* norm_e = nullptr, int* n_norm_e = nullptr, float* kg = nullptr, bool no_dinput = false)
+{   // no_dinput (st_train_step_groups, analysis bases frozen): the layer-1 data gradient + polar backward launch at the end is left out
+    // kg (st_model_bwd_knobs): the fused kernel of layers 2..8 also writes the per-group column sums of d a5 there
     hipStream_t s = st_stream(stream);
     const int FP = L.KP / 2, F = d->F, T = d->T, OT = d->OT, R = (int)w.R;
     const int wide_ht = ae_ht(d->prec);
@@ -996,6 +997,7 @@ static int ae_wide_bwd(const st_dims* d, const Layout& L, const float* mag, cons
     hipLaunchKernelGGL(stw::wide_grad_finish_kernel, dim3((w.so[9] + 63) / 64 + (L.PG + 63) / 64 + (syn ? norm_partials(d) : 0), 2), dim3(256), 0, s, w.slabs, w.nsplit, w.SL, tab, g_m, g_p,
                        (w.so[9] + 63) / 64, (const float*)w.inner_ws, inner_parts, L.PG, syn ? *syn : stw::SynReduce{}, norm_e);
     if (norm_e && n_norm_e) *n_norm_e = 2 * ((w.so[9] + 63) / 64 + (L.PG + 63) / 64);
+    if (no_dinput) { ST_LAUNCHED("ae_wide_bwd_noin"); return ST_OK; }
     {   // layer-1 data gradient + polar backward of both nets in one kernel
         stw::DvPolarArgs q;
         q.DA1m = w.DA[0][0]; q.DA1p = w.DA[1][0]; q.TLm = w.TL[0]; q.TLp = w.TL[1]; q.W1m = ae_m + L.go.w[0]; q.W1p = ae_p + L.go.w[0];
@@ -1021,8 +1023,10 @@ static int ae_bwd_body(const st_dims* d, const Layout& L, const float* mag, cons
                        const float* dAA, const float* g_mag_hat, float reg_coef, float* dmag, float* dphs, float* ws,
                        float* g_m, float* g_p, bool have_fwd, void* stream, bool* defer_reduce = nullptr,
                        const PolarSink* sink = nullptr, const stw::SynReduce* syn = nullptr, float* norm_e = nullptr, int* n_norm_e = nullptr,
-                       float* kg = nullptr, bool have_img = false)
+                       float* kg = nullptr, bool have_img = false, bool no_dinput = false)
 {
+    // no_dinput (st_train_step_groups, analysis bases frozen): nothing reads d mag / d phs.  The fused geometries' kernel runs as its NOIN instantiation;
+    // the split 16-bit kernels and the wide path's fused inner kernel keep forming the input gradient (the wide path drops its layer-1 data-gradient + polar launch)
     // have_img: the forward of this workspace was a fused one whose prep_kernel left the weight images there (ae_img_ptr)
     // kg (st_model_bwd_knobs): the kernel that holds d a5 also writes its per-group column sums there ([net][group][16]); only the instantiations the shipped
     // tuning defaults reach exist in that form (ae_kg_route)
@@ -1033,8 +1037,9 @@ static int ae_bwd_body(const st_dims* d, const Layout& L, const float* mag, cons
     if (ae_is_wide(d)) {
         if (defer_reduce) *defer_reduce = false;
         WideWS w; wide_carve(d, L, ws, &w);
-        return ae_wide_bwd(d, L, mag, phs, knobs, ae_m, ae_p, mag_hat, phs_hat, dAA, g_mag_hat, reg_coef, dmag, dphs, w, g_m, g_p, have_fwd, stream, sink, syn, norm_e, n_norm_e, kg);
+        return ae_wide_bwd(d, L, mag, phs, knobs, ae_m, ae_p, mag_hat, phs_hat, dAA, g_mag_hat, reg_coef, dmag, dphs, w, g_m, g_p, have_fwd, stream, sink, syn, norm_e, n_norm_e, kg, no_dinput);
     }
+    ST_REQ(!no_dinput || (!kg && !g_mag_hat), "st_ae_bwd: the form without the input gradient takes neither an upstream d mag_hat nor the knob-gradient output");
     if (kg && !(ae_kg_route(d) && have_fwd)) return st_fail(ST_ERR_UNSUPPORTED, "st_ae_bwd: no per-group d a5 output on this autoencoder backward route (%s)", ae_kg_why(d));
     const size_t lds = (size_t)sta::ae_bwd_lds_floats(AE_BWD_NW) * sizeof(float);
     static_assert((size_t)sta::ae_bwd_lds_floats(AE_BWD_NW) * sizeof(float) <= 160 * 1024, "ae_bwd LDS budget");
@@ -1073,6 +1078,20 @@ static int ae_bwd_body(const st_dims* d, const Layout& L, const float* mag, cons
     } else {
         // kernel variant: 1 = an upstream d/d mag_hat arrives (autograd entry), 2 = T - OT == 16 (tails already in registers), 0 = neither
         const int var = g_mag_hat ? 1 : (d->T - d->OT == 16 ? 2 : 0);
+        if (no_dinput) {                                  // VAR 0 / 2 only (no upstream d mag_hat), no per-group d a5 output
+            if (have_fwd && ae_use_saved(d)) {
+                const float* sv = ae_sv_ptr(d, L, ws);
+                const float* img = (have_img && ae_img_level(d) == 2) ? ae_img_ptr(ws) : nullptr;
+                ST_TRY(with_bool(var == 2, [&](auto T16) { return with_bool(img != nullptr, [&](auto IMG) {
+                    return launch_lds("ae_bwd_kernel", sta::ae_bwd_kernel<AE_BWD_NW, false, 0, T16() ? 2 : 0, true, false, IMG(), true>, dim3(grid, 2), dim3(AE_BWD_NW * 64), lds, s,
+                                      mag, phs, knobs, ae_m, ae_p, L.go, L.PG, mag_hat, phs_hat, dAA, g_mag_hat, reg_coef, expfac,
+                                      dmag, dphs, parts, d->B, d->T, d->OT, d->F, d->K, L.KP, live.t_lo, t_hi, nsl, slab, sv, kg, img); }); }));
+            } else
+                ST_TRY(with_ht(ht, [&](auto HT) { return with_bool(var == 2, [&](auto T16) {
+                    return launch_lds("ae_bwd_kernel", sta::ae_bwd_kernel<AE_BWD_NW, false, HT(), T16() ? 2 : 0, false, false, false, true>, dim3(grid, 2), dim3(AE_BWD_NW * 64), lds, s,
+                                      mag, phs, knobs, ae_m, ae_p, L.go, L.PG, mag_hat, phs_hat, dAA, g_mag_hat, reg_coef, expfac,
+                                      dmag, dphs, parts, d->B, d->T, d->OT, d->F, d->K, L.KP, live.t_lo, t_hi, nsl, slab, nullptr, nullptr, nullptr); }); }));
+        } else
         if (have_fwd && ae_use_saved(d)) {               // round 6: the forward of this workspace kept the activations -- no recompute (fp32 layers only)
             const float* sv = ae_sv_ptr(d, L, ws);
             const float* img = (have_img && ae_img_level(d) == 2) ? ae_img_ptr(ws) : nullptr;
@@ -1583,21 +1602,28 @@ static int wgrad16_and_reduce(Call& c, float* grads, bool synth, int half, float
     ST_LAUNCHED(synth ? "synthesis_wgrad_reduce" : "analysis_wgrad_reduce");
     return ST_OK;
 }
-static int backward_syn(Call& c, float* grads, int* defer_slabs = nullptr, stm::NyqJob* defer_nyq = nullptr)
+// stages (ST_STAGE_*, st_train_step_groups): a stage outside the set is not launched; every other caller runs them all
+static const int ST_STAGE_EVERY = ST_STAGE_SYN_DGRAD | ST_STAGE_SYN_WGRAD | ST_STAGE_AE_BWD | ST_STAGE_AE_DINPUT | ST_STAGE_ANA_WGRAD;
+static int backward_syn(Call& c, float* grads, int* defer_slabs = nullptr, stm::NyqJob* defer_nyq = nullptr, int stages = ST_STAGE_EVERY)
 {
     const st_dims* d = c.d; const Layout& L = c.L; WS& w = c.w; void* stream = c.stream;
+    const bool dgrad = (stages & ST_STAGE_SYN_DGRAD) != 0, wgrad = (stages & ST_STAGE_SYN_WGRAD) != 0;
     if (w.g16) {
-        ST_TRY(synthesis_dgrad16(d, w, stream));
+        if (dgrad) ST_TRY(synthesis_dgrad16(d, w, stream));
         if (defer_slabs && defer_nyq) { *defer_nyq = stm::NyqJob{}; defer_nyq->on = 0; }
-        return wgrad16_and_reduce(c, grads, true, -1, nullptr, 0, defer_slabs);
+        return wgrad ? wgrad16_and_reduce(c, grads, true, -1, nullptr, 0, defer_slabs) : ST_OK;
     }
+    if (dgrad) {
     if (use_planes(d) && g_pl_dgrad) ST_TRY(synthesis_dgrad_planes(d, w, stream)); else
     ST_TRY(synthesis_dgrad_impl(d, w.dsyn, true, w.Sfold, w.dAA, stream));
+    }
+    if (!wgrad) return ST_OK;
     return synthesis_wgrad_impl(d, w.AA, w.dsyn, true, w.wg, grads + L.offs[2], grads + L.offs[3], w.norm_s, stream, defer_slabs, defer_nyq);
 }
 static int backward_ae(Call& c, const float* params, float* grads, const float* g_mag_hat, const float* g_mag, float reg_coef, int syn_slabs = 0,
-                       const stm::NyqJob* syn_nyq = nullptr, float* kg = nullptr)
-{   // syn_slabs > 0: the synthesis weight-gradient slabs in w.wg are still to be summed (done by post_ae_kernel)
+                       const stm::NyqJob* syn_nyq = nullptr, float* kg = nullptr, int stages = ST_STAGE_EVERY)
+{   // stages without ST_STAGE_AE_DINPUT (st_train_step_groups, analysis bases frozen): no input gradient is wanted and no polar backward runs
+    // syn_slabs > 0: the synthesis weight-gradient slabs in w.wg are still to be summed (done by post_ae_kernel)
     const st_dims* d = c.d; const Layout& L = c.L; WS& w = c.w; void* stream = c.stream;
     const float* ae_m = params + L.offs[4]; const float* ae_p = params + L.offs[22];
     bool deferred = true;
@@ -1609,7 +1635,7 @@ static int backward_ae(Call& c, const float* params, float* grads, const float* 
     }
     ST_TRY(ae_bwd_body(d, L, w.mag, w.phs, c.knobs, ae_m, ae_p, w.mag_hat, w.phs_hat, w.dAA, g_mag_hat, reg_coef, w.dmag, w.dphs,
                        w.aews, grads + L.offs[4], grads + L.offs[22], true, stream, &deferred, &sink, syn.wg ? &syn : nullptr,
-                       (d->clip_all && ae_is_wide(d)) ? w.norm_e : nullptr, &w.n_norm_e, kg, true));      // the forward left its AE state in w.aews
+                       (d->clip_all && ae_is_wide(d)) ? w.norm_e : nullptr, &w.n_norm_e, kg, true, !(stages & ST_STAGE_AE_DINPUT)));      // the forward left its AE state in w.aews
     if (!deferred) return ST_OK;                       // wide geometries: the gradient-finish launch summed the partials (and the synthesis slabs), and the polar backward ran inside wide_dv_polar_kernel
     stm::PostAeArgs a;
     a.ws = w.aews + 2 * ae_h4_floats(d); a.nparts = ae_use_split(d) ? ae_split_grid(d) : ae_bwd_grid(d); a.PG = L.PG; a.g_m = grads + L.offs[4]; a.g_p = grads + L.offs[22];
@@ -1628,15 +1654,18 @@ static int backward_ae(Call& c, const float* params, float* grads, const float* 
     if (w.g16) { a.dG16 = w.dG16; a.ht = gemm_ht(d->prec); a.dG = nullptr; }      // the analysis weight-gradient GEMM is the only consumer on this path
     a.norm_e = nullptr;
     if (d->clip_all && a.n_red <= NORM_E_MAX) { a.norm_e = w.norm_e; w.n_norm_e = a.n_red; }
+    if (!(stages & ST_STAGE_AE_DINPUT)) a.n_polar = 0;      // the reduction blocks, then (if any) the synthesis slab blocks: the kernel's block arithmetic admits an empty polar role
     hipLaunchKernelGGL(stm::post_ae_kernel, dim3(a.n_red + a.n_polar + (syn_slabs > 0 ? norm_partials(d) : 0)), dim3(256), 0, st_stream(stream), a);
+    if (!(stages & ST_STAGE_AE_DINPUT)) { ST_LAUNCHED("post_ae_reduce"); return ST_OK; }
     ST_LAUNCHED("post_ae");
     return ST_OK;
 }
-static int backward_p1(Call& c, const float* params, float* grads, const float* g_mag_hat, const float* g_mag, float reg_coef, float* kg = nullptr)
+static int backward_p1(Call& c, const float* params, float* grads, const float* g_mag_hat, const float* g_mag, float reg_coef, float* kg = nullptr, int stages = ST_STAGE_EVERY)
 {
+    if (!(stages & ST_STAGE_AE_BWD)) return backward_syn(c, grads, nullptr, nullptr, stages);      // only the synthesis bases train: their GEMM and its own slab reduce
     int syn_slabs = 0; stm::NyqJob syn_nyq{}; syn_nyq.on = 0;
-    ST_TRY(backward_syn(c, grads, &syn_slabs, &syn_nyq));      // the slab sum rides in a later launch: post_ae_kernel (fused geometries) / wide_grad_finish_kernel (wide ones)
-    return backward_ae(c, params, grads, g_mag_hat, g_mag, reg_coef, syn_slabs, &syn_nyq, kg);
+    ST_TRY(backward_syn(c, grads, &syn_slabs, &syn_nyq, stages));      // the slab sum rides in a later launch: post_ae_kernel (fused geometries) / wide_grad_finish_kernel (wide ones)
+    return backward_ae(c, params, grads, g_mag_hat, g_mag, reg_coef, syn_slabs, &syn_nyq, kg, stages);
 }
 static int backward_p2(Call& c, float* grads, float* stage = nullptr, int stage_bf16 = 0)
 {
@@ -1916,6 +1945,72 @@ extern "C" int st_train_step(const st_dims* d, float* params, float* grads, floa
                              float lr, float beta1, float beta2, float eps, int step, void* stream)
 {
     return train_step_impl(d, params, grads, m, v, x, knobs, y_true, ws, scalars, lr, beta1, beta2, eps, step, stream, false);
+}
+
+// ------------------------------------------------------------------------------ the step with frozen parameter groups
+extern "C" int st_step_groups_stages(int trainable)
+{
+    if (trainable < 1 || trainable > ST_GROUP_ALL) return -1;
+    int s = 0;
+    if (trainable & ST_GROUP_SYNTHESIS) s |= ST_STAGE_SYN_WGRAD;
+    if (trainable & (ST_GROUP_AE_MAG | ST_GROUP_AE_PHS | ST_GROUP_ANALYSIS)) s |= ST_STAGE_AE_BWD | ST_STAGE_SYN_DGRAD;
+    if (trainable & ST_GROUP_ANALYSIS) s |= ST_STAGE_AE_DINPUT | ST_STAGE_ANA_WGRAD;
+    return s;
+}
+// The optimizer launch of a step is marked with the groups it updates (st_profile_report): bit g of the number = group g
+static const char* const CLIP_ADAM_GROUPS[16] = {"", "clip_adam_g1", "clip_adam_g2", "clip_adam_g3", "clip_adam_g4", "clip_adam_g5", "clip_adam_g6", "clip_adam_g7",
+                                                 "clip_adam_g8", "clip_adam_g9", "clip_adam_g10", "clip_adam_g11", "clip_adam_g12", "clip_adam_g13", "clip_adam_g14", "clip_adam_g15"};
+extern "C" int st_train_step_groups(const st_dims* d, float* params, float* grads, float* m, float* v, const float* x,
+                                    const float* knobs, const float* y_true, void* ws, float* scalars,
+                                    float lr, float beta1, float beta2, float eps, const int step[4], int trainable, void* stream)
+{
+    ST_REQ(trainable >= 1 && trainable <= ST_GROUP_ALL, "st_train_step_groups: trainable = %d is not a non-empty set of the four ST_GROUP_* bits (1..15)", trainable);
+    ST_REQ(step, "st_train_step_groups: null pointer (step)");
+    for (int g = 0; g < 4; ++g)
+        ST_REQ(!((trainable >> g) & 1) || step[g] >= 1, "st_train_step_groups: step[%d] = %d, the Adam step number of a trainable group must be at least 1", g, step[g]);
+    if (trainable == ST_GROUP_ALL && step[0] == step[1] && step[1] == step[2] && step[2] == step[3])      // nothing frozen, one step number: the plain step, launch for launch
+        return train_step_impl(d, params, grads, m, v, x, knobs, y_true, ws, scalars, lr, beta1, beta2, eps, step[0], stream, false);
+    Call c; ST_TRY(call_begin(&c, d, params, knobs, ws, stream, G16_PIPELINE));
+    const Layout& L = c.L; WS& w = c.w;
+    ST_REQ(params && grads && m && v && x && (knobs || d->K == 0) && y_true && ws && scalars, "st_train_step_groups: null pointer");
+    const int stages = st_step_groups_stages(trainable);
+    prof_mark("begin", stream);
+    ST_TRY(forward_impl(c, params, x, y_true, nullptr, nullptr, nullptr, true));
+    ST_TRY(backward_p1(c, params, grads, nullptr, nullptr, reg_coef_of(d), nullptr, stages));
+    if (stages & ST_STAGE_ANA_WGRAD) ST_TRY(backward_p2(c, grads));
+    const float inv_s = 1.0f / loss_scale_of(d);
+    // the clip norm: |g| partials of the trainable tensors of the clip scope only
+    stm::FinArgs f = fin_args(d, w.loss_p, w.reg_p, (trainable & ST_GROUP_ANALYSIS) ? w.norm_a : nullptr, (trainable & ST_GROUP_SYNTHESIS) ? w.norm_s : nullptr, inv_s);
+    const int ae_bits = trainable & (ST_GROUP_AE_MAG | ST_GROUP_AE_PHS);
+    if (d->clip_all && ae_bits) {
+        if (ae_bits == (ST_GROUP_AE_MAG | ST_GROUP_AE_PHS) && w.n_norm_e > 0) { f.norm_e = w.norm_e; f.n_ne = w.n_norm_e; }      // left by the kernel that summed both nets' gradients
+        else {
+            const int64_t b = (ae_bits & ST_GROUP_AE_MAG) ? L.offs[4] : L.offs[22], e = (ae_bits & ST_GROUP_AE_PHS) ? L.total : L.offs[22];
+            hipLaunchKernelGGL(stm::l1_partial_kernel, dim3(NORM_E_PARTIALS), dim3(256), 0, st_stream(stream), grads + b, e - b, 1.0f, w.norm_e);
+            ST_LAUNCHED("l1_partial_ae");
+            f.norm_e = w.norm_e; f.n_ne = NORM_E_PARTIALS;
+        }
+    }
+    // one range per run of adjacent trainable groups with one step number and one clip rule
+    const int64_t gb[5] = {L.offs[0], L.offs[2], L.offs[4], L.offs[22], L.total};
+    const float w1 = (float)(1.0 - (double)beta1), w2 = (float)(1.0 - (double)beta2);
+    stm::AdamRanges tab; tab.n = 0;
+    int64_t n4 = 0;
+    for (int g = 0; g < 4; ++g) {
+        if (!((trainable >> g) & 1)) continue;
+        const int clipped = (g < 2 || d->clip_all) ? 1 : 0;
+        const bool joins = tab.n > 0 && ((trainable >> (g - 1)) & 1) && step[g - 1] == step[g] && tab.r[tab.n - 1].clipped == clipped;
+        if (joins) tab.r[tab.n - 1].e4 = gb[g + 1] / 4;
+        else {
+            const double bc1 = 1.0 - pow((double)beta1, step[g]), bc2 = 1.0 - pow((double)beta2, step[g]);      // as clip_adam_impl forms them
+            tab.r[tab.n++] = stm::AdamRange{gb[g] / 4, gb[g + 1] / 4, clipped, (float)(-(double)lr / bc1), (float)sqrt(bc2)};
+        }
+        n4 += (gb[g + 1] - gb[g]) / 4;
+    }
+    for (int k = tab.n; k < 4; ++k) tab.r[k] = stm::AdamRange{0, 0, 0, 0.f, 1.f};
+    int grid = (int)((n4 + 255) / 256); if (grid > 2048) grid = 2048; if (grid < 1) grid = 1;
+    hipLaunchKernelGGL(stm::clip_adam_ranges_kernel, dim3(grid), dim3(256), 0, st_stream(stream), params, grads, m, v, tab, scalars, inv_s, w1, beta2, w2, eps, f);
+    ST_LAUNCHED(CLIP_ADAM_GROUPS[trainable]); return ST_OK;
 }
 
 extern "C" int st_dp_clip_adam(const st_dims* d, float* params, float* grads, float* m, float* v, void* ws,

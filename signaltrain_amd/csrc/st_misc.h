@@ -772,6 +772,16 @@ eval_finalize_kernel(const FinArgs f, const double beta, double* __restrict__ ac
 // DEV (the HIP-graph form of the step, st_graph_*): the step number and the learning rate are read from device memory
 // (scalars[6], scalars[7], written by step_tick_kernel at the head of the graph) and the bias corrections are formed here, in
 // double like the host does, so that ONE captured graph replays every iteration of a run.
+// one element of the update (both optimizer kernels below): sc, w1, b2, w2, bc2_sqrt, eps, neg_step_size and the float4s G, M, V, P are in scope
+#define ST_ADAM1(c)                                                        \
+    {                                                                  \
+        const float gg = (sc == 1.0f) ? G.c : G.c * sc;                \
+        M.c = M.c + w1 * (gg - M.c);                                   \
+        V.c = V.c * b2 + (w2 * gg) * gg;                               \
+        const float den = sqrtf(V.c) / bc2_sqrt + eps;                 \
+        P.c = P.c + (neg_step_size * M.c) / den;                       \
+        G.c = gg;                                                      \
+    }
 template <bool FIN, bool DEV = false>
 __global__ void __launch_bounds__(256)
 clip_adam_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
@@ -814,17 +824,7 @@ clip_adam_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict
         if (G.x == 0.f && G.y == 0.f && G.z == 0.f && G.w == 0.f && M.x == 0.f && M.y == 0.f && M.z == 0.f && M.w == 0.f &&
             V.x == 0.f && V.y == 0.f && V.z == 0.f && V.w == 0.f) continue;
         float4 P = reinterpret_cast<float4*>(p)[i];
-#define ST_ADAM1(c)                                                        \
-        {                                                                  \
-            const float gg = (sc == 1.0f) ? G.c : G.c * sc;                \
-            M.c = M.c + w1 * (gg - M.c);                                   \
-            V.c = V.c * b2 + (w2 * gg) * gg;                               \
-            const float den = sqrtf(V.c) / bc2_sqrt + eps;                 \
-            P.c = P.c + (neg_step_size * M.c) / den;                       \
-            G.c = gg;                                                      \
-        }
         ST_ADAM1(x) ST_ADAM1(y) ST_ADAM1(z) ST_ADAM1(w)
-#undef ST_ADAM1
         if (sc != 1.0f) reinterpret_cast<float4*>(g)[i] = G;       // the clipped / rescaled gradient is observable in the reference (p.grad); with sc == 1 (clip inactive, one rank,
                                                                    // no loss scale) the buffer already holds these very values: 12.6 MB of writes less per step
         reinterpret_cast<float4*>(m)[i] = M;
@@ -832,6 +832,52 @@ clip_adam_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict
         reinterpret_cast<float4*>(p)[i] = P;
     }
 }
+
+// The same step over up to four RANGES of the flat buffers (st_train_step_groups: the trainable parameter groups, adjacent ones with one step number
+// merged).  Everything outside the ranges -- parameters, moments, gradients of the frozen groups -- is neither read nor written.  Each range carries its
+// own Adam bias corrections (torch keeps state['step'] per parameter: a group unfrozen late starts at step 1) and says whether the clip coefficient
+// applies to it.  `fin` holds the |g| partials of the TRAINABLE tensors of the clip scope only; with none the norm is 0 and the coefficient 1.  One launch
+// rather than one per range: every launch re-derives the coefficient from the partial sums in every block, and the autoencoder ranges (33 KB each at
+// the default geometry) would be launches of nothing but that prologue.
+struct AdamRange { int64_t b4, e4; int clipped; float neg_step, bc2_sqrt; };      // [b4, e4) in float4 units
+struct AdamRanges { AdamRange r[4]; int n; };
+__global__ void __launch_bounds__(256)
+clip_adam_ranges_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, const AdamRanges tab,
+                        float* __restrict__ scalars, const float grad_scale, const float w1, const float b2, const float w2, const float eps, const FinArgs fin)
+{
+    __shared__ float red[4];
+    float lc, rg, nrm;
+    const float coef = finalize_block(fin, blockIdx.x == 0, red, lc, rg, nrm);
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        if (fin.loss_partial) { scalars[1] = lc; scalars[2] = rg; scalars[0] = lc + rg; }
+        scalars[3] = nrm; scalars[4] = coef;
+    }
+    if (!(nrm <= 3.0e38f)) {                         // overflow under the loss scale: no trainable group moves
+        if (blockIdx.x == 0 && threadIdx.x == 0) scalars[5] = scalars[5] + 1.0f;
+        return;
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        if (k >= tab.n) break;
+        const float sc = tab.r[k].clipped ? grad_scale * coef : grad_scale;
+        const float neg_step_size = tab.r[k].neg_step, bc2_sqrt = tab.r[k].bc2_sqrt;
+        const int64_t e4 = tab.r[k].e4;
+        for (int64_t i = tab.r[k].b4 + (int64_t)blockIdx.x * 256 + threadIdx.x; i < e4; i += (int64_t)gridDim.x * 256) {
+            float4 G = reinterpret_cast<float4*>(g)[i];
+            float4 M = reinterpret_cast<float4*>(m)[i];
+            float4 V = reinterpret_cast<float4*>(v)[i];
+            if (G.x == 0.f && G.y == 0.f && G.z == 0.f && G.w == 0.f && M.x == 0.f && M.y == 0.f && M.z == 0.f && M.w == 0.f &&
+                V.x == 0.f && V.y == 0.f && V.z == 0.f && V.w == 0.f) continue;      // the fixed point clip_adam_kernel skips
+            float4 P = reinterpret_cast<float4*>(p)[i];
+            ST_ADAM1(x) ST_ADAM1(y) ST_ADAM1(z) ST_ADAM1(w)
+            if (sc != 1.0f) reinterpret_cast<float4*>(g)[i] = G;
+            reinterpret_cast<float4*>(m)[i] = M;
+            reinterpret_cast<float4*>(v)[i] = V;
+            reinterpret_cast<float4*>(p)[i] = P;
+        }
+    }
+}
+#undef ST_ADAM1
 
 
 // Head of the captured step (st_graph_*): advance the device-side step counter and look the learning rate up in the device copy

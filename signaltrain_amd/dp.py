@@ -93,6 +93,10 @@ class DataParallel:
         eng = self.engine
         if self.world == 1 and not self.force:
             return eng.train_step(x, knobs, y, lr, **kw)
+        if getattr(eng, "trainable", _lib.GROUP_ALL) != _lib.GROUP_ALL or len(set(getattr(eng, "group_steps", [0]))) != 1:
+            # the exchange moves every gradient range and the step behind it updates every group with one step number
+            raise NotImplementedError("DataParallel: the data-parallel step has no form with frozen parameter groups (or with groups whose Adam step "
+                                      f"numbers differ): trainable mask {getattr(eng, 'trainable', None)}, group steps {getattr(eng, 'group_steps', None)}")
         if self.backend == "lib":
             return eng.dp_train_step(x, knobs, y, lr, force_exchange=self.force, split_last=(self.schedule == "staged"), pack16=self.pack16, **kw)
         if self.schedule == "two_bucket":

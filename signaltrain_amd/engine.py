@@ -117,6 +117,8 @@ class StepEngine:
         self.named = self.layout.views(self.params)
         self.named_grads = self.layout.views(self.grads)
         self.step_count = 0
+        self.trainable = _lib.GROUP_ALL      # ST_GROUP_* mask of the parameter groups train_step updates (set_trainable / sync_trainable)
+        self._group_lag = [0, 0, 0, 0]       # steps each group sat out frozen: group_steps = step_count - lag
         self.generation = 0          # bumped by every call that overwrites the saved-for-backward state in the workspace
         self.dp = None               # st_dp* of the library-owned RCCL communicator (dp.DataParallel attaches it)
         self._pending = None
@@ -147,7 +149,8 @@ class StepEngine:
         moment buffers copied to the host) -- what the reference writes into its checkpoints (misc.py:28)."""
         from . import misc
         m, v = self.layout.views(self.m.detach().cpu()), self.layout.views(self.v.detach().cpu())
-        return misc.adam_state_dict(self.step_count, self.lr if lr is None else lr,
+        steps = [self.group_steps[g] for g, sl in enumerate(misc.GROUP_SLICES) for _ in range(sl.stop - sl.start)]      # each parameter's own group step; 0 = never stepped
+        return misc.adam_state_dict(steps, self.lr if lr is None else lr,
                                     [t.clone() for t in m.values()], [t.clone() for t in v.values()])
 
     def load_optimizer_state_dict(self, osd):
@@ -162,10 +165,80 @@ class StepEngine:
             for view, src in zip(self.layout.views(buf).values(), flat[key]):
                 view.copy_(torch.from_numpy(src).to(self.device).reshape(view.shape))
         self.step_count = int(flat["step"])
+        self.group_steps = [int(flat["steps"][sl.start]) for sl in misc.GROUP_SLICES]
         self.lr = float(flat["lr"])
         return self.lr
 
     lr = 0.0        # last learning rate handed to train_step (recorded for optimizer_state_dict)
+
+    # ---------------------------------------------------------------- frozen parameter groups
+    GROUP_NAMES = ("analysis", "synthesis", "aenc", "phs_aenc")
+    GROUP_MODULES = ("mpaec.dft_analysis.", "mpaec.dft_synthesis.", "mpaec.aenc.", "mpaec.phs_aenc.")
+
+    @staticmethod
+    def group_mask(mask_or_names):
+        """An ST_GROUP_* mask from a mask or from an iterable of group names ("analysis", "synthesis", "aenc", "phs_aenc", "frontend" = the first two)."""
+        if isinstance(mask_or_names, (int, np.integer)):
+            mask = int(mask_or_names)
+        else:
+            names = [mask_or_names] if isinstance(mask_or_names, str) else list(mask_or_names)
+            bad = [n for n in names if n not in _lib.GROUP_SETS]
+            if bad:
+                raise ValueError(f"unknown parameter group(s) {bad}: the groups are {sorted(_lib.GROUP_SETS)}")
+            mask = 0
+            for n in names:
+                mask |= _lib.GROUP_SETS[n]
+        if not 0 <= mask <= _lib.GROUP_ALL:
+            raise ValueError(f"group mask {mask} is not a set of the four ST_GROUP_* bits")
+        return mask
+
+    @property
+    def group_steps(self):
+        """Adam step number of each group so far, in the order analysis, synthesis, aenc, phs_aenc (torch's per-parameter state['step']): step_count less
+        the steps the group sat out frozen.  step_count counts train_step calls; assigning to it moves every group along."""
+        return [max(int(self.step_count) - lag, 0) for lag in self._group_lag]
+
+    @group_steps.setter
+    def group_steps(self, steps):
+        steps = [int(s) for s in steps]
+        if len(steps) != 4 or min(steps) < 0 or max(steps) > int(self.step_count):
+            raise ValueError(f"group_steps: four step numbers in 0..step_count ({self.step_count}) expected, got {steps}")
+        self._group_lag = [int(self.step_count) - s for s in steps]
+
+    def set_trainable(self, mask_or_names):
+        """The groups train_step updates from now on (default: all four).  A frozen group's parameters and Adam moments are not written and its step
+        number stands still (st_train_step_groups in include/signaltrain_hip.h)."""
+        mask = self.group_mask(mask_or_names)
+        if mask == 0:
+            raise ValueError("set_trainable: nothing trainable -- at least one parameter group has to train")
+        self.trainable = mask
+        return mask
+
+    def sync_trainable(self, model):
+        """Take the mask from the requires_grad flags of `model` (an st_model, or anything whose named_parameters() carry its names): a group is trainable
+        iff all its parameters require grad -- what nn_proc.freeze_layers / st_model.freeze() leave behind.  The groups freeze as a whole: a group with
+        mixed flags raises ValueError naming its tensors, and so does a model with nothing trainable."""
+        flags = {n: bool(p.requires_grad) for n, p in model.named_parameters()}
+        mask = 0
+        for g, prefix in enumerate(self.GROUP_MODULES):
+            mine = {n: f for n, f in flags.items() if n.startswith(prefix)}
+            if not mine:
+                raise ValueError(f"sync_trainable: the model has no parameters under {prefix!r}")
+            if all(mine.values()):
+                mask |= 1 << g
+            elif any(mine.values()):
+                raise ValueError(f"sync_trainable: group {self.GROUP_NAMES[g]!r} is partly frozen (a group freezes as a whole): "
+                                 f"frozen {sorted(n for n, f in mine.items() if not f)}, trainable {sorted(n for n, f in mine.items() if f)}")
+        if mask == 0:
+            raise ValueError("sync_trainable: every parameter of the model is frozen -- nothing to train")
+        self.trainable = mask
+        return mask
+
+    def _refuse_frozen(self, what):
+        """The captured step and the data-parallel step update every group with one step number: no form with frozen groups."""
+        if self.trainable != _lib.GROUP_ALL or len(set(self.group_steps)) != 1:
+            raise NotImplementedError(f"{what}: no form with frozen parameter groups or with groups whose Adam step numbers differ "
+                                      f"(trainable mask {self.trainable}, group steps {self.group_steps}); train_step takes both")
 
     # ---------------------------------------------------------------- plumbing
     def _dims(self, B):
@@ -361,11 +434,22 @@ class StepEngine:
         time, i.e. lr_sched[max(i-1,0)] in the reference loop (train.py:150).  No host sync."""
         d, x, knobs, y = self._prep(x, knobs, y)
         self._pending = None               # a later clip_adam() must not carve the workspace with an older backward's dims
+        if self.step_count == 0:
+            self._group_lag = [0, 0, 0, 0]    # a reset optimizer (step_count = 0 with cleared moments): no group has a history
         self.step_count += 1; self.generation += 1; self.lr = float(lr)
-        self._call("st_train_step", C.byref(d), _lib.ptr(self.params), _lib.ptr(self.grads), _lib.ptr(self.m),
-                   _lib.ptr(self.v), _lib.ptr(x), _lib.ptr(knobs), _lib.ptr(y), _lib.ptr(self.ws),
-                   _lib.ptr(self.scalars), float(lr), float(betas[0]), float(betas[1]), float(eps),
-                   int(self.step_count), self._stream())
+        mask = int(self.trainable)
+        self._group_lag = [lag if (mask >> g) & 1 else lag + 1 for g, lag in enumerate(self._group_lag)]      # a frozen group's step number stands still
+        steps = self.group_steps
+        if mask == _lib.GROUP_ALL and len(set(steps)) == 1:
+            self._call("st_train_step", C.byref(d), _lib.ptr(self.params), _lib.ptr(self.grads), _lib.ptr(self.m),
+                       _lib.ptr(self.v), _lib.ptr(x), _lib.ptr(knobs), _lib.ptr(y), _lib.ptr(self.ws),
+                       _lib.ptr(self.scalars), float(lr), float(betas[0]), float(betas[1]), float(eps),
+                       int(steps[0]), self._stream())
+        else:
+            self._call("st_train_step_groups", C.byref(d), _lib.ptr(self.params), _lib.ptr(self.grads), _lib.ptr(self.m),
+                       _lib.ptr(self.v), _lib.ptr(x), _lib.ptr(knobs), _lib.ptr(y), _lib.ptr(self.ws),
+                       _lib.ptr(self.scalars), float(lr), float(betas[0]), float(betas[1]), float(eps),
+                       (C.c_int * 4)(*steps), mask, self._stream())
         return self.scalars
 
     # ---------------------------------------------------------------- validation on the device
@@ -396,6 +480,7 @@ class StepEngine:
         """Capture st_train_step for `batch` windows into a HIP graph (st_graph_create).  The step counter and the learning rate
         live on the device (scalars[6], scalars[7]; `lr_table` = the 1-cycle table, uploaded once): graph_step() then needs no
         per-step arguments.  The minibatch is read from the fixed buffers self.gx / self.gk / self.gy."""
+        self._refuse_frozen("graph_capture")
         d = self._dims(int(batch))
         dev = self.device
         self.gx = torch.zeros(d.B, d.L, dtype=torch.float32, device=dev)
@@ -419,6 +504,7 @@ class StepEngine:
     def graph_step(self, x=None, knobs=None, y=None):
         """One optimisation step = one hipGraphLaunch on the current stream.  x / knobs / y (optional) are copied into the
         graph's input buffers first; with all three None the buffers are used as they are (device-resident data)."""
+        self._refuse_frozen("graph_step")
         if x is not None:
             self.gx.copy_(x); self.gy.copy_(y)
             if self.dims.K: self.gk.copy_(knobs)

@@ -49,29 +49,42 @@ def load_checkpoint(checkpointname, fatal=False, device="cuda"):
 
 
 # ---------------------------------------------------------------------------------------- optimizer state <-> flat buffers
+# the four parameter groups that freeze or train as a whole (ST_GROUP_* of include/signaltrain_hip.h), as index ranges into the 40 tensors in state_dict order
+GROUP_SLICES = (slice(0, 2), slice(2, 4), slice(4, 22), slice(22, 40))
+
+
 def flatten_optimizer_state(opt_sd, shapes):
-    """torch.optim.Adam.state_dict() -> {'step': int, 'lr': float, 'betas', 'eps', 'exp_avg': [flat np.float32 per
+    """torch.optim.Adam.state_dict() -> {'step': int, 'steps': [int per parameter], 'lr': float, 'betas', 'eps', 'exp_avg': [flat np.float32 per
     parameter], 'exp_avg_sq': [...]}; None if `opt_sd` is not in that layout (e.g. the round-1 stand-in dict or {}).
-    `shapes`: the parameter shapes in state_dict order, used to validate."""
+    `shapes`: the parameter shapes in state_dict order, used to validate.  A parameter without state (torch creates none for one that never had a
+    gradient: a group frozen from the start) counts as step 0 with zero moments.  'step' is the common step, or the largest where the groups differ
+    (train.py froze some of them for a while); steps that differ INSIDE one of the four groups are refused (None): the engine keeps one step per group."""
     try:
         groups, state = opt_sd['param_groups'], opt_sd['state']
         order = [i for g in groups for i in g['params']]
-        if len(order) != len(shapes) or not all(i in state for i in order):
+        if len(order) != len(shapes) or not state:
             return None
         out = {'lr': float(groups[0]['lr']), 'betas': tuple(groups[0]['betas']), 'eps': float(groups[0]['eps']),
                'exp_avg': [], 'exp_avg_sq': []}
-        steps = set()
+        steps = []
         for i, shp in zip(order, shapes):
-            st = state[i]
+            st = state.get(i)
+            if st is None:
+                out['exp_avg'].append(np.zeros(int(np.prod(shp)), dtype=np.float32)); out['exp_avg_sq'].append(np.zeros(int(np.prod(shp)), dtype=np.float32))
+                steps.append(0)
+                continue
             m, v = st['exp_avg'], st['exp_avg_sq']
             if tuple(m.shape) != tuple(shp) or tuple(v.shape) != tuple(shp):
                 return None
             out['exp_avg'].append(np.ascontiguousarray(m.detach().cpu().numpy(), dtype=np.float32).ravel())
             out['exp_avg_sq'].append(np.ascontiguousarray(v.detach().cpu().numpy(), dtype=np.float32).ravel())
-            steps.add(int(float(st['step'])))
-        if len(steps) != 1:
+            steps.append(int(float(st['step'])))
+        if len(shapes) == 40:
+            if any(len(set(steps[sl])) != 1 for sl in GROUP_SLICES):
+                return None
+        elif len(set(steps)) != 1:
             return None
-        out['step'] = steps.pop()
+        out['step'], out['steps'] = max(steps), steps
         return out
     except (KeyError, TypeError, AttributeError, IndexError):
         return None
@@ -79,9 +92,13 @@ def flatten_optimizer_state(opt_sd, shapes):
 
 def adam_state_dict(step, lr, exp_avg, exp_avg_sq, betas=(0.9, 0.999), eps=1e-8, extra_group=None):
     """The inverse: per-parameter tensors (lists in state_dict order) -> torch.optim.Adam.state_dict() layout, loadable by
-    `torch.optim.Adam(model.parameters()).load_state_dict`."""
+    `torch.optim.Adam(model.parameters()).load_state_dict`.  step: one number for all parameters, or one per parameter (groups that were frozen for
+    part of the run lag behind; 0 = never stepped, written with its zero moments so that the file keeps one entry per parameter)."""
     n = len(exp_avg)
-    state = {i: {'step': torch.tensor(float(step)), 'exp_avg': exp_avg[i], 'exp_avg_sq': exp_avg_sq[i]} for i in range(n)}
+    steps = [step] * n if np.isscalar(step) else list(step)
+    if len(steps) != n:
+        raise ValueError(f"adam_state_dict: {len(steps)} step numbers for {n} parameters")
+    state = {i: {'step': torch.tensor(float(steps[i])), 'exp_avg': exp_avg[i], 'exp_avg_sq': exp_avg_sq[i]} for i in range(n)}
     group = {'lr': float(lr), 'betas': tuple(betas), 'eps': float(eps), 'weight_decay': 0, 'amsgrad': False, 'maximize': False,
              'foreach': None, 'capturable': False, 'differentiable': False, 'fused': None, 'decoupled_weight_decay': False,
              'params': list(range(n))}

@@ -23,6 +23,19 @@ def _say(*a):
         print(*a)
 
 
+def freeze_layers(layers):
+    """nn_proc.py:17-20: the parameters of these modules stop requiring grad.  The fused step honours the flags group by group once
+    StepEngine.sync_trainable(model) has read them (train_loop does so at the head of every epoch)."""
+    for module in layers:
+        module.requires_grad_(False)
+
+
+def unfreeze_layers(layers):
+    """nn_proc.py:22-25: the inverse of freeze_layers."""
+    for module in layers:
+        module.requires_grad_(True)
+
+
 class _Lin(nn.Module):
     """Parameter holder with nn.Linear's attribute names (weight [out,in], bias [out])."""
 
@@ -213,6 +226,8 @@ class AsymMPAEC(nn.Module):
             for p, v in zip(ps, new.named.values()):
                 v.copy_(p.detach().to(x.device).reshape(v.shape))
                 p.data = v
+        if eng is not None:
+            new.trainable = eng.trainable    # a larger batch or another device: what was frozen stays frozen
         self._engine = new
         return new
 
@@ -299,6 +314,18 @@ class st_model(nn.Module):
 
     def forward(self, x_cuda, knobs_cuda, return_acts=False):
         return self.mpaec.forward(x_cuda, knobs_cuda, return_acts=return_acts)
+
+    def freeze(self):
+        """Train the two autoencoders over a fixed front end: the analysis and synthesis bases stop requiring grad (the pair of methods the reference
+        left commented out as "not quite ready", nn_proc.py:395-401).  An engine already made takes the new mask at once."""
+        freeze_layers([self.mpaec.dft_analysis, self.mpaec.dft_synthesis])
+        if self.mpaec._engine is not None:
+            self.mpaec._engine.sync_trainable(self)
+
+    def unfreeze(self):
+        unfreeze_layers([self.mpaec.dft_analysis, self.mpaec.dft_synthesis])
+        if self.mpaec._engine is not None:
+            self.mpaec._engine.sync_trainable(self)
 
     def engine(self, example_x):
         """The fused StepEngine sharing this model's parameters (fast training path)."""

@@ -65,16 +65,37 @@ def eval_status_save(model, engine, effect, epoch, epochs, lr, mom, device, data
 
 def train_loop(model, engine, effect, device, epochs, batch_size, lr_sched, mom_sched, dataloader, dataloader_val,
                y_size, logfilename, out_checkpointname, plot_every=10, cp_every=25, sr=44100, lr_max=1e-4,
-               start_epoch=0, start_iter=0, lr_resume=None, device_eval=False):
-    """train.py:84-164.  start_epoch / start_iter / lr_resume: position restored from a checkpoint (epoch counter, optimizer
+               start_epoch=0, start_iter=0, lr_resume=None, device_eval=False, freeze=None, unfreeze_epoch=None):
+    """train.py:84-164.  freeze / unfreeze_epoch: see train().  start_epoch / start_iter / lr_resume: position restored from a checkpoint (epoch counter, optimizer
     step count = position in the 1-cycle table, the learning rate that sat in the optimizer) -- the reference restarts all
     three at zero on resume (train.py:229 TODO)."""
     dp = DataParallel(engine)
     try:
         return _train_loop(dp, model, engine, effect, device, epochs, batch_size, lr_sched, mom_sched, dataloader, dataloader_val,
-                           y_size, logfilename, out_checkpointname, plot_every, cp_every, sr, lr_max, start_epoch, start_iter, lr_resume, device_eval)
+                           y_size, logfilename, out_checkpointname, plot_every, cp_every, sr, lr_max, start_epoch, start_iter, lr_resume, device_eval,
+                           freeze, unfreeze_epoch)
     finally:
         dp.close()          # the library-owned RCCL communicator, its stream and events (before the caller destroys the process group)
+
+
+def freeze_modules(model, freeze):
+    """The modules of an st_model behind train()'s group names: "analysis", "synthesis", "aenc", "phs_aenc", "frontend" (= the first two)."""
+    groups = {"analysis": [model.mpaec.dft_analysis], "synthesis": [model.mpaec.dft_synthesis], "aenc": [model.mpaec.aenc],
+              "phs_aenc": [model.mpaec.phs_aenc]}
+    groups["frontend"] = groups["analysis"] + groups["synthesis"]
+    return [m for name in freeze for m in groups[name]]
+
+
+def check_freeze(freeze):
+    """train()'s freeze argument as a tuple of group names; ValueError for a name that is no group."""
+    if freeze is None:
+        return ()
+    names = (freeze,) if isinstance(freeze, str) else tuple(freeze)
+    known = ("analysis", "synthesis", "aenc", "phs_aenc", "frontend")
+    bad = [n for n in names if n not in known]
+    if bad:
+        raise ValueError(f"train(): freeze names unknown parameter group(s) {bad}; the groups are {known}")
+    return names
 
 
 def seed_data_streams(rank):
@@ -88,7 +109,9 @@ def seed_data_streams(rank):
 
 
 def _train_loop(dp, model, engine, effect, device, epochs, batch_size, lr_sched, mom_sched, dataloader, dataloader_val,
-                y_size, logfilename, out_checkpointname, plot_every, cp_every, sr, lr_max, start_epoch, start_iter, lr_resume, device_eval=False):
+                y_size, logfilename, out_checkpointname, plot_every, cp_every, sr, lr_max, start_epoch, start_iter, lr_resume, device_eval=False,
+                freeze=None, unfreeze_epoch=None):
+    freeze = check_freeze(freeze)
     dp.broadcast_parameters()
     is_main = (not dist.is_initialized()) or dist.get_rank() == 0
     iter_count, batch_num, status_every = int(start_iter), 0, 10
@@ -106,6 +129,11 @@ def _train_loop(dp, model, engine, effect, device, epochs, batch_size, lr_sched,
         if is_main:
             print("")
         data_point = 0
+        if freeze:                        # the two-phase schedule: these groups sit out the epochs before unfreeze_epoch (None: all of them)
+            frozen_now = unfreeze_epoch is None or epoch < int(unfreeze_epoch)
+            (nn_proc.freeze_layers if frozen_now else nn_proc.unfreeze_layers)(freeze_modules(model, freeze))
+        if hasattr(engine, "sync_trainable"):
+            engine.sync_trainable(model)  # requires_grad as it stands now, whoever set it (nn_proc.freeze_layers, st_model.freeze): the fused step trains exactly those groups
         t_ep = time.time()
         for x, y, knobs in dataloader:
             if x.shape[0] != batch_size:  # keep batches uniform (the reference's expand_as quirk)
@@ -175,7 +203,7 @@ def _train_loop(dp, model, engine, effect, device, epochs, batch_size, lr_sched,
 def train(effect=None, epochs=100, n_data_points=200000, batch_size=20, device=None, plot_every=10, cp_every=25, sr=44100,
           datapath=None, scale_factor=1, shrink_factor=4, apex_opt="O0", target_type="stream", lr_max=1e-4,
           in_checkpointname='modelcheckpoint.tar', compand=False, num_workers=10, device_feed=True, compute_dtype=None,
-          resume_optimizer=False, device_eval=False, choosers=None, input_path=None, synth_prob=0.0, preroll=0):
+          resume_optimizer=False, device_eval=False, choosers=None, input_path=None, synth_prob=0.0, preroll=0, freeze=None, unfreeze_epoch=None):
     """train.py:167-278.  datapath: directory with Train/ and Val/ wav pairs (datasets.AudioFileDataSet, the reference's
     file feed, e.g. the LA2A set of BASELINE configs[3]; pass effect=audio.FileEffect(datapath)); compand: mu-law compand that dataset's audio (datasets.py:218-220).
     apex_opt: "O0" = fp32 (the parity path); "O1" / "O2" / "O3" = the reference's Apex mixed precision (train.py:254-255),
@@ -198,7 +226,14 @@ def train(effect=None, epochs=100, n_data_points=200000, batch_size=20, device=N
     synth_prob: with input_path, the share of windows that are synthetic test signals of `choosers` instead (the reference's unused `synthprob`);
     preroll: with input_path, the samples of its own file the effect runs over in front of every recorded window, training and validation, so that the
     target carries the effect's state (the reference's streamed target; st_live_feed_stream, csrc/st_feed_stream.h); a multiple of 4, 0 (default) = the
-    effect starts from its zero state at the head of each window.  target_type belongs to datapath and is not read with input_path."""
+    effect starts from its zero state at the head of each window.  target_type belongs to datapath and is not read with input_path.
+    freeze: parameter groups that do not train, an iterable out of "analysis", "synthesis", "aenc", "phs_aenc", "frontend" (= the first two: the
+    autoencoders learn over the fixed DFT bases); their parameters and Adam state stay as they are and the step skips the work that only fed them
+    (st_train_step_groups).  unfreeze_epoch: the (0-based) epoch from which those groups train as well -- the two-phase schedule; None = frozen throughout.
+    requires_grad flags set by hand (nn_proc.freeze_layers, st_model.freeze) are honoured in the same way, read at the head of every epoch."""
+    freeze = check_freeze(freeze)
+    if unfreeze_epoch is not None and (not freeze or int(unfreeze_epoch) < 0):
+        raise ValueError(f"train(): unfreeze_epoch = {unfreeze_epoch} needs a freeze list and a non-negative epoch")
     if input_path is not None and datapath is not None:
         raise ValueError("train(): input_path (recorded input through the live effect) and datapath (recorded input / target pairs) are two different feeds: give one")
     if input_path is None and synth_prob:
@@ -329,5 +364,5 @@ def train(effect=None, epochs=100, n_data_points=200000, batch_size=20, device=N
     open(logfilename, "a").close()
     train_loop(model, engine, effect, device, epochs, batch_size, lr_sched, mom_sched, dataloader, dataloader_val,
                out_chunk_size, logfilename, "modelcheckpoint.tar", sr=sr, lr_max=lr_max,
-               start_epoch=start_epoch, start_iter=start_iter, lr_resume=lr_resume, device_eval=device_eval)
+               start_epoch=start_epoch, start_iter=start_iter, lr_resume=lr_resume, device_eval=device_eval, freeze=freeze, unfreeze_epoch=unfreeze_epoch)
     return model
