@@ -187,6 +187,16 @@ int st_synthesis_frames(const st_dims* d, const float* AA, const float* Sfold, f
  * Returns the entry count (one workgroup each; more than ncus = several rounds), 0 if the geometry does not use this kernel. */
 int st_nt128_worklist(const st_dims* d, int which, int ncus, unsigned* out, int cap, int* head6);
 
+/* Diagnostics, host only (no device work): the plan of the fp32 step's pair launch, which runs both 128 x 128-tile weight-gradient GEMMs (analysis and
+ * synthesis bases) in one launch -- every workgroup slot runs one k-slice of an analysis tile and then one of a synthesis tile, the tile columns paired so that
+ * the longest analysis slices meet the shortest synthesis slices.  out holds ten ints per slot, slots in the order (k-slice, tile row, tile column):
+ * {tile row, tile column, k-slice, k_begin, k_end} of the analysis entry, then the same of the synthesis entry; -1 five times where the slot has no entry of
+ * that GEMM (the GEMMs may have different k-slice counts).  k ranges are reduction rows of the frame-major order (row = (t - t_lo) * B + b) and are run in
+ * k-tiles of 32 rows; k_end <= k_begin is an empty slice whose tile is stored as zeros.  ncus <= 0: the current device's CU count; with ncus > 0 the result is
+ * a pure function of (d, ncus) and the tuning state.  Returns the slot count (cap only limits what is written), 0 where the step keeps one launch per GEMM
+ * at these dims (16-bit or split operands, wide autoencoder geometries, N % 256 != 0, st_set_tuning(9582)), < 0 on bad arguments. */
+int st_wgrad_pair_plan(const st_dims* d, int ncus, int* out, int cap);
+
 /* Diagnostics, host only: 1 if the frame-major row order may be used for a GEMM with R = (live frames) * B compact rows, i.e. if the kernels' division of a
  * row index r < R by B through a multiply-high with floor(2^32 / B) + 1 is exact (r * B < 2^32 for every r); 0: those launches keep the window-major order
  * and the untrimmed / uncropped tile sets.  (cls_fe_dft.py:28-31, :112-113: the trimming is an optimisation of the padded / cropped frames, never a

@@ -198,7 +198,8 @@ static int g_g16 = 1;        // 16-bit configurations: the fused step's GEMMs on
 static int g_g16_dma = 0;    // bit 0 / bit 1: its analysis forward / synthesis data-gradient GEMM on the LDS-DMA kernel gemm16_nt256_kernel.  MEASURED EQUAL to
                              // gemm16_nt_kernel (analysis forward, bf16, B = 256 / 1024: 34.2 / 138.6 us against 35.5 / 137.2): both deliver ~20 B/clk/CU from L2 to LDS, see st_gemm16.h
 static int g_nt128 = 1;      // fp32 synthesis frames / data-gradient GEMMs on the 128 x 128-tile NT kernel (st_gemm_tn.h); 0 = gemm_kernel<2, ...>
-static int g_tn128 = 1;      // weight-gradient GEMMs on the 128 x 128-tile kernel (st_gemm_tn.h) where it applies; 0 = gemm_kernel<3, ...>; 2 = its round-3 k-tile loop
+static int g_tn128 = 1;      // weight-gradient GEMMs on the 128 x 128-tile kernel (st_gemm_tn.h) where it applies; 0 = gemm_kernel<3, ...>; 2 = its round-3 k-tile loop;
+                             // 1 (default) also runs the two GEMMs of the fp32 step as ONE launch (wgrad_pair); 3 = the pipelined loop, one launch per GEMM (A/B timing, bit-equality test)
 static int g_tn_fm = 3;      // round 5: frame-major reduction order + per-tile-column row ranges (structural zeros skipped) in the 128 x 128 weight-gradient GEMMs: bit 0 synthesis
                              // (25 % of its reduction rows are cropped taps: 41.7 -> 37.0 us), bit 1 analysis (7.6 %: 113.8 -> 109.5 us)
 static int g_g16_crop = 15;  // round 5, 16-bit operand pipeline: structural zeros skipped (frame-major rows): bit 0 frames GEMM (dead tile columns return), bit 1 data gradient (live taps per tile row),
@@ -234,6 +235,7 @@ static const struct { int first, count; int* var; int value; int* also; } k_tuni
     {9300, 2, &g_wg_split, 0, nullptr},
     {9400, 2, &g_pl_bf16, 0, nullptr},
     {9500, 2, &g_tn128, 0, nullptr}, {9580, 1, &g_tn128, 2, nullptr}, {9581, 1, &g_tn128, 1, nullptr},      // 9580: its round-3 k-tile loop (A/B timing, bit-equality test)
+    {9582, 1, &g_tn128, 3, nullptr},      // the pipelined loop without the pair launch of the fp32 step: one launch per GEMM
     {9540, 4, &g_tn_fm, 0, nullptr},
     {9560, 16, &g_g16_crop, 0, nullptr},
     {9600, 2, &g_g16, 0, nullptr},
@@ -390,10 +392,10 @@ extern "C" int st_ola_loss_partials(const st_dims* d) { return check_dims(d) != 
 extern "C" int st_norm_partials(const st_dims* d) { return check_dims(d) != ST_OK ? 0 : norm_partials(d); }
 // k-slices of the 128 x 128-tile weight-gradient GEMM (st_gemm_tn.h): as many as fill the CUs with one workgroup each, never slices
 // shorter than 64 reduction rows
-static int tn_split(int R, int N)
+static int tn_split(int R, int N, int ncus = 0)      // ncus > 0: a pure function of its arguments (st_wgrad_pair_plan)
 {
     const int tiles = (N / 128) * (N / 128);
-    int s = num_cus() / (tiles > 0 ? tiles : 1); if (s > 16) s = 16;
+    int s = (ncus > 0 ? ncus : num_cus()) / (tiles > 0 ? tiles : 1); if (s > 16) s = 16;
     const int cap = R / 64; if (s > cap) s = cap;
     return s < 1 ? 1 : s;
 }
@@ -792,6 +794,32 @@ static TNFrameMajor tn_frame_major(const stg::TNOperand& ta, const stg::TNOperan
 }
 // g_tn128 == 2: the round-3 k-tile loop (st_set_tuning(9580)); otherwise the pipelined one (st_gemm_tn.h, round 7)
 #define ST_TN128(...) do { if (g_tn128 == 2) ST_TRY((stg::launch_tn128<32, false>(__VA_ARGS__))); else ST_TRY((stg::launch_tn128<32, true>(__VA_ARGS__))); } while (0)
+// The two weight-gradient GEMMs as problems of the 128 x 128-tile kernel -- operands in the padded workspace layout, the live rows (frame-major where that applies,
+// with the per-tile-column row ranges), the k-slice count -- stated once for the per-GEMM launches, the pair launch and its plan query.  fits: the kernel applies.
+struct TNProblem { stg::TNOperand a, b; const float* zeros; stg::RowMap map; stg::FrameTrim trim; int R, ns; bool fits; };
+static TNProblem tn_problem(const st_dims* d, const stg::TNOperand& ta, const stg::TNOperand& tb, const stg::RowMap& live, size_t extentA, int Ls, int fm_bit, bool padded, int ncus)
+{
+    TNProblem p; p.zeros = tb.base; p.R = live.rows(d->B);
+    p.fits = use_tn128(d, padded) && stg::tn128_fits(ta, tb, tb.base, live, d->N, d->N, extentA, (size_t)d->B * (Ls + 2 * d->N));
+    p.ns = tn_split(p.R, d->N, ncus);
+    const TNFrameMajor fm = tn_frame_major(ta, tb, live, d->B, d->H, d->N, d->N, Ls, (g_tn_fm & fm_bit) != 0);
+    p.a = fm.a; p.b = fm.b; p.map = fm.map; p.trim = fm.trim;
+    return p;
+}
+// synthesis (A = the spectra, B = the padded d syn): taps of d syn's frames outside the crop are zeros, skipped per tile column
+static TNProblem synthesis_tn_problem(const st_dims* d, const float* AA, const float* dsyn, bool padded, int ncus = 0)
+{
+    const int KP = st_kp_of(d->F);
+    const stg::TNOperand ta{AA, (unsigned)(d->OT * KP), (unsigned)KP}, tb{dsyn, (unsigned)(d->y + 2 * d->N), (unsigned)d->H};
+    return tn_problem(d, ta, tb, synth_live(d), (size_t)d->B * d->OT * KP, d->y, 1, padded, ncus);
+}
+// analysis (A = d G, B = the padded x / 2): taps of the partly padded frames (Conv1d padding, cls_fe_dft.py:28-31) are zeros, skipped per tile column
+static TNProblem analysis_tn_problem(const st_dims* d, const float* dG, const float* sig, bool padded, int ncus = 0)
+{
+    const int KP = st_kp_of(d->F);
+    const stg::TNOperand ta{dG, (unsigned)(d->T * KP), (unsigned)KP}, tb{sig, (unsigned)(d->L + 2 * d->N), (unsigned)d->H};
+    return tn_problem(d, ta, tb, stg::live_frames(d->T, d->H, d->N, d->N, d->L), (size_t)d->B * d->T * KP, d->L, 2, padded, ncus);
+}
 static int wgrad_tn128(const st_dims* d, const stg::TNOperand& ta, const stg::TNOperand& tb, const float* zeros, const stg::RowMap& map, int R,
                        float* ws, int ns, stm::NyqJob* nyq, void* stream, const stg::FrameTrim* trim)
 {
@@ -813,11 +841,10 @@ static int synthesis_wgrad_impl(const st_dims* d, const float* AA, const float* 
     const int R = ms.rows(d->B);
     int ns = wgrad_split_tiles(R, KP, d->N);
     stm::NyqJob nyq{}; nyq.on = 0;
-    const stg::TNOperand ta{AA, (unsigned)(d->OT * KP), (unsigned)KP}, tb{dsyn, (unsigned)(d->y + 2 * d->N), (unsigned)d->H};
-    if (use_tn128(d, padded) && stg::tn128_fits(ta, tb, dsyn, ms, d->N, d->N, (size_t)d->B * d->OT * KP, (size_t)d->B * (d->y + 2 * d->N))) {
-        ns = tn_split(R, d->N);
-        const TNFrameMajor fm = tn_frame_major(ta, tb, ms, d->B, d->H, d->N, d->N, d->y, (g_tn_fm & 1) != 0);      // taps of d syn's frames outside the crop are zeros: skipped per tile column
-        ST_TRY(wgrad_tn128(d, fm.a, fm.b, dsyn, fm.map, R, ws, ns, &nyq, stream, &fm.trim));
+    const TNProblem tp = synthesis_tn_problem(d, AA, dsyn, padded);
+    if (tp.fits) {
+        ns = tp.ns;
+        ST_TRY(wgrad_tn128(d, tp.a, tp.b, tp.zeros, tp.map, R, ws, ns, &nyq, stream, &tp.trim));
     } else {
         stg::PlainTN al{AA, R, KP, KP, ms};
         stg::StoreC ep{ws, KP, d->N, d->N, (size_t)KP * d->N, stg::all_frames(1)};
@@ -1153,11 +1180,10 @@ static int analysis_wgrad_impl(const st_dims* d, const float* dG, const float* s
     }
     const int M = half < 0 ? KP : KP / 2, m0 = half > 0 ? KP / 2 : 0;
     stm::NyqJob nyq{}; nyq.on = 0;
-    const stg::TNOperand ta{dG, (unsigned)(d->T * KP), (unsigned)KP}, tb{sig, (unsigned)(d->L + 2 * d->N), (unsigned)d->H};
-    if (half < 0 && use_tn128(d, padded) && stg::tn128_fits(ta, tb, sig, ma, d->N, d->N, (size_t)d->B * d->T * KP, (size_t)d->B * (d->L + 2 * d->N))) {
-        ns = tn_split(R, d->N);
-        const TNFrameMajor fm = tn_frame_major(ta, tb, ma, d->B, d->H, d->N, d->N, d->L, (g_tn_fm & 2) != 0);      // taps of the partly padded frames (Conv1d padding, cls_fe_dft.py:28-31) are zeros: skipped per tile column
-        ST_TRY(wgrad_tn128(d, fm.a, fm.b, sig, fm.map, R, ws, ns, &nyq, stream, &fm.trim));
+    const TNProblem tp = analysis_tn_problem(d, dG, sig, padded);
+    if (half < 0 && tp.fits) {
+        ns = tp.ns;
+        ST_TRY(wgrad_tn128(d, tp.a, tp.b, tp.zeros, tp.map, R, ws, ns, &nyq, stream, &tp.trim));
     } else {
         stg::PlainTN al{dG + m0, R, KP, M, ma};
         stg::StoreC ep{ws + (size_t)m0 * d->N, M, d->N, d->N, (size_t)KP * d->N, stg::all_frames(1)};
@@ -1242,7 +1268,7 @@ struct WS {
     // dAA, frs: NOT every element is written per step (the pitch-padding columns [F, FP) of dAA's halves, the all-cropped tiles of frs): no consumer may read those -- the
     // contract is stated at st_workspace_bytes in the header; the Python engine zero-fills the buffer once when it allocates it
     float *re, *im, *mag, *phs, *mag_hat, *phs_hat, *AA, *dAA, *Sfold, *SfoldT, *frs, *y_hat, *dsyn, *dmag, *dphs, *dG, *xp;
-    float *wg, *wg2, *aews, *loss_p, *reg_p, *norm_a, *norm_s, *norm_e;      // wg2: the synthesis weight gradient's own slabs in the data-parallel step (synth_wgrad_ws_floats)
+    float *wg, *wg2, *aews, *loss_p, *reg_p, *norm_a, *norm_s, *norm_e;      // wg2: the synthesis weight gradient's own slabs in the data-parallel step and in the pair launch of the fp32 step (synth_wgrad_ws_floats)
     // bfloat16 planes of the operands that are written once per step (st_gemm_planes.h): [3][same layout as the fp32 tensor]
     unsigned short *pl_W, *pl_Sfold, *pl_SfoldT;      // k-chunk-major: [K / 16][rows][3][16]
     // 16-bit GEMM operands (st_gemm16.h), each written by its producer in the layout of its fp32 counterpart: padded x/2, the analysis
@@ -1712,8 +1738,60 @@ static int analysis_wgrad_half(Call& c, float* grads, int half, float* stage, in
     ST_LAUNCHED("analysis_wgrad_reduce");
     return ST_OK;
 }
+// Both weight-gradient GEMMs of the fp32 step in ONE launch (stg::gemm_tn128_pair_kernel), then ONE launch that sums both sets of slabs.  Nothing between the two
+// GEMMs of the per-GEMM schedule needs the synthesis weight gradient (its slabs are only summed, and the sum is first read by the optimizer), and its operands
+// (the spectra, the padded d syn) are still in place when d G is ready.  Analysis slabs in w.wg, synthesis slabs in w.wg2, each with its Nyquist partials behind them.
+// The pair applies to: fp32 operands, the fused autoencoder geometries, both GEMMs on the 128 x 128 kernel, g_tn128 == 1.  false from make: per-GEMM launches.
+struct WgradPair { TNProblem pa, ps; stg::TNLaunch la, ls; stg::TNPair pair; bool on; };
+static void wgrad_pair_make(WgradPair& q, const st_dims* d, const WS& w, int ncus = 0)
+{
+    const int KP = st_kp_of(d->F), N = d->N, mh = (N / 2) / 128;
+    q.on = false;
+    if (g_tn128 != 1 || w.g16 || gemm_ht(d->prec) != 0 || ae_is_wide(d)) return;
+    q.pa = analysis_tn_problem(d, w.dG, w.xp, true, ncus); q.ps = synthesis_tn_problem(d, w.AA, w.dsyn, true, ncus);
+    if (!q.pa.fits || !q.ps.fits) return;
+    const unsigned c0 = (unsigned)(d->F - 1), c1 = (unsigned)(KP / 2 + d->F - 1);
+    const size_t slab = (size_t)KP * N;
+    q.la = stg::tn128_job(32, q.pa.a, q.pa.b, q.pa.zeros, q.pa.map, q.pa.R, N, mh, (unsigned)(KP / 2), N, w.wg, N, slab, q.pa.ns, w.wg + (size_t)q.pa.ns * slab, c0, c1, nullptr, &q.pa.trim);
+    q.ls = stg::tn128_job(32, q.ps.a, q.ps.b, q.ps.zeros, q.ps.map, q.ps.R, N, mh, (unsigned)(KP / 2), N, w.wg2, N, slab, q.ps.ns, w.wg2 + (size_t)q.ps.ns * slab, c0, c1, nullptr, &q.ps.trim);
+    q.on = stg::tn128_pair_make(q.pair, q.la, q.ls, 32);
+}
+static int wgrad_pair(Call& c, const WgradPair& q, float* grads)
+{
+    const st_dims* d = c.d; const Layout& L = c.L; void* stream = c.stream;
+    ST_TRY(stg::launch_tn128_pair<32>(q.pair, q.la, q.ls, st_stream(stream)));
+    ST_LAUNCHED("wgrad_pair");
+    stm::WgradPairArgs a;
+    const stg::TNLaunch* l[2] = {&q.la, &q.ls};
+    for (int i = 0; i < 2; ++i) {
+        a.ws[i] = l[i]->out; a.nz[i] = l[i]->j.nsplit; a.gRe[i] = grads + L.offs[2 * i]; a.gIm[i] = grads + L.offs[2 * i + 1]; a.norm[i] = i ? c.w.norm_s : c.w.norm_a;
+        a.nyq[i].part = l[i]->j.nyq_out; a.nyq[i].P = l[i]->j.nyq_P; a.nyq[i].on = 1;
+    }
+    a.N = d->N; a.F = d->F; a.KP = L.KP;
+    hipLaunchKernelGGL(stm::wgrad_pair_reduce_kernel, dim3(2 * norm_partials(d)), dim3(256), 0, st_stream(stream), a);
+    ST_LAUNCHED("wgrad_pair_reduce");
+    return ST_OK;
+}
+// Host-side view of the pair launch (no device work; the CPU suite checks it): ten ints per workgroup slot, see stg::tn128_pair_describe -- (tile row, tile column,
+// k-slice, k_begin, k_end) of the analysis entry, then of the synthesis entry, -1 five times where the slot has none; k ranges in reduction rows of the
+// frame-major order, k-tiles of 32.  ncus <= 0: the current device's CU count.  Returns the slot count, 0 where the step does not take the pair launch at these
+// dims (and tuning state), < 0 on bad arguments.
+extern "C" int st_wgrad_pair_plan(const st_dims* d, int ncus, int* out, int cap)
+{
+    Layout L;
+    if (make_layout(d, &L) != ST_OK || cap < 0 || (cap > 0 && !out)) return -1;
+    WS w; carve(d, L, reinterpret_cast<void*>(sizeof(float)), &w);       // a non-null dummy base (as st_workspace_offsets): only pointer differences are used
+    WgradPair q; wgrad_pair_make(q, d, w, ncus);
+    if (!q.on) return 0;
+    return stg::tn128_pair_describe(q.pair, d->N / 128, d->N / 128, 32, out, cap);
+}
 static int backward_impl(Call& c, const float* params, float* grads, const float* g_mag_hat, const float* g_mag, float reg_coef, float* kg = nullptr)
 {
+    WgradPair q; wgrad_pair_make(q, c.d, c.w);
+    if (q.on) {      // the data gradient alone, the autoencoders with post_ae_kernel free of slab blocks, then the pair
+        ST_TRY(backward_p1(c, params, grads, g_mag_hat, g_mag, reg_coef, kg, ST_STAGE_EVERY & ~ST_STAGE_SYN_WGRAD));
+        return wgrad_pair(c, q, grads);
+    }
     ST_TRY(backward_p1(c, params, grads, g_mag_hat, g_mag, reg_coef, kg));
     return backward_p2(c, grads);
 }

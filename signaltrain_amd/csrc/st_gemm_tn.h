@@ -67,6 +67,20 @@ static inline FrameTrim frame_trim(const RowMap& live, int B, int H, int Ntaps, 
     return f;
 }
 
+// The reduction rows [k_begin, k_end) of k-slice z of tile column tx: ONE rule for the kernels and for the host (the pair launch's plan, tn128_pair_make,
+// ranks tile columns by it, and st_wgrad_pair_plan reports it).  k_end <= k_begin: an empty slice (its tile is stored as zeros).
+__host__ __device__ static inline void tn128_krange(const TNJob& j, const int tx, const int z, const int ksplit, const int bkt, int& k_begin, int& k_end)
+{
+    k_begin = z * ksplit;
+    k_end = (k_begin + ksplit < j.K) ? k_begin + ksplit : j.K;
+    if (j.trim) {                                        // the rows that carry anything for this tile column, divided among the k-slices (workgroup-uniform)
+        const int lo = (int)j.fa[tx] * j.fB, hi = (int)j.fb[tx] * j.fB;
+        const int per = ((hi - lo + j.nsplit - 1) / j.nsplit + bkt - 1) / bkt * bkt;
+        k_begin = lo + z * per;
+        k_end = (k_begin + per < hi) ? k_begin + per : hi;      // a last k-tile may run past hi: those rows are structural zeros of B for this tile column (or past K: masked)
+    }
+}
+
 // One extra z-slice of workgroups (blockIdx.z == nsplit) forms the two Nyquist rows C[c][n] = sum_k A[k][c] * B[k][n], c in {nyq_c0, nyq_c1},
 // as nyq_P partial sums over groups of windows: out[p][0 | 1][n].  Light vector work (K / nyq_P rows of float4 FMAs per thread) that runs
 // beside the MFMA workgroups as a second resident workgroup of its CU; the slab-reduce kernel adds the nyq_P partials in a fixed order.
@@ -100,6 +114,174 @@ __device__ __forceinline__ void nyq_partial(const TNJob& j, const int p)
     }
 }
 
+// A thread's view of one 128 x 128 tile job: where its load passes read, the staging registers, the two LDS stages, and the round-7 pipelined k-tile loop.
+// A struct so that the two-job kernel (gemm_tn128_pair_kernel) runs the SAME loop twice on the same LDS, staging registers and accumulators: job() points
+// the addressing at a job, prologue() requests its first two k-tiles, loop() runs the range.  UNI: see gemm_tn128_kernel.
+template <int BKT, bool UNI> struct TNTile {
+    static constexpr int TS = BKT * 128;                // floats per operand tile
+    static constexpr int NP = BKT / 8;                  // load passes: 256 threads = 32 float4 columns x 8 k rows
+    static constexpr int KS = BKT / 2;                  // MFMA k-steps per tile
+    static constexpr int PAIRS = KS / 2;
+    static_assert(PAIRS % 2 == 0 && NP + 1 <= PAIRS - 1, "fragment buffers alternate by pair; stores and loads sit before the barrier");
+    float* As; float* Bs;                               // As[2][BKT][128] | Bs[2][BKT][128]
+    int c4, kr, a_off, b_off;
+    const char* base; unsigned la, lb, lz, sa1, sa2, sb1, sb2, magic; int Tv, t_lo, K;
+    unsigned ua[UNI ? NP : 1], ub[UNI ? NP : 1];
+    int k_begin, ntiles, k_last;
+    float4 ra[NP], rb[NP];
+    float2 fa[2][2], fb[2][2];
+
+    __device__ __forceinline__ void init(float* lds)
+    {
+        const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave >> 1, wn = wave & 1, h = lane >> 5, l31 = lane & 31;
+        As = lds; Bs = lds + 2 * TS;
+        c4 = tid & 31; kr = tid >> 5;
+        a_off = h * 128 + wm * 64 + 2 * l31;            // k-step s reads row 2 s + h
+        b_off = h * 128 + wn * 64 + 2 * l31;
+    }
+    // BYTE offsets from j.base; every product below has 24-bit factors (host-checked): full-rate v_mad_u32_u24 instead of the
+    // quarter-rate 32-bit multiplies (16 of them per k-tile were 9 % of the loop)
+    __device__ __forceinline__ void job(const TNJob& j, const unsigned rowA, const unsigned colB)
+    {
+        base = reinterpret_cast<const char*>(j.base);
+        la = 4u * (j.a0 + rowA + 4u * (unsigned)c4); lb = 4u * (j.b0 + colB + 4u * (unsigned)c4); lz = 4u * (j.zero + 4u * (unsigned)c4);
+        sa1 = 4u * j.SA1; sa2 = 4u * j.SA2; sb1 = 4u * j.SB1; sb2 = 4u * j.SB2;
+        magic = j.magic; Tv = j.Tv; t_lo = j.t_lo; K = j.K;
+        if constexpr (UNI) {
+#pragma unroll
+            for (int p = 0; p < NP; ++p) { ua[p] = la + (unsigned)(kr + 8 * p) * sa2; ub[p] = lb + (unsigned)(kr + 8 * p) * sb2; }
+        }
+    }
+    __device__ __forceinline__ float4 ld(const unsigned byte_off) const { return *reinterpret_cast<const float4*>(base + byte_off); }
+    __device__ __forceinline__ void gl(const int kt, const int p)      // load pass p of the tile at kt
+    {
+        if constexpr (UNI) {
+            // kt is workgroup-uniform and a multiple of BKT, which divides Tv: rows kt .. kt + BKT - 1 share b, their t is t0 + row (scalar ALU only)
+            const unsigned b = __umulhi((unsigned)kt, magic), t0 = (unsigned)t_lo + (unsigned)kt - b * (unsigned)Tv;
+            ra[p] = ld(b * sa1 + t0 * sa2 + ua[p]);
+            rb[p] = ld(b * sb1 + t0 * sb2 + ub[p]);
+        } else {
+            const int k = kt + kr + 8 * p;
+            const unsigned kc = (unsigned)(k < K ? k : K - 1);
+            const unsigned b = __umulhi(kc, magic);                                     // Tv >= 2 (host-checked): magic != 0
+            const unsigned t = (unsigned)t_lo + kc - __umul24(b, (unsigned)Tv);
+            const unsigned oa = __umul24(b, sa1) + __umul24(t, sa2) + la;
+            const unsigned ob = __umul24(b, sb1) + __umul24(t, sb2) + lb;
+            const unsigned live = (unsigned)((k - K) >> 31);         // all ones while k < K; a bit select (v_bfi), not a ?: the compiler turns into a branch
+            ra[p] = ld((oa & live) | (lz & ~live));                  // rows past the end of the reduction: the block of zeros (B's row is clamped: finite x 0)
+            rb[p] = ld(ob);
+        }
+    }
+    __device__ __forceinline__ void gload(const int kt)
+    {
+#pragma unroll
+        for (int p = 0; p < NP; ++p) gl(kt, p);
+    }
+    __device__ __forceinline__ void lstore_pass(const int buf, const int p)
+    {
+        float* as = As + buf * TS + kr * 128 + 4 * c4;
+        float* bs = Bs + buf * TS + kr * 128 + 4 * c4;
+        *reinterpret_cast<float4*>(as + p * 8 * 128) = ra[p];
+        *reinterpret_cast<float4*>(bs + p * 8 * 128) = rb[p];
+    }
+    __device__ __forceinline__ void lstore(const int buf)
+    {
+#pragma unroll
+        for (int p = 0; p < NP; ++p) lstore_pass(buf, p);
+    }
+    __device__ __forceinline__ void frag(const int stage, const int pr, const int buf)
+    {
+        const float* as = As + stage * TS + a_off;
+        const float* bs = Bs + stage * TS + b_off;
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            fa[buf][u] = *reinterpret_cast<const float2*>(as + (2 * pr + u) * 256);
+            fb[buf][u] = *reinterpret_cast<const float2*>(bs + (2 * pr + u) * 256);
+        }
+    }
+    __device__ __forceinline__ void mfma8(f32x16 (&acc)[2][2], const int buf) const
+    {
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const float2 a = fa[buf][u], b = fb[buf][u];
+            acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, b.x, acc[0][0], 0, 0, 0);
+            acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, b.y, acc[0][1], 0, 0, 0);
+            acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, b.x, acc[1][0], 0, 0, 0);
+            acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, b.y, acc[1][1], 0, 0, 0);
+        }
+    }
+    // Round 7.  At one wave per SIMD nothing else is resident to fill a hole, and the round-3 loop has two per k-tile: it ends with lstore / barrier
+    // and begins with fragment reads of the tile that barrier released (barrier skew, then an LDS round trip with four waves asking at once), and its
+    // eight ds_write_b128 issue after the last MFMA.  Here, with the same two LDS stages:
+    //   invariant at the top of tile i:  tile i complete in stage i & 1 AND its first fragment pair in registers; tile i + 1 in the staging registers
+    //   pairs 0 .. last - 1 (all but 8 MFMAs):  the stores of tile i + 1 into the other stage and the global loads of tile i + 2 among the first MFMAs,
+    //                                      the remaining fragment pairs of tile i one pair ahead as before;
+    //   ONE barrier, before the last pair's 8 MFMAs: every fragment of tile i has been read by then (its stage is next written in tile i + 1, behind
+    //   this barrier), the stores of tile i + 1 are complete, and the MFMAs that follow the barrier need nothing from it;
+    //   under those 8 MFMAs (512 cycles) the first fragment pair of tile i + 1 is read.
+    // No third stage is needed: a stage is written in the tile after its last read, and that read lies before the barrier in between.  The LDS request
+    // stays at 64 KB, so the Nyquist side workgroups still fit beside a GEMM workgroup.  The MFMAs per accumulator run in the same order: same bits.
+    // Tails: a k range of n tiles loads tiles min(i, n - 1) -- the last one is fetched (and stored, and its first fragments read) again instead of
+    // branching around the prefetch; n = 1 and n = 2 are the same code, an empty range skips the loop.
+    // Placement is by program order in chunks of one fragment pair (8 MFMAs) closed by a scheduling barrier: chunk p < NP holds the two stores of
+    // load pass p, chunk p + 1 the two loads that refill those registers (consumed 7 chunks = 56 MFMAs later).
+    //
+    // prologue(): tile 0 into stage 0 and tile 1 into the staging registers; no barrier yet (loop() opens with it).  After the last barrier of a loop only
+    // the re-fetched tile's first fragments are read, and nobody uses them: the next job's prologue may overwrite stage 0 without another barrier.
+    __device__ __forceinline__ void prologue(const int kb, const int ke)
+    {
+        k_begin = kb; ntiles = (ke - kb + BKT - 1) / BKT;
+        if (ntiles > 0) {
+            k_last = k_begin + (ntiles - 1) * BKT;
+            gload(k_begin);
+            lstore(0);
+            gload(ntiles > 1 ? k_begin + BKT : k_begin);
+        }
+    }
+    __device__ __forceinline__ void tile(f32x16 (&acc)[2][2], const int i, int& cur)
+    {
+        const int k2 = k_begin + (i + 2) * BKT, kn = k2 < k_last ? k2 : k_last;      // tile i + 2
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int pr = 0; pr < PAIRS - 1; ++pr) {
+            frag(cur, pr + 1, (pr + 1) & 1);                // one pair ahead, double-buffered in registers
+            if (pr < NP) lstore_pass(cur ^ 1, pr);          // tile i + 1 (the staging registers were loaded one tile ago)
+            if (pr >= 1 && pr <= NP) gl(kn, pr - 1);
+            mfma8(acc, pr & 1);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        __syncthreads();
+        frag(cur ^ 1, 0, 0);
+        mfma8(acc, 1);
+        __builtin_amdgcn_sched_barrier(0);
+        cur ^= 1;
+    }
+    // PEEL: the first k-tile as code of its own.  The wait counts of the loop body are those of its steady state (eight loads in flight); behind a prologue
+    // that was followed by the previous job's 32 tile stores (gemm_tn128_pair_kernel) they would make the first MFMAs wait for those stores as well --
+    // vector memory operations retire in order.  The peeled tile counts the stores in; every later wait is for loads issued after them.
+    template <bool PEEL> __device__ __forceinline__ void loop(f32x16 (&acc)[2][2])
+    {
+        if (ntiles > 0) {
+            __syncthreads();
+            frag(0, 0, 0);
+            int cur = 0, i = 0;
+            if constexpr (PEEL) { tile(acc, 0, cur); i = 1; }
+            for (; i < ntiles; ++i) tile(acc, i, cur);
+        }
+    }
+};
+// epilogue: acc[mi][nj][i] = C[tile row wm*64 + 2*d_row(i) + mi][tile col wn*64 + 2*l31 + nj]; o = the wave's first element of the lane's column pair
+__device__ __forceinline__ void tn128_store(const f32x16 (&acc)[2][2], float* __restrict__ o, const int ldo, const int lane)
+{
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+        const int r = 2 * d_row(i, lane);
+#pragma unroll
+        for (int mi = 0; mi < 2; ++mi)
+            *reinterpret_cast<float2*>(o + (size_t)(r + mi) * ldo) = make_float2(acc[mi][0][i], acc[mi][1][i]);
+    }
+}
+
 // PIPE (round 7): the k-tile loop with the barrier and the first fragment reads off the wave's critical path (see the loop); false = the round-3 loop,
 // kept for A/B timing and the bit-equality test (st_set_tuning(9580)).  UNI (PIPE only, chosen on the host, see tn128_uniform): every k-tile lies inside ONE
 // outer index of the row map (frame-major order, inner count a multiple of BKT, k ranges that start on such a multiple), so (b, t) of a tile is wave-uniform.
@@ -109,12 +291,8 @@ template <int BKT, bool PIPE = false, bool UNI = false>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2)))
 gemm_tn128_kernel(const TNJob j, float* __restrict__ out, const int ldo, const size_t slab, const int ksplit)
 {
-    constexpr int TS = BKT * 128;                       // floats per operand tile
-    constexpr int NP = BKT / 8;                         // load passes: 256 threads = 32 float4 columns x 8 k rows
-    constexpr int KS = BKT / 2;                         // MFMA k-steps per tile
+    constexpr int TS = BKT * 128, NP = BKT / 8, KS = BKT / 2;
     extern __shared__ __attribute__((aligned(16))) float tn_lds[];       // As[2][BKT][128] | Bs[2][BKT][128]
-    float* const As = tn_lds;
-    float* const Bs = tn_lds + 2 * TS;
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave >> 1, wn = wave & 1;
     // the Nyquist workgroups are the PHYSICAL last z-slice: dispatched after the GEMM workgroups, round-robin over the XCDs, and outside
@@ -123,48 +301,9 @@ gemm_tn128_kernel(const TNJob j, float* __restrict__ out, const int ldo, const s
     int tbx, tby, tbz; xcd_tile(tbx, tby, tbz, j.nsplit);
     const unsigned rowA = (unsigned)(tby % j.mh) * 128u + (unsigned)(tby / j.mh) * j.mstride;
     const unsigned colB = (unsigned)tbx * 128u;
-    int k_begin = tbz * ksplit;
-    int k_end = (k_begin + ksplit < j.K) ? k_begin + ksplit : j.K;
-    if (j.trim) {                                        // the rows that carry anything for this tile column, divided among the k-slices (workgroup-uniform)
-        const int lo = (int)j.fa[tbx] * j.fB, hi = (int)j.fb[tbx] * j.fB;
-        const int per = ((hi - lo + j.nsplit - 1) / j.nsplit + BKT - 1) / BKT * BKT;
-        k_begin = lo + tbz * per;
-        k_end = (k_begin + per < hi) ? k_begin + per : hi;      // a last k-tile may run past hi: those rows are structural zeros of B for this tile column (or past K: masked)
-    }
+    int k_begin, k_end; tn128_krange(j, tbx, tbz, ksplit, BKT, k_begin, k_end);
 
-    const int c4 = tid & 31, kr = tid >> 5;
-    // BYTE offsets from j.base; every product below has 24-bit factors (host-checked): full-rate v_mad_u32_u24 instead of the
-    // quarter-rate 32-bit multiplies (16 of them per k-tile were 9 % of the loop)
-    const unsigned la = 4u * (j.a0 + rowA + 4u * (unsigned)c4), lb = 4u * (j.b0 + colB + 4u * (unsigned)c4), lz = 4u * (j.zero + 4u * (unsigned)c4);
-    const unsigned sa1 = 4u * j.SA1, sa2 = 4u * j.SA2, sb1 = 4u * j.SB1, sb2 = 4u * j.SB2;
-    float4 ra[NP], rb[NP];
-    auto ld = [&](const unsigned byte_off) { return *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(j.base) + byte_off); };
-    auto gload_pass = [&](const int kt, const int p) {
-        const int k = kt + kr + 8 * p;
-        const unsigned kc = (unsigned)(k < j.K ? k : j.K - 1);
-        const unsigned b = __umulhi(kc, j.magic);                                   // Tv >= 2 (host-checked): magic != 0
-        const unsigned t = (unsigned)j.t_lo + kc - __umul24(b, (unsigned)j.Tv);
-        const unsigned oa = __umul24(b, sa1) + __umul24(t, sa2) + la;
-        const unsigned ob = __umul24(b, sb1) + __umul24(t, sb2) + lb;
-        const unsigned live = (unsigned)((k - j.K) >> 31);       // all ones while k < K; a bit select (v_bfi), not a ?: the compiler turns into a branch
-        ra[p] = ld((oa & live) | (lz & ~live));                  // rows past the end of the reduction: the block of zeros (B's row is clamped: finite x 0)
-        rb[p] = ld(ob);
-    };
-    auto gload = [&](const int kt) {
-#pragma unroll
-        for (int p = 0; p < NP; ++p) gload_pass(kt, p);
-    };
-    auto lstore_pass = [&](const int buf, const int p) {
-        float* as = As + buf * TS + kr * 128 + 4 * c4;
-        float* bs = Bs + buf * TS + kr * 128 + 4 * c4;
-        *reinterpret_cast<float4*>(as + p * 8 * 128) = ra[p];
-        *reinterpret_cast<float4*>(bs + p * 8 * 128) = rb[p];
-    };
-    auto lstore = [&](const int buf) {
-#pragma unroll
-        for (int p = 0; p < NP; ++p) lstore_pass(buf, p);
-    };
-
+    TNTile<BKT, UNI> t; t.init(tn_lds); t.job(j, rowA, colB);
     f32x16 acc[2][2];
 #pragma unroll
     for (int mi = 0; mi < 2; ++mi)
@@ -173,103 +312,24 @@ gemm_tn128_kernel(const TNJob j, float* __restrict__ out, const int ldo, const s
 #pragma unroll
             for (int i = 0; i < 16; ++i) acc[mi][nj][i] = 0.f;
 
-    const int h = lane >> 5, l31 = lane & 31;
+    const int l31 = lane & 31;
     if constexpr (PIPE) {
-        // Round 7.  At one wave per SIMD nothing else is resident to fill a hole, and the round-3 loop has two per k-tile: it ends with lstore / barrier
-        // and begins with fragment reads of the tile that barrier released (barrier skew, then an LDS round trip with four waves asking at once), and its
-        // eight ds_write_b128 issue after the last MFMA.  Here, with the same two LDS stages:
-        //   invariant at the top of tile i:  tile i complete in stage i & 1 AND its first fragment pair in registers; tile i + 1 in the staging registers
-        //   pairs 0 .. last - 1 (all but 8 MFMAs):  the stores of tile i + 1 into the other stage and the global loads of tile i + 2 among the first MFMAs,
-        //                                      the remaining fragment pairs of tile i one pair ahead as before;
-        //   ONE barrier, before the last pair's 8 MFMAs: every fragment of tile i has been read by then (its stage is next written in tile i + 1, behind
-        //   this barrier), the stores of tile i + 1 are complete, and the MFMAs that follow the barrier need nothing from it;
-        //   under those 8 MFMAs (512 cycles) the first fragment pair of tile i + 1 is read.
-        // No third stage is needed: a stage is written in the tile after its last read, and that read lies before the barrier in between.  The LDS request
-        // stays at 64 KB, so the Nyquist side workgroups still fit beside a GEMM workgroup.  The MFMAs per accumulator run in the same order: same bits.
-        // Tails: a k range of n tiles loads tiles min(i, n - 1) -- the last one is fetched (and stored, and its first fragments read) again instead of
-        // branching around the prefetch; n = 1 and n = 2 are the same code, an empty range skips the loop.
-        // Placement is by program order in chunks of one fragment pair (8 MFMAs) closed by a scheduling barrier: chunk p < NP holds the two stores of
-        // load pass p, chunk p + 1 the two loads that refill those registers (consumed 7 chunks = 56 MFMAs later).
-        constexpr int PAIRS = KS / 2;
-        static_assert(PAIRS % 2 == 0 && NP + 1 <= PAIRS - 1, "fragment buffers alternate by pair; stores and loads sit before the barrier");
-        const int ntiles = (k_end - k_begin + BKT - 1) / BKT;
-        if (ntiles > 0) {
-            const int k_last = k_begin + (ntiles - 1) * BKT;
-            unsigned ua[UNI ? NP : 1], ub[UNI ? NP : 1];
-            if constexpr (UNI) {
-#pragma unroll
-                for (int p = 0; p < NP; ++p) { ua[p] = la + (unsigned)(kr + 8 * p) * sa2; ub[p] = lb + (unsigned)(kr + 8 * p) * sb2; }
-            }
-            auto gl = [&](const int kt, const int p) {              // load pass p of the tile at kt
-                if constexpr (UNI) {
-                    // kt is workgroup-uniform and a multiple of BKT, which divides Tv: rows kt .. kt + BKT - 1 share b, their t is t0 + row (scalar ALU only)
-                    const unsigned b = __umulhi((unsigned)kt, j.magic), t0 = (unsigned)j.t_lo + (unsigned)kt - b * (unsigned)j.Tv;
-                    ra[p] = ld(b * sa1 + t0 * sa2 + ua[p]);
-                    rb[p] = ld(b * sb1 + t0 * sb2 + ub[p]);
-                } else gload_pass(kt, p);
-            };
-            const int a_off = h * 128 + wm * 64 + 2 * l31;          // k-step s reads row 2 s + h
-            const int b_off = h * 128 + wn * 64 + 2 * l31;
-            float2 fa[2][2], fb[2][2];
-            auto frag = [&](const int stage, const int pr, const int buf) {
-                const float* as = As + stage * TS + a_off;
-                const float* bs = Bs + stage * TS + b_off;
-#pragma unroll
-                for (int u = 0; u < 2; ++u) {
-                    fa[buf][u] = *reinterpret_cast<const float2*>(as + (2 * pr + u) * 256);
-                    fb[buf][u] = *reinterpret_cast<const float2*>(bs + (2 * pr + u) * 256);
-                }
-            };
-            auto mfma8 = [&](const int buf) {
-#pragma unroll
-                for (int u = 0; u < 2; ++u) {
-                    const float2 a = fa[buf][u], b = fb[buf][u];
-                    acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, b.x, acc[0][0], 0, 0, 0);
-                    acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, b.y, acc[0][1], 0, 0, 0);
-                    acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, b.x, acc[1][0], 0, 0, 0);
-                    acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, b.y, acc[1][1], 0, 0, 0);
-                }
-            };
-#pragma unroll
-            for (int p = 0; p < NP; ++p) gl(k_begin, p);
-            lstore(0);
-#pragma unroll
-            for (int p = 0; p < NP; ++p) gl(ntiles > 1 ? k_begin + BKT : k_begin, p);
-            __syncthreads();
-            frag(0, 0, 0);
-            int cur = 0;
-            for (int i = 0; i < ntiles; ++i) {
-                const int k2 = k_begin + (i + 2) * BKT, kn = k2 < k_last ? k2 : k_last;      // tile i + 2
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int pr = 0; pr < PAIRS - 1; ++pr) {
-                    frag(cur, pr + 1, (pr + 1) & 1);                // one pair ahead, double-buffered in registers
-                    if (pr < NP) lstore_pass(cur ^ 1, pr);          // tile i + 1 (the staging registers were loaded one tile ago)
-                    if (pr >= 1 && pr <= NP) gl(kn, pr - 1);
-                    mfma8(pr & 1);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-                __syncthreads();
-                frag(cur ^ 1, 0, 0);
-                mfma8(1);
-                __builtin_amdgcn_sched_barrier(0);
-                cur ^= 1;
-            }
-        }
+        t.prologue(k_begin, k_end);
+        t.template loop<false>(acc);
     } else if (k_begin < k_end) {
-        gload(k_begin);
-        lstore(0);
+        float* const As = t.As; float* const Bs = t.Bs;
+        t.gload(k_begin);
+        t.lstore(0);
         __syncthreads();
         int cur = 0;
-        const int a_off = h * 128 + wm * 64 + 2 * l31;          // k-step s reads row 2 s + h
-        const int b_off = h * 128 + wn * 64 + 2 * l31;
+        const int a_off = t.a_off, b_off = t.b_off;             // k-step s reads row 2 s + h
         float2 abl_f[4];                                        // ST_G128_ABLATE bit 1: stand-ins for the fragments, read once
 #pragma unroll
         for (int u = 0; u < 4; ++u) abl_f[u] = (ST_G128_ABLATE & 2) ? *reinterpret_cast<const float2*>(As + a_off + u * 256) : make_float2(0.f, 0.f);
         for (int kt = k_begin; kt < k_end; kt += BKT) {
             // one basic block per k-tile (the last iteration re-loads its own tile instead of branching around the prefetch)
             const bool more = kt + BKT < k_end;
-            if (!(ST_G128_ABLATE & 8)) gload(more ? kt + BKT : kt);
+            if (!(ST_G128_ABLATE & 8)) t.gload(more ? kt + BKT : kt);
             __builtin_amdgcn_sched_barrier(0);
             const float* as = As + cur * TS + a_off;
             const float* bs = Bs + cur * TS + b_off;
@@ -305,23 +365,89 @@ gemm_tn128_kernel(const TNJob j, float* __restrict__ out, const int ldo, const s
                 __builtin_amdgcn_sched_group_barrier(0x008, 8, 0);
             }
             __builtin_amdgcn_sched_barrier(0);
-            if (!(ST_G128_ABLATE & 4)) lstore(cur ^ 1);
+            if (!(ST_G128_ABLATE & 4)) t.lstore(cur ^ 1);
             else {
 #pragma unroll
-                for (int p = 0; p < NP; ++p) { asm volatile("" :: "v"(ra[p].x), "v"(ra[p].y), "v"(ra[p].z), "v"(ra[p].w)); asm volatile("" :: "v"(rb[p].x), "v"(rb[p].y), "v"(rb[p].z), "v"(rb[p].w)); }
+                for (int p = 0; p < NP; ++p) { asm volatile("" :: "v"(t.ra[p].x), "v"(t.ra[p].y), "v"(t.ra[p].z), "v"(t.ra[p].w)); asm volatile("" :: "v"(t.rb[p].x), "v"(t.rb[p].y), "v"(t.rb[p].z), "v"(t.rb[p].w)); }
             }
             if (!(ST_G128_ABLATE & 1)) __syncthreads();
             cur ^= 1;
         }
     }
-    // epilogue: acc[mi][nj][i] = C[tile row wm*64 + 2*d_row(i) + mi][tile col wn*64 + 2*l31 + nj]
-    float* o = out + (size_t)tbz * slab + (size_t)(rowA + wm * 64) * ldo + colB + wn * 64 + 2 * l31;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-        const int r = 2 * d_row(i, lane);
+    tn128_store(acc, out + (size_t)tbz * slab + (size_t)(rowA + wm * 64) * ldo + colB + wn * 64 + 2 * l31, ldo, lane);
+}
+
+// ---- two jobs in ONE launch: both weight-gradient GEMMs of the fp32 step (same tile grid, independent of each other).  As two launches each pays its ramp,
+// the first two k-tiles' load latency and its end-of-launch store burst with the whole chip waiting, and each ends when ITS longest slice ends.  Here every
+// workgroup slot (sx, sy, sz) of the grid runs slice sz of tile (sy, sx) of job 0, then slice sz of tile (sy, perm[sx]) of job 1: the host pairs the tile
+// columns with the most k-tiles in job 0 with those with the fewest in job 1 (tn128_pair_make), so the longest slot is shorter than the two longest slices
+// together (54 against 44 + 12 k-tiles at the default geometry, B = 256).  A whole column is permuted, so the operand tiles an XCD shares stay together.
+// Slices a job does not have (different slice counts at small batches) leave the slot with one entry.  Same LDS, accumulators and loop: see TNTile.
+struct TNPair {
+    TNJob j[2]; float* out[2]; int ldo[2]; size_t slab[2]; int ksplit[2];
+    int nz;                        // GEMM z-slices of the grid = max of the two slice counts; z = nz / nz + 1: the Nyquist workgroups of job 0 / 1
+    unsigned char perm[64];        // tile column of job 1 in the slots of tile column sx
+};
+// Entry of `job` in slot (sx, ., sz): false = none.  The rule of the kernel AND of the host-side plan (st_wgrad_pair_plan)
+__host__ __device__ static inline bool tn128_pair_entry(const TNPair& p, const int job, const int sx, const int sz, const int bkt, int& tx, int& k_begin, int& k_end)
+{
+    if (sz >= p.j[job].nsplit) return false;
+    tx = job ? (int)p.perm[sx] : sx;
+    tn128_krange(p.j[job], tx, sz, p.ksplit[job], bkt, k_begin, k_end);
+    return true;
+}
+template <int BKT, bool UNI>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2)))
+gemm_tn128_pair_kernel(const TNPair p)
+{
+    extern __shared__ __attribute__((aligned(16))) float tn_pair_lds[];       // As[2][BKT][128] | Bs[2][BKT][128], one set for both jobs
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave >> 1, wn = wave & 1, l31 = lane & 31;
+    if ((int)blockIdx.z >= p.nz) {                      // workgroup-uniform: the side workgroups, as in gemm_tn128_kernel -- each job's partials behind its own slabs
+        const int part = (int)(blockIdx.y * gridDim.x + blockIdx.x);
+        if ((int)blockIdx.z == p.nz) nyq_partial(p.j[0], part); else nyq_partial(p.j[1], part);
+        return;
+    }
+    int sx, sy, sz; xcd_tile(sx, sy, sz, p.nz);
+    int tx0 = 0, tx1 = 0, kb0 = 0, ke0 = 0, kb1 = 0, ke1 = 0;
+    const bool on0 = tn128_pair_entry(p, 0, sx, sz, BKT, tx0, kb0, ke0), on1 = tn128_pair_entry(p, 1, sx, sz, BKT, tx1, kb1, ke1);
+
+    TNTile<BKT, UNI> t; t.init(tn_pair_lds);
+    f32x16 acc[2][2];
+    auto clear = [&]() {
 #pragma unroll
         for (int mi = 0; mi < 2; ++mi)
-            *reinterpret_cast<float2*>(o + (size_t)(r + mi) * ldo) = make_float2(acc[mi][0][i], acc[mi][1][i]);
+#pragma unroll
+            for (int nj = 0; nj < 2; ++nj)
+#pragma unroll
+                for (int i = 0; i < 16; ++i) acc[mi][nj][i] = 0.f;
+    };
+    auto row_of = [&](const TNJob& j) { return (unsigned)(sy % j.mh) * 128u + (unsigned)(sy / j.mh) * j.mstride; };
+    auto tile_out = [&](const int job, const unsigned rowA, const unsigned colB) {
+        return p.out[job] + (size_t)sz * p.slab[job] + (size_t)(rowA + wm * 64) * p.ldo[job] + colB + wn * 64 + 2 * l31;
+    };
+    clear();
+    if (on0) {
+        t.job(p.j[0], row_of(p.j[0]), (unsigned)tx0 * 128u);
+        t.prologue(kb0, ke0);
+        t.template loop<false>(acc);
+    }
+    // the second job's first two k-tiles are requested BEFORE the first job's tile is stored: loads and stores retire in order, so a load behind the
+    // 32 stores would hold the first MFMAs until the stores had landed (and see TNTile::loop PEEL for the wait counts of the first k-tile)
+    if (on1) {
+        t.job(p.j[1], row_of(p.j[1]), (unsigned)tx1 * 128u);
+        t.prologue(kb1, ke1);
+    }
+    // (two copies of the second loop rather than one behind two ifs: where the stores are conditional the compiler must wait as if there were none)
+    if (on0) {
+        tn128_store(acc, tile_out(0, row_of(p.j[0]), (unsigned)tx0 * 128u), p.ldo[0], lane);
+        clear();
+        if (on1) {
+            t.template loop<true>(acc);
+            tn128_store(acc, tile_out(1, row_of(p.j[1]), (unsigned)tx1 * 128u), p.ldo[1], lane);
+        }
+    } else if (on1) {
+        t.template loop<false>(acc);
+        tn128_store(acc, tile_out(1, row_of(p.j[1]), (unsigned)tx1 * 128u), p.ldo[1], lane);
     }
 }
 
@@ -345,30 +471,96 @@ static inline bool tn128_uniform(const RowMap& map, int K, int bkt, const FrameT
     if (map.Tv % bkt || K % bkt) return false;
     return !(trim && trim->on) || trim->B % bkt == 0;
 }
-template <int BKT, bool PIPE = false>
-static inline int launch_tn128(const TNOperand& A, const TNOperand& B, const float* zeros, const RowMap& map, int K,
-                               int M, int mh, unsigned mstride, int Nc, float* out, int ldo, size_t slab, int nsplit, hipStream_t s,
-                               float* nyq_out = nullptr, unsigned nyq_c0 = 0, unsigned nyq_c1 = 0, int* nyq_P = nullptr, const FrameTrim* trim = nullptr)
+// The kernel's view of one launch: the job, its slab output and the k rows per slice of the untrimmed rule
+struct TNLaunch { TNJob j; float* out; int ldo; size_t slab; int ksplit, M, Nc; bool nyq, uniform; };
+static inline TNLaunch tn128_job(const int BKT, const TNOperand& A, const TNOperand& B, const float* zeros, const RowMap& map, int K,
+                                 int M, int mh, unsigned mstride, int Nc, float* out, int ldo, size_t slab, int nsplit,
+                                 float* nyq_out = nullptr, unsigned nyq_c0 = 0, unsigned nyq_c1 = 0, int* nyq_P = nullptr, const FrameTrim* trim = nullptr)
 {
     const float* lo = A.base < B.base ? A.base : B.base; if (zeros < lo) lo = zeros;
-    TNJob j;
+    TNLaunch l; TNJob& j = l.j;
     j.base = lo; j.a0 = (unsigned)(A.base - lo); j.b0 = (unsigned)(B.base - lo); j.zero = (unsigned)(zeros - lo);
     j.SA1 = A.S1; j.SA2 = A.S2; j.SB1 = B.S1; j.SB2 = B.S2;
     j.magic = map.magic; j.Tv = map.Tv; j.t_lo = map.t_lo; j.K = K; j.mh = mh; j.mstride = mstride;
     j.trim = (trim && trim->on) ? 1 : 0; j.fB = trim ? trim->B : 0;
     for (int i = 0; i < 64; ++i) { j.fa[i] = trim ? trim->fa[i] : 0; j.fb[i] = trim ? trim->fb[i] : 0; }
-    int ksplit = K;
-    if (nsplit > 1) ksplit = st_round_up((K + nsplit - 1) / nsplit, BKT);
-    constexpr size_t lds = (size_t)4 * BKT * 128 * sizeof(float);
-    static_assert(lds <= 65536, "the Nyquist side workgroups share a CU with a GEMM workgroup: 2 x 64 KB of the 160");
+    l.ksplit = K;
+    if (nsplit > 1) l.ksplit = st_round_up((K + nsplit - 1) / nsplit, BKT);
     const int nz = nsplit > 1 ? nsplit : 1, tiles = (Nc / 128) * (M / 128);
     j.nsplit = nz; j.Nc = Nc; j.nyq_out = nyq_out; j.nyq_c0 = nyq_c0; j.nyq_c1 = nyq_c1;
     j.nyq_P = tiles < 64 ? tiles : 64; { const int W = K / 8 > 0 ? K / 8 : 1; if (j.nyq_P > W) j.nyq_P = W; }      // partials of >= 8 reduction rows
     if (nyq_P) *nyq_P = j.nyq_P;
-    const dim3 grid(Nc / 128, M / 128, nz + (nyq_out ? 1 : 0));
+    l.out = out; l.ldo = ldo; l.slab = slab; l.M = M; l.Nc = Nc; l.nyq = nyq_out != nullptr; l.uniform = tn128_uniform(map, K, BKT, trim);
+    return l;
+}
+template <int BKT, bool PIPE = false>
+static inline int launch_tn128(const TNOperand& A, const TNOperand& B, const float* zeros, const RowMap& map, int K,
+                               int M, int mh, unsigned mstride, int Nc, float* out, int ldo, size_t slab, int nsplit, hipStream_t s,
+                               float* nyq_out = nullptr, unsigned nyq_c0 = 0, unsigned nyq_c1 = 0, int* nyq_P = nullptr, const FrameTrim* trim = nullptr)
+{
+    const TNLaunch l = tn128_job(BKT, A, B, zeros, map, K, M, mh, mstride, Nc, out, ldo, slab, nsplit, nyq_out, nyq_c0, nyq_c1, nyq_P, trim);
+    const TNJob& j = l.j; const int ksplit = l.ksplit;
+    constexpr size_t lds = (size_t)4 * BKT * 128 * sizeof(float);
+    static_assert(lds <= 65536, "the Nyquist side workgroups share a CU with a GEMM workgroup: 2 x 64 KB of the 160");
+    const dim3 grid(Nc / 128, M / 128, j.nsplit + (nyq_out ? 1 : 0));
     if (!PIPE) hipLaunchKernelGGL((gemm_tn128_kernel<BKT>), grid, dim3(256), lds, s, j, out, ldo, slab, ksplit);
-    else if (tn128_uniform(map, K, BKT, trim)) hipLaunchKernelGGL((gemm_tn128_kernel<BKT, PIPE, PIPE>), grid, dim3(256), lds, s, j, out, ldo, slab, ksplit);
+    else if (l.uniform) hipLaunchKernelGGL((gemm_tn128_kernel<BKT, PIPE, PIPE>), grid, dim3(256), lds, s, j, out, ldo, slab, ksplit);
     else hipLaunchKernelGGL((gemm_tn128_kernel<BKT, PIPE, false>), grid, dim3(256), lds, s, j, out, ldo, slab, ksplit);
+    return 0;
+}
+
+// ---- the pair launch, host side
+// k-tiles of the longest slice (slice 0) of tile column tx
+static inline int tn128_col_tiles(const TNLaunch& l, int tx, int bkt)
+{
+    int k0, k1; tn128_krange(l.j, tx, 0, l.ksplit, bkt, k0, k1);
+    return k1 > k0 ? (k1 - k0 + bkt - 1) / bkt : 0;
+}
+// false: these two launches cannot share one (different tile grids, more tile columns than the permutation holds, a job without its Nyquist slice).
+// The column pairing: job 0's columns by falling k-tile count against job 1's by rising count (ties by index) -- no pairing has a smaller largest sum.
+static inline bool tn128_pair_make(TNPair& p, const TNLaunch& a, const TNLaunch& b, int bkt)
+{
+    if (a.M != b.M || a.Nc != b.Nc || a.Nc / 128 > 64 || !a.nyq || !b.nyq) return false;
+    const TNLaunch* l[2] = {&a, &b};
+    for (int q = 0; q < 2; ++q) { p.j[q] = l[q]->j; p.out[q] = l[q]->out; p.ldo[q] = l[q]->ldo; p.slab[q] = l[q]->slab; p.ksplit[q] = l[q]->ksplit; }
+    p.nz = a.j.nsplit > b.j.nsplit ? a.j.nsplit : b.j.nsplit;
+    const int nx = a.Nc / 128;
+    int ia[64], ib[64];
+    for (int c = 0; c < nx; ++c) {                      // insertion sorts (stable)
+        const int ta = tn128_col_tiles(a, c, bkt), tb = tn128_col_tiles(b, c, bkt);
+        int i = c; while (i > 0 && tn128_col_tiles(a, ia[i - 1], bkt) < ta) { ia[i] = ia[i - 1]; --i; } ia[i] = c;
+        i = c; while (i > 0 && tn128_col_tiles(b, ib[i - 1], bkt) > tb) { ib[i] = ib[i - 1]; --i; } ib[i] = c;
+    }
+    for (int c = 0; c < 64; ++c) p.perm[c] = (unsigned char)c;
+    for (int i = 0; i < nx; ++i) p.perm[ia[i]] = (unsigned char)ib[i];
+    return true;
+}
+// The plan as numbers, slot by slot in the order (sz, sy, sx): ten ints per slot -- job 0's tile row, tile column, slice, k_begin, k_end, then job 1's; a job
+// without an entry in the slot reads -1 five times.  Returns the slot count.
+static inline int tn128_pair_describe(const TNPair& p, int ny, int nx, int bkt, int* out, int cap)
+{
+    int n = 0;
+    for (int sz = 0; sz < p.nz; ++sz)
+        for (int sy = 0; sy < ny; ++sy)
+            for (int sx = 0; sx < nx; ++sx, ++n) {
+                if (!out || n >= cap) continue;
+                for (int q = 0; q < 2; ++q) {
+                    int tx, k0, k1, *o = out + (size_t)n * 10 + 5 * q;
+                    if (tn128_pair_entry(p, q, sx, sz, bkt, tx, k0, k1)) { o[0] = sy; o[1] = tx; o[2] = sz; o[3] = k0; o[4] = k1; }
+                    else for (int i = 0; i < 5; ++i) o[i] = -1;
+                }
+            }
+    return n;
+}
+template <int BKT>
+static inline int launch_tn128_pair(const TNPair& p, const TNLaunch& a, const TNLaunch& b, hipStream_t s)
+{
+    constexpr size_t lds = (size_t)4 * BKT * 128 * sizeof(float);
+    static_assert(lds <= 65536, "the Nyquist side workgroups share a CU with a GEMM workgroup: 2 x 64 KB of the 160");
+    const dim3 grid(a.Nc / 128, a.M / 128, p.nz + 2);
+    // the wave-uniform address form only if it holds for BOTH jobs (other addresses, same bits)
+    if (a.uniform && b.uniform) hipLaunchKernelGGL((gemm_tn128_pair_kernel<BKT, true>), grid, dim3(256), lds, s, p);
+    else hipLaunchKernelGGL((gemm_tn128_pair_kernel<BKT, false>), grid, dim3(256), lds, s, p);
     return 0;
 }
 

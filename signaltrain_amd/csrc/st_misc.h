@@ -579,6 +579,17 @@ wgrad_reduce_kernel(const float* __restrict__ ws, int nz, float* __restrict__ gR
     const int row = (int)blockIdx.x < nrows ? (int)blockIdx.x + row0 : 2 * F + extra0 + ((int)blockIdx.x - nrows);
     wgrad_reduce_block(ws, nz, gRe, gIm, norm_partial, N, F, KP, mode, row, stage, nyq, stage_bf16);
 }
+// The slab sums behind the pair launch of the two weight-gradient GEMMs (gemm_tn128_pair_kernel) in ONE launch of 2 * norm_partial_count(F, N) blocks: the
+// first half is wgrad_reduce_kernel's whole-tensor launch over the analysis slabs (mode 0), the second the synthesis slab blocks of post_ae_kernel (mode 1,
+// mirrored rows) -- the same block function on the same rows in the same order, so the same bits.
+struct WgradPairArgs { const float* ws[2]; int nz[2]; float* gRe[2]; float* gIm[2]; float* norm[2]; NyqJob nyq[2]; int N, F, KP; };
+__global__ void __launch_bounds__(256)
+wgrad_pair_reduce_kernel(const WgradPairArgs a)
+{
+    const int n = norm_partial_count(a.F, a.N);
+    if ((int)blockIdx.x < n) wgrad_reduce_block(a.ws[0], a.nz[0], a.gRe[0], a.gIm[0], a.norm[0], a.N, a.F, a.KP, 0, (int)blockIdx.x, nullptr, a.nyq[0]);
+    else wgrad_reduce_block(a.ws[1], a.nz[1], a.gRe[1], a.gIm[1], a.norm[1], a.N, a.F, a.KP, 1, (int)blockIdx.x - n, nullptr, a.nyq[1]);
+}
 
 // L1 norm partials of an arbitrary flat range (data-parallel path: norm of the *reduced* gradient).
 __global__ void __launch_bounds__(256)
