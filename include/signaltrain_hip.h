@@ -297,6 +297,37 @@ int st_loss_backward(const st_dims* d, const float* params, float* grads, const 
 int st_eval_step(const st_dims* d, const float* params, const float* x, const float* knobs, const float* y_true,
                  float* y_hat /* may be NULL */, void* ws, double* acc /* device, 8 doubles */, double beta, void* stream);
 
+/* Whole-signal inference, utils/predict_long.py:30-79, as ONE call: a recording of n samples resident on the device goes through the model window by window
+ * without a copy of the windows, of the knob matrix or of the concatenated output.
+ * Windows (audio.sliding_window, audio.py:23-49, with overlap L - y): n < L gives one window, otherwise ceil((n - L) / y) + 1; window w reads
+ * signal[w y, w y + L) with zeros from sample n on -- no padded copy of the signal is made.  Output: st_predict_out_samples = max(n - (L - y), 0) floats; sample i
+ * belongs to window i / y at position i % y and to input sample (L - y) + i (the first window's lookback has no prediction, as in the reference); the last window
+ * is clipped inside the kernel, nothing at or past out + n_out is written and nothing at or past signal + n is read.
+ *   fmt         ST_PCM_F32 or ST_PCM_S16 (the pool formats of st_file_feed); an int16 sample converts as (float)((double)s / 32767.0), so an int16 recording gives,
+ *               bit for bit, the result of its float32 image.
+ *   knobs       [knob_rows][K], knob_rows == 1 (one setting for the whole signal) or == the window count (one row per window: knob automation); NULL for K == 0.
+ *   d->B        windows per internal batch: all batches are enqueued on `stream` by the one call -- no host synchronisation, no allocation, no hipMemcpy.
+ *   ws          st_predict_ws_bytes(d) bytes, 16-byte aligned: [what depends on the parameters only | the workspace of one batch].  The first part -- the folded
+ *               synthesis bases, the 16-bit (or three-plane) copies of the bases where st_dims.prec runs on them, the autoencoders' LDS weight images where the
+ *               fp32 forward kernel takes them -- is built ONCE per call (st_model_fwd / st_eval_step rebuild it per batch) and does not move when the last batch is
+ *               smaller than d->B; the second covers st_workspace_bytes of every batch 1 .. d->B.  Its saved-for-backward state is gone afterwards.
+ * Per batch: one staging launch (x / 2 with the Conv1d padding as the analysis GEMM's operand, fp32 or 16-bit, straight from the signal; the all-padding frames;
+ * the knob rows where knob_rows == 1), the forward st_eval_step takes at this st_dims.prec (the 16-bit levels run the pre-rounded operand GEMMs) with nothing kept
+ * for a backward and no mag / mag_hat copies, and one overlap-add launch that sums the synthesis frames in st_ola_loss's order, takes the residual from the signal
+ * and writes 2 (s + x / 2) to its place in out.  Parameters are only read; st_dims.loss_scale and clip_all are ignored.
+ * st_predict_supported (host only): 1 for every geometry of the fused autoencoder kernels (T <= 32 and OT <= 16) at every ST_PREC_* level; 0 for bad dims and for the
+ * wide geometries (e.g. the 65536-sample window), which stay on st_model_fwd batch by batch.  st_predict_windows / st_predict_out_samples (host only): 0 for bad
+ * dims (st_predict_windows: also for n <= 0).  st_predict_ws_bytes: 0 for bad or unsupported dims.
+ * Refused before any launch (ST_ERR_ARG, the rule in st_last_error()): bad dims; a null pointer (knobs only where K > 0); n <= 0; an unknown fmt; knob_rows neither 1
+ * nor the window count; signal or out not 16-byte aligned (ST_PCM_S16: signal 8-byte); ws not 16-byte aligned; dims st_predict_supported rejects.
+ * An n with no output sample (n <= L - y) returns ST_OK without a launch. */
+long long st_predict_windows(const st_dims* d, long long n);
+long long st_predict_out_samples(const st_dims* d, long long n);
+int       st_predict_supported(const st_dims* d);
+size_t    st_predict_ws_bytes(const st_dims* d);
+int st_predict_long(const st_dims* d, const float* params, int fmt, const void* signal, long long n,
+                    const float* knobs, long long knob_rows, float* out, void* ws, void* stream);
+
 /* Data-parallel split of st_loss_backward.  After p1 the gradients of the synthesis bases and both
  * autoencoders (grads[offs[2]..end)) are final: all-reduce them while p2 computes the analysis
  * weight gradient (rows [0,F) of tensors 0 and 1) and the loss scalars. */

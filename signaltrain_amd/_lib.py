@@ -115,6 +115,11 @@ SIGNATURES = {
     "st_model_bwd_knobs": (_i, [_D, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     "st_loss_backward": (_i, [_D, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     "st_eval_step": (_i, [_D, _p, _p, _p, _p, _p, _p, _p, C.c_double, _p]),
+    "st_predict_windows": (C.c_longlong, [_D, C.c_longlong]),
+    "st_predict_out_samples": (C.c_longlong, [_D, C.c_longlong]),
+    "st_predict_supported": (_i, [_D]),
+    "st_predict_ws_bytes": (C.c_size_t, [_D]),
+    "st_predict_long": (_i, [_D, _p, _i, _p, C.c_longlong, _p, C.c_longlong, _p, _p, _p]),
     "st_loss_backward_p1": (_i, [_D, _p, _p, _p, _p, _p, _p, _p]),
     "st_loss_backward_p2": (_i, [_D, _p, _p, _p, _p, _p]),
     "st_loss_backward_p2_staged": (_i, [_D, _p, _p, _p, _p, _p, _p]),

@@ -24,6 +24,7 @@
 #include "st_feed_files.h"
 #include "st_feed_live.h"
 #include "st_feed_stream.h"
+#include "st_predict.h"
 
 // ------------------------------------------------------------------------------ errors
 static thread_local char g_err[512] = "";
@@ -1924,6 +1925,141 @@ extern "C" int st_eval_step(const st_dims* d, const float* params, const float* 
     const stm::FinArgs f = fin_args(d, eval_p, c.w.reg_p, nullptr, nullptr, 1.0f);
     hipLaunchKernelGGL(stm::eval_finalize_kernel, dim3(1), dim3(256), 0, st_stream(stream), f, beta, acc);
     ST_LAUNCHED("eval_finalize"); return ST_OK;
+}
+
+// ------------------------------------------------------------------------------ whole-signal inference (st_predict.h)
+// utils/predict_long.py:30-79 in one call.  The workspace is [head | batch workspace]: the head holds what depends on the parameters only -- both orientations of the
+// folded synthesis bases in the form this level's GEMMs read (fp32, 16-bit, or three bfloat16 planes), the 16-bit / plane copies of the analysis rows, the forward
+// part of the autoencoders' LDS weight images -- and the batch's knob rows; it is built once per call and sized for every level, so it lies at the same place whatever
+// the batch, the level and the tuning state.  The batch workspace behind it is carved per batch exactly as the fused entries carve theirs.
+struct PredictWS {
+    float *Sfold, *SfoldT, *img, *knobs;
+    unsigned short *Sfold16, *SfoldT16, *W16, *pl_W, *pl_Sfold, *pl_SfoldT;
+    size_t head_bytes;
+};
+// the ready-made forward images do not depend on the batch here (they have a place of their own): wherever the fp32 forward kernel can take them (ae_img_level's rules but the room)
+static bool predict_img(const st_dims* d) { return g_ae_save != 2 && !ae_is_wide(d) && ae_ht(d->prec) == 0 && !ae_use_split(d) && st_kp_of(d->F) / 2 <= sta::CL::FWD_TOTAL; }
+static void predict_carve(const st_dims* d, void* base, PredictWS* p)
+{
+    const size_t F = d->F, KP = st_kp_of(d->F), N = d->N;
+    size_t off = 0;
+    auto take = [&](size_t n) { float* q = base ? reinterpret_cast<float*>(base) + off : nullptr; off += (n + 63) / 64 * 64; return q; };
+    auto take16 = [&](size_t n) { return reinterpret_cast<unsigned short*>(take((n + 1) / 2)); };
+    p->Sfold = take(KP * N); p->SfoldT = take(KP * N);
+    p->Sfold16 = take16(KP * N); p->SfoldT16 = take16(KP * N); p->W16 = take16(2 * F * N);
+    p->pl_W = take16(3 * 2 * F * N); p->pl_Sfold = take16(3 * KP * N); p->pl_SfoldT = take16(3 * KP * N);
+    p->img = take((size_t)sta::ae_img_fwd_floats((int)(KP / 2)));
+    p->knobs = take((size_t)d->B * (d->K > 0 ? d->K : 1));
+    p->head_bytes = off * sizeof(float);
+}
+static bool predict_ok(const st_dims* d) { return check_dims(d) == ST_OK && !ae_is_wide(d); }
+extern "C" int st_predict_supported(const st_dims* d) { return predict_ok(d) ? 1 : 0; }
+static long long predict_windows(const st_dims* d, long long n) { return n < d->L ? 1 : (n - d->L + d->y - 1) / d->y + 1; }      // audio.sliding_window with overlap L - y
+extern "C" long long st_predict_windows(const st_dims* d, long long n) { return (check_dims(d) != ST_OK || n <= 0) ? 0 : predict_windows(d, n); }
+extern "C" long long st_predict_out_samples(const st_dims* d, long long n)
+{
+    if (check_dims(d) != ST_OK) return 0;
+    const long long r = n - ((long long)d->L - d->y);
+    return r > 0 ? r : 0;
+}
+extern "C" size_t st_predict_ws_bytes(const st_dims* d)
+{
+    Layout L; if (make_layout(d, &L) != ST_OK || ae_is_wide(d)) return 0;
+    PredictWS p; predict_carve(d, nullptr, &p);
+    size_t best = 0;
+    st_dims q = *d;
+    for (int b = 1; b <= d->B; ++b) { q.B = b; WS w; carve(&q, L, nullptr, &w); if (w.bytes > best) best = w.bytes; }      // not monotonic in the batch (st_workspace_bytes_max)
+    return p.head_bytes + best;
+}
+template <typename T>
+static int predict_batches(const st_dims* d, const Layout& L, const PredictWS& p, const float* params, const T* signal, long long n,
+                           const float* knobs, long long knob_rows, float* out, long long n_out, void* ws, void* stream)
+{
+    const float* Wr = params + L.offs[0]; const float* Wi = params + L.offs[1];
+    const float* ae_m = params + L.offs[4]; const float* ae_p = params + L.offs[22];
+    const bool g16 = use_g16(d), planes = use_planes(d) && !g16, img = predict_img(d);
+    const long long nwin = (n_out + d->y - 1) / d->y;      // == predict_windows(d, n) wherever n_out > 0
+    for (long long w0 = 0; w0 < nwin; w0 += d->B) {
+        st_dims q = *d; q.B = (int)(nwin - w0 < d->B ? nwin - w0 : d->B);
+        WS w; carve(&q, L, reinterpret_cast<char*>(ws) + p.head_bytes, &w);
+        w.g16 = g16;
+        w.Sfold = p.Sfold; w.SfoldT = p.SfoldT; w.Sfold16 = p.Sfold16; w.SfoldT16 = p.SfoldT16; w.W16 = p.W16;
+        w.pl_W = p.pl_W; w.pl_Sfold = p.pl_Sfold; w.pl_SfoldT = p.pl_SfoldT;
+        const stg::RowMap map = stg::live_frames(q.T, q.H, q.N, q.N, q.L);
+        stp::StageArgs a;
+        a.signal = signal; a.n = n; a.s0 = w0 * q.y; a.y = q.y; a.L = q.L; a.pad = q.N; a.nb = q.B;
+        a.xp = w.xp; a.xp16 = w.xp16; a.ht = g16 ? gemm_ht(q.prec) : 0;
+        a.nbx = ((q.L + 2 * q.N) / 4 + 255) / 256; a.n_pad = a.nbx * q.B;
+        a.mag = w.mag; a.phs = w.phs; a.T = q.T; a.F = q.F; a.t_lo = map.t_lo; a.Tv = map.Tv; a.n_dead = q.B * (q.T - map.Tv);
+        const bool fill = knob_rows == 1 && q.K > 0;
+        a.knob_row = knobs; a.knobs = p.knobs; a.K = q.K; a.n_kn = fill ? (q.B * q.K + 255) / 256 : 0;
+        hipLaunchKernelGGL(stp::predict_stage_kernel<T>, dim3(a.n_pad + a.n_dead + a.n_kn), dim3(256), 0, st_stream(stream), a);
+        ST_LAUNCHED("predict_stage");
+        const float* kn = q.K == 0 ? params : fill ? p.knobs : knobs + (size_t)w0 * q.K;      // K == 0: any resident float (call_begin)
+        if (g16) ST_TRY(analysis_fwd16(&q, w, nullptr, nullptr, w.mag, w.phs, stream));
+        else if (planes) ST_TRY(analysis_fwd_planes(&q, w, nullptr, nullptr, w.mag, w.phs, stream));
+        else ST_TRY(analysis_fwd_impl(&q, w.xp, true, Wr, Wi, 1.0f, nullptr, nullptr, w.mag, w.phs, stream, true));
+        ST_TRY(ae_fwd_body(&q, L, w.mag, w.phs, kn, ae_m, ae_p, w.mag_hat, w.phs_hat, w.AA, w.reg_p, nullptr, stream, g16 ? w.AA16 : nullptr, false, nullptr,
+                           img ? p.img : nullptr));
+        if (g16) ST_TRY(synthesis_frames16(&q, w, stream)); else
+        if (planes) ST_TRY(synthesis_frames_planes(&q, w, stream)); else
+        ST_TRY(synthesis_frames_impl(&q, w.AA, w.Sfold, w.SfoldT, w.frs, stream));
+        const int ns = frame_slabs(&q);
+        const dim3 grid((q.y / 4 + 255) / 256, q.B);
+        const size_t slab = (size_t)q.B * q.OT * q.N;
+        const bool three = (q.N + q.H - 1) / q.H <= 3;      // the rule of ola_loss_impl for the four-sample form with all loads up front
+        with_bool(three, [&](auto NF3) { with_slabs(ns, [&](auto NS) {
+            hipLaunchKernelGGL((stp::predict_ola_kernel<T, NS(), NF3() ? 3 : 0>), grid, dim3(256), 0, st_stream(stream),
+                               w.frs, slab, signal, out, a.s0, n_out, q.L, q.N, q.H, q.OT, q.y); }); });
+        ST_LAUNCHED("predict_ola");
+    }
+    return ST_OK;
+}
+extern "C" int st_predict_long(const st_dims* d, const float* params, int fmt, const void* signal, long long n,
+                               const float* knobs, long long knob_rows, float* out, void* ws, void* stream)
+{
+    Layout L; ST_TRY(make_layout(d, &L));
+    ST_REQ(params, "st_predict_long: null pointer (params)"); ST_REQ(signal, "st_predict_long: null pointer (signal)");
+    ST_REQ(knobs || d->K == 0, "st_predict_long: null pointer (knobs, K = %d)", d->K);
+    ST_REQ(out, "st_predict_long: null pointer (out)"); ST_REQ(ws, "st_predict_long: null pointer (ws)");
+    ST_REQ(n > 0, "st_predict_long: n must be positive (n = %lld)", n);
+    ST_REQ(fmt == ST_PCM_F32 || fmt == ST_PCM_S16, "st_predict_long: fmt = %d is neither ST_PCM_F32 nor ST_PCM_S16", fmt);
+    const long long nwin = predict_windows(d, n);
+    ST_REQ(knob_rows == 1 || knob_rows == nwin, "st_predict_long: knob_rows = %lld must be 1 or the window count (%lld windows for n = %lld)", knob_rows, nwin, n);
+    const uintptr_t sa = fmt == ST_PCM_S16 ? 7 : 15;
+    ST_REQ((reinterpret_cast<uintptr_t>(signal) & sa) == 0, "st_predict_long: signal must be %d-byte aligned", (int)sa + 1);
+    ST_REQ((reinterpret_cast<uintptr_t>(out) & 15) == 0, "st_predict_long: out must be 16-byte aligned");
+    ST_REQ((reinterpret_cast<uintptr_t>(ws) & 15) == 0, "st_predict_long: ws must be 16-byte aligned");
+    ST_REQ(!ae_is_wide(d), "st_predict_long: not supported for the wide autoencoder geometries (T = %d > 32 or OT = %d > 16): st_predict_supported", d->T, d->OT);
+    const long long n_out = n - ((long long)d->L - d->y);
+    if (n_out <= 0) return ST_OK;      // shorter than the first window's lookback: nothing to predict, nothing launched
+    PredictWS p; predict_carve(d, ws, &p);
+    prof_mark("begin", stream);
+    {   // once per call: the parameter side of prep_kernel (its per-batch jobs have no blocks here)
+        const bool g16 = use_g16(d);
+        stm::PrepArgs a;
+        a.x = nullptr; a.xp = nullptr; a.Ls = d->L; a.pad = d->N; a.scale = 0.5f; a.nbx = 1; a.n_pad = 0;
+        a.Sr = params + L.offs[2]; a.Si = params + L.offs[3]; a.Sfold = p.Sfold; a.SfoldT = p.SfoldT; a.N = d->N; a.F = d->F; a.KP = L.KP; a.n_fold = (L.KP / 32) * (d->N / 32);
+        a.re = a.im = a.mag = a.phs = nullptr; a.T = d->T; a.t_lo = 0; a.Tv = d->T; a.n_dead = 0;
+        a.ht = g16 ? gemm_ht(d->prec) : 0; a.n_w16 = 0;
+        a.xp16 = nullptr; a.Sfold16 = p.Sfold16; a.SfoldT16 = p.SfoldT16; a.W16 = p.W16; a.Wr = params + L.offs[0]; a.Wi = params + L.offs[1];
+        if (a.ht) a.n_w16 = (int)(((size_t)2 * d->F * (d->N / 4) + 255) / 256);
+        a.wd = stm::PrepWide{}; a.wd.n_vpad = a.wd.n_kn = a.wd.n_pj = 0;
+        a.ai = sta::AEImgJob{}; a.ai.n_blk = 0;
+        if (predict_img(d)) {
+            a.ai.ae[0] = params + L.offs[4]; a.ai.ae[1] = params + L.offs[22]; a.ai.img = p.img; a.ai.go = L.go;
+            a.ai.T = d->T; a.ai.OT = d->OT; a.ai.K = d->K; a.ai.F = d->F; a.ai.FP = L.KP / 2; a.ai.expfac = expfac_of(d);
+            a.ai.n = sta::ae_img_fwd_floats(L.KP / 2); a.ai.n_blk = (a.ai.n + 255) / 256;
+        }
+        hipLaunchKernelGGL(stm::prep_kernel, dim3(a.n_fold + a.ai.n_blk + a.n_w16), dim3(256), 0, st_stream(stream), a);
+        ST_LAUNCHED("predict_prep");
+        if (use_planes(d) && !g16) {
+            WS w; w.Sfold = p.Sfold; w.SfoldT = p.SfoldT; w.pl_W = p.pl_W; w.pl_Sfold = p.pl_Sfold; w.pl_SfoldT = p.pl_SfoldT;
+            ST_TRY(planes_prepare(d, a.Wr, a.Wi, w, stream));
+        }
+    }
+    return fmt == ST_PCM_S16 ? predict_batches(d, L, p, params, reinterpret_cast<const short*>(signal), n, knobs, knob_rows, out, n_out, ws, stream)
+                             : predict_batches(d, L, p, params, reinterpret_cast<const float*>(signal), n, knobs, knob_rows, out, n_out, ws, stream);
 }
 
 // Data-parallel split of st_loss_backward: after phase 1 the synthesis + autoencoder gradients

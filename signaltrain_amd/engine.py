@@ -475,6 +475,53 @@ class StepEngine:
         """The eight accumulator values (EVAL_FIELDS order) as Python floats: ONE device->host sync."""
         return self.eval_acc.tolist()
 
+    # ---------------------------------------------------------------- whole-signal inference on the device
+    def predict_supported(self):
+        """Whether predict_long() runs this geometry (st_predict_supported: the fused autoencoder geometries; host arithmetic only)."""
+        return bool(self.lib.st_predict_supported(C.byref(self.dims.with_batch(1))))
+
+    def predict_long(self, signal, knobs, out=None, batch=None):
+        """A whole recording through the model in ONE C call (st_predict_long in include/signaltrain_hip.h; utils/predict_long.py:30-79).
+        signal: 1-D tensor on this engine's device, float32 or int16 (16-bit PCM, s / 32767); knobs: [K], [1, K] (one setting) or [nwin, K] (one row per
+        window); batch: windows per internal batch (default max_batch); out: a float32 device tensor of at least n - (L - y) samples to write into.
+        Returns the n - (L - y) predicted samples as a float32 device tensor (empty where the signal is shorter than the first window's lookback).  No host
+        sync.  The engine keeps a workspace of its own for this (st_predict_ws_bytes, allocated on first use): self.ws is not written; generation moves on."""
+        if not (torch.is_tensor(signal) and signal.dim() == 1 and signal.device == self.device and signal.dtype in (torch.float32, torch.int16)):
+            raise ValueError(f"predict_long: signal must be a 1-D float32 or int16 tensor on {self.device}")
+        signal = signal.contiguous()
+        if signal.data_ptr() % 16:
+            signal = signal.clone()           # a view that starts off a 16-byte boundary: the kernels read aligned quads
+        B = int(batch or self.max_batch)
+        if B < 1:
+            raise ValueError(f"predict_long: batch = {B}")
+        d = self.dims.with_batch(B)
+        d.prec, d.loss_scale, d.clip_all = _lib.PREC[self.compute_dtype], self.loss_scale, int(self.clip_all)
+        n = int(signal.numel())
+        nwin, n_out = int(self.lib.st_predict_windows(C.byref(d), n)), int(self.lib.st_predict_out_samples(C.byref(d), n))
+        kn, rows = None, 1
+        if d.K:
+            kn = torch.as_tensor(knobs).to(device=self.device, dtype=torch.float32).reshape(-1, d.K).contiguous()
+            rows = int(kn.shape[0])
+        if out is None:
+            out = torch.empty(n_out, dtype=torch.float32, device=self.device)
+        elif not (out.dtype == torch.float32 and out.device == self.device and out.dim() == 1 and out.is_contiguous() and out.numel() >= n_out and out.data_ptr() % 16 == 0):
+            raise ValueError(f"predict_long: out must be a contiguous, 16-byte aligned 1-D float32 tensor of at least {n_out} samples on {self.device}")
+        sizes = self.__dict__.setdefault("_predict_sizes", {})       # st_predict_ws_bytes carves every batch 1 .. B (milliseconds at B = 1024): once per (B, dtype)
+        if (B, self.compute_dtype) not in sizes:
+            sizes[(B, self.compute_dtype)] = int(self.lib.st_predict_ws_bytes(C.byref(d)))
+        need = sizes[(B, self.compute_dtype)]
+        if need <= 0:
+            raise RuntimeError(f"predict_long: st_predict_supported refuses this geometry (T={d.T}, OT={d.OT}): the wide autoencoder geometries stay on forward()")
+        if d.K and rows not in (1, nwin):
+            raise ValueError(f"predict_long: knobs has {rows} rows: one row, or one per window ({nwin} windows for {n} samples)")
+        if getattr(self, "_predict_ws", None) is None or self._predict_ws.numel() < need:
+            self._predict_ws = torch.zeros(need, dtype=torch.uint8, device=self.device)
+        self.generation += 1
+        if n_out > 0:
+            self._call("st_predict_long", C.byref(d), _lib.ptr(self.params), _lib.PCM_S16 if signal.dtype == torch.int16 else _lib.PCM_F32,
+                       C.c_void_p(signal.data_ptr()), n, _lib.ptr(kn), rows, C.c_void_p(out.data_ptr()), _lib.ptr(self._predict_ws), self._stream())
+        return out[:n_out]
+
     # ---------------------------------------------------------------- the step as one HIP graph
     def graph_capture(self, batch, lr_table, betas=(0.9, 0.999), eps=1e-8):
         """Capture st_train_step for `batch` windows into a HIP graph (st_graph_create).  The step counter and the learning rate

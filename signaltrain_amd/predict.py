@@ -6,9 +6,18 @@ overlapping windows to the device and appends the outputs on the host.  Here the
 ONCE; the overlapping windows are a strided device view (`unfold`), each batch goes through the HIP forward
 (st_model.forward / StepEngine.forward) and the non-overlapping outputs are written straight into one device buffer.
 Same arguments, same return value: a 1-D float32 numpy array of len(signal) - (chunk_size - out_chunk_size) samples
-(the first window's lookback has no prediction, exactly as in the reference)."""
+(the first window's lookback has no prediction, exactly as in the reference).
+
+route="device" runs the same prediction as ONE C call (st_predict_long, StepEngine.predict_long): the signal is uploaded as it is -- no padded copy, no
+window or knob copies -- every batch is enqueued by that call, the forward is the one validation takes at the model's compute dtype, and knobs_nn may carry one
+row per window.  route="batched" (the default) is the path described above."""
+import warnings
+
 import numpy as np
 import torch
+
+ROUTES = ("batched", "device")
+_warned_unsupported = False
 
 
 
@@ -25,9 +34,43 @@ def _windows(signal, chunk_size, step, device):
     return sig.unfold(0, chunk_size, step)                             # [nwin, chunk_size] view, no copy
 
 
+def _batched_windows(x, knobs_nn, model, out_chunk_size, batch_size):
+    """The batched route on the device: x [nwin, chunk_size] (the strided view of _windows) through model.forward batch by batch; returns the
+    nwin * out_chunk_size predicted samples as a device tensor (tools/predict_rtf.py times this part on its own)."""
+    nwin, device = x.shape[0], x.device
+    kn_np = np.asarray(knobs_nn, dtype=np.float32)
+    per_window = kn_np.ndim == 2 and nwin > 1 and kn_np.shape[0] == nwin      # one row per window (what route="device" takes, kept through its fallback)
+    kn_row = torch.as_tensor(kn_np if per_window else kn_np.reshape(1, -1), device=device)
+    y_pred = torch.empty(nwin * out_chunk_size, dtype=torch.float32, device=device)
+    bs = min(int(batch_size), nwin)
+    bmax = max(int(np.round(nwin / bs)), 1)                            # the reference's batching rule (predict_long.py:53)
+    with torch.no_grad():
+        for b in range(bmax):
+            bstart = b * bs
+            nb = (nwin - bstart) if b == bmax - 1 else bs              # the last batch takes whatever is left
+            xb = x[bstart:bstart + nb].contiguous()
+            kb = kn_row[bstart:bstart + nb] if per_window else kn_row.expand(nb, -1)
+            y_hat = model.forward(xb, kb.contiguous())[0]
+            y_pred[bstart * out_chunk_size:(bstart + nb) * out_chunk_size] = y_hat.reshape(-1)
+    return y_pred
+
+
 def predict_long(signal, knobs_nn, model, chunk_size, out_chunk_size, sr=44100, effect=None, device=None, compand=False,
-                 batch_size=200, verbose=False):
+                 batch_size=200, verbose=False, route="batched"):
+    """signal: a 1-D numpy array, or a 1-D tensor (a device tensor stays on the device with route="device"); knobs_nn: [K] normalised settings, with
+    route="device" also [nwin, K], one row per window.  Returns a 1-D float32 numpy array of len(signal) - (chunk_size - out_chunk_size) samples."""
+    if route not in ROUTES:
+        raise ValueError(f"predict_long: route must be one of {ROUTES}, not {route!r}")
     device = torch.device(device) if device is not None else next(model.parameters()).device
+    if route == "device":
+        y = _predict_device(signal, knobs_nn, model, chunk_size, out_chunk_size, device, compand, batch_size, verbose)
+        if y is not None:
+            return y
+    if torch.is_tensor(signal):
+        pcm16 = signal.dtype == torch.int16                            # 16-bit PCM means s / 32767 on either route
+        signal = signal.detach().cpu().numpy()
+        if pcm16:
+            signal = (signal.astype(np.float64) / 32767.0).astype(np.float32)
     signal = np.ascontiguousarray(signal, dtype=np.float32)
     if compand:                                                        # predict_long.py:38-40 compands every window; the map is elementwise, so the signal once
         from . import audio
@@ -42,21 +85,46 @@ def predict_long(signal, knobs_nn, model, chunk_size, out_chunk_size, sr=44100, 
     if verbose:
         print("predict_long: chunk_size, out_chunk_size, overlap = ", chunk_size, out_chunk_size, overlap)
         print("predict_long: x.shape, signal.shape = ", tuple(x.shape), signal.shape)
-    kn_row = torch.as_tensor(np.asarray(knobs_nn, dtype=np.float32).reshape(1, -1), device=device)
-    y_pred = torch.empty(nwin * out_chunk_size, dtype=torch.float32, device=device)
-    bs = min(int(batch_size), nwin)
-    bmax = max(int(np.round(nwin / bs)), 1)                            # the reference's batching rule (predict_long.py:53)
-    with torch.no_grad():
-        for b in range(bmax):
-            bstart = b * bs
-            nb = (nwin - bstart) if b == bmax - 1 else bs              # the last batch takes whatever is left
-            xb = x[bstart:bstart + nb].contiguous()
-            y_hat = model.forward(xb, kn_row.expand(nb, -1).contiguous())[0]
-            y_pred[bstart * out_chunk_size:(bstart + nb) * out_chunk_size] = y_hat.reshape(-1)
+    y_pred = _batched_windows(x, knobs_nn, model, out_chunk_size, batch_size)
     unique = chunk_size + (nwin - 1) * (chunk_size - overlap)          # predict_long.py:72-73
     num_extra = unique - n
     out = y_pred.cpu().numpy()
     return out[0:-num_extra] if num_extra > 0 else out
+
+
+def _predict_device(signal, knobs_nn, model, chunk_size, out_chunk_size, device, compand, batch_size, verbose):
+    """route="device" of predict_long; None where the library does not run this geometry that way (the caller then takes the batched route)."""
+    global _warned_unsupported
+    n = int(signal.shape[-1])
+    nwin = 1 if n < chunk_size else -(-(n - chunk_size) // out_chunk_size) + 1
+    bs = max(min(int(batch_size), nwin), 1)
+    eng = model.engine(torch.empty((), dtype=torch.float32, device=device).expand(bs, chunk_size))      # shape and device only: nothing is read
+    if (eng.dims.L, eng.dims.y) != (chunk_size, out_chunk_size):
+        raise ValueError(f"predict_long: chunk_size / out_chunk_size = {chunk_size} / {out_chunk_size}, the model has {eng.dims.L} / {eng.dims.y}")
+    if not eng.predict_supported():
+        if not _warned_unsupported:
+            _warned_unsupported = True
+            warnings.warn(f"signaltrain_amd.predict_long: route='device' does not run this geometry (T={eng.dims.T}, OT={eng.dims.OT}: st_predict_supported); "
+                          "taking the batched route", RuntimeWarning, stacklevel=3)
+        return None
+    if torch.is_tensor(signal) and not compand:
+        sig = signal.detach().to(device)
+        if sig.dtype != torch.int16:
+            sig = sig.float()
+    else:
+        host = signal.detach().cpu().numpy() if torch.is_tensor(signal) else signal
+        host = np.ascontiguousarray(host, dtype=np.float32)
+        if compand:                                                    # a host map before the upload, as on the batched route
+            from . import audio
+            print("Companding input")
+            host = np.ascontiguousarray(audio.mu_compand(host), dtype=np.float32)
+        sig = torch.from_numpy(host).to(device)
+    if verbose:
+        print("predict_long (device route): chunk_size, out_chunk_size, windows = ", chunk_size, out_chunk_size, nwin)
+    kn = torch.as_tensor(np.asarray(knobs_nn, dtype=np.float32), device=device)
+    with torch.no_grad():
+        y = eng.predict_long(sig.reshape(-1), kn, batch=bs)
+    return y.cpu().numpy()
 
 
 def fit_knobs(signal, target, model, chunk_size, out_chunk_size, steps=50, lr=0.05, init=None, batch_size=200, compand=False, grad_history=None):
