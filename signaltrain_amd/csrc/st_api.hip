@@ -329,6 +329,12 @@ template <class F> static inline auto with_ht(int ht, F&& f) { return ht == 1 ? 
 template <class F> static inline auto with_ht16(int ht, F&& f) { return ht == 2 ? f(ic<2>{}) : f(ic<1>{}); }                          // the two 16-bit levels
 template <class F> static inline auto with_bool(bool b, F&& f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
 template <class F> static inline auto with_var(int var, F&& f) { return with_ht(var, f); }                                        // ae_bwd_kernel's VAR: 0 / 1 / 2 as well (see ae_bwd_body)
+template <class F> static inline auto with_fx(int effect, F&& f)                                                                  // a feed's ST_FX_* id (feed_effect_ok checked it before)
+{
+    return effect == ST_FX_COMP ? f(ic<ST_FX_COMP>{}) : effect == ST_FX_LOWPASS ? f(ic<ST_FX_LOWPASS>{}) : effect == ST_FX_DENOISE ? f(ic<ST_FX_DENOISE>{}) :
+           effect == ST_FX_ECHO ? f(ic<ST_FX_ECHO>{}) : effect == ST_FX_DECOMP4C ? f(ic<ST_FX_DECOMP4C>{}) : f(ic<ST_FX_COMP4C>{});
+}
+template <class F> static inline auto with_pcm(int fmt, F&& f) { return fmt == ST_PCM_S16 ? f(short()) : f(float()); }              // a value of the pool's sample type: ST_PCM_S16 / ST_PCM_F32
 template <class F> static inline auto with_slabs(int ns, F&& f) { return ns == 3 ? f(ic<3>{}) : ns == 2 ? f(ic<2>{}) : f(ic<1>{}); }   // 1..3 split-K slabs
 static const int AE_FWD_NW = 8, AE_BWD_NW = 4;
 template <class F> static inline auto with_fwd_nw(int nw, F&& f) { return nw == 11 ? f(ic<11>{}) : f(ic<AE_FWD_NW>{}); }                             // ae_fwd_nw: {8, 11}
@@ -2304,10 +2310,25 @@ static const int FEED_FFT_SUB = 1024;      // windows per pass-1 / pass-2 launch
 static bool feed_long_fft(int L) { return L > stf::FFT_MAX && (L & (L - 1)) == 0 && L / stf::PL_N1 <= 256; }
 static bool feed_effect_ok(int effect) { return effect >= ST_FX_COMP4C && effect <= ST_FX_DECOMP4C; }
 static bool feed_effect_splits(int effect) { return effect == ST_FX_COMP4C || effect == ST_FX_COMP || effect == ST_FX_DECOMP4C; }      // has a lane-per-window / second-launch form through the scratch
+// The compressors' form through the scratch, the head of every feed's scratch: [gain curve or dB signal B * L | world knobs 4 B].  It is taken when the caller
+// brings scratch and L % 64 == 0 (comp_smooth_kernel's tiles); the floats are part of the scratch size whatever L is.  ST_FX_LOWPASS / ST_FX_DENOISE / ST_FX_ECHO: none.
+struct FeedSplit { float* gc; float* kw; explicit operator bool() const { return gc != nullptr; } };      // both NULL: the effect runs inside the feed kernel
+static size_t feed_split_floats(int effect, int B, int L) { return feed_effect_splits(effect) ? (size_t)B * (L + 4) : 0; }
+static FeedSplit feed_split(int effect, int B, int L, float* scratch)
+{
+    return scratch && L % 64 == 0 && feed_effect_splits(effect) ? FeedSplit{scratch, scratch + (size_t)B * L} : FeedSplit{nullptr, nullptr};
+}
+// at most 32768 windows per launch (a grid's y dimension stays below 65536): f(b0, nb) for every run of windows [b0, b0 + nb) of B
+template <class F> static inline int feed_window_runs(int B, F&& f)
+{
+    const int SUB = 32768;
+    for (int b0 = 0; b0 < B; b0 += SUB) ST_TRY(f(b0, B - b0 < SUB ? B - b0 : SUB));
+    return ST_OK;
+}
 extern "C" size_t st_synth_effect_scratch_floats(int effect, int B, int L)
 {
     if (!feed_effect_ok(effect) || B <= 0 || L <= 0) return 0;
-    size_t n = feed_effect_splits(effect) ? (size_t)B * (L + 4) : 0;      // the compressors: [gain curve or dB signal B * L | world knobs 4 B]; ST_FX_LOWPASS / ST_FX_DENOISE / ST_FX_ECHO: only the long windows' noise
+    size_t n = feed_split_floats(effect, B, L);
     if (feed_long_fft(L)) n += (size_t)B * L + (size_t)st_round_up(B, 64) + (size_t)2 * (B < FEED_FFT_SUB ? B : FEED_FFT_SUB) * L;
     return n;
 }
@@ -2328,11 +2349,6 @@ static int feed_launch(const stf::FeedArgs& a, int B, size_t lds, void* stream)
     hipLaunchKernelGGL((stf::synth_feed_kernel<FX, EXT>), dim3(B), dim3(256), lds, st_stream(stream), a);
     ST_LAUNCHED(FX == ST_FX_COMP ? "synth_comp" : FX == ST_FX_LOWPASS ? "synth_lowpass" : FX == ST_FX_DENOISE ? "synth_denoise" : FX == ST_FX_ECHO ? "synth_echo" :
                 FX == ST_FX_DECOMP4C ? "synth_decomp4c" : "synth_comp4c"); return ST_OK;
-}
-template <int FX>
-static int feed_launch_fx(bool ext, const stf::FeedArgs& a, int B, size_t lds, void* stream)
-{
-    return ext ? feed_launch<FX, true>(a, B, lds, stream) : feed_launch<FX, false>(a, B, lds, stream);
 }
 // what every feed refuses about the effect, its knob count and (host arrays, checked as soon as they are there) its knob ranges
 static int feed_effect_check(const char* who, int effect, int K, float sr, const float* knob_lo, const float* knob_hi)
@@ -2398,11 +2414,11 @@ static int synth_effect_run(const char* who, int effect, unsigned families, bool
     a.x = x; a.y = y; a.knobs = knobs; a.pink_in = pink_in; a.pink_peak = nullptr; a.seed = seed; a.first = first_window;
     a.L = L; a.ysz = ysz; a.K = K; a.sr = sr; a.augment = augment; a.chooser = chooser; a.families = families;
     for (int k = 0; k < 4; ++k) { a.lo[k] = knob_lo[k]; a.hi[k] = knob_hi[k]; }
-    const bool split = scratch && L % 64 == 0 && feed_effect_splits(effect);
-    a.gc = split ? scratch : nullptr; a.kw = split ? scratch + (size_t)B * L : nullptr;
+    const FeedSplit split = feed_split(effect, B, L, scratch);
+    a.gc = split.gc; a.kw = split.kw;
     if (long_fft) {
         // the window's 1/f noise by the library's own four-step inverse FFT (st_feed.h pink_long_pass1 / 2), 1024 windows at a time through the FFT buffer
-        float* pink = scratch + (feed_effect_splits(effect) ? (size_t)B * (L + 4) : 0);
+        float* pink = scratch + feed_split_floats(effect, B, L);
         float* peak = pink + (size_t)B * L;
         float2* fbuf = reinterpret_cast<float2*>(peak + st_round_up(B, 64));
         const int N2 = L / stf::PL_N1;
@@ -2420,12 +2436,7 @@ static int synth_effect_run(const char* who, int effect, unsigned families, bool
     static_assert(sizeof(stm::LpLds) <= (size_t)stm::COMP_CH * sizeof(float), "the low-pass scan's LDS must fit the in-kernel effect's buffer");
     static_assert(sizeof(stm::EchoLds) <= (size_t)stm::COMP_CH * sizeof(float), "the echo's taps must fit the in-kernel effect's buffer");
     const size_t lds = a.pink_in ? (split ? 0 : (size_t)stm::COMP_CH * sizeof(float)) : (size_t)stf::FFT_MAX * sizeof(float2);
-    if (effect == ST_FX_LOWPASS) return feed_launch_fx<ST_FX_LOWPASS>(ext, a, B, lds, stream);
-    if (effect == ST_FX_DENOISE) return feed_launch_fx<ST_FX_DENOISE>(ext, a, B, lds, stream);
-    if (effect == ST_FX_ECHO) return feed_launch_fx<ST_FX_ECHO>(ext, a, B, lds, stream);
-    if (effect == ST_FX_DECOMP4C) ST_TRY(feed_launch_fx<ST_FX_DECOMP4C>(ext, a, B, lds, stream));
-    else if (effect == ST_FX_COMP) ST_TRY(feed_launch_fx<ST_FX_COMP>(ext, a, B, lds, stream));
-    else ST_TRY(feed_launch_fx<ST_FX_COMP4C>(ext, a, B, lds, stream));
+    ST_TRY(with_fx(effect, [&](auto FX) { return with_bool(ext, [&](auto EXT) { return feed_launch<FX(), EXT()>(a, B, lds, stream); }); }));
     return split && finish ? feed_effect_finish(effect, B, L, ysz, sr, x, y, a.gc, a.kw, stream) : ST_OK;
 }
 extern "C" int st_synth_effect(int effect, unsigned seed, unsigned long long first_window, int B, int L, int ysz, int K, float sr,
@@ -2461,6 +2472,21 @@ extern "C" int st_synth_comp4c(unsigned seed, unsigned long long first_window, i
     return st_synth_effect(ST_FX_COMP4C, seed, first_window, B, L, ysz, K, sr, knob_lo, knob_hi, augment, chooser, pink_in, x, y, knobs, scratch, stream);
 }
 
+// what every feed of recorded input refuses about its window sizes, and about the pool it cuts them from
+static int feed_window_check(const char* who, int B, int L, int ysz, int nfiles)
+{
+    ST_REQ(B > 0 && L > 0 && ysz > 0 && nfiles > 0, "%s: bad sizes: B, L, ysz and nfiles must be positive (B=%d L=%d ysz=%d nfiles=%d)", who, B, L, ysz, nfiles);
+    ST_REQ(ysz <= L, "%s: ysz = %d exceeds L = %d (the target is the last ysz samples of the window)", who, ysz, L);
+    ST_REQ(L % 4 == 0 && ysz % 4 == 0, "%s: L = %d and ysz = %d must be multiples of 4 (the st_dims rule: 16-byte rows)", who, L, ysz);
+    return ST_OK;
+}
+static int feed_pool_check(const char* who, int fmt, int L, long long min_len, long long pool_samples)
+{
+    ST_REQ(fmt == ST_PCM_F32 || fmt == ST_PCM_S16, "%s: fmt = %d is not an ST_PCM_* id (ST_PCM_F32 = 0, ST_PCM_S16 = 1)", who, fmt);
+    ST_REQ(min_len > (long long)L, "%s: min_len = %lld: every file must be longer than the window L = %d", who, min_len, L);
+    ST_REQ(pool_samples >= min_len, "%s: pool_samples = %lld is below min_len = %lld", who, pool_samples, min_len);
+    return ST_OK;
+}
 // The feed of recorded input / target pairs (st_feed_files.h): B windows cut out of the device-resident audio pool in one launch.
 extern "C" int st_file_feed(unsigned seed, unsigned long long first_window, int B, int L, int ysz, int K, int fmt,
                             const void* pool_x, const void* pool_y, const long long* file_off, const long long* file_len, int nfiles,
@@ -2469,31 +2495,23 @@ extern "C" int st_file_feed(unsigned seed, unsigned long long first_window, int 
 {
     ST_REQ(pool_x && file_off && file_len && x, "st_file_feed: null pointer (pool_x, file_off, file_len and x are required)");
     ST_REQ(!y || pool_y, "st_file_feed: null pointer (pool_y is required when y is asked for)");
-    ST_REQ(B > 0 && L > 0 && ysz > 0 && nfiles > 0, "st_file_feed: bad sizes: B, L, ysz and nfiles must be positive (B=%d L=%d ysz=%d nfiles=%d)", B, L, ysz, nfiles);
-    ST_REQ(ysz <= L, "st_file_feed: ysz = %d exceeds L = %d (the target is the last ysz samples of the window)", ysz, L);
-    ST_REQ(L % 4 == 0 && ysz % 4 == 0, "st_file_feed: L = %d and ysz = %d must be multiples of 4 (the st_dims rule: 16-byte rows)", L, ysz);
+    ST_TRY(feed_window_check("st_file_feed", B, L, ysz, nfiles));
     ST_REQ(K >= 0 && K <= 16, "st_file_feed: K = %d knobs is outside [0, 16]", K);
     ST_REQ(K == 0 || (file_knobs && knobs), "st_file_feed: null pointer (file_knobs and knobs are required when K = %d > 0)", K);
     ST_REQ(K > 0 || !file_knobs, "st_file_feed: file_knobs must be NULL when K = 0");
-    ST_REQ(fmt == ST_PCM_F32 || fmt == ST_PCM_S16, "st_file_feed: fmt = %d is not an ST_PCM_* id (ST_PCM_F32 = 0, ST_PCM_S16 = 1)", fmt);
-    ST_REQ(min_len > (long long)L, "st_file_feed: min_len = %lld: every file must be longer than the window L = %d", min_len, L);
-    ST_REQ(pool_samples >= min_len, "st_file_feed: pool_samples = %lld is below min_len = %lld", pool_samples, min_len);
+    ST_TRY(feed_pool_check("st_file_feed", fmt, L, min_len, pool_samples));
     stf::FileFeedArgs a;
     a.pool_x = pool_x; a.pool_y = pool_y; a.file_off = file_off; a.file_len = file_len; a.file_knobs = file_knobs;
     a.pool_samples = pool_samples; a.seed = seed; a.L = L; a.ysz = ysz; a.K = K; a.nfiles = nfiles; a.augment = augment ? 1 : 0;
     a.nsx = (L + stf::FILE_SEG - 1) / stf::FILE_SEG;
     const int nsy = y ? (ysz + stf::FILE_SEG - 1) / stf::FILE_SEG : 0;
-    const int SUB = 32768;                                   // windows per launch: gridDim.y stays below 65536
-    for (int b0 = 0; b0 < B; b0 += SUB) {
-        const int nb = B - b0 < SUB ? B - b0 : SUB;
+    return feed_window_runs(B, [&](int b0, int nb) -> int {
         a.first = first_window + (unsigned long long)b0;
         a.x = x + (size_t)b0 * L; a.y = y ? y + (size_t)b0 * ysz : nullptr; a.knobs = knobs ? knobs + (size_t)b0 * K : nullptr;
         a.meta = meta ? meta + (size_t)b0 * 3 : nullptr;
-        if (fmt == ST_PCM_S16) hipLaunchKernelGGL(stf::file_feed_kernel<short>, dim3(a.nsx + nsy, nb), dim3(256), 0, st_stream(stream), a);
-        else hipLaunchKernelGGL(stf::file_feed_kernel<float>, dim3(a.nsx + nsy, nb), dim3(256), 0, st_stream(stream), a);
-        ST_LAUNCHED(fmt == ST_PCM_S16 ? "file_feed_s16" : "file_feed_f32");
-    }
-    return ST_OK;
+        with_pcm(fmt, [&](auto T) { hipLaunchKernelGGL(stf::file_feed_kernel<decltype(T)>, dim3(a.nsx + nsy, nb), dim3(256), 0, st_stream(stream), a); });
+        ST_LAUNCHED(fmt == ST_PCM_S16 ? "file_feed_s16" : "file_feed_f32"); return ST_OK;
+    });
 }
 
 // The feed of recorded input through a live effect (st_feed_live.h): per window a span of the audio pool, fresh knobs and the effect on the spot; a
@@ -2502,33 +2520,27 @@ extern "C" size_t st_live_feed_scratch_floats(int effect, int B, int L, float sy
 {
     if (synth_prob > 0.f) return st_synth_effect_scratch_floats(effect, B, L);      // the synthetic rows' generator shares the scratch
     if (!feed_effect_ok(effect) || B <= 0 || L <= 0) return 0;
-    return feed_effect_splits(effect) ? (size_t)B * (L + 4) : 0;
+    return feed_split_floats(effect, B, L);
 }
-template <int FX>
-static int live_launch(int fmt, const stf::LiveFeedArgs& a, int B, size_t lds, void* stream)
-{
-    if (fmt == ST_PCM_S16) hipLaunchKernelGGL((stf::live_feed_kernel<FX, short>), dim3(B), dim3(256), lds, st_stream(stream), a);
-    else hipLaunchKernelGGL((stf::live_feed_kernel<FX, float>), dim3(B), dim3(256), lds, st_stream(stream), a);
-    ST_LAUNCHED(fmt == ST_PCM_S16 ? "live_feed_s16" : "live_feed_f32"); return ST_OK;
-}
-// what st_live_feed and st_live_feed_stream refuse alike, before any launch
-static int live_feed_check(const char* who, int effect, unsigned family_mask, float synth_prob, int B, int L, int ysz, int K, float sr, const float* knob_lo, const float* knob_hi,
-                           int fmt, const void* pool_x, const long long* file_off, const long long* file_len, int nfiles, long long min_len, long long pool_samples,
-                           const float* x, const float* y, const float* knobs)
+// what st_live_feed and st_live_feed_stream refuse alike, before any launch, and the kernel arguments they share (gc / kw stay NULL: st_live_feed sets them)
+static int live_feed_prepare(const char* who, int effect, unsigned family_mask, float synth_prob, unsigned seed, unsigned long long first_window,
+                             int B, int L, int ysz, int K, float sr, const float* knob_lo, const float* knob_hi, int augment,
+                             int fmt, const void* pool_x, const long long* file_off, const long long* file_len, int nfiles, long long min_len, long long pool_samples,
+                             float* x, float* y, float* knobs, long long* meta, stf::LiveFeedArgs& a)
 {
     ST_REQ(knob_lo && knob_hi, "%s: null pointer (knob_lo and knob_hi, four host floats each, are required)", who);
     ST_TRY(feed_effect_check(who, effect, K, sr, knob_lo, knob_hi));
-    ST_REQ(B > 0 && L > 0 && ysz > 0 && nfiles > 0, "%s: bad sizes: B, L, ysz and nfiles must be positive (B=%d L=%d ysz=%d nfiles=%d)", who, B, L, ysz, nfiles);
-    ST_REQ(ysz <= L, "%s: ysz = %d exceeds L = %d (the target is the last ysz samples of the window)", who, ysz, L);
-    ST_REQ(L % 4 == 0 && ysz % 4 == 0, "%s: L = %d and ysz = %d must be multiples of 4 (the st_dims rule: 16-byte rows)", who, L, ysz);
+    ST_TRY(feed_window_check(who, B, L, ysz, nfiles));
     ST_REQ(sr > 0.f, "%s: sr = %g must be positive", who, sr);
     ST_REQ(synth_prob >= 0.f && synth_prob <= 1.f, "%s: synth_prob = %g is not a probability in [0, 1]", who, synth_prob);      // refuses NaN as well
-    ST_REQ(fmt == ST_PCM_F32 || fmt == ST_PCM_S16, "%s: fmt = %d is not an ST_PCM_* id (ST_PCM_F32 = 0, ST_PCM_S16 = 1)", who, fmt);
-    ST_REQ(min_len > (long long)L, "%s: min_len = %lld: every file must be longer than the window L = %d", who, min_len, L);
-    ST_REQ(pool_samples >= min_len, "%s: pool_samples = %lld is below min_len = %lld", who, pool_samples, min_len);
+    ST_TRY(feed_pool_check(who, fmt, L, min_len, pool_samples));
     ST_REQ(pool_x && file_off && file_len, "%s: null pointer (pool_x, file_off and file_len are required)", who);
     ST_REQ(x && y && knobs, "%s: null pointer (x, y and knobs are required)", who);
     if (synth_prob > 0.f) ST_TRY(family_mask_check(who, family_mask));
+    a.pool = pool_x; a.file_off = file_off; a.file_len = file_len; a.x = x; a.y = y; a.knobs = knobs; a.meta = meta; a.gc = nullptr; a.kw = nullptr;
+    a.pool_samples = pool_samples; a.seed = seed; a.first = first_window; a.L = L; a.ysz = ysz; a.K = K; a.nfiles = nfiles; a.augment = augment ? 1 : 0;
+    a.sr = sr; a.synth_prob = synth_prob;
+    for (int k = 0; k < 4; ++k) { a.lo[k] = knob_lo[k]; a.hi[k] = knob_hi[k]; }
     return ST_OK;
 }
 extern "C" int st_live_feed(int effect, unsigned family_mask, float synth_prob, unsigned seed, unsigned long long first_window,
@@ -2538,30 +2550,22 @@ extern "C" int st_live_feed(int effect, unsigned family_mask, float synth_prob, 
                             float* x, float* y, float* knobs, long long* meta, float* scratch, void* stream)
 {
     const char* who = "st_live_feed";
-    ST_TRY(live_feed_check(who, effect, family_mask, synth_prob, B, L, ysz, K, sr, knob_lo, knob_hi, fmt, pool_x, file_off, file_len, nfiles, min_len, pool_samples, x, y, knobs));
-    const bool split = scratch && L % 64 == 0 && feed_effect_splits(effect);
-    float* gc = split ? scratch : nullptr; float* kw = split ? scratch + (size_t)B * L : nullptr;
+    stf::LiveFeedArgs a;
+    ST_TRY(live_feed_prepare(who, effect, family_mask, synth_prob, seed, first_window, B, L, ysz, K, sr, knob_lo, knob_hi, augment, fmt, pool_x, file_off, file_len, nfiles,
+                             min_len, pool_samples, x, y, knobs, meta, a));
+    const FeedSplit split = feed_split(effect, B, L, scratch);
+    a.gc = split.gc; a.kw = split.kw;
     // synthetic rows: the generator of st_synth_effect_families over the whole batch (its checks, the long windows' scratch contract among them, come before its
     // first launch); the recorded rows are overwritten below and the scratch form's second launches run once, after both
     if (synth_prob > 0.f)
         ST_TRY(synth_effect_run(who, effect, family_mask, true, seed, first_window, B, L, ysz, K, sr, knob_lo, knob_hi, augment, -1, nullptr, x, y, knobs, scratch, stream, false));
     if (synth_prob < 1.f || meta) {
-        stf::LiveFeedArgs a;
-        a.pool = pool_x; a.file_off = file_off; a.file_len = file_len; a.x = x; a.y = y; a.knobs = knobs; a.meta = meta; a.gc = gc; a.kw = kw;
-        a.pool_samples = pool_samples; a.seed = seed; a.first = first_window; a.L = L; a.ysz = ysz; a.K = K; a.nfiles = nfiles; a.augment = augment ? 1 : 0;
-        a.sr = sr; a.synth_prob = synth_prob;
-        for (int k = 0; k < 4; ++k) { a.lo[k] = knob_lo[k]; a.hi[k] = knob_hi[k]; }
         const size_t lds = split || effect == ST_FX_DENOISE ? 0 : (size_t)stm::COMP_CH * sizeof(float);      // the in-workgroup effect's buffer (synth_effect_run's static_asserts)
-        switch (effect) {
-        case ST_FX_COMP: ST_TRY(live_launch<ST_FX_COMP>(fmt, a, B, lds, stream)); break;
-        case ST_FX_LOWPASS: ST_TRY(live_launch<ST_FX_LOWPASS>(fmt, a, B, lds, stream)); break;
-        case ST_FX_DENOISE: ST_TRY(live_launch<ST_FX_DENOISE>(fmt, a, B, lds, stream)); break;
-        case ST_FX_ECHO: ST_TRY(live_launch<ST_FX_ECHO>(fmt, a, B, lds, stream)); break;
-        case ST_FX_DECOMP4C: ST_TRY(live_launch<ST_FX_DECOMP4C>(fmt, a, B, lds, stream)); break;
-        default: ST_TRY(live_launch<ST_FX_COMP4C>(fmt, a, B, lds, stream)); break;
-        }
+        with_fx(effect, [&](auto FX) { with_pcm(fmt, [&](auto T) {
+            hipLaunchKernelGGL((stf::live_feed_kernel<FX(), decltype(T)>), dim3(B), dim3(256), lds, st_stream(stream), a); }); });
+        ST_LAUNCHED(fmt == ST_PCM_S16 ? "live_feed_s16" : "live_feed_f32");
     }
-    return split ? feed_effect_finish(effect, B, L, ysz, sr, x, y, gc, kw, stream) : ST_OK;
+    return split ? feed_effect_finish(effect, B, L, ysz, sr, x, y, split.gc, split.kw, stream) : ST_OK;
 }
 
 // st_live_feed with the effect's history (st_feed_stream.h).  Scratch of the pre-roll form, P = round_up(preroll + L, 64):
@@ -2585,13 +2589,6 @@ extern "C" size_t st_live_feed_stream_scratch_floats(int effect, int B, int L, i
     if (effect != ST_FX_DENOISE) n += (size_t)B * stream_pitch(L, preroll);
     return n + (synth_prob > 0.f ? st_live_feed_scratch_floats(effect, B, L, synth_prob) : 0);
 }
-template <int FX>
-static int stream_launch(int fmt, const stf::StreamFeedArgs& a, int B, size_t lds, void* stream)
-{
-    if (fmt == ST_PCM_S16) hipLaunchKernelGGL((stf::stream_feed_kernel<FX, short>), dim3(B), dim3(256), lds, st_stream(stream), a);
-    else hipLaunchKernelGGL((stf::stream_feed_kernel<FX, float>), dim3(B), dim3(256), lds, st_stream(stream), a);
-    ST_LAUNCHED(fmt == ST_PCM_S16 ? "stream_feed_s16" : "stream_feed_f32"); return ST_OK;
-}
 extern "C" int st_live_feed_stream(int effect, unsigned family_mask, float synth_prob, int preroll, unsigned seed, unsigned long long first_window,
                                    int B, int L, int ysz, int K, float sr, const float* knob_lo, const float* knob_hi, int augment,
                                    int fmt, const void* pool_x, const long long* file_off, const long long* file_len, int nfiles,
@@ -2605,10 +2602,11 @@ extern "C" int st_live_feed_stream(int effect, unsigned family_mask, float synth
     const char* why = stream_limit(B, L, preroll);
     ST_REQ(!why, "%s: %s (preroll=%d B=%d L=%d)", who, why, preroll, B, L);
     ST_REQ(scratch, "%s: null pointer (scratch, st_live_feed_stream_scratch_floats() floats, is required with preroll = %d > 0)", who, preroll);
-    ST_TRY(live_feed_check(who, effect, family_mask, synth_prob, B, L, ysz, K, sr, knob_lo, knob_hi, fmt, pool_x, file_off, file_len, nfiles, min_len, pool_samples, x, y, knobs));
+    stf::StreamFeedArgs s;
+    ST_TRY(live_feed_prepare(who, effect, family_mask, synth_prob, seed, first_window, B, L, ysz, K, sr, knob_lo, knob_hi, augment, fmt, pool_x, file_off, file_len, nfiles,
+                             min_len, pool_samples, x, y, knobs, meta, s.live));
     const int P = stream_pitch(L, preroll);
     const bool gain = effect == ST_FX_COMP4C || effect == ST_FX_DECOMP4C;
-    stf::StreamFeedArgs s;
     s.kw = scratch; s.rr = reinterpret_cast<int*>(scratch + (size_t)4 * B);
     float* rest = scratch + (size_t)4 * B + (size_t)st_round_up(B, 4);
     s.buf = effect == ST_FX_DENOISE ? nullptr : rest;
@@ -2619,37 +2617,26 @@ extern "C" int st_live_feed_stream(int effect, unsigned family_mask, float synth
     if (synth_prob > 0.f) {
         float* scr_l = st_live_feed_scratch_floats(effect, B, L, synth_prob) ? rest : nullptr;
         ST_TRY(synth_effect_run(who, effect, family_mask, true, seed, first_window, B, L, ysz, K, sr, knob_lo, knob_hi, augment, -1, nullptr, x, y, knobs, scr_l, stream, false));
-        if (scr_l && L % 64 == 0 && feed_effect_splits(effect)) ST_TRY(feed_effect_finish(effect, B, L, ysz, sr, x, y, scr_l, scr_l + (size_t)B * L, stream));
+        if (const FeedSplit sp = feed_split(effect, B, L, scr_l)) ST_TRY(feed_effect_finish(effect, B, L, ysz, sr, x, y, sp.gc, sp.kw, stream));
     }
-    stf::LiveFeedArgs& a = s.live;
-    a.pool = pool_x; a.file_off = file_off; a.file_len = file_len; a.x = x; a.y = y; a.knobs = knobs; a.meta = meta; a.gc = nullptr; a.kw = nullptr;
-    a.pool_samples = pool_samples; a.seed = seed; a.first = first_window; a.L = L; a.ysz = ysz; a.K = K; a.nfiles = nfiles; a.augment = augment ? 1 : 0;
-    a.sr = sr; a.synth_prob = synth_prob;
-    for (int k = 0; k < 4; ++k) { a.lo[k] = knob_lo[k]; a.hi[k] = knob_hi[k]; }
     const size_t lds = gain || effect == ST_FX_DENOISE ? 0 : (size_t)stm::COMP_CH * sizeof(float);      // the in-workgroup effect's buffer (synth_effect_run's static_asserts)
-    switch (effect) {
-    case ST_FX_COMP: ST_TRY(stream_launch<ST_FX_COMP>(fmt, s, B, lds, stream)); break;
-    case ST_FX_LOWPASS: ST_TRY(stream_launch<ST_FX_LOWPASS>(fmt, s, B, lds, stream)); break;
-    case ST_FX_DENOISE: ST_TRY(stream_launch<ST_FX_DENOISE>(fmt, s, B, lds, stream)); break;
-    case ST_FX_ECHO: ST_TRY(stream_launch<ST_FX_ECHO>(fmt, s, B, lds, stream)); break;
-    case ST_FX_DECOMP4C: ST_TRY(stream_launch<ST_FX_DECOMP4C>(fmt, s, B, lds, stream)); break;
-    default: ST_TRY(stream_launch<ST_FX_COMP4C>(fmt, s, B, lds, stream)); break;
-    }
+    with_fx(effect, [&](auto FX) { with_pcm(fmt, [&](auto T) {
+        hipLaunchKernelGGL((stf::stream_feed_kernel<FX(), decltype(T)>), dim3(B), dim3(256), lds, st_stream(stream), s); }); });
+    ST_LAUNCHED(fmt == ST_PCM_S16 ? "stream_feed_s16" : "stream_feed_f32");
     if (!gain) return ST_OK;
     // the recorded rows' chain at pitch P: history tiles advance the state, only the tiles the apply kernel reads are stored
     const int keep0 = (P - (effect == ST_FX_DECOMP4C ? L : ysz)) & ~63;
     hipLaunchKernelGGL(stf::stream_smooth_kernel, dim3((B + 63) / 64), dim3(64), 0, st_stream(stream), s.buf, (const float*)s.kw, (const int*)s.rr, sr, B, L, P, keep0);
     ST_LAUNCHED("stream_smooth");
-    const int SUB = 32768;                                   // windows per launch: gridDim.y stays below 65536
-    for (int b0 = 0; b0 < B; b0 += SUB) {
-        const int nb = B - b0 < SUB ? B - b0 : SUB;
+    feed_window_runs(B, [&](int b0, int nb) -> int {
         if (effect == ST_FX_DECOMP4C)
             hipLaunchKernelGGL(stf::stream_apply_inplace_kernel, dim3((L + 2047) / 2048 < 65535 ? (L + 2047) / 2048 : 65535, nb), dim3(256), 0, st_stream(stream),
                                x + (size_t)b0 * L, (const float*)s.buf + (size_t)b0 * P, (const int*)s.rr + b0, L, P);
         else
             hipLaunchKernelGGL(stf::stream_apply_kernel, dim3((ysz + 255) / 256, nb), dim3(256), 0, st_stream(stream),
                                (const float*)x + (size_t)b0 * L, (const float*)s.buf + (size_t)b0 * P, (const int*)s.rr + b0, L, P, ysz, y + (size_t)b0 * ysz);
-    }
+        return ST_OK;
+    });
     ST_LAUNCHED(effect == ST_FX_DECOMP4C ? "stream_apply_inplace" : "stream_apply");
     return ST_OK;
 }

@@ -130,6 +130,34 @@ __device__ __forceinline__ float world_knob_f32(const float lo, const float hi, 
     const float t = (kn + 0.5f) * (hi - lo);
     return lo + t;
 }
+// THE KNOB RULE of every feed with drawn knobs (synth_feed_kernel, live_feed_kernel, stream_feed_kernel): kn[k] = Beta(0.8, 0.8) - 0.5 from the next draws of
+// `d` -- all four, whatever K is: one stream for every K -- and the world knobs kw[k] = lo + (kn + 0.5) (hi - lo), the ones past K fixed at their low end.
+// ST_FX_LOWPASS / ST_FX_DENOISE: the one knob as float32 Effect.knobs_wc gives it, every step rounded.  ST_FX_ECHO: Echo.go_wc (audio.py:547), float32 world
+// knobs with the delay and the echo count rounded half to even.  So st_compressor_4c / st_compressor / st_lowpass / st_echo / st_denoise_input on
+// (x, these knobs) reproduce the feed bit for bit.
+template <int FX>
+__device__ __forceinline__ void feed_knobs(Draw& d, const float (&lo)[4], const float (&hi)[4], const int K, float (&kn)[4], float (&kw)[4])
+{
+    for (int k = 0; k < 4; ++k) { kn[k] = d.beta(0.8f) - 0.5f; kw[k] = lo[k] + (kn[k] + 0.5f) * (hi[k] - lo[k]); }
+    for (int k = K; k < 4; ++k) kw[k] = lo[k];
+    if (FX == ST_FX_LOWPASS || FX == ST_FX_DENOISE) kw[0] = world_knob_f32(lo[0], hi[0], kn[0]);
+    if (FX == ST_FX_ECHO) {
+        kw[0] = rintf(world_knob_f32(lo[0], hi[0], kn[0]));
+        kw[1] = world_knob_f32(lo[1], hi[1], kn[1]);
+        kw[2] = rintf(world_knob_f32(lo[2], hi[2], kn[2]));
+    }
+}
+// four consecutive samples at once: denoise_add on samples n .. n + 3, and what the compressors' second launches read (the static gain curve; ST_FX_COMP: the dB signal)
+__device__ __forceinline__ float4 denoise_add4(const unsigned key, const unsigned n, const float strength, const float4 v)
+{
+    return make_float4(denoise_add(key, n, strength, v.x), denoise_add(key, n + 1u, strength, v.y), denoise_add(key, n + 2u, strength, v.z), denoise_add(key, n + 3u, strength, v.w));
+}
+__device__ __forceinline__ float4 comp_gain_curve4(const float4 v, const float thresh, const float ratio)
+{
+    return make_float4(stm::comp_gain_curve(v.x, (double)thresh, (double)ratio), stm::comp_gain_curve(v.y, (double)thresh, (double)ratio),
+                       stm::comp_gain_curve(v.z, (double)thresh, (double)ratio), stm::comp_gain_curve(v.w, (double)thresh, (double)ratio));
+}
+__device__ __forceinline__ float4 env_db4(const float4 v) { return make_float4(stm::env_db(v.x), stm::env_db(v.y), stm::env_db(v.z), stm::env_db(v.w)); }
 struct FeedArgs {
     float* x; float* y; float* knobs;       // outputs
     const float* pink_in;                   // [B][L] 1/f noise for windows longer than the in-kernel FFT handles (else NULL): unit-peak from the caller, or
@@ -207,9 +235,7 @@ denoise_input_kernel(const unsigned seed, const unsigned long long first, const 
     for (int n4 = blockIdx.y * 256 + threadIdx.x; n4 < L / 4; n4 += gridDim.y * 256) {
         const size_t o = (size_t)b * L + 4 * (size_t)n4;
         const unsigned n = 4u * (unsigned)n4;
-        float4 v = *reinterpret_cast<const float4*>(x + o);
-        v = make_float4(denoise_add(key, n, sgth, v.x), denoise_add(key, n + 1u, sgth, v.y), denoise_add(key, n + 2u, sgth, v.z), denoise_add(key, n + 3u, sgth, v.w));
-        *reinterpret_cast<float4*>(x_noisy + o) = v;
+        *reinterpret_cast<float4*>(x_noisy + o) = denoise_add4(key, n, sgth, *reinterpret_cast<const float4*>(x + o));
     }
 }
 // G independent in-place inverse FFTs of length n = 2^logn in LDS (a[g * n + i], input stored bit-reversed), 256 threads; tw[k] = e^{2 pi i k / n}, k < n / 2
@@ -323,15 +349,7 @@ synth_feed_kernel(const FeedArgs a)
     // ---- the window's parameters (datasets.py:317, audio.py:296-334)
     const int ch = EXT ? feed_family(d, a.chooser, a.families) : feed_family(d, a.chooser);      // {0, 1, 2, 4, 6, 7} unless EXT
     float kn[4], kw[4];
-    for (int k = 0; k < 4; ++k) { kn[k] = d.beta(0.8f) - 0.5f; kw[k] = a.lo[k] + (kn[k] + 0.5f) * (a.hi[k] - a.lo[k]); }
-    for (int k = a.K; k < 4; ++k) kw[k] = a.lo[k];                   // K < 4: the remaining knobs are fixed settings (all four are drawn: one stream for every K)
-    if (FX == ST_FX_LOWPASS || FX == ST_FX_DENOISE)                  // the one knob as float32 Effect.knobs_wc gives it, every step rounded: st_lowpass / st_denoise_input
-        kw[0] = world_knob_f32(a.lo[0], a.hi[0], kn[0]);                                             // on (x, these knobs) reproduce the feed bit for bit
-    if (FX == ST_FX_ECHO) {                                          // Echo.go_wc (audio.py:547): float32 world knobs, the delay and the echo count rounded half to even;
-        kw[0] = rintf(world_knob_f32(a.lo[0], a.hi[0], kn[0]));      // st_echo on (x, these knobs) reproduces the feed bit for bit
-        kw[1] = world_knob_f32(a.lo[1], a.hi[1], kn[1]);
-        kw[2] = rintf(world_knob_f32(a.lo[2], a.hi[2], kn[2]));
-    }
+    feed_knobs<FX>(d, a.lo, a.hi, a.K, kn, kw);                      // the next draws of the first sequence (the knob rule: feed_knobs)
     // randsine (audio.py:96-104)
     const int s_n = d.randint(1, 3);
     float s_amp[2], s_frq[2], s_t0[2];
@@ -482,16 +500,9 @@ synth_feed_kernel(const FeedArgs a)
                 if (j + 2 >= 0) yb[j + 2] = v.z;
                 if (j + 3 >= 0) yb[j + 3] = v.w;
             }
-            if (FX == ST_FX_DENOISE) {                               // ... and the input leaves with the noise on it
-                v = make_float4(denoise_add(key, (unsigned)n, kw[0], v.x), denoise_add(key, (unsigned)n + 1u, kw[0], v.y),
-                                denoise_add(key, (unsigned)n + 2u, kw[0], v.z), denoise_add(key, (unsigned)n + 3u, kw[0], v.w));
-            }
+            if (FX == ST_FX_DENOISE) v = denoise_add4(key, (unsigned)n, kw[0], v);      // ... and the input leaves with the noise on it
             *reinterpret_cast<float4*>(xb + n) = v;
-            if (gcb) {
-                if (FX == ST_FX_COMP) *reinterpret_cast<float4*>(gcb + n) = make_float4(stm::env_db(v.x), stm::env_db(v.y), stm::env_db(v.z), stm::env_db(v.w));
-                else *reinterpret_cast<float4*>(gcb + n) = make_float4(stm::comp_gain_curve(v.x, (double)kw[0], (double)kw[1]), stm::comp_gain_curve(v.y, (double)kw[0], (double)kw[1]),
-                                                                       stm::comp_gain_curve(v.z, (double)kw[0], (double)kw[1]), stm::comp_gain_curve(v.w, (double)kw[0], (double)kw[1]));
-            }
+            if (gcb) *reinterpret_cast<float4*>(gcb + n) = FX == ST_FX_COMP ? env_db4(v) : comp_gain_curve4(v, kw[0], kw[1]);
         }
     } else {
         for (int n = threadIdx.x; n < L; n += 256) {

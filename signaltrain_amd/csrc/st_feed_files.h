@@ -9,11 +9,7 @@
 // THE DRAW LAW (integer arithmetic only; datasets.file_feed_draw is its host replica):
 //   key     = feed_key(seed, w)                                        (st_feed.h: the window key of every feed of this library)
 //   h_i     = mix32(key + 0x9E3779B9 * i)   (mod 2^32), i = 1, 2, 3    (Draw::h(): the i-th 32-bit hash of the window's sequential stream)
-//   file    = (uint64(h_1) * nfiles) >> 32                             in [0, nfiles): uniform over files, not weighted by length
-//   start   = (uint64(h_2) * (file_len[file] - L)) >> 32               in [0, len - L): the last position is excluded, as np.random.randint excludes it
-//   flipped = augment ? h_3 >> 31 : 0                                  (h_3 is drawn either way: one stream for both settings)
-// A bounded draw ((uint64)h * n) >> 32 reaches every value below n <= 2^31 - 1 (n <= 2^32 values spread over 2^32 hashes), so every start of
-// a file of up to 2^31 - 1 samples can occur; a float32-scaled draw cannot place a start on an odd sample beyond 2^24.
+//   (file, start, flipped) = feed_span(h_1, h_2, h_3, ...)             (below: THE SPAN CHOICE of every feed of recorded input; h_3 is drawn either way)
 // Outputs: x [B][L] = pool_x[off + start .. + L), y [B][ysz] = the last ysz samples of the same span of pool_y, both times -1 where flipped;
 // knobs [B][K] = row `file` of file_knobs; meta [B][3] = (file, start, flipped).
 // ST_PCM_S16 converts a sample s as audio.read_audio_file does, (float)((double)s / 32767.0).  The float32 division (float)s / 32767.0f is
@@ -25,8 +21,7 @@
 // Destination rows are 16-byte aligned (L % 4 == ysz % 4 == 0, hipMalloc'ed bases): 16-byte stores.  A source span starts at ANY sample, so the
 // loads go through vector types DECLARED with the element's alignment (f32x4_a4: 16 bytes aligned 4; s16x4_a2: 8 bytes aligned 2) -- never a
 // float4 / short4 pointer at an address below its alignment.  All of a lane's loads are issued before its first store.
-// Addresses: file < nfiles by construction; len - L is clamped to [1, 2^31 - 1] and off + start to [0, pool_samples - L], so whatever the tables
-// say, every address formed lies inside [0, pool_samples) (the entry refuses pool_samples <= L).  Truthful tables are never clamped.
+// Addresses: feed_span's clamps (below) keep every address formed inside [0, pool_samples), whatever the tables say.
 #pragma once
 #include "st_feed.h"
 
@@ -52,6 +47,42 @@ __device__ __forceinline__ float4 file_quad(const short* p)
     return make_float4((float)v.x / 32767.0f, (float)v.y / 32767.0f, (float)v.z / 32767.0f, (float)v.w / 32767.0f);
 }
 
+// THE SPAN CHOICE of every feed of recorded input (file_feed_kernel, live_feed_kernel, stream_feed_kernel), from three 32-bit hashes of the window:
+//   file    = (uint64(h_file) * nfiles) >> 32                          in [0, nfiles): uniform over files, not weighted by length
+//   start   = (uint64(h_start) * (file_len[file] - L)) >> 32           in [0, len - L): the last position is excluded, as np.random.randint excludes it
+//   flipped = augment ? h_flip >> 31 : 0
+// A bounded draw ((uint64)h * n) >> 32 reaches every value below n <= 2^31 - 1 (n <= 2^32 values spread over 2^32 hashes), so every start of
+// a file of up to 2^31 - 1 samples can occur; a float32-scaled draw cannot place a start on an odd sample beyond 2^24.
+// Addresses: file < nfiles by construction; len - L is clamped to [1, 2^31 - 1] and base = off + start to [0, pool_samples - L], so whatever the tables
+// say, every address of the span [base, base + L) lies inside [0, pool_samples) (the entries refuse pool_samples <= L).  Truthful tables are never clamped.
+struct FeedSpan { int f; long long base; bool flip; };      // base: the span's first sample in the pool; start = base - file_off[f]
+__device__ __forceinline__ FeedSpan feed_span(const unsigned h_file, const unsigned h_start, const unsigned h_flip, const long long* file_off, const long long* file_len,
+                                              const int nfiles, const int L, const long long pool_samples, const int augment)
+{
+    const int f = below(h_file, nfiles);
+    long long n = file_len[f] - (long long)L;
+    n = n < 1 ? 1 : (n > 0x7fffffffLL ? 0x7fffffffLL : n);
+    long long base = file_off[f] + (long long)(((unsigned long long)h_start * (unsigned long long)n) >> 32);
+    const long long top = pool_samples - (long long)L;
+    base = base < 0 ? 0 : (base > top ? top : base);
+    return {f, base, augment && (h_flip >> 31)};
+}
+
+// THE WINDOW LOADER: TRIPS quads of 4 samples per lane, quad t of a lane at sample quad_at(i0, t) of a span of len samples (len % 4 == 0: a quad lies
+// inside the span or outside it).  The loads are unconditional -- a quad past the end re-reads the span's last one -- so no branch stands between them,
+// and the caller stores only after the call: all of a lane's loads are issued before its first store.
+__device__ __forceinline__ unsigned quad_at(const unsigned i0, const int t) { return i0 + 4u * (t * 256 + threadIdx.x); }
+template <int TRIPS, typename T>
+__device__ __forceinline__ void load_quads(const T* __restrict__ src, const unsigned i0, const unsigned len, float4 (&q)[TRIPS])
+{
+#pragma unroll
+    for (int t = 0; t < TRIPS; ++t) {
+        const unsigned i = quad_at(i0, t);
+        q[t] = file_quad(src + (i < len ? i : len - 4u));
+    }
+}
+__device__ __forceinline__ float4 quad_sign(const float4 v, const float sg) { return make_float4(v.x * sg, v.y * sg, v.z * sg, v.w * sg); }
+
 template <typename T>
 __global__ void __launch_bounds__(256)
 file_feed_kernel(const FileFeedArgs a)
@@ -60,13 +91,7 @@ file_feed_kernel(const FileFeedArgs a)
     const unsigned long long w = a.first + (unsigned long long)b;
     Draw d{feed_key(a.seed, w), 0u};
     const unsigned h1 = d.h(), h2 = d.h(), h3 = d.h();
-    const int f = (int)(((unsigned long long)h1 * (unsigned long long)(unsigned)a.nfiles) >> 32);
-    long long n = a.file_len[f] - (long long)L;
-    n = n < 1 ? 1 : (n > 0x7fffffffLL ? 0x7fffffffLL : n);
-    long long base = a.file_off[f] + (long long)(((unsigned long long)h2 * (unsigned long long)n) >> 32);
-    const long long top = a.pool_samples - (long long)L;
-    base = base < 0 ? 0 : (base > top ? top : base);
-    const bool flip = a.augment && (h3 >> 31);
+    const auto [f, base, flip] = feed_span(h1, h2, h3, a.file_off, a.file_len, a.nfiles, L, a.pool_samples, a.augment);
     const float sg = flip ? -1.f : 1.f;
 
     const bool is_y = (int)blockIdx.x >= a.nsx;                          // workgroup-uniform
@@ -75,16 +100,11 @@ file_feed_kernel(const FileFeedArgs a)
     const T* __restrict__ src = reinterpret_cast<const T*>(is_y ? a.pool_y : a.pool_x) + base + (is_y ? L - a.ysz : 0);
     float* __restrict__ dst = is_y ? a.y + (size_t)b * a.ysz : a.x + (size_t)b * L;
     float4 v[FILE_TRIPS];
+    load_quads<FILE_TRIPS>(src, (unsigned)seg * FILE_SEG, len, v);
 #pragma unroll
     for (int t = 0; t < FILE_TRIPS; ++t) {
-        const unsigned i = (unsigned)seg * FILE_SEG + 4u * (t * 256 + threadIdx.x);
-        v[t] = file_quad(src + (i < len ? i : len - 4u));               // unconditional (a quad past the end re-reads the span's last one): no branch between the loads
-    }
-#pragma unroll
-    for (int t = 0; t < FILE_TRIPS; ++t) {
-        const unsigned i = (unsigned)seg * FILE_SEG + 4u * (t * 256 + threadIdx.x);
-        if (i < len) *reinterpret_cast<float4*>(dst + i) =      // len % 4 == 0: a quad lies inside the row or outside it
-            make_float4(v[t].x * sg, v[t].y * sg, v[t].z * sg, v[t].w * sg);
+        const unsigned i = quad_at((unsigned)seg * FILE_SEG, t);
+        if (i < len) *reinterpret_cast<float4*>(dst + i) = quad_sign(v[t], sg);
     }
     if (blockIdx.x == 0) {
         if ((int)threadIdx.x < a.K) a.knobs[(size_t)b * a.K + threadIdx.x] = a.file_knobs[(size_t)f * a.K + threadIdx.x];

@@ -11,9 +11,7 @@
 // this library.  The four scalar draws use indices 16 to 19 of the second, loop-free sequence of st_feed.h (integer hashes; datasets.live_feed_draw
 // is their host replica):   key2 = feed_key2(key),   h_i = mix32(key2 + 0x9E3779B9 i),   u_i = (h_i >> 8) / 2^24,   below(h, n) = (uint64 h * n) >> 32
 //   16  synthetic  iff u_16 < synth_prob (float32 compare): 0 = never, 1 = always
-//   17  file     = below(h_17, nfiles)                                      uniform over the files, not weighted by length
-//   18  start    = below(h_18, clamp(file_len[file] - L, 1, 2^31 - 1))      in [0, len - L): the last position is excluded, as np.random.randint excludes it
-//   19  flipped  = augment ? h_19 >> 31 : 0
+//   17, 18, 19  (file, start, flipped) = feed_span(h_17, h_18, h_19, ...)   (st_feed_files.h: THE SPAN CHOICE of every feed of recorded input)
 // Every window has all four draws, whatever it turns out to be; meta [B][4] = (synthetic, file, start, flipped) records them.
 // A RECORDED window is x[n] = +-pool[file_off[file] + start + n] (ST_PCM_S16: (float)s / 32767.0f, st_feed_files.h), minus where flipped.  It gets
 // neither the 1e-8 noise nor the random polarity of audio.py:334: those belong to synth_input_sample, and the reference's file dataset flips only
@@ -28,9 +26,9 @@
 // comp_apply_inplace_kernel finishes every row afterwards: comp_smooth_kernel works in place, so no row may pass it twice.
 // Every output row is a function of (seed, w) and the pool only, whatever the batching and whatever the other rows are.
 //
-// Addresses, as in st_file_feed: file < nfiles by construction; len - L is clamped to [1, 2^31 - 1] and off + start to [0, pool_samples - L], so
-// whatever the tables say every address formed lies inside the pool.  A span starts at ANY sample: the loads go through file_quad's vector types
-// declared with the element's alignment.  Destination rows are 16-byte aligned (L % 4 == ysz % 4 == 0): 16-byte stores.
+// Addresses, as in st_file_feed: feed_span's clamps keep every address formed inside the pool, whatever the tables say.  A span starts at ANY sample:
+// the loads go through load_quads / file_quad's vector types declared with the element's alignment.  Destination rows are 16-byte aligned
+// (L % 4 == ysz % 4 == 0): 16-byte stores.
 #pragma once
 #include "st_feed_files.h"
 
@@ -61,30 +59,17 @@ live_feed_kernel(const LiveFeedArgs a)
     // ---- the window's four scalar draws (law: top of this file)
     const unsigned key2 = feed_key2(key);
     const bool synthetic = u01(h2(key2, 16u)) < a.synth_prob;
-    const int f = below(h2(key2, 17u), a.nfiles);
-    long long span = a.file_len[f] - (long long)L;
-    span = span < 1 ? 1 : (span > 0x7fffffffLL ? 0x7fffffffLL : span);
-    long long base = a.file_off[f] + (long long)(((unsigned long long)h2(key2, 18u) * (unsigned long long)span) >> 32);
-    const long long top = a.pool_samples - (long long)L;
-    base = base < 0 ? 0 : (base > top ? top : base);
-    const bool flip = a.augment && (h2(key2, 19u) >> 31);
+    const auto [f, base, flip] = feed_span(h2(key2, 17u), h2(key2, 18u), h2(key2, 19u), a.file_off, a.file_len, a.nfiles, L, a.pool_samples, a.augment);
     if (a.meta && threadIdx.x == 64) {
         long long* m = a.meta + (size_t)b * 4;
         m[0] = synthetic ? 1 : 0; m[1] = f; m[2] = base - a.file_off[f]; m[3] = flip ? 1 : 0;
     }
     if (synthetic) return;                                           // workgroup-uniform: the row is synth_feed_kernel's
 
-    // ---- the knobs: the first draws of the first sequence, world values by the synthetic feed's rule (st_feed.h)
+    // ---- the knobs: the first draws of the first sequence, world values by the synthetic feed's rule (st_feed.h: feed_knobs)
     Draw d{key, 0u};
     float kn[4], kw[4];
-    for (int k = 0; k < 4; ++k) { kn[k] = d.beta(0.8f) - 0.5f; kw[k] = a.lo[k] + (kn[k] + 0.5f) * (a.hi[k] - a.lo[k]); }
-    for (int k = a.K; k < 4; ++k) kw[k] = a.lo[k];
-    if (FX == ST_FX_LOWPASS || FX == ST_FX_DENOISE) kw[0] = world_knob_f32(a.lo[0], a.hi[0], kn[0]);
-    if (FX == ST_FX_ECHO) {
-        kw[0] = rintf(world_knob_f32(a.lo[0], a.hi[0], kn[0]));
-        kw[1] = world_knob_f32(a.lo[1], a.hi[1], kn[1]);
-        kw[2] = rintf(world_knob_f32(a.lo[2], a.hi[2], kn[2]));
-    }
+    feed_knobs<FX>(d, a.lo, a.hi, a.K, kn, kw);
 
     // ---- the window: LIVE_TRIPS quads per lane and trip, all loads before the first store; with the second-launch form of the effect the static
     // gain curve of each sample right away, from the value in registers
@@ -96,29 +81,18 @@ live_feed_kernel(const LiveFeedArgs a)
     const unsigned len = (unsigned)L, tail = (unsigned)(L - a.ysz);
     for (unsigned i0 = 0; i0 < len; i0 += 4u * 256u * LIVE_TRIPS) {
         float4 q[LIVE_TRIPS];
+        load_quads<LIVE_TRIPS>(src, i0, len, q);
 #pragma unroll
         for (int t = 0; t < LIVE_TRIPS; ++t) {
-            const unsigned i = i0 + 4u * (t * 256 + threadIdx.x);
-            q[t] = file_quad(src + (i < len ? i : len - 4u));          // unconditional (a quad past the end re-reads the span's last one)
-        }
-#pragma unroll
-        for (int t = 0; t < LIVE_TRIPS; ++t) {
-            const unsigned i = i0 + 4u * (t * 256 + threadIdx.x);
+            const unsigned i = quad_at(i0, t);
             if (i >= len) continue;                                  // L % 4 == 0: a quad lies inside the row or outside it
-            float4 v = make_float4(q[t].x * sg, q[t].y * sg, q[t].z * sg, q[t].w * sg);
+            float4 v = quad_sign(q[t], sg);
             if (FX == ST_FX_DENOISE || FX == ST_FX_DECOMP4C) {       // the target is the clean tail (ysz % 4 == 0: whole quads) ...
                 if (i >= tail) *reinterpret_cast<float4*>(yb + (i - tail)) = v;
             }
-            if (FX == ST_FX_DENOISE) {                               // ... and the input leaves with the noise on it
-                v = make_float4(denoise_add(key, i, kw[0], v.x), denoise_add(key, i + 1u, kw[0], v.y),
-                                denoise_add(key, i + 2u, kw[0], v.z), denoise_add(key, i + 3u, kw[0], v.w));
-            }
+            if (FX == ST_FX_DENOISE) v = denoise_add4(key, i, kw[0], v);      // ... and the input leaves with the noise on it
             *reinterpret_cast<float4*>(xb + i) = v;
-            if (gcb) {
-                if (FX == ST_FX_COMP) *reinterpret_cast<float4*>(gcb + i) = make_float4(stm::env_db(v.x), stm::env_db(v.y), stm::env_db(v.z), stm::env_db(v.w));
-                else *reinterpret_cast<float4*>(gcb + i) = make_float4(stm::comp_gain_curve(v.x, (double)kw[0], (double)kw[1]), stm::comp_gain_curve(v.y, (double)kw[0], (double)kw[1]),
-                                                                       stm::comp_gain_curve(v.z, (double)kw[0], (double)kw[1]), stm::comp_gain_curve(v.w, (double)kw[0], (double)kw[1]));
-            }
+            if (gcb) *reinterpret_cast<float4*>(gcb + i) = FX == ST_FX_COMP ? env_db4(v) : comp_gain_curve4(v, kw[0], kw[1]);
         }
     }
     if (threadIdx.x == 0) { for (int k = 0; k < 4; ++k) if (k < a.K) a.knobs[(size_t)b * a.K + k] = kn[k]; }

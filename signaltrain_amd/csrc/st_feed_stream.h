@@ -22,7 +22,7 @@
 // A synthetic row (synth_prob > 0) has no history: row w of st_synth_effect_families, bit for bit, as in st_live_feed.  A recorded row depends on
 // (seed, w), the pool and preroll only -- not on synth_prob, the batching or the other rows.
 //
-// Addresses: st_live_feed's clamps first (file < nfiles, off + start in [0, pool_samples - L]), then start = clamp(base - file_off[file], 0, base) and R from
+// Addresses: feed_span's clamps first (st_feed_files.h: file < nfiles, off + start in [0, pool_samples - L]), then start = clamp(base - file_off[file], 0, base) and R from
 // that, so base - R >= 0: whatever the tables say, every address formed lies inside the pool, and with truthful tables the history never leaves the window's file.
 //
 // HOW IT RUNS.  One 256-lane workgroup per window, quads loaded before the first store, file_quad for unaligned spans, as live_feed_kernel.  The scratch holds
@@ -62,13 +62,7 @@ stream_feed_kernel(const StreamFeedArgs s)
     // ---- the window's four scalar draws: st_live_feed's, clamps included
     const unsigned key2 = feed_key2(key);
     const bool synthetic = u01(h2(key2, 16u)) < a.synth_prob;
-    const int f = below(h2(key2, 17u), a.nfiles);
-    long long span = a.file_len[f] - (long long)L;
-    span = span < 1 ? 1 : (span > 0x7fffffffLL ? 0x7fffffffLL : span);
-    long long base = a.file_off[f] + (long long)(((unsigned long long)h2(key2, 18u) * (unsigned long long)span) >> 32);
-    const long long top = a.pool_samples - (long long)L;
-    base = base < 0 ? 0 : (base > top ? top : base);
-    const bool flip = a.augment && (h2(key2, 19u) >> 31);
+    const auto [f, base, flip] = feed_span(h2(key2, 17u), h2(key2, 18u), h2(key2, 19u), a.file_off, a.file_len, a.nfiles, L, a.pool_samples, a.augment);
     const long long start = base - a.file_off[f];
     if (a.meta && threadIdx.x == 64) {
         long long* m = a.meta + (size_t)b * 4;
@@ -83,17 +77,10 @@ stream_feed_kernel(const StreamFeedArgs s)
     const long long hist = sc & ~3LL;
     const int R = FX == ST_FX_DENOISE ? 0 : (int)(hist < (long long)s.preroll ? hist : (long long)s.preroll);
 
-    // ---- the knobs: st_live_feed's
+    // ---- the knobs: st_live_feed's (st_feed.h: feed_knobs)
     Draw d{key, 0u};
     float kn[4], kw[4];
-    for (int k = 0; k < 4; ++k) { kn[k] = d.beta(0.8f) - 0.5f; kw[k] = a.lo[k] + (kn[k] + 0.5f) * (a.hi[k] - a.lo[k]); }
-    for (int k = a.K; k < 4; ++k) kw[k] = a.lo[k];
-    if (FX == ST_FX_LOWPASS || FX == ST_FX_DENOISE) kw[0] = world_knob_f32(a.lo[0], a.hi[0], kn[0]);
-    if (FX == ST_FX_ECHO) {
-        kw[0] = rintf(world_knob_f32(a.lo[0], a.hi[0], kn[0]));
-        kw[1] = world_knob_f32(a.lo[1], a.hi[1], kn[1]);
-        kw[2] = rintf(world_knob_f32(a.lo[2], a.hi[2], kn[2]));
-    }
+    feed_knobs<FX>(d, a.lo, a.hi, a.K, kn, kw);
 
     // ---- the extended span: LIVE_TRIPS quads per lane and trip, all loads before the first store; the window's part goes to x (and y), the whole of it,
     // as samples or as their static gain, into the row's right-aligned place in buf
@@ -111,19 +98,14 @@ stream_feed_kernel(const StreamFeedArgs s)
     const float sg = flip ? -1.f : 1.f;
     for (unsigned i0 = 0; i0 < len; i0 += 4u * 256u * LIVE_TRIPS) {
         float4 q[LIVE_TRIPS];
+        load_quads<LIVE_TRIPS>(src, i0, len, q);
 #pragma unroll
         for (int t = 0; t < LIVE_TRIPS; ++t) {
-            const unsigned i = i0 + 4u * (t * 256 + threadIdx.x);
-            q[t] = file_quad(src + (i < len ? i : len - 4u));          // unconditional (a quad past the end re-reads the span's last one)
-        }
-#pragma unroll
-        for (int t = 0; t < LIVE_TRIPS; ++t) {
-            const unsigned i = i0 + 4u * (t * 256 + threadIdx.x);
+            const unsigned i = quad_at(i0, t);
             if (i >= len) continue;                                  // len % 4 == 0: a quad lies inside the span or outside it
-            float4 v = make_float4(q[t].x * sg, q[t].y * sg, q[t].z * sg, q[t].w * sg);
+            float4 v = quad_sign(q[t], sg);
             if (GAIN) {
-                float4 g = make_float4(stm::comp_gain_curve(v.x, (double)kw[0], (double)kw[1]), stm::comp_gain_curve(v.y, (double)kw[0], (double)kw[1]),
-                                       stm::comp_gain_curve(v.z, (double)kw[0], (double)kw[1]), stm::comp_gain_curve(v.w, (double)kw[0], (double)kw[1]));
+                float4 g = comp_gain_curve4(v, kw[0], kw[1]);
                 if (i == 0u) g.x = 0.f;                              // lin_A[0] = 0 at the span's true first sample
                 *reinterpret_cast<float4*>(eb + i) = g;
             } else if (FX != ST_FX_DENOISE) {
@@ -134,10 +116,7 @@ stream_feed_kernel(const StreamFeedArgs s)
             if (FX == ST_FX_DENOISE || FX == ST_FX_DECOMP4C) {       // the target is the clean tail
                 if (j >= tail) *reinterpret_cast<float4*>(yb + (j - tail)) = v;
             }
-            if (FX == ST_FX_DENOISE) {                               // the noise index is relative to the window
-                v = make_float4(denoise_add(key, j, kw[0], v.x), denoise_add(key, j + 1u, kw[0], v.y),
-                                denoise_add(key, j + 2u, kw[0], v.z), denoise_add(key, j + 3u, kw[0], v.w));
-            }
+            if (FX == ST_FX_DENOISE) v = denoise_add4(key, j, kw[0], v);      // the noise index is relative to the window
             *reinterpret_cast<float4*>(xb + j) = v;
         }
     }
