@@ -197,6 +197,27 @@ int st_nt128_worklist(const st_dims* d, int which, int ncus, unsigned* out, int 
  * at these dims (16-bit or split operands, wide autoencoder geometries, N % 256 != 0, st_set_tuning(9582)), < 0 on bad arguments. */
 int st_wgrad_pair_plan(const st_dims* d, int ncus, int* out, int cap);
 
+/* Diagnostics, host only: what ONE weight-gradient GEMM and the sum of its k-slice slabs do at these dims -- the plan the launches themselves ask for, so with
+ * ncus <= 0 (the current device's CU count) exactly what a launch on this device does under the current tuning state; with ncus > 0 a pure function of its
+ * arguments and the tuning state.  which: 0 = the analysis bases, 1 = the synthesis bases.  half: -1 = the whole tensor, 0 / 1 = the real / imaginary basis alone
+ * (analysis only: the split exchange of st_dp_train_step, stages 2 / 3 of st_loss_backward_stage).  flags: ST_WGPLAN_PADDED = operands in the padded workspace
+ * layout (every fused entry; 0 = st_analysis_wgrad / st_synthesis_wgrad), ST_WGPLAN_G16 = the entry asks for the 16-bit operand pipeline (the training and
+ * validation entries; taken where the precision admits it; needs ST_WGPLAN_PADDED), ST_WGPLAN_STAGED = st_loss_backward_stage, whose one-basis launches keep
+ * the 96 x 96 kernel.  out receives min(cap, ST_WGRAD_PLAN_INTS) ints in the order of the ST_WGP_* indices:
+ *   FORM      0 = the 128 x 128 fp32 kernel, 1 = the 96 x 96 three-wave kernel, 2 = the 16-bit kernel
+ *   R         live reduction rows: B x the frames with a tap inside the unpadded signal
+ *   SLICES    k-slices = slabs [KP][N] written at the start of the area
+ *   M0, M     output rows [M0, M0 + M) of each slab (KP rows for the whole tensor, KP / 2 for one basis)
+ *   FRAME_MAJOR, TRIM   reduction rows enumerated frame-major; per tile column only the rows that carry a tap inside the signal
+ *   NYQ_P, NYQ_OFF, NYQ_WRITE   the slab sum reads NYQ_P Nyquist partials [2][N] at float offset NYQ_OFF of the area (0: the slabs hold those rows); 1 = this
+ *             launch writes them (the real basis' launch writes them for both)
+ *   USED      floats of the area the launch and its slab sum touch: never more than st_wgrad_ws_floats(d)
+ * Returns ST_WGRAD_PLAN_INTS; < 0 on bad arguments (unsupported dims, which / half / flags out of range, one basis of the synthesis pair, cap < 0). */
+enum { ST_WGPLAN_PADDED = 1, ST_WGPLAN_G16 = 2, ST_WGPLAN_STAGED = 4 };
+enum { ST_WGP_FORM = 0, ST_WGP_R, ST_WGP_SLICES, ST_WGP_M0, ST_WGP_M, ST_WGP_FRAME_MAJOR, ST_WGP_TRIM, ST_WGP_NYQ_P, ST_WGP_NYQ_OFF, ST_WGP_NYQ_WRITE, ST_WGP_USED,
+       ST_WGRAD_PLAN_INTS };
+int st_wgrad_plan(const st_dims* d, int which, int half, int flags, int ncus, int* out, int cap);
+
 /* Diagnostics, host only: 1 if the frame-major row order may be used for a GEMM with R = (live frames) * B compact rows, i.e. if the kernels' division of a
  * row index r < R by B through a multiply-high with floor(2^32 / B) + 1 is exact (r * B < 2^32 for every r); 0: those launches keep the window-major order
  * and the untrimmed / uncropped tile sets.  (cls_fe_dft.py:28-31, :112-113: the trimming is an optimisation of the padded / cropped frames, never a

@@ -375,16 +375,52 @@ static int ae_bwd_grid(const st_dims* d) { int groups = d->B * (st_kp_of(d->F) /
 // 121-tile weight-gradient GEMMs get there by splitting K and summing the slabs in the consumer kernel.
 static const int WSPLIT_ROWS = 200, WSPLIT_MAX = 16;      // reduction rows per weight-gradient k-slice, and the cap of the slice count
 static int wgrad_split(int R) { int s = R / WSPLIT_ROWS; if (s < 1) s = 1; if (s > WSPLIT_MAX) s = WSPLIT_MAX; return s; }
-// ... and never more k-slices than keep all workgroups co-resident: the 3-wave weight-gradient workgroup (25 KB of LDS, 95 registers)
-// fits six to a CU, and a second, partly filled round costs more than the shorter k-chains save (measured sawtooth at B = 256,
-// 121 tiles: 10 / 12 / 16 slices -> 151 / 153 / 160 us incl. the slab reduce; 11, 13 -> 160, 169)
-static int wgrad_split_tiles(int R, int M, int Nc)
+// The k-slice count of a weight-gradient GEMM: ONE function for the three kernel forms, each over the whole tensor (M = KP output rows) or over one basis of the
+// analysis pair (M = KP / 2), so six rules side by side.  R: live reduction rows.  room: slabs the workspace area holds once its Nyquist partials are set aside
+// (wgrad_area_slabs): no rule exceeds it.  The two whole-tensor fp32 rules are what the area is sized by (over all B * T frames, on the device's CU count), so
+// there the cap binds only when a query assumes more CUs than the device has.  ncus > 0 makes the function pure given its arguments (the host queries);
+// otherwise the current device's CU count.
+enum { WG_TN128 = 0, WG_96 = 1, WG_TN16 = 2 };      // the 128 x 128 TN kernel (st_gemm_tn.h), the 96 x 96 three-wave kernel behind ST_GEMM_WG, the 16-bit TN kernel (st_gemm16.h)
+static int wgrad_slices(int form, bool one_basis, int R, int KP, int N, int room, int ncus = 0)
 {
-    int s = wgrad_split(R);
-    const int tiles = ((M + 95) / 96) * ((Nc + 95) / 96), slots = 6 * num_cus();
-    int fit = slots / (tiles > 0 ? tiles : 1); if (fit < 1) fit = 1;
-    if (fit >= 2) fit &= ~1;                       // even slice counts: odd ones leave a ragged last slice (k-slices are multiples of 32 rows)
-    return s < fit ? s : fit;
+    const int cus = ncus > 0 ? ncus : num_cus(), M = one_basis ? KP / 2 : KP;
+    auto per_tiles = [](int n, int tiles) { return n / (tiles > 0 ? tiles : 1); };
+    int s;
+    if (form == WG_TN128) {
+        // as many slices as fill the CUs with one workgroup each, never slices shorter than 64 reduction rows.  One basis: half the tiles, so each half
+        // fills the chip with twice the k-slices of the whole-tensor launch and the two launches together do the work of the one
+        s = per_tiles(cus, (one_basis ? (N / 2) / 128 : N / 128) * (N / 128)); if (s > 16) s = 16;
+        if (s > R / 64) s = R / 64;
+        if (one_basis && s > room) s = room;
+    } else if (form == WG_TN16) {
+        // about two workgroups per CU (their time is staging, not matrix work), never slices under 128 reduction rows, never more slabs than the workspace holds
+        s = per_tiles(2 * cus, ((M + 127) / 128) * (N / 128));
+        if (s > R / 128) s = R / 128;
+        if (s > room) s = room;
+    } else {
+        // never more k-slices than keep all workgroups co-resident: the 3-wave weight-gradient workgroup (25 KB of LDS, 95 registers)
+        // fits six to a CU, and a second, partly filled round costs more than the shorter k-chains save (measured sawtooth at B = 256,
+        // 121 tiles: 10 / 12 / 16 slices -> 151 / 153 / 160 us incl. the slab reduce; 11, 13 -> 160, 169)
+        s = wgrad_split(R);
+        int fit = per_tiles(6 * cus, ((KP + 95) / 96) * ((N + 95) / 96)); if (fit < 1) fit = 1;
+        if (fit >= 2) fit &= ~1;                       // even slice counts: odd ones leave a ragged last slice (k-slices are multiples of 32 rows)
+        if (fit < s) s = fit;
+        if (one_basis) {
+            // One-basis GEMM: 6 x 11 tiles of 96 x 96, one 3-wave workgroup per CU at a time, so the run time goes with
+            // ceil(tiles * ns / CUs) / ns (measured sawtooth, B=256: ns = 7, 11, 15 are the minima, 8 / 12 / 16 cost +40..60 us).
+            // Pick the split in [ns/2, ns] that fills its last round best; never above the slab count the workspace holds.
+            const int tiles = ((M + 95) / 96) * ((N + 95) / 96);
+            int best = s; double bf = -1.0;
+            for (int c = s; c >= (s + 1) / 2 && c >= 1; --c) {
+                const int w = tiles * c, rounds = (w + cus - 1) / cus;
+                const double f = (double)w / ((double)rounds * cus);
+                if (f > bf + 1e-9) { bf = f; best = c; }
+            }
+            s = best;
+        }
+    }
+    if (s > room) s = room;      // every form, whatever CU count is assumed: never more slabs than the workspace area holds
+    return s < 1 ? 1 : s;
 }
 static int synth_split(int R) { return R >= 4096 ? 1 : 3; }   // consumers (ola_loss_kernel, ae_bwd_kernel) sum at most 3 slabs
 static int dgrad_slabs(int R) { return synth_split(R); }      // split-K slabs of the synthesis data-gradient GEMM over R live rows
@@ -397,27 +433,21 @@ static int norm_partials(const st_dims* d) { return stm::norm_partial_count(d->F
 extern "C" int st_ae_fwd_partials(const st_dims* d) { return check_dims(d) != ST_OK ? 0 : ae_fwd_partials(d); }
 extern "C" int st_ola_loss_partials(const st_dims* d) { return check_dims(d) != ST_OK ? 0 : ola_loss_partials(d); }
 extern "C" int st_norm_partials(const st_dims* d) { return check_dims(d) != ST_OK ? 0 : norm_partials(d); }
-// k-slices of the 128 x 128-tile weight-gradient GEMM (st_gemm_tn.h): as many as fill the CUs with one workgroup each, never slices
-// shorter than 64 reduction rows
-static int tn_split(int R, int N, int ncus = 0)      // ncus > 0: a pure function of its arguments (st_wgrad_pair_plan)
+// The slab area of the weight-gradient GEMMs: room for the larger of the two whole-tensor fp32 rules over ALL B * T frames (the live rows of either GEMM are
+// no more), then 64 Nyquist partials [2][N] of the 128 x 128-tile form.  What every launch must keep (tests/test_wgrad_plan_host.py): its slabs, and behind
+// them its Nyquist partials, fit this area -- for every batch, precision, half and kernel form.
+static const int WGRAD_NYQ_MAX = 64;
+static int wgrad_area_slabs(const st_dims* d)      // always by the device's own CU count: the area is what the caller allocated, whatever count a query assumes
 {
-    const int tiles = (N / 128) * (N / 128);
-    int s = (ncus > 0 ? ncus : num_cus()) / (tiles > 0 ? tiles : 1); if (s > 16) s = 16;
-    const int cap = R / 64; if (s > cap) s = cap;
-    return s < 1 ? 1 : s;
+    const int KP = st_kp_of(d->F), R = d->B * d->T, unbounded = 1 << 30;      // the two rules that size the area, before any area bounds them
+    const int s = wgrad_slices(WG_96, false, R, KP, d->N, unbounded), s2 = wgrad_slices(WG_TN128, false, R, KP, d->N, unbounded);
+    return s2 > s ? s2 : s;
 }
 static size_t wgrad_ws_floats(const st_dims* d)
 {
-    int s = wgrad_split_tiles(d->B * d->T, st_kp_of(d->F), d->N);
-    const int s2 = tn_split(d->B * d->T, d->N); if (s2 > s) s = s2;
-    return (size_t)s * st_kp_of(d->F) * d->N + (size_t)64 * 2 * d->N;       // + the Nyquist partials of the 128 x 128-tile form
+    return (size_t)wgrad_area_slabs(d) * st_kp_of(d->F) * d->N + (size_t)WGRAD_NYQ_MAX * 2 * d->N;
 }
 extern "C" size_t st_wgrad_ws_floats(const st_dims* d) { return check_dims(d) != ST_OK ? 0 : wgrad_ws_floats(d); }
-// Round 6: a second slab area for the SYNTHESIS weight gradient alone.  In the data-parallel step its slabs are summed on the communicator stream beside the autoencoder
-// backward; with a buffer of their own the analysis weight-gradient GEMM (which reuses the first area) needs no communicator -> compute wait before it starts -- one
-// barrier packet (~6 us of bubble on this stack) less on the compute stream.  Same size as the first: every slab-count rule of the fp32 and 16-bit weight-gradient
-// launches is capped by that area's size.
-static size_t synth_wgrad_ws_floats(const st_dims* d) { return wgrad_ws_floats(d); }
 static int synth_slabs(const st_dims* d) { return dgrad_slabs(synth_live_rows(d)); }
 extern "C" int st_synth_slabs(const st_dims* d) { return check_dims(d) != ST_OK ? 0 : synth_slabs(d); }
 // split-K slabs of the synthesis FRAMES GEMM (summed by ola_loss_kernel, which takes up to 6; the dgrad slabs are summed
@@ -801,75 +831,122 @@ static TNFrameMajor tn_frame_major(const stg::TNOperand& ta, const stg::TNOperan
 }
 // g_tn128 == 2: the round-3 k-tile loop (st_set_tuning(9580)); otherwise the pipelined one (st_gemm_tn.h, round 7)
 #define ST_TN128(...) do { if (g_tn128 == 2) ST_TRY((stg::launch_tn128<32, false>(__VA_ARGS__))); else ST_TRY((stg::launch_tn128<32, true>(__VA_ARGS__))); } while (0)
-// The two weight-gradient GEMMs as problems of the 128 x 128-tile kernel -- operands in the padded workspace layout, the live rows (frame-major where that applies,
-// with the per-tile-column row ranges), the k-slice count -- stated once for the per-GEMM launches, the pair launch and its plan query.  fits: the kernel applies.
-struct TNProblem { stg::TNOperand a, b; const float* zeros; stg::RowMap map; stg::FrameTrim trim; int R, ns; bool fits; };
-static TNProblem tn_problem(const st_dims* d, const stg::TNOperand& ta, const stg::TNOperand& tb, const stg::RowMap& live, size_t extentA, int Ls, int fm_bit, bool padded, int ncus)
+// ------------------------------------------------------------------------------ the weight-gradient GEMMs: plan, launch, slab sum
+// Everything ONE weight-gradient GEMM and the sum of its slabs need, decided in one place (wgrad_plan; it launches nothing) for the per-op entries, the fused
+// steps, the staged and data-parallel schedules, the pair launch and the host queries (st_wgrad_plan, st_wgrad_pair_plan).
+// which: 0 = the analysis bases (A = d G, B = the padded x / 2, L samples): taps of the partly padded frames (Conv1d padding, cls_fe_dft.py:28-31) are zeros;
+//        1 = the synthesis bases (A = the spectra, B = the padded d syn, y samples): taps of d syn's frames outside the crop are zeros.
+// half = -1: both bases in one GEMM (M = KP output rows = columns of A); 0 / 1: only the real / imaginary basis of the analysis pair (rows [m0, m0 + KP / 2)),
+// so that in data parallel the first basis' all-reduce runs under the second basis' GEMM (st_loss_backward_stage; st_dp_train_step, exchange flag 2: only F * N
+// values -- 2.1 MB; 1.05 MB bf16-packed -- stay exposed behind the last GEMM of the step).
+enum { WGP_PADDED = 1,         // operands in the padded workspace layout (the fused entries); else the per-op entries' unpadded signal
+       WGP_G16 = 2,            // the call runs the 16-bit operand pipeline (WS::g16)
+       WGP_HALVES_96 = 4 };    // st_loss_backward_stage: its one-basis launches stay on the 96 x 96 form (st_dp_train_step's take the 128 x 128 one where it applies)
+struct WgOps { const float *A, *B; const unsigned short *A16, *B16; float in_scale; };      // in_scale: the per-op analysis entry's signal is x, not x / 2
+struct WgradPlan {
+    const st_dims* d; WgOps o; float* area;            // area: the slabs [ns][KP][N], the Nyquist partials behind them (st_wgrad_ws_floats)
+    int which, half, flags, form, R, ns, m0, M, Ls;    // form: WG_*; R: live reduction rows; ns: k-slices = slabs; output rows [m0, m0 + M); Ls: samples of B's signal
+    unsigned SA1, SB1; size_t slab;                    // window strides of the padded operands; slab stride
+    stg::RowMap live;                                  // the frames with a tap inside the signal, window-major (all-zero frames contribute nothing)
+    bool frame_major; stg::FrameTrim trim;             // round 5: reduction rows enumerated frame-major, and (trim.on) only the rows each tile column needs
+    // The rows the 128-row tiles do not cover (the Nyquist bin of each basis).  nyq_P > 0: the slab sum takes them from nyq_P partials [2][N] at area + nyq_off
+    // (whole tensor: right behind its ns slabs; one basis: behind all the slabs the area holds, where both halves find them); nyq_write: this launch forms them
+    // (half 0 for BOTH bases -- its A origin is column 0 --, half 1 has no Nyquist slice)
+    int nyq_P; size_t nyq_off; bool nyq_write;
+    stg::TNOperand a, b; stg::RowMap map; stg::TNLaunch tn;      // WG_TN128: operands and rows as the kernel takes them, and its job (the pair launch joins two)
+    size_t used() const { const size_t s = (size_t)ns * slab, q = nyq_P > 0 ? nyq_off + (size_t)nyq_P * 2 * d->N : 0; return s > q ? s : q; }
+    stm::NyqJob nyq() const { stm::NyqJob q{}; q.on = nyq_P > 0 ? 1 : 0; if (q.on) { q.part = area + nyq_off; q.P = nyq_P; } return q; }
+};
+static WgradPlan wgrad_plan(const st_dims* d, int which, int half, int flags, const WgOps& o, float* area, int ncus = 0)
 {
-    TNProblem p; p.zeros = tb.base; p.R = live.rows(d->B);
-    p.fits = use_tn128(d, padded) && stg::tn128_fits(ta, tb, tb.base, live, d->N, d->N, extentA, (size_t)d->B * (Ls + 2 * d->N));
-    p.ns = tn_split(p.R, d->N, ncus);
-    const TNFrameMajor fm = tn_frame_major(ta, tb, live, d->B, d->H, d->N, d->N, Ls, (g_tn_fm & fm_bit) != 0);
-    p.a = fm.a; p.b = fm.b; p.map = fm.map; p.trim = fm.trim;
+    const int KP = st_kp_of(d->F), N = d->N, Tf = which ? d->OT : d->T, room = wgrad_area_slabs(d);
+    WgradPlan p; p.d = d; p.o = o; p.area = area; p.which = which; p.half = half; p.flags = flags;
+    p.Ls = which ? d->y : d->L; p.live = stg::live_frames(Tf, d->H, N, N, p.Ls); p.R = p.live.rows(d->B);
+    p.M = half < 0 ? KP : KP / 2; p.m0 = half > 0 ? KP / 2 : 0; p.slab = (size_t)KP * N;
+    p.SA1 = (unsigned)(Tf * KP); p.SB1 = (unsigned)(p.Ls + 2 * N);
+    const stg::TNOperand ta{o.A + p.m0, p.SA1, (unsigned)KP}, tb{o.B, p.SB1, (unsigned)d->H};
+    const int Mt = half < 0 ? N : N / 2;               // rows the 128-row tiles cover: the F - 1 non-Nyquist bins of each basis
+    if (flags & WGP_G16) p.form = WG_TN16;
+    else p.form = (use_tn128(d, (flags & WGP_PADDED) != 0) && !(half >= 0 && (flags & WGP_HALVES_96)) &&
+                   stg::tn128_fits(ta, tb, tb.base, p.live, Mt, N, (size_t)d->B * Tf * KP, (size_t)d->B * p.SB1)) ? WG_TN128 : WG_96;
+    p.ns = wgrad_slices(p.form, half >= 0, p.R, KP, N, room, ncus);
+    const bool fm = p.form == WG_TN128 ? (g_tn_fm & (which ? 1 : 2)) != 0 : p.form == WG_TN16 && (g_g16_crop & (which ? 4 : 8)) != 0;
+    const TNFrameMajor f = tn_frame_major(ta, tb, p.live, d->B, d->H, N, N, p.Ls, fm);
+    p.frame_major = f.on; p.trim = f.trim; p.a = f.a; p.b = f.b; p.map = f.map;
+    p.nyq_P = 0; p.nyq_off = 0; p.nyq_write = false;
+    if (p.form == WG_TN128) {
+        p.nyq_off = (size_t)(half < 0 ? p.ns : room) * p.slab; p.nyq_write = half <= 0;
+        p.tn = stg::tn128_job(32, p.a, p.b, tb.base, p.map, p.R, Mt, (N / 2) / 128, (unsigned)(KP / 2), N, area + (size_t)p.m0 * N, N, p.slab, p.ns,
+                              p.nyq_write ? area + p.nyq_off : nullptr, (unsigned)(d->F - 1), (unsigned)(KP / 2 + d->F - 1), nullptr, &p.trim);
+        p.nyq_P = p.tn.j.nyq_P;
+    }
     return p;
 }
-// synthesis (A = the spectra, B = the padded d syn): taps of d syn's frames outside the crop are zeros, skipped per tile column
-static TNProblem synthesis_tn_problem(const st_dims* d, const float* AA, const float* dsyn, bool padded, int ncus = 0)
+// WG_TN16.  A: [rows (b, t)][KP] 16-bit (d G or the spectra), B: frames of a padded 16-bit signal whose first N elements are zero (the block of zeros)
+static int wgrad_gemm16(const WgradPlan& p, void* stream)
 {
-    const int KP = st_kp_of(d->F);
-    const stg::TNOperand ta{AA, (unsigned)(d->OT * KP), (unsigned)KP}, tb{dsyn, (unsigned)(d->y + 2 * d->N), (unsigned)d->H};
-    return tn_problem(d, ta, tb, synth_live(d), (size_t)d->B * d->OT * KP, d->y, 1, padded, ncus);
+    const st_dims* d = p.d; const stg::RowMap& map = p.live;
+    const int KP = st_kp_of(d->F), R = p.R;
+    const unsigned short *A = p.o.A16, *Bsig = p.o.B16, *lo = A < Bsig ? A : Bsig;
+    const unsigned SA1 = p.SA1, SB1 = p.SB1;
+    ST_REQ((size_t)(A - lo) + (size_t)R / map.Tv * SA1 + 256 < ((size_t)1 << 30) && (size_t)(Bsig - lo) + (size_t)R / map.Tv * SB1 + 256 < ((size_t)1 << 30) && map.Tv >= 2 &&
+           SA1 < (1u << 23) && SB1 < (1u << 23), "16-bit weight-gradient GEMM: operands out of the 32-bit / 24-bit addressing range (B=%d)", d->B);
+    stg::TN16Job j;
+    j.base = lo; j.a0 = (unsigned)(A - lo) + (unsigned)p.m0; j.b0 = (unsigned)(Bsig - lo); j.zero = j.b0;
+    j.SA1 = SA1; j.SA2 = (unsigned)KP; j.SB1 = SB1; j.SB2 = (unsigned)d->H;
+    j.magic = map.magic; j.Tv = map.Tv; j.t_lo = map.t_lo; j.K = R;
+    j.trim = 0; j.fB = 0; j.nsplit = 1;
+    for (int i = 0; i < 64; ++i) { j.fa[i] = 0; j.fb[i] = 0; }
+    if (p.frame_major) {
+        // (outer, inner) = (frame, window): the strides swap roles, the origins move to frame t_lo (the zero block stays where it is)
+        j.a0 += (unsigned)map.t_lo * (unsigned)KP; j.b0 += (unsigned)map.t_lo * (unsigned)d->H;
+        j.SA1 = (unsigned)KP; j.SA2 = SA1; j.SB1 = (unsigned)d->H; j.SB2 = SB1;
+        j.magic = stg::rowmap_magic(d->B); j.Tv = d->B; j.t_lo = 0;
+        j.trim = p.trim.on; j.fB = d->B;
+        for (int i = 0; i < 64; ++i) { j.fa[i] = p.trim.fa[i]; j.fb[i] = p.trim.fb[i]; }
+    }
+    stg::StoreC ep{p.area + (size_t)p.m0 * d->N, p.M, d->N, d->N, p.slab, stg::all_frames(1)};
+    return with_ht16(gemm_ht(d->prec), [&](auto HT) { return stg::launch16_tn<HT(), 64>(j, ep, p.M, d->N, p.ns, st_stream(stream)); });
 }
-// analysis (A = d G, B = the padded x / 2): taps of the partly padded frames (Conv1d padding, cls_fe_dft.py:28-31) are zeros, skipped per tile column
-static TNProblem analysis_tn_problem(const st_dims* d, const float* dG, const float* sig, bool padded, int ncus = 0)
+// The GEMM of a plan, whatever its form, into the plan's slabs
+static int wgrad_gemm(const WgradPlan& p, void* stream)
 {
-    const int KP = st_kp_of(d->F);
-    const stg::TNOperand ta{dG, (unsigned)(d->T * KP), (unsigned)KP}, tb{sig, (unsigned)(d->L + 2 * d->N), (unsigned)d->H};
-    return tn_problem(d, ta, tb, stg::live_frames(d->T, d->H, d->N, d->N, d->L), (size_t)d->B * d->T * KP, d->L, 2, padded, ncus);
-}
-static int wgrad_tn128(const st_dims* d, const stg::TNOperand& ta, const stg::TNOperand& tb, const float* zeros, const stg::RowMap& map, int R,
-                       float* ws, int ns, stm::NyqJob* nyq, void* stream, const stg::FrameTrim* trim)
-{
-    const int KP = st_kp_of(d->F);
-    const int mh = (d->N / 2) / 128;
-    // Nyquist partials [P][2][N] sit behind the ns slabs (st_wgrad_ws_floats reserves the room)
-    float* part = ws + (size_t)ns * KP * d->N;
-    int P = 0;
-    const unsigned c0 = (unsigned)(d->F - 1), c1 = (unsigned)(KP / 2 + d->F - 1);
-    ST_TN128(ta, tb, zeros, map, R, d->N, mh, (unsigned)(KP / 2), d->N, ws, d->N, (size_t)KP * d->N, ns, st_stream(stream), part, c0, c1, &P, trim);
-    nyq->part = part; nyq->P = P; nyq->on = 1;
+    const st_dims* d = p.d; const int KP = st_kp_of(d->F), N = d->N;
+    if (p.form == WG_TN128)
+        ST_TN128(p.a, p.b, p.o.B, p.map, p.R, p.tn.M, p.tn.j.mh, p.tn.j.mstride, N, p.tn.out, N, p.slab, p.ns, st_stream(stream),
+                 p.tn.j.nyq_out, p.tn.j.nyq_c0, p.tn.j.nyq_c1, nullptr, &p.trim);
+    else if (p.form == WG_TN16) ST_TRY(wgrad_gemm16(p, stream));
+    else {
+        stg::PlainTN al{p.o.A + p.m0, p.R, KP, p.M, p.live};
+        stg::StoreC ep{p.area + (size_t)p.m0 * N, p.M, N, N, p.slab, stg::all_frames(1)};
+        if (p.flags & WGP_PADDED) { stg::FramedTN<true> bl{p.o.B, p.Ls, d->H, N, p.R, N, 1.0f, p.live}; ST_GEMM_WG(al, bl, ep, p.M, N, p.R, p.ns, st_stream(stream)); }
+        else { stg::FramedTN<false> bl{p.o.B, p.Ls, d->H, N, p.R, N, p.o.in_scale, p.live}; ST_GEMM_WG(al, bl, ep, p.M, N, p.R, p.ns, st_stream(stream)); }
+    }
+    ST_LAUNCHED(p.which ? "synthesis_wgrad" : "analysis_wgrad");
     return ST_OK;
 }
-static int synthesis_wgrad_impl(const st_dims* d, const float* AA, const float* dsyn, bool padded, float* ws,
-                                float* gSr, float* gSi, float* norm_partial, void* stream, int* defer_slabs = nullptr, stm::NyqJob* defer_nyq = nullptr)
-{   // defer_slabs: the caller sums the slabs itself (post_ae_kernel); receives the slab count (and the Nyquist job)
-    const int KP = st_kp_of(d->F);
-    const stg::RowMap ms = synth_live(d);
-    const int R = ms.rows(d->B);
-    int ns = wgrad_split_tiles(R, KP, d->N);
-    stm::NyqJob nyq{}; nyq.on = 0;
-    const TNProblem tp = synthesis_tn_problem(d, AA, dsyn, padded);
-    if (tp.fits) {
-        ns = tp.ns;
-        ST_TRY(wgrad_tn128(d, tp.a, tp.b, tp.zeros, tp.map, R, ws, ns, &nyq, stream, &tp.trim));
-    } else {
-        stg::PlainTN al{AA, R, KP, KP, ms};
-        stg::StoreC ep{ws, KP, d->N, d->N, (size_t)KP * d->N, stg::all_frames(1)};
-        if (padded) { stg::FramedTN<true> bl{dsyn, d->y, d->H, d->N, R, d->N, 1.0f, ms}; ST_GEMM_WG(al, bl, ep, KP, d->N, R, ns, st_stream(stream)); }
-        else { stg::FramedTN<false> bl{dsyn, d->y, d->H, d->N, R, d->N, 1.0f, ms}; ST_GEMM_WG(al, bl, ep, KP, d->N, R, ns, st_stream(stream)); }
-    }
-    ST_LAUNCHED("synthesis_wgrad");
-    if (defer_slabs) { *defer_slabs = ns; if (defer_nyq) *defer_nyq = nyq; return ST_OK; }
-    hipLaunchKernelGGL(stm::wgrad_reduce_kernel, dim3(norm_partials(d)), dim3(256), 0, st_stream(stream),
-                       ws, ns, gSr, gSi, norm_partial, d->N, d->F, KP, 1, 0, 2 * d->F, (float*)nullptr, nyq);
-    ST_LAUNCHED("synthesis_wgrad_reduce");
+// The sum of a plan's slabs (and Nyquist partials) into the two gradient tensors, the |g| partials into `norm`, the live analysis rows also packed into `stage`
+// where given: the ONE place that spells out wgrad_reduce_kernel's arguments.  Grid: the gradient rows of this plan, then its share of the Nyquist blocks resp.
+// unused partial slots -- all of them for the whole tensor, each basis' own half for a one-basis plan.  On `s`: st_dp_train_step sums on its communicator stream.
+static void wgrad_reduce(const WgradPlan& p, float* gRe, float* gIm, float* norm, float* stage, int stage_bf16, hipStream_t s)
+{
+    const st_dims* d = p.d; const int F = d->F, per = stm::nyq_blocks(d->N) / 2;
+    const int nrows = p.half < 0 ? 2 * F : F, extra = p.half < 0 ? 2 * per : per;
+    hipLaunchKernelGGL(stm::wgrad_reduce_kernel, dim3(nrows + extra), dim3(256), 0, s,
+                       p.area, p.ns, gRe, gIm, norm, d->N, F, st_kp_of(F), p.which, p.half > 0 ? F : 0, nrows, stage, p.nyq(), p.half > 0 ? per : 0, stage_bf16);
+}
+static int wgrad_gemm_and_sum(const WgradPlan& p, float* gRe, float* gIm, float* norm, float* stage, int stage_bf16, void* stream)
+{
+    ST_TRY(wgrad_gemm(p, stream));
+    wgrad_reduce(p, gRe, gIm, norm, stage, stage_bf16, st_stream(stream));
+    ST_LAUNCHED(p.which ? "synthesis_wgrad_reduce" : "analysis_wgrad_reduce");
     return ST_OK;
 }
 extern "C" int st_synthesis_wgrad(const st_dims* d, const float* AA, const float* dsyn, float* ws,
                                   float* gSr, float* gSi, float* norm_partial, void* stream)
 {
     ST_TRY(check_dims(d)); ST_REQ(AA && dsyn && ws && gSr && gSi && norm_partial, "st_synthesis_wgrad: null pointer");
-    return synthesis_wgrad_impl(d, AA, dsyn, false, ws, gSr, gSi, norm_partial, stream);
+    return wgrad_gemm_and_sum(wgrad_plan(d, 1, -1, 0, WgOps{AA, dsyn, nullptr, nullptr, 1.0f}, ws), gSr, gSi, norm_partial, nullptr, 0, stream);
 }
 
 
@@ -1163,53 +1240,11 @@ extern "C" int st_polar_bwd(const st_dims* d, const float* re, const float* im, 
     ST_LAUNCHED("polar_bwd"); return ST_OK;
 }
 
-// half = -1: both bases in one GEMM (M = KP rows of dG^T); half = 0 / 1: only the real / imaginary basis (M = KP/2), so
-// that in data parallel the first half's all-reduce runs under the second half's GEMM (st_loss_backward_stage).
-static int analysis_wgrad_impl(const st_dims* d, const float* dG, const float* sig, bool padded, float in_scale, float* ws,
-                               float* gWr, float* gWi, float* norm_partial, void* stream, int half = -1, float* stage = nullptr, int stage_bf16 = 0)
-{
-    const int KP = st_kp_of(d->F);
-    const stg::RowMap ma = stg::live_frames(d->T, d->H, d->N, d->N, d->L);   // all-zero frames contribute nothing
-    const int R = ma.rows(d->B);
-    int ns = wgrad_split_tiles(R, KP, d->N);
-    if (half >= 0) {
-        // One-basis GEMM: 6 x 11 tiles of 96 x 96, one 3-wave workgroup per CU at a time, so the run time goes with
-        // ceil(tiles * ns / CUs) / ns (measured sawtooth, B=256: ns = 7, 11, 15 are the minima, 8 / 12 / 16 cost +40..60 us).
-        // Pick the split in [ns/2, ns] that fills its last round best; never above the slab count the workspace holds.
-        const int tiles = ((KP / 2 + 95) / 96) * ((d->N + 95) / 96), cus = num_cus();
-        int best = ns; double bf = -1.0;
-        for (int c = ns; c >= (ns + 1) / 2 && c >= 1; --c) {
-            const int w = tiles * c, rounds = (w + cus - 1) / cus;
-            const double f = (double)w / ((double)rounds * cus);
-            if (f > bf + 1e-9) { bf = f; best = c; }
-        }
-        ns = best;
-    }
-    const int M = half < 0 ? KP : KP / 2, m0 = half > 0 ? KP / 2 : 0;
-    stm::NyqJob nyq{}; nyq.on = 0;
-    const TNProblem tp = analysis_tn_problem(d, dG, sig, padded);
-    if (half < 0 && tp.fits) {
-        ns = tp.ns;
-        ST_TRY(wgrad_tn128(d, tp.a, tp.b, tp.zeros, tp.map, R, ws, ns, &nyq, stream, &tp.trim));
-    } else {
-        stg::PlainTN al{dG + m0, R, KP, M, ma};
-        stg::StoreC ep{ws + (size_t)m0 * d->N, M, d->N, d->N, (size_t)KP * d->N, stg::all_frames(1)};
-        if (padded) { stg::FramedTN<true> bl{sig, d->L, d->H, d->N, R, d->N, 1.0f, ma}; ST_GEMM_WG(al, bl, ep, M, d->N, R, ns, st_stream(stream)); }
-        else { stg::FramedTN<false> bl{sig, d->L, d->H, d->N, R, d->N, in_scale, ma}; ST_GEMM_WG(al, bl, ep, M, d->N, R, ns, st_stream(stream)); }
-    }
-    ST_LAUNCHED("analysis_wgrad");
-    // grid: the gradient rows of this call, then (whole tensor / second half) the Nyquist blocks resp. the unused partial slots
-    const int nrows = half < 0 ? 2 * d->F : d->F, extra = half == 0 ? 0 : stm::nyq_blocks(d->N);
-    hipLaunchKernelGGL(stm::wgrad_reduce_kernel, dim3(nrows + extra), dim3(256), 0, st_stream(stream),
-                       ws, ns, gWr, gWi, norm_partial, d->N, d->F, KP, 0, half > 0 ? d->F : 0, nrows, stage, nyq, 0, stage_bf16);
-    ST_LAUNCHED("analysis_wgrad_reduce");
-    return ST_OK;
-}
 extern "C" int st_analysis_wgrad(const st_dims* d, const float* dG, const float* x, float in_scale, float* ws,
                                  float* gWr, float* gWi, float* norm_partial, void* stream)
 {
     ST_TRY(check_dims(d)); ST_REQ(dG && x && ws && gWr && gWi && norm_partial, "st_analysis_wgrad: null pointer");
-    return analysis_wgrad_impl(d, dG, x, false, in_scale, ws, gWr, gWi, norm_partial, stream);
+    return wgrad_gemm_and_sum(wgrad_plan(d, 0, -1, 0, WgOps{dG, x, nullptr, nullptr, in_scale}, ws), gWr, gWi, norm_partial, nullptr, 0, stream);
 }
 
 static stm::FinArgs fin_args(const st_dims* d, const float* loss_partial, const float* reg_partial, const float* norm_a, const float* norm_s, float norm_scale)
@@ -1275,7 +1310,7 @@ struct WS {
     // dAA, frs: NOT every element is written per step (the pitch-padding columns [F, FP) of dAA's halves, the all-cropped tiles of frs): no consumer may read those -- the
     // contract is stated at st_workspace_bytes in the header; the Python engine zero-fills the buffer once when it allocates it
     float *re, *im, *mag, *phs, *mag_hat, *phs_hat, *AA, *dAA, *Sfold, *SfoldT, *frs, *y_hat, *dsyn, *dmag, *dphs, *dG, *xp;
-    float *wg, *wg2, *aews, *loss_p, *reg_p, *norm_a, *norm_s, *norm_e;      // wg2: the synthesis weight gradient's own slabs in the data-parallel step and in the pair launch of the fp32 step (synth_wgrad_ws_floats)
+    float *wg, *wg2, *aews, *loss_p, *reg_p, *norm_a, *norm_s, *norm_e;      // wg2: the synthesis weight gradient's own slabs in the data-parallel step and in the pair launch of the fp32 step (see carve)
     // bfloat16 planes of the operands that are written once per step (st_gemm_planes.h): [3][same layout as the fp32 tensor]
     unsigned short *pl_W, *pl_Sfold, *pl_SfoldT;      // k-chunk-major: [K / 16][rows][3][16]
     // 16-bit GEMM operands (st_gemm16.h), each written by its producer in the layout of its fp32 counterpart: padded x/2, the analysis
@@ -1307,7 +1342,10 @@ static void carve(const st_dims* d, const Layout& L, void* base, WS* w)
     // (+ 256: the 128-wide tiles of the TN kernel read up to 96 elements past the last row of an M/N-contiguous operand; masked outputs)
     w->xp16 = take16((size_t)d->B * (d->L + 2 * d->N) + 256); w->W16 = take16((size_t)2 * F * N); w->Sfold16 = take16(KP * N); w->SfoldT16 = take16(KP * N);
     w->AA16 = take16(RO * KP + 256); w->dsyn16 = take16((size_t)d->B * (d->y + 2 * d->N) + 256); w->dG16 = take16(RT * KP + 256);
-    w->wg2 = take(synth_wgrad_ws_floats(d));      // last: every earlier offset stays what it was
+    // Round 6: a second slab area for the SYNTHESIS weight gradient alone.  In the data-parallel step its slabs are summed on the communicator stream beside the autoencoder
+    // backward; with a buffer of their own the analysis weight-gradient GEMM (which reuses the first area) needs no communicator -> compute wait before it starts -- one
+    // barrier packet (~6 us of bubble on this stack) less on the compute stream.  Same size as the first: every slice rule is bounded by that area's size (wgrad_slices).
+    w->wg2 = take(wgrad_ws_floats(d));      // last: every earlier offset stays what it was
     w->g16 = false;
     w->bytes = off * sizeof(float);
 }
@@ -1480,44 +1518,6 @@ static int synthesis_dgrad16(const st_dims* d, WS& w, void* stream)
                                                                       : stg::launch16_nt<HT()>(ra, rb, ep, R, KP, d->N, ns, st_stream(stream), &cr); }));
     ST_LAUNCHED("synthesis_dgrad"); return ST_OK;
 }
-// k-slices of a 16-bit weight-gradient GEMM: about two workgroups per CU (their time is staging, not matrix work), never slices under
-// 128 reduction rows, never more slabs than the workspace holds
-static int g16_wsplit(const st_dims* d, int R)
-{
-    const int KP = st_kp_of(d->F), tiles = ((KP + 127) / 128) * (d->N / 128);
-    int s = (2 * num_cus()) / (tiles > 0 ? tiles : 1);
-    const int cap = R / 128; if (s > cap) s = cap;
-    const int room = (int)(wgrad_ws_floats(d) / ((size_t)KP * d->N)); if (s > room) s = room;
-    return s < 1 ? 1 : s;
-}
-// A: [rows (b, t)][KP] 16-bit (d G or the spectra), B: frames of a padded 16-bit signal whose first N elements are zero (the block of zeros)
-static int wgrad16(const st_dims* d, const unsigned short* A, unsigned SA1, const unsigned short* Bsig, unsigned SB1, const stg::RowMap& map, int R,
-                   float* slabs, int ns, void* stream, int m0 = 0, int M = -1,      // [m0, m0 + M): the output rows (= columns of A) of this launch; default all KP
-                   int trim_Ls = 0)                                                  // > 0: frame-major reduction order, rows per tile column trimmed to the frames with a tap inside [pad, pad + Ls) (round 5)
-{
-    const int KP = st_kp_of(d->F);
-    if (M < 0) M = KP;
-    const unsigned short* lo = A < Bsig ? A : Bsig;
-    ST_REQ((size_t)(A - lo) + (size_t)R / map.Tv * SA1 + 256 < ((size_t)1 << 30) && (size_t)(Bsig - lo) + (size_t)R / map.Tv * SB1 + 256 < ((size_t)1 << 30) && map.Tv >= 2 &&
-           SA1 < (1u << 23) && SB1 < (1u << 23), "16-bit weight-gradient GEMM: operands out of the 32-bit / 24-bit addressing range (B=%d)", d->B);
-    stg::TN16Job j;
-    j.base = lo; j.a0 = (unsigned)(A - lo) + (unsigned)m0; j.b0 = (unsigned)(Bsig - lo); j.zero = j.b0;
-    j.SA1 = SA1; j.SA2 = (unsigned)KP; j.SB1 = SB1; j.SB2 = (unsigned)d->H;
-    j.magic = map.magic; j.Tv = map.Tv; j.t_lo = map.t_lo; j.K = R;
-    j.trim = 0; j.fB = 0; j.nsplit = 1;
-    for (int i = 0; i < 64; ++i) { j.fa[i] = 0; j.fb[i] = 0; }
-    if (trim_Ls > 0 && d->B >= 2 && fm_div_exact(R, d->B)) {
-        const stg::FrameTrim ft = stg::frame_trim(map, d->B, d->H, d->N, d->N, trim_Ls);
-        // (outer, inner) = (frame, window): the strides swap roles, the origins move to frame t_lo (the zero block stays where it is)
-        j.a0 += (unsigned)map.t_lo * (unsigned)KP; j.b0 += (unsigned)map.t_lo * (unsigned)d->H;
-        j.SA1 = (unsigned)KP; j.SA2 = SA1; j.SB1 = (unsigned)d->H; j.SB2 = SB1;
-        j.magic = stg::rowmap_magic(d->B); j.Tv = d->B; j.t_lo = 0;
-        j.trim = ft.on; j.fB = d->B;
-        for (int i = 0; i < 64; ++i) { j.fa[i] = ft.fa[i]; j.fb[i] = ft.fb[i]; }
-    }
-    stg::StoreC ep{slabs + (size_t)m0 * d->N, M, d->N, d->N, (size_t)KP * d->N, stg::all_frames(1)};
-    return with_ht16(gemm_ht(d->prec), [&](auto HT) { return stg::launch16_tn<HT(), 64>(j, ep, M, d->N, ns, st_stream(stream)); });
-}
 
 // ------------------------------------------------------------------------------ fused entry points
 // What a fused entry derives from its arguments before its first launch, handed down in one piece.  call_begin validates the dims (and nothing else: every
@@ -1533,6 +1533,12 @@ static int call_begin(Call* c, const st_dims* d, const float* params, const floa
     carve(d, c->L, ws, &c->w);
     c->w.g16 = g16 && use_g16(d);
     return ST_OK;
+}
+// A weight-gradient plan on the workspace's own operands.  area: where the slabs go (default: the first area, w.wg); more: WGP_HALVES_96; ncus: the host queries
+static WgradPlan step_wgrad_plan(const st_dims* d, const WS& w, int which, int half = -1, float* area = nullptr, int more = 0, int ncus = 0)
+{
+    const WgOps o = which ? WgOps{w.AA, w.dsyn, w.AA16, w.dsyn16, 1.0f} : WgOps{w.dG, w.xp, w.dG16, w.xp16, 1.0f};
+    return wgrad_plan(d, which, half, WGP_PADDED | (w.g16 ? WGP_G16 : 0) | more, o, area ? area : w.wg, ncus);
 }
 static int forward_impl(Call& c, const float* params, const float* x, const float* y_true, float* y_hat, float* mag, float* mag_hat, bool save, float* eval_p = nullptr)
 {
@@ -1605,66 +1611,33 @@ static int forward_impl(Call& c, const float* params, const float* x, const floa
 // backward of everything behind d syn (workspace holds the forward state): autograd of train.py:138.
 // phase 1 = synthesis dgrad/wgrad + autoencoders + polar backward (fills grads[n_stft/2 ..));
 // phase 2 = analysis weight gradient (fills rows [0,F) of the first two tensors).
-// The weight-gradient GEMM of the 16-bit operand pipeline and the sum of its slabs.  synth: the synthesis bases (A = the spectra, B = the padded d syn), else the
-// analysis bases (A = d G, B = the padded input); half = -1 the whole tensor, 0 / 1 one basis of the analysis pair (analysis_wgrad_half: twice the k-slices on half
-// the tiles).  defer_slabs: the caller sums the slabs itself and receives their count.  No Nyquist job on this path.
-static int wgrad16_and_reduce(Call& c, float* grads, bool synth, int half, float* stage, int stage_bf16, int* defer_slabs = nullptr)
-{
-    const st_dims* d = c.d; const Layout& L = c.L; WS& w = c.w; void* stream = c.stream;
-    const int KP = L.KP, F = d->F, N = d->N;
-    const stg::RowMap map = synth ? synth_live(d) : stg::live_frames(d->T, d->H, d->N, d->N, d->L);
-    const int R = map.rows(d->B);
-    int ns = g16_wsplit(d, R);
-    if (half >= 0) {
-        const int room = (int)((wgrad_ws_floats(d) - (size_t)64 * 2 * N) / ((size_t)KP * N));      // slabs the workspace holds (the Nyquist partials sit behind them)
-        const int tiles = ((KP / 2 + 127) / 128) * (N / 128);
-        ns = (2 * num_cus()) / (tiles > 0 ? tiles : 1);
-        if (ns > R / 128) ns = R / 128; if (ns > room) ns = room; if (ns < 1) ns = 1;
-    }
-    if (synth) ST_TRY(wgrad16(d, w.AA16, (unsigned)(d->OT * KP), w.dsyn16, (unsigned)(d->y + 2 * N), map, R, w.wg, ns, stream, 0, -1, (g_g16_crop & 4) ? d->y : 0));
-    else ST_TRY(wgrad16(d, w.dG16, (unsigned)(d->T * KP), w.xp16, (unsigned)(d->L + 2 * N), map, R, w.wg, ns, stream, half > 0 ? KP / 2 : 0, half < 0 ? -1 : KP / 2, (g_g16_crop & 8) ? d->L : 0));
-    ST_LAUNCHED(synth ? "synthesis_wgrad" : "analysis_wgrad");
-    if (defer_slabs) { *defer_slabs = ns; return ST_OK; }
-    stm::NyqJob nq{}; nq.on = 0;
-    float* const g0 = grads + L.offs[synth ? 2 : 0]; float* const g1 = grads + L.offs[synth ? 3 : 1];
-    const int per = stm::nyq_blocks(N) / 2;
-    if (half < 0) hipLaunchKernelGGL(stm::wgrad_reduce_kernel, dim3(norm_partials(d)), dim3(256), 0, st_stream(stream),
-                                     w.wg, ns, g0, g1, synth ? w.norm_s : w.norm_a, N, F, KP, synth ? 1 : 0, 0, 2 * F, stage, nq, 0, stage_bf16);
-    else hipLaunchKernelGGL(stm::wgrad_reduce_kernel, dim3(F + per), dim3(256), 0, st_stream(stream),
-                            w.wg, ns, g0, g1, w.norm_a, N, F, KP, 0, half * F, F, stage, nq, half * per, stage_bf16);
-    ST_LAUNCHED(synth ? "synthesis_wgrad_reduce" : "analysis_wgrad_reduce");
-    return ST_OK;
-}
 // stages (ST_STAGE_*, st_train_step_groups): a stage outside the set is not launched; every other caller runs them all
 static const int ST_STAGE_EVERY = ST_STAGE_SYN_DGRAD | ST_STAGE_SYN_WGRAD | ST_STAGE_AE_BWD | ST_STAGE_AE_DINPUT | ST_STAGE_ANA_WGRAD;
-static int backward_syn(Call& c, float* grads, int* defer_slabs = nullptr, stm::NyqJob* defer_nyq = nullptr, int stages = ST_STAGE_EVERY)
-{
+static int backward_syn(Call& c, float* grads, const WgradPlan* deferred = nullptr, int stages = ST_STAGE_EVERY)
+{   // deferred: the caller's synthesis plan, whose slabs the caller sums itself (post_ae_kernel, the gradient-finish launch, the communicator stream); else summed here
     const st_dims* d = c.d; const Layout& L = c.L; WS& w = c.w; void* stream = c.stream;
-    const bool dgrad = (stages & ST_STAGE_SYN_DGRAD) != 0, wgrad = (stages & ST_STAGE_SYN_WGRAD) != 0;
-    if (w.g16) {
-        if (dgrad) ST_TRY(synthesis_dgrad16(d, w, stream));
-        if (defer_slabs && defer_nyq) { *defer_nyq = stm::NyqJob{}; defer_nyq->on = 0; }
-        return wgrad ? wgrad16_and_reduce(c, grads, true, -1, nullptr, 0, defer_slabs) : ST_OK;
-    }
-    if (dgrad) {
+    if (stages & ST_STAGE_SYN_DGRAD) {
+    if (w.g16) ST_TRY(synthesis_dgrad16(d, w, stream)); else
     if (use_planes(d) && g_pl_dgrad) ST_TRY(synthesis_dgrad_planes(d, w, stream)); else
     ST_TRY(synthesis_dgrad_impl(d, w.dsyn, true, w.Sfold, w.dAA, stream));
     }
-    if (!wgrad) return ST_OK;
-    return synthesis_wgrad_impl(d, w.AA, w.dsyn, true, w.wg, grads + L.offs[2], grads + L.offs[3], w.norm_s, stream, defer_slabs, defer_nyq);
+    if (!(stages & ST_STAGE_SYN_WGRAD)) return ST_OK;
+    if (deferred) return wgrad_gemm(*deferred, stream);
+    return wgrad_gemm_and_sum(step_wgrad_plan(d, w, 1), grads + L.offs[2], grads + L.offs[3], w.norm_s, nullptr, 0, stream);
 }
-static int backward_ae(Call& c, const float* params, float* grads, const float* g_mag_hat, const float* g_mag, float reg_coef, int syn_slabs = 0,
-                       const stm::NyqJob* syn_nyq = nullptr, float* kg = nullptr, int stages = ST_STAGE_EVERY)
+static int backward_ae(Call& c, const float* params, float* grads, const float* g_mag_hat, const float* g_mag, float reg_coef, const WgradPlan* syn_plan = nullptr,
+                       float* kg = nullptr, int stages = ST_STAGE_EVERY)
 {   // stages without ST_STAGE_AE_DINPUT (st_train_step_groups, analysis bases frozen): no input gradient is wanted and no polar backward runs
-    // syn_slabs > 0: the synthesis weight-gradient slabs in w.wg are still to be summed (done by post_ae_kernel)
+    // syn_plan: the synthesis weight-gradient slabs of that plan are still to be summed (done by post_ae_kernel)
     const st_dims* d = c.d; const Layout& L = c.L; WS& w = c.w; void* stream = c.stream;
+    const int syn_slabs = syn_plan ? syn_plan->ns : 0;
     const float* ae_m = params + L.offs[4]; const float* ae_p = params + L.offs[22];
     bool deferred = true;
     const PolarSink sink{w.re, w.im, g_mag, w.g16 ? nullptr : w.dG, w.g16 ? w.dG16 : nullptr};
     stw::SynReduce syn{};
     if (syn_slabs > 0 && ae_is_wide(d)) {              // wide geometries: the synthesis slab sum rides in the gradient-finish launch of the autoencoder backward
-        syn.wg = w.wg; syn.nz = syn_slabs; syn.gSr = grads + L.offs[2]; syn.gSi = grads + L.offs[3]; syn.norm_s = w.norm_s; syn.N = d->N; syn.F = d->F; syn.KP = L.KP;
-        syn.nyq = stm::NyqJob{}; syn.nyq.on = 0; if (syn_nyq) syn.nyq = *syn_nyq;
+        syn.wg = syn_plan->area; syn.nz = syn_slabs; syn.gSr = grads + L.offs[2]; syn.gSi = grads + L.offs[3]; syn.norm_s = w.norm_s; syn.N = d->N; syn.F = d->F; syn.KP = L.KP;
+        syn.nyq = syn_plan->nyq();
     }
     ST_TRY(ae_bwd_body(d, L, w.mag, w.phs, c.knobs, ae_m, ae_p, w.mag_hat, w.phs_hat, w.dAA, g_mag_hat, reg_coef, w.dmag, w.dphs,
                        w.aews, grads + L.offs[4], grads + L.offs[22], true, stream, &deferred, &sink, syn.wg ? &syn : nullptr,
@@ -1681,8 +1654,8 @@ static int backward_ae(Call& c, const float* params, float* grads, const float* 
         a.polar_total = (unsigned)((long long)d->B * d->T * (L.KP / 2)); a.polar_magic = stm::polar_magic(L.KP / 2);
         a.n_polar = (int)((a.polar_total + 256 * stm::POLAR_EPT - 1) / (256 * stm::POLAR_EPT));
     }
-    a.wg = w.wg; a.wg_nz = syn_slabs; a.gSr = grads + L.offs[2]; a.gSi = grads + L.offs[3]; a.norm_s = w.norm_s; a.N = d->N;
-    a.nyq = stm::NyqJob{}; a.nyq.on = 0; if (syn_nyq) a.nyq = *syn_nyq;
+    a.wg = syn_plan ? syn_plan->area : w.wg; a.wg_nz = syn_slabs; a.gSr = grads + L.offs[2]; a.gSi = grads + L.offs[3]; a.norm_s = w.norm_s; a.N = d->N;
+    a.nyq = stm::NyqJob{}; a.nyq.on = 0; if (syn_plan) a.nyq = syn_plan->nyq();
     a.dG16 = nullptr; a.ht = 0;
     if (w.g16) { a.dG16 = w.dG16; a.ht = gemm_ht(d->prec); a.dG = nullptr; }      // the analysis weight-gradient GEMM is the only consumer on this path
     a.norm_e = nullptr;
@@ -1695,84 +1668,38 @@ static int backward_ae(Call& c, const float* params, float* grads, const float* 
 }
 static int backward_p1(Call& c, const float* params, float* grads, const float* g_mag_hat, const float* g_mag, float reg_coef, float* kg = nullptr, int stages = ST_STAGE_EVERY)
 {
-    if (!(stages & ST_STAGE_AE_BWD)) return backward_syn(c, grads, nullptr, nullptr, stages);      // only the synthesis bases train: their GEMM and its own slab reduce
-    int syn_slabs = 0; stm::NyqJob syn_nyq{}; syn_nyq.on = 0;
-    ST_TRY(backward_syn(c, grads, &syn_slabs, &syn_nyq, stages));      // the slab sum rides in a later launch: post_ae_kernel (fused geometries) / wide_grad_finish_kernel (wide ones)
-    return backward_ae(c, params, grads, g_mag_hat, g_mag, reg_coef, syn_slabs, &syn_nyq, kg, stages);
+    if (!(stages & ST_STAGE_AE_BWD)) return backward_syn(c, grads, nullptr, stages);      // only the synthesis bases train: their GEMM and its own slab reduce
+    const WgradPlan sp = step_wgrad_plan(c.d, c.w, 1);
+    ST_TRY(backward_syn(c, grads, &sp, stages));      // the slab sum rides in a later launch: post_ae_kernel (fused geometries) / wide_grad_finish_kernel (wide ones)
+    return backward_ae(c, params, grads, g_mag_hat, g_mag, reg_coef, (stages & ST_STAGE_SYN_WGRAD) ? &sp : nullptr, kg, stages);
 }
-static int backward_p2(Call& c, float* grads, float* stage = nullptr, int stage_bf16 = 0)
+// The analysis weight gradient: the whole tensor, or ONE basis (half 0 = real, 1 = imaginary: gradient rows and packed stage rows [half * F, half * F + F))
+static int backward_p2(Call& c, float* grads, float* stage = nullptr, int stage_bf16 = 0, int half = -1, int more = 0)
 {
-    if (c.w.g16) return wgrad16_and_reduce(c, grads, false, -1, stage, stage_bf16);
-    return analysis_wgrad_impl(c.d, c.w.dG, c.w.xp, true, 1.0f, c.w.wg, grads + c.L.offs[0], grads + c.L.offs[1], c.w.norm_a, c.stream, -1, stage, stage_bf16);
-}
-// ONE basis (half 0 = real, 1 = imaginary) of the analysis weight gradient -- its GEMM over that basis' rows and its slab reduce (gradient rows, packed
-// stage rows [half * F, half * F + F)) -- so that the data-parallel exchange of the first basis runs under the GEMM of the second (st_dp_train_step,
-// exchange flag 2): only F * N values (2.1 MB; 1.05 MB bf16-packed) stay exposed behind the last GEMM of the step.  Each half fills the chip with twice
-// the k-slices of the whole-tensor launch (half the tiles), so the two launches together do the work of the one.  nyq_io carries the Nyquist partials'
-// description (128 x 128-tile form: formed for BOTH bases by the first launch) from half 0 to half 1.
-static int analysis_wgrad_half(Call& c, float* grads, int half, float* stage, int stage_bf16, stm::NyqJob* nyq_io)
-{
-    const st_dims* d = c.d; const Layout& L = c.L; WS& w = c.w; void* stream = c.stream;
-    const int KP = st_kp_of(d->F), F = d->F, N = d->N, m0 = half ? KP / 2 : 0;
-    const stg::RowMap ma = stg::live_frames(d->T, d->H, d->N, d->N, d->L);
-    const int R = ma.rows(d->B);
-    const int room = (int)((wgrad_ws_floats(d) - (size_t)64 * 2 * N) / ((size_t)KP * N));      // slabs the workspace holds (the Nyquist partials sit behind them)
-    const int per = stm::nyq_blocks(N) / 2;
-    int ns;
-    const stg::TNOperand ta{w.dG + m0, (unsigned)(d->T * KP), (unsigned)KP}, tb{w.xp, (unsigned)(d->L + 2 * d->N), (unsigned)d->H};
-    if (w.g16) {
-        if (!half) { *nyq_io = stm::NyqJob{}; nyq_io->on = 0; }
-        return wgrad16_and_reduce(c, grads, false, half, stage, stage_bf16);
-    }
-    if (use_tn128(d, true) && stg::tn128_fits(ta, tb, w.xp, ma, N / 2, N, (size_t)d->B * d->T * KP, (size_t)d->B * (d->L + 2 * d->N))) {
-        const int mh = (N / 2) / 128, tiles = mh * (N / 128);
-        ns = num_cus() / (tiles > 0 ? tiles : 1); if (ns > 16) ns = 16; if (ns > R / 64) ns = R / 64; if (ns > room) ns = room; if (ns < 1) ns = 1;
-        float* part = w.wg + (size_t)room * KP * N;
-        int P = 0;
-        const TNFrameMajor fm = tn_frame_major(ta, tb, ma, d->B, d->H, N, N, d->L, (g_tn_fm & 2) != 0);
-        // half 0 also forms the Nyquist partials of BOTH bases (its A origin is column 0: c0 = F - 1, c1 = KP / 2 + F - 1); half 1 has no Nyquist slice
-        ST_TN128(fm.a, fm.b, w.xp, fm.map, R, N / 2, mh, (unsigned)(KP / 2), N, w.wg + (size_t)m0 * N, N, (size_t)KP * N, ns, st_stream(stream),
-                 half ? nullptr : part, (unsigned)(F - 1), (unsigned)(KP / 2 + F - 1), &P, &fm.trim);
-        if (!half) { nyq_io->part = part; nyq_io->P = P; nyq_io->on = 1; }
-    } else {
-        ST_LAUNCHED("analysis_wgrad");
-        if (!half) { *nyq_io = stm::NyqJob{}; nyq_io->on = 0; }
-        return analysis_wgrad_impl(d, w.dG, w.xp, true, 1.0f, w.wg, grads + L.offs[0], grads + L.offs[1], w.norm_a, stream, half, stage, stage_bf16);
-    }
-    ST_LAUNCHED("analysis_wgrad");
-    hipLaunchKernelGGL(stm::wgrad_reduce_kernel, dim3(F + per), dim3(256), 0, st_stream(stream),
-                       w.wg, ns, grads + L.offs[0], grads + L.offs[1], w.norm_a, N, F, KP, 0, half * F, F, stage, *nyq_io, half * per, stage_bf16);
-    ST_LAUNCHED("analysis_wgrad_reduce");
-    return ST_OK;
+    return wgrad_gemm_and_sum(step_wgrad_plan(c.d, c.w, 0, half, nullptr, more), grads + c.L.offs[0], grads + c.L.offs[1], c.w.norm_a, stage, stage_bf16, c.stream);
 }
 // Both weight-gradient GEMMs of the fp32 step in ONE launch (stg::gemm_tn128_pair_kernel), then ONE launch that sums both sets of slabs.  Nothing between the two
 // GEMMs of the per-GEMM schedule needs the synthesis weight gradient (its slabs are only summed, and the sum is first read by the optimizer), and its operands
 // (the spectra, the padded d syn) are still in place when d G is ready.  Analysis slabs in w.wg, synthesis slabs in w.wg2, each with its Nyquist partials behind them.
 // The pair applies to: fp32 operands, the fused autoencoder geometries, both GEMMs on the 128 x 128 kernel, g_tn128 == 1.  false from make: per-GEMM launches.
-struct WgradPair { TNProblem pa, ps; stg::TNLaunch la, ls; stg::TNPair pair; bool on; };
+struct WgradPair { WgradPlan p[2]; stg::TNPair pair; bool on; };      // p[0] the analysis plan, p[1] the synthesis plan
 static void wgrad_pair_make(WgradPair& q, const st_dims* d, const WS& w, int ncus = 0)
 {
-    const int KP = st_kp_of(d->F), N = d->N, mh = (N / 2) / 128;
     q.on = false;
     if (g_tn128 != 1 || w.g16 || gemm_ht(d->prec) != 0 || ae_is_wide(d)) return;
-    q.pa = analysis_tn_problem(d, w.dG, w.xp, true, ncus); q.ps = synthesis_tn_problem(d, w.AA, w.dsyn, true, ncus);
-    if (!q.pa.fits || !q.ps.fits) return;
-    const unsigned c0 = (unsigned)(d->F - 1), c1 = (unsigned)(KP / 2 + d->F - 1);
-    const size_t slab = (size_t)KP * N;
-    q.la = stg::tn128_job(32, q.pa.a, q.pa.b, q.pa.zeros, q.pa.map, q.pa.R, N, mh, (unsigned)(KP / 2), N, w.wg, N, slab, q.pa.ns, w.wg + (size_t)q.pa.ns * slab, c0, c1, nullptr, &q.pa.trim);
-    q.ls = stg::tn128_job(32, q.ps.a, q.ps.b, q.ps.zeros, q.ps.map, q.ps.R, N, mh, (unsigned)(KP / 2), N, w.wg2, N, slab, q.ps.ns, w.wg2 + (size_t)q.ps.ns * slab, c0, c1, nullptr, &q.ps.trim);
-    q.on = stg::tn128_pair_make(q.pair, q.la, q.ls, 32);
+    q.p[0] = step_wgrad_plan(d, w, 0, -1, w.wg, 0, ncus); q.p[1] = step_wgrad_plan(d, w, 1, -1, w.wg2, 0, ncus);
+    if (q.p[0].form != WG_TN128 || q.p[1].form != WG_TN128) return;
+    q.on = stg::tn128_pair_make(q.pair, q.p[0].tn, q.p[1].tn, 32);
 }
 static int wgrad_pair(Call& c, const WgradPair& q, float* grads)
 {
     const st_dims* d = c.d; const Layout& L = c.L; void* stream = c.stream;
-    ST_TRY(stg::launch_tn128_pair<32>(q.pair, q.la, q.ls, st_stream(stream)));
+    ST_TRY(stg::launch_tn128_pair<32>(q.pair, q.p[0].tn, q.p[1].tn, st_stream(stream)));
     ST_LAUNCHED("wgrad_pair");
     stm::WgradPairArgs a;
-    const stg::TNLaunch* l[2] = {&q.la, &q.ls};
     for (int i = 0; i < 2; ++i) {
-        a.ws[i] = l[i]->out; a.nz[i] = l[i]->j.nsplit; a.gRe[i] = grads + L.offs[2 * i]; a.gIm[i] = grads + L.offs[2 * i + 1]; a.norm[i] = i ? c.w.norm_s : c.w.norm_a;
-        a.nyq[i].part = l[i]->j.nyq_out; a.nyq[i].P = l[i]->j.nyq_P; a.nyq[i].on = 1;
+        a.ws[i] = q.p[i].area; a.nz[i] = q.p[i].ns; a.gRe[i] = grads + L.offs[2 * i]; a.gIm[i] = grads + L.offs[2 * i + 1]; a.norm[i] = i ? c.w.norm_s : c.w.norm_a;
+        a.nyq[i] = q.p[i].nyq();
     }
     a.N = d->N; a.F = d->F; a.KP = L.KP;
     hipLaunchKernelGGL(stm::wgrad_pair_reduce_kernel, dim3(2 * norm_partials(d)), dim3(256), 0, st_stream(stream), a);
@@ -1791,6 +1718,24 @@ extern "C" int st_wgrad_pair_plan(const st_dims* d, int ncus, int* out, int cap)
     WgradPair q; wgrad_pair_make(q, d, w, ncus);
     if (!q.on) return 0;
     return stg::tn128_pair_describe(q.pair, d->N / 128, d->N / 128, 32, out, cap);
+}
+// Host-side view of ONE weight-gradient launch (no device work): the plan the launches themselves ask for, as ST_WGRAD_PLAN_INTS ints (signaltrain_hip.h).
+// which 0 / 1: analysis / synthesis bases; half -1 / 0 / 1 (one basis: analysis only); flags: ST_WGPLAN_*; ncus <= 0: the current device's CU count -- then the
+// answer is what a launch on this device does under the current tuning state.  Fills min(cap, count) ints and returns the count; < 0 on bad arguments.
+extern "C" int st_wgrad_plan(const st_dims* d, int which, int half, int flags, int ncus, int* out, int cap)
+{
+    static_assert(ST_WGPLAN_PADDED == WGP_PADDED && ST_WGPLAN_G16 == WGP_G16 && ST_WGPLAN_STAGED == WGP_HALVES_96, "st_wgrad_plan: flag values");
+    Layout L;
+    if (make_layout(d, &L) != ST_OK || cap < 0 || (cap > 0 && !out)) return -1;
+    if (which < 0 || which > 1 || half < -1 || half > 1 || (half >= 0 && which) || (flags & ~(WGP_PADDED | WGP_G16 | WGP_HALVES_96)) ||
+        ((flags & WGP_G16) && !(flags & WGP_PADDED))) return -1;
+    WS w; carve(d, L, reinterpret_cast<void*>(sizeof(float)), &w);       // a non-null dummy base: only pointer differences are used
+    w.g16 = (flags & WGP_G16) && use_g16(d);                              // as call_begin: the pipeline is taken where the precision admits it
+    const WgradPlan p = (flags & WGP_PADDED) ? step_wgrad_plan(d, w, which, half, nullptr, flags & WGP_HALVES_96, ncus)
+                                             : wgrad_plan(d, which, half, flags, WgOps{w.dG, w.xp, nullptr, nullptr, 1.0f}, w.wg, ncus);
+    const int v[ST_WGRAD_PLAN_INTS] = {p.form, p.R, p.ns, p.m0, p.M, p.frame_major ? 1 : 0, p.trim.on ? 1 : 0, p.nyq_P, (int)p.nyq_off, p.nyq_write ? 1 : 0, (int)p.used()};
+    for (int i = 0; i < ST_WGRAD_PLAN_INTS && i < cap; ++i) out[i] = v[i];
+    return ST_WGRAD_PLAN_INTS;
 }
 static int backward_impl(Call& c, const float* params, float* grads, const float* g_mag_hat, const float* g_mag, float reg_coef, float* kg = nullptr)
 {
@@ -2118,7 +2063,7 @@ extern "C" int st_loss_backward_stage(const st_dims* d, const float* params, flo
                                       const float* y_true, void* ws, float* scalars, int stage, void* stream)
 {
     Call c; ST_TRY(call_begin(&c, d, params, knobs, ws, stream, FP32_OPERANDS));
-    const Layout& L = c.L; WS& w = c.w;
+    WS& w = c.w;
     ST_REQ(params && grads && x && (knobs || d->K == 0) && y_true && ws && scalars, "st_loss_backward_stage: null pointer");
     ST_REQ(stage >= 0 && stage < 4, "st_loss_backward_stage: stage %d not in 0..3", stage);
     switch (stage) {
@@ -2129,9 +2074,9 @@ extern "C" int st_loss_backward_stage(const st_dims* d, const float* params, flo
     case 1:
         return backward_ae(c, params, grads, nullptr, nullptr, reg_coef_of(d));
     case 2:
-        return analysis_wgrad_impl(d, w.dG, w.xp, true, 1.0f, w.wg, grads + L.offs[0], grads + L.offs[1], w.norm_a, stream, 0);
+        return backward_p2(c, grads, nullptr, 0, 0, WGP_HALVES_96);
     default:
-        ST_TRY(analysis_wgrad_impl(d, w.dG, w.xp, true, 1.0f, w.wg, grads + L.offs[0], grads + L.offs[1], w.norm_a, stream, 1));
+        ST_TRY(backward_p2(c, grads, nullptr, 0, 1, WGP_HALVES_96));
         return finalize_scalars(d, w.loss_p, w.reg_p, w.norm_a, w.norm_s, 1.0f / loss_scale_of(d), scalars, stream);
     }
 }
@@ -2925,21 +2870,17 @@ extern "C" int st_dp_train_step(st_dp* p, const st_dims* d, float* params, float
     {
         prof_mark("begin", stream);
         ST_TRY(forward_impl(c, params, x, y_true, nullptr, nullptr, nullptr, true));
-        int syn_slabs = 0; stm::NyqJob syn_nyq{}; syn_nyq.on = 0;
-        float* const wg_main = w.wg;
-        if (g_dp_inline) w.wg = w.wg2;                                                  // round 6: the synthesis slabs in their own area (no wait before the analysis GEMM reuses the first)
-        ST_TRY(backward_syn(c, grads, &syn_slabs, &syn_nyq));                           // GEMMs only; the slabs are summed on the communicator stream
+        const WgradPlan sp = step_wgrad_plan(d, w, 1, -1, g_dp_inline ? w.wg2 : w.wg);  // round 6: the synthesis slabs in their own area (no wait before the analysis GEMM reuses the first)
+        ST_TRY(backward_syn(c, grads, &sp));                                            // GEMMs only; the slabs are summed on the communicator stream
         ST_TRY(dp_fork(p, stream));
-        hipLaunchKernelGGL(stm::wgrad_reduce_kernel, dim3(norm_partials(d)), dim3(256), 0, p->cs,
-                           w.wg, syn_slabs, grads + L.offs[2], grads + L.offs[3], w.norm_s, d->N, d->F, L.KP, 1, 0, 2 * d->F, (float*)nullptr, syn_nyq);
-        w.wg = wg_main;
+        wgrad_reduce(sp, grads + L.offs[2], grads + L.offs[3], w.norm_s, nullptr, 0, p->cs);
         if (!g_dp_inline) ST_HIP(hipEventRecord(p->wgfree, p->cs), "event record");     // the analysis weight-gradient GEMM reuses the slab buffer
         ST_TRY(dp_allreduce_on_cs(p, grads + L.offs[2], L.offs[4] - L.offs[2], ncclFloat32));
         // The clip norm is that of the REDUCED, 1/world-scaled gradient.  The two ranges whose exchange is hidden get their |g| partials on the communicator
         // stream right behind their collective (hidden as well); only the analysis rows' share is formed after the exposed collective, in the pass that
         // copies them back (unstage_l1_kernel).  Same kernels, same order, same data on every rank: the norm is bit-identical across ranks.
         hipLaunchKernelGGL(stm::l1_partial_kernel, dim3(norm_partials(d)), dim3(256), 0, p->cs, grads + L.offs[2], L.offs[4] - L.offs[2], gs, w.norm_s);
-        ST_TRY(backward_ae(c, params, grads, nullptr, nullptr, reg_coef_of(d), 0, nullptr));
+        ST_TRY(backward_ae(c, params, grads, nullptr, nullptr, reg_coef_of(d)));
         ST_TRY(st_dp_allreduce(p, grads + L.offs[4], L.total - L.offs[4], stream));
         if (d->clip_all) hipLaunchKernelGGL(stm::l1_partial_kernel, dim3(NORM_E_PARTIALS), dim3(256), 0, p->cs, grads + L.n_stft, L.total - L.n_stft, gs, w.norm_e);
         if (!g_dp_inline) ST_HIP(hipStreamWaitEvent(st_stream(stream), p->wgfree, 0), "stream wait");
@@ -2961,9 +2902,8 @@ extern "C" int st_dp_train_step(st_dp* p, const st_dims* d, float* params, float
         ST_TRY(dp_fork(p, stream));
         ST_TRY(dp_allreduce_on_cs(p, stage, 2 * half_n, pack16 ? ncclBfloat16 : ncclFloat32));
     } else {
-        stm::NyqJob nyq{}; nyq.on = 0;
         for (int h = 0; h < 2; ++h) {
-            ST_TRY(analysis_wgrad_half(c, grads, h, stage, pack16, &nyq));
+            ST_TRY(backward_p2(c, grads, stage, pack16, h));
             void* part = pack16 ? (void*)(reinterpret_cast<unsigned short*>(stage) + (size_t)h * half_n) : (void*)(stage + (size_t)h * half_n);
             if (h == 1 && g_dp_inline) {        // the second half's exchange is the exposed one: in line, behind the join recorded when the first half's was issued
                 ST_HIP(hipStreamWaitEvent(st_stream(stream), p->done, 0), "stream wait");
