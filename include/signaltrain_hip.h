@@ -218,6 +218,31 @@ enum { ST_WGP_FORM = 0, ST_WGP_R, ST_WGP_SLICES, ST_WGP_M0, ST_WGP_M, ST_WGP_FRA
        ST_WGRAD_PLAN_INTS };
 int st_wgrad_plan(const st_dims* d, int which, int half, int flags, int ncus, int* out, int cap);
 
+/* Diagnostics, host only: what ONE of the other three STFT GEMMs does at these dims -- which: ST_STFT_ANALYSIS = the analysis forward (st_analysis_fwd),
+ * ST_STFT_FRAMES = the synthesis frames (st_synthesis_frames), ST_STFT_DGRAD = the synthesis data gradient (st_synthesis_dgrad) -- the plan the launches
+ * themselves ask for; ncus as in st_wgrad_plan.  flags: 0 = the per-op entry; ST_STFTPLAN_PADDED = operands in the padded workspace layout (every fused entry),
+ * ST_STFTPLAN_SFOLDT = the transposed fold is there (every fused entry), ST_STFTPLAN_G16 = the entry asks for the 16-bit operand pipeline (the training,
+ * validation and prediction entries; taken where the precision admits it); the last two need ST_STFTPLAN_PADDED.  out receives min(cap, ST_STFT_PLAN_INTS)
+ * ints in the order of the ST_SGP_* indices:
+ *   FAMILY    operands: 0 = fp32 on the fp32 MFMA, 1 = fp32 converted while staged (bf16 / f16 / the in-kernel three-plane split of ST_PREC_F32X3),
+ *             2 = bfloat16 planes of the once-per-step operands, 3 = the 16-bit operand pipeline
+ *   FORM      kernel: 0 = the small-tile kernel ((32 WAVES) x 96), 1 = the 128 x 128 work-list kernel (st_nt128_worklist is its list), 2 = the plane kernel
+ *             ((32 WAVES) x 96), 3 = the 16-bit 128 x 128 kernel, 4 = the 16-bit LDS-DMA kernel (256 x 128)
+ *   WAVES     waves per workgroup of forms 0 and 2 (0 elsewhere: fixed by the kernel)
+ *   BK, XT    family 0 on form 0: k-tile depth (16 / 32) and 1 = k-quad-major staging; 0 elsewhere
+ *   R, M, NC, K   live rows (B x the frames with a tap inside the signal resp. the crop); the GEMM is M = R rows x NC columns over K
+ *   SLABS     split-K slabs: 1 for the analysis forward, st_synth_frame_slabs(d) / st_synth_slabs(d) for the other two, whatever the family
+ *   FRAME_MAJOR, CROP   rows enumerated frame-major (only where st_fm_div_exact(R, B)); structural zeros of the crop skipped: 0 none, 1 the dead tile columns of
+ *             the frames GEMM, 2 the dead taps per tile row of the data gradient
+ *   WORK      entries of the work list (form 1; 0 elsewhere)
+ *   T_LO, TV  the live frames [T_LO, T_LO + TV)
+ * Returns ST_STFT_PLAN_INTS; < 0 on bad arguments (unsupported dims, which / flags out of range, cap < 0). */
+enum { ST_STFT_ANALYSIS = 0, ST_STFT_FRAMES = 1, ST_STFT_DGRAD = 2 };
+enum { ST_STFTPLAN_PADDED = 1, ST_STFTPLAN_G16 = 2, ST_STFTPLAN_SFOLDT = 4 };
+enum { ST_SGP_FAMILY = 0, ST_SGP_FORM, ST_SGP_WAVES, ST_SGP_BK, ST_SGP_XT, ST_SGP_R, ST_SGP_M, ST_SGP_NC, ST_SGP_K, ST_SGP_SLABS, ST_SGP_FRAME_MAJOR, ST_SGP_CROP,
+       ST_SGP_WORK, ST_SGP_T_LO, ST_SGP_TV, ST_STFT_PLAN_INTS };
+int st_stft_plan(const st_dims* d, int which, int flags, int ncus, int* out, int cap);
+
 /* Diagnostics, host only: 1 if the frame-major row order may be used for a GEMM with R = (live frames) * B compact rows, i.e. if the kernels' division of a
  * row index r < R by B through a multiply-high with floor(2^32 / B) + 1 is exact (r * B < 2^32 for every r); 0: those launches keep the window-major order
  * and the untrimmed / uncropped tile sets.  (cls_fe_dft.py:28-31, :112-113: the trimming is an optimisation of the padded / cropped frames, never a

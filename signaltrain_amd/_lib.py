@@ -92,6 +92,7 @@ SIGNATURES = {
     "st_nt128_worklist": (_i, [_D, _i, _i, C.POINTER(C.c_uint), _i, C.POINTER(C.c_int)]),
     "st_wgrad_pair_plan": (_i, [_D, _i, C.POINTER(C.c_int), _i]),
     "st_wgrad_plan": (_i, [_D, _i, _i, _i, _i, C.POINTER(C.c_int), _i]),
+    "st_stft_plan": (_i, [_D, _i, _i, _i, C.POINTER(C.c_int), _i]),
     "st_fm_div_exact": (_i, [_i, _i]),
     "st_synth_fold": (_i, [_D, _p, _p, _p, _p]),
     "st_synthesis_frames": (_i, [_D, _p, _p, _p, _p]),

@@ -191,7 +191,7 @@ static int g_ae_split = -1;  // autoencoder backward of the fused geometries: 0 
 static int g_ae32 = 1;       // 16-bit autoencoder forward of the fused geometries on 32-row groups / v_mfma_f32_32x32x16 (st_ae32.h); 0 = the 16-row kernel of st_ae.h
 static int g_pl_bf16 = 0;    // ST_PREC_BF16*: analysis / frames GEMMs on the plane kernel with ONE plane (bf16 copies of the bases, k-chunk-major).  MEASURED SLOWER at B = 256
                              // (analysis 53.8 vs 49.8 us + 12 us for the copies): three MFMAs per 16-deep k-tile and barrier; needs a 64-deep tile
-static int g_wg_split = 0;   // ST_PREC_F32X3: weight-gradient GEMMs on the in-kernel three-plane split instead of the fp32 MFMA kernel (see ST_GEMM_WG)
+static int g_wg_split = 0;   // ST_PREC_F32X3: weight-gradient GEMMs on the in-kernel three-plane split instead of the fp32 MFMA kernel (see wgrad_small_gemm)
 static int g_pl_dgrad = 0;   // ST_PREC_F32X3: synthesis data gradient on the plane kernel (measured slower than the fp32 MFMA kernel at B = 256: 57 vs 45 us)
 static int g_pl_shape = 3;   // analysis plane GEMM tile (ST_PREC_F32X3): 0 = 4 waves x (32 x 96) [91.9 us], 1 = 2 waves x (64 x 96) [117], 2 = 4 waves x (64 x 96) [112],
                              // 3 = 8 waves x (32 x 96) = 256 x 96, one workgroup per CU: a quarter less L2 traffic at the same two waves per SIMD [88.1]
@@ -212,7 +212,7 @@ static int g_xt = 0;       // 1: M/N-contiguous operands staged k-quad-major (st
 static const int NORM_E_PARTIALS = 32;     // |g| partials of the autoencoder gradient range (st_dims.clip_all) when they come from l1_partial_kernel
 static const int NORM_E_MAX = 4096;        // room for the per-block partials of the reducing kernels themselves (post_ae_kernel / wide_grad_finish_kernel)
 static int g_wide_direct = 1; // wide geometries: the analysis epilogue writes the wide autoencoder path's feature-major input itself (no wide_in_kernel in the fused step); 0 = copy kernel
-static int g_an_bk = 32;   // k-tile depth of the analysis forward GEMM (see ST_GEMM_AN)
+static int g_an_bk = 32;   // k-tile depth of the analysis forward GEMM (see stft_plan)
 static int g_bk = 16;   // k-tile depth of the GEMM family (16: 36 KB LDS/WG -> 4 WGs/CU; 32: 64 KB -> 2 WGs/CU)
 static int g_wg_mode = 0;    // weight-gradient GEMMs: 0 = three waves share a 96 x 96 tile (32 x 96 strips), 2 = the same on the k-quad-major staging (see g_xt)
 // The diagnostic switches above as ONE readable state, in st_get_tuning's order, with their shipped defaults.  The product path never sets them;
@@ -284,21 +284,6 @@ static inline float loss_scale_of(const st_dims* d) { return d->loss_scale > 0.f
 static inline float reg_scale_of(const st_dims* d) { return (float)(2e-5 / 10.0) / ((float)d->B * (float)d->OT * (float)d->F); }
 static inline float reg_coef_of(const st_dims* d) { return loss_scale_of(d) * (float)(2e-5 / 10.0) / ((float)d->B * (float)d->OT * (float)d->F); }
 static inline float expfac_of(const st_dims* d) { return (float)(7.0 / d->F); }
-// every ST_GEMM* user has `d` (const st_dims*) in scope
-#define ST_GEMM_BK(BK_, W_, ...) do { const int ht_ = gemm_ht(d->prec); \
-                              if (ht_ == 1) stg::launch_half<W_, 1>(__VA_ARGS__); else if (ht_ == 2) stg::launch_half<W_, 2>(__VA_ARGS__); \
-                              else if (ht_ == 3) { ST_TRY((stg::launch_half<W_, 1, 3>(__VA_ARGS__))); } \
-                              else if (g_xt) { if ((BK_) == 16) stg::launch<W_, 16, true>(__VA_ARGS__); else stg::launch<W_, 32, true>(__VA_ARGS__); } \
-                              else if ((BK_) == 16) stg::launch<W_, 16>(__VA_ARGS__); else stg::launch<W_, 32>(__VA_ARGS__); } while (0)
-#define ST_GEMM(W_, ...) ST_GEMM_BK(g_bk, W_, __VA_ARGS__)
-// the analysis forward GEMM (K = N = 1024, two 4-wave workgroups per CU either way) runs 5 % faster with 32-deep k-tiles
-// (half the barriers); every other GEMM of the step is faster with 16 (more workgroups per CU)
-#define ST_GEMM_AN(W_, ...) ST_GEMM_BK(g_an_bk, W_, __VA_ARGS__)
-// ST_PREC_F32X3: the weight-gradient GEMMs reduce along the ROWS of both operands (k-major staging, 4x4 register transposes); their
-// in-kernel three-plane split measured slower than the fp32 MFMA kernel (176 vs 141 us, 62 vs 55 us at B = 256), so that precision
-// level keeps them on the fp32 kernel (st_set_tuning(9301) selects the split form).
-#define ST_GEMM_WG(...) do { if (g_wg_mode == 2 && gemm_ht(d->prec) == 0) stg::launch<3, 16, true>(__VA_ARGS__); \
-                             else if (gemm_ht(d->prec) == 3 && !g_wg_split) stg::launch<3, 16>(__VA_ARGS__); else ST_GEMM(3, __VA_ARGS__); } while (0)
 // Kernels with > 64 KB of dynamic LDS need the attribute once per (device, kernel); the result is checked (round 1 discarded
 // it behind non-atomic flags: a failure surfaced later as an opaque launch error).
 static int ensure_dyn_lds(const void* fn, const char* name)
@@ -339,6 +324,29 @@ template <class F> static inline auto with_slabs(int ns, F&& f) { return ns == 3
 static const int AE_FWD_NW = 8, AE_BWD_NW = 4;
 template <class F> static inline auto with_fwd_nw(int nw, F&& f) { return nw == 11 ? f(ic<11>{}) : f(ic<AE_FWD_NW>{}); }                             // ae_fwd_nw: {8, 11}
 template <class F> static inline auto with_inner_nw(int nw, F&& f) { return nw == 9 ? f(ic<9>{}) : nw == 12 ? f(ic<12>{}) : f(ic<AE_FWD_NW>{}); }   // ae_inner_nw: {8, 9, 12}
+// The small-tile GEMM (st_gemm.h: W waves share a (32 W) x 96 tile) at the arithmetic of `prec`: the converting gemm_half_kernel for the 16-bit levels and for
+// ST_PREC_F32X3 (its in-kernel three-plane split), else the fp32 MFMA kernel with bk-deep k-tiles (16: 36 KB LDS/WG -> 4 WGs/CU; 32: 64 KB -> 2 WGs/CU) on the
+// k-major or (xt) k-quad-major staging.  Every launcher's return code is the function's.
+template <int W, class AL, class BL, class EPI>
+static int small_gemm(int prec, int bk, bool xt, const AL& al, const BL& bl, const EPI& ep, int M, int Nc, int K, int ns, hipStream_t s)
+{
+    const int ht = gemm_ht(prec);
+    if (ht == 3) return stg::launch_half<W, 1, 3>(al, bl, ep, M, Nc, K, ns, s);
+    if (ht != 0) return with_ht16(ht, [&](auto HT) { return stg::launch_half<W, HT()>(al, bl, ep, M, Nc, K, ns, s); });
+    with_bool(xt, [&](auto XT) { if (bk == 16) stg::launch<W, 16, XT()>(al, bl, ep, M, Nc, K, ns, s); else stg::launch<W, 32, XT()>(al, bl, ep, M, Nc, K, ns, s); });
+    return ST_OK;
+}
+// The 96 x 96 three-wave form of the weight-gradient GEMMs (WG_96).  ST_PREC_F32X3: they reduce along the ROWS of both operands (k-major staging, 4x4 register
+// transposes); their in-kernel three-plane split measured slower than the fp32 MFMA kernel (176 vs 141 us, 62 vs 55 us at B = 256), so that precision level keeps
+// them on the fp32 kernel (st_set_tuning(9301) selects the split form).
+template <class AL, class BL, class EPI>
+static int wgrad_small_gemm(int prec, const AL& al, const BL& bl, const EPI& ep, int M, int Nc, int K, int ns, hipStream_t s)
+{
+    const int ht = gemm_ht(prec);
+    if (g_wg_mode == 2 && ht == 0) { stg::launch<3, 16, true>(al, bl, ep, M, Nc, K, ns, s); return ST_OK; }
+    if (ht == 3 && !g_wg_split) { stg::launch<3, 16>(al, bl, ep, M, Nc, K, ns, s); return ST_OK; }
+    return small_gemm<3>(prec, g_bk, g_xt != 0, al, bl, ep, M, Nc, K, ns, s);
+}
 static int synth_live_rows(const st_dims* d);
 static bool ae_is_wide(const st_dims* d);
 // Waves per workgroup of the fused forward kernel: 8, or 11 where that removes the tail round.  A wave walks whole 16-row groups,
@@ -380,7 +388,7 @@ static int wgrad_split(int R) { int s = R / WSPLIT_ROWS; if (s < 1) s = 1; if (s
 // (wgrad_area_slabs): no rule exceeds it.  The two whole-tensor fp32 rules are what the area is sized by (over all B * T frames, on the device's CU count), so
 // there the cap binds only when a query assumes more CUs than the device has.  ncus > 0 makes the function pure given its arguments (the host queries);
 // otherwise the current device's CU count.
-enum { WG_TN128 = 0, WG_96 = 1, WG_TN16 = 2 };      // the 128 x 128 TN kernel (st_gemm_tn.h), the 96 x 96 three-wave kernel behind ST_GEMM_WG, the 16-bit TN kernel (st_gemm16.h)
+enum { WG_TN128 = 0, WG_96 = 1, WG_TN16 = 2 };      // the 128 x 128 TN kernel (st_gemm_tn.h), the 96 x 96 three-wave kernel behind wgrad_small_gemm, the 16-bit TN kernel (st_gemm16.h)
 static int wgrad_slices(int form, bool one_basis, int R, int KP, int N, int room, int ncus = 0)
 {
     const int cus = ncus > 0 ? ncus : num_cus(), M = one_basis ? KP / 2 : KP;
@@ -422,8 +430,12 @@ static int wgrad_slices(int form, bool one_basis, int R, int KP, int N, int room
     if (s > room) s = room;      // every form, whatever CU count is assumed: never more slabs than the workspace area holds
     return s < 1 ? 1 : s;
 }
-static int synth_split(int R) { return R >= 4096 ? 1 : 3; }   // consumers (ola_loss_kernel, ae_bwd_kernel) sum at most 3 slabs
-static int dgrad_slabs(int R) { return synth_split(R); }      // split-K slabs of the synthesis data-gradient GEMM over R live rows
+// The two synthesis GEMMs (frames, data gradient) over R live rows: from STFT_TALL_ROWS rows on, 4-wave tiles (128 rows) and the whole reduction in one slab
+// fill the chip; below, 2-wave tiles (64 rows) and K split over 3 slabs (frames GEMM: 3, 4 measured equal, 6 slower -- only 66 k-tiles to split).  The consumers
+// (ola_loss_kernel, ae_bwd_kernel: with_slabs) sum at most 3 slabs; the workspace (carve) holds as many as this rule says, for every operand family.
+static const int STFT_TALL_ROWS = 4096;
+struct SynthTile { int waves, ns; };
+static SynthTile synth_tile(int R) { return R >= STFT_TALL_ROWS ? SynthTile{4, 1} : SynthTile{2, 3}; }
 
 // Sizes for internal code, which holds checked dims; the extern "C" functions of these names ask check_dims first
 // (the host size functions answer 0 for dims outside the supported family, with the rule in st_last_error(): check_dims)
@@ -448,12 +460,10 @@ static size_t wgrad_ws_floats(const st_dims* d)
     return (size_t)wgrad_area_slabs(d) * st_kp_of(d->F) * d->N + (size_t)WGRAD_NYQ_MAX * 2 * d->N;
 }
 extern "C" size_t st_wgrad_ws_floats(const st_dims* d) { return check_dims(d) != ST_OK ? 0 : wgrad_ws_floats(d); }
-static int synth_slabs(const st_dims* d) { return dgrad_slabs(synth_live_rows(d)); }
+// split-K slabs of the synthesis data-gradient GEMM (dAA; summed inside ae_bwd_kernel) and of the synthesis frames GEMM (frs; summed by ola_loss_kernel): synth_tile
+static int synth_slabs(const st_dims* d) { return synth_tile(synth_live_rows(d)).ns; }
 extern "C" int st_synth_slabs(const st_dims* d) { return check_dims(d) != ST_OK ? 0 : synth_slabs(d); }
-// split-K slabs of the synthesis FRAMES GEMM (summed by ola_loss_kernel, which takes up to 6; the dgrad slabs are summed
-// inside ae_bwd_kernel where every extra slab costs 8 loads per row group, hence the separate, smaller count above)
-static int frames_split(int R) { return R >= 4096 ? 1 : 3; }      // 3, 4 measured equal, 6 slower (only 66 k-tiles to split)
-static int frame_slabs(const st_dims* d) { return frames_split(synth_live_rows(d)); }
+static int frame_slabs(const st_dims* d) { return synth_tile(synth_live_rows(d)).ns; }
 extern "C" int st_synth_frame_slabs(const st_dims* d) { return check_dims(d) != ST_OK ? 0 : frame_slabs(d); }
 // Wide geometries (T > 32 or OT > 16) run the autoencoders as feature-major GEMMs (st_ae_wide.h) and need workspace
 // for the activations [features][B*FP]; the fused kernels of st_ae.h need none in forward.
@@ -559,34 +569,6 @@ static int ae_wide_fwd(const st_dims* d, const Layout& L, const float* mag, cons
 // Feature-major destination of the polar epilogue on wide geometries (st_gemm.h PolarStore::Vm / Vp): the wide autoencoder path's input layout
 struct PolarWide { float* Vm; float* Vp; int FP; unsigned RV; };
 static inline void polar_wide_set(stg::PolarStore& ep, const PolarWide* pw) { if (pw && pw->Vm) { ep.Vm = pw->Vm; ep.Vp = pw->Vp; ep.FP = pw->FP; ep.RV = pw->RV; } }
-// `padded`: sig is the workspace copy [B][N + L + N] (zero margins, input scale applied) written by pad_scale_kernel.
-static int analysis_fwd_impl(const st_dims* d, const float* sig, bool padded, const float* Wr, const float* Wi, float in_scale,
-                             float* re, float* im, float* mag, float* phs, void* stream, bool dead_frames_done = false, const PolarWide* pw = nullptr)
-{
-    const stg::RowMap map = stg::live_frames(d->T, d->H, d->N, d->N, d->L);   // frames entirely inside the Conv1d padding are skipped
-    const int R = map.rows(d->B);
-    stg::AnalysisW bl{Wr, Wi, d->F, d->N};
-    stg::PolarStore ep{re, im, mag, phs, R, d->F, map};
-    polar_wide_set(ep, pw);
-    if (padded) {
-        stg::FramedNT<true> al{sig, d->L, d->H, d->N, R, d->N, 1.0f, map};
-        ST_GEMM_AN(4, al, bl, ep, R, 2 * d->F, d->N, 1, st_stream(stream));
-    }
-    else { stg::FramedNT<false> al{sig, d->L, d->H, d->N, R, d->N, in_scale, map}; ST_GEMM(4, al, bl, ep, R, 2 * d->F, d->N, 1, st_stream(stream)); }
-    ST_LAUNCHED("analysis_fwd");
-    if (map.Tv < d->T && !dead_frames_done) {   // ... and are exact zeros (re=im=mag=0, phs=atan2(0,1e-7)=0)
-        hipLaunchKernelGGL(stm::zero_dead_frames_kernel, dim3(d->B * (d->T - map.Tv)), dim3(256), 0, st_stream(stream),
-                           re, im, mag, phs, d->T, d->F, map.t_lo, map.Tv);
-        ST_LAUNCHED("zero_dead_frames");
-    }
-    return ST_OK;
-}
-extern "C" int st_analysis_fwd(const st_dims* d, const float* x, const float* Wr, const float* Wi, float in_scale,
-                               float* re, float* im, float* mag, float* phs, void* stream)
-{
-    ST_TRY(check_dims(d)); ST_REQ(x && Wr && Wi, "st_analysis_fwd: null input");
-    return analysis_fwd_impl(d, x, false, Wr, Wi, in_scale, re, im, mag, phs, stream);
-}
 static int pad_scale(const float* in, float* out, int B, int Ls, int pad, float s, void* stream)
 {
     hipLaunchKernelGGL(stm::pad_scale_kernel, dim3(((Ls + 2 * pad) / 4 + 255) / 256, B), dim3(256), 0, st_stream(stream), in, out, Ls, pad, s);
@@ -655,13 +637,6 @@ extern "C" int st_synth_fold(const st_dims* d, const float* Sr, const float* Si,
 static stg::RowMap synth_live(const st_dims* d) { return stg::live_frames(d->OT, d->H, d->N, d->N, d->y); }
 static int synth_live_rows(const st_dims* d) { return synth_live(d).rows(d->B); }
 
-// SfoldT != NULL: the transposed fold [N][KP] the fused forward builds (prep_kernel) -- both operands K-contiguous
-static int synthesis_frames_impl(const st_dims* d, const float* AA, const float* Sfold, const float* SfoldT, float* frs, void* stream);
-extern "C" int st_synthesis_frames(const st_dims* d, const float* AA, const float* Sfold, float* frs, void* stream)
-{
-    ST_TRY(check_dims(d)); ST_REQ(AA && Sfold && frs, "st_synthesis_frames: null pointer");
-    return synthesis_frames_impl(d, AA, Sfold, nullptr, frs, stream);
-}
 // Fraction of the synthesis frames' taps that the crop of cls_fe_dft.py:113 throws away (the structural zeros the work list skips): 25 % at the 8192-sample window
 // (7 live frames), 4 % at the 65536-sample window (44 live frames)
 static double synth_crop_fraction(const st_dims* d)
@@ -687,33 +662,197 @@ static bool use_nt128(const st_dims* d, int M, int Nc, int ncus = 0)      // a p
     if (ncus <= 0) ncus = num_cus();
     return ((M + 127) / 128) * ((Nc + 127) / 128) * 2 <= ncus || synth_crop_fraction(d) >= 0.10;
 }
-static int synthesis_frames_impl(const st_dims* d, const float* AA, const float* Sfold, const float* SfoldT, float* frs, void* stream)
+// ------------------------------------------------------------------------------ the forward and data-gradient GEMMs: plan, launch
+// The three STFT GEMMs that are no weight gradient -- the analysis forward (frames of x / 2 times the analysis bases, polar epilogue), the synthesis frames
+// (spectra times the folded synthesis bases) and the synthesis data gradient (frames of d syn times the fold) -- decided in one place (stft_plan; it launches
+// nothing) for the per-op entries, the fused steps, st_predict_long and the host queries (st_stft_plan, st_nt128_worklist), and launched in one (stft_gemm).
+enum { GEMM_ANALYSIS = 0, GEMM_FRAMES = 1, GEMM_DGRAD = 2 };
+enum { SGP_PADDED = 1,         // operands in the padded workspace layout (the fused entries); else the per-op entries' unpadded signal with its in_scale
+       SGP_G16 = 2,            // the entry asks for the 16-bit operand pipeline (WS::g16 is its answer)
+       SGP_SFOLDT = 4 };       // the transposed fold [N][KP] is there (the fused forward builds it: prep_kernel) -- both operands of the frames GEMM K-contiguous
+enum { GF_FP32 = 0,            // fp32 operands, fp32 MFMA
+       GF_HALF = 1,            // fp32 operands converted as they are staged: gemm_half_kernel (bf16 / f16 / the in-kernel three-plane split of ST_PREC_F32X3)
+       GF_PLANES = 2,          // bfloat16 planes of the once-per-step operands (st_gemm_planes.h; planes_prepare writes them)
+       GF_G16 = 3 };           // the 16-bit operand pipeline (st_gemm16.h): every operand pre-rounded by its producer
+enum { GK_SMALL = 0,           // gemm_kernel / gemm_half_kernel: `waves` waves share a (32 waves) x 96 tile (small_gemm)
+       GK_NT128 = 1,           // the 128 x 128 work-list kernel (st_gemm_tn.h) on the plan's NTWork list
+       GK_PLANES = 2,          // gemm_planes_kernel, `waves` x (32 x 96)
+       GK_NT16 = 3, GK_NT256 = 4 };      // launch16_nt / the LDS-DMA kernel behind launch16_nt256
+// The operand family: the ONE statement of the rule.  The per-op entries have fp32 operands and nothing else; a fused entry runs the 16-bit pipeline where it
+// asks for it and use_g16 admits the precision, else the plane kernel where use_planes does (ST_PREC_F32X3; the bf16 levels under g_pl_bf16, which turns the
+// 16-bit pipeline off) -- the data gradient only under g_pl_dgrad (measured slower than the fp32 MFMA kernel) --, else the kernels of the per-op entries.
+static bool use_planes(const st_dims* d) { return (gemm_ht(d->prec) == 3 || (gemm_ht(d->prec) == 1 && g_pl_bf16)) && d->N % 16 == 0 && st_kp_of(d->F) % 16 == 0; }
+static int planes_of(const st_dims* d) { return gemm_ht(d->prec) == 3 ? 3 : 1; }
+template <class F> static inline auto with_planes(int pl, F&& f) { return pl == 1 ? f(ic<1>{}) : f(ic<3>{}); }
+static bool use_g16(const st_dims* d)
 {
-    const int KP = st_kp_of(d->F);
-    const stg::RowMap ms = synth_live(d);      // output frames that land wholly in the cropped margins are never needed
-    const int R = ms.rows(d->B);
-    stg::PlainNT al{AA, R, KP, KP, ms};
-    stg::PlainTN bl{Sfold, KP, d->N, d->N, stg::all_frames(1)};
-    // frs holds st_synth_frame_slabs() split-K slabs [B*OT, N]; st_ola_loss sums them
-    stg::StoreC ep{frs, R, d->N, d->N, (size_t)d->B * d->OT * d->N, ms};
-    if (SfoldT && g_frs_nt) {
-        stg::PlainNT bt{SfoldT, d->N, KP, KP, stg::all_frames(1)};
-        stg::NTWork wk;
-        if (use_nt128(d, R, d->N) && stg::ntw_frames(wk, ms, d->B, d->H, d->N, d->N, d->y, KP, frames_split(R), num_cus())) {
-            // frame-major rows; only the tile columns whose taps survive the crop (cls_fe_dft.py:113): the others are never read by ola_loss_kernel
-            const stg::NTRows ra = stg::ntrows_frame_major(AA, (unsigned)(d->OT * KP), (unsigned)KP, ms, d->B, R), rb{SfoldT, (unsigned)KP, 0u, 0u, 1, 0, d->N};
-            const stg::StoreSlab es{frs, R, d->N, d->N, (size_t)d->B * d->OT * d->N, stg::frame_major(ms, d->B)};
-            ST_TRY(stg::launch_nt128(ra, rb, es, wk, st_stream(stream)));
-        }
-        else if (R >= 4096) ST_GEMM(4, al, bt, ep, R, d->N, KP, 1, st_stream(stream));
-        else ST_GEMM(2, al, bt, ep, R, d->N, KP, frames_split(R), st_stream(stream));
+    const int ht = gemm_ht(d->prec);
+    return g_g16 && (ht == 1 || ht == 2) && !g_pl_bf16 && d->N % 128 == 0 && num_cus() > 0;
+}
+static int stft_family(const st_dims* d, int which, int flags)
+{
+    if (flags & SGP_PADDED) {
+        if ((flags & SGP_G16) && use_g16(d)) return GF_G16;
+        if (use_planes(d) && (which != GEMM_DGRAD || g_pl_dgrad)) return GF_PLANES;
     }
-    else if (R >= 4096) ST_GEMM(4, al, bl, ep, R, d->N, KP, 1, st_stream(stream));
-    else ST_GEMM(2, al, bl, ep, R, d->N, KP, frames_split(R), st_stream(stream));
-    ST_LAUNCHED("synthesis_frames"); return ST_OK;
+    return gemm_ht(d->prec) == 0 ? GF_FP32 : GF_HALF;
+}
+// The operand pointers of whichever family is taken.  A: the signal (x, or the padded x / 2), the spectra AA, d syn.  B: Wr, Sfold, Sfold; B2: Wi resp. the
+// transposed fold.  A16 / B16: the 16-bit copies (B16 of the frames GEMM: SfoldT16).  Bpl: the plane copy of B (frames GEMM: of the transposed fold).
+struct GemmOps { const float *A, *B, *B2; const unsigned short *A16, *B16, *Bpl; float in_scale; };
+struct GemmPlan {
+    const st_dims* d; GemmOps o;
+    int which, flags, family, form;
+    int waves, bk, xt;          // GK_SMALL / GK_PLANES: waves per workgroup (tile height 32 * waves); GK_SMALL on GF_FP32: k-tile depth, k-quad-major staging (g_xt); else 0
+    bool transposed;            // frames GEMM on GK_SMALL / GK_NT128: B is the transposed fold (SGP_SFOLDT and g_frs_nt)
+    stg::RowMap live;           // the frames with a tap inside the signal, window-major
+    int R, M, Nc, K, ns;        // live rows; the GEMM is M = R x Nc over K; split-K slabs
+    size_t slab;                // slab stride of the output (frs, dAA)
+    bool frame_major; int crop; // rows enumerated frame-major; structural zeros of the crop (cls_fe_dft.py:113) skipped: 0 none, 1 the frames GEMM's dead tile columns,
+                                // 2 the data gradient's dead taps per tile row -- stg::Crop16::mode on GF_G16, the work list on GK_NT128
+    stg::NTWork wk;             // GK_NT128: the list, built here once (wk.n = 0 on every other form)
+};
+// ncus > 0 makes the plan a pure function of its arguments and the tuning state (the host queries); otherwise the current device's CU count.
+static GemmPlan stft_plan(const st_dims* d, int which, int flags, const GemmOps& o, int ncus = 0)
+{
+    const int KP = st_kp_of(d->F), N = d->N;
+    const bool padded = (flags & SGP_PADDED) != 0;
+    GemmPlan p; p.d = d; p.o = o; p.which = which; p.flags = flags;
+    p.live = which == GEMM_ANALYSIS ? stg::live_frames(d->T, d->H, N, N, d->L)      // frames entirely inside the Conv1d padding are skipped
+                                    : synth_live(d);                                // output frames that land wholly in the cropped margins are never needed
+    p.R = p.M = p.live.rows(d->B);
+    p.Nc = which == GEMM_ANALYSIS ? 2 * d->F : which == GEMM_FRAMES ? N : KP; p.K = which == GEMM_FRAMES ? KP : N;
+    // the analysis forward (Nc = 2 F columns) fills the chip with 4-wave tiles and one slab at every batch; the synthesis pair by synth_tile
+    const SynthTile t = which == GEMM_ANALYSIS ? SynthTile{4, 1} : synth_tile(p.R);
+    p.waves = t.waves; p.ns = t.ns; p.slab = which == GEMM_ANALYSIS ? 0 : (size_t)d->B * d->OT * p.Nc;
+    p.family = stft_family(d, which, flags);
+    p.bk = p.xt = 0; p.transposed = false; p.frame_major = false; p.crop = 0; p.wk.n = 0;
+    if (p.family == GF_G16) {
+        // g_g16_dma: bit 0 the analysis forward, bit 1 the data gradient on the LDS-DMA kernel (64-deep k-tiles, at least one per slab); it has no crop
+        const int dma = which == GEMM_ANALYSIS ? 1 : which == GEMM_DGRAD ? 2 : 0;
+        p.form = ((g_g16_dma & dma) && N % 64 == 0 && N / 64 >= p.ns) ? GK_NT256 : GK_NT16; p.waves = 0;
+        // g_g16_crop: bit 0 the frames GEMM, bit 1 the data gradient (off wherever g_g16_dma asks for the DMA kernel); on the frame-major row order
+        const bool crop = which == GEMM_FRAMES ? (g_g16_crop & 1) != 0 : which == GEMM_DGRAD && (g_g16_crop & 2) && !(g_g16_dma & 2);
+        if (crop && fm_div_exact(p.R, d->B)) { p.frame_major = true; p.crop = which; }
+    } else if (p.family == GF_PLANES) {
+        p.form = GK_PLANES;
+        if (which == GEMM_ANALYSIS && planes_of(d) == 3 && g_pl_shape == 3) p.waves = 8;      // 256 x 96, one workgroup per CU
+    } else {
+        p.form = GK_SMALL;
+        p.transposed = which == GEMM_FRAMES && (flags & SGP_SFOLDT) && g_frs_nt;
+        const int cus = ncus > 0 ? ncus : num_cus();
+        // the work-list kernel takes K-contiguous operands in the padded layout; whether a list fits (and with how many k-slices) is the builder's decision
+        if ((which == GEMM_FRAMES ? p.transposed : which == GEMM_DGRAD && padded) && use_nt128(d, p.R, p.Nc, cus) &&
+            (which == GEMM_FRAMES ? stg::ntw_frames(p.wk, p.live, d->B, d->H, N, N, d->y, KP, p.ns, cus)
+                                  : stg::ntw_dgrad(p.wk, p.live, d->B, d->H, N, N, d->y, d->F, KP, p.ns, cus))) {
+            p.form = GK_NT128; p.waves = 0; p.frame_major = true; p.crop = which;
+        } else {
+            p.wk.n = 0;
+            // the padded analysis forward (K = N = 1024, two 4-wave workgroups per CU either way) runs 5 % faster with 32-deep k-tiles (half the barriers);
+            // every other GEMM of the step is faster with 16 (more workgroups per CU)
+            if (p.family == GF_FP32) { p.bk = (which == GEMM_ANALYSIS && padded) ? g_an_bk : g_bk; p.xt = g_xt ? 1 : 0; }
+        }
+    }
+    return p;
+}
+// Where a plan's GEMM writes: re / im / mag / phs [B][T][F] (any may be NULL) and, on wide geometries, the feature-major copy `pw` of the analysis forward;
+// C = frs (ns slabs [B * OT][N]; st_ola_loss sums them) resp. dAA (ns slabs [B * OT][KP]; st_ae_bwd sums them and treats the rows of dead frames, which are
+// NOT written, as zero) of the synthesis pair.
+struct GemmOut { float *re, *im, *mag, *phs; const PolarWide* pw; float* C; };
+static GemmOut slabs_at(float* C) { return GemmOut{nullptr, nullptr, nullptr, nullptr, nullptr, C}; }
+// The GEMM of a plan, whatever its family and form.  Rows of the data gradient: dfrs[b, t, n] = dfull[b, H t + n] with dfull = zero-pad(d syn, N each side).
+static int stft_gemm(const GemmPlan& p, const GemmOut& out, void* stream)
+{
+    const st_dims* d = p.d; const GemmOps& o = p.o; hipStream_t s = st_stream(stream);
+    const int KP = st_kp_of(d->F), N = d->N, R = p.R;
+    const stg::RowMap rows = p.frame_major ? stg::frame_major(p.live, d->B) : p.live;      // the epilogue's row order
+    auto g16 = [&](const stg::Rows16& ra, const stg::Rows16& rb, const auto& ep, const stg::Crop16* cr) {
+        return with_ht16(gemm_ht(d->prec), [&](auto HT) {
+            return p.form == GK_NT256 ? stg::launch16_nt256<HT()>(ra, rb, ep, p.M, p.Nc, p.K, p.ns, s) : stg::launch16_nt<HT()>(ra, rb, ep, p.M, p.Nc, p.K, p.ns, s, cr); }); };
+    if (p.which == GEMM_ANALYSIS) {
+        stg::PolarStore ep{out.re, out.im, out.mag, out.phs, R, d->F, rows};
+        polar_wide_set(ep, out.pw);
+        if (p.family == GF_G16)
+            ST_TRY(g16(stg::rows16(o.A16, (unsigned)(d->L + 2 * N), (unsigned)d->H, p.live, R), stg::rows16_plain(o.B16, (unsigned)N, 2 * d->F), ep, nullptr));
+        else if (!(p.flags & SGP_PADDED)) {
+            stg::FramedNT<false> al{o.A, d->L, d->H, N, R, N, o.in_scale, p.live};
+            ST_TRY(small_gemm<4>(d->prec, p.bk, p.xt != 0, al, stg::AnalysisW{o.B, o.B2, d->F, N}, ep, p.M, p.Nc, p.K, p.ns, s));
+        } else {      // the workspace copy [B][N + L + N] (zero margins, input scale applied)
+            stg::FramedNT<true> al{o.A, d->L, d->H, N, R, N, 1.0f, p.live};
+            if (p.family == GF_PLANES) {
+                stg::ChunkP bl{o.Bpl, 2 * d->F};
+                ST_TRY((planes_of(d) == 1 ? stg::launch_planes<4, 1>(al, bl, ep, p.M, p.Nc, p.K, p.ns, s) :
+                        p.waves == 8 ? stg::launch_planes<8, 3>(al, bl, ep, p.M, p.Nc, p.K, p.ns, s) : stg::launch_planes<4, 3>(al, bl, ep, p.M, p.Nc, p.K, p.ns, s)));
+            } else ST_TRY(small_gemm<4>(d->prec, p.bk, p.xt != 0, al, stg::AnalysisW{o.B, o.B2, d->F, N}, ep, p.M, p.Nc, p.K, p.ns, s));
+        }
+        ST_LAUNCHED("analysis_fwd");
+        return ST_OK;
+    }
+    const bool frames = p.which == GEMM_FRAMES;
+    const unsigned s_win = frames ? (unsigned)(d->OT * KP) : (unsigned)(d->y + 2 * N), s_frm = frames ? (unsigned)KP : (unsigned)d->H;      // A's window and frame strides
+    auto small = [&](const auto& al, const auto& bl) {
+        const stg::StoreC ep{out.C, R, p.Nc, p.Nc, p.slab, rows};
+        return p.waves == 4 ? small_gemm<4>(d->prec, p.bk, p.xt != 0, al, bl, ep, p.M, p.Nc, p.K, p.ns, s) : small_gemm<2>(d->prec, p.bk, p.xt != 0, al, bl, ep, p.M, p.Nc, p.K, p.ns, s); };
+    auto planes = [&](const auto& al) {
+        const stg::StoreC ep{out.C, R, p.Nc, p.Nc, p.slab, rows}; const stg::ChunkP bl{o.Bpl, p.Nc};
+        return with_planes(planes_of(d), [&](auto PL) {
+            return p.waves == 4 ? stg::launch_planes<4, PL()>(al, bl, ep, p.M, p.Nc, p.K, p.ns, s) : stg::launch_planes<2, PL()>(al, bl, ep, p.M, p.Nc, p.K, p.ns, s); }); };
+    if (p.family == GF_G16) {
+        // crop 1: tile columns without a tap inside the crop are not computed (ola_loss_kernel never reads them); 2: per tile row only the taps that lie inside
+        // d syn (the rest of the padded copy is zeros)
+        const stg::Rows16 ra = p.frame_major ? stg::rows16_frame_major(o.A16, s_win, s_frm, p.live, d->B, R) : stg::rows16(o.A16, s_win, s_frm, p.live, R);
+        const stg::Crop16 cr{p.crop, d->B, d->H, N, N, d->y, p.live.t_lo, R, 1};
+        ST_TRY(g16(ra, stg::rows16_plain(o.B16, (unsigned)p.K, p.Nc), stg::StoreC{out.C, R, p.Nc, p.Nc, p.slab, rows}, &cr));
+    } else if (p.form == GK_NT128) {
+        // frame-major rows.  Frames GEMM: only the tile columns whose taps survive the crop.  Data gradient: per tile row only the taps inside d syn (the margins
+        // of the padded copy are zeros), the Nyquist columns apart
+        const stg::NTRows ra = stg::ntrows_frame_major(o.A, s_win, s_frm, p.live, d->B, R);
+        const stg::NTRows rb = frames ? stg::NTRows{o.B2, (unsigned)KP, 0u, 0u, 1, 0, N} :
+                               p.wk.col_h ? stg::NTRows{o.B, (unsigned)((KP / 2) * N), (unsigned)N, stg::rowmap_magic(d->F - 1), d->F - 1, 0, 2 * (d->F - 1)}
+                                          : stg::NTRows{o.B, (unsigned)N, 0u, 0u, 1, 0, KP};
+        ST_TRY(stg::launch_nt128(ra, rb, stg::StoreSlab{out.C, R, p.Nc, p.Nc, p.slab, rows}, p.wk, s));
+    } else if (frames) {
+        const stg::PlainNT al{o.A, R, KP, KP, p.live};
+        if (p.family == GF_PLANES) ST_TRY(planes(al));
+        else if (p.transposed) ST_TRY(small(al, stg::PlainNT{o.B2, N, KP, KP, stg::all_frames(1)}));
+        else ST_TRY(small(al, stg::PlainTN{o.B, KP, N, N, stg::all_frames(1)}));
+    } else {
+        const stg::PlainNT bl{o.B, KP, N, N, stg::all_frames(1)};
+        if (!(p.flags & SGP_PADDED)) ST_TRY(small(stg::FramedNT<false>{o.A, d->y, d->H, N, R, N, 1.0f, p.live}, bl));
+        else {
+            const stg::FramedNT<true> al{o.A, d->y, d->H, N, R, N, 1.0f, p.live};
+            if (p.family == GF_PLANES) ST_TRY(planes(al)); else ST_TRY(small(al, bl));
+        }
+    }
+    ST_LAUNCHED(frames ? "synthesis_frames" : "synthesis_dgrad");
+    return ST_OK;
+}
+extern "C" int st_analysis_fwd(const st_dims* d, const float* x, const float* Wr, const float* Wi, float in_scale,
+                               float* re, float* im, float* mag, float* phs, void* stream)
+{
+    ST_TRY(check_dims(d)); ST_REQ(x && Wr && Wi, "st_analysis_fwd: null input");
+    const GemmPlan p = stft_plan(d, GEMM_ANALYSIS, 0, GemmOps{x, Wr, Wi, nullptr, nullptr, nullptr, in_scale});
+    ST_TRY(stft_gemm(p, GemmOut{re, im, mag, phs, nullptr, nullptr}, stream));
+    if (p.live.Tv < d->T) {   // the skipped frames are exact zeros (re=im=mag=0, phs=atan2(0,1e-7)=0); the fused entries fill them in prep_kernel
+        hipLaunchKernelGGL(stm::zero_dead_frames_kernel, dim3(d->B * (d->T - p.live.Tv)), dim3(256), 0, st_stream(stream),
+                           re, im, mag, phs, d->T, d->F, p.live.t_lo, p.live.Tv);
+        ST_LAUNCHED("zero_dead_frames");
+    }
+    return ST_OK;
+}
+extern "C" int st_synthesis_frames(const st_dims* d, const float* AA, const float* Sfold, float* frs, void* stream)
+{
+    ST_TRY(check_dims(d)); ST_REQ(AA && Sfold && frs, "st_synthesis_frames: null pointer");
+    return stft_gemm(stft_plan(d, GEMM_FRAMES, 0, GemmOps{AA, Sfold, nullptr, nullptr, nullptr, nullptr, 1.0f}), slabs_at(frs), stream);
+}
+extern "C" int st_synthesis_dgrad(const st_dims* d, const float* dsyn, const float* Sfold, float* dAA, void* stream)
+{
+    ST_TRY(check_dims(d)); ST_REQ(dsyn && Sfold && dAA, "st_synthesis_dgrad: null pointer");
+    return stft_gemm(stft_plan(d, GEMM_DGRAD, 0, GemmOps{dsyn, Sfold, nullptr, nullptr, nullptr, nullptr, 1.0f}), slabs_at(dAA), stream);
 }
 
-// Host-side view of the work list of the 128 x 128-tile synthesis GEMMs (st_gemm_tn.h, round 5): which = 0 the frames GEMM, 1 the data gradient.
+// Host-side view of the work list of the 128 x 128-tile synthesis GEMMs (st_gemm_tn.h, round 5): which = 0 the frames GEMM, 1 the data gradient -- the list of the
+// plan a fused entry on fp32 operands launches.
 // out[i] = the packed entry i (tile row (8 bits) | tile column (6) << 8 | slab (2) << 14 | first zero-filled slab (2; 0 = none) << 16 | kind (1) << 18 | first k unit (6) << 19 |
 // k units (7) << 25); head6 = {slabs, col_h, col_stride, frame-major windows per frame, k-tiles (of 32) per k unit, k-tiles of the whole reduction}.  Returns the number of
 // entries (= workgroups), 0 when this geometry does not run on the work-list kernel, < 0 on bad arguments.  No device work: the CPU test-suite checks the list against the
@@ -721,18 +860,26 @@ static int synthesis_frames_impl(const st_dims* d, const float* AA, const float*
 extern "C" int st_nt128_worklist(const st_dims* d, int which, int ncus, unsigned* out, int cap, int* head6)
 {
     if (check_dims(d) != ST_OK || !out || !head6 || cap < 0 || (which != 0 && which != 1)) return -1;
-    const int KP = st_kp_of(d->F);
-    const stg::RowMap ms = synth_live(d);
-    const int R = ms.rows(d->B);
-    if (ncus <= 0) ncus = num_cus();
-    stg::NTWork wk; wk.n = 0;
-    if (!use_nt128(d, R, which ? KP : d->N, ncus)) return 0;
-    const bool ok = which ? stg::ntw_dgrad(wk, ms, d->B, d->H, d->N, d->N, d->y, d->F, KP, dgrad_slabs(R), ncus)
-                          : stg::ntw_frames(wk, ms, d->B, d->H, d->N, d->N, d->y, KP, frames_split(R), ncus);
-    if (!ok) return 0;
+    const GemmPlan p = stft_plan(d, which ? GEMM_DGRAD : GEMM_FRAMES, SGP_PADDED | SGP_SFOLDT, GemmOps{}, ncus);
+    if (p.form != GK_NT128) return 0;
+    const stg::NTWork& wk = p.wk;
     head6[0] = wk.nslabs; head6[1] = wk.col_h; head6[2] = wk.col_stride; head6[3] = d->B; head6[4] = wk.kunit; head6[5] = wk.kt_total;
     for (int i = 0; i < wk.n && i < cap; ++i) out[i] = wk.e[i];
     return wk.n;
+}
+// Host-side view of ONE of the three GEMMs (no device work): the plan the launches themselves ask for, as ST_STFT_PLAN_INTS ints (signaltrain_hip.h).
+// which: ST_STFT_*; flags: ST_STFTPLAN_*; ncus <= 0: the current device's CU count -- then the answer is what a launch on this device does under the current
+// tuning state.  Fills min(cap, count) ints and returns the count; < 0 on bad arguments.
+extern "C" int st_stft_plan(const st_dims* d, int which, int flags, int ncus, int* out, int cap)
+{
+    static_assert(ST_STFT_ANALYSIS == GEMM_ANALYSIS && ST_STFT_FRAMES == GEMM_FRAMES && ST_STFT_DGRAD == GEMM_DGRAD, "st_stft_plan: which values");
+    static_assert(ST_STFTPLAN_PADDED == SGP_PADDED && ST_STFTPLAN_G16 == SGP_G16 && ST_STFTPLAN_SFOLDT == SGP_SFOLDT, "st_stft_plan: flag values");
+    if (check_dims(d) != ST_OK || cap < 0 || (cap > 0 && !out) || which < GEMM_ANALYSIS || which > GEMM_DGRAD) return -1;
+    if ((flags & ~(SGP_PADDED | SGP_G16 | SGP_SFOLDT)) || ((flags & (SGP_G16 | SGP_SFOLDT)) && !(flags & SGP_PADDED))) return -1;      // the fused entries' alone
+    const GemmPlan p = stft_plan(d, which, flags, GemmOps{}, ncus);
+    const int v[ST_STFT_PLAN_INTS] = {p.family, p.form, p.waves, p.bk, p.xt, p.R, p.M, p.Nc, p.K, p.ns, p.frame_major ? 1 : 0, p.crop, p.wk.n, p.live.t_lo, p.live.Tv};
+    for (int i = 0; i < ST_STFT_PLAN_INTS && i < cap; ++i) out[i] = v[i];
+    return ST_STFT_PLAN_INTS;
 }
 
 // with_mae (the validation pass, st_eval_step): the kernels' MAE instantiations -- loss_partial then has room for a second array of st_ola_loss_partials() floats, the
@@ -770,43 +917,6 @@ extern "C" int st_ola_loss(const st_dims* d, const float* frs, const float* x, c
 {
     ST_TRY(check_dims(d)); ST_REQ(frs, "st_ola_loss: null pointer");
     return ola_loss_impl(d, frs, x, y_true, y_hat, dsyn, 0, loss_partial, stream);
-}
-
-static int synthesis_dgrad_impl(const st_dims* d, const float* dsyn, bool padded, const float* Sfold, float* dAA, void* stream)
-{
-    const int KP = st_kp_of(d->F);
-    const stg::RowMap ms = synth_live(d);
-    const int R = ms.rows(d->B);
-    // dfrs[b,t,n] = dfull[b, H t + n] with dfull = zero-pad(dsyn, N each side)  == frames of dsyn with pad N.
-    // Rows of dAA for dead frames are NOT written (st_ae_bwd treats them as zero).
-    // dAA holds st_synth_slabs() split-K slabs [B*OT, KP]; st_ae_bwd sums them
-    stg::PlainNT bl{Sfold, KP, d->N, d->N, stg::all_frames(1)};
-    stg::StoreC ep{dAA, R, KP, KP, (size_t)d->B * d->OT * KP, ms};
-    const int ns = dgrad_slabs(R);
-    if (padded) {
-        stg::FramedNT<true> al{dsyn, d->y, d->H, d->N, R, d->N, 1.0f, ms};
-        stg::NTWork wk;
-        if (use_nt128(d, R, KP) && stg::ntw_dgrad(wk, ms, d->B, d->H, d->N, d->N, d->y, d->F, KP, ns, num_cus())) {
-            // frame-major rows, per tile row only the taps that lie inside d syn (the margins of the padded copy are zeros), Nyquist columns apart
-            const stg::NTRows ra = stg::ntrows_frame_major(dsyn, (unsigned)(d->y + 2 * d->N), (unsigned)d->H, ms, d->B, R);
-            const stg::NTRows rb = wk.col_h ? stg::NTRows{Sfold, (unsigned)((KP / 2) * d->N), (unsigned)d->N, stg::rowmap_magic(d->F - 1), d->F - 1, 0, 2 * (d->F - 1)}
-                                            : stg::NTRows{Sfold, (unsigned)d->N, 0u, 0u, 1, 0, KP};
-            const stg::StoreSlab es{dAA, R, KP, KP, (size_t)d->B * d->OT * KP, stg::frame_major(ms, d->B)};
-            ST_TRY(stg::launch_nt128(ra, rb, es, wk, st_stream(stream)));
-        }
-        else if (R >= 4096) ST_GEMM(4, al, bl, ep, R, KP, d->N, ns, st_stream(stream));
-        else ST_GEMM(2, al, bl, ep, R, KP, d->N, ns, st_stream(stream));
-    } else {
-        stg::FramedNT<false> al{dsyn, d->y, d->H, d->N, R, d->N, 1.0f, ms};
-        if (R >= 4096) ST_GEMM(4, al, bl, ep, R, KP, d->N, ns, st_stream(stream)); else ST_GEMM(2, al, bl, ep, R, KP, d->N, ns, st_stream(stream));
-    }
-    ST_LAUNCHED("synthesis_dgrad");
-    return ST_OK;
-}
-extern "C" int st_synthesis_dgrad(const st_dims* d, const float* dsyn, const float* Sfold, float* dAA, void* stream)
-{
-    ST_TRY(check_dims(d)); ST_REQ(dsyn && Sfold && dAA, "st_synthesis_dgrad: null pointer");
-    return synthesis_dgrad_impl(d, dsyn, false, Sfold, dAA, stream);
 }
 
 // The 128 x 128-tile form (st_gemm_tn.h): fp32 products (ST_PREC_F32, and ST_PREC_F32X3 whose weight gradients stay on the fp32 MFMA), operands
@@ -919,8 +1029,8 @@ static int wgrad_gemm(const WgradPlan& p, void* stream)
     else {
         stg::PlainTN al{p.o.A + p.m0, p.R, KP, p.M, p.live};
         stg::StoreC ep{p.area + (size_t)p.m0 * N, p.M, N, N, p.slab, stg::all_frames(1)};
-        if (p.flags & WGP_PADDED) { stg::FramedTN<true> bl{p.o.B, p.Ls, d->H, N, p.R, N, 1.0f, p.live}; ST_GEMM_WG(al, bl, ep, p.M, N, p.R, p.ns, st_stream(stream)); }
-        else { stg::FramedTN<false> bl{p.o.B, p.Ls, d->H, N, p.R, N, p.o.in_scale, p.live}; ST_GEMM_WG(al, bl, ep, p.M, N, p.R, p.ns, st_stream(stream)); }
+        if (p.flags & WGP_PADDED) { stg::FramedTN<true> bl{p.o.B, p.Ls, d->H, N, p.R, N, 1.0f, p.live}; ST_TRY(wgrad_small_gemm(d->prec, al, bl, ep, p.M, N, p.R, p.ns, st_stream(stream))); }
+        else { stg::FramedTN<false> bl{p.o.B, p.Ls, d->H, N, p.R, N, p.o.in_scale, p.live}; ST_TRY(wgrad_small_gemm(d->prec, al, bl, ep, p.M, N, p.R, p.ns, st_stream(stream))); }
     }
     ST_LAUNCHED(p.which ? "synthesis_wgrad" : "analysis_wgrad");
     return ST_OK;
@@ -1317,7 +1427,7 @@ struct WS {
     // bases as rows (bin, re | im) [2F][N], the folded synthesis bases [KP][N] and [N][KP], the spectra, the padded d syn, d G
     unsigned short *xp16, *W16, *Sfold16, *SfoldT16, *AA16, *dsyn16, *dG16;
     int n_norm_e;      // > 0: the autoencoder backward of this call left that many |g| partials of its gradients in norm_e (clip_all needs no l1_partial launch)
-    bool g16;          // this call runs the 16-bit operand pipeline (call_begin's g16 argument and use_g16(); the autograd entries and the
+    bool g16;          // this call runs the 16-bit operand pipeline (call_begin's g16 argument and stft_family; the autograd entries and the
                        // four-stage schedule keep fp32 operands + gemm_half_kernel)
     size_t bytes;
 };
@@ -1408,10 +1518,7 @@ extern "C" size_t st_workspace_bytes_max(const st_dims* d)
 // ------------------------------------------------------------------------------ the plane GEMMs of the fused step (ST_PREC_F32X3)
 // Operands written once per step -- the padded waveform, the F used rows of the analysis bases, the folded synthesis bases in both
 // orientations -- become three bfloat16 planes in one elementwise launch; the spectra AA and d syn (one consumer each) are split as
-// their GEMM stages them.  The weight-gradient GEMMs (reduction along the rows of both operands) keep the fp32 MFMA kernel.
-static bool use_planes(const st_dims* d) { return (gemm_ht(d->prec) == 3 || (gemm_ht(d->prec) == 1 && g_pl_bf16)) && d->N % 16 == 0 && st_kp_of(d->F) % 16 == 0; }
-static int planes_of(const st_dims* d) { return gemm_ht(d->prec) == 3 ? 3 : 1; }
-template <class F> static inline auto with_planes(int pl, F&& f) { return pl == 1 ? f(ic<1>{}) : f(ic<3>{}); }
+// their GEMM stages them (stft_plan: GF_PLANES).  The weight-gradient GEMMs (reduction along the rows of both operands) keep the fp32 MFMA kernel.
 static int planes_prepare(const st_dims* d, const float* Wr, const float* Wi, WS& w, void* stream)
 {
     const int KP = st_kp_of(d->F);
@@ -1427,102 +1534,11 @@ static int planes_prepare(const st_dims* d, const float* Wr, const float* Wi, WS
     ST_LAUNCHED("planes");
     return ST_OK;
 }
-static int analysis_fwd_planes(const st_dims* d, WS& w, float* re, float* im, float* mag, float* phs, void* stream, const PolarWide* pw = nullptr)
-{
-    const stg::RowMap map = stg::live_frames(d->T, d->H, d->N, d->N, d->L);
-    const int R = map.rows(d->B);
-    stg::FramedNT<true> al{w.xp, d->L, d->H, d->N, R, d->N, 1.0f, map};
-    stg::ChunkP bl{w.pl_W, 2 * d->F};
-    stg::PolarStore ep{re, im, mag, phs, R, d->F, map};
-    polar_wide_set(ep, pw);
-    if (planes_of(d) == 1) ST_TRY((stg::launch_planes<4, 1>(al, bl, ep, R, 2 * d->F, d->N, 1, st_stream(stream))));
-    else if (g_pl_shape == 3) ST_TRY((stg::launch_planes<8, 3>(al, bl, ep, R, 2 * d->F, d->N, 1, st_stream(stream))));
-    else ST_TRY((stg::launch_planes<4, 3>(al, bl, ep, R, 2 * d->F, d->N, 1, st_stream(stream))));
-    ST_LAUNCHED("analysis_fwd");
-    return ST_OK;
-}
-static int synthesis_frames_planes(const st_dims* d, WS& w, void* stream)
-{
-    const int KP = st_kp_of(d->F);
-    const stg::RowMap ms = synth_live(d);
-    const int R = ms.rows(d->B);
-    stg::PlainNT al{w.AA, R, KP, KP, ms};
-    stg::ChunkP bt{w.pl_SfoldT, d->N};
-    stg::StoreC ep{w.frs, R, d->N, d->N, (size_t)d->B * d->OT * d->N, ms};
-    ST_TRY(with_planes(planes_of(d), [&](auto PL) {
-        return R >= 4096 ? stg::launch_planes<4, PL()>(al, bt, ep, R, d->N, KP, 1, st_stream(stream))
-                         : stg::launch_planes<2, PL()>(al, bt, ep, R, d->N, KP, frames_split(R), st_stream(stream)); }));
-    ST_LAUNCHED("synthesis_frames"); return ST_OK;
-}
-static int synthesis_dgrad_planes(const st_dims* d, WS& w, void* stream)
-{
-    const int KP = st_kp_of(d->F);
-    const stg::RowMap ms = synth_live(d);
-    const int R = ms.rows(d->B);
-    stg::FramedNT<true> al{w.dsyn, d->y, d->H, d->N, R, d->N, 1.0f, ms};
-    stg::ChunkP bl{w.pl_Sfold, KP};
-    stg::StoreC ep{w.dAA, R, KP, KP, (size_t)d->B * d->OT * KP, ms};
-    const int ns = dgrad_slabs(R);
-    ST_TRY(with_planes(planes_of(d), [&](auto PL) {
-        return R >= 4096 ? stg::launch_planes<4, PL()>(al, bl, ep, R, KP, d->N, ns, st_stream(stream))
-                         : stg::launch_planes<2, PL()>(al, bl, ep, R, KP, d->N, ns, st_stream(stream)); }));
-    ST_LAUNCHED("synthesis_dgrad"); return ST_OK;
-}
-
-// ------------------------------------------------------------------------------ the 16-bit operand pipeline (st_gemm16.h)
-static bool use_g16(const st_dims* d)
-{
-    const int ht = gemm_ht(d->prec);
-    return g_g16 && (ht == 1 || ht == 2) && !g_pl_bf16 && d->N % 128 == 0 && num_cus() > 0;
-}
-static int analysis_fwd16(const st_dims* d, WS& w, float* re, float* im, float* mag, float* phs, void* stream, const PolarWide* pw = nullptr)
-{
-    const stg::RowMap map = stg::live_frames(d->T, d->H, d->N, d->N, d->L);
-    const int R = map.rows(d->B);
-    const stg::Rows16 ra = stg::rows16(w.xp16, (unsigned)(d->L + 2 * d->N), (unsigned)d->H, map, R);
-    const stg::Rows16 rb = stg::rows16_plain(w.W16, (unsigned)d->N, 2 * d->F);
-    stg::PolarStore ep{re, im, mag, phs, R, d->F, map};
-    polar_wide_set(ep, pw);
-    ST_TRY(with_ht16(gemm_ht(d->prec), [&](auto HT) {
-        return ((g_g16_dma & 1) && d->N % 64 == 0) ? stg::launch16_nt256<HT()>(ra, rb, ep, R, 2 * d->F, d->N, 1, st_stream(stream))
-                                                   : stg::launch16_nt<HT()>(ra, rb, ep, R, 2 * d->F, d->N, 1, st_stream(stream)); }));
-    ST_LAUNCHED("analysis_fwd"); return ST_OK;
-}
-static int synthesis_frames16(const st_dims* d, WS& w, void* stream)
-{
-    const int KP = st_kp_of(d->F);
-    const stg::RowMap ms = synth_live(d);
-    const int R = ms.rows(d->B);
-    const bool crop = (g_g16_crop & 1) && d->N % 128 == 0 && fm_div_exact(R, d->B);
-    const stg::Rows16 ra = crop ? stg::rows16_frame_major(w.AA16, (unsigned)(d->OT * KP), (unsigned)KP, ms, d->B, R) : stg::rows16(w.AA16, (unsigned)(d->OT * KP), (unsigned)KP, ms, R);
-    const stg::Rows16 rb = stg::rows16_plain(w.SfoldT16, (unsigned)KP, d->N);
-    stg::StoreC ep{w.frs, R, d->N, d->N, (size_t)d->B * d->OT * d->N, crop ? stg::frame_major(ms, d->B) : ms};
-    const stg::Crop16 cr{crop ? 1 : 0, d->B, d->H, d->N, d->N, d->y, ms.t_lo, R, 1};      // tile columns without a tap inside the crop (cls_fe_dft.py:113) are not computed: ola_loss_kernel never reads them
-    const int ns = frames_split(R);
-    ST_TRY(with_ht16(gemm_ht(d->prec), [&](auto HT) { return stg::launch16_nt<HT()>(ra, rb, ep, R, d->N, KP, ns, st_stream(stream), &cr); }));
-    ST_LAUNCHED("synthesis_frames"); return ST_OK;
-}
-static int synthesis_dgrad16(const st_dims* d, WS& w, void* stream)
-{
-    const int KP = st_kp_of(d->F);
-    const stg::RowMap ms = synth_live(d);
-    const int R = ms.rows(d->B);
-    const bool crop = (g_g16_crop & 2) && !(g_g16_dma & 2) && fm_div_exact(R, d->B);
-    const stg::Rows16 ra = crop ? stg::rows16_frame_major(w.dsyn16, (unsigned)(d->y + 2 * d->N), (unsigned)d->H, ms, d->B, R) : stg::rows16(w.dsyn16, (unsigned)(d->y + 2 * d->N), (unsigned)d->H, ms, R);
-    const stg::Rows16 rb = stg::rows16_plain(w.Sfold16, (unsigned)d->N, KP);
-    stg::StoreC ep{w.dAA, R, KP, KP, (size_t)d->B * d->OT * KP, crop ? stg::frame_major(ms, d->B) : ms};
-    const stg::Crop16 cr{crop ? 2 : 0, d->B, d->H, d->N, d->N, d->y, ms.t_lo, R, 1};      // per tile row only the taps that lie inside d syn: the rest of the padded copy is zeros
-    const int ns = dgrad_slabs(R);
-    ST_TRY(with_ht16(gemm_ht(d->prec), [&](auto HT) {
-        return ((g_g16_dma & 2) && d->N % 64 == 0 && d->N / 64 >= ns) ? stg::launch16_nt256<HT()>(ra, rb, ep, R, KP, d->N, ns, st_stream(stream))
-                                                                      : stg::launch16_nt<HT()>(ra, rb, ep, R, KP, d->N, ns, st_stream(stream), &cr); }));
-    ST_LAUNCHED("synthesis_dgrad"); return ST_OK;
-}
 
 // ------------------------------------------------------------------------------ fused entry points
 // What a fused entry derives from its arguments before its first launch, handed down in one piece.  call_begin validates the dims (and nothing else: every
 // entry keeps its own pointer checks, after it), lays out the parameters, carves the workspace and lets knobs fall back to any resident float where K == 0.
-// g16 is each entry's own choice: the training and validation entries ask for the 16-bit operand pipeline (taken where use_g16() admits the precision),
+// g16 is each entry's own choice: the training and validation entries ask for the 16-bit operand pipeline (taken where stft_family admits the precision),
 // the autograd entries and the four-stage schedule do not and keep fp32 operands + gemm_half_kernel.
 struct Call { const st_dims* d; Layout L; WS w; const float* knobs; void* stream; };
 static const bool G16_PIPELINE = true, FP32_OPERANDS = false;
@@ -1531,7 +1547,7 @@ static int call_begin(Call* c, const st_dims* d, const float* params, const floa
     ST_TRY(make_layout(d, &c->L));
     c->d = d; c->knobs = knobs ? knobs : params; c->stream = stream;
     carve(d, c->L, ws, &c->w);
-    c->w.g16 = g16 && use_g16(d);
+    c->w.g16 = g16 && stft_family(d, GEMM_ANALYSIS, SGP_PADDED | SGP_G16) == GF_G16;
     return ST_OK;
 }
 // A weight-gradient plan on the workspace's own operands.  area: where the slabs go (default: the first area, w.wg); more: WGP_HALVES_96; ncus: the host queries
@@ -1539,6 +1555,13 @@ static WgradPlan step_wgrad_plan(const st_dims* d, const WS& w, int which, int h
 {
     const WgOps o = which ? WgOps{w.AA, w.dsyn, w.AA16, w.dsyn16, 1.0f} : WgOps{w.dG, w.xp, w.dG16, w.xp16, 1.0f};
     return wgrad_plan(d, which, half, WGP_PADDED | (w.g16 ? WGP_G16 : 0) | more, o, area ? area : w.wg, ncus);
+}
+// One of the three GEMMs of stft_plan on the workspace's own operands (Wr, Wi: the analysis bases, which live with the parameters)
+static GemmPlan step_stft_plan(const st_dims* d, const WS& w, int which, const float* Wr = nullptr, const float* Wi = nullptr)
+{
+    const GemmOps o = which == GEMM_ANALYSIS ? GemmOps{w.xp, Wr, Wi, w.xp16, w.W16, w.pl_W, 1.0f} :
+                      which == GEMM_FRAMES ? GemmOps{w.AA, w.Sfold, w.SfoldT, w.AA16, w.SfoldT16, w.pl_SfoldT, 1.0f} : GemmOps{w.dsyn, w.Sfold, nullptr, w.dsyn16, w.Sfold16, w.pl_Sfold, 1.0f};
+    return stft_plan(d, which, SGP_PADDED | SGP_SFOLDT | (w.g16 ? SGP_G16 : 0), o);
 }
 static int forward_impl(Call& c, const float* params, const float* x, const float* y_true, float* y_hat, float* mag, float* mag_hat, bool save, float* eval_p = nullptr)
 {
@@ -1583,23 +1606,17 @@ static int forward_impl(Call& c, const float* params, const float* x, const floa
         hipLaunchKernelGGL(stm::prep_kernel, dim3(a.n_pad + a.n_fold + n_dead + a.wd.n_vpad + a.wd.n_kn + a.wd.n_pj + a.ai.n_blk + a.n_w16), dim3(256), 0, st_stream(stream), a);
         ST_LAUNCHED("prep");
     }
-    const bool planes = use_planes(d) && !w.g16;
     // a training call (target given, no user-visible |STFT| requested) on the direct wide path needs mag / phs ONLY in the feature-major layout
     const bool polar_rows = !(wide_direct && y_true && !mag);
     float* const pmag = polar_rows ? w.mag : nullptr; float* const pphs = polar_rows ? w.phs : nullptr;
-    if (w.g16) ST_TRY(analysis_fwd16(d, w, save ? w.re : nullptr, save ? w.im : nullptr, pmag, pphs, stream, &pwide));
-    else if (planes) {
-        ST_TRY(planes_prepare(d, Wr, Wi, w, stream));
-        ST_TRY(analysis_fwd_planes(d, w, save ? w.re : nullptr, save ? w.im : nullptr, pmag, pphs, stream, &pwide));
-    } else
-    ST_TRY(analysis_fwd_impl(d, w.xp, true, Wr, Wi, 1.0f, save ? w.re : nullptr, save ? w.im : nullptr, pmag, pphs, stream, true, &pwide));
+    const GemmPlan ap = step_stft_plan(d, w, GEMM_ANALYSIS, Wr, Wi);
+    if (ap.family == GF_PLANES) ST_TRY(planes_prepare(d, Wr, Wi, w, stream));
+    ST_TRY(stft_gemm(ap, GemmOut{save ? w.re : nullptr, save ? w.im : nullptr, pmag, pphs, &pwide, nullptr}, stream));
     float* const sv = (save && ae_use_saved(d)) ? ae_sv_ptr(d, L, w.aews) : nullptr;      // round 6: the activations stay for the backward
     ST_TRY(ae_fwd_body(d, L, w.mag, w.phs, knobs, ae_m, ae_p, w.mag_hat, w.phs_hat, w.AA, w.reg_p,
                        (ae_is_wide(d) || (save && ae_use_split(d))) ? w.aews : nullptr, stream, w.g16 ? w.AA16 : nullptr, wide_direct, sv,
                        ae_img_level(d) ? ae_img_ptr(w.aews) : nullptr));     // fused geometries: the code h4 is kept for the split backward
-    if (w.g16) ST_TRY(synthesis_frames16(d, w, stream)); else
-    if (planes) ST_TRY(synthesis_frames_planes(d, w, stream)); else
-    ST_TRY(synthesis_frames_impl(d, w.AA, w.Sfold, w.SfoldT, w.frs, stream));
+    ST_TRY(stft_gemm(step_stft_plan(d, w, GEMM_FRAMES), slabs_at(w.frs), stream));
     ST_TRY(ola_loss_impl(d, w.frs, x, y_true, y_hat ? y_hat : w.y_hat, (save && y_true) ? w.dsyn : nullptr, d->N,
                          eval_p ? eval_p : y_true ? w.loss_p : nullptr, stream, w.g16 ? w.dsyn16 : nullptr, eval_p != nullptr));      // eval_p: loss + MAE partials (st_eval_step)
     const size_t nm = (size_t)d->B * d->T * d->F * sizeof(float), nh = (size_t)d->B * d->OT * d->F * sizeof(float);
@@ -1616,11 +1633,7 @@ static const int ST_STAGE_EVERY = ST_STAGE_SYN_DGRAD | ST_STAGE_SYN_WGRAD | ST_S
 static int backward_syn(Call& c, float* grads, const WgradPlan* deferred = nullptr, int stages = ST_STAGE_EVERY)
 {   // deferred: the caller's synthesis plan, whose slabs the caller sums itself (post_ae_kernel, the gradient-finish launch, the communicator stream); else summed here
     const st_dims* d = c.d; const Layout& L = c.L; WS& w = c.w; void* stream = c.stream;
-    if (stages & ST_STAGE_SYN_DGRAD) {
-    if (w.g16) ST_TRY(synthesis_dgrad16(d, w, stream)); else
-    if (use_planes(d) && g_pl_dgrad) ST_TRY(synthesis_dgrad_planes(d, w, stream)); else
-    ST_TRY(synthesis_dgrad_impl(d, w.dsyn, true, w.Sfold, w.dAA, stream));
-    }
+    if (stages & ST_STAGE_SYN_DGRAD) ST_TRY(stft_gemm(step_stft_plan(d, w, GEMM_DGRAD), slabs_at(w.dAA), stream));
     if (!(stages & ST_STAGE_SYN_WGRAD)) return ST_OK;
     if (deferred) return wgrad_gemm(*deferred, stream);
     return wgrad_gemm_and_sum(step_wgrad_plan(d, w, 1), grads + L.offs[2], grads + L.offs[3], w.norm_s, nullptr, 0, stream);
@@ -1730,7 +1743,7 @@ extern "C" int st_wgrad_plan(const st_dims* d, int which, int half, int flags, i
     if (which < 0 || which > 1 || half < -1 || half > 1 || (half >= 0 && which) || (flags & ~(WGP_PADDED | WGP_G16 | WGP_HALVES_96)) ||
         ((flags & WGP_G16) && !(flags & WGP_PADDED))) return -1;
     WS w; carve(d, L, reinterpret_cast<void*>(sizeof(float)), &w);       // a non-null dummy base: only pointer differences are used
-    w.g16 = (flags & WGP_G16) && use_g16(d);                              // as call_begin: the pipeline is taken where the precision admits it
+    w.g16 = (flags & WGP_G16) && stft_family(d, GEMM_ANALYSIS, SGP_PADDED | SGP_G16) == GF_G16;      // as call_begin: the pipeline is taken where the precision admits it
     const WgradPlan p = (flags & WGP_PADDED) ? step_wgrad_plan(d, w, which, half, nullptr, flags & WGP_HALVES_96, ncus)
                                              : wgrad_plan(d, which, half, flags, WgOps{w.dG, w.xp, nullptr, nullptr, 1.0f}, w.wg, ncus);
     const int v[ST_WGRAD_PLAN_INTS] = {p.form, p.R, p.ns, p.m0, p.M, p.frame_major ? 1 : 0, p.trim.on ? 1 : 0, p.nyq_P, (int)p.nyq_off, p.nyq_write ? 1 : 0, (int)p.used()};
@@ -1928,7 +1941,7 @@ static int predict_batches(const st_dims* d, const Layout& L, const PredictWS& p
 {
     const float* Wr = params + L.offs[0]; const float* Wi = params + L.offs[1];
     const float* ae_m = params + L.offs[4]; const float* ae_p = params + L.offs[22];
-    const bool g16 = use_g16(d), planes = use_planes(d) && !g16, img = predict_img(d);
+    const bool g16 = stft_family(d, GEMM_ANALYSIS, SGP_PADDED | SGP_G16) == GF_G16, img = predict_img(d);      // the 16-bit pipeline wherever the precision admits it, as the training entries
     const long long nwin = (n_out + d->y - 1) / d->y;      // == predict_windows(d, n) wherever n_out > 0
     for (long long w0 = 0; w0 < nwin; w0 += d->B) {
         st_dims q = *d; q.B = (int)(nwin - w0 < d->B ? nwin - w0 : d->B);
@@ -1947,14 +1960,10 @@ static int predict_batches(const st_dims* d, const Layout& L, const PredictWS& p
         hipLaunchKernelGGL(stp::predict_stage_kernel<T>, dim3(a.n_pad + a.n_dead + a.n_kn), dim3(256), 0, st_stream(stream), a);
         ST_LAUNCHED("predict_stage");
         const float* kn = q.K == 0 ? params : fill ? p.knobs : knobs + (size_t)w0 * q.K;      // K == 0: any resident float (call_begin)
-        if (g16) ST_TRY(analysis_fwd16(&q, w, nullptr, nullptr, w.mag, w.phs, stream));
-        else if (planes) ST_TRY(analysis_fwd_planes(&q, w, nullptr, nullptr, w.mag, w.phs, stream));
-        else ST_TRY(analysis_fwd_impl(&q, w.xp, true, Wr, Wi, 1.0f, nullptr, nullptr, w.mag, w.phs, stream, true));
+        ST_TRY(stft_gemm(step_stft_plan(&q, w, GEMM_ANALYSIS, Wr, Wi), GemmOut{nullptr, nullptr, w.mag, w.phs, nullptr, nullptr}, stream));
         ST_TRY(ae_fwd_body(&q, L, w.mag, w.phs, kn, ae_m, ae_p, w.mag_hat, w.phs_hat, w.AA, w.reg_p, nullptr, stream, g16 ? w.AA16 : nullptr, false, nullptr,
                            img ? p.img : nullptr));
-        if (g16) ST_TRY(synthesis_frames16(&q, w, stream)); else
-        if (planes) ST_TRY(synthesis_frames_planes(&q, w, stream)); else
-        ST_TRY(synthesis_frames_impl(&q, w.AA, w.Sfold, w.SfoldT, w.frs, stream));
+        ST_TRY(stft_gemm(step_stft_plan(&q, w, GEMM_FRAMES), slabs_at(w.frs), stream));
         const int ns = frame_slabs(&q);
         const dim3 grid((q.y / 4 + 255) / 256, q.B);
         const size_t slab = (size_t)q.B * q.OT * q.N;
@@ -1987,7 +1996,8 @@ extern "C" int st_predict_long(const st_dims* d, const float* params, int fmt, c
     PredictWS p; predict_carve(d, ws, &p);
     prof_mark("begin", stream);
     {   // once per call: the parameter side of prep_kernel (its per-batch jobs have no blocks here)
-        const bool g16 = use_g16(d);
+        const int family = stft_family(d, GEMM_ANALYSIS, SGP_PADDED | SGP_G16);      // as predict_batches
+        const bool g16 = family == GF_G16;
         stm::PrepArgs a;
         a.x = nullptr; a.xp = nullptr; a.Ls = d->L; a.pad = d->N; a.scale = 0.5f; a.nbx = 1; a.n_pad = 0;
         a.Sr = params + L.offs[2]; a.Si = params + L.offs[3]; a.Sfold = p.Sfold; a.SfoldT = p.SfoldT; a.N = d->N; a.F = d->F; a.KP = L.KP; a.n_fold = (L.KP / 32) * (d->N / 32);
@@ -2004,7 +2014,7 @@ extern "C" int st_predict_long(const st_dims* d, const float* params, int fmt, c
         }
         hipLaunchKernelGGL(stm::prep_kernel, dim3(a.n_fold + a.ai.n_blk + a.n_w16), dim3(256), 0, st_stream(stream), a);
         ST_LAUNCHED("predict_prep");
-        if (use_planes(d) && !g16) {
+        if (family == GF_PLANES) {
             WS w; w.Sfold = p.Sfold; w.SfoldT = p.SfoldT; w.pl_W = p.pl_W; w.pl_Sfold = p.pl_Sfold; w.pl_SfoldT = p.pl_SfoldT;
             ST_TRY(planes_prepare(d, a.Wr, a.Wi, w, stream));
         }
