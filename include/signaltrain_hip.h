@@ -374,6 +374,42 @@ size_t    st_predict_ws_bytes(const st_dims* d);
 int st_predict_long(const st_dims* d, const float* params, int fmt, const void* signal, long long n,
                     const float* knobs, long long knob_rows, float* out, void* ws, void* stream);
 
+/* Knob fit on the device: the knob settings for which the model turns `signal` into `target` (predict.fit_knobs), every batch of every optimiser step enqueued by
+ * ONE call.  Windows, lengths and formats are st_predict_long's: nwin = st_predict_windows(d, n); window w reads signal[w y, w y + L) with zeros from sample n on;
+ * fmt (ST_PCM_F32 / ST_PCM_S16, an int16 sample converts as (float)((double)s / 32767.0)) applies to both recordings; target holds the same n samples, aligned with
+ * signal, and the target of output sample i, 0 <= i < n_out = st_predict_out_samples(d, n), is target[(L - y) + i].  Nothing at or past signal + n or target + n is read.
+ * Objective: J(knobs) = (1 / n_out) * sum_{i < n_out} logcosh(y_hat_i - target_i), y_hat as st_predict_long forms it at this st_dims.prec.  Output positions of the last
+ * window that lie behind the end of the recording carry no loss and no gradient (the host route of predict.fit_knobs counts its zero-padded tail; the two objectives
+ * coincide when n = L + k y).
+ *   knobs       [knob_rows][K], start values in, fitted values out.  knob_rows == 1: one setting, its gradient the sum over all windows in ascending window order;
+ *               knob_rows == nwin: one row per window (knob automation), row w receives window w's own gradient of the same J.
+ *   adam_m, adam_v  [knob_rows][K] Adam moments, updated in place (zeros before the first step).
+ *   per step s = 0 .. steps - 1: loss_hist[s] = J at the knobs BEFORE the update; grad_hist[s] ([knob_rows][K], skipped where grad_hist is NULL) that gradient; then
+ *               torch.optim.Adam's update at step number first_step + s (1-based, bias-corrected, denom = sqrt(v) / sqrt(1 - beta2^t) + eps) and a clamp to
+ *               [-0.5, 0.5].  `steps` calls of one step chained through first_step are, bit for bit, one call of `steps` steps.
+ *   loss_hist   device, [steps] doubles;  grad_hist  device, [steps][knob_rows][K] floats or NULL.
+ *   ws          st_fit_knobs_ws_bytes(d) bytes (>= st_predict_ws_bytes(d)), 16-byte aligned: [st_predict_long's parameter-only head, built once per call | the
+ *               per-window gradient rows of a batch, the one-row accumulator and the per-group scratch | one batch's workspace].
+ * Per batch: st_predict_long's staging launch, analysis GEMM and autoencoder forward (the 16-wide code h4 kept), the frames GEMM; one overlap-add launch that also
+ * writes 2 tanh(y_hat - target) as the padded operand of the synthesis data-gradient GEMM (zeros in the padding and behind the recording's end) and the log-cosh
+ * partials in st_ola_loss's formula; that GEMM; the knob-only autoencoder backward (data gradients of layers 9..6 and ELU' at layer 5: no weight or bias gradient,
+ * no encoder half, no polar backward); the per-window reduce that applies W5; one tail launch (loss partials into loss_hist[s] in double; after the step's last batch
+ * the window sum, 1 / n_out, grad_hist[s], Adam and the clamp).  1 / n_out is applied in fp32 BEHIND the reduce that applies W5: the operand of the data-gradient GEMM
+ * is unscaled, so the 16-bit levels do not lose it to the fp16 subnormal range however long the recording.  st_dims.loss_scale and clip_all are ignored.
+ * No float atomics: every reduction has a fixed order and a repeated call repeats its bits.  No allocation, no hipMemcpy, no host synchronisation; parameters are only read.
+ * st_fit_knobs_supported (host only): st_predict_supported(d) && d->K >= 1.  st_fit_knobs_ws_bytes: 0 for bad or unsupported dims.
+ * Refused before any launch (ST_ERR_ARG, the rule in st_last_error(), naming st_fit_knobs): bad dims; K < 1; a null pointer, named (grad_hist may be NULL); n <= 0; an
+ * unknown fmt; knob_rows neither 1 nor the window count; steps < 1; first_step < 1; lr, beta1, beta2 or eps not finite, lr < 0, a beta outside [0, 1), eps <= 0;
+ * signal or target not 16-byte aligned (ST_PCM_S16: 8-byte); knobs, adam_m, adam_v or ws not 16-byte aligned; dims st_fit_knobs_supported rejects (the wide geometries).
+ * An n with no output sample (n <= L - y) returns ST_OK without a launch and leaves every buffer alone. */
+int    st_fit_knobs_supported(const st_dims* d);
+size_t st_fit_knobs_ws_bytes(const st_dims* d);
+int    st_fit_knobs(const st_dims* d, const float* params, int fmt, const void* signal, const void* target, long long n,
+                    float* knobs, long long knob_rows, float* adam_m, float* adam_v,
+                    long long first_step, int steps, float lr, float beta1, float beta2, float eps,
+                    double* loss_hist /* device, [steps] */, float* grad_hist /* device, [steps][knob_rows][K], may be NULL */,
+                    void* ws, void* stream);
+
 /* Data-parallel split of st_loss_backward.  After p1 the gradients of the synthesis bases and both
  * autoencoders (grads[offs[2]..end)) are final: all-reduce them while p2 computes the analysis
  * weight gradient (rows [0,F) of tensors 0 and 1) and the loss scalars. */

@@ -25,6 +25,7 @@
 #include "st_feed_live.h"
 #include "st_feed_stream.h"
 #include "st_predict.h"
+#include "st_fit.h"
 
 // ------------------------------------------------------------------------------ errors
 static thread_local char g_err[512] = "";
@@ -1891,6 +1892,9 @@ extern "C" int st_eval_step(const st_dims* d, const float* params, const float* 
     ST_LAUNCHED("eval_finalize"); return ST_OK;
 }
 
+// ae_knob_bwd_kernel (st_fit.h): 12-wave workgroups, three waves per SIMD, one workgroup per CU: grid.y = 2 nets -> up to half the CUs per net
+static const int AE_KNOB_NW = 12;
+static int ae_knob_grid(const st_dims* d) { int g = (ae_fwd_groups(d) + AE_KNOB_NW - 1) / AE_KNOB_NW; int c = num_cus() / 2; if (c < 1) c = 1; return g < c ? g : c; }
 // ------------------------------------------------------------------------------ whole-signal inference (st_predict.h)
 // utils/predict_long.py:30-79 in one call.  The workspace is [head | batch workspace]: the head holds what depends on the parameters only -- both orientations of the
 // folded synthesis bases in the form this level's GEMMs read (fp32, 16-bit, or three bfloat16 planes), the 16-bit / plane copies of the analysis rows, the forward
@@ -1935,17 +1939,27 @@ extern "C" size_t st_predict_ws_bytes(const st_dims* d)
     for (int b = 1; b <= d->B; ++b) { q.B = b; WS w; carve(&q, L, nullptr, &w); if (w.bytes > best) best = w.bytes; }      // not monotonic in the batch (st_workspace_bytes_max)
     return p.head_bytes + best;
 }
+// One optimiser step of st_fit_knobs rides on the same batch loop (fit != NULL): the forward keeps h4, and behind the frames GEMM come fit_ola, the synthesis
+// data-gradient GEMM, ae_knob_bwd, knob_grad and the per-batch tail instead of predict_ola.  batch_off: where the batch workspace starts (behind the head, and for
+// the fit behind its own rows and scratch).
+struct FitJob {
+    const void* target; float *kg, *rows, *acc;      // per-group scratch [2][groups of a batch][16], per-window rows [d->B][K], the one-row accumulator [K]
+    float *knobs, *m, *v, *grad; double* loss;       // grad: this step's row(s) of grad_hist, or NULL
+    stf::TailArgs hyper;                             // inv_n, inv_n_d and Adam's scalars of this step
+};
 template <typename T>
 static int predict_batches(const st_dims* d, const Layout& L, const PredictWS& p, const float* params, const T* signal, long long n,
-                           const float* knobs, long long knob_rows, float* out, long long n_out, void* ws, void* stream)
+                           const float* knobs, long long knob_rows, float* out, long long n_out, void* ws, void* stream,
+                           const FitJob* fit = nullptr, size_t batch_off = 0)
 {
+    if (!batch_off) batch_off = p.head_bytes;
     const float* Wr = params + L.offs[0]; const float* Wi = params + L.offs[1];
     const float* ae_m = params + L.offs[4]; const float* ae_p = params + L.offs[22];
     const bool g16 = stft_family(d, GEMM_ANALYSIS, SGP_PADDED | SGP_G16) == GF_G16, img = predict_img(d);      // the 16-bit pipeline wherever the precision admits it, as the training entries
     const long long nwin = (n_out + d->y - 1) / d->y;      // == predict_windows(d, n) wherever n_out > 0
     for (long long w0 = 0; w0 < nwin; w0 += d->B) {
         st_dims q = *d; q.B = (int)(nwin - w0 < d->B ? nwin - w0 : d->B);
-        WS w; carve(&q, L, reinterpret_cast<char*>(ws) + p.head_bytes, &w);
+        WS w; carve(&q, L, reinterpret_cast<char*>(ws) + batch_off, &w);
         w.g16 = g16;
         w.Sfold = p.Sfold; w.SfoldT = p.SfoldT; w.Sfold16 = p.Sfold16; w.SfoldT16 = p.SfoldT16; w.W16 = p.W16;
         w.pl_W = p.pl_W; w.pl_Sfold = p.pl_Sfold; w.pl_SfoldT = p.pl_SfoldT;
@@ -1961,41 +1975,58 @@ static int predict_batches(const st_dims* d, const Layout& L, const PredictWS& p
         ST_LAUNCHED("predict_stage");
         const float* kn = q.K == 0 ? params : fill ? p.knobs : knobs + (size_t)w0 * q.K;      // K == 0: any resident float (call_begin)
         ST_TRY(stft_gemm(step_stft_plan(&q, w, GEMM_ANALYSIS, Wr, Wi), GemmOut{nullptr, nullptr, w.mag, w.phs, nullptr, nullptr}, stream));
-        ST_TRY(ae_fwd_body(&q, L, w.mag, w.phs, kn, ae_m, ae_p, w.mag_hat, w.phs_hat, w.AA, w.reg_p, nullptr, stream, g16 ? w.AA16 : nullptr, false, nullptr,
-                           img ? p.img : nullptr));
+        ST_TRY(ae_fwd_body(&q, L, w.mag, w.phs, kn, ae_m, ae_p, w.mag_hat, w.phs_hat, w.AA, w.reg_p, fit ? w.aews : nullptr, stream, g16 ? w.AA16 : nullptr, false, nullptr,
+                           img ? p.img : nullptr));      // fit: the code h4 stays at the head of the autoencoder workspace
         ST_TRY(stft_gemm(step_stft_plan(&q, w, GEMM_FRAMES), slabs_at(w.frs), stream));
         const int ns = frame_slabs(&q);
         const dim3 grid((q.y / 4 + 255) / 256, q.B);
         const size_t slab = (size_t)q.B * q.OT * q.N;
         const bool three = (q.N + q.H - 1) / q.H <= 3;      // the rule of ola_loss_impl for the four-sample form with all loads up front
+        if (!fit) {
+            with_bool(three, [&](auto NF3) { with_slabs(ns, [&](auto NS) {
+                hipLaunchKernelGGL((stp::predict_ola_kernel<T, NS(), NF3() ? 3 : 0>), grid, dim3(256), 0, st_stream(stream),
+                                   w.frs, slab, signal, out, a.s0, n_out, q.L, q.N, q.H, q.OT, q.y); }); });
+            ST_LAUNCHED("predict_ola");
+            continue;
+        }
+        const int nslot = (q.y + 255) / 256;
         with_bool(three, [&](auto NF3) { with_slabs(ns, [&](auto NS) {
-            hipLaunchKernelGGL((stp::predict_ola_kernel<T, NS(), NF3() ? 3 : 0>), grid, dim3(256), 0, st_stream(stream),
-                               w.frs, slab, signal, out, a.s0, n_out, q.L, q.N, q.H, q.OT, q.y); }); });
-        ST_LAUNCHED("predict_ola");
+            hipLaunchKernelGGL((stf::fit_ola_kernel<T, NS(), NF3() ? 3 : 0>), grid, dim3(256), 0, st_stream(stream),
+                               w.frs, slab, signal, reinterpret_cast<const T*>(fit->target), w.dsyn, g16 ? w.dsyn16 : nullptr, g16 ? gemm_ht(q.prec) : 0, w.loss_p, nslot,
+                               a.s0, n_out, q.L, q.N, q.H, q.OT, q.y); }); });
+        ST_LAUNCHED("fit_ola");
+        ST_TRY(stft_gemm(step_stft_plan(&q, w, GEMM_DGRAD), slabs_at(w.dAA), stream));
+        {
+            ST_REQ((size_t)synth_slabs(&q) * q.B * q.OT * L.KP < ((size_t)1 << 30) && (size_t)q.B * q.T * L.KP < ((size_t)1 << 30),
+                   "st_fit_knobs: batch too large for the kernel's 32-bit element offsets (B=%d)", q.B);
+            const stg::RowMap live = synth_live(&q);
+            const int groups = ae_fwd_groups(&q), kgrid = ae_knob_grid(&q);
+            ST_TRY(with_ht(ae_ht(q.prec), [&](auto HT) {
+                return launch_lds("ae_knob_bwd_kernel", sta::ae_knob_bwd_kernel<AE_KNOB_NW, HT()>, dim3(kgrid, 2), dim3(AE_KNOB_NW * 64),
+                                  (size_t)sta::ae_knob_lds_floats(AE_KNOB_NW) * sizeof(float), st_stream(stream),
+                                  w.mag, kn, ae_m, ae_p, L.go, w.mag_hat, w.phs_hat, w.dAA, w.aews, fit->kg, q.B, q.T, q.OT, q.F, q.K, L.KP,
+                                  live.t_lo, live.t_lo + live.Tv - 1, synth_slabs(&q), (size_t)q.B * q.OT * L.KP); }));
+            ST_LAUNCHED("ae_knob_bwd");
+            const size_t w5 = (size_t)L.offs[4] + (size_t)L.go.w[4];
+            hipLaunchKernelGGL(knob_grad_kernel, dim3(q.B), dim3(64), 0, st_stream(stream), params + w5, (const float*)fit->kg, params + w5 + L.PG,
+                               (const float*)fit->kg + (size_t)groups * 16, q.K, fit->rows, L.KP / 32);
+            ST_LAUNCHED("knob_grad");
+            stf::TailArgs t = fit->hyper;
+            t.loss_p = w.loss_p; t.n_lp = q.B * nslot; t.loss = fit->loss;
+            t.rows = fit->rows; t.nb = q.B; t.K = q.K; t.acc = fit->acc;
+            t.per_window = knob_rows != 1; t.first = w0 == 0; t.last = w0 + q.B >= nwin;
+            const size_t ro = t.per_window ? (size_t)w0 * q.K : 0;
+            t.knobs = fit->knobs + ro; t.m = fit->m + ro; t.v = fit->v + ro; t.grad = fit->grad ? fit->grad + ro : nullptr;
+            hipLaunchKernelGGL(stf::fit_tail_kernel, dim3(1), dim3(256), 0, st_stream(stream), t);
+            ST_LAUNCHED("fit_tail");
+        }
     }
     return ST_OK;
 }
-extern "C" int st_predict_long(const st_dims* d, const float* params, int fmt, const void* signal, long long n,
-                               const float* knobs, long long knob_rows, float* out, void* ws, void* stream)
+// once per call: the parameter side of prep_kernel (its per-batch jobs have no blocks here) into the head of the workspace
+static int predict_prep(const st_dims* d, const Layout& L, const PredictWS& p, const float* params, void* stream)
 {
-    Layout L; ST_TRY(make_layout(d, &L));
-    ST_REQ(params, "st_predict_long: null pointer (params)"); ST_REQ(signal, "st_predict_long: null pointer (signal)");
-    ST_REQ(knobs || d->K == 0, "st_predict_long: null pointer (knobs, K = %d)", d->K);
-    ST_REQ(out, "st_predict_long: null pointer (out)"); ST_REQ(ws, "st_predict_long: null pointer (ws)");
-    ST_REQ(n > 0, "st_predict_long: n must be positive (n = %lld)", n);
-    ST_REQ(fmt == ST_PCM_F32 || fmt == ST_PCM_S16, "st_predict_long: fmt = %d is neither ST_PCM_F32 nor ST_PCM_S16", fmt);
-    const long long nwin = predict_windows(d, n);
-    ST_REQ(knob_rows == 1 || knob_rows == nwin, "st_predict_long: knob_rows = %lld must be 1 or the window count (%lld windows for n = %lld)", knob_rows, nwin, n);
-    const uintptr_t sa = fmt == ST_PCM_S16 ? 7 : 15;
-    ST_REQ((reinterpret_cast<uintptr_t>(signal) & sa) == 0, "st_predict_long: signal must be %d-byte aligned", (int)sa + 1);
-    ST_REQ((reinterpret_cast<uintptr_t>(out) & 15) == 0, "st_predict_long: out must be 16-byte aligned");
-    ST_REQ((reinterpret_cast<uintptr_t>(ws) & 15) == 0, "st_predict_long: ws must be 16-byte aligned");
-    ST_REQ(!ae_is_wide(d), "st_predict_long: not supported for the wide autoencoder geometries (T = %d > 32 or OT = %d > 16): st_predict_supported", d->T, d->OT);
-    const long long n_out = n - ((long long)d->L - d->y);
-    if (n_out <= 0) return ST_OK;      // shorter than the first window's lookback: nothing to predict, nothing launched
-    PredictWS p; predict_carve(d, ws, &p);
-    prof_mark("begin", stream);
-    {   // once per call: the parameter side of prep_kernel (its per-batch jobs have no blocks here)
+    {
         const int family = stft_family(d, GEMM_ANALYSIS, SGP_PADDED | SGP_G16);      // as predict_batches
         const bool g16 = family == GF_G16;
         stm::PrepArgs a;
@@ -2019,8 +2050,108 @@ extern "C" int st_predict_long(const st_dims* d, const float* params, int fmt, c
             ST_TRY(planes_prepare(d, a.Wr, a.Wi, w, stream));
         }
     }
+    return ST_OK;
+}
+extern "C" int st_predict_long(const st_dims* d, const float* params, int fmt, const void* signal, long long n,
+                               const float* knobs, long long knob_rows, float* out, void* ws, void* stream)
+{
+    Layout L; ST_TRY(make_layout(d, &L));
+    ST_REQ(params, "st_predict_long: null pointer (params)"); ST_REQ(signal, "st_predict_long: null pointer (signal)");
+    ST_REQ(knobs || d->K == 0, "st_predict_long: null pointer (knobs, K = %d)", d->K);
+    ST_REQ(out, "st_predict_long: null pointer (out)"); ST_REQ(ws, "st_predict_long: null pointer (ws)");
+    ST_REQ(n > 0, "st_predict_long: n must be positive (n = %lld)", n);
+    ST_REQ(fmt == ST_PCM_F32 || fmt == ST_PCM_S16, "st_predict_long: fmt = %d is neither ST_PCM_F32 nor ST_PCM_S16", fmt);
+    const long long nwin = predict_windows(d, n);
+    ST_REQ(knob_rows == 1 || knob_rows == nwin, "st_predict_long: knob_rows = %lld must be 1 or the window count (%lld windows for n = %lld)", knob_rows, nwin, n);
+    const uintptr_t sa = fmt == ST_PCM_S16 ? 7 : 15;
+    ST_REQ((reinterpret_cast<uintptr_t>(signal) & sa) == 0, "st_predict_long: signal must be %d-byte aligned", (int)sa + 1);
+    ST_REQ((reinterpret_cast<uintptr_t>(out) & 15) == 0, "st_predict_long: out must be 16-byte aligned");
+    ST_REQ((reinterpret_cast<uintptr_t>(ws) & 15) == 0, "st_predict_long: ws must be 16-byte aligned");
+    ST_REQ(!ae_is_wide(d), "st_predict_long: not supported for the wide autoencoder geometries (T = %d > 32 or OT = %d > 16): st_predict_supported", d->T, d->OT);
+    const long long n_out = n - ((long long)d->L - d->y);
+    if (n_out <= 0) return ST_OK;      // shorter than the first window's lookback: nothing to predict, nothing launched
+    PredictWS p; predict_carve(d, ws, &p);
+    prof_mark("begin", stream);
+    ST_TRY(predict_prep(d, L, p, params, stream));
     return fmt == ST_PCM_S16 ? predict_batches(d, L, p, params, reinterpret_cast<const short*>(signal), n, knobs, knob_rows, out, n_out, ws, stream)
                              : predict_batches(d, L, p, params, reinterpret_cast<const float*>(signal), n, knobs, knob_rows, out, n_out, ws, stream);
+}
+
+// ------------------------------------------------------------------------------ knob fit on the device (st_fit.h)
+// predict.fit_knobs in one call: every batch of every optimiser step is enqueued here.  The workspace is [st_predict_long's head | the fit's own rows and scratch |
+// one batch's workspace]: per-window gradient rows [d->B][K] (a batch's windows; one knob row: summed into the accumulator batch by batch in ascending window
+// order, one row per window: consumed by the batch's own tail launch), the accumulator [64] and the per-group column sums of d a5 [2][d->B * KP / 32][16].
+struct FitWS { float *rows, *acc, *kg; size_t bytes; };
+static void fit_carve(const st_dims* d, void* base, FitWS* f)
+{
+    size_t off = 0;
+    auto take = [&](size_t n) { float* q = base ? reinterpret_cast<float*>(base) + off : nullptr; off += (n + 63) / 64 * 64; return q; };
+    f->rows = take((size_t)d->B * (d->K > 0 ? d->K : 1)); f->acc = take(64); f->kg = take((size_t)2 * ae_fwd_groups(d) * 16);
+    f->bytes = off * sizeof(float);
+}
+extern "C" int st_fit_knobs_supported(const st_dims* d) { return (predict_ok(d) && d->K >= 1) ? 1 : 0; }
+extern "C" size_t st_fit_knobs_ws_bytes(const st_dims* d)
+{
+    if (!st_fit_knobs_supported(d)) return 0;
+    const size_t pb = st_predict_ws_bytes(d);
+    if (!pb) return 0;
+    FitWS f; fit_carve(d, nullptr, &f);
+    return pb + f.bytes;
+}
+extern "C" int st_fit_knobs(const st_dims* d, const float* params, int fmt, const void* signal, const void* target, long long n,
+                            float* knobs, long long knob_rows, float* adam_m, float* adam_v,
+                            long long first_step, int steps, float lr, float beta1, float beta2, float eps,
+                            double* loss_hist, float* grad_hist, void* ws, void* stream)
+{
+    Layout L;
+    if (make_layout(d, &L) != ST_OK) {      // the dims rule that failed, under this entry's name
+        char rule[400]; snprintf(rule, sizeof(rule), "%s", st_last_error());
+        return st_fail(ST_ERR_ARG, "st_fit_knobs: %s", rule);
+    }
+    ST_REQ(d->K >= 1, "st_fit_knobs: K = %d (a model without knobs has no knobs to fit)", d->K);
+    ST_REQ(params, "st_fit_knobs: null pointer (params)"); ST_REQ(signal, "st_fit_knobs: null pointer (signal)"); ST_REQ(target, "st_fit_knobs: null pointer (target)");
+    ST_REQ(knobs, "st_fit_knobs: null pointer (knobs)"); ST_REQ(adam_m, "st_fit_knobs: null pointer (adam_m)"); ST_REQ(adam_v, "st_fit_knobs: null pointer (adam_v)");
+    ST_REQ(loss_hist, "st_fit_knobs: null pointer (loss_hist)"); ST_REQ(ws, "st_fit_knobs: null pointer (ws)");
+    ST_REQ(n > 0, "st_fit_knobs: n must be positive (n = %lld)", n);
+    ST_REQ(fmt == ST_PCM_F32 || fmt == ST_PCM_S16, "st_fit_knobs: fmt = %d is neither ST_PCM_F32 nor ST_PCM_S16", fmt);
+    const long long nwin = predict_windows(d, n);
+    ST_REQ(knob_rows == 1 || knob_rows == nwin, "st_fit_knobs: knob_rows = %lld must be 1 or the window count (%lld windows for n = %lld)", knob_rows, nwin, n);
+    ST_REQ(steps >= 1, "st_fit_knobs: steps = %d must be at least 1", steps);
+    ST_REQ(first_step >= 1, "st_fit_knobs: first_step = %lld must be at least 1 (Adam's step number is 1-based)", first_step);
+    ST_REQ(std::isfinite(lr) && lr >= 0.f, "st_fit_knobs: lr = %g must be finite and not negative", (double)lr);
+    ST_REQ(std::isfinite(beta1) && beta1 >= 0.f && beta1 < 1.f, "st_fit_knobs: beta1 = %g must lie in [0, 1)", (double)beta1);
+    ST_REQ(std::isfinite(beta2) && beta2 >= 0.f && beta2 < 1.f, "st_fit_knobs: beta2 = %g must lie in [0, 1)", (double)beta2);
+    ST_REQ(std::isfinite(eps) && eps > 0.f, "st_fit_knobs: eps = %g must be finite and positive", (double)eps);
+    const uintptr_t sa = fmt == ST_PCM_S16 ? 7 : 15;
+    ST_REQ((reinterpret_cast<uintptr_t>(signal) & sa) == 0, "st_fit_knobs: signal must be %d-byte aligned", (int)sa + 1);
+    ST_REQ((reinterpret_cast<uintptr_t>(target) & sa) == 0, "st_fit_knobs: target must be %d-byte aligned", (int)sa + 1);
+    ST_REQ((reinterpret_cast<uintptr_t>(knobs) & 15) == 0, "st_fit_knobs: knobs must be 16-byte aligned");
+    ST_REQ((reinterpret_cast<uintptr_t>(adam_m) & 15) == 0, "st_fit_knobs: adam_m must be 16-byte aligned");
+    ST_REQ((reinterpret_cast<uintptr_t>(adam_v) & 15) == 0, "st_fit_knobs: adam_v must be 16-byte aligned");
+    ST_REQ((reinterpret_cast<uintptr_t>(ws) & 15) == 0, "st_fit_knobs: ws must be 16-byte aligned");
+    ST_REQ(!ae_is_wide(d), "st_fit_knobs: not supported for the wide autoencoder geometries (T = %d > 32 or OT = %d > 16): st_fit_knobs_supported", d->T, d->OT);
+    const long long n_out = n - ((long long)d->L - d->y);
+    if (n_out <= 0) return ST_OK;      // no output sample, no objective: nothing launched, every buffer left alone
+    PredictWS p; predict_carve(d, ws, &p);
+    FitWS f; fit_carve(d, reinterpret_cast<char*>(ws) + p.head_bytes, &f);
+    const size_t batch_off = p.head_bytes + f.bytes;
+    prof_mark("begin", stream);
+    ST_TRY(predict_prep(d, L, p, params, stream));
+    const size_t row_floats = (size_t)knob_rows * d->K;
+    for (int s = 0; s < steps; ++s) {
+        const double t = (double)(first_step + s);
+        const double bc1 = 1.0 - pow((double)beta1, t), bc2 = 1.0 - pow((double)beta2, t);
+        FitJob job;
+        job.target = target; job.kg = f.kg; job.rows = f.rows; job.acc = f.acc;
+        job.knobs = knobs; job.m = adam_m; job.v = adam_v; job.grad = grad_hist ? grad_hist + (size_t)s * row_floats : nullptr; job.loss = loss_hist + s;
+        job.hyper = stf::TailArgs{};
+        job.hyper.inv_n_d = 1.0 / (double)n_out; job.hyper.inv_n = (float)(1.0 / (double)n_out);
+        job.hyper.neg_step = (float)(-(double)lr / bc1); job.hyper.bc2_sqrt = (float)sqrt(bc2);
+        job.hyper.w1 = (float)(1.0 - (double)beta1); job.hyper.b2 = beta2; job.hyper.w2 = (float)(1.0 - (double)beta2); job.hyper.eps = eps;
+        ST_TRY(fmt == ST_PCM_S16 ? predict_batches(d, L, p, params, reinterpret_cast<const short*>(signal), n, knobs, knob_rows, nullptr, n_out, ws, stream, &job, batch_off)
+                                 : predict_batches(d, L, p, params, reinterpret_cast<const float*>(signal), n, knobs, knob_rows, nullptr, n_out, ws, stream, &job, batch_off));
+    }
+    return ST_OK;
 }
 
 // Data-parallel split of st_loss_backward: after phase 1 the synthesis + autoencoder gradients

@@ -522,6 +522,72 @@ class StepEngine:
                        C.c_void_p(signal.data_ptr()), n, _lib.ptr(kn), rows, C.c_void_p(out.data_ptr()), _lib.ptr(self._predict_ws), self._stream())
         return out[:n_out]
 
+    # ---------------------------------------------------------------- knob fit on the device
+    def fit_knobs_supported(self):
+        """Whether fit_knobs() runs this geometry (st_fit_knobs_supported: predict_supported() and at least one knob; host arithmetic only)."""
+        return bool(self.lib.st_fit_knobs_supported(C.byref(self.dims.with_batch(1))))
+
+    def fit_knobs(self, signal, target, knobs, steps=50, lr=0.05, betas=(0.9, 0.999), eps=1e-8, batch=None, state=None, want_grads=False):
+        """The knob settings for which the model turns `signal` into `target`, fitted on the device in ONE C call (st_fit_knobs in include/signaltrain_hip.h):
+        `steps` steps of Adam on J = mean over the n - (L - y) output samples of logcosh(y_hat - target), clamped to [-0.5, 0.5] after every step.  Output
+        positions of the last window behind the recording's end carry no loss and no gradient (predict.fit_knobs' batched route counts its zero-padded tail);
+        the two objectives coincide when n = L + k y.
+        signal, target: 1-D float32 or int16 tensors of equal length on this engine's device (mixed dtypes: the int16 one is converted on the device, s / 32767);
+        knobs: [K] (one setting) or [nwin, K] (one row per window), the start values -- cloned; batch: windows per internal batch (default max_batch);
+        state: (m, v, first_step) as a previous call returned it, so that calls chain (default: zeros and step 1).
+        Returns (knobs, loss_hist [steps] float64, grad_hist [steps, rows, K] or None, (m, v, next_step)), all on the device.  No host sync.  The engine keeps
+        a workspace of its own for this (st_fit_knobs_ws_bytes, allocated on first use): self.ws and predict_long's workspace are not written."""
+        for name, t in (("signal", signal), ("target", target)):
+            if not (torch.is_tensor(t) and t.dim() == 1 and t.device == self.device and t.dtype in (torch.float32, torch.int16)):
+                raise ValueError(f"fit_knobs: {name} must be a 1-D float32 or int16 tensor on {self.device}")
+        if signal.numel() != target.numel():
+            raise ValueError(f"fit_knobs: signal has {signal.numel()} samples, target {target.numel()}")
+        if signal.dtype != target.dtype:          # the C rule for int16: (float)((double)s / 32767.0)
+            signal, target = ((t.double() / 32767.0).float() if t.dtype == torch.int16 else t for t in (signal, target))
+        align = 8 if signal.dtype == torch.int16 else 16
+
+        def aligned(t):
+            t = t.contiguous()
+            return t.clone() if t.data_ptr() % align else t      # a view that starts off the boundary the kernels' quads need
+        signal, target = aligned(signal), aligned(target)
+        B = int(batch or self.max_batch)
+        if B < 1:
+            raise ValueError(f"fit_knobs: batch = {B}")
+        steps = int(steps)
+        d = self.dims.with_batch(B)
+        d.prec, d.loss_scale, d.clip_all = _lib.PREC[self.compute_dtype], self.loss_scale, int(self.clip_all)
+        if d.K < 1:
+            raise ValueError("fit_knobs: the model has no knobs")
+        n = int(signal.numel())
+        nwin = int(self.lib.st_predict_windows(C.byref(d), n))
+        kn = torch.as_tensor(knobs).to(device=self.device, dtype=torch.float32).reshape(-1, d.K).clone()
+        rows = int(kn.shape[0])
+        if rows not in (1, nwin):
+            raise ValueError(f"fit_knobs: knobs has {rows} rows: one row, or one per window ({nwin} windows for {n} samples)")
+        if state is None:
+            m, v, first = torch.zeros_like(kn), torch.zeros_like(kn), 1
+        else:
+            m, v, first = state
+            m = m.to(device=self.device, dtype=torch.float32).reshape(rows, d.K).clone()
+            v = v.to(device=self.device, dtype=torch.float32).reshape(rows, d.K).clone()
+            first = int(first)
+        sizes = self.__dict__.setdefault("_fit_sizes", {})           # as predict_long: the size query carves every batch 1 .. B, once per (B, dtype)
+        if (B, self.compute_dtype) not in sizes:
+            sizes[(B, self.compute_dtype)] = int(self.lib.st_fit_knobs_ws_bytes(C.byref(d)))
+        need = sizes[(B, self.compute_dtype)]
+        if need <= 0:
+            raise RuntimeError(f"fit_knobs: st_fit_knobs_supported refuses this geometry (T={d.T}, OT={d.OT}): the wide autoencoder geometries stay on the batched route")
+        if getattr(self, "_fit_ws", None) is None or self._fit_ws.numel() < need:
+            self._fit_ws = torch.zeros(need, dtype=torch.uint8, device=self.device)
+        loss_hist = torch.zeros(max(steps, 0), dtype=torch.float64, device=self.device)
+        grad_hist = torch.zeros(max(steps, 0), rows, d.K, dtype=torch.float32, device=self.device) if want_grads else None
+        self._call("st_fit_knobs", C.byref(d), _lib.ptr(self.params), _lib.PCM_S16 if signal.dtype == torch.int16 else _lib.PCM_F32,
+                   C.c_void_p(signal.data_ptr()), C.c_void_p(target.data_ptr()), n, _lib.ptr(kn), rows, _lib.ptr(m), _lib.ptr(v),
+                   first, steps, float(lr), float(betas[0]), float(betas[1]), float(eps),
+                   C.c_void_p(loss_hist.data_ptr()), _lib.ptr(grad_hist), _lib.ptr(self._fit_ws), self._stream())
+        shape = (d.K,) if (rows == 1 and torch.as_tensor(knobs).dim() == 1) else (rows, d.K)
+        return kn.reshape(shape), loss_hist, grad_hist, (m, v, first + steps)
+
     # ---------------------------------------------------------------- the step as one HIP graph
     def graph_capture(self, batch, lr_table, betas=(0.9, 0.999), eps=1e-8):
         """Capture st_train_step for `batch` windows into a HIP graph (st_graph_create).  The step counter and the learning rate

@@ -17,7 +17,9 @@ import numpy as np
 import torch
 
 ROUTES = ("batched", "device")
+FIT_ROUTES = ("batched", "device")
 _warned_unsupported = False
+_warned_fit_unsupported = False
 
 
 
@@ -127,13 +129,26 @@ def _predict_device(signal, knobs_nn, model, chunk_size, out_chunk_size, device,
     return y.cpu().numpy()
 
 
-def fit_knobs(signal, target, model, chunk_size, out_chunk_size, steps=50, lr=0.05, init=None, batch_size=200, compand=False, grad_history=None):
+def fit_knobs(signal, target, model, chunk_size, out_chunk_size, steps=50, lr=0.05, init=None, batch_size=200, compand=False, grad_history=None,
+              route="batched"):
     """The trained model used the other way round: given a recording and its processed version, the ONE knob vector (normalised settings, [-0.5, 0.5])
     for which the model turns `signal` into `target`.  Both are windowed as predict_long windows its input (the target of a window is its last
     out_chunk_size samples); the objective is the mean log-cosh of y_hat - target over all windows, minimised by torch's Adam on the K values, clamped to
     [-0.5, 0.5] after every step.  The gradient of a step is the sum over windows of d / d knobs out of the ONE backward pass per batch
     (StepEngine.backward_with_knob_grad with g_y_hat = tanh(y_hat - target) / n).
-    init: start vector (default zeros).  grad_history: a list that receives every step's gradient (numpy [K]).  Returns (knobs_nn [K] float32, loss_history)."""
+    init: start vector (default zeros).  grad_history: a list that receives every step's gradient (numpy [K]).  Returns (knobs_nn [K] float32, loss_history).
+    route="device" (FIT_ROUTES) runs the whole fit as ONE C call (st_fit_knobs, StepEngine.fit_knobs): the two recordings go to the device once, every batch of
+    every step is enqueued by that call and nothing synchronises with the host until the result is read.  It also takes init of shape [nwin, K] -- one knob row
+    per window (knob automation; the result is then [nwin, K], grad_history receives [nwin, K] arrays).  Its objective is the mean over the
+    len(signal) - (chunk_size - out_chunk_size) output samples the recording really has: positions of the last window behind the recording's end carry no loss
+    and no gradient, where the batched route counts its zero-padded tail.  The two objectives coincide when len(signal) = chunk_size + k * out_chunk_size.
+    On a geometry st_fit_knobs_supported rejects it warns once and takes the batched route."""
+    if route not in FIT_ROUTES:
+        raise ValueError(f"fit_knobs: route must be one of {FIT_ROUTES}, not {route!r}")
+    if route == "device":
+        res = _fit_device(signal, target, model, chunk_size, out_chunk_size, steps, lr, init, batch_size, compand, grad_history)
+        if res is not None:
+            return res
     device = next(model.parameters()).device
     signal = np.ascontiguousarray(signal, dtype=np.float32); target = np.ascontiguousarray(target, dtype=np.float32)
     assert signal.shape == target.shape and signal.ndim == 1, (signal.shape, target.shape)
@@ -173,3 +188,36 @@ def fit_knobs(signal, target, model, chunk_size, out_chunk_size, steps=50, lr=0.
         with torch.no_grad():
             kn.clamp_(-0.5, 0.5)
     return kn.detach().cpu().numpy(), history
+
+
+def _fit_device(signal, target, model, chunk_size, out_chunk_size, steps, lr, init, batch_size, compand, grad_history):
+    """route="device" of fit_knobs; None where the library does not run this geometry that way (the caller then takes the batched route)."""
+    global _warned_fit_unsupported
+    device = next(model.parameters()).device
+    signal = np.ascontiguousarray(signal, dtype=np.float32); target = np.ascontiguousarray(target, dtype=np.float32)
+    assert signal.shape == target.shape and signal.ndim == 1, (signal.shape, target.shape)
+    n = int(signal.shape[0])
+    nwin = 1 if n < chunk_size else -(-(n - chunk_size) // out_chunk_size) + 1
+    bs = max(min(int(batch_size), nwin), 1)
+    eng = model.engine(torch.empty((), dtype=torch.float32, device=device).expand(bs, chunk_size))      # shape and device only: nothing is read
+    if (eng.dims.L, eng.dims.y) != (chunk_size, out_chunk_size):
+        raise ValueError(f"fit_knobs: chunk_size / out_chunk_size = {chunk_size} / {out_chunk_size}, the model has {eng.dims.L} / {eng.dims.y}")
+    if not eng.fit_knobs_supported():
+        if not _warned_fit_unsupported:
+            _warned_fit_unsupported = True
+            warnings.warn(f"signaltrain_amd.fit_knobs: route='device' does not run this geometry (T={eng.dims.T}, OT={eng.dims.OT}, K={eng.dims.K}: "
+                          "st_fit_knobs_supported); taking the batched route", RuntimeWarning, stacklevel=3)
+        return None
+    if compand:                                                        # a host map before the upload, as on the batched route
+        from . import audio
+        signal = np.ascontiguousarray(audio.mu_compand(signal), dtype=np.float32); target = np.ascontiguousarray(audio.mu_compand(target), dtype=np.float32)
+    K = int(model.num_knobs)
+    kn0 = np.zeros(K, np.float32) if init is None else np.asarray(init, dtype=np.float32)
+    kn0 = kn0.reshape(nwin, K) if (kn0.ndim == 2 and kn0.shape[0] == nwin and nwin > 1) else kn0.reshape(K)
+    with torch.no_grad():
+        kn, loss, grads, _ = eng.fit_knobs(torch.from_numpy(signal).to(device), torch.from_numpy(target).to(device), torch.from_numpy(kn0).to(device),
+                                           steps=int(steps), lr=lr, batch=bs, want_grads=grad_history is not None)
+    if grad_history is not None:
+        g = grads.cpu().numpy()
+        grad_history.extend(g[s].reshape(kn0.shape).copy() for s in range(g.shape[0]))
+    return kn.cpu().numpy(), [float(v) for v in loss.cpu().numpy()]
