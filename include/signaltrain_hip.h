@@ -410,6 +410,42 @@ int    st_fit_knobs(const st_dims* d, const float* params, int fmt, const void* 
                     double* loss_hist /* device, [steps] */, float* grad_hist /* device, [steps][knob_rows][K], may be NULL */,
                     void* ws, void* stream);
 
+/* Encode a recording once, decode it at any knob setting.  The knobs enter at layer 5 of 9: window staging, the analysis GEMM, the polar form and encoder layers
+ * 1..4 of both autoencoders do not depend on them.  st_encode_long runs that half over the recording (windows, lengths and formats are st_predict_long's) and
+ * leaves the recording's CODE in device memory; st_decode_long and st_fit_knobs_coded then run only layers 5..9, the polar epilogue, the frames GEMM and the
+ * overlap-add per knob setting / optimiser step.  The fused autoencoder geometries only (st_decode_supported == st_predict_supported).
+ *   code        st_code_bytes(d, n) bytes, 16-byte aligned, opaque.  Per window of st_predict_windows(d, n): the 16-wide code h4 of both nets and the last OT frames
+ *               of the window's mag and phs, rows padded to KP / 2 bins:
+ *                   st_code_bytes(d, n) = st_predict_windows(d, n) * (st_kp(d->F) / 2) * (32 + 2 * d->OT) * sizeof(float)
+ *               and 0 for bad dims, the wide geometries and n <= 0.  Window-major: it does not depend on d->B, so a code built at one batch size decodes at another.
+ *               It is valid for the st_dims.prec, the parameters and the recording it was built from; that none of them changed since the encode is the caller's
+ *               precondition (nothing detects it).
+ *   ws          st_decode_ws_bytes(d) bytes (== st_predict_ws_bytes(d)), 16-byte aligned, for st_encode_long and st_decode_long; st_fit_knobs_coded takes
+ *               st_fit_knobs_ws_bytes(d).  Scratch: nothing in it is read before it is written.
+ * st_decode_long: knobs [n_settings][knob_rows][K] on the device, knob_rows = 1 (one setting for the whole recording) or the window count (one row per window),
+ *   n_settings >= 1.  Row s of the result -- the n_out = n - (L - y) samples st_predict_long gives at setting s at this st_dims.prec, up to the order of a few sums --
+ *   goes to out + s * out_pitch; out_pitch >= n_out, out_pitch % 4 == 0, out 16-byte aligned; nothing outside [0, n_out) of a row is written.  The recording is an
+ *   argument because the overlap-add takes the residual x / 2 from it; nothing at or past signal + n is read.  Settings run inside the batch loop: settings 2..S of a
+ *   batch read its code from the caches.
+ * st_fit_knobs_coded: st_fit_knobs with the code after params; every argument, result and refusal is st_fit_knobs' (named st_fit_knobs_coded), plus: code NULL or
+ *   not 16-byte aligned.  Every step's forward is the decoder forward from the code -- no staging launch, no analysis GEMM, no encoder; everything behind the frames
+ *   GEMM is st_fit_knobs'.
+ * No float atomics, fixed summation orders, no allocation, no hipMemcpy, no host synchronisation; parameters, the code (decode, fit) and the recording are only read.
+ * Refused before any launch (ST_ERR_ARG, the rule in st_last_error(), naming the entry): bad dims; a null pointer, named; n <= 0; an unknown fmt; signal not 16-byte
+ * aligned (ST_PCM_S16: 8-byte); code, out or ws not 16-byte aligned; knob_rows neither 1 nor the window count; n_settings < 1; out_pitch < n_out or not a multiple of
+ * 4; dims st_decode_supported rejects (the wide geometries).  An n with no output sample (n <= L - y) returns ST_OK without a launch. */
+int    st_decode_supported(const st_dims* d);
+size_t st_decode_ws_bytes(const st_dims* d);
+size_t st_code_bytes(const st_dims* d, long long n);
+int    st_encode_long(const st_dims* d, const float* params, int fmt, const void* signal, long long n, void* code, void* ws, void* stream);
+int    st_decode_long(const st_dims* d, const float* params, const void* code, int fmt, const void* signal, long long n,
+                      const float* knobs, long long knob_rows, int n_settings, float* out, long long out_pitch, void* ws, void* stream);
+int    st_fit_knobs_coded(const st_dims* d, const float* params, const void* code, int fmt, const void* signal, const void* target, long long n,
+                          float* knobs, long long knob_rows, float* adam_m, float* adam_v,
+                          long long first_step, int steps, float lr, float beta1, float beta2, float eps,
+                          double* loss_hist /* device, [steps] */, float* grad_hist /* device, [steps][knob_rows][K], may be NULL */,
+                          void* ws, void* stream);
+
 /* Data-parallel split of st_loss_backward.  After p1 the gradients of the synthesis bases and both
  * autoencoders (grads[offs[2]..end)) are final: all-reduce them while p2 computes the analysis
  * weight gradient (rows [0,F) of tensors 0 and 1) and the loss scalars. */

@@ -125,6 +125,12 @@ SIGNATURES = {
     "st_fit_knobs_supported": (_i, [_D]),
     "st_fit_knobs_ws_bytes": (C.c_size_t, [_D]),
     "st_fit_knobs": (_i, [_D, _p, _i, _p, _p, C.c_longlong, _p, C.c_longlong, _p, _p, C.c_longlong, _i, _f, _f, _f, _f, _p, _p, _p, _p]),
+    "st_decode_supported": (_i, [_D]),
+    "st_decode_ws_bytes": (C.c_size_t, [_D]),
+    "st_code_bytes": (C.c_size_t, [_D, C.c_longlong]),
+    "st_encode_long": (_i, [_D, _p, _i, _p, C.c_longlong, _p, _p, _p]),
+    "st_decode_long": (_i, [_D, _p, _p, _i, _p, C.c_longlong, _p, C.c_longlong, _i, _p, C.c_longlong, _p, _p]),
+    "st_fit_knobs_coded": (_i, [_D, _p, _p, _i, _p, _p, C.c_longlong, _p, C.c_longlong, _p, _p, C.c_longlong, _i, _f, _f, _f, _f, _p, _p, _p, _p]),
     "st_loss_backward_p1": (_i, [_D, _p, _p, _p, _p, _p, _p, _p]),
     "st_loss_backward_p2": (_i, [_D, _p, _p, _p, _p, _p]),
     "st_loss_backward_p2_staged": (_i, [_D, _p, _p, _p, _p, _p, _p]),

@@ -25,6 +25,7 @@
 #include "st_feed_live.h"
 #include "st_feed_stream.h"
 #include "st_predict.h"
+#include "st_decode.h"
 #include "st_fit.h"
 
 // ------------------------------------------------------------------------------ errors
@@ -1947,12 +1948,23 @@ struct FitJob {
     float *knobs, *m, *v, *grad; double* loss;       // grad: this step's row(s) of grad_hist, or NULL
     stf::TailArgs hyper;                             // inv_n, inv_n_d and Adam's scalars of this step
 };
+// The coded routes ride on it too (cj != NULL, st_decode.h).  code_out: st_encode_long -- the knob-independent half of every batch (stage kernel, analysis GEMM, the
+// forward kernel's code-only pass) and the pack kernel, nothing else.  code: the forward of a batch is ae_dec_fwd_kernel from the code -- st_decode_long runs it, the
+// frames GEMM and predict_ola once per knob setting INSIDE the batch (settings 2..S find the batch's code in L2 / Infinity Cache), st_fit_knobs_coded once, with
+// mag_hat / phs_hat and the batch-layout h4, magnitude tail and knob rows ae_knob_bwd_kernel reads written through.  cj == NULL: the launches of st_predict_long and
+// st_fit_knobs, unchanged.
+struct CodeJob { float* code_out; const float* code; int n_settings; long long out_pitch; size_t set_stride; };      // set_stride: floats between two settings' knob rows
+// ae_dec_fwd_kernel: 8-wave workgroups, four waves per SIMD, two workgroups per CU
+static int ae_dec_grid(const st_dims* d) { int g = (ae_fwd_groups(d) + sta::AE_DEC_NW - 1) / sta::AE_DEC_NW; int c = num_cus() * sta::AE_DEC_WGS; return g < c ? g : c; }
 template <typename T>
 static int predict_batches(const st_dims* d, const Layout& L, const PredictWS& p, const float* params, const T* signal, long long n,
                            const float* knobs, long long knob_rows, float* out, long long n_out, void* ws, void* stream,
-                           const FitJob* fit = nullptr, size_t batch_off = 0)
+                           const FitJob* fit = nullptr, size_t batch_off = 0, const CodeJob* cj = nullptr)
 {
     if (!batch_off) batch_off = p.head_bytes;
+    const bool enc = cj && cj->code_out, dec = cj && cj->code;
+    const int nset = dec && !fit ? cj->n_settings : 1;
+    const size_t CW = stc::code_window_floats(L.KP / 2, d->OT);
     const float* Wr = params + L.offs[0]; const float* Wi = params + L.offs[1];
     const float* ae_m = params + L.offs[4]; const float* ae_p = params + L.offs[22];
     const bool g16 = stft_family(d, GEMM_ANALYSIS, SGP_PADDED | SGP_G16) == GF_G16, img = predict_img(d);      // the 16-bit pipeline wherever the precision admits it, as the training entries
@@ -1971,54 +1983,83 @@ static int predict_batches(const st_dims* d, const Layout& L, const PredictWS& p
         a.mag = w.mag; a.phs = w.phs; a.T = q.T; a.F = q.F; a.t_lo = map.t_lo; a.Tv = map.Tv; a.n_dead = q.B * (q.T - map.Tv);
         const bool fill = knob_rows == 1 && q.K > 0;
         a.knob_row = knobs; a.knobs = p.knobs; a.K = q.K; a.n_kn = fill ? (q.B * q.K + 255) / 256 : 0;
-        hipLaunchKernelGGL(stp::predict_stage_kernel<T>, dim3(a.n_pad + a.n_dead + a.n_kn), dim3(256), 0, st_stream(stream), a);
-        ST_LAUNCHED("predict_stage");
         const float* kn = q.K == 0 ? params : fill ? p.knobs : knobs + (size_t)w0 * q.K;      // K == 0: any resident float (call_begin)
-        ST_TRY(stft_gemm(step_stft_plan(&q, w, GEMM_ANALYSIS, Wr, Wi), GemmOut{nullptr, nullptr, w.mag, w.phs, nullptr, nullptr}, stream));
-        ST_TRY(ae_fwd_body(&q, L, w.mag, w.phs, kn, ae_m, ae_p, w.mag_hat, w.phs_hat, w.AA, w.reg_p, fit ? w.aews : nullptr, stream, g16 ? w.AA16 : nullptr, false, nullptr,
-                           img ? p.img : nullptr));      // fit: the code h4 stays at the head of the autoencoder workspace
-        ST_TRY(stft_gemm(step_stft_plan(&q, w, GEMM_FRAMES), slabs_at(w.frs), stream));
-        const int ns = frame_slabs(&q);
-        const dim3 grid((q.y / 4 + 255) / 256, q.B);
-        const size_t slab = (size_t)q.B * q.OT * q.N;
-        const bool three = (q.N + q.H - 1) / q.H <= 3;      // the rule of ola_loss_impl for the four-sample form with all loads up front
-        if (!fit) {
-            with_bool(three, [&](auto NF3) { with_slabs(ns, [&](auto NS) {
-                hipLaunchKernelGGL((stp::predict_ola_kernel<T, NS(), NF3() ? 3 : 0>), grid, dim3(256), 0, st_stream(stream),
-                                   w.frs, slab, signal, out, a.s0, n_out, q.L, q.N, q.H, q.OT, q.y); }); });
-            ST_LAUNCHED("predict_ola");
+        if (!dec) {
+            if (enc) a.n_kn = 0;      // the code does not depend on the knobs: the code-only pass loads a knob row (any resident floats) and drops it
+            hipLaunchKernelGGL(stp::predict_stage_kernel<T>, dim3(a.n_pad + a.n_dead + a.n_kn), dim3(256), 0, st_stream(stream), a);
+            ST_LAUNCHED("predict_stage");
+            ST_TRY(stft_gemm(step_stft_plan(&q, w, GEMM_ANALYSIS, Wr, Wi), GemmOut{nullptr, nullptr, w.mag, w.phs, nullptr, nullptr}, stream));
+        }
+        if (enc) {      // st_encode_long: the knob-independent half, then the batch's h4 and tails to their windows of the code
+            ST_TRY(ae_fwd_body(&q, L, w.mag, w.phs, q.K == 0 ? params : p.knobs, ae_m, ae_p, nullptr, nullptr, nullptr, nullptr, w.aews, stream, nullptr, false, nullptr,
+                               img ? p.img : nullptr));
+            const int n4 = (int)(CW / 4);
+            hipLaunchKernelGGL(stc::code_pack_kernel, dim3((n4 + 1023) / 1024, q.B), dim3(256), 0, st_stream(stream),
+                               (const float*)w.aews, (const float*)w.mag, (const float*)w.phs, cj->code_out + (size_t)w0 * CW, q.B, q.T, q.OT, q.F, L.KP / 2);
+            ST_LAUNCHED("code_pack");
             continue;
         }
-        const int nslot = (q.y + 255) / 256;
-        with_bool(three, [&](auto NF3) { with_slabs(ns, [&](auto NS) {
-            hipLaunchKernelGGL((stf::fit_ola_kernel<T, NS(), NF3() ? 3 : 0>), grid, dim3(256), 0, st_stream(stream),
-                               w.frs, slab, signal, reinterpret_cast<const T*>(fit->target), w.dsyn, g16 ? w.dsyn16 : nullptr, g16 ? gemm_ht(q.prec) : 0, w.loss_p, nslot,
-                               a.s0, n_out, q.L, q.N, q.H, q.OT, q.y); }); });
-        ST_LAUNCHED("fit_ola");
-        ST_TRY(stft_gemm(step_stft_plan(&q, w, GEMM_DGRAD), slabs_at(w.dAA), stream));
-        {
-            ST_REQ((size_t)synth_slabs(&q) * q.B * q.OT * L.KP < ((size_t)1 << 30) && (size_t)q.B * q.T * L.KP < ((size_t)1 << 30),
-                   "st_fit_knobs: batch too large for the kernel's 32-bit element offsets (B=%d)", q.B);
-            const stg::RowMap live = synth_live(&q);
-            const int groups = ae_fwd_groups(&q), kgrid = ae_knob_grid(&q);
-            ST_TRY(with_ht(ae_ht(q.prec), [&](auto HT) {
-                return launch_lds("ae_knob_bwd_kernel", sta::ae_knob_bwd_kernel<AE_KNOB_NW, HT()>, dim3(kgrid, 2), dim3(AE_KNOB_NW * 64),
-                                  (size_t)sta::ae_knob_lds_floats(AE_KNOB_NW) * sizeof(float), st_stream(stream),
-                                  w.mag, kn, ae_m, ae_p, L.go, w.mag_hat, w.phs_hat, w.dAA, w.aews, fit->kg, q.B, q.T, q.OT, q.F, q.K, L.KP,
-                                  live.t_lo, live.t_lo + live.Tv - 1, synth_slabs(&q), (size_t)q.B * q.OT * L.KP); }));
-            ST_LAUNCHED("ae_knob_bwd");
-            const size_t w5 = (size_t)L.offs[4] + (size_t)L.go.w[4];
-            hipLaunchKernelGGL(knob_grad_kernel, dim3(q.B), dim3(64), 0, st_stream(stream), params + w5, (const float*)fit->kg, params + w5 + L.PG,
-                               (const float*)fit->kg + (size_t)groups * 16, q.K, fit->rows, L.KP / 32);
-            ST_LAUNCHED("knob_grad");
-            stf::TailArgs t = fit->hyper;
-            t.loss_p = w.loss_p; t.n_lp = q.B * nslot; t.loss = fit->loss;
-            t.rows = fit->rows; t.nb = q.B; t.K = q.K; t.acc = fit->acc;
-            t.per_window = knob_rows != 1; t.first = w0 == 0; t.last = w0 + q.B >= nwin;
-            const size_t ro = t.per_window ? (size_t)w0 * q.K : 0;
-            t.knobs = fit->knobs + ro; t.m = fit->m + ro; t.v = fit->v + ro; t.grad = fit->grad ? fit->grad + ro : nullptr;
-            hipLaunchKernelGGL(stf::fit_tail_kernel, dim3(1), dim3(256), 0, st_stream(stream), t);
-            ST_LAUNCHED("fit_tail");
+        for (int s = 0; s < nset; ++s) {
+            if (dec) {      // the decoder forward from the code: no stage kernel, no analysis GEMM, no encoder (st_decode.h)
+                ST_REQ((size_t)q.B * CW < ((size_t)1 << 30) && (size_t)q.B * q.T * q.F < ((size_t)1 << 30) && (size_t)q.B * q.OT * L.KP < ((size_t)1 << 30) &&
+                       (size_t)q.B * q.T < ((size_t)1 << 24),      // the last: the 24-bit products b * T and b * OT of the row offsets
+                       "st_decode_long / st_fit_knobs_coded: batch too large for the kernel's 32-bit element offsets (B=%d)", q.B);
+                const bool one = knob_rows == 1;
+                const float* ks = q.K == 0 ? params : knobs + (size_t)s * cj->set_stride + (one ? 0 : (size_t)w0 * q.K);
+                ST_TRY(with_ht(ae_ht(q.prec), [&](auto HT) {
+                    return launch_lds("ae_dec_fwd_kernel", sta::ae_dec_fwd_kernel<sta::AE_DEC_NW, HT()>, dim3(ae_dec_grid(&q)), dim3(sta::AE_DEC_NW * 64),
+                                      (size_t)sta::ae_dec_lds_floats() * sizeof(float), st_stream(stream),
+                                      cj->code + (size_t)w0 * CW, ks, (one || q.K == 0) ? 0 : q.K, ae_m, ae_p, L.go,
+                                      fit ? w.mag_hat : nullptr, fit ? w.phs_hat : nullptr, w.AA, g16 ? w.AA16 : nullptr, g16 ? gemm_ht(q.prec) : 0,
+                                      fit ? w.aews : nullptr, fit ? w.mag : nullptr, fit ? p.knobs : nullptr, q.B, q.T, q.OT, q.F, q.K, L.KP); }));
+                ST_LAUNCHED("ae_dec_fwd");
+            } else {
+                ST_TRY(ae_fwd_body(&q, L, w.mag, w.phs, kn, ae_m, ae_p, w.mag_hat, w.phs_hat, w.AA, w.reg_p, fit ? w.aews : nullptr, stream, g16 ? w.AA16 : nullptr, false, nullptr,
+                                   img ? p.img : nullptr));      // fit: the code h4 stays at the head of the autoencoder workspace
+            }
+            ST_TRY(stft_gemm(step_stft_plan(&q, w, GEMM_FRAMES), slabs_at(w.frs), stream));
+            const int ns = frame_slabs(&q);
+            const dim3 grid((q.y / 4 + 255) / 256, q.B);
+            const size_t slab = (size_t)q.B * q.OT * q.N;
+            const bool three = (q.N + q.H - 1) / q.H <= 3;      // the rule of ola_loss_impl for the four-sample form with all loads up front
+            if (!fit) {
+                with_bool(three, [&](auto NF3) { with_slabs(ns, [&](auto NS) {
+                    hipLaunchKernelGGL((stp::predict_ola_kernel<T, NS(), NF3() ? 3 : 0>), grid, dim3(256), 0, st_stream(stream),
+                                       w.frs, slab, signal, dec ? out + (size_t)s * cj->out_pitch : out, a.s0, n_out, q.L, q.N, q.H, q.OT, q.y); }); });
+                ST_LAUNCHED("predict_ola");
+                continue;
+            }
+            const int nslot = (q.y + 255) / 256;
+            with_bool(three, [&](auto NF3) { with_slabs(ns, [&](auto NS) {
+                hipLaunchKernelGGL((stf::fit_ola_kernel<T, NS(), NF3() ? 3 : 0>), grid, dim3(256), 0, st_stream(stream),
+                                   w.frs, slab, signal, reinterpret_cast<const T*>(fit->target), w.dsyn, g16 ? w.dsyn16 : nullptr, g16 ? gemm_ht(q.prec) : 0, w.loss_p, nslot,
+                                   a.s0, n_out, q.L, q.N, q.H, q.OT, q.y); }); });
+            ST_LAUNCHED("fit_ola");
+            ST_TRY(stft_gemm(step_stft_plan(&q, w, GEMM_DGRAD), slabs_at(w.dAA), stream));
+            {
+                ST_REQ((size_t)synth_slabs(&q) * q.B * q.OT * L.KP < ((size_t)1 << 30) && (size_t)q.B * q.T * L.KP < ((size_t)1 << 30),
+                       "st_fit_knobs: batch too large for the kernel's 32-bit element offsets (B=%d)", q.B);
+                const stg::RowMap live = synth_live(&q);
+                const int groups = ae_fwd_groups(&q), kgrid = ae_knob_grid(&q);
+                ST_TRY(with_ht(ae_ht(q.prec), [&](auto HT) {
+                    return launch_lds("ae_knob_bwd_kernel", sta::ae_knob_bwd_kernel<AE_KNOB_NW, HT()>, dim3(kgrid, 2), dim3(AE_KNOB_NW * 64),
+                                      (size_t)sta::ae_knob_lds_floats(AE_KNOB_NW) * sizeof(float), st_stream(stream),
+                                      w.mag, kn, ae_m, ae_p, L.go, w.mag_hat, w.phs_hat, w.dAA, w.aews, fit->kg, q.B, q.T, q.OT, q.F, q.K, L.KP,
+                                      live.t_lo, live.t_lo + live.Tv - 1, synth_slabs(&q), (size_t)q.B * q.OT * L.KP); }));
+                ST_LAUNCHED("ae_knob_bwd");
+                const size_t w5 = (size_t)L.offs[4] + (size_t)L.go.w[4];
+                hipLaunchKernelGGL(knob_grad_kernel, dim3(q.B), dim3(64), 0, st_stream(stream), params + w5, (const float*)fit->kg, params + w5 + L.PG,
+                                   (const float*)fit->kg + (size_t)groups * 16, q.K, fit->rows, L.KP / 32);
+                ST_LAUNCHED("knob_grad");
+                stf::TailArgs t = fit->hyper;
+                t.loss_p = w.loss_p; t.n_lp = q.B * nslot; t.loss = fit->loss;
+                t.rows = fit->rows; t.nb = q.B; t.K = q.K; t.acc = fit->acc;
+                t.per_window = knob_rows != 1; t.first = w0 == 0; t.last = w0 + q.B >= nwin;
+                const size_t ro = t.per_window ? (size_t)w0 * q.K : 0;
+                t.knobs = fit->knobs + ro; t.m = fit->m + ro; t.v = fit->v + ro; t.grad = fit->grad ? fit->grad + ro : nullptr;
+                hipLaunchKernelGGL(stf::fit_tail_kernel, dim3(1), dim3(256), 0, st_stream(stream), t);
+                ST_LAUNCHED("fit_tail");
+            }
         }
     }
     return ST_OK;
@@ -2098,38 +2139,40 @@ extern "C" size_t st_fit_knobs_ws_bytes(const st_dims* d)
     FitWS f; fit_carve(d, nullptr, &f);
     return pb + f.bytes;
 }
-extern "C" int st_fit_knobs(const st_dims* d, const float* params, int fmt, const void* signal, const void* target, long long n,
-                            float* knobs, long long knob_rows, float* adam_m, float* adam_v,
-                            long long first_step, int steps, float lr, float beta1, float beta2, float eps,
-                            double* loss_hist, float* grad_hist, void* ws, void* stream)
+static int fit_knobs_impl(const char* name, const bool coded, const st_dims* d, const float* params, const float* code, int fmt, const void* signal, const void* target, long long n,
+                          float* knobs, long long knob_rows, float* adam_m, float* adam_v,
+                          long long first_step, int steps, float lr, float beta1, float beta2, float eps,
+                          double* loss_hist, float* grad_hist, void* ws, void* stream)
 {
     Layout L;
     if (make_layout(d, &L) != ST_OK) {      // the dims rule that failed, under this entry's name
         char rule[400]; snprintf(rule, sizeof(rule), "%s", st_last_error());
-        return st_fail(ST_ERR_ARG, "st_fit_knobs: %s", rule);
+        return st_fail(ST_ERR_ARG, "%s: %s", name, rule);
     }
-    ST_REQ(d->K >= 1, "st_fit_knobs: K = %d (a model without knobs has no knobs to fit)", d->K);
-    ST_REQ(params, "st_fit_knobs: null pointer (params)"); ST_REQ(signal, "st_fit_knobs: null pointer (signal)"); ST_REQ(target, "st_fit_knobs: null pointer (target)");
-    ST_REQ(knobs, "st_fit_knobs: null pointer (knobs)"); ST_REQ(adam_m, "st_fit_knobs: null pointer (adam_m)"); ST_REQ(adam_v, "st_fit_knobs: null pointer (adam_v)");
-    ST_REQ(loss_hist, "st_fit_knobs: null pointer (loss_hist)"); ST_REQ(ws, "st_fit_knobs: null pointer (ws)");
-    ST_REQ(n > 0, "st_fit_knobs: n must be positive (n = %lld)", n);
-    ST_REQ(fmt == ST_PCM_F32 || fmt == ST_PCM_S16, "st_fit_knobs: fmt = %d is neither ST_PCM_F32 nor ST_PCM_S16", fmt);
+    ST_REQ(d->K >= 1, "%s: K = %d (a model without knobs has no knobs to fit)", name, d->K);
+    ST_REQ(params, "%s: null pointer (params)", name); ST_REQ(signal, "%s: null pointer (signal)", name); ST_REQ(target, "%s: null pointer (target)", name);
+    ST_REQ(knobs, "%s: null pointer (knobs)", name); ST_REQ(adam_m, "%s: null pointer (adam_m)", name); ST_REQ(adam_v, "%s: null pointer (adam_v)", name);
+    ST_REQ(loss_hist, "%s: null pointer (loss_hist)", name); ST_REQ(ws, "%s: null pointer (ws)", name);
+    ST_REQ(code || !coded, "%s: null pointer (code)", name);
+    ST_REQ(n > 0, "%s: n must be positive (n = %lld)", name, n);
+    ST_REQ(fmt == ST_PCM_F32 || fmt == ST_PCM_S16, "%s: fmt = %d is neither ST_PCM_F32 nor ST_PCM_S16", name, fmt);
     const long long nwin = predict_windows(d, n);
-    ST_REQ(knob_rows == 1 || knob_rows == nwin, "st_fit_knobs: knob_rows = %lld must be 1 or the window count (%lld windows for n = %lld)", knob_rows, nwin, n);
-    ST_REQ(steps >= 1, "st_fit_knobs: steps = %d must be at least 1", steps);
-    ST_REQ(first_step >= 1, "st_fit_knobs: first_step = %lld must be at least 1 (Adam's step number is 1-based)", first_step);
-    ST_REQ(std::isfinite(lr) && lr >= 0.f, "st_fit_knobs: lr = %g must be finite and not negative", (double)lr);
-    ST_REQ(std::isfinite(beta1) && beta1 >= 0.f && beta1 < 1.f, "st_fit_knobs: beta1 = %g must lie in [0, 1)", (double)beta1);
-    ST_REQ(std::isfinite(beta2) && beta2 >= 0.f && beta2 < 1.f, "st_fit_knobs: beta2 = %g must lie in [0, 1)", (double)beta2);
-    ST_REQ(std::isfinite(eps) && eps > 0.f, "st_fit_knobs: eps = %g must be finite and positive", (double)eps);
+    ST_REQ(knob_rows == 1 || knob_rows == nwin, "%s: knob_rows = %lld must be 1 or the window count (%lld windows for n = %lld)", name, knob_rows, nwin, n);
+    ST_REQ(steps >= 1, "%s: steps = %d must be at least 1", name, steps);
+    ST_REQ(first_step >= 1, "%s: first_step = %lld must be at least 1 (Adam's step number is 1-based)", name, first_step);
+    ST_REQ(std::isfinite(lr) && lr >= 0.f, "%s: lr = %g must be finite and not negative", name, (double)lr);
+    ST_REQ(std::isfinite(beta1) && beta1 >= 0.f && beta1 < 1.f, "%s: beta1 = %g must lie in [0, 1)", name, (double)beta1);
+    ST_REQ(std::isfinite(beta2) && beta2 >= 0.f && beta2 < 1.f, "%s: beta2 = %g must lie in [0, 1)", name, (double)beta2);
+    ST_REQ(std::isfinite(eps) && eps > 0.f, "%s: eps = %g must be finite and positive", name, (double)eps);
     const uintptr_t sa = fmt == ST_PCM_S16 ? 7 : 15;
-    ST_REQ((reinterpret_cast<uintptr_t>(signal) & sa) == 0, "st_fit_knobs: signal must be %d-byte aligned", (int)sa + 1);
-    ST_REQ((reinterpret_cast<uintptr_t>(target) & sa) == 0, "st_fit_knobs: target must be %d-byte aligned", (int)sa + 1);
-    ST_REQ((reinterpret_cast<uintptr_t>(knobs) & 15) == 0, "st_fit_knobs: knobs must be 16-byte aligned");
-    ST_REQ((reinterpret_cast<uintptr_t>(adam_m) & 15) == 0, "st_fit_knobs: adam_m must be 16-byte aligned");
-    ST_REQ((reinterpret_cast<uintptr_t>(adam_v) & 15) == 0, "st_fit_knobs: adam_v must be 16-byte aligned");
-    ST_REQ((reinterpret_cast<uintptr_t>(ws) & 15) == 0, "st_fit_knobs: ws must be 16-byte aligned");
-    ST_REQ(!ae_is_wide(d), "st_fit_knobs: not supported for the wide autoencoder geometries (T = %d > 32 or OT = %d > 16): st_fit_knobs_supported", d->T, d->OT);
+    ST_REQ((reinterpret_cast<uintptr_t>(signal) & sa) == 0, "%s: signal must be %d-byte aligned", name, (int)sa + 1);
+    ST_REQ((reinterpret_cast<uintptr_t>(target) & sa) == 0, "%s: target must be %d-byte aligned", name, (int)sa + 1);
+    ST_REQ((reinterpret_cast<uintptr_t>(knobs) & 15) == 0, "%s: knobs must be 16-byte aligned", name);
+    ST_REQ((reinterpret_cast<uintptr_t>(adam_m) & 15) == 0, "%s: adam_m must be 16-byte aligned", name);
+    ST_REQ((reinterpret_cast<uintptr_t>(adam_v) & 15) == 0, "%s: adam_v must be 16-byte aligned", name);
+    ST_REQ((reinterpret_cast<uintptr_t>(ws) & 15) == 0, "%s: ws must be 16-byte aligned", name);
+    ST_REQ((reinterpret_cast<uintptr_t>(code) & 15) == 0, "%s: code must be 16-byte aligned", name);
+    ST_REQ(!ae_is_wide(d), "%s: not supported for the wide autoencoder geometries (T = %d > 32 or OT = %d > 16): st_fit_knobs_supported", name, d->T, d->OT);
     const long long n_out = n - ((long long)d->L - d->y);
     if (n_out <= 0) return ST_OK;      // no output sample, no objective: nothing launched, every buffer left alone
     PredictWS p; predict_carve(d, ws, &p);
@@ -2148,10 +2191,91 @@ extern "C" int st_fit_knobs(const st_dims* d, const float* params, int fmt, cons
         job.hyper.inv_n_d = 1.0 / (double)n_out; job.hyper.inv_n = (float)(1.0 / (double)n_out);
         job.hyper.neg_step = (float)(-(double)lr / bc1); job.hyper.bc2_sqrt = (float)sqrt(bc2);
         job.hyper.w1 = (float)(1.0 - (double)beta1); job.hyper.b2 = beta2; job.hyper.w2 = (float)(1.0 - (double)beta2); job.hyper.eps = eps;
-        ST_TRY(fmt == ST_PCM_S16 ? predict_batches(d, L, p, params, reinterpret_cast<const short*>(signal), n, knobs, knob_rows, nullptr, n_out, ws, stream, &job, batch_off)
-                                 : predict_batches(d, L, p, params, reinterpret_cast<const float*>(signal), n, knobs, knob_rows, nullptr, n_out, ws, stream, &job, batch_off));
+        const CodeJob cj{nullptr, code, 1, 0, 0};
+        const CodeJob* const cjp = coded ? &cj : nullptr;
+        ST_TRY(fmt == ST_PCM_S16 ? predict_batches(d, L, p, params, reinterpret_cast<const short*>(signal), n, knobs, knob_rows, nullptr, n_out, ws, stream, &job, batch_off, cjp)
+                                 : predict_batches(d, L, p, params, reinterpret_cast<const float*>(signal), n, knobs, knob_rows, nullptr, n_out, ws, stream, &job, batch_off, cjp));
     }
     return ST_OK;
+}
+extern "C" int st_fit_knobs(const st_dims* d, const float* params, int fmt, const void* signal, const void* target, long long n,
+                            float* knobs, long long knob_rows, float* adam_m, float* adam_v,
+                            long long first_step, int steps, float lr, float beta1, float beta2, float eps,
+                            double* loss_hist, float* grad_hist, void* ws, void* stream)
+{
+    return fit_knobs_impl("st_fit_knobs", false, d, params, nullptr, fmt, signal, target, n, knobs, knob_rows, adam_m, adam_v, first_step, steps, lr, beta1, beta2, eps,
+                          loss_hist, grad_hist, ws, stream);
+}
+// st_fit_knobs from the code of the recording (st_encode_long): every step's forward is the decoder forward; everything behind the frames GEMM is st_fit_knobs'.
+extern "C" int st_fit_knobs_coded(const st_dims* d, const float* params, const void* code, int fmt, const void* signal, const void* target, long long n,
+                                  float* knobs, long long knob_rows, float* adam_m, float* adam_v,
+                                  long long first_step, int steps, float lr, float beta1, float beta2, float eps,
+                                  double* loss_hist, float* grad_hist, void* ws, void* stream)
+{
+    return fit_knobs_impl("st_fit_knobs_coded", true, d, params, reinterpret_cast<const float*>(code), fmt, signal, target, n, knobs, knob_rows, adam_m, adam_v,
+                          first_step, steps, lr, beta1, beta2, eps, loss_hist, grad_hist, ws, stream);
+}
+
+// ------------------------------------------------------------------------------ encode once, decode at any knob setting (st_decode.h)
+// Every ae_dec_fwd_kernel instantiation passes the ISA scan (tools/check_mfma_hazards.py), so every arithmetic level of the fused geometries is served.
+static bool decode_ok(const st_dims* d) { return predict_ok(d); }
+extern "C" int st_decode_supported(const st_dims* d) { return decode_ok(d) ? 1 : 0; }
+extern "C" size_t st_decode_ws_bytes(const st_dims* d) { return decode_ok(d) ? st_predict_ws_bytes(d) : 0; }
+extern "C" size_t st_code_bytes(const st_dims* d, long long n)
+{
+    if (!decode_ok(d) || n <= 0) return 0;
+    return (size_t)predict_windows(d, n) * stc::code_window_floats(st_kp_of(d->F) / 2, d->OT) * sizeof(float);
+}
+// what st_encode_long and st_decode_long ask of the recording and the workspace, under the entry's name
+static int coded_args(const char* name, const st_dims* d, Layout* L, const float* params, const void* code, int fmt, const void* signal, long long n, const void* ws)
+{
+    if (make_layout(d, L) != ST_OK) {
+        char rule[400]; snprintf(rule, sizeof(rule), "%s", st_last_error());
+        return st_fail(ST_ERR_ARG, "%s: %s", name, rule);
+    }
+    ST_REQ(params, "%s: null pointer (params)", name); ST_REQ(code, "%s: null pointer (code)", name); ST_REQ(signal, "%s: null pointer (signal)", name);
+    ST_REQ(ws, "%s: null pointer (ws)", name);
+    ST_REQ(n > 0, "%s: n must be positive (n = %lld)", name, n);
+    ST_REQ(fmt == ST_PCM_F32 || fmt == ST_PCM_S16, "%s: fmt = %d is neither ST_PCM_F32 nor ST_PCM_S16", name, fmt);
+    const uintptr_t sa = fmt == ST_PCM_S16 ? 7 : 15;
+    ST_REQ((reinterpret_cast<uintptr_t>(signal) & sa) == 0, "%s: signal must be %d-byte aligned", name, (int)sa + 1);
+    ST_REQ((reinterpret_cast<uintptr_t>(code) & 15) == 0, "%s: code must be 16-byte aligned", name);
+    ST_REQ((reinterpret_cast<uintptr_t>(ws) & 15) == 0, "%s: ws must be 16-byte aligned", name);
+    ST_REQ(!ae_is_wide(d), "%s: not supported for the wide autoencoder geometries (T = %d > 32 or OT = %d > 16): st_decode_supported", name, d->T, d->OT);
+    return ST_OK;
+}
+extern "C" int st_encode_long(const st_dims* d, const float* params, int fmt, const void* signal, long long n, void* code, void* ws, void* stream)
+{
+    Layout L; ST_TRY(coded_args("st_encode_long", d, &L, params, code, fmt, signal, n, ws));
+    const long long n_out = n - ((long long)d->L - d->y);
+    if (n_out <= 0) return ST_OK;      // as st_predict_long: no output sample, nothing launched
+    PredictWS p; predict_carve(d, ws, &p);
+    prof_mark("begin", stream);
+    ST_TRY(predict_prep(d, L, p, params, stream));
+    const CodeJob cj{reinterpret_cast<float*>(code), nullptr, 1, 0, 0};
+    return fmt == ST_PCM_S16 ? predict_batches(d, L, p, params, reinterpret_cast<const short*>(signal), n, nullptr, 1, nullptr, n_out, ws, stream, nullptr, 0, &cj)
+                             : predict_batches(d, L, p, params, reinterpret_cast<const float*>(signal), n, nullptr, 1, nullptr, n_out, ws, stream, nullptr, 0, &cj);
+}
+extern "C" int st_decode_long(const st_dims* d, const float* params, const void* code, int fmt, const void* signal, long long n,
+                              const float* knobs, long long knob_rows, int n_settings, float* out, long long out_pitch, void* ws, void* stream)
+{
+    Layout L; ST_TRY(coded_args("st_decode_long", d, &L, params, code, fmt, signal, n, ws));
+    ST_REQ(knobs || d->K == 0, "st_decode_long: null pointer (knobs, K = %d)", d->K);
+    ST_REQ(out, "st_decode_long: null pointer (out)");
+    const long long nwin = predict_windows(d, n);
+    ST_REQ(knob_rows == 1 || knob_rows == nwin, "st_decode_long: knob_rows = %lld must be 1 or the window count (%lld windows for n = %lld)", knob_rows, nwin, n);
+    ST_REQ(n_settings >= 1, "st_decode_long: n_settings = %d must be at least 1", n_settings);
+    const long long n_out = n - ((long long)d->L - d->y);
+    ST_REQ(out_pitch >= n_out && out_pitch >= 0 && out_pitch % 4 == 0,
+           "st_decode_long: out_pitch = %lld must be a multiple of 4 and at least the %lld output samples of a setting", out_pitch, n_out > 0 ? n_out : 0);
+    ST_REQ((reinterpret_cast<uintptr_t>(out) & 15) == 0, "st_decode_long: out must be 16-byte aligned");
+    if (n_out <= 0) return ST_OK;
+    PredictWS p; predict_carve(d, ws, &p);
+    prof_mark("begin", stream);
+    ST_TRY(predict_prep(d, L, p, params, stream));      // the parameter-only head (folded synthesis bases, their 16-bit / plane copies), once per call
+    const CodeJob cj{nullptr, reinterpret_cast<const float*>(code), n_settings, out_pitch, (size_t)knob_rows * d->K};
+    return fmt == ST_PCM_S16 ? predict_batches(d, L, p, params, reinterpret_cast<const short*>(signal), n, knobs, knob_rows, out, n_out, ws, stream, nullptr, 0, &cj)
+                             : predict_batches(d, L, p, params, reinterpret_cast<const float*>(signal), n, knobs, knob_rows, out, n_out, ws, stream, nullptr, 0, &cj);
 }
 
 // Data-parallel split of st_loss_backward: after phase 1 the synthesis + autoencoder gradients

@@ -70,6 +70,15 @@ class _OptimizerView:
         return self.engine.optimizer_state_dict()
 
 
+class RecordingCode:
+    """What StepEngine.encode_long() leaves of a recording: the code tensor (opaque, layout in csrc/st_decode.h), the signal tensor it was built from (the
+    overlap-add reads its residual), its length n, the window count, and the geometry and compute dtype it is valid for."""
+    __slots__ = ("code", "signal", "n", "nwin", "geometry", "compute_dtype")
+
+    def __init__(self, code, signal, n, nwin, geometry, compute_dtype):
+        self.code, self.signal, self.n, self.nwin, self.geometry, self.compute_dtype = code, signal, int(n), int(nwin), tuple(geometry), compute_dtype
+
+
 def workspace_bytes_upto(lib, dims, max_batch):
     """Bytes of ONE workspace that serves every batch of 1 .. max_batch windows at every arithmetic level and clip scope: st_workspace_bytes_max (the exact
     st_workspace_bytes is a function of all three and is monotonic in none of them: INTEGRATION.md "Sizing the workspace")."""
@@ -522,6 +531,113 @@ class StepEngine:
                        C.c_void_p(signal.data_ptr()), n, _lib.ptr(kn), rows, C.c_void_p(out.data_ptr()), _lib.ptr(self._predict_ws), self._stream())
         return out[:n_out]
 
+    # ---------------------------------------------------------------- encode once, decode at any knob setting
+    def decode_supported(self):
+        """Whether encode_long() / decode_long() run this geometry at this compute dtype (st_decode_supported; host arithmetic only)."""
+        d = self.dims.with_batch(1)
+        d.prec = _lib.PREC[self.compute_dtype]
+        return bool(self.lib.st_decode_supported(C.byref(d)))
+
+    def _coded_dims(self, what, batch):
+        B = int(batch or self.max_batch)
+        if B < 1:
+            raise ValueError(f"{what}: batch = {B}")
+        d = self.dims.with_batch(B)
+        d.prec, d.loss_scale, d.clip_all = _lib.PREC[self.compute_dtype], self.loss_scale, int(self.clip_all)
+        return d
+
+    def _coded_ws(self, what, d):
+        """The workspace of encode_long / decode_long: one of their own (st_decode_ws_bytes, allocated on first use), not predict_long's."""
+        sizes = self.__dict__.setdefault("_decode_sizes", {})
+        if (d.B, self.compute_dtype) not in sizes:
+            sizes[(d.B, self.compute_dtype)] = int(self.lib.st_decode_ws_bytes(C.byref(d)))
+        need = sizes[(d.B, self.compute_dtype)]
+        if need <= 0:
+            raise RuntimeError(f"{what}: st_decode_supported refuses this geometry (T={d.T}, OT={d.OT}): the wide autoencoder geometries stay on predict_long's batched route")
+        if getattr(self, "_decode_ws", None) is None or self._decode_ws.numel() < need:
+            self._decode_ws = torch.zeros(need, dtype=torch.uint8, device=self.device)
+        return self._decode_ws
+
+    def _geometry_key(self):
+        return tuple(getattr(self.dims, k) for k in ("L", "N", "H", "T", "OT", "F", "K", "y"))
+
+    def encode_long(self, signal, batch=None):
+        """The knob-independent half of the model over a whole recording, once (st_encode_long in include/signaltrain_hip.h): window staging, the analysis GEMM, the
+        polar form and encoder layers 1..4 of both autoencoders.  signal as predict_long takes it.  Returns a RecordingCode for decode_long() and
+        fit_knobs(code=...); it is valid for this geometry, this compute dtype, this recording and the parameters as they are now -- that the parameters have not
+        changed since the encode is the caller's precondition.  No host sync; self.ws is not written."""
+        if not (torch.is_tensor(signal) and signal.dim() == 1 and signal.device == self.device and signal.dtype in (torch.float32, torch.int16)):
+            raise ValueError(f"encode_long: signal must be a 1-D float32 or int16 tensor on {self.device}")
+        signal = signal.contiguous()
+        if signal.data_ptr() % 16:
+            signal = signal.clone()
+        d = self._coded_dims("encode_long", batch)
+        ws = self._coded_ws("encode_long", d)
+        n = int(signal.numel())
+        nwin = int(self.lib.st_predict_windows(C.byref(d), n))
+        nbytes = int(self.lib.st_code_bytes(C.byref(d), n))
+        code = torch.empty(max(nbytes, 16) // 4, dtype=torch.float32, device=self.device)
+        if n > 0:
+            self._call("st_encode_long", C.byref(d), _lib.ptr(self.params), _lib.PCM_S16 if signal.dtype == torch.int16 else _lib.PCM_F32,
+                       C.c_void_p(signal.data_ptr()), n, _lib.ptr(code), _lib.ptr(ws), self._stream())
+        return RecordingCode(code, signal, n, nwin, self._geometry_key(), self.compute_dtype)
+
+    def _check_code(self, what, code):
+        """A RecordingCode this engine can read: its geometry, compute dtype and device, the signal it holds as long as it says, the code as large as
+        st_code_bytes asks for that length (a hand-built or truncated one must not reach the kernels)."""
+        if not isinstance(code, RecordingCode):
+            raise ValueError(f"{what}: code must be the RecordingCode encode_long() returned")
+        if code.geometry != self._geometry_key():
+            raise ValueError(f"{what}: the RecordingCode was built for another geometry ({code.geometry}, this engine has {self._geometry_key()})")
+        if code.compute_dtype != self.compute_dtype:
+            raise ValueError(f"{what}: the RecordingCode was built at compute dtype {code.compute_dtype!r}, this engine runs {self.compute_dtype!r}")
+        if code.code.device != self.device or code.signal.device != self.device:
+            raise ValueError(f"{what}: the RecordingCode lives on {code.code.device}, this engine on {self.device}")
+        if int(code.signal.numel()) != code.n:
+            raise ValueError(f"{what}: the RecordingCode was built from {code.n} samples, the signal it holds has {int(code.signal.numel())}")
+        d = self.dims.with_batch(1)
+        d.prec = _lib.PREC[self.compute_dtype]
+        need = int(self.lib.st_code_bytes(C.byref(d), code.n))
+        if code.code.dtype != torch.float32 or not code.code.is_contiguous() or int(code.code.numel()) * 4 != max(need, 16) or code.nwin != int(self.lib.st_predict_windows(C.byref(d), code.n)):
+            raise ValueError(f"{what}: the RecordingCode holds {int(code.code.numel()) * 4} bytes in {code.nwin} windows; {code.n} samples need {need} bytes (st_code_bytes)")
+
+    def decode_long(self, code, knobs, out=None, batch=None):
+        """The recording behind `code` (encode_long) at one or several knob settings in ONE C call (st_decode_long): per setting only layers 5..9, the polar
+        epilogue, the frames GEMM and the overlap-add run.  knobs: [K] (one setting; returns [n_out]), [S, K] (S settings) or [S, nwin, K] (S settings of one row
+        per window); returns [S, n_out], row s what predict_long gives at setting s up to the order of a few sums.  out: a float32 device tensor [S, pitch] with
+        pitch >= n_out, pitch % 4 == 0, 16-byte aligned rows, to write into.  batch need not be the batch of the encode.  No host sync; self.ws is not written."""
+        self._check_code("decode_long", code)
+        d = self._coded_dims("decode_long", batch)
+        ws = self._coded_ws("decode_long", d)
+        n, nwin = code.n, code.nwin
+        n_out = int(self.lib.st_predict_out_samples(C.byref(d), n))
+        single = False
+        if d.K:
+            kn = torch.as_tensor(knobs).to(device=self.device, dtype=torch.float32)
+            single = kn.dim() == 1
+            if kn.dim() == 3:
+                if int(kn.shape[1]) not in (1, nwin) or int(kn.shape[2]) != d.K:
+                    raise ValueError(f"decode_long: knobs [S, rows, K] has {int(kn.shape[1])} rows per setting: one row, or one per window ({nwin} windows for {n} samples)")
+            else:
+                kn = kn.reshape(-1, 1, d.K)
+            kn = kn.contiguous()
+            S, rows = int(kn.shape[0]), int(kn.shape[1])
+        else:
+            kn, S, rows = None, 1, 1
+        if S < 1:
+            raise ValueError("decode_long: no knob setting")
+        pitch = (n_out + 3) // 4 * 4
+        if out is None:
+            out = torch.empty(S, pitch, dtype=torch.float32, device=self.device)
+        elif not (out.dtype == torch.float32 and out.device == self.device and out.dim() == 2 and int(out.shape[0]) >= S and out.stride(1) == 1 and
+                  out.stride(0) >= n_out and out.stride(0) % 4 == 0 and int(out.shape[1]) >= min(n_out, out.stride(0)) and out.data_ptr() % 16 == 0):
+            raise ValueError(f"decode_long: out must be a 16-byte aligned float32 tensor [S >= {S}, >= {n_out}] on {self.device} with a row pitch that is a multiple of 4")
+        if n_out > 0:
+            self._call("st_decode_long", C.byref(d), _lib.ptr(self.params), _lib.ptr(code.code), _lib.PCM_S16 if code.signal.dtype == torch.int16 else _lib.PCM_F32,
+                       C.c_void_p(code.signal.data_ptr()), n, _lib.ptr(kn), rows, S, C.c_void_p(out.data_ptr()), int(out.stride(0)), _lib.ptr(ws), self._stream())
+        y = out[:S, :n_out]
+        return y[0] if single else y
+
     # ---------------------------------------------------------------- knob fit on the device
     def fit_knobs_supported(self):
         """Whether fit_knobs() runs this geometry (st_fit_knobs_supported: predict_supported() and at least one knob; host arithmetic only)."""
@@ -536,7 +652,14 @@ class StepEngine:
         knobs: [K] (one setting) or [nwin, K] (one row per window), the start values -- cloned; batch: windows per internal batch (default max_batch);
         state: (m, v, first_step) as a previous call returned it, so that calls chain (default: zeros and step 1).
         Returns (knobs, loss_hist [steps] float64, grad_hist [steps, rows, K] or None, (m, v, next_step)), all on the device.  No host sync.  The engine keeps
-        a workspace of its own for this (st_fit_knobs_ws_bytes, allocated on first use): self.ws and predict_long's workspace are not written."""
+        a workspace of its own for this (st_fit_knobs_ws_bytes, allocated on first use): self.ws and predict_long's workspace are not written.
+        signal may also be the RecordingCode encode_long() returned for the recording (st_fit_knobs_coded): every step's forward then starts at layer 5 from
+        the code -- no staging, no analysis GEMM, no encoder.  The parameters must not have changed since the encode."""
+        code = None
+        if isinstance(signal, RecordingCode):
+            code = signal
+            self._check_code("fit_knobs", code)
+            signal = code.signal
         for name, t in (("signal", signal), ("target", target)):
             if not (torch.is_tensor(t) and t.dim() == 1 and t.device == self.device and t.dtype in (torch.float32, torch.int16)):
                 raise ValueError(f"fit_knobs: {name} must be a 1-D float32 or int16 tensor on {self.device}")
@@ -581,7 +704,8 @@ class StepEngine:
             self._fit_ws = torch.zeros(need, dtype=torch.uint8, device=self.device)
         loss_hist = torch.zeros(max(steps, 0), dtype=torch.float64, device=self.device)
         grad_hist = torch.zeros(max(steps, 0), rows, d.K, dtype=torch.float32, device=self.device) if want_grads else None
-        self._call("st_fit_knobs", C.byref(d), _lib.ptr(self.params), _lib.PCM_S16 if signal.dtype == torch.int16 else _lib.PCM_F32,
+        head = ("st_fit_knobs", C.byref(d), _lib.ptr(self.params)) if code is None else ("st_fit_knobs_coded", C.byref(d), _lib.ptr(self.params), _lib.ptr(code.code))
+        self._call(*head, _lib.PCM_S16 if signal.dtype == torch.int16 else _lib.PCM_F32,
                    C.c_void_p(signal.data_ptr()), C.c_void_p(target.data_ptr()), n, _lib.ptr(kn), rows, _lib.ptr(m), _lib.ptr(v),
                    first, steps, float(lr), float(betas[0]), float(betas[1]), float(eps),
                    C.c_void_p(loss_hist.data_ptr()), _lib.ptr(grad_hist), _lib.ptr(self._fit_ws), self._stream())

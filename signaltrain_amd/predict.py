@@ -10,7 +10,10 @@ Same arguments, same return value: a 1-D float32 numpy array of len(signal) - (c
 
 route="device" runs the same prediction as ONE C call (st_predict_long, StepEngine.predict_long): the signal is uploaded as it is -- no padded copy, no
 window or knob copies -- every batch is enqueued by that call, the forward is the one validation takes at the model's compute dtype, and knobs_nn may carry one
-row per window.  route="batched" (the default) is the path described above."""
+row per window.  route="batched" (the default) is the path described above.
+
+predict_sweep renders one recording at several knob settings: the half of the forward in front of the knobs runs once (StepEngine.encode_long), the rest once per
+setting (StepEngine.decode_long); fit_knobs(route="device", encode_once=True) fits from the same code."""
 import warnings
 
 import numpy as np
@@ -20,6 +23,7 @@ ROUTES = ("batched", "device")
 FIT_ROUTES = ("batched", "device")
 _warned_unsupported = False
 _warned_fit_unsupported = False
+_warned_sweep_unsupported = False
 
 
 
@@ -94,6 +98,20 @@ def predict_long(signal, knobs_nn, model, chunk_size, out_chunk_size, sr=44100, 
     return out[0:-num_extra] if num_extra > 0 else out
 
 
+def _resident(signal, device, compand):
+    """The recording on the device for the one-call routes: a tensor stays what it is (16-bit PCM included), a host array goes up as float32."""
+    if torch.is_tensor(signal) and not compand:
+        sig = signal.detach().to(device)
+        return sig if sig.dtype == torch.int16 else sig.float()
+    host = signal.detach().cpu().numpy() if torch.is_tensor(signal) else signal
+    host = np.ascontiguousarray(host, dtype=np.float32)
+    if compand:                                                        # a host map before the upload, as on the batched route
+        from . import audio
+        print("Companding input")
+        host = np.ascontiguousarray(audio.mu_compand(host), dtype=np.float32)
+    return torch.from_numpy(host).to(device)
+
+
 def _predict_device(signal, knobs_nn, model, chunk_size, out_chunk_size, device, compand, batch_size, verbose):
     """route="device" of predict_long; None where the library does not run this geometry that way (the caller then takes the batched route)."""
     global _warned_unsupported
@@ -109,18 +127,7 @@ def _predict_device(signal, knobs_nn, model, chunk_size, out_chunk_size, device,
             warnings.warn(f"signaltrain_amd.predict_long: route='device' does not run this geometry (T={eng.dims.T}, OT={eng.dims.OT}: st_predict_supported); "
                           "taking the batched route", RuntimeWarning, stacklevel=3)
         return None
-    if torch.is_tensor(signal) and not compand:
-        sig = signal.detach().to(device)
-        if sig.dtype != torch.int16:
-            sig = sig.float()
-    else:
-        host = signal.detach().cpu().numpy() if torch.is_tensor(signal) else signal
-        host = np.ascontiguousarray(host, dtype=np.float32)
-        if compand:                                                    # a host map before the upload, as on the batched route
-            from . import audio
-            print("Companding input")
-            host = np.ascontiguousarray(audio.mu_compand(host), dtype=np.float32)
-        sig = torch.from_numpy(host).to(device)
+    sig = _resident(signal, device, compand)
     if verbose:
         print("predict_long (device route): chunk_size, out_chunk_size, windows = ", chunk_size, out_chunk_size, nwin)
     kn = torch.as_tensor(np.asarray(knobs_nn, dtype=np.float32), device=device)
@@ -129,8 +136,44 @@ def _predict_device(signal, knobs_nn, model, chunk_size, out_chunk_size, device,
     return y.cpu().numpy()
 
 
+def predict_sweep(signal, knob_settings, model, chunk_size, out_chunk_size, sr=44100, effect=None, device=None, compand=False,
+                  batch_size=200, verbose=False, route="device"):
+    """predict_long at S knob settings: knob_settings is [S, K], or [S, nwin, K] for one row per window.  Returns [S, len(signal) - (chunk_size -
+    out_chunk_size)] float32.  route="device" encodes the recording ONCE (StepEngine.encode_long: everything in front of the knobs, layer 5 of 9) and decodes it
+    at the S settings in one call (StepEngine.decode_long); on a geometry st_decode_supported rejects it warns once and loops over predict_long's batched route,
+    which route="batched" does outright.  The parameters must not change between the encode and the decode (they cannot inside this call)."""
+    global _warned_sweep_unsupported
+    if route not in ROUTES:
+        raise ValueError(f"predict_sweep: route must be one of {ROUTES}, not {route!r}")
+    kn = np.asarray(knob_settings, dtype=np.float32)
+    if kn.ndim not in (2, 3):
+        raise ValueError(f"predict_sweep: knob_settings must be [S, K] or [S, nwin, K], not {kn.shape}")
+    device = torch.device(device) if device is not None else next(model.parameters()).device
+    if route == "device":
+        n = int(signal.shape[-1])
+        nwin = 1 if n < chunk_size else -(-(n - chunk_size) // out_chunk_size) + 1
+        bs = max(min(int(batch_size), nwin), 1)
+        eng = model.engine(torch.empty((), dtype=torch.float32, device=device).expand(bs, chunk_size))      # shape and device only: nothing is read
+        if (eng.dims.L, eng.dims.y) != (chunk_size, out_chunk_size):
+            raise ValueError(f"predict_sweep: chunk_size / out_chunk_size = {chunk_size} / {out_chunk_size}, the model has {eng.dims.L} / {eng.dims.y}")
+        if eng.decode_supported():
+            sig = _resident(signal, device, compand)
+            if verbose:
+                print("predict_sweep (device route): chunk_size, out_chunk_size, windows, settings = ", chunk_size, out_chunk_size, nwin, kn.shape[0])
+            with torch.no_grad():
+                code = eng.encode_long(sig.reshape(-1), batch=bs)
+                y = eng.decode_long(code, torch.from_numpy(kn).to(device), batch=bs)
+            return np.ascontiguousarray(y.cpu().numpy())
+        if not _warned_sweep_unsupported:
+            _warned_sweep_unsupported = True
+            warnings.warn(f"signaltrain_amd.predict_sweep: route='device' does not run this geometry (T={eng.dims.T}, OT={eng.dims.OT}: st_decode_supported); "
+                          "taking the batched route, setting by setting", RuntimeWarning, stacklevel=2)
+    return np.stack([predict_long(signal, k, model, chunk_size, out_chunk_size, sr=sr, effect=effect, device=device, compand=compand, batch_size=batch_size,
+                                  verbose=verbose) for k in kn])
+
+
 def fit_knobs(signal, target, model, chunk_size, out_chunk_size, steps=50, lr=0.05, init=None, batch_size=200, compand=False, grad_history=None,
-              route="batched"):
+              route="batched", encode_once=False):
     """The trained model used the other way round: given a recording and its processed version, the ONE knob vector (normalised settings, [-0.5, 0.5])
     for which the model turns `signal` into `target`.  Both are windowed as predict_long windows its input (the target of a window is its last
     out_chunk_size samples); the objective is the mean log-cosh of y_hat - target over all windows, minimised by torch's Adam on the K values, clamped to
@@ -142,11 +185,15 @@ def fit_knobs(signal, target, model, chunk_size, out_chunk_size, steps=50, lr=0.
     per window (knob automation; the result is then [nwin, K], grad_history receives [nwin, K] arrays).  Its objective is the mean over the
     len(signal) - (chunk_size - out_chunk_size) output samples the recording really has: positions of the last window behind the recording's end carry no loss
     and no gradient, where the batched route counts its zero-padded tail.  The two objectives coincide when len(signal) = chunk_size + k * out_chunk_size.
-    On a geometry st_fit_knobs_supported rejects it warns once and takes the batched route."""
+    On a geometry st_fit_knobs_supported rejects it warns once and takes the batched route.
+    encode_once=True (route="device" only; ValueError otherwise): the recording is encoded once (StepEngine.encode_long) and every step's forward starts at the knobs' layer from that
+    code (st_fit_knobs_coded) -- same objective, same steps, results equal up to the order of a few sums."""
     if route not in FIT_ROUTES:
         raise ValueError(f"fit_knobs: route must be one of {FIT_ROUTES}, not {route!r}")
+    if encode_once and route != "device":
+        raise ValueError(f"fit_knobs: encode_once needs route=\"device\" (route={route!r} runs the whole forward per step)")
     if route == "device":
-        res = _fit_device(signal, target, model, chunk_size, out_chunk_size, steps, lr, init, batch_size, compand, grad_history)
+        res = _fit_device(signal, target, model, chunk_size, out_chunk_size, steps, lr, init, batch_size, compand, grad_history, encode_once)
         if res is not None:
             return res
     device = next(model.parameters()).device
@@ -190,7 +237,7 @@ def fit_knobs(signal, target, model, chunk_size, out_chunk_size, steps=50, lr=0.
     return kn.detach().cpu().numpy(), history
 
 
-def _fit_device(signal, target, model, chunk_size, out_chunk_size, steps, lr, init, batch_size, compand, grad_history):
+def _fit_device(signal, target, model, chunk_size, out_chunk_size, steps, lr, init, batch_size, compand, grad_history, encode_once=False):
     """route="device" of fit_knobs; None where the library does not run this geometry that way (the caller then takes the batched route)."""
     global _warned_fit_unsupported
     device = next(model.parameters()).device
@@ -215,7 +262,9 @@ def _fit_device(signal, target, model, chunk_size, out_chunk_size, steps, lr, in
     kn0 = np.zeros(K, np.float32) if init is None else np.asarray(init, dtype=np.float32)
     kn0 = kn0.reshape(nwin, K) if (kn0.ndim == 2 and kn0.shape[0] == nwin and nwin > 1) else kn0.reshape(K)
     with torch.no_grad():
-        kn, loss, grads, _ = eng.fit_knobs(torch.from_numpy(signal).to(device), torch.from_numpy(target).to(device), torch.from_numpy(kn0).to(device),
+        sig = torch.from_numpy(signal).to(device)
+        code = eng.encode_long(sig, batch=bs) if (encode_once and eng.decode_supported()) else None
+        kn, loss, grads, _ = eng.fit_knobs(sig if code is None else code, torch.from_numpy(target).to(device), torch.from_numpy(kn0).to(device),
                                            steps=int(steps), lr=lr, batch=bs, want_grads=grad_history is not None)
     if grad_history is not None:
         g = grads.cpu().numpy()
