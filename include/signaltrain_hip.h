@@ -446,6 +446,48 @@ int    st_fit_knobs_coded(const st_dims* d, const float* params, const void* cod
                           double* loss_hist /* device, [steps] */, float* grad_hist /* device, [steps][knob_rows][K], may be NULL */,
                           void* ws, void* stream);
 
+/* Many knob settings of one recording from its code: a loss-only SCORE of S settings and a FIT of S starts at once.  J is not convex in the knobs, so a search scores
+ * many candidates, keeps the best few and refines them together; both steps read the code st_encode_long left (valid as stated there).  Windows, lengths, formats
+ * and the objective J are st_fit_knobs_coded's.  The fused autoencoder geometries only, K >= 1 (st_fit_knobs_supported).
+ * Rows of an internal batch are (setting, window) pairs, so that a recording shorter than a batch still fills it.  st_knob_multi_plan (host arithmetic only) gives
+ * the batches both entries walk, as 4-tuples (w0, nw, s0, ns) in out[4 i .. 4 i + 3], i < min(count, cap): windows w0 .. w0 + nw - 1 at settings s0 .. s0 + ns - 1,
+ * nw * ns <= d->B rows, row r of the batch being setting s0 + r / nw at window w0 + r % nw.  The rule, with nwin = st_predict_windows(d, n):
+ *     2 * nwin > d->B    st_decode_long's batches: ns == 1, nw = min(d->B, nwin - w0), the settings loop inside the window batch;
+ *     otherwise          every batch holds the whole recording ns = min(d->B / nwin, n_settings - s0) times (stacked).
+ * Every (setting, window) pair appears exactly once; the windows of any one setting appear in ascending order.  Returns the tuple count -- also when cap is too
+ * small or out is NULL -- and 0 for bad or unsupported dims, n <= 0 and n_settings < 1.
+ *   knobs       [n_settings][knob_rows][K] on the device, knob_rows == 1 or the window count.  Only the base pointer needs 16-byte alignment: the settings' rows are
+ *               read with scalar loads, whatever K.
+ *   ws          st_knob_multi_ws_bytes(d, n_settings) bytes (>= st_fit_knobs_ws_bytes(d), not decreasing in n_settings; 0 for bad or unsupported dims and
+ *               n_settings < 1), 16-byte aligned: st_fit_knobs' workspace with the per-setting gradient accumulators and the score's per-setting loss partials
+ *               of one window batch in front of the batch's.  Scratch: nothing in it is read before it is written.
+ * st_score_knobs_coded: loss[s] = J at setting s; win_loss[s][w] (may be NULL) = the sum of log-cosh over window w's valid output samples times 1 / n_out -- the rows
+ *   sum to loss[s] up to rounding; with knob_rows == nwin that is the per-window best of a grid.  Per plan batch: the decoder forward, the frames GEMM, ONE
+ *   overlap-add launch that forms st_fit_knobs' sums and log-cosh partials (the same formula, the same per-slot tree, the same validity rule behind the recording's
+ *   end) and writes no output sample and no gradient operand; a tail launch of one workgroup per setting then folds the partials into loss / win_loss in
+ *   double, in a fixed order -- behind every stacked batch, and once per window batch, behind its last setting, where the recording is not stacked.  No
+ *   [S][n_out] buffer exists.
+ * st_fit_knobs_multi_coded: S independent runs of st_fit_knobs_coded -- setting s has its own rows of knobs / adam_m / adam_v ([n_settings][knob_rows][K], in place),
+ *   loss_hist[step][s] and grad_hist[step][s][knob_rows][K] (may be NULL).  Per plan batch it runs what st_fit_knobs_coded runs, over the stacked rows; the tail, per
+ *   setting: the loss partials in st_fit_knobs' order, the setting's rows summed in ascending window order (or taken row by row for knob_rows == nwin), and after the
+ *   setting's last batch of the step 1 / n_out, grad_hist, Adam and the clamp, in st_fit_knobs' arithmetic.  The parameter-only head is built once per call.
+ *   `steps` calls of one step chained through first_step are, bit for bit, one call of `steps` steps; n_settings == 1 is st_fit_knobs_coded bit for bit.
+ * No float atomics: every sum has a fixed order and a repeated call repeats its bits.  No allocation, no hipMemcpy, no host synchronisation; parameters, the code and
+ * the recordings are only read.
+ * Refused before any launch (ST_ERR_ARG, the rule in st_last_error(), naming the entry): everything st_fit_knobs_coded refuses (the optimiser's arguments: the fit
+ * only), n_settings < 1, a null loss / loss_hist, and a plan batch whose stacked row count exceeds the kernels' 32-bit element offsets.  An n with no output sample
+ * (n <= L - y) returns ST_OK without a launch. */
+int    st_knob_multi_plan(const st_dims* d, long long n, int n_settings, int* out, int cap);
+size_t st_knob_multi_ws_bytes(const st_dims* d, int n_settings);
+int    st_score_knobs_coded(const st_dims* d, const float* params, const void* code, int fmt, const void* signal, const void* target, long long n,
+                            const float* knobs /* [n_settings][knob_rows][K] */, long long knob_rows, int n_settings,
+                            double* loss /* device, [n_settings] */, float* win_loss /* device, [n_settings][nwin], may be NULL */, void* ws, void* stream);
+int    st_fit_knobs_multi_coded(const st_dims* d, const float* params, const void* code, int fmt, const void* signal, const void* target, long long n,
+                                float* knobs /* [n_settings][knob_rows][K], in / out */, long long knob_rows, int n_settings, float* adam_m, float* adam_v,
+                                long long first_step, int steps, float lr, float beta1, float beta2, float eps,
+                                double* loss_hist /* device, [steps][n_settings] */, float* grad_hist /* device, [steps][n_settings][knob_rows][K], may be NULL */,
+                                void* ws, void* stream);
+
 /* Data-parallel split of st_loss_backward.  After p1 the gradients of the synthesis bases and both
  * autoencoders (grads[offs[2]..end)) are final: all-reduce them while p2 computes the analysis
  * weight gradient (rows [0,F) of tensors 0 and 1) and the loss scalars. */

@@ -131,6 +131,10 @@ SIGNATURES = {
     "st_encode_long": (_i, [_D, _p, _i, _p, C.c_longlong, _p, _p, _p]),
     "st_decode_long": (_i, [_D, _p, _p, _i, _p, C.c_longlong, _p, C.c_longlong, _i, _p, C.c_longlong, _p, _p]),
     "st_fit_knobs_coded": (_i, [_D, _p, _p, _i, _p, _p, C.c_longlong, _p, C.c_longlong, _p, _p, C.c_longlong, _i, _f, _f, _f, _f, _p, _p, _p, _p]),
+    "st_knob_multi_plan": (_i, [_D, C.c_longlong, _i, C.POINTER(C.c_int), _i]),
+    "st_knob_multi_ws_bytes": (C.c_size_t, [_D, _i]),
+    "st_score_knobs_coded": (_i, [_D, _p, _p, _i, _p, _p, C.c_longlong, _p, C.c_longlong, _i, _p, _p, _p, _p]),
+    "st_fit_knobs_multi_coded": (_i, [_D, _p, _p, _i, _p, _p, C.c_longlong, _p, C.c_longlong, _i, _p, _p, C.c_longlong, _i, _f, _f, _f, _f, _p, _p, _p, _p]),
     "st_loss_backward_p1": (_i, [_D, _p, _p, _p, _p, _p, _p, _p]),
     "st_loss_backward_p2": (_i, [_D, _p, _p, _p, _p, _p]),
     "st_loss_backward_p2_staged": (_i, [_D, _p, _p, _p, _p, _p, _p]),

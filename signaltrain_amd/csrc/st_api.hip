@@ -27,6 +27,7 @@
 #include "st_predict.h"
 #include "st_decode.h"
 #include "st_fit.h"
+#include "st_multi.h"
 
 // ------------------------------------------------------------------------------ errors
 static thread_local char g_err[512] = "";
@@ -2011,7 +2012,7 @@ static int predict_batches(const st_dims* d, const Layout& L, const PredictWS& p
                                       (size_t)sta::ae_dec_lds_floats() * sizeof(float), st_stream(stream),
                                       cj->code + (size_t)w0 * CW, ks, (one || q.K == 0) ? 0 : q.K, ae_m, ae_p, L.go,
                                       fit ? w.mag_hat : nullptr, fit ? w.phs_hat : nullptr, w.AA, g16 ? w.AA16 : nullptr, g16 ? gemm_ht(q.prec) : 0,
-                                      fit ? w.aews : nullptr, fit ? w.mag : nullptr, fit ? p.knobs : nullptr, q.B, q.T, q.OT, q.F, q.K, L.KP); }));
+                                      fit ? w.aews : nullptr, fit ? w.mag : nullptr, fit ? p.knobs : nullptr, q.B, q.T, q.OT, q.F, q.K, L.KP, 0, 0u); }));
                 ST_LAUNCHED("ae_dec_fwd");
             } else {
                 ST_TRY(ae_fwd_body(&q, L, w.mag, w.phs, kn, ae_m, ae_p, w.mag_hat, w.phs_hat, w.AA, w.reg_p, fit ? w.aews : nullptr, stream, g16 ? w.AA16 : nullptr, false, nullptr,
@@ -2033,7 +2034,7 @@ static int predict_batches(const st_dims* d, const Layout& L, const PredictWS& p
             with_bool(three, [&](auto NF3) { with_slabs(ns, [&](auto NS) {
                 hipLaunchKernelGGL((stf::fit_ola_kernel<T, NS(), NF3() ? 3 : 0>), grid, dim3(256), 0, st_stream(stream),
                                    w.frs, slab, signal, reinterpret_cast<const T*>(fit->target), w.dsyn, g16 ? w.dsyn16 : nullptr, g16 ? gemm_ht(q.prec) : 0, w.loss_p, nslot,
-                                   a.s0, n_out, q.L, q.N, q.H, q.OT, q.y); }); });
+                                   a.s0, n_out, q.L, q.N, q.H, q.OT, q.y, 0); }); });
             ST_LAUNCHED("fit_ola");
             ST_TRY(stft_gemm(step_stft_plan(&q, w, GEMM_DGRAD), slabs_at(w.dAA), stream));
             {
@@ -2276,6 +2277,216 @@ extern "C" int st_decode_long(const st_dims* d, const float* params, const void*
     const CodeJob cj{nullptr, reinterpret_cast<const float*>(code), n_settings, out_pitch, (size_t)knob_rows * d->K};
     return fmt == ST_PCM_S16 ? predict_batches(d, L, p, params, reinterpret_cast<const short*>(signal), n, knobs, knob_rows, out, n_out, ws, stream, nullptr, 0, &cj)
                              : predict_batches(d, L, p, params, reinterpret_cast<const float*>(signal), n, knobs, knob_rows, out, n_out, ws, stream, nullptr, 0, &cj);
+}
+
+// ------------------------------------------------------------------------------ many knob settings from one code (st_multi.h)
+// st_score_knobs_coded and st_fit_knobs_multi_coded walk the batches of st_knob_multi_plan: rows of a batch are (setting, window) pairs.  The workspace is
+// st_fit_knobs' with the per-setting gradient accumulators [S][16] and the score's per-setting loss partials [S][partials of a batch of d->B] in front of the batch
+// workspace: [head | the fit's rows and scratch | acc | partials | one batch's workspace].
+static size_t multi_acc_bytes(int S) { return ((size_t)S * 16 + 63) / 64 * 64 * sizeof(float); }
+static size_t multi_extra_bytes(const st_dims* d, int S) { return multi_acc_bytes(S) + ((size_t)S * ola_loss_partials(d) + 63) / 64 * 64 * sizeof(float); }
+static bool multi_plan_of(const st_dims* d, long long n, int n_settings, stx::MultiPlan* mp)
+{
+    if (!st_fit_knobs_supported(d) || n <= 0 || n_settings < 1) return false;
+    const long long nwin = predict_windows(d, n);
+    if (nwin > 0x7fffffffLL) return false;
+    *mp = stx::multi_plan(nwin, d->B, n_settings);
+    return mp->count() <= 0x7fffffffLL;
+}
+extern "C" int st_knob_multi_plan(const st_dims* d, long long n, int n_settings, int* out, int cap)
+{
+    stx::MultiPlan mp;
+    if (!multi_plan_of(d, n, n_settings, &mp)) return 0;
+    const long long cnt = mp.count();
+    for (long long i = 0; out && i < cnt && i < cap; ++i) {
+        const stx::MultiBatch b = mp.at(i);
+        out[4 * i] = b.w0; out[4 * i + 1] = b.nw; out[4 * i + 2] = b.s0; out[4 * i + 3] = b.ns;
+    }
+    return (int)cnt;
+}
+extern "C" size_t st_knob_multi_ws_bytes(const st_dims* d, int n_settings)
+{
+    if (n_settings < 1) return 0;
+    const size_t fb = st_fit_knobs_ws_bytes(d);
+    return fb ? fb + multi_extra_bytes(d, n_settings) : 0;
+}
+// what both entries ask of the recording, the code, the knob rows and the workspace, under the entry's name (st_fit_knobs_coded's rules and wording)
+static int multi_args(const char* name, const st_dims* d, Layout* L, const float* params, const void* code, int fmt, const void* signal, const void* target, long long n,
+                      const float* knobs, long long knob_rows, int n_settings, const void* ws)
+{
+    if (make_layout(d, L) != ST_OK) {
+        char rule[400]; snprintf(rule, sizeof(rule), "%s", st_last_error());
+        return st_fail(ST_ERR_ARG, "%s: %s", name, rule);
+    }
+    ST_REQ(d->K >= 1, "%s: K = %d (a model without knobs has no knobs to fit)", name, d->K);
+    ST_REQ(params, "%s: null pointer (params)", name); ST_REQ(code, "%s: null pointer (code)", name); ST_REQ(signal, "%s: null pointer (signal)", name);
+    ST_REQ(target, "%s: null pointer (target)", name); ST_REQ(knobs, "%s: null pointer (knobs)", name); ST_REQ(ws, "%s: null pointer (ws)", name);
+    ST_REQ(n > 0, "%s: n must be positive (n = %lld)", name, n);
+    ST_REQ(fmt == ST_PCM_F32 || fmt == ST_PCM_S16, "%s: fmt = %d is neither ST_PCM_F32 nor ST_PCM_S16", name, fmt);
+    const long long nwin = predict_windows(d, n);
+    ST_REQ(knob_rows == 1 || knob_rows == nwin, "%s: knob_rows = %lld must be 1 or the window count (%lld windows for n = %lld)", name, knob_rows, nwin, n);
+    ST_REQ(n_settings >= 1, "%s: n_settings = %d must be at least 1", name, n_settings);
+    const uintptr_t sa = fmt == ST_PCM_S16 ? 7 : 15;
+    ST_REQ((reinterpret_cast<uintptr_t>(signal) & sa) == 0, "%s: signal must be %d-byte aligned", name, (int)sa + 1);
+    ST_REQ((reinterpret_cast<uintptr_t>(target) & sa) == 0, "%s: target must be %d-byte aligned", name, (int)sa + 1);
+    ST_REQ((reinterpret_cast<uintptr_t>(knobs) & 15) == 0, "%s: knobs must be 16-byte aligned", name);
+    ST_REQ((reinterpret_cast<uintptr_t>(ws) & 15) == 0, "%s: ws must be 16-byte aligned", name);
+    ST_REQ((reinterpret_cast<uintptr_t>(code) & 15) == 0, "%s: code must be 16-byte aligned", name);
+    ST_REQ(!ae_is_wide(d), "%s: not supported for the wide autoencoder geometries (T = %d > 32 or OT = %d > 16): st_fit_knobs_supported", name, d->T, d->OT);
+    stx::MultiPlan mp;
+    ST_REQ(multi_plan_of(d, n, n_settings, &mp), "%s: the plan of %lld windows x %d settings does not fit (st_knob_multi_plan)", name, nwin, n_settings);
+    // the 32-bit element offsets of the kernels (predict_batches' guards) at the plan's largest batch: its rows are the stacked (setting, window) pairs
+    const size_t rows = mp.stacked ? (size_t)mp.per * (size_t)nwin : (size_t)(nwin < d->B ? nwin : d->B);
+    const size_t CW = stc::code_window_floats(L->KP / 2, d->OT);
+    ST_REQ(rows * CW < ((size_t)1 << 30) && rows * d->T * d->F < ((size_t)1 << 30) && rows * d->OT * L->KP < ((size_t)1 << 30) && rows * d->T < ((size_t)1 << 24) &&
+           (size_t)synth_slabs(d) * rows * d->OT * L->KP < ((size_t)1 << 30) && rows * d->T * L->KP < ((size_t)1 << 30) &&
+           (size_t)knob_rows * d->K * (mp.stacked ? (size_t)mp.per : 1) < ((size_t)1 << 30),
+           "%s: batch too large for the kernels' 32-bit element offsets (%zu stacked rows)", name, rows);
+    return ST_OK;
+}
+struct MultiJob {
+    const float* code; const void* target; long long nwin; int S;
+    float* knobs; long long knob_rows;      // [S][knob_rows][K]
+    const FitJob* fit;                      // NULL: score
+    double* loss; float* win_loss;          // loss[S] of this step (or of the score); win_loss [S][nwin] or NULL
+    double inv_n_d; float *acc, *lp_all;    // lp_all: [S][ola_loss_partials(d)], the score's partials of every setting of a window batch
+};
+template <typename T>
+static int multi_batches(const st_dims* d, const Layout& L, const PredictWS& p, const float* params, const T* signal, long long n_out, const MultiJob& j,
+                         void* ws, size_t batch_off, void* stream)
+{
+    const FitJob* const fit = j.fit;
+    const size_t CW = stc::code_window_floats(L.KP / 2, d->OT);
+    const float* ae_m = params + L.offs[4]; const float* ae_p = params + L.offs[22];
+    const bool g16 = stft_family(d, GEMM_ANALYSIS, SGP_PADDED | SGP_G16) == GF_G16;      // as predict_batches
+    const bool one = j.knob_rows == 1;
+    const size_t set_stride = (size_t)j.knob_rows * d->K;
+    const stx::MultiPlan mp = stx::multi_plan(j.nwin, d->B, j.S);
+    const long long cnt = mp.count();
+    const bool defer = !fit && !mp.stacked;      // the score of a recording that is not stacked: one tail launch per window batch, behind its last setting
+    const size_t lpn = (size_t)ola_loss_partials(d);
+    for (long long bi = 0; bi < cnt; ++bi) {
+        const stx::MultiBatch mb = mp.at(bi);
+        st_dims q = *d; q.B = mb.nw * mb.ns;
+        WS w; carve(&q, L, reinterpret_cast<char*>(ws) + batch_off, &w);
+        w.g16 = g16;
+        w.Sfold = p.Sfold; w.SfoldT = p.SfoldT; w.Sfold16 = p.Sfold16; w.SfoldT16 = p.SfoldT16; w.W16 = p.W16;
+        w.pl_W = p.pl_W; w.pl_Sfold = p.pl_Sfold; w.pl_SfoldT = p.pl_SfoldT;
+        const size_t ro = (size_t)mb.s0 * set_stride + (one ? 0 : (size_t)mb.w0 * q.K);      // the batch's first knob row
+        ST_TRY(with_ht(ae_ht(q.prec), [&](auto HT) {
+            return launch_lds("ae_dec_fwd_kernel", sta::ae_dec_fwd_kernel<sta::AE_DEC_NW, HT(), true>, dim3(ae_dec_grid(&q)), dim3(sta::AE_DEC_NW * 64),
+                              (size_t)sta::ae_dec_lds_floats() * sizeof(float), st_stream(stream),
+                              j.code + (size_t)mb.w0 * CW, (const float*)j.knobs + ro, one ? 0 : q.K, ae_m, ae_p, L.go,
+                              fit ? w.mag_hat : nullptr, fit ? w.phs_hat : nullptr, w.AA, g16 ? w.AA16 : nullptr, g16 ? gemm_ht(q.prec) : 0,
+                              fit ? w.aews : nullptr, fit ? w.mag : nullptr, fit ? p.knobs : nullptr, q.B, q.T, q.OT, q.F, q.K, L.KP, mb.nw, (unsigned)set_stride); }));
+        ST_LAUNCHED("ae_dec_fwd");
+        ST_TRY(stft_gemm(step_stft_plan(&q, w, GEMM_FRAMES), slabs_at(w.frs), stream));
+        const int ns = frame_slabs(&q);
+        const dim3 grid((q.y / 4 + 255) / 256, q.B);
+        const size_t slab = (size_t)q.B * q.OT * q.N;
+        const bool three = (q.N + q.H - 1) / q.H <= 3;
+        const int nslot = (q.y + 255) / 256;
+        const long long s0 = (long long)mb.w0 * q.y;
+        float* const lp = defer ? j.lp_all + (size_t)mb.s0 * lpn : w.loss_p;
+        with_bool(fit != nullptr, [&](auto FIT) { with_bool(three, [&](auto NF3) { with_slabs(ns, [&](auto NS) {
+            hipLaunchKernelGGL((stf::fit_ola_kernel<T, NS(), NF3() ? 3 : 0, FIT() ? 1 : 2>), grid, dim3(256), 0, st_stream(stream),
+                               w.frs, slab, signal, reinterpret_cast<const T*>(j.target), w.dsyn, g16 ? w.dsyn16 : nullptr, g16 ? gemm_ht(q.prec) : 0, lp, nslot,
+                               s0, n_out, q.L, q.N, q.H, q.OT, q.y, mb.nw); }); }); });
+        ST_LAUNCHED("fit_ola");
+        if (defer && mb.s0 + 1 < j.S) continue;
+        const int ts0 = defer ? 0 : mb.s0, tns = defer ? j.S : mb.ns;      // the settings this tail launch folds
+        stx::MultiTailArgs m;
+        m.t = fit ? fit->hyper : stf::TailArgs{};
+        m.t.inv_n_d = j.inv_n_d;
+        m.t.loss_p = defer ? j.lp_all : w.loss_p; m.lp_stride = defer ? lpn : (size_t)mb.nw * nslot; m.t.n_lp = mb.nw * nslot; m.t.loss = nullptr; m.t.acc = nullptr;
+        m.t.rows = nullptr; m.t.nb = mb.nw; m.t.K = q.K;
+        m.t.per_window = !one; m.t.first = mb.w0 == 0; m.t.last = mb.w0 + mb.nw >= j.nwin;
+        m.t.knobs = m.t.m = m.t.v = m.t.grad = nullptr;
+        if (fit) {
+            ST_TRY(stft_gemm(step_stft_plan(&q, w, GEMM_DGRAD), slabs_at(w.dAA), stream));
+            const stg::RowMap live = synth_live(&q);
+            const int groups = ae_fwd_groups(&q), kgrid = ae_knob_grid(&q);
+            ST_TRY(with_ht(ae_ht(q.prec), [&](auto HT) {
+                return launch_lds("ae_knob_bwd_kernel", sta::ae_knob_bwd_kernel<AE_KNOB_NW, HT()>, dim3(kgrid, 2), dim3(AE_KNOB_NW * 64),
+                                  (size_t)sta::ae_knob_lds_floats(AE_KNOB_NW) * sizeof(float), st_stream(stream),
+                                  w.mag, (const float*)p.knobs, ae_m, ae_p, L.go, w.mag_hat, w.phs_hat, w.dAA, w.aews, fit->kg, q.B, q.T, q.OT, q.F, q.K, L.KP,
+                                  live.t_lo, live.t_lo + live.Tv - 1, synth_slabs(&q), (size_t)q.B * q.OT * L.KP); }));
+            ST_LAUNCHED("ae_knob_bwd");
+            const size_t w5 = (size_t)L.offs[4] + (size_t)L.go.w[4];
+            hipLaunchKernelGGL(knob_grad_kernel, dim3(q.B), dim3(64), 0, st_stream(stream), params + w5, (const float*)fit->kg, params + w5 + L.PG,
+                               (const float*)fit->kg + (size_t)groups * 16, q.K, fit->rows, L.KP / 32);
+            ST_LAUNCHED("knob_grad");
+            m.t.rows = fit->rows;
+            m.t.knobs = fit->knobs + ro; m.t.m = fit->m + ro; m.t.v = fit->v + ro; m.t.grad = fit->grad ? fit->grad + ro : nullptr;
+        }
+        m.nw = mb.nw; m.nslot = nslot; m.set_stride = set_stride;
+        m.loss = j.loss + ts0;
+        m.win_loss = j.win_loss ? j.win_loss + (size_t)ts0 * j.nwin + mb.w0 : nullptr; m.win_pitch = j.nwin;
+        m.acc = j.acc + (size_t)ts0 * 16;
+        hipLaunchKernelGGL(stx::multi_tail_kernel, dim3(tns), dim3(256), 0, st_stream(stream), m);
+        ST_LAUNCHED("multi_tail");
+    }
+    return ST_OK;
+}
+extern "C" int st_score_knobs_coded(const st_dims* d, const float* params, const void* code, int fmt, const void* signal, const void* target, long long n,
+                                    const float* knobs, long long knob_rows, int n_settings, double* loss, float* win_loss, void* ws, void* stream)
+{
+    static const char* const name = "st_score_knobs_coded";
+    Layout L; ST_TRY(multi_args(name, d, &L, params, code, fmt, signal, target, n, knobs, knob_rows, n_settings, ws));
+    ST_REQ(loss, "%s: null pointer (loss)", name);
+    const long long n_out = n - ((long long)d->L - d->y);
+    if (n_out <= 0) return ST_OK;      // no output sample, no objective: nothing launched, every buffer left alone
+    PredictWS p; predict_carve(d, ws, &p);
+    FitWS f; fit_carve(d, reinterpret_cast<char*>(ws) + p.head_bytes, &f);
+    MultiJob j{reinterpret_cast<const float*>(code), target, predict_windows(d, n), n_settings, const_cast<float*>(knobs), knob_rows, nullptr, loss, win_loss,
+               1.0 / (double)n_out, reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + p.head_bytes + f.bytes),
+               reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + p.head_bytes + f.bytes + multi_acc_bytes(n_settings))};
+    const size_t batch_off = p.head_bytes + f.bytes + multi_extra_bytes(d, n_settings);
+    prof_mark("begin", stream);
+    ST_TRY(predict_prep(d, L, p, params, stream));
+    return fmt == ST_PCM_S16 ? multi_batches(d, L, p, params, reinterpret_cast<const short*>(signal), n_out, j, ws, batch_off, stream)
+                             : multi_batches(d, L, p, params, reinterpret_cast<const float*>(signal), n_out, j, ws, batch_off, stream);
+}
+extern "C" int st_fit_knobs_multi_coded(const st_dims* d, const float* params, const void* code, int fmt, const void* signal, const void* target, long long n,
+                                        float* knobs, long long knob_rows, int n_settings, float* adam_m, float* adam_v,
+                                        long long first_step, int steps, float lr, float beta1, float beta2, float eps,
+                                        double* loss_hist, float* grad_hist, void* ws, void* stream)
+{
+    static const char* const name = "st_fit_knobs_multi_coded";
+    Layout L; ST_TRY(multi_args(name, d, &L, params, code, fmt, signal, target, n, knobs, knob_rows, n_settings, ws));
+    ST_REQ(adam_m, "%s: null pointer (adam_m)", name); ST_REQ(adam_v, "%s: null pointer (adam_v)", name); ST_REQ(loss_hist, "%s: null pointer (loss_hist)", name);
+    ST_REQ(steps >= 1, "%s: steps = %d must be at least 1", name, steps);
+    ST_REQ(first_step >= 1, "%s: first_step = %lld must be at least 1 (Adam's step number is 1-based)", name, first_step);
+    ST_REQ(std::isfinite(lr) && lr >= 0.f, "%s: lr = %g must be finite and not negative", name, (double)lr);
+    ST_REQ(std::isfinite(beta1) && beta1 >= 0.f && beta1 < 1.f, "%s: beta1 = %g must lie in [0, 1)", name, (double)beta1);
+    ST_REQ(std::isfinite(beta2) && beta2 >= 0.f && beta2 < 1.f, "%s: beta2 = %g must lie in [0, 1)", name, (double)beta2);
+    ST_REQ(std::isfinite(eps) && eps > 0.f, "%s: eps = %g must be finite and positive", name, (double)eps);
+    ST_REQ((reinterpret_cast<uintptr_t>(adam_m) & 15) == 0, "%s: adam_m must be 16-byte aligned", name);
+    ST_REQ((reinterpret_cast<uintptr_t>(adam_v) & 15) == 0, "%s: adam_v must be 16-byte aligned", name);
+    const long long n_out = n - ((long long)d->L - d->y);
+    if (n_out <= 0) return ST_OK;
+    PredictWS p; predict_carve(d, ws, &p);
+    FitWS f; fit_carve(d, reinterpret_cast<char*>(ws) + p.head_bytes, &f);
+    const size_t batch_off = p.head_bytes + f.bytes + multi_extra_bytes(d, n_settings);
+    prof_mark("begin", stream);
+    ST_TRY(predict_prep(d, L, p, params, stream));      // once per call, whatever the number of starts and steps
+    const size_t all_floats = (size_t)n_settings * knob_rows * d->K;
+    for (int s = 0; s < steps; ++s) {
+        const double t = (double)(first_step + s);
+        const double bc1 = 1.0 - pow((double)beta1, t), bc2 = 1.0 - pow((double)beta2, t);
+        FitJob job;
+        job.target = target; job.kg = f.kg; job.rows = f.rows; job.acc = nullptr;
+        job.knobs = knobs; job.m = adam_m; job.v = adam_v; job.grad = grad_hist ? grad_hist + (size_t)s * all_floats : nullptr; job.loss = nullptr;
+        job.hyper = stf::TailArgs{};      // st_fit_knobs' scalars of this step
+        job.hyper.inv_n_d = 1.0 / (double)n_out; job.hyper.inv_n = (float)(1.0 / (double)n_out);
+        job.hyper.neg_step = (float)(-(double)lr / bc1); job.hyper.bc2_sqrt = (float)sqrt(bc2);
+        job.hyper.w1 = (float)(1.0 - (double)beta1); job.hyper.b2 = beta2; job.hyper.w2 = (float)(1.0 - (double)beta2); job.hyper.eps = eps;
+        MultiJob j{reinterpret_cast<const float*>(code), target, predict_windows(d, n), n_settings, knobs, knob_rows, &job, loss_hist + (size_t)s * n_settings, nullptr,
+                   1.0 / (double)n_out, reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + p.head_bytes + f.bytes), nullptr};
+        ST_TRY(fmt == ST_PCM_S16 ? multi_batches(d, L, p, params, reinterpret_cast<const short*>(signal), n_out, j, ws, batch_off, stream)
+                                 : multi_batches(d, L, p, params, reinterpret_cast<const float*>(signal), n_out, j, ws, batch_off, stream));
+    }
+    return ST_OK;
 }
 
 // Data-parallel split of st_loss_backward: after phase 1 the synthesis + autoencoder gradients

@@ -70,13 +70,16 @@ struct DecIn { f32x4 h4[2]; f32x4 kn; float tl[2][4]; };
 //   AA / AA16          [B][OT][KP] spectra, fp32 or rounded to the GEMM's operand type (AA16 != NULL), exactly as ae_fwd_kernel chooses; pad bins get zeros
 //   h4_keep, mag_keep, kn_keep (all or none): the batch-layout copies ae_knob_bwd_kernel reads -- h4 [net][B * gpw][64] float4, the tail rows of a [B][T][F] mag,
 //                      the knob row repeated over the batch [B][K] (kstride == 0 only)
-template <int NW, int BF = 0>
+// STK (st_multi.h): rows of the batch are (setting, window) pairs -- row b is window b % nw of the batch's windows at setting b / nw: it reads the code of window
+//                      b % nw and the knob row at (b / nw) * set_stride + (b % nw) * kstride, and kn_keep always receives the [B][K] copy of the rows' knobs.
+//                      STK == false is the kernel as it was: nw and set_stride are not read.
+template <int NW, int BF = 0, bool STK = false>
 __global__ void __launch_bounds__(NW * 64, 4)
 ae_dec_fwd_kernel(const float* __restrict__ code, const float* __restrict__ knobs, const int kstride,
                   const float* __restrict__ ae_m, const float* __restrict__ ae_p, const AEOffsets go,
                   float* __restrict__ mag_hat, float* __restrict__ phs_hat, float* __restrict__ AA, unsigned short* __restrict__ AA16, const int aa_ht,
                   float* __restrict__ h4_keep, float* __restrict__ mag_keep, float* __restrict__ kn_keep,
-                  const int B, const int T, const int OT, const int F, const int K, const int KP)
+                  const int B, const int T, const int OT, const int F, const int K, const int KP, const int nw, const unsigned set_stride)
 {
     using P = CP<1>;
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -99,12 +102,13 @@ ae_dec_fwd_kernel(const float* __restrict__ code, const float* __restrict__ knob
     // RAW loads from always valid addresses (a padding row re-reads row 0 of the tail, a knob past K knob 0); masked where they are consumed
     auto load_in = [&](const int gq, DecIn& in) {
         const int b = gq / gpw, fg = gq - b * gpw;
-        const unsigned wb = ST_MUL24(b, CW);
+        const int bs = STK ? b / nw : 0, bw = STK ? b - bs * nw : b;      // the row's setting and window inside the batch
+        const unsigned wb = ST_MUL24(bw, CW);
         const unsigned h = wb + (unsigned)(fg * 256 + lane * 4);
         in.h4[0] = *reinterpret_cast<const f32x4*>(reinterpret_cast<const char*>(code) + (size_t)(h << 2));
         in.h4[1] = *reinterpret_cast<const f32x4*>(reinterpret_cast<const char*>(code) + (size_t)((h + (unsigned)FP * 16u) << 2));
         const unsigned tb = wb + (unsigned)(fg * 16 + c);
-        const unsigned kb = ST_MUL24(b, kstride);
+        const unsigned kb = ST_MUL24(bw, kstride) + (STK ? (unsigned)bs * set_stride : 0u);
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             in.tl[0][r] = ldg32(code, tb + tl0 + toT[r]); in.tl[1][r] = ldg32(code, tb + tl1 + toT[r]);
@@ -136,7 +140,7 @@ ae_dec_fwd_kernel(const float* __restrict__ code, const float* __restrict__ knob
             for (int r = 0; r < 4; ++r) {
                 const int to = 4 * g + r;
                 if (fv && to < OT) stg32(mag_keep, mo + ST_MUL24(to, F), cur.tl[0][r]);
-                if (kstride == 0 && fg == 0 && c == 0 && to < K) kn_keep[ST_MUL24(b, K) + (unsigned)to] = cur.kn[r];
+                if ((STK || kstride == 0) && fg == 0 && c == 0 && to < K) kn_keep[ST_MUL24(b, K) + (unsigned)to] = cur.kn[r];
             }
         }
         { const float* const W[2] = ST_DW2(P::A4); const float* const bb[2] = ST_DW2(P::B4); layer_fwd<2, 1, 2, CL::O4, BF>(W, bb, hk, h5, g, c); }

@@ -25,15 +25,17 @@ namespace stf {
 // Four output samples per lane, grid (ceil(y / 4 / 256), windows of the batch): predict_ola_kernel's sums (NF = 3 / NF = 0 as there), then the loss side.  A wave's 64
 // quads are one slot of 256 samples: slot = 4 * blockIdx.x + wave, nslot = ceil(y / 256) per window, the tree of ola_loss4_kernel.  Samples at or behind n_out carry
 // neither loss nor gradient.  dsyn16 != NULL: the operand goes out rounded to the 16-bit type ht INSTEAD of fp32 (what the 16-bit data-gradient GEMM reads).
-template <typename T, int NS, int NF>
+// STK (st_multi.h): 0, the kernel as it was (nw is not read).  1: rows of the batch are (setting, window) pairs -- the frames, the d-syn row and the partials are
+// row b's, the recording's samples those of window b % nw.  2: the same rows, the score form: the sums and the log-cosh partials, no d-syn operand written.
+template <typename T, int NS, int NF, int STK = 0>
 __global__ void __launch_bounds__(256)
 fit_ola_kernel(const float* __restrict__ frs, const size_t slab, const T* __restrict__ sig, const T* __restrict__ tgt,
                float* __restrict__ dsyn, unsigned short* __restrict__ dsyn16, const int ht, float* __restrict__ loss_partial, const int nslot,
-               const long long s0, const long long n_out, const int L, const int N, const int H, const int OT, const int ysz)
+               const long long s0, const long long n_out, const int L, const int N, const int H, const int OT, const int ysz, const int nw)
 {
     const int b = blockIdx.y;
     const int j = 4 * (blockIdx.x * 256 + threadIdx.x);
-    const long long i = s0 + (long long)b * ysz + j;      // output sample; its input and target sample is (L - ysz) + i < n wherever i < n_out
+    const long long i = s0 + (long long)(STK ? b % nw : b) * ysz + j;      // output sample; its input and target sample is (L - ysz) + i < n wherever i < n_out
     float lc = 0.f;
     float ds[4] = {0.f, 0.f, 0.f, 0.f};
     if (j < ysz && i < n_out) {
@@ -88,14 +90,16 @@ fit_ola_kernel(const float* __restrict__ frs, const size_t slab, const T* __rest
             ds[q] = valid ? -2.0f * tanhf(dlt) : 0.f;      // 2 tanh(y_hat - target): d y_hat / d (overlap-added sample) = 2; 1 / n_out comes behind W5
         }
     }
-    const size_t ro = (size_t)b * (ysz + 2 * N);
-    if (j < ysz) {
-        if (dsyn16) *reinterpret_cast<uint2*>(dsyn16 + ro + N + j) = st_to_h16x4(make_float4(ds[0], ds[1], ds[2], ds[3]), ht);
-        else *reinterpret_cast<float4*>(dsyn + ro + N + j) = make_float4(ds[0], ds[1], ds[2], ds[3]);
-    }
-    for (int m = blockIdx.x * 256 + threadIdx.x; m < 2 * N; m += gridDim.x * 256) {      // the Conv padding of the gradient signal
-        if (dsyn16) dsyn16[ro + (m < N ? m : ysz + m)] = 0;
-        else dsyn[ro + (m < N ? m : ysz + m)] = 0.f;
+    if constexpr (STK != 2) {
+        const size_t ro = (size_t)b * (ysz + 2 * N);
+        if (j < ysz) {
+            if (dsyn16) *reinterpret_cast<uint2*>(dsyn16 + ro + N + j) = st_to_h16x4(make_float4(ds[0], ds[1], ds[2], ds[3]), ht);
+            else *reinterpret_cast<float4*>(dsyn + ro + N + j) = make_float4(ds[0], ds[1], ds[2], ds[3]);
+        }
+        for (int m = blockIdx.x * 256 + threadIdx.x; m < 2 * N; m += gridDim.x * 256) {      // the Conv padding of the gradient signal
+            if (dsyn16) dsyn16[ro + (m < N ? m : ysz + m)] = 0;
+            else dsyn[ro + (m < N ? m : ysz + m)] = 0.f;
+        }
     }
     float q = lc;        // ((l0 + l1) + l2) + l3, formed in sample order above
 #pragma unroll

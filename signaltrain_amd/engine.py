@@ -712,6 +712,88 @@ class StepEngine:
         shape = (d.K,) if (rows == 1 and torch.as_tensor(knobs).dim() == 1) else (rows, d.K)
         return kn.reshape(shape), loss_hist, grad_hist, (m, v, first + steps)
 
+    # ---------------------------------------------------------------- many knob settings from one code
+    def _multi_args(self, what, code, target, knobs, batch):
+        """What score_knobs and fit_knobs_multi share: the code's validity (fit_knobs' checks), the recordings in one format, the settings as [S, rows, K], the
+        dims and the workspace (st_knob_multi_ws_bytes, the engine's own, allocated on first use)."""
+        self._check_code(what, code)
+        signal = code.signal
+        if not (torch.is_tensor(target) and target.dim() == 1 and target.device == self.device and target.dtype in (torch.float32, torch.int16)):
+            raise ValueError(f"{what}: target must be a 1-D float32 or int16 tensor on {self.device}")
+        if signal.numel() != target.numel():
+            raise ValueError(f"{what}: the recording has {signal.numel()} samples, target {target.numel()}")
+        if signal.dtype != target.dtype:          # the C rule for int16: (float)((double)s / 32767.0)
+            signal, target = ((t.double() / 32767.0).float() if t.dtype == torch.int16 else t for t in (signal, target))
+        align = 8 if signal.dtype == torch.int16 else 16
+
+        def aligned(t):
+            t = t.contiguous()
+            return t.clone() if t.data_ptr() % align else t
+        signal, target = aligned(signal), aligned(target)
+        d = self._coded_dims(what, batch)
+        if d.K < 1:
+            raise ValueError(f"{what}: the model has no knobs")
+        n, nwin = code.n, code.nwin
+        kn = torch.as_tensor(knobs).to(device=self.device, dtype=torch.float32)
+        if kn.dim() == 2 and int(kn.shape[1]) == d.K:
+            kn = kn.reshape(-1, 1, d.K)
+        elif not (kn.dim() == 3 and int(kn.shape[1]) in (1, nwin) and int(kn.shape[2]) == d.K):
+            raise ValueError(f"{what}: knobs must be [S, {d.K}] or [S, rows, {d.K}] with one row per setting, or one per window ({nwin} windows for {n} samples), "
+                             f"not {tuple(kn.shape)}")
+        kn = kn.contiguous().clone()
+        S = int(kn.shape[0])
+        if S < 1:
+            raise ValueError(f"{what}: no knob setting")
+        sizes = self.__dict__.setdefault("_multi_sizes", {})
+        if (d.B, S, self.compute_dtype) not in sizes:       # as fit_knobs: the size query carves every batch 1 .. B, once per (B, S, dtype)
+            sizes[(d.B, S, self.compute_dtype)] = int(self.lib.st_knob_multi_ws_bytes(C.byref(d), S))
+        need = sizes[(d.B, S, self.compute_dtype)]
+        if need <= 0:
+            raise RuntimeError(f"{what}: st_fit_knobs_supported refuses this geometry (T={d.T}, OT={d.OT}): the wide autoencoder geometries stay on the batched route")
+        if getattr(self, "_multi_ws", None) is None or self._multi_ws.numel() < need:
+            self._multi_ws = torch.zeros(need, dtype=torch.uint8, device=self.device)
+        fmt = _lib.PCM_S16 if signal.dtype == torch.int16 else _lib.PCM_F32
+        return d, signal, target, fmt, kn, S, n, nwin
+
+    def score_knobs(self, code, target, knobs, batch=None, per_window=False):
+        """J = mean log-cosh of (model output - target) of the recording behind `code` (encode_long) at S knob settings, in ONE C call (st_score_knobs_coded in
+        include/signaltrain_hip.h): per setting only the decoder forward, the frames GEMM and one overlap-add that keeps nothing but the loss partials run -- no
+        [S, n_out] output exists.  knobs: [S, K], or [S, nwin, K] for one row per window.  Returns loss [S] float64 on the device; per_window=True: (loss,
+        win_loss [S, nwin] float32), win_loss[s, w] window w's share of loss[s].  A recording of at most half a batch is stacked: rows of a batch are
+        (setting, window) pairs (st_knob_multi_plan).  The code must be valid (fit_knobs' checks; that the parameters have not changed is the caller's
+        precondition).  No host sync; self.ws is not written."""
+        d, signal, target, fmt, kn, S, n, nwin = self._multi_args("score_knobs", code, target, knobs, batch)
+        loss = torch.zeros(S, dtype=torch.float64, device=self.device)
+        win = torch.zeros(S, nwin, dtype=torch.float32, device=self.device) if per_window else None
+        self._call("st_score_knobs_coded", C.byref(d), _lib.ptr(self.params), _lib.ptr(code.code), fmt, C.c_void_p(signal.data_ptr()), C.c_void_p(target.data_ptr()), n,
+                   _lib.ptr(kn), int(kn.shape[1]), S, C.c_void_p(loss.data_ptr()), _lib.ptr(win), _lib.ptr(self._multi_ws), self._stream())
+        return (loss, win) if per_window else loss
+
+    def fit_knobs_multi(self, code, target, knobs, steps=50, lr=0.05, betas=(0.9, 0.999), eps=1e-8, batch=None, state=None, want_grads=False):
+        """fit_knobs from S starts at once, in ONE C call (st_fit_knobs_multi_coded): S independent Adam runs on the objective of fit_knobs, each with its own
+        knob rows, moments, loss history and gradient history, from the recording's code.  knobs: [S, K] or [S, nwin, K], the start values -- cloned; state:
+        (m, v, first_step) as a previous call returned it, so that calls chain (default: zeros and step 1), as fit_knobs.  Returns (knobs [S, ...] in the shape
+        given, loss_hist [steps, S] float64, (m, v, next_step)) and, with want_grads=True, grads [steps, S, rows, K] behind them.  A recording of at most half a
+        batch is stacked: rows of a batch are (setting, window) pairs (st_knob_multi_plan).  No host sync; self.ws is not written."""
+        d, signal, target, fmt, kn, S, n, nwin = self._multi_args("fit_knobs_multi", code, target, knobs, batch)
+        steps = int(steps)
+        rows = int(kn.shape[1])
+        if state is None:
+            m, v, first = torch.zeros_like(kn), torch.zeros_like(kn), 1
+        else:
+            m, v, first = state
+            m = m.to(device=self.device, dtype=torch.float32).reshape(S, rows, d.K).clone()
+            v = v.to(device=self.device, dtype=torch.float32).reshape(S, rows, d.K).clone()
+            first = int(first)
+        loss_hist = torch.zeros(max(steps, 0), S, dtype=torch.float64, device=self.device)
+        grads = torch.zeros(max(steps, 0), S, rows, d.K, dtype=torch.float32, device=self.device) if want_grads else None
+        self._call("st_fit_knobs_multi_coded", C.byref(d), _lib.ptr(self.params), _lib.ptr(code.code), fmt, C.c_void_p(signal.data_ptr()),
+                   C.c_void_p(target.data_ptr()), n, _lib.ptr(kn), rows, S, _lib.ptr(m), _lib.ptr(v), first, steps, float(lr), float(betas[0]), float(betas[1]),
+                   float(eps), C.c_void_p(loss_hist.data_ptr()), _lib.ptr(grads), _lib.ptr(self._multi_ws), self._stream())
+        shape = tuple(torch.as_tensor(knobs).shape)
+        res = (kn.reshape(shape), loss_hist, (m.reshape(shape), v.reshape(shape), first + steps))
+        return res + (grads,) if want_grads else res
+
     # ---------------------------------------------------------------- the step as one HIP graph
     def graph_capture(self, batch, lr_table, betas=(0.9, 0.999), eps=1e-8):
         """Capture st_train_step for `batch` windows into a HIP graph (st_graph_create).  The step counter and the learning rate

@@ -24,6 +24,7 @@ FIT_ROUTES = ("batched", "device")
 _warned_unsupported = False
 _warned_fit_unsupported = False
 _warned_sweep_unsupported = False
+_warned_search_unsupported = False
 
 
 
@@ -235,6 +236,82 @@ def fit_knobs(signal, target, model, chunk_size, out_chunk_size, steps=50, lr=0.
         with torch.no_grad():
             kn.clamp_(-0.5, 0.5)
     return kn.detach().cpu().numpy(), history
+
+
+def _logcosh_mean(y, t):
+    """mean log cosh(y - t) in float64 on y's device: the objective of fit_knobs on outputs that exist."""
+    a = (y.double() - t.double()).abs()
+    return float((a + torch.log1p(torch.exp(-2.0 * a)) - 0.6931471805599453).mean().item())
+
+
+def _never_worse(finals, final_losses, starts, start_losses):
+    """A fit that ended above its start (Adam overshoots on a short run) gives the start back: a search never returns worse than a candidate it scored."""
+    finals, final_losses = np.array(finals, dtype=np.float32), np.array(final_losses, dtype=np.float64)
+    worse = final_losses > start_losses
+    finals[worse] = starts[worse]
+    final_losses[worse] = start_losses[worse]
+    return finals, final_losses
+
+
+def search_knobs(signal, target, model, chunk_size, out_chunk_size, candidates, keep=8, steps=50, lr=0.05, batch_size=200, compand=False, route="device"):
+    """A search for the knob vector for which the model turns `signal` into `target`, where one fit from one start is only a local answer (the objective of
+    fit_knobs is not convex in the knobs): score every row of candidates [S, K], keep the `keep` lowest, fit those together for `steps` Adam steps and take the
+    winner.  Returns (best_knobs [K] float32, best_loss, finals [keep, K] float32, final_losses [keep]): finals in ascending order of the candidates' SCORED loss
+    (finals[0] grew from the best-scoring candidate), final_losses the objective at the fitted knobs, best the lowest of them.
+    route="device": the recording is encoded ONCE (StepEngine.encode_long), the candidates are scored in one call that keeps only the S losses
+    (StepEngine.score_knobs) and the kept ones are fitted in one call (StepEngine.fit_knobs_multi); a short recording fills the batch with (setting, window) rows.
+    route="batched", and a geometry st_fit_knobs_supported rejects (after one warning): predict_long and fit_knobs' batched route, candidate by candidate -- the
+    objective there counts the zero-padded tail of the last window, as fit_knobs' batched route does."""
+    global _warned_search_unsupported
+    if route not in FIT_ROUTES:
+        raise ValueError(f"search_knobs: route must be one of {FIT_ROUTES}, not {route!r}")
+    cand = np.ascontiguousarray(candidates, dtype=np.float32)
+    if cand.ndim != 2 or cand.shape[0] < 1:
+        raise ValueError(f"search_knobs: candidates must be [S, K] with S >= 1, not {cand.shape}")
+    keep = max(min(int(keep), cand.shape[0]), 1)
+    device = next(model.parameters()).device
+    signal = np.ascontiguousarray(signal, dtype=np.float32); target = np.ascontiguousarray(target, dtype=np.float32)
+    assert signal.shape == target.shape and signal.ndim == 1, (signal.shape, target.shape)
+    n = int(signal.shape[0])
+    nwin = 1 if n < chunk_size else -(-(n - chunk_size) // out_chunk_size) + 1
+    if route == "device":
+        bs = max(int(batch_size), 1)                                       # not clipped to the window count: a short recording is stacked into the batch
+        eng = model.engine(torch.empty((), dtype=torch.float32, device=device).expand(min(bs, nwin), chunk_size))      # shape and device only: nothing is read
+        if (eng.dims.L, eng.dims.y) != (chunk_size, out_chunk_size):
+            raise ValueError(f"search_knobs: chunk_size / out_chunk_size = {chunk_size} / {out_chunk_size}, the model has {eng.dims.L} / {eng.dims.y}")
+        if eng.fit_knobs_supported():
+            if compand:
+                from . import audio
+                signal = np.ascontiguousarray(audio.mu_compand(signal), dtype=np.float32); target = np.ascontiguousarray(audio.mu_compand(target), dtype=np.float32)
+            with torch.no_grad():
+                sig, tgt = torch.from_numpy(signal).to(device), torch.from_numpy(target).to(device)
+                code = eng.encode_long(sig, batch=min(bs, nwin))
+                scored = eng.score_knobs(code, tgt, torch.from_numpy(cand).to(device), batch=bs).cpu().numpy()
+                order = np.argsort(scored, kind="stable")[:keep]
+                finals = eng.fit_knobs_multi(code, tgt, torch.from_numpy(cand[order]).to(device), steps=int(steps), lr=lr, batch=bs)[0]
+                final_losses = eng.score_knobs(code, tgt, finals, batch=bs).cpu().numpy()
+            finals, final_losses = _never_worse(finals.cpu().numpy(), final_losses, cand[order], scored[order])
+            best = int(np.argmin(final_losses))
+            return finals[best].copy(), float(final_losses[best]), finals, final_losses
+        if not _warned_search_unsupported:
+            _warned_search_unsupported = True
+            warnings.warn(f"signaltrain_amd.search_knobs: route='device' does not run this geometry (T={eng.dims.T}, OT={eng.dims.OT}, K={eng.dims.K}: "
+                          "st_fit_knobs_supported); taking the batched route, candidate by candidate", RuntimeWarning, stacklevel=2)
+
+    def objective(k):          # the batched route's J: over the nwin * out_chunk_size window outputs, the tail behind the recording's end against zeros
+        y = predict_long(signal, k, model, chunk_size, out_chunk_size, compand=compand, batch_size=batch_size)
+        t = target
+        if compand:
+            from . import audio
+            t = np.ascontiguousarray(audio.mu_compand(target), dtype=np.float32)
+        return _logcosh_mean(torch.from_numpy(np.ascontiguousarray(y)), torch.from_numpy(t[chunk_size - out_chunk_size:][:y.shape[0]]))
+    scored = np.array([objective(k) for k in cand])
+    order = np.argsort(scored, kind="stable")[:keep]
+    finals = np.stack([fit_knobs(signal, target, model, chunk_size, out_chunk_size, steps=steps, lr=lr, init=cand[i], batch_size=batch_size, compand=compand)[0]
+                       for i in order]).astype(np.float32)
+    finals, final_losses = _never_worse(finals, np.array([objective(k) for k in finals]), cand[order], scored[order])
+    best = int(np.argmin(final_losses))
+    return finals[best].copy(), float(final_losses[best]), finals, final_losses
 
 
 def _fit_device(signal, target, model, chunk_size, out_chunk_size, steps, lr, init, batch_size, compand, grad_history, encode_once=False):
