@@ -374,6 +374,59 @@ size_t    st_predict_ws_bytes(const st_dims* d);
 int st_predict_long(const st_dims* d, const float* params, int fmt, const void* signal, long long n,
                     const float* knobs, long long knob_rows, float* out, void* ws, void* stream);
 
+/* Predict session: st_predict_long's inference fed block by block, `channels` signals in lockstep (st_predict_stream.h).  The model has no look-ahead -- output
+ * sample i belongs to input sample (L - y) + i -- so a session emits every output sample as soon as its window is complete and keeps only the samples no complete
+ * window has consumed yet.  That history stays on the device, the parameter-only head of the workspace is built once at open, and a batch's rows are (channel,
+ * window) pairs, so many channels fill a batch even at one window per push.
+ *   st_predict_stream   plain data in HOST memory, owned by the caller, written by open / push / reset only: samples received and emitted per channel, channels,
+ *               samples held, which history half is current, the closed flag, and the geometry, prec and B the session was opened with.
+ *   state       st_predict_stream_state_bytes(d, channels) = 2 * channels * L * sizeof(float) bytes on the device, 16-byte aligned: two history halves
+ *               [2][channels][L] float32 (float32 whatever the block format, so an int16 stream equals its float image bit for bit).  Need not be initialised.
+ *   ws          st_predict_stream_ws_bytes(d) bytes (>= st_predict_ws_bytes(d)) on the device, 16-byte aligned: [parameter-only head | one batch's workspace].
+ *               It belongs to the session from open to its last push: st_predict_stream_open builds the head (what st_predict_long builds once per call), the
+ *               pushes only read it.  That the parameters have not changed since open is the caller's precondition.
+ *   push        m new samples per channel, block[c][0 .. m) at pitch block_pitch (elements), ST_PCM_F32 or ST_PCM_S16 ((float)s / 32767.0f, as everywhere).  With
+ *               n0 samples received before the push, n1 = n0 + m after it, and Wc(n) = n < L ? 0 : (n - L) / y + 1 complete windows in n samples, a non-final push
+ *               computes windows Wc(n0) .. Wc(n1) - 1 of every channel and writes their y samples each, concatenated, to out[c][0 .. nw y) at pitch out_pitch.  A
+ *               final push (any m >= 0) also computes the one zero-padded last window where st_predict_windows(d, n1) > Wc(n1), clipped as st_predict_long clips
+ *               it: over its life a session emits exactly st_predict_out_samples(d, n) samples per channel, the ones st_predict_long gives for the concatenated
+ *               channel.  After a final push the session is closed until st_predict_stream_reset (host only: zero samples received, same geometry and channels).
+ *   plan        st_predict_stream_plan (host arithmetic only; the push uses the same function): out4 = {first window, window count, samples emitted per channel,
+ *               samples held afterwards} for a push of m at n_in samples received.  Held after a non-final push: [Wc(n1) y, n1), at most L - 1 samples
+ *               (L - y + (n1 - L) % y once n1 >= L); after a final push nothing.
+ *   alignment   a non-final push needs m % 4 == 0, so the held count and every window start stay multiples of four: every quad of the pair (history | block) is
+ *               one aligned access and none straddles the join.  block: 16-byte aligned (ST_PCM_S16: 8-byte), block_pitch >= m and % 4 == 0; out: 16-byte
+ *               aligned, out_pitch >= the emitted count and % 4 == 0.  Nothing at or past block[c] + m is read and nothing outside out[c][0 .. emitted) is written.
+ *   knobs       [knob_rows][K], knob_rows == 1 (all channels) or == channels (one setting per channel), held for every window of the push; NULL only for K == 0.
+ *               Finer automation means smaller pushes.
+ *   rows        a push that computes nw windows of C channels has C * nw rows; row r = c * nw + k is window Wc(n0) + k of channel c.  d->B is the most rows per
+ *               batch; a push with more rows runs its batches one after the other inside the call.  No allocation, no hipMemcpy, no host synchronisation, no float
+ *               atomics, no captured graph: the host struct is advanced by host arithmetic when the push is enqueued.
+ * Per batch: one staging launch (st_predict_long's, reading the pair; the knob rows always filled, per channel), st_predict_long's analysis GEMM, autoencoder
+ * forward and frames GEMM at this st_dims.prec, one overlap-add launch in st_predict_long's summation order with the residual from the pair.  After the last
+ * batch of a non-final push one carry launch copies the samples to keep into the other history half and the halves swap; it is the only launch of a push that
+ * completes no window.  Equal bits: a batch whose rows are the windows of one st_predict_long batch (same d->B, same row count) gives that batch's bits; an int16
+ * stream its float image's; knob_rows == 1 the row repeated.  Other partitions into pushes give other row counts per batch: equal to 1e-6 of max|y|, as between
+ * two batch sizes of st_predict_long.
+ * The fused autoencoder geometries only (st_predict_supported), at every ST_PREC_* level.  The size functions give 0 for bad or unsupported dims (state: also for
+ * channels < 1).
+ * Refused before any launch (ST_ERR_ARG, the rule in st_last_error(), naming the entry): bad or unsupported dims; dims, prec or B that differ from the ones the
+ * session was opened with; channels < 1 (or above 65535); a null pointer, named (knobs only where K > 0; block only where m > 0; out only where the plan emits
+ * something); m < 0 or m > 2^30; a non-final m % 4 != 0; an unknown fmt; knob_rows neither 1 nor channels; block_pitch < m or % 4 != 0; out_pitch below the
+ * emitted count or % 4 != 0; block misaligned; out, state or ws not 16-byte aligned; a push on a closed session. */
+typedef struct st_predict_stream {
+    long long received, emitted;        /* samples per channel so far */
+    int channels, held, half, closed;   /* held: samples [received - held, received) of every channel lie in history half `half` */
+    int L, N, H, T, OT, F, K, y, prec, B;
+} st_predict_stream;
+size_t st_predict_stream_state_bytes(const st_dims* d, int channels);
+size_t st_predict_stream_ws_bytes(const st_dims* d);
+int    st_predict_stream_plan(const st_dims* d, long long n_in, long long m, int final, long long out4[4]);
+int    st_predict_stream_open(const st_dims* d, const float* params, int channels, st_predict_stream* s, void* state, void* ws, void* stream);
+int    st_predict_stream_push(const st_dims* d, const float* params, st_predict_stream* s, int fmt, const void* block, long long m, long long block_pitch,
+                              int final, const float* knobs, long long knob_rows, float* out, long long out_pitch, void* state, void* ws, void* stream);
+int    st_predict_stream_reset(st_predict_stream* s);
+
 /* Knob fit on the device: the knob settings for which the model turns `signal` into `target` (predict.fit_knobs), every batch of every optimiser step enqueued by
  * ONE call.  Windows, lengths and formats are st_predict_long's: nwin = st_predict_windows(d, n); window w reads signal[w y, w y + L) with zeros from sample n on;
  * fmt (ST_PCM_F32 / ST_PCM_S16, an int16 sample converts as (float)((double)s / 32767.0)) applies to both recordings; target holds the same n samples, aligned with

@@ -29,6 +29,12 @@ class st_dims(C.Structure):
         d = st_dims(); C.memmove(C.byref(d), C.byref(self), C.sizeof(st_dims)); d.B = int(B); return d
 
 
+class st_predict_stream(C.Structure):
+    """Mirror of `struct st_predict_stream` (include/signaltrain_hip.h): a predict session's host-side counters."""
+    _fields_ = [("received", C.c_longlong), ("emitted", C.c_longlong)] + \
+               [(n, C.c_int) for n in ("channels", "held", "half", "closed", "L", "N", "H", "T", "OT", "F", "K", "y", "prec", "B")]
+
+
 _p = C.c_void_p
 _f = C.c_float
 _i = C.c_int
@@ -122,6 +128,12 @@ SIGNATURES = {
     "st_predict_supported": (_i, [_D]),
     "st_predict_ws_bytes": (C.c_size_t, [_D]),
     "st_predict_long": (_i, [_D, _p, _i, _p, C.c_longlong, _p, C.c_longlong, _p, _p, _p]),
+    "st_predict_stream_state_bytes": (C.c_size_t, [_D, _i]),
+    "st_predict_stream_ws_bytes": (C.c_size_t, [_D]),
+    "st_predict_stream_plan": (_i, [_D, C.c_longlong, C.c_longlong, _i, C.POINTER(C.c_longlong)]),
+    "st_predict_stream_open": (_i, [_D, _p, _i, C.POINTER(st_predict_stream), _p, _p, _p]),
+    "st_predict_stream_push": (_i, [_D, _p, C.POINTER(st_predict_stream), _i, _p, C.c_longlong, C.c_longlong, _i, _p, C.c_longlong, _p, C.c_longlong, _p, _p, _p]),
+    "st_predict_stream_reset": (_i, [C.POINTER(st_predict_stream)]),
     "st_fit_knobs_supported": (_i, [_D]),
     "st_fit_knobs_ws_bytes": (C.c_size_t, [_D]),
     "st_fit_knobs": (_i, [_D, _p, _i, _p, _p, C.c_longlong, _p, C.c_longlong, _p, _p, C.c_longlong, _i, _f, _f, _f, _f, _p, _p, _p, _p]),

@@ -25,6 +25,7 @@
 #include "st_feed_live.h"
 #include "st_feed_stream.h"
 #include "st_predict.h"
+#include "st_predict_stream.h"
 #include "st_decode.h"
 #include "st_fit.h"
 #include "st_multi.h"
@@ -2117,6 +2118,154 @@ extern "C" int st_predict_long(const st_dims* d, const float* params, int fmt, c
     ST_TRY(predict_prep(d, L, p, params, stream));
     return fmt == ST_PCM_S16 ? predict_batches(d, L, p, params, reinterpret_cast<const short*>(signal), n, knobs, knob_rows, out, n_out, ws, stream)
                              : predict_batches(d, L, p, params, reinterpret_cast<const float*>(signal), n, knobs, knob_rows, out, n_out, ws, stream);
+}
+
+// ------------------------------------------------------------------------------ predict session: inference fed block by block (st_predict_stream.h)
+// st_predict_long's batch -- its staging, forward and overlap-add -- on rows that are (channel, window) pairs, read from (history | block) instead of a resident
+// signal.  The workspace is st_predict_long's, [head | one batch's workspace]; the head is built by st_predict_stream_open and only read afterwards.  The schedule
+// (which windows a push completes, what it emits, what stays held) is host arithmetic in stream_plan, shared by st_predict_stream_plan and the push.
+static long long stream_wc(const st_dims* d, long long n) { return n < d->L ? 0 : (n - d->L) / d->y + 1; }      // complete windows in n samples
+static void stream_plan(const st_dims* d, long long n_in, long long m, int final, long long out4[4])
+{
+    const long long n1 = n_in + m, first = stream_wc(d, n_in), wc1 = stream_wc(d, n1);
+    out4[0] = first; out4[1] = wc1 - first; out4[2] = (wc1 - first) * d->y; out4[3] = n1 - wc1 * d->y;
+    if (final) {      // the zero-padded last window as well, clipped as st_predict_long clips it; nothing stays held
+        const long long n_out = n1 > (long long)d->L - d->y ? n1 - ((long long)d->L - d->y) : 0;
+        out4[1] = (n_out + d->y - 1) / d->y - first; out4[2] = n_out - first * d->y; out4[3] = 0;
+    }
+}
+extern "C" int st_predict_stream_plan(const st_dims* d, long long n_in, long long m, int final, long long out4[4])
+{
+    ST_TRY(check_dims(d));
+    ST_REQ(out4, "st_predict_stream_plan: null pointer (out4)");
+    ST_REQ(n_in >= 0 && m >= 0, "st_predict_stream_plan: n_in = %lld and m = %lld must not be negative", n_in, m);
+    stream_plan(d, n_in, m, final, out4);
+    return ST_OK;
+}
+extern "C" size_t st_predict_stream_state_bytes(const st_dims* d, int channels)
+{
+    return (predict_ok(d) && channels >= 1) ? (size_t)2 * channels * d->L * sizeof(float) : 0;
+}
+extern "C" size_t st_predict_stream_ws_bytes(const st_dims* d) { return st_predict_ws_bytes(d); }
+static const int STREAM_MAX_CHANNELS = 65535;      // the carry kernel's grid.y
+extern "C" int st_predict_stream_open(const st_dims* d, const float* params, int channels, st_predict_stream* s, void* state, void* ws, void* stream)
+{
+    Layout L; ST_TRY(make_layout(d, &L));
+    ST_REQ(!ae_is_wide(d), "st_predict_stream_open: not supported for the wide autoencoder geometries (T = %d > 32 or OT = %d > 16): st_predict_supported", d->T, d->OT);
+    ST_REQ(channels >= 1 && channels <= STREAM_MAX_CHANNELS, "st_predict_stream_open: channels = %d must lie in 1 .. %d", channels, STREAM_MAX_CHANNELS);
+    ST_REQ(params, "st_predict_stream_open: null pointer (params)"); ST_REQ(s, "st_predict_stream_open: null pointer (s)");
+    ST_REQ(state, "st_predict_stream_open: null pointer (state)"); ST_REQ(ws, "st_predict_stream_open: null pointer (ws)");
+    ST_REQ((reinterpret_cast<uintptr_t>(state) & 15) == 0, "st_predict_stream_open: state must be 16-byte aligned");
+    ST_REQ((reinterpret_cast<uintptr_t>(ws) & 15) == 0, "st_predict_stream_open: ws must be 16-byte aligned");
+    *s = st_predict_stream{};
+    s->channels = channels;
+    s->L = d->L; s->N = d->N; s->H = d->H; s->T = d->T; s->OT = d->OT; s->F = d->F; s->K = d->K; s->y = d->y; s->prec = d->prec; s->B = d->B;
+    PredictWS p; predict_carve(d, ws, &p);
+    prof_mark("begin", stream);
+    return predict_prep(d, L, p, params, stream);
+}
+extern "C" int st_predict_stream_reset(st_predict_stream* s)
+{
+    ST_REQ(s, "st_predict_stream_reset: null pointer (s)");
+    ST_REQ(s->channels >= 1, "st_predict_stream_reset: the session was never opened (channels = %d)", s->channels);
+    s->received = s->emitted = 0; s->held = 0; s->half = 0; s->closed = 0;
+    return ST_OK;
+}
+// One push's batches: the launches of predict_batches for !fit && !cj, with the stream's two streamers around them.
+template <typename T>
+static int stream_batches(const st_dims* d, const Layout& L, const PredictWS& p, const float* params, const sts::Src& src, int channels,
+                          const long long plan[4], const float* knobs, long long knob_rows, float* out, long long out_pitch, void* ws, void* stream)
+{
+    const float* Wr = params + L.offs[0]; const float* Wi = params + L.offs[1];
+    const float* ae_m = params + L.offs[4]; const float* ae_p = params + L.offs[22];
+    const bool g16 = stft_family(d, GEMM_ANALYSIS, SGP_PADDED | SGP_G16) == GF_G16, img = predict_img(d);      // as predict_batches
+    const long long rows = plan[1] * channels;
+    for (long long r0 = 0; r0 < rows; r0 += d->B) {
+        st_dims q = *d; q.B = (int)(rows - r0 < d->B ? rows - r0 : d->B);
+        WS w; carve(&q, L, reinterpret_cast<char*>(ws) + p.head_bytes, &w);
+        w.g16 = g16;
+        w.Sfold = p.Sfold; w.SfoldT = p.SfoldT; w.Sfold16 = p.Sfold16; w.SfoldT16 = p.SfoldT16; w.W16 = p.W16;
+        w.pl_W = p.pl_W; w.pl_Sfold = p.pl_Sfold; w.pl_SfoldT = p.pl_SfoldT;
+        const stg::RowMap map = stg::live_frames(q.T, q.H, q.N, q.N, q.L);
+        sts::StageArgs a;
+        a.s = src; a.first = plan[0]; a.nw = plan[1]; a.r0 = r0; a.y = q.y; a.L = q.L; a.pad = q.N; a.nb = q.B;
+        a.xp = w.xp; a.xp16 = w.xp16; a.ht = g16 ? gemm_ht(q.prec) : 0;
+        a.nbx = ((q.L + 2 * q.N) / 4 + 255) / 256; a.n_pad = a.nbx * q.B;
+        a.mag = w.mag; a.phs = w.phs; a.T = q.T; a.F = q.F; a.t_lo = map.t_lo; a.Tv = map.Tv; a.n_dead = q.B * (q.T - map.Tv);
+        a.knob_src = knobs; a.knob_stride = knob_rows == 1 ? 0 : q.K; a.knobs = p.knobs; a.K = q.K; a.n_kn = q.K > 0 ? (q.B * q.K + 255) / 256 : 0;
+        const float* kn = q.K == 0 ? params : p.knobs;      // K == 0: any resident float (call_begin)
+        hipLaunchKernelGGL(sts::stream_stage_kernel<T>, dim3(a.n_pad + a.n_dead + a.n_kn), dim3(256), 0, st_stream(stream), a);
+        ST_LAUNCHED("stream_stage");
+        ST_TRY(stft_gemm(step_stft_plan(&q, w, GEMM_ANALYSIS, Wr, Wi), GemmOut{nullptr, nullptr, w.mag, w.phs, nullptr, nullptr}, stream));
+        ST_TRY(ae_fwd_body(&q, L, w.mag, w.phs, kn, ae_m, ae_p, w.mag_hat, w.phs_hat, w.AA, w.reg_p, nullptr, stream, g16 ? w.AA16 : nullptr, false, nullptr,
+                           img ? p.img : nullptr));
+        ST_TRY(stft_gemm(step_stft_plan(&q, w, GEMM_FRAMES), slabs_at(w.frs), stream));
+        const int ns = frame_slabs(&q);
+        const dim3 grid((q.y / 4 + 255) / 256, q.B);
+        const size_t slab = (size_t)q.B * q.OT * q.N;
+        const bool three = (q.N + q.H - 1) / q.H <= 3;      // as predict_batches
+        with_bool(three, [&](auto NF3) { with_slabs(ns, [&](auto NS) {
+            hipLaunchKernelGGL((sts::stream_ola_kernel<T, NS(), NF3() ? 3 : 0>), grid, dim3(256), 0, st_stream(stream),
+                               w.frs, slab, src, out, out_pitch, plan[0], plan[1], r0, plan[2], q.L, q.N, q.H, q.OT, q.y); }); });
+        ST_LAUNCHED("stream_ola");
+    }
+    return ST_OK;
+}
+extern "C" int st_predict_stream_push(const st_dims* d, const float* params, st_predict_stream* s, int fmt, const void* block, long long m, long long block_pitch,
+                                      int final, const float* knobs, long long knob_rows, float* out, long long out_pitch, void* state, void* ws, void* stream)
+{
+    Layout L; ST_TRY(make_layout(d, &L));
+    ST_REQ(!ae_is_wide(d), "st_predict_stream_push: not supported for the wide autoencoder geometries (T = %d > 32 or OT = %d > 16): st_predict_supported", d->T, d->OT);
+    ST_REQ(s, "st_predict_stream_push: null pointer (s)");
+    ST_REQ(s->channels >= 1 && s->channels <= STREAM_MAX_CHANNELS, "st_predict_stream_push: channels = %d: the session was not opened by st_predict_stream_open", s->channels);
+    ST_REQ(s->L == d->L && s->N == d->N && s->H == d->H && s->T == d->T && s->OT == d->OT && s->F == d->F && s->K == d->K && s->y == d->y,
+           "st_predict_stream_push: dims differ from the ones the session was opened with (L = %d, N = %d, H = %d, K = %d at open)", s->L, s->N, s->H, s->K);
+    ST_REQ(s->prec == d->prec, "st_predict_stream_push: prec = %d differs from the one the session was opened with (%d)", d->prec, s->prec);
+    ST_REQ(s->B == d->B, "st_predict_stream_push: B = %d differs from the one the session was opened with (%d)", d->B, s->B);
+    ST_REQ(!s->closed, "st_predict_stream_push: the session is closed (a final push came before): st_predict_stream_reset");
+    ST_REQ(params, "st_predict_stream_push: null pointer (params)");
+    ST_REQ(knobs || d->K == 0, "st_predict_stream_push: null pointer (knobs, K = %d)", d->K);
+    ST_REQ(state, "st_predict_stream_push: null pointer (state)"); ST_REQ(ws, "st_predict_stream_push: null pointer (ws)");
+    ST_REQ(m >= 0 && m <= (1ll << 30), "st_predict_stream_push: m = %lld must lie in 0 .. 2^30", m);
+    ST_REQ(final || m % 4 == 0, "st_predict_stream_push: m = %lld of a non-final push must be a multiple of 4", m);
+    ST_REQ(fmt == ST_PCM_F32 || fmt == ST_PCM_S16, "st_predict_stream_push: fmt = %d is neither ST_PCM_F32 nor ST_PCM_S16", fmt);
+    ST_REQ(knob_rows == 1 || knob_rows == s->channels, "st_predict_stream_push: knob_rows = %lld must be 1 or the channel count (%d)", knob_rows, s->channels);
+    ST_REQ(block || m == 0, "st_predict_stream_push: null pointer (block, m = %lld)", m);
+    ST_REQ(block_pitch >= m && block_pitch % 4 == 0, "st_predict_stream_push: block_pitch = %lld must be a multiple of 4 and at least m = %lld", block_pitch, m);
+    const long long n0 = s->received;
+    ST_REQ(n0 >= 0 && s->held >= 0 && s->held < d->L && s->held <= n0 && n0 % 4 == 0 && s->held % 4 == 0 && (s->half == 0 || s->half == 1),
+           "st_predict_stream_push: the session's counters are inconsistent (received = %lld, held = %d)", n0, s->held);
+    long long plan[4]; stream_plan(d, n0, m, final, plan);
+    ST_REQ(s->held == n0 - plan[0] * d->y, "st_predict_stream_push: the session's counters are inconsistent (received = %lld, held = %d)", n0, s->held);
+    ST_REQ(out || plan[2] == 0, "st_predict_stream_push: null pointer (out, %lld samples per channel to emit)", plan[2]);
+    ST_REQ(out_pitch >= plan[2] && out_pitch % 4 == 0, "st_predict_stream_push: out_pitch = %lld must be a multiple of 4 and at least the emitted count (%lld)", out_pitch, plan[2]);
+    const uintptr_t ba = fmt == ST_PCM_S16 ? 7 : 15;
+    ST_REQ((reinterpret_cast<uintptr_t>(block) & ba) == 0, "st_predict_stream_push: block must be %d-byte aligned", (int)ba + 1);
+    ST_REQ((reinterpret_cast<uintptr_t>(out) & 15) == 0, "st_predict_stream_push: out must be 16-byte aligned");
+    ST_REQ((reinterpret_cast<uintptr_t>(state) & 15) == 0, "st_predict_stream_push: state must be 16-byte aligned");
+    ST_REQ((reinterpret_cast<uintptr_t>(ws) & 15) == 0, "st_predict_stream_push: ws must be 16-byte aligned");
+    const size_t half = (size_t)s->channels * d->L;
+    float* hist = reinterpret_cast<float*>(state);
+    sts::Src src{hist + s->half * half, block, n0 - s->held, n0, m, block_pitch, d->L};
+    prof_mark("begin", stream);
+    if (plan[1] > 0) {
+        PredictWS p; predict_carve(d, ws, &p);
+        ST_TRY(fmt == ST_PCM_S16 ? stream_batches<short>(d, L, p, params, src, s->channels, plan, knobs, knob_rows, out, out_pitch, ws, stream)
+                                 : stream_batches<float>(d, L, p, params, src, s->channels, plan, knobs, knob_rows, out, out_pitch, ws, stream));
+    }
+    if (!final && m > 0) {      // what no complete window has consumed, to the other half; a final push keeps nothing
+        const int held1 = (int)plan[3];
+        if (held1 > 0) {
+            const dim3 grid((held1 / 4 + 255) / 256, s->channels);
+            float* next = hist + (s->half ^ 1) * half;
+            if (fmt == ST_PCM_S16) hipLaunchKernelGGL(sts::stream_carry_kernel<short>, grid, dim3(256), 0, st_stream(stream), src, next, n0 + m - held1, held1);
+            else hipLaunchKernelGGL(sts::stream_carry_kernel<float>, grid, dim3(256), 0, st_stream(stream), src, next, n0 + m - held1, held1);
+            ST_LAUNCHED("stream_carry");
+        }
+        s->half ^= 1;
+    }
+    s->received = n0 + m; s->emitted += plan[2]; s->held = (int)plan[3]; s->closed = final ? 1 : 0;
+    return ST_OK;
 }
 
 // ------------------------------------------------------------------------------ knob fit on the device (st_fit.h)

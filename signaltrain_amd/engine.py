@@ -79,6 +79,108 @@ class RecordingCode:
         self.code, self.signal, self.n, self.nwin, self.geometry, self.compute_dtype = code, signal, int(n), int(nwin), tuple(geometry), compute_dtype
 
 
+_warned_channels_unsupported = False
+
+
+class PredictStream:
+    """A predict session of a StepEngine (StepEngine.open_stream; st_predict_stream_* in include/signaltrain_hip.h): C channels fed block by block in
+    lockstep.  push() enqueues and returns device tensors; nothing synchronises with the host.  The parameter-only head of the workspace is built at open and
+    rebuilt by refresh() -- which push() calls by itself when the engine has taken a train step since; after any other change of engine.params call refresh()."""
+
+    def __init__(self, engine, channels=1, batch=None):
+        self.engine, self.channels = engine, int(channels)
+        B = int(batch or engine.max_batch)
+        if B < 1 or self.channels < 1:
+            raise ValueError(f"open_stream: channels = {channels}, batch = {B}")
+        d = engine.dims.with_batch(B)
+        d.prec, d.loss_scale, d.clip_all = _lib.PREC[engine.compute_dtype], engine.loss_scale, int(engine.clip_all)
+        self.dims = d
+        lib = engine.lib
+        if not lib.st_predict_supported(C.byref(d)):
+            raise RuntimeError(f"open_stream: st_predict_supported refuses this geometry (T={d.T}, OT={d.OT}): the wide autoencoder geometries have no "
+                               "predict session; predict_channels falls back to forward() batch by batch")
+        self.state = torch.empty(int(lib.st_predict_stream_state_bytes(C.byref(d), self.channels)), dtype=torch.uint8, device=engine.device)
+        self.ws = torch.zeros(int(lib.st_predict_stream_ws_bytes(C.byref(d))), dtype=torch.uint8, device=engine.device)
+        self.s = _lib.st_predict_stream()
+        self._open(self.s)
+
+    def _open(self, s):
+        e = self.engine
+        e._call("st_predict_stream_open", C.byref(self.dims), _lib.ptr(e.params), self.channels, C.byref(s), _lib.ptr(self.state), _lib.ptr(self.ws), e._stream())
+        self._built_at = e.step_count
+
+    def reopen(self):
+        """st_predict_stream_open again on the same tensors: zero samples received and the head rebuilt from the engine's current parameters."""
+        self._open(self.s)
+
+    def refresh(self):
+        """Rebuild the parameter-only head from the engine's current parameters; the session's samples and counters stay."""
+        self._open(_lib.st_predict_stream())
+
+    received = property(lambda self: int(self.s.received), doc="samples per channel pushed so far")
+    emitted = property(lambda self: int(self.s.emitted), doc="samples per channel emitted so far")
+    pending = property(lambda self: int(self.s.held), doc="samples per channel held for windows still incomplete")
+    closed = property(lambda self: bool(self.s.closed))
+
+    def reset(self):
+        """Back to zero samples received (host only); same geometry, channels, workspace."""
+        _lib.check(self.engine.lib.st_predict_stream_reset(C.byref(self.s)), "st_predict_stream_reset")
+
+    def plan(self, m, final=False):
+        """(first window, windows, samples emitted per channel, samples held afterwards) of a push of m samples now: st_predict_stream_plan."""
+        out4 = (C.c_longlong * 4)()
+        _lib.check(self.engine.lib.st_predict_stream_plan(C.byref(self.dims), self.s.received, int(m), int(bool(final)), out4), "st_predict_stream_plan")
+        return tuple(int(v) for v in out4)
+
+    def push(self, block, knobs, final=False, out=None):
+        """block: [C, m] (or 1-D for C == 1) float32 / int16 tensor on the engine's device, m % 4 == 0 unless final; knobs: [K] / [1, K] (all channels) or
+        [C, K]; out: a float32 device tensor [C, >= emitted] (1-D for a 1-D block) with 16-byte aligned rows to write into.  Returns the [C, emitted]
+        (1-D for a 1-D block) float32 device tensor this push completes -- possibly empty.  No host sync."""
+        e, d, Cn = self.engine, self.dims, self.channels
+        if self.s.closed:
+            raise RuntimeError("PredictStream.push: the session is closed (a final push came before): reset()")
+        if not (torch.is_tensor(block) and block.device == e.device and block.dtype in (torch.float32, torch.int16) and block.dim() in (1, 2)):
+            raise ValueError(f"PredictStream.push: block must be a [C, m] (or 1-D) float32 or int16 tensor on {e.device}")
+        flat = block.dim() == 1
+        if flat:
+            block = block.reshape(1, -1)
+        if block.shape[0] != Cn or (flat and Cn != 1):
+            raise ValueError(f"PredictStream.push: block has {block.shape[0]} channels, the session {Cn}")
+        m = int(block.shape[1])
+        if not final and m % 4:
+            raise ValueError(f"PredictStream.push: m = {m} of a non-final push must be a multiple of 4")
+        align = 8 if block.dtype == torch.int16 else 16
+        pitch = (m + 3) // 4 * 4 if Cn == 1 else int(block.stride(0))
+        if m and (block.stride(1) != 1 or pitch < m or pitch % 4 or block.data_ptr() % align):      # a view the kernels cannot read as aligned quads: one copy
+            pitch = (m + 3) // 4 * 4
+            copy = torch.empty(Cn, pitch, dtype=block.dtype, device=e.device)
+            copy[:, :m] = block
+            block = copy
+        _, _, emit, _ = self.plan(m, final)
+        opitch = (emit + 3) // 4 * 4
+        if out is None:
+            res = torch.empty(Cn, opitch, dtype=torch.float32, device=e.device)
+        else:
+            res = out.reshape(1, -1) if out.dim() == 1 else out
+            if not (out.dtype == torch.float32 and out.device == e.device and out.dim() == (1 if flat else 2) and res.shape[0] == Cn and res.shape[1] >= emit
+                    and (res.stride(1) == 1 or res.shape[1] <= 1) and res.data_ptr() % 16 == 0 and (Cn == 1 or (res.stride(0) % 4 == 0 and res.stride(0) >= emit))):
+                raise ValueError(f"PredictStream.push: out must be a float32 [C, >= {emit}] tensor on {e.device} with unit sample stride and 16-byte aligned rows")
+            opitch = opitch if Cn == 1 else int(res.stride(0))
+        kn, rows = None, 1
+        if d.K:
+            kn = torch.as_tensor(knobs).to(device=e.device, dtype=torch.float32).reshape(-1, d.K).contiguous()
+            rows = int(kn.shape[0])
+            if rows not in (1, Cn):
+                raise ValueError(f"PredictStream.push: knobs has {rows} rows: one row, or one per channel ({Cn})")
+        if e.step_count != self._built_at:
+            self.refresh()
+        e._call("st_predict_stream_push", C.byref(d), _lib.ptr(e.params), C.byref(self.s), _lib.PCM_S16 if block.dtype == torch.int16 else _lib.PCM_F32,
+                C.c_void_p(block.data_ptr()) if m else None, m, pitch, int(bool(final)), _lib.ptr(kn), rows,
+                C.c_void_p(res.data_ptr()) if emit else None, opitch, _lib.ptr(self.state), _lib.ptr(self.ws), e._stream())
+        res = res[:, :emit]
+        return res.reshape(-1) if flat else res
+
+
 def workspace_bytes_upto(lib, dims, max_batch):
     """Bytes of ONE workspace that serves every batch of 1 .. max_batch windows at every arithmetic level and clip scope: st_workspace_bytes_max (the exact
     st_workspace_bytes is a function of all three and is monotonic in none of them: INTEGRATION.md "Sizing the workspace")."""
@@ -530,6 +632,53 @@ class StepEngine:
             self._call("st_predict_long", C.byref(d), _lib.ptr(self.params), _lib.PCM_S16 if signal.dtype == torch.int16 else _lib.PCM_F32,
                        C.c_void_p(signal.data_ptr()), n, _lib.ptr(kn), rows, C.c_void_p(out.data_ptr()), _lib.ptr(self._predict_ws), self._stream())
         return out[:n_out]
+
+    # ---------------------------------------------------------------- predict session: inference fed block by block
+    def open_stream(self, channels=1, batch=None):
+        """A predict session (st_predict_stream_* in include/signaltrain_hip.h): `channels` signals fed in lockstep block by block, every output sample
+        emitted as soon as its window is complete.  batch: most (channel, window) rows per internal batch (default max_batch).  The session owns its history
+        and workspace tensors, sized once here; self.ws and predict_long's workspace are not written.  RuntimeError on a geometry st_predict_supported rejects."""
+        return PredictStream(self, channels, batch)
+
+    def predict_channels(self, signal_2d, knobs, out=None, batch=None):
+        """A resident [C, n] recording (float32 or int16) through the model, all channels in one session: one open_stream plus one final push.  knobs: [K] or
+        [1, K] (all channels) or [C, K] (one setting per channel).  Returns [C, n - (L - y)] float32 on the device: row c is what predict_long gives for channel
+        c, up to the order of the batches (1e-6).  On a geometry st_predict_supported rejects: one RuntimeWarning, then forward() window batch by window batch."""
+        if not (torch.is_tensor(signal_2d) and signal_2d.dim() == 2 and signal_2d.shape[0] >= 1 and signal_2d.device == self.device
+                and signal_2d.dtype in (torch.float32, torch.int16)):
+            raise ValueError(f"predict_channels: signal must be a [C, n] float32 or int16 tensor on {self.device}")
+        if self.predict_supported():
+            key = (int(signal_2d.shape[0]), int(batch or self.max_batch), self.compute_dtype)
+            kept = getattr(self, "_channel_stream", None)       # the last call's session: its history and workspace serve again, opened anew
+            if kept is None or kept[0] != key:
+                self._channel_stream = kept = (key, self.open_stream(key[0], key[1]))
+            else:
+                kept[1].reopen()
+            return kept[1].push(signal_2d, knobs, final=True, out=out)
+        global _warned_channels_unsupported
+        if not _warned_channels_unsupported:
+            _warned_channels_unsupported = True
+            import warnings
+            warnings.warn(f"signaltrain_amd: predict_channels does not run this geometry in a session (T={self.dims.T}, OT={self.dims.OT}: st_predict_supported); "
+                          "taking the batched route, channel by channel", RuntimeWarning, stacklevel=2)
+        C_, n = int(signal_2d.shape[0]), int(signal_2d.shape[1])
+        L, y, K = self.dims.L, self.dims.y, self.dims.K
+        n_out = max(n - (L - y), 0)
+        sig = signal_2d.float() / 32767.0 if signal_2d.dtype == torch.int16 else signal_2d
+        nwin = 1 if n < L else -(-(n - L) // y) + 1
+        kn = torch.as_tensor(knobs).to(device=self.device, dtype=torch.float32).reshape(-1, K) if K else torch.zeros(1, 0, device=self.device)
+        if kn.shape[0] not in (1, C_):
+            raise ValueError(f"predict_channels: knobs has {kn.shape[0]} rows: one row, or one per channel ({C_})")
+        res = torch.empty(C_, n_out, dtype=torch.float32, device=self.device) if out is None else out
+        bs = min(int(batch or self.max_batch), self.max_batch)
+        for c in range(C_ if n_out else 0):
+            padded = torch.zeros(L + (nwin - 1) * y, dtype=torch.float32, device=self.device)
+            padded[:n] = sig[c]
+            xw = padded.unfold(0, L, y)
+            kc = kn[c if kn.shape[0] > 1 else 0].reshape(1, K)
+            yc = torch.cat([self.forward(xw[b0:b0 + bs].contiguous(), kc.expand(min(bs, nwin - b0), K).contiguous())[0].reshape(-1) for b0 in range(0, nwin, bs)])
+            res[c, :n_out] = yc[:n_out]
+        return res[:, :n_out]
 
     # ---------------------------------------------------------------- encode once, decode at any knob setting
     def decode_supported(self):

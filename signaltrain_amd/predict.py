@@ -137,6 +137,41 @@ def _predict_device(signal, knobs_nn, model, chunk_size, out_chunk_size, device,
     return y.cpu().numpy()
 
 
+def predict_stream(blocks, knobs, model, chunk_size, out_chunk_size, device=None, batch_size=200):
+    """predict_long on audio that arrives block by block: a generator over an iterable of blocks -- numpy arrays or tensors, [m] (one channel) or [C, m]
+    (C channels in lockstep), float32 or int16 -- that yields what each block completes (StepEngine.open_stream / PredictStream.push): every output sample as
+    soon as its window is whole, possibly none for a block.  The last block of the iterable is pushed as the final one (it also emits the zero-padded last
+    window, clipped); every other block needs m % 4 == 0.  Over the iterable the outputs concatenate to predict_long's for the concatenated blocks, len - (chunk_size -
+    out_chunk_size) samples per channel.  knobs: [K] or [C, K], or a callable block_index -> knobs evaluated per block (knob automation at block rate).
+    A numpy block yields a numpy array, a tensor block a device tensor (no host sync then).  batch_size: most (channel, window) rows per internal batch."""
+    device = torch.device(device) if device is not None else next(model.parameters()).device
+    eng = model.engine(torch.empty((), dtype=torch.float32, device=device).expand(max(int(batch_size), 1), chunk_size))      # shape and device only: nothing is read
+    if (eng.dims.L, eng.dims.y) != (chunk_size, out_chunk_size):
+        raise ValueError(f"predict_stream: chunk_size / out_chunk_size = {chunk_size} / {out_chunk_size}, the model has {eng.dims.L} / {eng.dims.y}")
+    session, held, index = None, None, 0
+
+    def push(block, final):
+        nonlocal session, index
+        host = not torch.is_tensor(block)
+        t = torch.from_numpy(np.ascontiguousarray(block if np.asarray(block).dtype == np.int16 else np.asarray(block, dtype=np.float32))) if host else block.detach()
+        t = t.to(device)
+        t = t if t.dtype == torch.int16 else t.float()
+        if session is None:
+            session = eng.open_stream(1 if t.dim() == 1 else int(t.shape[0]), batch=max(int(batch_size), 1))
+        kn = knobs(index) if callable(knobs) else knobs
+        index += 1
+        with torch.no_grad():
+            y = session.push(t, torch.as_tensor(np.asarray(kn, dtype=np.float32), device=device), final=final)
+        return y.cpu().numpy() if host else y
+
+    for block in blocks:
+        if held is not None:
+            yield push(held, False)
+        held = block
+    if held is not None:
+        yield push(held, True)
+
+
 def predict_sweep(signal, knob_settings, model, chunk_size, out_chunk_size, sr=44100, effect=None, device=None, compand=False,
                   batch_size=200, verbose=False, route="device"):
     """predict_long at S knob settings: knob_settings is [S, K], or [S, nwin, K] for one row per window.  Returns [S, len(signal) - (chunk_size -
