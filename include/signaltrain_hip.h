@@ -541,6 +541,41 @@ int    st_fit_knobs_multi_coded(const st_dims* d, const float* params, const voi
                                 double* loss_hist /* device, [steps][n_settings] */, float* grad_hist /* device, [steps][n_settings][knob_rows][K], may be NULL */,
                                 void* ws, void* stream);
 
+/* ---- a folder of recordings in one call: st_eval_pool (csrc/st_eval_pool.h) ----------------------------------------------------
+ * Reporting a model on a SignalTrain test set: every file of the folder (input_N_.wav / target_N_<effect>__k1__k2....wav, datasets.py:64-259) WHOLE through the
+ * network at the knob setting in its name (utils/predict_long.py:30-79 per file), and the error per file.  The folder is the pool the device feeds keep
+ * (st_file_feed): pool_x / pool_y, the files' audio concatenated (fmt as there), file_off / file_len (device int64, in samples) and one knob row per file.
+ * Batch rows are (file, window) pairs: row r is window r - win_off[f] of file f, win_off[f] <= r < win_off[f + 1] (file-major, windows ascending), so short clips
+ * share a batch of up to d->B rows and a long file spans several.  Windows of a file of `len` samples: st_predict_windows(d, len) if len > L - y, else 0 (no
+ * output sample, no row).  st_eval_pool_rows is host arithmetic: it returns the total and, if win_off_host != NULL, fills the prefix sums [nfiles + 1] the
+ * caller uploads as win_off (0 for bad dims, a null file_len_host or nfiles < 1).
+ *
+ * One call enqueues every batch: the parameter-only head of the workspace once (as st_predict_long), then per batch the forward at st_dims.prec (every level).
+ * No allocation, no hipMemcpy, no host synchronisation; parameters and pools are only read.
+ *   out    (may be NULL: the score form) pool-shaped, [pool_samples]: the prediction for output sample i of file f at out[file_off[f] + (L - y) + i] --
+ *          time-aligned with the input (predict_long.py:222-223) -- clipped at the file's end; the first min(L - y, len) samples of every file's span are
+ *          written as 0.  Every sample of out inside some file's span is written by the call: out needs no initialisation; what lies between spans is not touched.
+ *   stats  (NULL iff pool_y == NULL: predict only) device double [nfiles][ST_POOL_STATS], with e = y_hat - t over the file's n_out = max(len - (L - y), 0)
+ *          output samples:  n_out, sum log cosh e, sum |e|, sum e^2, max |e|, sum t^2, sum y_hat^2, 0.  Per-sample terms and the sums of 256 samples are
+ *          float32 (st_ola_loss's formula and tree), everything above that double in ascending row order.  Every row of stats is written by the call (all
+ *          zeros for a file without a window): no initialisation.  No float atomics; a repeated call repeats its bits.
+ * file_off need not be a multiple of four (such files are read and written sample by sample where a 16-byte access would be misaligned: same values).  Whatever
+ * the tables hold, no address outside [0, pool_samples) of the pools and of out is formed (offsets and lengths are clamped, as st_file_feed clamps).
+ * ws: st_eval_pool_ws_bytes(d) bytes (>= st_predict_ws_bytes(d); 0 for bad or unsupported dims), 16-byte aligned.
+ * Refused before any launch (ST_ERR_ARG, the rule in st_last_error()): bad dims, dims st_eval_pool_supported rejects (= st_predict_supported: the wide
+ * autoencoder geometries), a null required pointer (named), an unknown fmt, nfiles < 1, total_rows < 0, pool_samples < 1, stats and pool_y not both null or both
+ * given, out and stats both null, out / stats / ws not 16-byte aligned, pools not 16-byte aligned (int16: 8-byte), a batch whose offsets would exceed the
+ * kernels' 32-bit element offsets.  total_rows == 0 returns ST_OK and writes only the zero spans and the zero statistics. */
+enum { ST_POOL_STATS = 8 };  /* per file: n_out, S logcosh(e), S |e|, S e^2, max |e|, S t^2, S y_hat^2, 0 */
+int       st_eval_pool_supported(const st_dims* d);              /* = st_predict_supported */
+long long st_eval_pool_rows(const st_dims* d, const long long* file_len_host, int nfiles, long long* win_off_host /* [nfiles+1], may be NULL */);
+size_t    st_eval_pool_ws_bytes(const st_dims* d);               /* >= st_predict_ws_bytes(d); 0 for bad / unsupported dims */
+int st_eval_pool(const st_dims* d, const float* params, int fmt, const void* pool_x, const void* pool_y /* NULL: predict only */,
+                 const long long* file_off, const long long* file_len, const long long* win_off /* device */, int nfiles,
+                 long long total_rows, long long pool_samples, const float* file_knobs /* [nfiles][K]; NULL iff K == 0 */,
+                 double* stats /* device [nfiles][ST_POOL_STATS]; NULL iff pool_y == NULL */, float* out /* [pool_samples], may be NULL */,
+                 void* ws, void* stream);
+
 /* Data-parallel split of st_loss_backward.  After p1 the gradients of the synthesis bases and both
  * autoencoders (grads[offs[2]..end)) are final: all-reduce them while p2 computes the analysis
  * weight gradient (rows [0,F) of tensors 0 and 1) and the loss scalars. */

@@ -147,6 +147,10 @@ SIGNATURES = {
     "st_knob_multi_ws_bytes": (C.c_size_t, [_D, _i]),
     "st_score_knobs_coded": (_i, [_D, _p, _p, _i, _p, _p, C.c_longlong, _p, C.c_longlong, _i, _p, _p, _p, _p]),
     "st_fit_knobs_multi_coded": (_i, [_D, _p, _p, _i, _p, _p, C.c_longlong, _p, C.c_longlong, _i, _p, _p, C.c_longlong, _i, _f, _f, _f, _f, _p, _p, _p, _p]),
+    "st_eval_pool_supported": (_i, [_D]),
+    "st_eval_pool_rows": (C.c_longlong, [_D, C.POINTER(C.c_longlong), _i, C.POINTER(C.c_longlong)]),
+    "st_eval_pool_ws_bytes": (C.c_size_t, [_D]),
+    "st_eval_pool": (_i, [_D, _p, _i, _p, _p, _p, _p, _p, _i, C.c_longlong, C.c_longlong, _p, _p, _p, _p, _p]),
     "st_loss_backward_p1": (_i, [_D, _p, _p, _p, _p, _p, _p, _p]),
     "st_loss_backward_p2": (_i, [_D, _p, _p, _p, _p, _p]),
     "st_loss_backward_p2_staged": (_i, [_D, _p, _p, _p, _p, _p, _p]),
@@ -188,6 +192,9 @@ def family_mask(choosers):
     return sum(1 << f for f in fams)
 # sample formats of st_file_feed's audio pools (include/signaltrain_hip.h ST_PCM_*)
 PCM_F32, PCM_S16 = 0, 1
+# st_eval_pool's per-file statistics (ST_POOL_STATS values per file, in this order; the last is always 0)
+POOL_STATS = 8
+POOL_FIELDS = ("n", "sum_logcosh", "sum_abs", "sum_sq", "peak", "sum_t_sq", "sum_y_sq", "zero")
 
 # parameter groups of st_train_step_groups (ST_GROUP_*) by the names train.train(freeze=...) takes, and the stages st_step_groups_stages reports (ST_STAGE_*)
 GROUPS = {"analysis": 1, "synthesis": 2, "aenc": 4, "phs_aenc": 8}

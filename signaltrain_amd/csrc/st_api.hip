@@ -26,6 +26,7 @@
 #include "st_feed_stream.h"
 #include "st_predict.h"
 #include "st_predict_stream.h"
+#include "st_eval_pool.h"
 #include "st_decode.h"
 #include "st_fit.h"
 #include "st_multi.h"
@@ -2266,6 +2267,119 @@ extern "C" int st_predict_stream_push(const st_dims* d, const float* params, st_
     }
     s->received = n0 + m; s->emitted += plan[2]; s->held = (int)plan[3]; s->closed = final ? 1 : 0;
     return ST_OK;
+}
+
+// ------------------------------------------------------------------------------ a folder of recordings in one call (st_eval_pool.h)
+// st_predict_long's batch on rows that are (file, window) pairs of the feeds' pool, every file at its own knob row, with the per-file error statistics left on the
+// device.  The workspace is [st_predict_long's head | the batch's partials [POOL_PART][d->B * ceil(y / 256)] | one batch's workspace].
+static size_t pool_part_plane(const st_dims* d) { return ((size_t)d->B * ((d->y + 255) / 256) + 63) / 64 * 64; }
+static size_t pool_part_bytes(const st_dims* d) { return (size_t)stq::POOL_PART * pool_part_plane(d) * sizeof(float); }
+static long long pool_windows(const st_dims* d, long long len) { return len > (long long)d->L - d->y ? predict_windows(d, len) : 0; }      // no output sample, no row
+extern "C" int st_eval_pool_supported(const st_dims* d) { return st_predict_supported(d); }
+extern "C" long long st_eval_pool_rows(const st_dims* d, const long long* file_len_host, int nfiles, long long* win_off_host)
+{
+    if (check_dims(d) != ST_OK || !file_len_host || nfiles < 1) return 0;
+    long long rows = 0;
+    for (int f = 0; f < nfiles; ++f) {
+        if (win_off_host) win_off_host[f] = rows;
+        rows += pool_windows(d, file_len_host[f]);
+    }
+    if (win_off_host) win_off_host[nfiles] = rows;
+    return rows;
+}
+extern "C" size_t st_eval_pool_ws_bytes(const st_dims* d)
+{
+    const size_t pb = st_predict_ws_bytes(d);
+    return pb ? pb + pool_part_bytes(d) : 0;
+}
+template <typename T>
+static int pool_batches(const st_dims* d, const Layout& L, const PredictWS& p, const float* params, const T* pool_x, const T* pool_y, const stq::Tables& tb,
+                        long long total_rows, const float* file_knobs, double* stats, float* out, void* ws, void* stream)
+{
+    const float* Wr = params + L.offs[0]; const float* Wi = params + L.offs[1];
+    const float* ae_m = params + L.offs[4]; const float* ae_p = params + L.offs[22];
+    const bool g16 = stft_family(d, GEMM_ANALYSIS, SGP_PADDED | SGP_G16) == GF_G16, img = predict_img(d);      // as predict_batches
+    float* part = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + p.head_bytes);
+    const size_t batch_off = p.head_bytes + pool_part_bytes(d);
+    const size_t plane = pool_part_plane(d);
+    const int nslot = (d->y + 255) / 256;
+    const int n_zero = tb.nfiles < 1024 ? tb.nfiles : 1024;
+    if (total_rows == 0) {      // nothing to predict: the side role alone (the zero spans and the zero statistics)
+        stq::StageArgs a{};
+        a.t = tb; a.L = d->L; a.y = d->y; a.out = out; a.stats = stats; a.n_zero = n_zero;
+        hipLaunchKernelGGL(stq::pool_stage_kernel<T>, dim3(n_zero), dim3(256), 0, st_stream(stream), a);
+        ST_LAUNCHED("pool_stage");
+        return ST_OK;
+    }
+    for (long long r0 = 0; r0 < total_rows; r0 += d->B) {
+        st_dims q = *d; q.B = (int)(total_rows - r0 < d->B ? total_rows - r0 : d->B);
+        WS w; carve(&q, L, reinterpret_cast<char*>(ws) + batch_off, &w);
+        w.g16 = g16;
+        w.Sfold = p.Sfold; w.SfoldT = p.SfoldT; w.Sfold16 = p.Sfold16; w.SfoldT16 = p.SfoldT16; w.W16 = p.W16;
+        w.pl_W = p.pl_W; w.pl_Sfold = p.pl_Sfold; w.pl_SfoldT = p.pl_SfoldT;
+        const stg::RowMap map = stg::live_frames(q.T, q.H, q.N, q.N, q.L);
+        stq::StageArgs a;
+        a.pool_x = pool_x; a.t = tb; a.r0 = r0; a.y = q.y; a.L = q.L; a.pad = q.N; a.nb = q.B;
+        a.xp = w.xp; a.xp16 = w.xp16; a.ht = g16 ? gemm_ht(q.prec) : 0;
+        a.nbx = ((q.L + 2 * q.N) / 4 + 255) / 256; a.n_pad = a.nbx * q.B;
+        a.mag = w.mag; a.phs = w.phs; a.T = q.T; a.F = q.F; a.t_lo = map.t_lo; a.Tv = map.Tv; a.n_dead = q.B * (q.T - map.Tv);
+        a.file_knobs = file_knobs; a.knobs = p.knobs; a.K = q.K; a.n_kn = q.K > 0 ? (q.B * q.K + 255) / 256 : 0;
+        a.out = out; a.stats = stats; a.n_zero = r0 == 0 ? n_zero : 0;
+        const float* kn = q.K == 0 ? params : p.knobs;      // K == 0: any resident float (call_begin)
+        hipLaunchKernelGGL(stq::pool_stage_kernel<T>, dim3(a.n_pad + a.n_dead + a.n_kn + a.n_zero), dim3(256), 0, st_stream(stream), a);
+        ST_LAUNCHED("pool_stage");
+        ST_TRY(stft_gemm(step_stft_plan(&q, w, GEMM_ANALYSIS, Wr, Wi), GemmOut{nullptr, nullptr, w.mag, w.phs, nullptr, nullptr}, stream));
+        ST_TRY(ae_fwd_body(&q, L, w.mag, w.phs, kn, ae_m, ae_p, w.mag_hat, w.phs_hat, w.AA, w.reg_p, nullptr, stream, g16 ? w.AA16 : nullptr, false, nullptr,
+                           img ? p.img : nullptr));
+        ST_TRY(stft_gemm(step_stft_plan(&q, w, GEMM_FRAMES), slabs_at(w.frs), stream));
+        const int ns = frame_slabs(&q);
+        const dim3 grid((q.y / 4 + 255) / 256, q.B);
+        const size_t slab = (size_t)q.B * q.OT * q.N;
+        const bool three = (q.N + q.H - 1) / q.H <= 3;      // as predict_batches
+        with_bool(three, [&](auto NF3) { with_slabs(ns, [&](auto NS) {
+            hipLaunchKernelGGL((stq::pool_ola_kernel<T, NS(), NF3() ? 3 : 0>), grid, dim3(256), 0, st_stream(stream),
+                               w.frs, slab, pool_x, pool_y, out, part, plane, nslot, tb, r0, q.L, q.N, q.H, q.OT, q.y); }); });
+        ST_LAUNCHED("pool_ola");
+        if (stats) {
+            hipLaunchKernelGGL(stq::pool_tail_kernel, dim3(q.B), dim3(256), 0, st_stream(stream), (const float*)part, plane, nslot, tb, r0, q.B, q.L, q.y, stats);
+            ST_LAUNCHED("pool_tail");
+        }
+    }
+    return ST_OK;
+}
+extern "C" int st_eval_pool(const st_dims* d, const float* params, int fmt, const void* pool_x, const void* pool_y,
+                            const long long* file_off, const long long* file_len, const long long* win_off, int nfiles,
+                            long long total_rows, long long pool_samples, const float* file_knobs, double* stats, float* out, void* ws, void* stream)
+{
+    Layout L; ST_TRY(make_layout(d, &L));
+    ST_REQ(!ae_is_wide(d), "st_eval_pool: not supported for the wide autoencoder geometries (T = %d > 32 or OT = %d > 16): st_eval_pool_supported", d->T, d->OT);
+    ST_REQ(params, "st_eval_pool: null pointer (params)"); ST_REQ(pool_x, "st_eval_pool: null pointer (pool_x)");
+    ST_REQ(file_off, "st_eval_pool: null pointer (file_off)"); ST_REQ(file_len, "st_eval_pool: null pointer (file_len)"); ST_REQ(win_off, "st_eval_pool: null pointer (win_off)");
+    ST_REQ(file_knobs || d->K == 0, "st_eval_pool: null pointer (file_knobs, K = %d)", d->K);
+    ST_REQ(ws, "st_eval_pool: null pointer (ws)");
+    ST_REQ(fmt == ST_PCM_F32 || fmt == ST_PCM_S16, "st_eval_pool: fmt = %d is neither ST_PCM_F32 nor ST_PCM_S16", fmt);
+    ST_REQ(nfiles >= 1, "st_eval_pool: nfiles = %d must be at least 1", nfiles);
+    ST_REQ(total_rows >= 0, "st_eval_pool: total_rows = %lld must not be negative", total_rows);
+    ST_REQ(pool_samples >= 1, "st_eval_pool: pool_samples = %lld must be at least 1", pool_samples);
+    ST_REQ((stats != nullptr) == (pool_y != nullptr), "st_eval_pool: stats and pool_y come together (stats %s, pool_y %s)", stats ? "given" : "null", pool_y ? "given" : "null");
+    ST_REQ(out || stats, "st_eval_pool: out and stats are both null: nothing to compute");
+    const uintptr_t pa = fmt == ST_PCM_S16 ? 7 : 15;
+    ST_REQ((reinterpret_cast<uintptr_t>(pool_x) & pa) == 0, "st_eval_pool: pool_x must be %d-byte aligned", (int)pa + 1);
+    ST_REQ((reinterpret_cast<uintptr_t>(pool_y) & pa) == 0, "st_eval_pool: pool_y must be %d-byte aligned", (int)pa + 1);
+    ST_REQ((reinterpret_cast<uintptr_t>(out) & 15) == 0, "st_eval_pool: out must be 16-byte aligned");
+    ST_REQ((reinterpret_cast<uintptr_t>(stats) & 15) == 0, "st_eval_pool: stats must be 16-byte aligned");
+    ST_REQ((reinterpret_cast<uintptr_t>(ws) & 15) == 0, "st_eval_pool: ws must be 16-byte aligned");
+    {   // the kernels' 32-bit element offsets at the largest batch: the frame slabs and the synthesis operand (check_dims holds the rest at d->B)
+        const size_t rows = (size_t)(total_rows < d->B ? total_rows : d->B);
+        ST_REQ((size_t)frame_slabs(d) * rows * d->OT * d->N < ((size_t)1 << 30) && (size_t)synth_slabs(d) * rows * d->OT * L.KP < ((size_t)1 << 30),
+               "st_eval_pool: batch too large for the kernels' 32-bit element offsets (%zu rows)", rows);
+    }
+    PredictWS p; predict_carve(d, ws, &p);
+    const stq::Tables tb{file_off, file_len, win_off, nfiles, pool_samples};
+    prof_mark("begin", stream);
+    if (total_rows > 0) { ST_TRY(predict_prep(d, L, p, params, stream)); }
+    return fmt == ST_PCM_S16 ? pool_batches(d, L, p, params, reinterpret_cast<const short*>(pool_x), reinterpret_cast<const short*>(pool_y), tb, total_rows, file_knobs, stats, out, ws, stream)
+                             : pool_batches(d, L, p, params, reinterpret_cast<const float*>(pool_x), reinterpret_cast<const float*>(pool_y), tb, total_rows, file_knobs, stats, out, ws, stream);
 }
 
 // ------------------------------------------------------------------------------ knob fit on the device (st_fit.h)

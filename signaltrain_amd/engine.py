@@ -633,6 +633,67 @@ class StepEngine:
                        C.c_void_p(signal.data_ptr()), n, _lib.ptr(kn), rows, C.c_void_p(out.data_ptr()), _lib.ptr(self._predict_ws), self._stream())
         return out[:n_out]
 
+    # ---------------------------------------------------------------- a folder of recordings in one call
+    def eval_pool_supported(self):
+        """Whether eval_pool() runs this geometry (st_eval_pool_supported = st_predict_supported; host arithmetic only)."""
+        return bool(self.lib.st_eval_pool_supported(C.byref(self.dims.with_batch(1))))
+
+    def eval_pool(self, pool_x, pool_y, off, length, knobs, want_out=False, batch=None):
+        """Every file of a device feed's pool WHOLE through the model, each at its own knob row, in ONE C call (st_eval_pool in include/signaltrain_hip.h).
+        pool_x / pool_y: the concatenated audio on this engine's device, float32 or int16 (both the same; pool_y None: predict only); off / length: int64
+        [nfiles], host arrays (tensors are read back to the host: the rows are formed there, and the device tables are kept from call to call
+        while the arrays stay the same); knobs: [nfiles, K] (None for K == 0); batch: (file, window) rows per internal batch (default max_batch).
+        Returns (stats, out): stats float64 [nfiles, 8] on the device (_lib.POOL_FIELDS; None without pool_y), out the pool-shaped float32 prediction,
+        time-aligned with the input, zeros over each file's first L - y samples (None unless want_out or pool_y is None).  No host sync once the tables
+        are known.  The engine keeps a workspace of its own for this: self.ws is not written; generation moves on."""
+        dev = self.device
+        if not (torch.is_tensor(pool_x) and pool_x.dim() == 1 and pool_x.device == dev and pool_x.dtype in (torch.float32, torch.int16) and pool_x.numel() >= 1):
+            raise ValueError(f"eval_pool: pool_x must be a non-empty 1-D float32 or int16 tensor on {dev}")
+        if pool_y is not None and not (torch.is_tensor(pool_y) and pool_y.shape == pool_x.shape and pool_y.device == dev and pool_y.dtype == pool_x.dtype):
+            raise ValueError("eval_pool: pool_y must match pool_x in shape, dtype and device (or be None)")
+        al = lambda t: t if t is None or (t.is_contiguous() and t.data_ptr() % 16 == 0) else t.contiguous().clone()
+        pool_x, pool_y = al(pool_x), al(pool_y)
+        want_out = bool(want_out or pool_y is None)
+        B = int(batch or self.max_batch)
+        if B < 1:
+            raise ValueError(f"eval_pool: batch = {B}")
+        d = self.dims.with_batch(B)
+        d.prec, d.loss_scale, d.clip_all = _lib.PREC[self.compute_dtype], self.loss_scale, int(self.clip_all)
+        host = lambda t: np.ascontiguousarray(t.detach().cpu().numpy() if torch.is_tensor(t) else t, dtype=np.int64).reshape(-1)
+        off_h, len_h = host(off), host(length)
+        nfiles = int(len_h.size)
+        if nfiles < 1 or off_h.size != nfiles:
+            raise ValueError(f"eval_pool: off and length must hold one entry per file ({off_h.size} and {nfiles})")
+        tables = self.__dict__.setdefault("_pool_tables", {})       # the device tables and win_off: built once per (offsets, lengths, geometry) from the host lengths
+        key = (off_h.tobytes(), len_h.tobytes(), d.L, d.y)
+        if key not in tables:
+            tables.clear()
+            win = np.zeros(nfiles + 1, np.int64)
+            rows = int(self.lib.st_eval_pool_rows(C.byref(d), len_h.ctypes.data_as(C.POINTER(C.c_longlong)), nfiles, win.ctypes.data_as(C.POINTER(C.c_longlong))))
+            tables[key] = tuple(torch.from_numpy(a).to(dev) for a in (off_h, len_h, win)) + (rows,)
+        off_d, len_d, win_d, rows = tables[key]
+        kn = None
+        if d.K:
+            kn = torch.as_tensor(knobs).to(device=dev, dtype=torch.float32).reshape(-1, d.K).contiguous()
+            if kn.shape[0] != nfiles:
+                raise ValueError(f"eval_pool: knobs has {kn.shape[0]} rows for {nfiles} files")
+        sizes = self.__dict__.setdefault("_pool_sizes", {})
+        if (B, self.compute_dtype) not in sizes:
+            sizes[(B, self.compute_dtype)] = int(self.lib.st_eval_pool_ws_bytes(C.byref(d)))
+        need = sizes[(B, self.compute_dtype)]
+        if need <= 0:
+            raise RuntimeError(f"eval_pool: st_eval_pool_supported refuses this geometry (T={d.T}, OT={d.OT}): the wide autoencoder geometries stay on forward()")
+        if getattr(self, "_pool_ws", None) is None or self._pool_ws.numel() < need:
+            self._pool_ws = torch.zeros(need, dtype=torch.uint8, device=dev)
+        stats = torch.empty(nfiles, _lib.POOL_STATS, dtype=torch.float64, device=dev) if pool_y is not None else None
+        out = torch.empty(pool_x.numel(), dtype=torch.float32, device=dev) if want_out else None
+        self.generation += 1
+        self._call("st_eval_pool", C.byref(d), _lib.ptr(self.params), _lib.PCM_S16 if pool_x.dtype == torch.int16 else _lib.PCM_F32,
+                   C.c_void_p(pool_x.data_ptr()), None if pool_y is None else C.c_void_p(pool_y.data_ptr()), C.c_void_p(off_d.data_ptr()), C.c_void_p(len_d.data_ptr()),
+                   C.c_void_p(win_d.data_ptr()), nfiles, rows, int(pool_x.numel()), _lib.ptr(kn), None if stats is None else C.c_void_p(stats.data_ptr()),
+                   None if out is None else C.c_void_p(out.data_ptr()), _lib.ptr(self._pool_ws), self._stream())
+        return stats, out
+
     # ---------------------------------------------------------------- predict session: inference fed block by block
     def open_stream(self, channels=1, batch=None):
         """A predict session (st_predict_stream_* in include/signaltrain_hip.h): `channels` signals fed in lockstep block by block, every output sample

@@ -203,7 +203,8 @@ def _train_loop(dp, model, engine, effect, device, epochs, batch_size, lr_sched,
 def train(effect=None, epochs=100, n_data_points=200000, batch_size=20, device=None, plot_every=10, cp_every=25, sr=44100,
           datapath=None, scale_factor=1, shrink_factor=4, apex_opt="O0", target_type="stream", lr_max=1e-4,
           in_checkpointname='modelcheckpoint.tar', compand=False, num_workers=10, device_feed=True, compute_dtype=None,
-          resume_optimizer=False, device_eval=False, choosers=None, input_path=None, synth_prob=0.0, preroll=0, freeze=None, unfreeze_epoch=None):
+          resume_optimizer=False, device_eval=False, choosers=None, input_path=None, synth_prob=0.0, preroll=0, freeze=None, unfreeze_epoch=None,
+          file_report=False):
     """train.py:167-278.  datapath: directory with Train/ and Val/ wav pairs (datasets.AudioFileDataSet, the reference's
     file feed, e.g. the LA2A set of BASELINE configs[3]; pass effect=audio.FileEffect(datapath)); compand: mu-law compand that dataset's audio (datasets.py:218-220).
     apex_opt: "O0" = fp32 (the parity path); "O1" / "O2" / "O3" = the reference's Apex mixed precision (train.py:254-255),
@@ -230,8 +231,12 @@ def train(effect=None, epochs=100, n_data_points=200000, batch_size=20, device=N
     freeze: parameter groups that do not train, an iterable out of "analysis", "synthesis", "aenc", "phs_aenc", "frontend" (= the first two: the
     autoencoders learn over the fixed DFT bases); their parameters and Adam state stay as they are and the step skips the work that only fed them
     (st_train_step_groups).  unfreeze_epoch: the (0-based) epoch from which those groups train as well -- the two-phase schedule; None = frozen throughout.
-    requires_grad flags set by hand (nn_proc.freeze_layers, st_model.freeze) are honoured in the same way, read at the head of every epoch."""
+    requires_grad flags set by hand (nn_proc.freeze_layers, st_model.freeze) are honoured in the same way, read at the head of every epoch.
+    file_report: with datapath, after the last epoch every file of Val/ goes WHOLE through the model at its own knob setting and the per-file error table
+    is printed (datasets.AudioFileDataSet.evaluate: one st_eval_pool call, csrc/st_eval_pool.h)."""
     freeze = check_freeze(freeze)
+    if file_report and (datapath is None or target_type != "stream"):
+        raise ValueError("train(): file_report reports the recorded files of datapath's Val/ folder against their recorded targets: it needs datapath and target_type=\"stream\"")
     if unfreeze_epoch is not None and (not freeze or int(unfreeze_epoch) < 0):
         raise ValueError(f"train(): unfreeze_epoch = {unfreeze_epoch} needs a freeze list and a non-negative epoch")
     if input_path is not None and datapath is not None:
@@ -365,4 +370,9 @@ def train(effect=None, epochs=100, n_data_points=200000, batch_size=20, device=N
     train_loop(model, engine, effect, device, epochs, batch_size, lr_sched, mom_sched, dataloader, dataloader_val,
                out_chunk_size, logfilename, "modelcheckpoint.tar", sr=sr, lr_max=lr_max,
                start_epoch=start_epoch, start_iter=start_iter, lr_resume=lr_resume, device_eval=device_eval, freeze=freeze, unfreeze_epoch=unfreeze_epoch)
+    if file_report and not (dist.is_initialized() and dist.get_rank() != 0):
+        import os
+        rep = dataset_val.evaluate(model, device=device)
+        print("Val set, file by file (whole files, each at its own knob setting):")
+        print(datasets.format_file_report(rep, [os.path.basename(f) for f in dataset_val.target_filenames]))
     return model
