@@ -1959,43 +1959,136 @@ struct FitJob {
 struct CodeJob { float* code_out; const float* code; int n_settings; long long out_pitch; size_t set_stride; };      // set_stride: floats between two settings' knob rows
 // ae_dec_fwd_kernel: 8-wave workgroups, four waves per SIMD, two workgroups per CU
 static int ae_dec_grid(const st_dims* d) { int g = (ae_fwd_groups(d) + sta::AE_DEC_NW - 1) / sta::AE_DEC_NW; int c = num_cus() * sta::AE_DEC_WGS; return g < c ? g : c; }
+
+// ---- the batch of the whole-signal entries, stated once: st_predict_long, the coded routes, the fits, the predict session and st_eval_pool all build theirs from these
+// the head's parameter-side operands, where the GEMM plans look for them
+static void ws_head(WS& w, const PredictWS& p)
+{
+    w.Sfold = p.Sfold; w.SfoldT = p.SfoldT; w.Sfold16 = p.Sfold16; w.SfoldT16 = p.SfoldT16; w.W16 = p.W16;
+    w.pl_W = p.pl_W; w.pl_Sfold = p.pl_Sfold; w.pl_SfoldT = p.pl_SfoldT;
+}
+struct InferBatch {
+    st_dims q; WS w;                           // the dims at this batch's row count, its workspace (carved as the fused entries carve theirs, the head's operands in place)
+    bool g16, img;                             // the 16-bit pipeline wherever the precision admits it, as the training entries; ready-made forward images
+    const Layout* L; const PredictWS* p; const float *params, *Wr, *Wi, *ae_m, *ae_p;
+    int ht() const { return g16 ? gemm_ht(q.prec) : 0; }
+    const float* resident_knobs() const { return q.K == 0 ? params : p->knobs; }      // K == 0: any resident float (call_begin)
+};
+static InferBatch infer_batch(const st_dims* d, const Layout& L, const PredictWS& p, const float* params, void* ws, size_t batch_off, long long rows)
+{
+    InferBatch b;
+    b.q = *d; b.q.B = (int)rows;
+    carve(&b.q, L, reinterpret_cast<char*>(ws) + batch_off, &b.w);
+    b.g16 = stft_family(d, GEMM_ANALYSIS, SGP_PADDED | SGP_G16) == GF_G16; b.img = predict_img(d);
+    b.w.g16 = b.g16;
+    ws_head(b.w, p);
+    b.L = &L; b.p = &p; b.params = params;
+    b.Wr = params + L.offs[0]; b.Wi = params + L.offs[1]; b.ae_m = params + L.offs[4]; b.ae_p = params + L.offs[22];
+    return b;
+}
+// what every stage kernel is told about the batch; fill_knobs: its knob blocks write the batch's knob rows into the head
+static stp::StageCommon stage_common(const InferBatch& b, bool fill_knobs)
+{
+    const st_dims& q = b.q;
+    const stg::RowMap map = stg::live_frames(q.T, q.H, q.N, q.N, q.L);
+    stp::StageCommon c;
+    c.y = q.y; c.L = q.L; c.pad = q.N; c.nb = q.B;
+    c.xp = b.w.xp; c.xp16 = b.w.xp16; c.ht = b.ht();
+    c.nbx = ((q.L + 2 * q.N) / 4 + 255) / 256; c.n_pad = c.nbx * q.B;
+    c.mag = b.w.mag; c.phs = b.w.phs; c.T = q.T; c.F = q.F; c.t_lo = map.t_lo; c.Tv = map.Tv; c.n_dead = q.B * (q.T - map.Tv);
+    c.knobs = b.p->knobs; c.K = q.K; c.n_kn = fill_knobs && q.K > 0 ? (q.B * q.K + 255) / 256 : 0;
+    return c;
+}
+static int infer_analysis(const InferBatch& b, void* stream)
+{
+    return stft_gemm(step_stft_plan(&b.q, b.w, GEMM_ANALYSIS, b.Wr, b.Wi), GemmOut{nullptr, nullptr, b.w.mag, b.w.phs, nullptr, nullptr}, stream);
+}
+static int infer_frames(const InferBatch& b, void* stream) { return stft_gemm(step_stft_plan(&b.q, b.w, GEMM_FRAMES), slabs_at(b.w.frs), stream); }
+// staged rows -> frames: analysis GEMM, the autoencoders at knob rows kn, frames GEMM.  keep_h4 (the fits): the code h4 stays at the head of the autoencoder workspace
+static int infer_forward(const InferBatch& b, const float* kn, bool keep_h4, void* stream)
+{
+    ST_TRY(infer_analysis(b, stream));
+    ST_TRY(ae_fwd_body(&b.q, *b.L, b.w.mag, b.w.phs, kn, b.ae_m, b.ae_p, b.w.mag_hat, b.w.phs_hat, b.w.AA, b.w.reg_p, keep_h4 ? b.w.aews : nullptr, stream,
+                       b.g16 ? b.w.AA16 : nullptr, false, nullptr, b.img ? b.p->img : nullptr));
+    return infer_frames(b, stream);
+}
+// The launch shape of every overlap-add kernel of the family (st_predict.h: ola_frame_sum): launch(NS, NF, grid, slab) names the kernel and its arguments.
+// NF = 3: the rule of ola_loss_impl for the four-sample form with all loads up front.
+template <class F> static void ola_launch(const InferBatch& b, F&& launch)
+{
+    const st_dims& q = b.q;
+    const int ns = frame_slabs(&q);
+    const dim3 grid((q.y / 4 + 255) / 256, q.B);
+    const size_t slab = (size_t)q.B * q.OT * q.N;
+    const bool three = (q.N + q.H - 1) / q.H <= 3;
+    with_bool(three, [&](auto NF3) { with_slabs(ns, [&](auto NS) { launch(NS, ic<NF3() ? 3 : 0>{}, grid, slab); }); });
+}
+// d J / d knobs of a batch whose fit_ola has written d syn: data-gradient GEMM -> ae_knob_bwd_kernel (knob rows kn) -> knob_grad_kernel, into fit.rows [rows][K]
+// The offset guard is st_fit_knobs' and st_fit_knobs_coded's (their wording); st_fit_knobs_multi_coded never reaches it: multi_args has refused these sizes, at the
+// plan's largest batch and under its own name, before the first launch.
+static int knob_backward(const InferBatch& b, const float* kn, const FitJob& fit, void* stream)
+{
+    const st_dims& q = b.q; const Layout& L = *b.L; const WS& w = b.w;
+    ST_REQ((size_t)synth_slabs(&q) * q.B * q.OT * L.KP < ((size_t)1 << 30) && (size_t)q.B * q.T * L.KP < ((size_t)1 << 30),
+           "st_fit_knobs: batch too large for the kernel's 32-bit element offsets (B=%d)", q.B);
+    ST_TRY(stft_gemm(step_stft_plan(&q, w, GEMM_DGRAD), slabs_at(w.dAA), stream));
+    const stg::RowMap live = synth_live(&q);
+    const int groups = ae_fwd_groups(&q), kgrid = ae_knob_grid(&q);
+    ST_TRY(with_ht(ae_ht(q.prec), [&](auto HT) {
+        return launch_lds("ae_knob_bwd_kernel", sta::ae_knob_bwd_kernel<AE_KNOB_NW, HT()>, dim3(kgrid, 2), dim3(AE_KNOB_NW * 64),
+                          (size_t)sta::ae_knob_lds_floats(AE_KNOB_NW) * sizeof(float), st_stream(stream),
+                          w.mag, kn, b.ae_m, b.ae_p, L.go, w.mag_hat, w.phs_hat, w.dAA, w.aews, fit.kg, q.B, q.T, q.OT, q.F, q.K, L.KP,
+                          live.t_lo, live.t_lo + live.Tv - 1, synth_slabs(&q), (size_t)q.B * q.OT * L.KP); }));
+    ST_LAUNCHED("ae_knob_bwd");
+    const size_t w5 = (size_t)L.offs[4] + (size_t)L.go.w[4];
+    hipLaunchKernelGGL(knob_grad_kernel, dim3(q.B), dim3(64), 0, st_stream(stream), b.params + w5, (const float*)fit.kg, b.params + w5 + L.PG,
+                       (const float*)fit.kg + (size_t)groups * 16, q.K, fit.rows, L.KP / 32);
+    ST_LAUNCHED("knob_grad");
+    return ST_OK;
+}
+// the decoder forward of a batch from the code (st_decode.h): no stage kernel, no analysis GEMM, no encoder.  fit: mag_hat / phs_hat and the batch-layout h4, magnitude
+// tail and knob rows ae_knob_bwd_kernel reads are written through.  STK: rows are (setting, window) pairs, nw windows each, the settings set_stride floats apart.
+template <bool STK>
+static int dec_forward(const InferBatch& b, const float* code, const float* kn, int kn_pitch, bool fit, void* stream, int nw = 0, unsigned set_stride = 0u)
+{
+    const st_dims& q = b.q; const WS& w = b.w;
+    ST_TRY(with_ht(ae_ht(q.prec), [&](auto HT) {
+        return launch_lds("ae_dec_fwd_kernel", sta::ae_dec_fwd_kernel<sta::AE_DEC_NW, HT(), STK>, dim3(ae_dec_grid(&q)), dim3(sta::AE_DEC_NW * 64),
+                          (size_t)sta::ae_dec_lds_floats() * sizeof(float), st_stream(stream),
+                          code, kn, kn_pitch, b.ae_m, b.ae_p, b.L->go,
+                          fit ? w.mag_hat : nullptr, fit ? w.phs_hat : nullptr, w.AA, b.g16 ? w.AA16 : nullptr, b.ht(),
+                          fit ? w.aews : nullptr, fit ? w.mag : nullptr, fit ? b.p->knobs : nullptr, q.B, q.T, q.OT, q.F, q.K, b.L->KP, nw, set_stride); }));
+    ST_LAUNCHED("ae_dec_fwd");
+    return ST_OK;
+}
 template <typename T>
-static int predict_batches(const st_dims* d, const Layout& L, const PredictWS& p, const float* params, const T* signal, long long n,
+static int predict_batches(const st_dims* d, const Layout& L, const PredictWS& p, const float* params, const void* signal_v, long long n,
                            const float* knobs, long long knob_rows, float* out, long long n_out, void* ws, void* stream,
                            const FitJob* fit = nullptr, size_t batch_off = 0, const CodeJob* cj = nullptr)
 {
+    const T* signal = reinterpret_cast<const T*>(signal_v);
     if (!batch_off) batch_off = p.head_bytes;
     const bool enc = cj && cj->code_out, dec = cj && cj->code;
     const int nset = dec && !fit ? cj->n_settings : 1;
     const size_t CW = stc::code_window_floats(L.KP / 2, d->OT);
-    const float* Wr = params + L.offs[0]; const float* Wi = params + L.offs[1];
-    const float* ae_m = params + L.offs[4]; const float* ae_p = params + L.offs[22];
-    const bool g16 = stft_family(d, GEMM_ANALYSIS, SGP_PADDED | SGP_G16) == GF_G16, img = predict_img(d);      // the 16-bit pipeline wherever the precision admits it, as the training entries
     const long long nwin = (n_out + d->y - 1) / d->y;      // == predict_windows(d, n) wherever n_out > 0
     for (long long w0 = 0; w0 < nwin; w0 += d->B) {
-        st_dims q = *d; q.B = (int)(nwin - w0 < d->B ? nwin - w0 : d->B);
-        WS w; carve(&q, L, reinterpret_cast<char*>(ws) + batch_off, &w);
-        w.g16 = g16;
-        w.Sfold = p.Sfold; w.SfoldT = p.SfoldT; w.Sfold16 = p.Sfold16; w.SfoldT16 = p.SfoldT16; w.W16 = p.W16;
-        w.pl_W = p.pl_W; w.pl_Sfold = p.pl_Sfold; w.pl_SfoldT = p.pl_SfoldT;
-        const stg::RowMap map = stg::live_frames(q.T, q.H, q.N, q.N, q.L);
-        stp::StageArgs a;
-        a.signal = signal; a.n = n; a.s0 = w0 * q.y; a.y = q.y; a.L = q.L; a.pad = q.N; a.nb = q.B;
-        a.xp = w.xp; a.xp16 = w.xp16; a.ht = g16 ? gemm_ht(q.prec) : 0;
-        a.nbx = ((q.L + 2 * q.N) / 4 + 255) / 256; a.n_pad = a.nbx * q.B;
-        a.mag = w.mag; a.phs = w.phs; a.T = q.T; a.F = q.F; a.t_lo = map.t_lo; a.Tv = map.Tv; a.n_dead = q.B * (q.T - map.Tv);
+        const InferBatch b = infer_batch(d, L, p, params, ws, batch_off, nwin - w0 < d->B ? nwin - w0 : d->B);
+        const st_dims& q = b.q; const WS& w = b.w;
+        const long long s0 = w0 * q.y;
         const bool fill = knob_rows == 1 && q.K > 0;
-        a.knob_row = knobs; a.knobs = p.knobs; a.K = q.K; a.n_kn = fill ? (q.B * q.K + 255) / 256 : 0;
         const float* kn = q.K == 0 ? params : fill ? p.knobs : knobs + (size_t)w0 * q.K;      // K == 0: any resident float (call_begin)
         if (!dec) {
-            if (enc) a.n_kn = 0;      // the code does not depend on the knobs: the code-only pass loads a knob row (any resident floats) and drops it
-            hipLaunchKernelGGL(stp::predict_stage_kernel<T>, dim3(a.n_pad + a.n_dead + a.n_kn), dim3(256), 0, st_stream(stream), a);
+            stp::StageArgs a;
+            a.c = stage_common(b, fill && !enc);      // the code does not depend on the knobs: the code-only pass loads a knob row (any resident floats) and drops it
+            a.signal = signal; a.n = n; a.s0 = s0; a.knob_row = knobs;
+            hipLaunchKernelGGL(stp::predict_stage_kernel<T>, dim3(a.c.n_pad + a.c.n_dead + a.c.n_kn), dim3(256), 0, st_stream(stream), a);
             ST_LAUNCHED("predict_stage");
-            ST_TRY(stft_gemm(step_stft_plan(&q, w, GEMM_ANALYSIS, Wr, Wi), GemmOut{nullptr, nullptr, w.mag, w.phs, nullptr, nullptr}, stream));
         }
         if (enc) {      // st_encode_long: the knob-independent half, then the batch's h4 and tails to their windows of the code
-            ST_TRY(ae_fwd_body(&q, L, w.mag, w.phs, q.K == 0 ? params : p.knobs, ae_m, ae_p, nullptr, nullptr, nullptr, nullptr, w.aews, stream, nullptr, false, nullptr,
-                               img ? p.img : nullptr));
+            ST_TRY(infer_analysis(b, stream));
+            ST_TRY(ae_fwd_body(&q, L, w.mag, w.phs, b.resident_knobs(), b.ae_m, b.ae_p, nullptr, nullptr, nullptr, nullptr, w.aews, stream, nullptr, false, nullptr,
+                               b.img ? p.img : nullptr));
             const int n4 = (int)(CW / 4);
             hipLaunchKernelGGL(stc::code_pack_kernel, dim3((n4 + 1023) / 1024, q.B), dim3(256), 0, st_stream(stream),
                                (const float*)w.aews, (const float*)w.mag, (const float*)w.phs, cj->code_out + (size_t)w0 * CW, q.B, q.T, q.OT, q.F, L.KP / 2);
@@ -2003,66 +2096,38 @@ static int predict_batches(const st_dims* d, const Layout& L, const PredictWS& p
             continue;
         }
         for (int s = 0; s < nset; ++s) {
-            if (dec) {      // the decoder forward from the code: no stage kernel, no analysis GEMM, no encoder (st_decode.h)
+            if (dec) {
                 ST_REQ((size_t)q.B * CW < ((size_t)1 << 30) && (size_t)q.B * q.T * q.F < ((size_t)1 << 30) && (size_t)q.B * q.OT * L.KP < ((size_t)1 << 30) &&
                        (size_t)q.B * q.T < ((size_t)1 << 24),      // the last: the 24-bit products b * T and b * OT of the row offsets
                        "st_decode_long / st_fit_knobs_coded: batch too large for the kernel's 32-bit element offsets (B=%d)", q.B);
                 const bool one = knob_rows == 1;
                 const float* ks = q.K == 0 ? params : knobs + (size_t)s * cj->set_stride + (one ? 0 : (size_t)w0 * q.K);
-                ST_TRY(with_ht(ae_ht(q.prec), [&](auto HT) {
-                    return launch_lds("ae_dec_fwd_kernel", sta::ae_dec_fwd_kernel<sta::AE_DEC_NW, HT()>, dim3(ae_dec_grid(&q)), dim3(sta::AE_DEC_NW * 64),
-                                      (size_t)sta::ae_dec_lds_floats() * sizeof(float), st_stream(stream),
-                                      cj->code + (size_t)w0 * CW, ks, (one || q.K == 0) ? 0 : q.K, ae_m, ae_p, L.go,
-                                      fit ? w.mag_hat : nullptr, fit ? w.phs_hat : nullptr, w.AA, g16 ? w.AA16 : nullptr, g16 ? gemm_ht(q.prec) : 0,
-                                      fit ? w.aews : nullptr, fit ? w.mag : nullptr, fit ? p.knobs : nullptr, q.B, q.T, q.OT, q.F, q.K, L.KP, 0, 0u); }));
-                ST_LAUNCHED("ae_dec_fwd");
-            } else {
-                ST_TRY(ae_fwd_body(&q, L, w.mag, w.phs, kn, ae_m, ae_p, w.mag_hat, w.phs_hat, w.AA, w.reg_p, fit ? w.aews : nullptr, stream, g16 ? w.AA16 : nullptr, false, nullptr,
-                                   img ? p.img : nullptr));      // fit: the code h4 stays at the head of the autoencoder workspace
+                ST_TRY(dec_forward<false>(b, cj->code + (size_t)w0 * CW, ks, (one || q.K == 0) ? 0 : q.K, fit != nullptr, stream));
+                ST_TRY(infer_frames(b, stream));
             }
-            ST_TRY(stft_gemm(step_stft_plan(&q, w, GEMM_FRAMES), slabs_at(w.frs), stream));
-            const int ns = frame_slabs(&q);
-            const dim3 grid((q.y / 4 + 255) / 256, q.B);
-            const size_t slab = (size_t)q.B * q.OT * q.N;
-            const bool three = (q.N + q.H - 1) / q.H <= 3;      // the rule of ola_loss_impl for the four-sample form with all loads up front
+            else ST_TRY(infer_forward(b, kn, fit != nullptr, stream));
             if (!fit) {
-                with_bool(three, [&](auto NF3) { with_slabs(ns, [&](auto NS) {
-                    hipLaunchKernelGGL((stp::predict_ola_kernel<T, NS(), NF3() ? 3 : 0>), grid, dim3(256), 0, st_stream(stream),
-                                       w.frs, slab, signal, dec ? out + (size_t)s * cj->out_pitch : out, a.s0, n_out, q.L, q.N, q.H, q.OT, q.y); }); });
+                ola_launch(b, [&](auto NS, auto NF, dim3 grid, size_t slab) {
+                    hipLaunchKernelGGL((stp::predict_ola_kernel<T, NS(), NF()>), grid, dim3(256), 0, st_stream(stream),
+                                       w.frs, slab, signal, dec ? out + (size_t)s * cj->out_pitch : out, s0, n_out, q.L, q.N, q.H, q.OT, q.y); });
                 ST_LAUNCHED("predict_ola");
                 continue;
             }
             const int nslot = (q.y + 255) / 256;
-            with_bool(three, [&](auto NF3) { with_slabs(ns, [&](auto NS) {
-                hipLaunchKernelGGL((stf::fit_ola_kernel<T, NS(), NF3() ? 3 : 0>), grid, dim3(256), 0, st_stream(stream),
-                                   w.frs, slab, signal, reinterpret_cast<const T*>(fit->target), w.dsyn, g16 ? w.dsyn16 : nullptr, g16 ? gemm_ht(q.prec) : 0, w.loss_p, nslot,
-                                   a.s0, n_out, q.L, q.N, q.H, q.OT, q.y, 0); }); });
+            ola_launch(b, [&](auto NS, auto NF, dim3 grid, size_t slab) {
+                hipLaunchKernelGGL((stf::fit_ola_kernel<T, NS(), NF()>), grid, dim3(256), 0, st_stream(stream),
+                                   w.frs, slab, signal, reinterpret_cast<const T*>(fit->target), w.dsyn, b.g16 ? w.dsyn16 : nullptr, b.ht(), w.loss_p, nslot,
+                                   s0, n_out, q.L, q.N, q.H, q.OT, q.y, 0); });
             ST_LAUNCHED("fit_ola");
-            ST_TRY(stft_gemm(step_stft_plan(&q, w, GEMM_DGRAD), slabs_at(w.dAA), stream));
-            {
-                ST_REQ((size_t)synth_slabs(&q) * q.B * q.OT * L.KP < ((size_t)1 << 30) && (size_t)q.B * q.T * L.KP < ((size_t)1 << 30),
-                       "st_fit_knobs: batch too large for the kernel's 32-bit element offsets (B=%d)", q.B);
-                const stg::RowMap live = synth_live(&q);
-                const int groups = ae_fwd_groups(&q), kgrid = ae_knob_grid(&q);
-                ST_TRY(with_ht(ae_ht(q.prec), [&](auto HT) {
-                    return launch_lds("ae_knob_bwd_kernel", sta::ae_knob_bwd_kernel<AE_KNOB_NW, HT()>, dim3(kgrid, 2), dim3(AE_KNOB_NW * 64),
-                                      (size_t)sta::ae_knob_lds_floats(AE_KNOB_NW) * sizeof(float), st_stream(stream),
-                                      w.mag, kn, ae_m, ae_p, L.go, w.mag_hat, w.phs_hat, w.dAA, w.aews, fit->kg, q.B, q.T, q.OT, q.F, q.K, L.KP,
-                                      live.t_lo, live.t_lo + live.Tv - 1, synth_slabs(&q), (size_t)q.B * q.OT * L.KP); }));
-                ST_LAUNCHED("ae_knob_bwd");
-                const size_t w5 = (size_t)L.offs[4] + (size_t)L.go.w[4];
-                hipLaunchKernelGGL(knob_grad_kernel, dim3(q.B), dim3(64), 0, st_stream(stream), params + w5, (const float*)fit->kg, params + w5 + L.PG,
-                                   (const float*)fit->kg + (size_t)groups * 16, q.K, fit->rows, L.KP / 32);
-                ST_LAUNCHED("knob_grad");
-                stf::TailArgs t = fit->hyper;
-                t.loss_p = w.loss_p; t.n_lp = q.B * nslot; t.loss = fit->loss;
-                t.rows = fit->rows; t.nb = q.B; t.K = q.K; t.acc = fit->acc;
-                t.per_window = knob_rows != 1; t.first = w0 == 0; t.last = w0 + q.B >= nwin;
-                const size_t ro = t.per_window ? (size_t)w0 * q.K : 0;
-                t.knobs = fit->knobs + ro; t.m = fit->m + ro; t.v = fit->v + ro; t.grad = fit->grad ? fit->grad + ro : nullptr;
-                hipLaunchKernelGGL(stf::fit_tail_kernel, dim3(1), dim3(256), 0, st_stream(stream), t);
-                ST_LAUNCHED("fit_tail");
-            }
+            ST_TRY(knob_backward(b, kn, *fit, stream));
+            stf::TailArgs t = fit->hyper;
+            t.loss_p = w.loss_p; t.n_lp = q.B * nslot; t.loss = fit->loss;
+            t.rows = fit->rows; t.nb = q.B; t.K = q.K; t.acc = fit->acc;
+            t.per_window = knob_rows != 1; t.first = w0 == 0; t.last = w0 + q.B >= nwin;
+            const size_t ro = t.per_window ? (size_t)w0 * q.K : 0;
+            t.knobs = fit->knobs + ro; t.m = fit->m + ro; t.v = fit->v + ro; t.grad = fit->grad ? fit->grad + ro : nullptr;
+            hipLaunchKernelGGL(stf::fit_tail_kernel, dim3(1), dim3(256), 0, st_stream(stream), t);
+            ST_LAUNCHED("fit_tail");
         }
     }
     return ST_OK;
@@ -2090,35 +2155,86 @@ static int predict_prep(const st_dims* d, const Layout& L, const PredictWS& p, c
         hipLaunchKernelGGL(stm::prep_kernel, dim3(a.n_fold + a.ai.n_blk + a.n_w16), dim3(256), 0, st_stream(stream), a);
         ST_LAUNCHED("predict_prep");
         if (family == GF_PLANES) {
-            WS w; w.Sfold = p.Sfold; w.SfoldT = p.SfoldT; w.pl_W = p.pl_W; w.pl_Sfold = p.pl_Sfold; w.pl_SfoldT = p.pl_SfoldT;
+            WS w; ws_head(w, p);
             ST_TRY(planes_prepare(d, a.Wr, a.Wi, w, stream));
         }
     }
     return ST_OK;
 }
+// ---- what the whole-signal entries ask of their arguments, each rule and its wording in one place, under the entry's name
+// the dims rule that failed, under this entry's name
+static int layout_named(const char* name, const st_dims* d, Layout* L)
+{
+    if (make_layout(d, L) == ST_OK) return ST_OK;
+    char rule[400]; snprintf(rule, sizeof(rule), "%s", st_last_error());
+    return st_fail(ST_ERR_ARG, "%s: %s", name, rule);
+}
+static int refuse_wide(const char* name, const char* hint, const st_dims* d)
+{
+    ST_REQ(!ae_is_wide(d), "%s: not supported for the wide autoencoder geometries (T = %d > 32 or OT = %d > 16): %s", name, d->T, d->OT, hint);
+    return ST_OK;
+}
+static int pcm_align(int fmt) { return fmt == ST_PCM_S16 ? 8 : 16; }      // one quad of samples is one aligned access
+// a pointer the entry needs: present, and aligned to `align` bytes (1: any address)
+static int check_ptr(const char* name, const char* what, const void* p, int align)
+{
+    ST_REQ(p, "%s: null pointer (%s)", name, what);
+    ST_REQ((reinterpret_cast<uintptr_t>(p) & (uintptr_t)(align - 1)) == 0, "%s: %s must be %d-byte aligned", name, what, align);
+    return ST_OK;
+}
+// the recording and the workspace: parameters, a positive length, a known format, bases a quad access can take
+static int check_recording(const char* name, const float* params, int fmt, const void* signal, long long n, const void* ws)
+{
+    ST_TRY(check_ptr(name, "params", params, 1));
+    ST_REQ(n > 0, "%s: n must be positive (n = %lld)", name, n);
+    ST_REQ(fmt == ST_PCM_F32 || fmt == ST_PCM_S16, "%s: fmt = %d is neither ST_PCM_F32 nor ST_PCM_S16", name, fmt);
+    ST_TRY(check_ptr(name, "signal", signal, pcm_align(fmt)));
+    return check_ptr(name, "ws", ws, 16);
+}
+static int check_knob_rows(const char* name, const st_dims* d, long long n, long long knob_rows)
+{
+    const long long nwin = predict_windows(d, n);
+    ST_REQ(knob_rows == 1 || knob_rows == nwin, "%s: knob_rows = %lld must be 1 or the window count (%lld windows for n = %lld)", name, knob_rows, nwin, n);
+    return ST_OK;
+}
+// Adam's scalars of a fit entry, and what one step makes of them for the tail kernels (inv_n, inv_n_d and torch.optim.Adam's step constants)
+struct AdamArgs { long long first_step; int steps; float lr, beta1, beta2, eps; };
+static int check_adam(const char* name, const AdamArgs& h)
+{
+    ST_REQ(h.steps >= 1, "%s: steps = %d must be at least 1", name, h.steps);
+    ST_REQ(h.first_step >= 1, "%s: first_step = %lld must be at least 1 (Adam's step number is 1-based)", name, h.first_step);
+    ST_REQ(std::isfinite(h.lr) && h.lr >= 0.f, "%s: lr = %g must be finite and not negative", name, (double)h.lr);
+    ST_REQ(std::isfinite(h.beta1) && h.beta1 >= 0.f && h.beta1 < 1.f, "%s: beta1 = %g must lie in [0, 1)", name, (double)h.beta1);
+    ST_REQ(std::isfinite(h.beta2) && h.beta2 >= 0.f && h.beta2 < 1.f, "%s: beta2 = %g must lie in [0, 1)", name, (double)h.beta2);
+    ST_REQ(std::isfinite(h.eps) && h.eps > 0.f, "%s: eps = %g must be finite and positive", name, (double)h.eps);
+    return ST_OK;
+}
+static stf::TailArgs adam_step(const AdamArgs& h, int s, long long n_out)
+{
+    const double t = (double)(h.first_step + s);
+    const double bc1 = 1.0 - pow((double)h.beta1, t), bc2 = 1.0 - pow((double)h.beta2, t);
+    stf::TailArgs a{};
+    a.inv_n_d = 1.0 / (double)n_out; a.inv_n = (float)(1.0 / (double)n_out);
+    a.neg_step = (float)(-(double)h.lr / bc1); a.bc2_sqrt = (float)sqrt(bc2);
+    a.w1 = (float)(1.0 - (double)h.beta1); a.b2 = h.beta2; a.w2 = (float)(1.0 - (double)h.beta2); a.eps = h.eps;
+    return a;
+}
 extern "C" int st_predict_long(const st_dims* d, const float* params, int fmt, const void* signal, long long n,
                                const float* knobs, long long knob_rows, float* out, void* ws, void* stream)
 {
+    static const char* const name = "st_predict_long";
     Layout L; ST_TRY(make_layout(d, &L));
-    ST_REQ(params, "st_predict_long: null pointer (params)"); ST_REQ(signal, "st_predict_long: null pointer (signal)");
-    ST_REQ(knobs || d->K == 0, "st_predict_long: null pointer (knobs, K = %d)", d->K);
-    ST_REQ(out, "st_predict_long: null pointer (out)"); ST_REQ(ws, "st_predict_long: null pointer (ws)");
-    ST_REQ(n > 0, "st_predict_long: n must be positive (n = %lld)", n);
-    ST_REQ(fmt == ST_PCM_F32 || fmt == ST_PCM_S16, "st_predict_long: fmt = %d is neither ST_PCM_F32 nor ST_PCM_S16", fmt);
-    const long long nwin = predict_windows(d, n);
-    ST_REQ(knob_rows == 1 || knob_rows == nwin, "st_predict_long: knob_rows = %lld must be 1 or the window count (%lld windows for n = %lld)", knob_rows, nwin, n);
-    const uintptr_t sa = fmt == ST_PCM_S16 ? 7 : 15;
-    ST_REQ((reinterpret_cast<uintptr_t>(signal) & sa) == 0, "st_predict_long: signal must be %d-byte aligned", (int)sa + 1);
-    ST_REQ((reinterpret_cast<uintptr_t>(out) & 15) == 0, "st_predict_long: out must be 16-byte aligned");
-    ST_REQ((reinterpret_cast<uintptr_t>(ws) & 15) == 0, "st_predict_long: ws must be 16-byte aligned");
-    ST_REQ(!ae_is_wide(d), "st_predict_long: not supported for the wide autoencoder geometries (T = %d > 32 or OT = %d > 16): st_predict_supported", d->T, d->OT);
+    ST_TRY(check_recording(name, params, fmt, signal, n, ws));
+    ST_REQ(knobs || d->K == 0, "%s: null pointer (knobs, K = %d)", name, d->K);
+    ST_TRY(check_ptr(name, "out", out, 16));
+    ST_TRY(check_knob_rows(name, d, n, knob_rows));
+    ST_TRY(refuse_wide(name, "st_predict_supported", d));
     const long long n_out = n - ((long long)d->L - d->y);
     if (n_out <= 0) return ST_OK;      // shorter than the first window's lookback: nothing to predict, nothing launched
     PredictWS p; predict_carve(d, ws, &p);
     prof_mark("begin", stream);
     ST_TRY(predict_prep(d, L, p, params, stream));
-    return fmt == ST_PCM_S16 ? predict_batches(d, L, p, params, reinterpret_cast<const short*>(signal), n, knobs, knob_rows, out, n_out, ws, stream)
-                             : predict_batches(d, L, p, params, reinterpret_cast<const float*>(signal), n, knobs, knob_rows, out, n_out, ws, stream);
+    return with_pcm(fmt, [&](auto z) { return predict_batches<decltype(z)>(d, L, p, params, signal, n, knobs, knob_rows, out, n_out, ws, stream); });
 }
 
 // ------------------------------------------------------------------------------ predict session: inference fed block by block (st_predict_stream.h)
@@ -2152,7 +2268,7 @@ static const int STREAM_MAX_CHANNELS = 65535;      // the carry kernel's grid.y
 extern "C" int st_predict_stream_open(const st_dims* d, const float* params, int channels, st_predict_stream* s, void* state, void* ws, void* stream)
 {
     Layout L; ST_TRY(make_layout(d, &L));
-    ST_REQ(!ae_is_wide(d), "st_predict_stream_open: not supported for the wide autoencoder geometries (T = %d > 32 or OT = %d > 16): st_predict_supported", d->T, d->OT);
+    ST_TRY(refuse_wide("st_predict_stream_open", "st_predict_supported", d));
     ST_REQ(channels >= 1 && channels <= STREAM_MAX_CHANNELS, "st_predict_stream_open: channels = %d must lie in 1 .. %d", channels, STREAM_MAX_CHANNELS);
     ST_REQ(params, "st_predict_stream_open: null pointer (params)"); ST_REQ(s, "st_predict_stream_open: null pointer (s)");
     ST_REQ(state, "st_predict_stream_open: null pointer (state)"); ST_REQ(ws, "st_predict_stream_open: null pointer (ws)");
@@ -2172,42 +2288,25 @@ extern "C" int st_predict_stream_reset(st_predict_stream* s)
     s->received = s->emitted = 0; s->held = 0; s->half = 0; s->closed = 0;
     return ST_OK;
 }
-// One push's batches: the launches of predict_batches for !fit && !cj, with the stream's two streamers around them.
+// One push's batches: st_predict_long's batch with the stream's stage and overlap-add kernels around the forward.
 template <typename T>
 static int stream_batches(const st_dims* d, const Layout& L, const PredictWS& p, const float* params, const sts::Src& src, int channels,
                           const long long plan[4], const float* knobs, long long knob_rows, float* out, long long out_pitch, void* ws, void* stream)
 {
-    const float* Wr = params + L.offs[0]; const float* Wi = params + L.offs[1];
-    const float* ae_m = params + L.offs[4]; const float* ae_p = params + L.offs[22];
-    const bool g16 = stft_family(d, GEMM_ANALYSIS, SGP_PADDED | SGP_G16) == GF_G16, img = predict_img(d);      // as predict_batches
     const long long rows = plan[1] * channels;
     for (long long r0 = 0; r0 < rows; r0 += d->B) {
-        st_dims q = *d; q.B = (int)(rows - r0 < d->B ? rows - r0 : d->B);
-        WS w; carve(&q, L, reinterpret_cast<char*>(ws) + p.head_bytes, &w);
-        w.g16 = g16;
-        w.Sfold = p.Sfold; w.SfoldT = p.SfoldT; w.Sfold16 = p.Sfold16; w.SfoldT16 = p.SfoldT16; w.W16 = p.W16;
-        w.pl_W = p.pl_W; w.pl_Sfold = p.pl_Sfold; w.pl_SfoldT = p.pl_SfoldT;
-        const stg::RowMap map = stg::live_frames(q.T, q.H, q.N, q.N, q.L);
+        const InferBatch b = infer_batch(d, L, p, params, ws, p.head_bytes, rows - r0 < d->B ? rows - r0 : d->B);
+        const st_dims& q = b.q;
         sts::StageArgs a;
-        a.s = src; a.first = plan[0]; a.nw = plan[1]; a.r0 = r0; a.y = q.y; a.L = q.L; a.pad = q.N; a.nb = q.B;
-        a.xp = w.xp; a.xp16 = w.xp16; a.ht = g16 ? gemm_ht(q.prec) : 0;
-        a.nbx = ((q.L + 2 * q.N) / 4 + 255) / 256; a.n_pad = a.nbx * q.B;
-        a.mag = w.mag; a.phs = w.phs; a.T = q.T; a.F = q.F; a.t_lo = map.t_lo; a.Tv = map.Tv; a.n_dead = q.B * (q.T - map.Tv);
-        a.knob_src = knobs; a.knob_stride = knob_rows == 1 ? 0 : q.K; a.knobs = p.knobs; a.K = q.K; a.n_kn = q.K > 0 ? (q.B * q.K + 255) / 256 : 0;
-        const float* kn = q.K == 0 ? params : p.knobs;      // K == 0: any resident float (call_begin)
-        hipLaunchKernelGGL(sts::stream_stage_kernel<T>, dim3(a.n_pad + a.n_dead + a.n_kn), dim3(256), 0, st_stream(stream), a);
+        a.c = stage_common(b, true);
+        a.s = src; a.first = plan[0]; a.nw = plan[1]; a.r0 = r0;
+        a.knob_src = knobs; a.knob_stride = knob_rows == 1 ? 0 : q.K;
+        hipLaunchKernelGGL(sts::stream_stage_kernel<T>, dim3(a.c.n_pad + a.c.n_dead + a.c.n_kn), dim3(256), 0, st_stream(stream), a);
         ST_LAUNCHED("stream_stage");
-        ST_TRY(stft_gemm(step_stft_plan(&q, w, GEMM_ANALYSIS, Wr, Wi), GemmOut{nullptr, nullptr, w.mag, w.phs, nullptr, nullptr}, stream));
-        ST_TRY(ae_fwd_body(&q, L, w.mag, w.phs, kn, ae_m, ae_p, w.mag_hat, w.phs_hat, w.AA, w.reg_p, nullptr, stream, g16 ? w.AA16 : nullptr, false, nullptr,
-                           img ? p.img : nullptr));
-        ST_TRY(stft_gemm(step_stft_plan(&q, w, GEMM_FRAMES), slabs_at(w.frs), stream));
-        const int ns = frame_slabs(&q);
-        const dim3 grid((q.y / 4 + 255) / 256, q.B);
-        const size_t slab = (size_t)q.B * q.OT * q.N;
-        const bool three = (q.N + q.H - 1) / q.H <= 3;      // as predict_batches
-        with_bool(three, [&](auto NF3) { with_slabs(ns, [&](auto NS) {
-            hipLaunchKernelGGL((sts::stream_ola_kernel<T, NS(), NF3() ? 3 : 0>), grid, dim3(256), 0, st_stream(stream),
-                               w.frs, slab, src, out, out_pitch, plan[0], plan[1], r0, plan[2], q.L, q.N, q.H, q.OT, q.y); }); });
+        ST_TRY(infer_forward(b, b.resident_knobs(), false, stream));
+        ola_launch(b, [&](auto NS, auto NF, dim3 grid, size_t slab) {
+            hipLaunchKernelGGL((sts::stream_ola_kernel<T, NS(), NF()>), grid, dim3(256), 0, st_stream(stream),
+                               b.w.frs, slab, src, out, out_pitch, plan[0], plan[1], r0, plan[2], q.L, q.N, q.H, q.OT, q.y); });
         ST_LAUNCHED("stream_ola");
     }
     return ST_OK;
@@ -2216,7 +2315,7 @@ extern "C" int st_predict_stream_push(const st_dims* d, const float* params, st_
                                       int final, const float* knobs, long long knob_rows, float* out, long long out_pitch, void* state, void* ws, void* stream)
 {
     Layout L; ST_TRY(make_layout(d, &L));
-    ST_REQ(!ae_is_wide(d), "st_predict_stream_push: not supported for the wide autoencoder geometries (T = %d > 32 or OT = %d > 16): st_predict_supported", d->T, d->OT);
+    ST_TRY(refuse_wide("st_predict_stream_push", "st_predict_supported", d));
     ST_REQ(s, "st_predict_stream_push: null pointer (s)");
     ST_REQ(s->channels >= 1 && s->channels <= STREAM_MAX_CHANNELS, "st_predict_stream_push: channels = %d: the session was not opened by st_predict_stream_open", s->channels);
     ST_REQ(s->L == d->L && s->N == d->N && s->H == d->H && s->T == d->T && s->OT == d->OT && s->F == d->F && s->K == d->K && s->y == d->y,
@@ -2251,16 +2350,14 @@ extern "C" int st_predict_stream_push(const st_dims* d, const float* params, st_
     prof_mark("begin", stream);
     if (plan[1] > 0) {
         PredictWS p; predict_carve(d, ws, &p);
-        ST_TRY(fmt == ST_PCM_S16 ? stream_batches<short>(d, L, p, params, src, s->channels, plan, knobs, knob_rows, out, out_pitch, ws, stream)
-                                 : stream_batches<float>(d, L, p, params, src, s->channels, plan, knobs, knob_rows, out, out_pitch, ws, stream));
+        ST_TRY(with_pcm(fmt, [&](auto z) { return stream_batches<decltype(z)>(d, L, p, params, src, s->channels, plan, knobs, knob_rows, out, out_pitch, ws, stream); }));
     }
     if (!final && m > 0) {      // what no complete window has consumed, to the other half; a final push keeps nothing
         const int held1 = (int)plan[3];
         if (held1 > 0) {
             const dim3 grid((held1 / 4 + 255) / 256, s->channels);
             float* next = hist + (s->half ^ 1) * half;
-            if (fmt == ST_PCM_S16) hipLaunchKernelGGL(sts::stream_carry_kernel<short>, grid, dim3(256), 0, st_stream(stream), src, next, n0 + m - held1, held1);
-            else hipLaunchKernelGGL(sts::stream_carry_kernel<float>, grid, dim3(256), 0, st_stream(stream), src, next, n0 + m - held1, held1);
+            with_pcm(fmt, [&](auto z) { hipLaunchKernelGGL(sts::stream_carry_kernel<decltype(z)>, grid, dim3(256), 0, st_stream(stream), src, next, n0 + m - held1, held1); });
             ST_LAUNCHED("stream_carry");
         }
         s->half ^= 1;
@@ -2293,12 +2390,10 @@ extern "C" size_t st_eval_pool_ws_bytes(const st_dims* d)
     return pb ? pb + pool_part_bytes(d) : 0;
 }
 template <typename T>
-static int pool_batches(const st_dims* d, const Layout& L, const PredictWS& p, const float* params, const T* pool_x, const T* pool_y, const stq::Tables& tb,
+static int pool_batches(const st_dims* d, const Layout& L, const PredictWS& p, const float* params, const void* pool_x_v, const void* pool_y_v, const stq::Tables& tb,
                         long long total_rows, const float* file_knobs, double* stats, float* out, void* ws, void* stream)
 {
-    const float* Wr = params + L.offs[0]; const float* Wi = params + L.offs[1];
-    const float* ae_m = params + L.offs[4]; const float* ae_p = params + L.offs[22];
-    const bool g16 = stft_family(d, GEMM_ANALYSIS, SGP_PADDED | SGP_G16) == GF_G16, img = predict_img(d);      // as predict_batches
+    const T* pool_x = reinterpret_cast<const T*>(pool_x_v); const T* pool_y = reinterpret_cast<const T*>(pool_y_v);
     float* part = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + p.head_bytes);
     const size_t batch_off = p.head_bytes + pool_part_bytes(d);
     const size_t plane = pool_part_plane(d);
@@ -2306,39 +2401,24 @@ static int pool_batches(const st_dims* d, const Layout& L, const PredictWS& p, c
     const int n_zero = tb.nfiles < 1024 ? tb.nfiles : 1024;
     if (total_rows == 0) {      // nothing to predict: the side role alone (the zero spans and the zero statistics)
         stq::StageArgs a{};
-        a.t = tb; a.L = d->L; a.y = d->y; a.out = out; a.stats = stats; a.n_zero = n_zero;
+        a.t = tb; a.c.L = d->L; a.c.y = d->y; a.out = out; a.stats = stats; a.n_zero = n_zero;
         hipLaunchKernelGGL(stq::pool_stage_kernel<T>, dim3(n_zero), dim3(256), 0, st_stream(stream), a);
         ST_LAUNCHED("pool_stage");
         return ST_OK;
     }
     for (long long r0 = 0; r0 < total_rows; r0 += d->B) {
-        st_dims q = *d; q.B = (int)(total_rows - r0 < d->B ? total_rows - r0 : d->B);
-        WS w; carve(&q, L, reinterpret_cast<char*>(ws) + batch_off, &w);
-        w.g16 = g16;
-        w.Sfold = p.Sfold; w.SfoldT = p.SfoldT; w.Sfold16 = p.Sfold16; w.SfoldT16 = p.SfoldT16; w.W16 = p.W16;
-        w.pl_W = p.pl_W; w.pl_Sfold = p.pl_Sfold; w.pl_SfoldT = p.pl_SfoldT;
-        const stg::RowMap map = stg::live_frames(q.T, q.H, q.N, q.N, q.L);
+        const InferBatch b = infer_batch(d, L, p, params, ws, batch_off, total_rows - r0 < d->B ? total_rows - r0 : d->B);
+        const st_dims& q = b.q;
         stq::StageArgs a;
-        a.pool_x = pool_x; a.t = tb; a.r0 = r0; a.y = q.y; a.L = q.L; a.pad = q.N; a.nb = q.B;
-        a.xp = w.xp; a.xp16 = w.xp16; a.ht = g16 ? gemm_ht(q.prec) : 0;
-        a.nbx = ((q.L + 2 * q.N) / 4 + 255) / 256; a.n_pad = a.nbx * q.B;
-        a.mag = w.mag; a.phs = w.phs; a.T = q.T; a.F = q.F; a.t_lo = map.t_lo; a.Tv = map.Tv; a.n_dead = q.B * (q.T - map.Tv);
-        a.file_knobs = file_knobs; a.knobs = p.knobs; a.K = q.K; a.n_kn = q.K > 0 ? (q.B * q.K + 255) / 256 : 0;
+        a.c = stage_common(b, true);
+        a.pool_x = pool_x; a.t = tb; a.r0 = r0; a.file_knobs = file_knobs;
         a.out = out; a.stats = stats; a.n_zero = r0 == 0 ? n_zero : 0;
-        const float* kn = q.K == 0 ? params : p.knobs;      // K == 0: any resident float (call_begin)
-        hipLaunchKernelGGL(stq::pool_stage_kernel<T>, dim3(a.n_pad + a.n_dead + a.n_kn + a.n_zero), dim3(256), 0, st_stream(stream), a);
+        hipLaunchKernelGGL(stq::pool_stage_kernel<T>, dim3(a.c.n_pad + a.c.n_dead + a.c.n_kn + a.n_zero), dim3(256), 0, st_stream(stream), a);
         ST_LAUNCHED("pool_stage");
-        ST_TRY(stft_gemm(step_stft_plan(&q, w, GEMM_ANALYSIS, Wr, Wi), GemmOut{nullptr, nullptr, w.mag, w.phs, nullptr, nullptr}, stream));
-        ST_TRY(ae_fwd_body(&q, L, w.mag, w.phs, kn, ae_m, ae_p, w.mag_hat, w.phs_hat, w.AA, w.reg_p, nullptr, stream, g16 ? w.AA16 : nullptr, false, nullptr,
-                           img ? p.img : nullptr));
-        ST_TRY(stft_gemm(step_stft_plan(&q, w, GEMM_FRAMES), slabs_at(w.frs), stream));
-        const int ns = frame_slabs(&q);
-        const dim3 grid((q.y / 4 + 255) / 256, q.B);
-        const size_t slab = (size_t)q.B * q.OT * q.N;
-        const bool three = (q.N + q.H - 1) / q.H <= 3;      // as predict_batches
-        with_bool(three, [&](auto NF3) { with_slabs(ns, [&](auto NS) {
-            hipLaunchKernelGGL((stq::pool_ola_kernel<T, NS(), NF3() ? 3 : 0>), grid, dim3(256), 0, st_stream(stream),
-                               w.frs, slab, pool_x, pool_y, out, part, plane, nslot, tb, r0, q.L, q.N, q.H, q.OT, q.y); }); });
+        ST_TRY(infer_forward(b, b.resident_knobs(), false, stream));
+        ola_launch(b, [&](auto NS, auto NF, dim3 grid, size_t slab) {
+            hipLaunchKernelGGL((stq::pool_ola_kernel<T, NS(), NF()>), grid, dim3(256), 0, st_stream(stream),
+                               b.w.frs, slab, pool_x, pool_y, out, part, plane, nslot, tb, r0, q.L, q.N, q.H, q.OT, q.y); });
         ST_LAUNCHED("pool_ola");
         if (stats) {
             hipLaunchKernelGGL(stq::pool_tail_kernel, dim3(q.B), dim3(256), 0, st_stream(stream), (const float*)part, plane, nslot, tb, r0, q.B, q.L, q.y, stats);
@@ -2352,7 +2432,7 @@ extern "C" int st_eval_pool(const st_dims* d, const float* params, int fmt, cons
                             long long total_rows, long long pool_samples, const float* file_knobs, double* stats, float* out, void* ws, void* stream)
 {
     Layout L; ST_TRY(make_layout(d, &L));
-    ST_REQ(!ae_is_wide(d), "st_eval_pool: not supported for the wide autoencoder geometries (T = %d > 32 or OT = %d > 16): st_eval_pool_supported", d->T, d->OT);
+    ST_TRY(refuse_wide("st_eval_pool", "st_eval_pool_supported", d));
     ST_REQ(params, "st_eval_pool: null pointer (params)"); ST_REQ(pool_x, "st_eval_pool: null pointer (pool_x)");
     ST_REQ(file_off, "st_eval_pool: null pointer (file_off)"); ST_REQ(file_len, "st_eval_pool: null pointer (file_len)"); ST_REQ(win_off, "st_eval_pool: null pointer (win_off)");
     ST_REQ(file_knobs || d->K == 0, "st_eval_pool: null pointer (file_knobs, K = %d)", d->K);
@@ -2378,8 +2458,7 @@ extern "C" int st_eval_pool(const st_dims* d, const float* params, int fmt, cons
     const stq::Tables tb{file_off, file_len, win_off, nfiles, pool_samples};
     prof_mark("begin", stream);
     if (total_rows > 0) { ST_TRY(predict_prep(d, L, p, params, stream)); }
-    return fmt == ST_PCM_S16 ? pool_batches(d, L, p, params, reinterpret_cast<const short*>(pool_x), reinterpret_cast<const short*>(pool_y), tb, total_rows, file_knobs, stats, out, ws, stream)
-                             : pool_batches(d, L, p, params, reinterpret_cast<const float*>(pool_x), reinterpret_cast<const float*>(pool_y), tb, total_rows, file_knobs, stats, out, ws, stream);
+    return with_pcm(fmt, [&](auto z) { return pool_batches<decltype(z)>(d, L, p, params, pool_x, pool_y, tb, total_rows, file_knobs, stats, out, ws, stream); });
 }
 
 // ------------------------------------------------------------------------------ knob fit on the device (st_fit.h)
@@ -2404,39 +2483,19 @@ extern "C" size_t st_fit_knobs_ws_bytes(const st_dims* d)
     return pb + f.bytes;
 }
 static int fit_knobs_impl(const char* name, const bool coded, const st_dims* d, const float* params, const float* code, int fmt, const void* signal, const void* target, long long n,
-                          float* knobs, long long knob_rows, float* adam_m, float* adam_v,
-                          long long first_step, int steps, float lr, float beta1, float beta2, float eps,
+                          float* knobs, long long knob_rows, float* adam_m, float* adam_v, const AdamArgs& h,
                           double* loss_hist, float* grad_hist, void* ws, void* stream)
 {
-    Layout L;
-    if (make_layout(d, &L) != ST_OK) {      // the dims rule that failed, under this entry's name
-        char rule[400]; snprintf(rule, sizeof(rule), "%s", st_last_error());
-        return st_fail(ST_ERR_ARG, "%s: %s", name, rule);
-    }
+    Layout L; ST_TRY(layout_named(name, d, &L));
     ST_REQ(d->K >= 1, "%s: K = %d (a model without knobs has no knobs to fit)", name, d->K);
-    ST_REQ(params, "%s: null pointer (params)", name); ST_REQ(signal, "%s: null pointer (signal)", name); ST_REQ(target, "%s: null pointer (target)", name);
-    ST_REQ(knobs, "%s: null pointer (knobs)", name); ST_REQ(adam_m, "%s: null pointer (adam_m)", name); ST_REQ(adam_v, "%s: null pointer (adam_v)", name);
-    ST_REQ(loss_hist, "%s: null pointer (loss_hist)", name); ST_REQ(ws, "%s: null pointer (ws)", name);
-    ST_REQ(code || !coded, "%s: null pointer (code)", name);
-    ST_REQ(n > 0, "%s: n must be positive (n = %lld)", name, n);
-    ST_REQ(fmt == ST_PCM_F32 || fmt == ST_PCM_S16, "%s: fmt = %d is neither ST_PCM_F32 nor ST_PCM_S16", name, fmt);
-    const long long nwin = predict_windows(d, n);
-    ST_REQ(knob_rows == 1 || knob_rows == nwin, "%s: knob_rows = %lld must be 1 or the window count (%lld windows for n = %lld)", name, knob_rows, nwin, n);
-    ST_REQ(steps >= 1, "%s: steps = %d must be at least 1", name, steps);
-    ST_REQ(first_step >= 1, "%s: first_step = %lld must be at least 1 (Adam's step number is 1-based)", name, first_step);
-    ST_REQ(std::isfinite(lr) && lr >= 0.f, "%s: lr = %g must be finite and not negative", name, (double)lr);
-    ST_REQ(std::isfinite(beta1) && beta1 >= 0.f && beta1 < 1.f, "%s: beta1 = %g must lie in [0, 1)", name, (double)beta1);
-    ST_REQ(std::isfinite(beta2) && beta2 >= 0.f && beta2 < 1.f, "%s: beta2 = %g must lie in [0, 1)", name, (double)beta2);
-    ST_REQ(std::isfinite(eps) && eps > 0.f, "%s: eps = %g must be finite and positive", name, (double)eps);
-    const uintptr_t sa = fmt == ST_PCM_S16 ? 7 : 15;
-    ST_REQ((reinterpret_cast<uintptr_t>(signal) & sa) == 0, "%s: signal must be %d-byte aligned", name, (int)sa + 1);
-    ST_REQ((reinterpret_cast<uintptr_t>(target) & sa) == 0, "%s: target must be %d-byte aligned", name, (int)sa + 1);
-    ST_REQ((reinterpret_cast<uintptr_t>(knobs) & 15) == 0, "%s: knobs must be 16-byte aligned", name);
-    ST_REQ((reinterpret_cast<uintptr_t>(adam_m) & 15) == 0, "%s: adam_m must be 16-byte aligned", name);
-    ST_REQ((reinterpret_cast<uintptr_t>(adam_v) & 15) == 0, "%s: adam_v must be 16-byte aligned", name);
-    ST_REQ((reinterpret_cast<uintptr_t>(ws) & 15) == 0, "%s: ws must be 16-byte aligned", name);
-    ST_REQ((reinterpret_cast<uintptr_t>(code) & 15) == 0, "%s: code must be 16-byte aligned", name);
-    ST_REQ(!ae_is_wide(d), "%s: not supported for the wide autoencoder geometries (T = %d > 32 or OT = %d > 16): st_fit_knobs_supported", name, d->T, d->OT);
+    ST_TRY(check_recording(name, params, fmt, signal, n, ws));
+    ST_TRY(check_ptr(name, "target", target, pcm_align(fmt)));
+    ST_TRY(check_ptr(name, "knobs", knobs, 16)); ST_TRY(check_ptr(name, "adam_m", adam_m, 16)); ST_TRY(check_ptr(name, "adam_v", adam_v, 16));
+    ST_TRY(check_ptr(name, "loss_hist", loss_hist, 1));
+    if (coded) ST_TRY(check_ptr(name, "code", code, 16));
+    ST_TRY(check_knob_rows(name, d, n, knob_rows));
+    ST_TRY(check_adam(name, h));
+    ST_TRY(refuse_wide(name, "st_fit_knobs_supported", d));
     const long long n_out = n - ((long long)d->L - d->y);
     if (n_out <= 0) return ST_OK;      // no output sample, no objective: nothing launched, every buffer left alone
     PredictWS p; predict_carve(d, ws, &p);
@@ -2445,20 +2504,14 @@ static int fit_knobs_impl(const char* name, const bool coded, const st_dims* d, 
     prof_mark("begin", stream);
     ST_TRY(predict_prep(d, L, p, params, stream));
     const size_t row_floats = (size_t)knob_rows * d->K;
-    for (int s = 0; s < steps; ++s) {
-        const double t = (double)(first_step + s);
-        const double bc1 = 1.0 - pow((double)beta1, t), bc2 = 1.0 - pow((double)beta2, t);
+    for (int s = 0; s < h.steps; ++s) {
         FitJob job;
         job.target = target; job.kg = f.kg; job.rows = f.rows; job.acc = f.acc;
         job.knobs = knobs; job.m = adam_m; job.v = adam_v; job.grad = grad_hist ? grad_hist + (size_t)s * row_floats : nullptr; job.loss = loss_hist + s;
-        job.hyper = stf::TailArgs{};
-        job.hyper.inv_n_d = 1.0 / (double)n_out; job.hyper.inv_n = (float)(1.0 / (double)n_out);
-        job.hyper.neg_step = (float)(-(double)lr / bc1); job.hyper.bc2_sqrt = (float)sqrt(bc2);
-        job.hyper.w1 = (float)(1.0 - (double)beta1); job.hyper.b2 = beta2; job.hyper.w2 = (float)(1.0 - (double)beta2); job.hyper.eps = eps;
+        job.hyper = adam_step(h, s, n_out);
         const CodeJob cj{nullptr, code, 1, 0, 0};
-        const CodeJob* const cjp = coded ? &cj : nullptr;
-        ST_TRY(fmt == ST_PCM_S16 ? predict_batches(d, L, p, params, reinterpret_cast<const short*>(signal), n, knobs, knob_rows, nullptr, n_out, ws, stream, &job, batch_off, cjp)
-                                 : predict_batches(d, L, p, params, reinterpret_cast<const float*>(signal), n, knobs, knob_rows, nullptr, n_out, ws, stream, &job, batch_off, cjp));
+        ST_TRY(with_pcm(fmt, [&](auto z) {
+            return predict_batches<decltype(z)>(d, L, p, params, signal, n, knobs, knob_rows, nullptr, n_out, ws, stream, &job, batch_off, coded ? &cj : nullptr); }));
     }
     return ST_OK;
 }
@@ -2467,8 +2520,8 @@ extern "C" int st_fit_knobs(const st_dims* d, const float* params, int fmt, cons
                             long long first_step, int steps, float lr, float beta1, float beta2, float eps,
                             double* loss_hist, float* grad_hist, void* ws, void* stream)
 {
-    return fit_knobs_impl("st_fit_knobs", false, d, params, nullptr, fmt, signal, target, n, knobs, knob_rows, adam_m, adam_v, first_step, steps, lr, beta1, beta2, eps,
-                          loss_hist, grad_hist, ws, stream);
+    return fit_knobs_impl("st_fit_knobs", false, d, params, nullptr, fmt, signal, target, n, knobs, knob_rows, adam_m, adam_v,
+                          AdamArgs{first_step, steps, lr, beta1, beta2, eps}, loss_hist, grad_hist, ws, stream);
 }
 // st_fit_knobs from the code of the recording (st_encode_long): every step's forward is the decoder forward; everything behind the frames GEMM is st_fit_knobs'.
 extern "C" int st_fit_knobs_coded(const st_dims* d, const float* params, const void* code, int fmt, const void* signal, const void* target, long long n,
@@ -2477,7 +2530,7 @@ extern "C" int st_fit_knobs_coded(const st_dims* d, const float* params, const v
                                   double* loss_hist, float* grad_hist, void* ws, void* stream)
 {
     return fit_knobs_impl("st_fit_knobs_coded", true, d, params, reinterpret_cast<const float*>(code), fmt, signal, target, n, knobs, knob_rows, adam_m, adam_v,
-                          first_step, steps, lr, beta1, beta2, eps, loss_hist, grad_hist, ws, stream);
+                          AdamArgs{first_step, steps, lr, beta1, beta2, eps}, loss_hist, grad_hist, ws, stream);
 }
 
 // ------------------------------------------------------------------------------ encode once, decode at any knob setting (st_decode.h)
@@ -2493,20 +2546,10 @@ extern "C" size_t st_code_bytes(const st_dims* d, long long n)
 // what st_encode_long and st_decode_long ask of the recording and the workspace, under the entry's name
 static int coded_args(const char* name, const st_dims* d, Layout* L, const float* params, const void* code, int fmt, const void* signal, long long n, const void* ws)
 {
-    if (make_layout(d, L) != ST_OK) {
-        char rule[400]; snprintf(rule, sizeof(rule), "%s", st_last_error());
-        return st_fail(ST_ERR_ARG, "%s: %s", name, rule);
-    }
-    ST_REQ(params, "%s: null pointer (params)", name); ST_REQ(code, "%s: null pointer (code)", name); ST_REQ(signal, "%s: null pointer (signal)", name);
-    ST_REQ(ws, "%s: null pointer (ws)", name);
-    ST_REQ(n > 0, "%s: n must be positive (n = %lld)", name, n);
-    ST_REQ(fmt == ST_PCM_F32 || fmt == ST_PCM_S16, "%s: fmt = %d is neither ST_PCM_F32 nor ST_PCM_S16", name, fmt);
-    const uintptr_t sa = fmt == ST_PCM_S16 ? 7 : 15;
-    ST_REQ((reinterpret_cast<uintptr_t>(signal) & sa) == 0, "%s: signal must be %d-byte aligned", name, (int)sa + 1);
-    ST_REQ((reinterpret_cast<uintptr_t>(code) & 15) == 0, "%s: code must be 16-byte aligned", name);
-    ST_REQ((reinterpret_cast<uintptr_t>(ws) & 15) == 0, "%s: ws must be 16-byte aligned", name);
-    ST_REQ(!ae_is_wide(d), "%s: not supported for the wide autoencoder geometries (T = %d > 32 or OT = %d > 16): st_decode_supported", name, d->T, d->OT);
-    return ST_OK;
+    ST_TRY(layout_named(name, d, L));
+    ST_TRY(check_recording(name, params, fmt, signal, n, ws));
+    ST_TRY(check_ptr(name, "code", code, 16));
+    return refuse_wide(name, "st_decode_supported", d);
 }
 extern "C" int st_encode_long(const st_dims* d, const float* params, int fmt, const void* signal, long long n, void* code, void* ws, void* stream)
 {
@@ -2517,29 +2560,25 @@ extern "C" int st_encode_long(const st_dims* d, const float* params, int fmt, co
     prof_mark("begin", stream);
     ST_TRY(predict_prep(d, L, p, params, stream));
     const CodeJob cj{reinterpret_cast<float*>(code), nullptr, 1, 0, 0};
-    return fmt == ST_PCM_S16 ? predict_batches(d, L, p, params, reinterpret_cast<const short*>(signal), n, nullptr, 1, nullptr, n_out, ws, stream, nullptr, 0, &cj)
-                             : predict_batches(d, L, p, params, reinterpret_cast<const float*>(signal), n, nullptr, 1, nullptr, n_out, ws, stream, nullptr, 0, &cj);
+    return with_pcm(fmt, [&](auto z) { return predict_batches<decltype(z)>(d, L, p, params, signal, n, nullptr, 1, nullptr, n_out, ws, stream, nullptr, 0, &cj); });
 }
 extern "C" int st_decode_long(const st_dims* d, const float* params, const void* code, int fmt, const void* signal, long long n,
                               const float* knobs, long long knob_rows, int n_settings, float* out, long long out_pitch, void* ws, void* stream)
 {
     Layout L; ST_TRY(coded_args("st_decode_long", d, &L, params, code, fmt, signal, n, ws));
     ST_REQ(knobs || d->K == 0, "st_decode_long: null pointer (knobs, K = %d)", d->K);
-    ST_REQ(out, "st_decode_long: null pointer (out)");
-    const long long nwin = predict_windows(d, n);
-    ST_REQ(knob_rows == 1 || knob_rows == nwin, "st_decode_long: knob_rows = %lld must be 1 or the window count (%lld windows for n = %lld)", knob_rows, nwin, n);
+    ST_TRY(check_ptr("st_decode_long", "out", out, 16));
+    ST_TRY(check_knob_rows("st_decode_long", d, n, knob_rows));
     ST_REQ(n_settings >= 1, "st_decode_long: n_settings = %d must be at least 1", n_settings);
     const long long n_out = n - ((long long)d->L - d->y);
     ST_REQ(out_pitch >= n_out && out_pitch >= 0 && out_pitch % 4 == 0,
            "st_decode_long: out_pitch = %lld must be a multiple of 4 and at least the %lld output samples of a setting", out_pitch, n_out > 0 ? n_out : 0);
-    ST_REQ((reinterpret_cast<uintptr_t>(out) & 15) == 0, "st_decode_long: out must be 16-byte aligned");
     if (n_out <= 0) return ST_OK;
     PredictWS p; predict_carve(d, ws, &p);
     prof_mark("begin", stream);
     ST_TRY(predict_prep(d, L, p, params, stream));      // the parameter-only head (folded synthesis bases, their 16-bit / plane copies), once per call
     const CodeJob cj{nullptr, reinterpret_cast<const float*>(code), n_settings, out_pitch, (size_t)knob_rows * d->K};
-    return fmt == ST_PCM_S16 ? predict_batches(d, L, p, params, reinterpret_cast<const short*>(signal), n, knobs, knob_rows, out, n_out, ws, stream, nullptr, 0, &cj)
-                             : predict_batches(d, L, p, params, reinterpret_cast<const float*>(signal), n, knobs, knob_rows, out, n_out, ws, stream, nullptr, 0, &cj);
+    return with_pcm(fmt, [&](auto z) { return predict_batches<decltype(z)>(d, L, p, params, signal, n, knobs, knob_rows, out, n_out, ws, stream, nullptr, 0, &cj); });
 }
 
 // ------------------------------------------------------------------------------ many knob settings from one code (st_multi.h)
@@ -2577,25 +2616,16 @@ extern "C" size_t st_knob_multi_ws_bytes(const st_dims* d, int n_settings)
 static int multi_args(const char* name, const st_dims* d, Layout* L, const float* params, const void* code, int fmt, const void* signal, const void* target, long long n,
                       const float* knobs, long long knob_rows, int n_settings, const void* ws)
 {
-    if (make_layout(d, L) != ST_OK) {
-        char rule[400]; snprintf(rule, sizeof(rule), "%s", st_last_error());
-        return st_fail(ST_ERR_ARG, "%s: %s", name, rule);
-    }
+    ST_TRY(layout_named(name, d, L));
     ST_REQ(d->K >= 1, "%s: K = %d (a model without knobs has no knobs to fit)", name, d->K);
-    ST_REQ(params, "%s: null pointer (params)", name); ST_REQ(code, "%s: null pointer (code)", name); ST_REQ(signal, "%s: null pointer (signal)", name);
-    ST_REQ(target, "%s: null pointer (target)", name); ST_REQ(knobs, "%s: null pointer (knobs)", name); ST_REQ(ws, "%s: null pointer (ws)", name);
-    ST_REQ(n > 0, "%s: n must be positive (n = %lld)", name, n);
-    ST_REQ(fmt == ST_PCM_F32 || fmt == ST_PCM_S16, "%s: fmt = %d is neither ST_PCM_F32 nor ST_PCM_S16", name, fmt);
-    const long long nwin = predict_windows(d, n);
-    ST_REQ(knob_rows == 1 || knob_rows == nwin, "%s: knob_rows = %lld must be 1 or the window count (%lld windows for n = %lld)", name, knob_rows, nwin, n);
+    ST_TRY(check_recording(name, params, fmt, signal, n, ws));
+    ST_TRY(check_ptr(name, "code", code, 16));
+    ST_TRY(check_ptr(name, "target", target, pcm_align(fmt)));
+    ST_TRY(check_ptr(name, "knobs", knobs, 16));
+    ST_TRY(check_knob_rows(name, d, n, knob_rows));
     ST_REQ(n_settings >= 1, "%s: n_settings = %d must be at least 1", name, n_settings);
-    const uintptr_t sa = fmt == ST_PCM_S16 ? 7 : 15;
-    ST_REQ((reinterpret_cast<uintptr_t>(signal) & sa) == 0, "%s: signal must be %d-byte aligned", name, (int)sa + 1);
-    ST_REQ((reinterpret_cast<uintptr_t>(target) & sa) == 0, "%s: target must be %d-byte aligned", name, (int)sa + 1);
-    ST_REQ((reinterpret_cast<uintptr_t>(knobs) & 15) == 0, "%s: knobs must be 16-byte aligned", name);
-    ST_REQ((reinterpret_cast<uintptr_t>(ws) & 15) == 0, "%s: ws must be 16-byte aligned", name);
-    ST_REQ((reinterpret_cast<uintptr_t>(code) & 15) == 0, "%s: code must be 16-byte aligned", name);
-    ST_REQ(!ae_is_wide(d), "%s: not supported for the wide autoencoder geometries (T = %d > 32 or OT = %d > 16): st_fit_knobs_supported", name, d->T, d->OT);
+    ST_TRY(refuse_wide(name, "st_fit_knobs_supported", d));
+    const long long nwin = predict_windows(d, n);
     stx::MultiPlan mp;
     ST_REQ(multi_plan_of(d, n, n_settings, &mp), "%s: the plan of %lld windows x %d settings does not fit (st_knob_multi_plan)", name, nwin, n_settings);
     // the 32-bit element offsets of the kernels (predict_batches' guards) at the plan's largest batch: its rows are the stacked (setting, window) pairs
@@ -2615,13 +2645,12 @@ struct MultiJob {
     double inv_n_d; float *acc, *lp_all;    // lp_all: [S][ola_loss_partials(d)], the score's partials of every setting of a window batch
 };
 template <typename T>
-static int multi_batches(const st_dims* d, const Layout& L, const PredictWS& p, const float* params, const T* signal, long long n_out, const MultiJob& j,
+static int multi_batches(const st_dims* d, const Layout& L, const PredictWS& p, const float* params, const void* signal_v, long long n_out, const MultiJob& j,
                          void* ws, size_t batch_off, void* stream)
 {
+    const T* signal = reinterpret_cast<const T*>(signal_v);
     const FitJob* const fit = j.fit;
     const size_t CW = stc::code_window_floats(L.KP / 2, d->OT);
-    const float* ae_m = params + L.offs[4]; const float* ae_p = params + L.offs[22];
-    const bool g16 = stft_family(d, GEMM_ANALYSIS, SGP_PADDED | SGP_G16) == GF_G16;      // as predict_batches
     const bool one = j.knob_rows == 1;
     const size_t set_stride = (size_t)j.knob_rows * d->K;
     const stx::MultiPlan mp = stx::multi_plan(j.nwin, d->B, j.S);
@@ -2630,31 +2659,18 @@ static int multi_batches(const st_dims* d, const Layout& L, const PredictWS& p, 
     const size_t lpn = (size_t)ola_loss_partials(d);
     for (long long bi = 0; bi < cnt; ++bi) {
         const stx::MultiBatch mb = mp.at(bi);
-        st_dims q = *d; q.B = mb.nw * mb.ns;
-        WS w; carve(&q, L, reinterpret_cast<char*>(ws) + batch_off, &w);
-        w.g16 = g16;
-        w.Sfold = p.Sfold; w.SfoldT = p.SfoldT; w.Sfold16 = p.Sfold16; w.SfoldT16 = p.SfoldT16; w.W16 = p.W16;
-        w.pl_W = p.pl_W; w.pl_Sfold = p.pl_Sfold; w.pl_SfoldT = p.pl_SfoldT;
+        const InferBatch b = infer_batch(d, L, p, params, ws, batch_off, (long long)mb.nw * mb.ns);
+        const st_dims& q = b.q; const WS& w = b.w;
         const size_t ro = (size_t)mb.s0 * set_stride + (one ? 0 : (size_t)mb.w0 * q.K);      // the batch's first knob row
-        ST_TRY(with_ht(ae_ht(q.prec), [&](auto HT) {
-            return launch_lds("ae_dec_fwd_kernel", sta::ae_dec_fwd_kernel<sta::AE_DEC_NW, HT(), true>, dim3(ae_dec_grid(&q)), dim3(sta::AE_DEC_NW * 64),
-                              (size_t)sta::ae_dec_lds_floats() * sizeof(float), st_stream(stream),
-                              j.code + (size_t)mb.w0 * CW, (const float*)j.knobs + ro, one ? 0 : q.K, ae_m, ae_p, L.go,
-                              fit ? w.mag_hat : nullptr, fit ? w.phs_hat : nullptr, w.AA, g16 ? w.AA16 : nullptr, g16 ? gemm_ht(q.prec) : 0,
-                              fit ? w.aews : nullptr, fit ? w.mag : nullptr, fit ? p.knobs : nullptr, q.B, q.T, q.OT, q.F, q.K, L.KP, mb.nw, (unsigned)set_stride); }));
-        ST_LAUNCHED("ae_dec_fwd");
-        ST_TRY(stft_gemm(step_stft_plan(&q, w, GEMM_FRAMES), slabs_at(w.frs), stream));
-        const int ns = frame_slabs(&q);
-        const dim3 grid((q.y / 4 + 255) / 256, q.B);
-        const size_t slab = (size_t)q.B * q.OT * q.N;
-        const bool three = (q.N + q.H - 1) / q.H <= 3;
+        ST_TRY(dec_forward<true>(b, j.code + (size_t)mb.w0 * CW, (const float*)j.knobs + ro, one ? 0 : q.K, fit != nullptr, stream, mb.nw, (unsigned)set_stride));
+        ST_TRY(infer_frames(b, stream));
         const int nslot = (q.y + 255) / 256;
         const long long s0 = (long long)mb.w0 * q.y;
         float* const lp = defer ? j.lp_all + (size_t)mb.s0 * lpn : w.loss_p;
-        with_bool(fit != nullptr, [&](auto FIT) { with_bool(three, [&](auto NF3) { with_slabs(ns, [&](auto NS) {
-            hipLaunchKernelGGL((stf::fit_ola_kernel<T, NS(), NF3() ? 3 : 0, FIT() ? 1 : 2>), grid, dim3(256), 0, st_stream(stream),
-                               w.frs, slab, signal, reinterpret_cast<const T*>(j.target), w.dsyn, g16 ? w.dsyn16 : nullptr, g16 ? gemm_ht(q.prec) : 0, lp, nslot,
-                               s0, n_out, q.L, q.N, q.H, q.OT, q.y, mb.nw); }); }); });
+        with_bool(fit != nullptr, [&](auto FIT) { ola_launch(b, [&](auto NS, auto NF, dim3 grid, size_t slab) {
+            hipLaunchKernelGGL((stf::fit_ola_kernel<T, NS(), NF(), FIT() ? 1 : 2>), grid, dim3(256), 0, st_stream(stream),
+                               w.frs, slab, signal, reinterpret_cast<const T*>(j.target), w.dsyn, b.g16 ? w.dsyn16 : nullptr, b.ht(), lp, nslot,
+                               s0, n_out, q.L, q.N, q.H, q.OT, q.y, mb.nw); }); });
         ST_LAUNCHED("fit_ola");
         if (defer && mb.s0 + 1 < j.S) continue;
         const int ts0 = defer ? 0 : mb.s0, tns = defer ? j.S : mb.ns;      // the settings this tail launch folds
@@ -2666,19 +2682,7 @@ static int multi_batches(const st_dims* d, const Layout& L, const PredictWS& p, 
         m.t.per_window = !one; m.t.first = mb.w0 == 0; m.t.last = mb.w0 + mb.nw >= j.nwin;
         m.t.knobs = m.t.m = m.t.v = m.t.grad = nullptr;
         if (fit) {
-            ST_TRY(stft_gemm(step_stft_plan(&q, w, GEMM_DGRAD), slabs_at(w.dAA), stream));
-            const stg::RowMap live = synth_live(&q);
-            const int groups = ae_fwd_groups(&q), kgrid = ae_knob_grid(&q);
-            ST_TRY(with_ht(ae_ht(q.prec), [&](auto HT) {
-                return launch_lds("ae_knob_bwd_kernel", sta::ae_knob_bwd_kernel<AE_KNOB_NW, HT()>, dim3(kgrid, 2), dim3(AE_KNOB_NW * 64),
-                                  (size_t)sta::ae_knob_lds_floats(AE_KNOB_NW) * sizeof(float), st_stream(stream),
-                                  w.mag, (const float*)p.knobs, ae_m, ae_p, L.go, w.mag_hat, w.phs_hat, w.dAA, w.aews, fit->kg, q.B, q.T, q.OT, q.F, q.K, L.KP,
-                                  live.t_lo, live.t_lo + live.Tv - 1, synth_slabs(&q), (size_t)q.B * q.OT * L.KP); }));
-            ST_LAUNCHED("ae_knob_bwd");
-            const size_t w5 = (size_t)L.offs[4] + (size_t)L.go.w[4];
-            hipLaunchKernelGGL(knob_grad_kernel, dim3(q.B), dim3(64), 0, st_stream(stream), params + w5, (const float*)fit->kg, params + w5 + L.PG,
-                               (const float*)fit->kg + (size_t)groups * 16, q.K, fit->rows, L.KP / 32);
-            ST_LAUNCHED("knob_grad");
+            ST_TRY(knob_backward(b, p.knobs, *fit, stream));
             m.t.rows = fit->rows;
             m.t.knobs = fit->knobs + ro; m.t.m = fit->m + ro; m.t.v = fit->v + ro; m.t.grad = fit->grad ? fit->grad + ro : nullptr;
         }
@@ -2691,6 +2695,16 @@ static int multi_batches(const st_dims* d, const Layout& L, const PredictWS& p, 
     }
     return ST_OK;
 }
+// what both entries' jobs have in common; acc: the per-setting accumulators behind the fit's rows and scratch (st_knob_multi_ws_bytes).  fit, loss, win_loss and
+// lp_all (the score's alone) stay null for the entry to set.
+static MultiJob multi_job(const st_dims* d, const void* code, const void* target, long long n, int S, float* knobs, long long knob_rows, float* acc)
+{
+    MultiJob j{};
+    j.code = reinterpret_cast<const float*>(code); j.target = target; j.nwin = predict_windows(d, n); j.S = S; j.knobs = knobs; j.knob_rows = knob_rows;
+    j.inv_n_d = 1.0 / (double)(n - ((long long)d->L - d->y));
+    j.acc = acc;
+    return j;
+}
 extern "C" int st_score_knobs_coded(const st_dims* d, const float* params, const void* code, int fmt, const void* signal, const void* target, long long n,
                                     const float* knobs, long long knob_rows, int n_settings, double* loss, float* win_loss, void* ws, void* stream)
 {
@@ -2701,14 +2715,13 @@ extern "C" int st_score_knobs_coded(const st_dims* d, const float* params, const
     if (n_out <= 0) return ST_OK;      // no output sample, no objective: nothing launched, every buffer left alone
     PredictWS p; predict_carve(d, ws, &p);
     FitWS f; fit_carve(d, reinterpret_cast<char*>(ws) + p.head_bytes, &f);
-    MultiJob j{reinterpret_cast<const float*>(code), target, predict_windows(d, n), n_settings, const_cast<float*>(knobs), knob_rows, nullptr, loss, win_loss,
-               1.0 / (double)n_out, reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + p.head_bytes + f.bytes),
-               reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + p.head_bytes + f.bytes + multi_acc_bytes(n_settings))};
+    char* const extra = reinterpret_cast<char*>(ws) + p.head_bytes + f.bytes;
+    MultiJob j = multi_job(d, code, target, n, n_settings, const_cast<float*>(knobs), knob_rows, reinterpret_cast<float*>(extra));
+    j.loss = loss; j.win_loss = win_loss; j.lp_all = reinterpret_cast<float*>(extra + multi_acc_bytes(n_settings));
     const size_t batch_off = p.head_bytes + f.bytes + multi_extra_bytes(d, n_settings);
     prof_mark("begin", stream);
     ST_TRY(predict_prep(d, L, p, params, stream));
-    return fmt == ST_PCM_S16 ? multi_batches(d, L, p, params, reinterpret_cast<const short*>(signal), n_out, j, ws, batch_off, stream)
-                             : multi_batches(d, L, p, params, reinterpret_cast<const float*>(signal), n_out, j, ws, batch_off, stream);
+    return with_pcm(fmt, [&](auto z) { return multi_batches<decltype(z)>(d, L, p, params, signal, n_out, j, ws, batch_off, stream); });
 }
 extern "C" int st_fit_knobs_multi_coded(const st_dims* d, const float* params, const void* code, int fmt, const void* signal, const void* target, long long n,
                                         float* knobs, long long knob_rows, int n_settings, float* adam_m, float* adam_v,
@@ -2717,15 +2730,9 @@ extern "C" int st_fit_knobs_multi_coded(const st_dims* d, const float* params, c
 {
     static const char* const name = "st_fit_knobs_multi_coded";
     Layout L; ST_TRY(multi_args(name, d, &L, params, code, fmt, signal, target, n, knobs, knob_rows, n_settings, ws));
-    ST_REQ(adam_m, "%s: null pointer (adam_m)", name); ST_REQ(adam_v, "%s: null pointer (adam_v)", name); ST_REQ(loss_hist, "%s: null pointer (loss_hist)", name);
-    ST_REQ(steps >= 1, "%s: steps = %d must be at least 1", name, steps);
-    ST_REQ(first_step >= 1, "%s: first_step = %lld must be at least 1 (Adam's step number is 1-based)", name, first_step);
-    ST_REQ(std::isfinite(lr) && lr >= 0.f, "%s: lr = %g must be finite and not negative", name, (double)lr);
-    ST_REQ(std::isfinite(beta1) && beta1 >= 0.f && beta1 < 1.f, "%s: beta1 = %g must lie in [0, 1)", name, (double)beta1);
-    ST_REQ(std::isfinite(beta2) && beta2 >= 0.f && beta2 < 1.f, "%s: beta2 = %g must lie in [0, 1)", name, (double)beta2);
-    ST_REQ(std::isfinite(eps) && eps > 0.f, "%s: eps = %g must be finite and positive", name, (double)eps);
-    ST_REQ((reinterpret_cast<uintptr_t>(adam_m) & 15) == 0, "%s: adam_m must be 16-byte aligned", name);
-    ST_REQ((reinterpret_cast<uintptr_t>(adam_v) & 15) == 0, "%s: adam_v must be 16-byte aligned", name);
+    const AdamArgs h{first_step, steps, lr, beta1, beta2, eps};
+    ST_TRY(check_ptr(name, "adam_m", adam_m, 16)); ST_TRY(check_ptr(name, "adam_v", adam_v, 16)); ST_TRY(check_ptr(name, "loss_hist", loss_hist, 1));
+    ST_TRY(check_adam(name, h));
     const long long n_out = n - ((long long)d->L - d->y);
     if (n_out <= 0) return ST_OK;
     PredictWS p; predict_carve(d, ws, &p);
@@ -2735,19 +2742,13 @@ extern "C" int st_fit_knobs_multi_coded(const st_dims* d, const float* params, c
     ST_TRY(predict_prep(d, L, p, params, stream));      // once per call, whatever the number of starts and steps
     const size_t all_floats = (size_t)n_settings * knob_rows * d->K;
     for (int s = 0; s < steps; ++s) {
-        const double t = (double)(first_step + s);
-        const double bc1 = 1.0 - pow((double)beta1, t), bc2 = 1.0 - pow((double)beta2, t);
         FitJob job;
         job.target = target; job.kg = f.kg; job.rows = f.rows; job.acc = nullptr;
         job.knobs = knobs; job.m = adam_m; job.v = adam_v; job.grad = grad_hist ? grad_hist + (size_t)s * all_floats : nullptr; job.loss = nullptr;
-        job.hyper = stf::TailArgs{};      // st_fit_knobs' scalars of this step
-        job.hyper.inv_n_d = 1.0 / (double)n_out; job.hyper.inv_n = (float)(1.0 / (double)n_out);
-        job.hyper.neg_step = (float)(-(double)lr / bc1); job.hyper.bc2_sqrt = (float)sqrt(bc2);
-        job.hyper.w1 = (float)(1.0 - (double)beta1); job.hyper.b2 = beta2; job.hyper.w2 = (float)(1.0 - (double)beta2); job.hyper.eps = eps;
-        MultiJob j{reinterpret_cast<const float*>(code), target, predict_windows(d, n), n_settings, knobs, knob_rows, &job, loss_hist + (size_t)s * n_settings, nullptr,
-                   1.0 / (double)n_out, reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + p.head_bytes + f.bytes), nullptr};
-        ST_TRY(fmt == ST_PCM_S16 ? multi_batches(d, L, p, params, reinterpret_cast<const short*>(signal), n_out, j, ws, batch_off, stream)
-                                 : multi_batches(d, L, p, params, reinterpret_cast<const float*>(signal), n_out, j, ws, batch_off, stream));
+        job.hyper = adam_step(h, s, n_out);      // st_fit_knobs' scalars of this step
+        MultiJob j = multi_job(d, code, target, n, n_settings, knobs, knob_rows, reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + p.head_bytes + f.bytes));
+        j.fit = &job; j.loss = loss_hist + (size_t)s * n_settings;
+        ST_TRY(with_pcm(fmt, [&](auto z) { return multi_batches<decltype(z)>(d, L, p, params, signal, n_out, j, ws, batch_off, stream); }));
     }
     return ST_OK;
 }

@@ -8,18 +8,17 @@
 // Rows.  Row r of the pool is window r - win_off[f] of file f, win_off[f] <= r < win_off[f + 1]: file-major, windows ascending.  win_off[nfiles + 1] (int64, device)
 // holds the prefix sums of the files' window counts (st_eval_pool_rows); every kernel finds f by a binary search of it.  A batch is rows [r0, r0 + nb), nb <= d->B.
 //
-//   pool_stage_kernel   predict_stage_kernel element for element (x / 2 with the Conv1d padding as fp32 or as the 16-bit operand, the all-padding frames) with the
-//                       window read from its file, zeros behind the file's end, and the knob rows ALWAYS filled: row b gets its file's row of file_knobs.  A side
-//                       role (extra blocks, the call's first launch only) writes what no row writes: the zero head of every file's span of `out` and the zero
-//                       statistics of the files without a window.
-//   pool_ola_kernel     predict_ola_kernel's overlap-add (same NF = 3 / NF = 0 forms, same frame and slab order), the residual from the file, the result at
-//                       out[file_off + (L - y) + i] -- time-aligned with the input -- clipped at the file's end; with a target pool, the per-slot float32 partials of
-//                       log cosh e (fit_ola_kernel's formula), |e|, e^2, t^2, y_hat^2 and max |e| (e = y_hat - t), one slot = one wave = 256 samples.
+//   pool_stage_kernel   stp::stage_blocks (st_predict.h) with the window read from its file, zeros behind the file's end, and the knob rows ALWAYS filled: row b
+//                       gets its file's row of file_knobs.  A side role (extra blocks, the call's first launch only) writes what no row writes: the zero head of
+//                       every file's span of `out` and the zero statistics of the files without a window.
+//   pool_ola_kernel     stp::ola_frame_sum, the residual from the file, the result at out[file_off + (L - y) + i] -- time-aligned with the input -- clipped at the
+//                       file's end; with a target pool, the per-slot float32 partials of log cosh e (stp::logcosh_term), |e|, e^2, t^2, y_hat^2 and max |e|
+//                       (e = y_hat - t), one slot = one wave = 256 samples.
 //   pool_tail_kernel    one launch per batch, one workgroup per file the batch touches: that file's partials of the batch into stats[f] in double.
 //
 // Addresses.  file_off[f] need not be a multiple of four.  A quad of four samples is ONE 16-byte access (int16: 8-byte) only where its pool address is aligned and
-// it lies wholly inside the file; otherwise it is read (written) sample by sample -- the values are the same either way.  file_of() clamps what the tables say:
-// off to [0, pool_samples], len to [0, pool_samples - off], the window index to >= 0 -- so whatever the tables hold, every address formed lies inside
+// it lies wholly inside the file; otherwise it is read (written) sample by sample -- the values are the same either way.  file_span() clamps what the tables say:
+// off to [0, pool_samples], len to [0, pool_samples - off], and file_of() the window index to >= 0 -- so whatever the tables hold, every address formed lies inside
 // [0, pool_samples) of the pools and of out, and inside [0, nfiles) of the tables (as st_file_feed's clamps, st_feed_files.h).  Truthful tables are never clamped.
 // No float atomics; every sum has a fixed order; a repeated call repeats its bits.
 #pragma once
@@ -35,6 +34,13 @@ struct Tables {
 };
 struct FileRow { int f; long long off, len, w, first, end; };      // file, its clamped span, the window of the row, the file's first row and the row behind its last
 
+// file f's span as the tables give it, clamped: off to [0, pool_samples], len to [0, pool_samples - off]
+__device__ __forceinline__ void file_span(const Tables& t, const int f, long long& off, long long& len)
+{
+    off = t.file_off[f]; len = t.file_len[f];
+    off = off < 0 ? 0 : (off > t.pool_samples ? t.pool_samples : off);
+    len = len < 0 ? 0 : (len > t.pool_samples - off ? t.pool_samples - off : len);
+}
 // the file of row r: the last f with win_off[f] <= r (files without a window share their successor's entry and are passed over)
 __device__ __forceinline__ FileRow file_of(const Tables& t, const long long r)
 {
@@ -45,10 +51,7 @@ __device__ __forceinline__ FileRow file_of(const Tables& t, const long long r)
     }
     FileRow q;
     q.f = lo;
-    long long off = t.file_off[lo], len = t.file_len[lo];
-    off = off < 0 ? 0 : (off > t.pool_samples ? t.pool_samples : off);
-    len = len < 0 ? 0 : (len > t.pool_samples - off ? t.pool_samples - off : len);
-    q.off = off; q.len = len;
+    file_span(t, lo, q.off, q.len);
     q.first = t.win_off[lo]; q.end = t.win_off[lo + 1];
     q.w = r - q.first; if (q.w < 0) q.w = 0;
     return q;
@@ -72,62 +75,36 @@ __device__ __forceinline__ float square_rn(const float a)
 }
 
 struct StageArgs {
+    stp::StageCommon c;
     const void* pool_x; Tables t;
     long long r0;                             // first row of this batch
-    int y, L, pad, nb;                        // hop, window length, Conv1d padding (= N), rows of this batch
-    float* xp; unsigned short* xp16; int ht;  // as stp::StageArgs
-    int nbx, n_pad;
-    float *mag, *phs; int T, F, t_lo, Tv, n_dead;
-    const float* file_knobs; float* knobs; int K, n_kn;      // knobs[b][k] = file_knobs[f][k], f the file of row r0 + b
+    const float* file_knobs;                  // knobs[b][k] = file_knobs[f][k], f the file of row r0 + b
     float* out; double* stats; int n_zero;    // the side role: n_zero blocks (0 in every launch but the call's first); out / stats may be NULL
 };
-// Block ranges and arithmetic: predict_stage_kernel's, element for element; behind them the n_zero blocks of the side role, file f by block f % n_zero.
+// stp::stage_blocks' three ranges; behind them the n_zero blocks of the side role, file f by block f % n_zero.
 template <typename T>
 __global__ void __launch_bounds__(256)
 pool_stage_kernel(const StageArgs a)
 {
-    const int blk = blockIdx.x;
-    if (blk < a.n_pad) {
-        const int b = blk / a.nbx, bx = blk - b * a.nbx;
-        const T* __restrict__ pool = reinterpret_cast<const T*>(a.pool_x);
-        const FileRow fr = file_of(a.t, a.r0 + b);
-        const long long w0 = fr.w * a.y;
-        const int Lp4 = (a.L + 2 * a.pad) / 4;
-        float4* dst = reinterpret_cast<float4*>(a.xp + (size_t)b * (a.L + 2 * a.pad));
-        uint2* dst16 = reinterpret_cast<uint2*>(a.xp16 + (size_t)b * (a.L + 2 * a.pad));
-        for (int i = bx * 256 + threadIdx.x; i < Lp4; i += a.nbx * 256) {
-            const int j = i - a.pad / 4;
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (j >= 0 && j < a.L / 4) {
-                const long long g = w0 + 4ll * j;
-                if (g < fr.len) { v = file_quad(pool, fr.off, g, fr.len); v.x *= 0.5f; v.y *= 0.5f; v.z *= 0.5f; v.w *= 0.5f; }
-            }
-            if (a.ht) dst16[i] = st_to_h16x4(v, a.ht);
-            else dst[i] = v;
-        }
-    }
-    else if (blk < a.n_pad + a.n_dead) stm::zero_dead_frame(nullptr, nullptr, a.mag, a.phs, a.T, a.F, a.t_lo, a.Tv, blk - a.n_pad);
-    else if (blk < a.n_pad + a.n_dead + a.n_kn) {
-        const int i = (blk - a.n_pad - a.n_dead) * 256 + (int)threadIdx.x;
-        if (i < a.nb * a.K) {
-            const FileRow fr = file_of(a.t, a.r0 + i / a.K);
-            a.knobs[i] = a.file_knobs[(size_t)fr.f * a.K + i % a.K];
-        }
-    }
-    else {
-        for (int f = blk - a.n_pad - a.n_dead - a.n_kn; f < a.t.nfiles; f += a.n_zero) {
-            long long off = a.t.file_off[f], len = a.t.file_len[f];      // file_of's clamps
-            off = off < 0 ? 0 : (off > a.t.pool_samples ? a.t.pool_samples : off);
-            len = len < 0 ? 0 : (len > a.t.pool_samples - off ? a.t.pool_samples - off : len);
-            const long long head = len < a.L - a.y ? len : a.L - a.y;      // no window predicts these samples
-            if (a.out) for (long long i = threadIdx.x; i < head; i += 256) a.out[off + i] = 0.f;
-            if (a.stats && a.t.win_off[f + 1] <= a.t.win_off[f] && threadIdx.x < POOL_STATS) a.stats[(size_t)f * POOL_STATS + threadIdx.x] = 0.0;
-        }
+    const T* __restrict__ pool = reinterpret_cast<const T*>(a.pool_x);
+    const bool staged = stp::stage_blocks(a.c, blockIdx.x,
+        [&](const int b) {
+            const FileRow fr = file_of(a.t, a.r0 + b);
+            const long long w0 = fr.w * a.c.y;
+            return [=](const long long g) { return w0 + g < fr.len ? file_quad(pool, fr.off, w0 + g, fr.len) : make_float4(0.f, 0.f, 0.f, 0.f); };
+        },
+        [&](const int b) { return a.file_knobs + (size_t)file_of(a.t, a.r0 + b).f * a.c.K; });
+    if (staged) return;
+    for (int f = blockIdx.x - a.c.n_pad - a.c.n_dead - a.c.n_kn; f < a.t.nfiles; f += a.n_zero) {
+        long long off, len; file_span(a.t, f, off, len);
+        const long long head = len < a.c.L - a.c.y ? len : a.c.L - a.c.y;      // no window predicts these samples
+        if (a.out) for (long long i = threadIdx.x; i < head; i += 256) a.out[off + i] = 0.f;
+        if (a.stats && a.t.win_off[f + 1] <= a.t.win_off[f] && threadIdx.x < POOL_STATS) a.stats[(size_t)f * POOL_STATS + threadIdx.x] = 0.0;
     }
 }
 
-// Four output samples per lane, grid (ceil(y / 4 / 256), rows of the batch): predict_ola_kernel's sums in predict_ola_kernel's order (NF = 3 and NF = 0, every slab
-// count), then 2 * (s + x / 2) with x the residual sample of the file.  tgt != NULL: the loss side as fit_ola_kernel forms it -- a wave's 64 quads are one slot of
+// Four output samples per lane, grid (ceil(y / 4 / 256), rows of the batch): stp::ola_frame_sum, then stp::ola_out4 with x the residual sample of the file.
+// tgt != NULL: the loss side as fit_ola_kernel forms it -- a wave's 64 quads are one slot of
 // 256 samples, slot = 4 * blockIdx.x + wave, nslot = ceil(y / 256) per row; per lane ((q0 + q1) + q2) + q3 in sample order, then the xor tree over the 64 lanes (max for
 // the peak).  Samples at or behind the file's end carry nothing.  part: [POOL_PART][plane] floats, plane >= rows of the batch * nslot, element b * nslot + slot.
 // out == NULL: the score form, nothing stored but the partials.
@@ -145,64 +122,22 @@ pool_ola_kernel(const float* __restrict__ frs, const size_t slab, const T* __res
     float acc[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
     float peak = 0.f;
     if (j < ysz && i < n_out) {
-        const int t0 = j / H + 1;                             // first frame with N + j - H t < N
-        int t1 = (N + j) / H;                                 // last frame with N + j - H t >= 0
-        if (t1 > OT - 1) t1 = OT - 1;
-        const float* fb = frs + (size_t)b * OT * N;
-        float s[4] = {0.f, 0.f, 0.f, 0.f};
+        float s[4], r[4];
         float4 xv, tv = make_float4(0.f, 0.f, 0.f, 0.f);
-        if constexpr (NF > 0) {
-            float4 v[NF][NS];
-#pragma unroll
-            for (int u = 0; u < NF; ++u) {
-                const int t = t0 + u <= t1 ? t0 + u : t1;
-                const size_t o = (size_t)t * N + (size_t)(N + j - H * t);
-#pragma unroll
-                for (int z = 0; z < NS; ++z) v[u][z] = *reinterpret_cast<const float4*>(fb + z * slab + o);
-            }
+        stp::ola_frame_sum<NS, NF>(frs + (size_t)b * OT * N, slab, N, H, OT, j, s, [&] {
             xv = file_quad(pool_x, fr.off, i + (L - ysz), fr.len);
             if (tgt) tv = file_quad(tgt, fr.off, i + (L - ysz), fr.len);
-#pragma unroll
-            for (int u = 0; u < NF; ++u) {
-                const bool live = t0 + u <= t1;
-#pragma unroll
-                for (int z = 0; z < NS; ++z) {
-                    s[0] += live ? v[u][z].x : 0.f; s[1] += live ? v[u][z].y : 0.f; s[2] += live ? v[u][z].z : 0.f; s[3] += live ? v[u][z].w : 0.f;
-                }
-            }
-        } else {
-            xv = file_quad(pool_x, fr.off, i + (L - ysz), fr.len);
-            if (tgt) tv = file_quad(tgt, fr.off, i + (L - ysz), fr.len);
-            for (int t = t0; t <= t1; ++t) {
-                const size_t o = (size_t)t * N + (size_t)(N + j - H * t);
-                float4 v[NS];
-#pragma unroll
-                for (int z = 0; z < NS; ++z) v[z] = *reinterpret_cast<const float4*>(fb + z * slab + o);
-#pragma unroll
-                for (int z = 0; z < NS; ++z) { s[0] += v[z].x; s[1] += v[z].y; s[2] += v[z].z; s[3] += v[z].w; }
-            }
-        }
-        const float xs[4] = {xv.x, xv.y, xv.z, xv.w}, ts[4] = {tv.x, tv.y, tv.z, tv.w};
-        float r[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) r[q] = 2.0f * (s[q] + 0.5f * xs[q]);
-        if (out) {
-            float* o = out + fr.off + (L - ysz) + i;
-            if (i + 4 <= n_out && (fr.off & 3) == 0) *reinterpret_cast<float4*>(o) = make_float4(r[0], r[1], r[2], r[3]);
-            else {
-#pragma unroll
-                for (int q = 0; q < 4; ++q) if (i + q < n_out) o[q] = r[q];
-            }
-        }
+        });
+        stp::ola_out4(s, xv, r);
+        if (out) stp::store_quad_upto(out + fr.off + (L - ysz), r, i, n_out, (fr.off & 3) == 0);
         if (tgt) {
+            const float ts[4] = {tv.x, tv.y, tv.z, tv.w};
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const bool valid = i + q < n_out;
                 const float dlt = ts[q] - r[q];
                 const float e = fabsf(dlt);
-                float l1;      // log cosh as ola_loss4_kernel forms it (st_misc.h)
-                if (e < 8.0f) { const float u = expm1f(0.5f * e); const float sh = 0.5f * (u + u / (u + 1.0f)); l1 = log1pf(2.0f * sh * sh); }
-                else l1 = e + log1pf(__expf(-2.0f * e)) - 0.69314718056f;
+                const float l1 = stp::logcosh_term(e);
                 acc[0] += valid ? l1 : 0.f;
                 acc[1] += valid ? e : 0.f;
                 acc[2] += valid ? square_rn(dlt) : 0.f;

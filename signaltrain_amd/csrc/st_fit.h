@@ -4,10 +4,10 @@
 // output sample i belongs to input sample (L - y) + i, and so does its target).  The knobs enter at fnn_addknobs, layer 5 of 9 (nn_proc.py:92-93), so behind the
 // forward d J / d knobs needs the synthesis data-gradient GEMM, the data-gradient chain of layers 9..6 and ELU' at layer 5 -- and nothing else:
 //
-//   fit_ola_kernel        predict_ola_kernel's overlap-add (same frame order, same residual from the recording) with the loss side: d = y_hat - target, the
+//   fit_ola_kernel        predict_ola_kernel's overlap-add (stp::ola_frame_sum, the same residual from the recording) with the loss side: d = y_hat - target, the
 //                         target read straight from the target recording; 2 tanh(d) into the padded d syn operand of the data-gradient GEMM (fp32, or rounded to
 //                         the 16-bit operand type where the 16-bit pipeline runs), zero margins, zeros at and behind the recording's end, and the per-slot
-//                         log-cosh partials in ola_loss4_kernel's formula and tree.  d syn is NOT scaled by 1 / n_out: tanh / n_out of a ten-minute recording
+//                         log-cosh partials (stp::logcosh_term) in ola_loss4_kernel's tree.  d syn is NOT scaled by 1 / n_out: tanh / n_out of a ten-minute recording
 //                         is ~1e-7, below the fp16 subnormal range -- the scale is applied in fp32 behind W5 (fit_tail_kernel).
 //   ae_knob_bwd_kernel    the decoder half of st_ae_split.h without its 17 weight-gradient tiles, bias gradients, d a4, tails, gradient images and end-of-kernel
 //                         reduction: h4 (kept by the forward kernel) -> layers 5..9 recomputed -> d out -> data gradients 9, 8, 7, 6 -> ELU' at layer 5 ->
@@ -22,7 +22,7 @@
 
 namespace stf {
 
-// Four output samples per lane, grid (ceil(y / 4 / 256), windows of the batch): predict_ola_kernel's sums (NF = 3 / NF = 0 as there), then the loss side.  A wave's 64
+// Four output samples per lane, grid (ceil(y / 4 / 256), windows of the batch): stp::ola_frame_sum (NF = 3 / NF = 0 as there), then the loss side.  A wave's 64
 // quads are one slot of 256 samples: slot = 4 * blockIdx.x + wave, nslot = ceil(y / 256) per window, the tree of ola_loss4_kernel.  Samples at or behind n_out carry
 // neither loss nor gradient.  dsyn16 != NULL: the operand goes out rounded to the 16-bit type ht INSTEAD of fp32 (what the 16-bit data-gradient GEMM reads).
 // STK (st_multi.h): 0, the kernel as it was (nw is not read).  1: rows of the batch are (setting, window) pairs -- the frames, the d-syn row and the partials are
@@ -39,53 +39,19 @@ fit_ola_kernel(const float* __restrict__ frs, const size_t slab, const T* __rest
     float lc = 0.f;
     float ds[4] = {0.f, 0.f, 0.f, 0.f};
     if (j < ysz && i < n_out) {
-        const int t0 = j / H + 1;                             // first frame with N + j - H t < N
-        int t1 = (N + j) / H;                                 // last frame with N + j - H t >= 0
-        if (t1 > OT - 1) t1 = OT - 1;
-        const float* fb = frs + (size_t)b * OT * N;
-        float s[4] = {0.f, 0.f, 0.f, 0.f};
+        float s[4], out[4];
         float4 xv, tv;
-        if constexpr (NF > 0) {
-            float4 v[NF][NS];
-#pragma unroll
-            for (int u = 0; u < NF; ++u) {
-                const int t = t0 + u <= t1 ? t0 + u : t1;
-                const size_t o = (size_t)t * N + (size_t)(N + j - H * t);
-#pragma unroll
-                for (int z = 0; z < NS; ++z) v[u][z] = *reinterpret_cast<const float4*>(fb + z * slab + o);
-            }
+        stp::ola_frame_sum<NS, NF>(frs + (size_t)b * OT * N, slab, N, H, OT, j, s, [&] {
             xv = stp::pcm_quad_upto(sig, i + (L - ysz), n_out + (L - ysz));
             tv = stp::pcm_quad_upto(tgt, i + (L - ysz), n_out + (L - ysz));
-#pragma unroll
-            for (int u = 0; u < NF; ++u) {
-                const bool live = t0 + u <= t1;
-#pragma unroll
-                for (int z = 0; z < NS; ++z) {
-                    s[0] += live ? v[u][z].x : 0.f; s[1] += live ? v[u][z].y : 0.f; s[2] += live ? v[u][z].z : 0.f; s[3] += live ? v[u][z].w : 0.f;
-                }
-            }
-        } else {
-            xv = stp::pcm_quad_upto(sig, i + (L - ysz), n_out + (L - ysz));
-            tv = stp::pcm_quad_upto(tgt, i + (L - ysz), n_out + (L - ysz));
-            for (int t = t0; t <= t1; ++t) {
-                const size_t o = (size_t)t * N + (size_t)(N + j - H * t);
-                float4 v[NS];
-#pragma unroll
-                for (int z = 0; z < NS; ++z) v[z] = *reinterpret_cast<const float4*>(fb + z * slab + o);
-#pragma unroll
-                for (int z = 0; z < NS; ++z) { s[0] += v[z].x; s[1] += v[z].y; s[2] += v[z].z; s[3] += v[z].w; }
-            }
-        }
-        const float xs[4] = {xv.x, xv.y, xv.z, xv.w}, ts[4] = {tv.x, tv.y, tv.z, tv.w};
+        });
+        stp::ola_out4(s, xv, out);
+        const float ts[4] = {tv.x, tv.y, tv.z, tv.w};
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const bool valid = i + q < n_out;
-            const float out = 2.0f * (s[q] + 0.5f * xs[q]);
-            const float dlt = ts[q] - out;
-            const float a = fabsf(dlt);
-            float l1;      // log cosh as ola_loss4_kernel forms it (st_misc.h)
-            if (a < 8.0f) { const float u = expm1f(0.5f * a); const float sh = 0.5f * (u + u / (u + 1.0f)); l1 = log1pf(2.0f * sh * sh); }
-            else l1 = a + log1pf(__expf(-2.0f * a)) - 0.69314718056f;
+            const float dlt = ts[q] - out[q];
+            const float l1 = stp::logcosh_term(fabsf(dlt));
             lc += valid ? l1 : 0.f;
             ds[q] = valid ? -2.0f * tanhf(dlt) : 0.f;      // 2 tanh(y_hat - target): d y_hat / d (overlap-added sample) = 2; 1 / n_out comes behind W5
         }

@@ -8,9 +8,9 @@
 //                                                 =  block[c][g - n0] for n0 <= g < n1
 //                                                 =  0                from n1 on            (reached in a final push only: the zero-padded last window)
 //
-//   stream_stage_kernel   predict_stage_kernel (st_predict.h) with that pair as the signal: x / 2 with the Conv1d padding as fp32 or as the 16-bit GEMM operand, the
-//                         all-padding frames, and the knob rows -- ALWAYS filled here, row b from the knob row of its channel (or from the one row).
-//   stream_ola_kernel     predict_ola_kernel with the residual from the pair; row (c, k) goes to out + c * out_pitch + k * y, clipped to the push's emitted count.
+//   stream_stage_kernel   stp::stage_blocks (st_predict.h) with that pair as the signal; the knob rows are ALWAYS filled here, row b from the knob row of its
+//                         channel (or from the one row).
+//   stream_ola_kernel     stp::ola_frame_sum with the residual from the pair; row (c, k) goes to out + c * out_pitch + k * y, clipped to the push's emitted count.
 //   stream_carry_kernel   the samples to keep, [Wc(n1) y, n1) of every channel, from the pair into the OTHER history half (the halves then swap on the host): no
 //                         quad is read and written in the same half, so the kernel needs no order among its lanes.
 //
@@ -43,47 +43,25 @@ __device__ __forceinline__ float4 src_quad(const Src& s, const long long c, cons
 }
 
 struct StageArgs {
+    stp::StageCommon c;
     Src s;
     long long first, nw, r0;                  // first window of the push, windows of the push per channel, first row of this batch
-    int y, L, pad, nb;                        // hop, window length, Conv1d padding (= N), rows of this batch
-    float* xp; unsigned short* xp16; int ht;  // as stp::StageArgs
-    int nbx, n_pad;
-    float *mag, *phs; int T, F, t_lo, Tv, n_dead;
-    const float* knob_src; int knob_stride;   // knobs[b][k] = knob_src[c * knob_stride + k], c the channel of row r0 + b (knob_stride = 0: one setting for all channels)
-    float* knobs; int K, n_kn;
+    const float* knob_src; int knob_stride;   // knobs[b][k] = knob_src[ch * knob_stride + k], ch the channel of row r0 + b (knob_stride = 0: one setting for all channels)
 };
-// Block ranges and arithmetic: predict_stage_kernel's, element for element.
 template <typename T>
 __global__ void __launch_bounds__(256)
 stream_stage_kernel(const StageArgs a)
 {
-    const int blk = blockIdx.x;
-    if (blk < a.n_pad) {
-        const int b = blk / a.nbx, bx = blk - b * a.nbx;
-        const long long r = a.r0 + b, c = r / a.nw, k = r - c * a.nw;
-        const long long w0 = (a.first + k) * a.y;
-        const int Lp4 = (a.L + 2 * a.pad) / 4;
-        float4* dst = reinterpret_cast<float4*>(a.xp + (size_t)b * (a.L + 2 * a.pad));
-        uint2* dst16 = reinterpret_cast<uint2*>(a.xp16 + (size_t)b * (a.L + 2 * a.pad));
-        for (int i = bx * 256 + threadIdx.x; i < Lp4; i += a.nbx * 256) {
-            const int j = i - a.pad / 4;
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (j >= 0 && j < a.L / 4) { v = src_quad<T>(a.s, c, w0 + 4ll * j); v.x *= 0.5f; v.y *= 0.5f; v.z *= 0.5f; v.w *= 0.5f; }
-            if (a.ht) dst16[i] = st_to_h16x4(v, a.ht);
-            else dst[i] = v;
-        }
-    }
-    else if (blk < a.n_pad + a.n_dead) stm::zero_dead_frame(nullptr, nullptr, a.mag, a.phs, a.T, a.F, a.t_lo, a.Tv, blk - a.n_pad);
-    else {
-        const int i = (blk - a.n_pad - a.n_dead) * 256 + (int)threadIdx.x;
-        if (i < a.nb * a.K) {
-            const long long c = (a.r0 + i / a.K) / a.nw;
-            a.knobs[i] = a.knob_src[c * a.knob_stride + i % a.K];
-        }
-    }
+    stp::stage_blocks(a.c, blockIdx.x,
+                      [&](const int b) {
+                          const long long r = a.r0 + b, ch = r / a.nw, k = r - ch * a.nw;
+                          const long long w0 = (a.first + k) * a.c.y;
+                          return [=, &a](const long long g) { return src_quad<T>(a.s, ch, w0 + g); };
+                      },
+                      [&](const int b) { return a.knob_src + (a.r0 + b) / a.nw * a.knob_stride; });
 }
 
-// predict_ola_kernel's sums in predict_ola_kernel's order (NF = 3 and NF = 0, every slab count); grid (ceil(y / 4 / 256), rows of the batch).
+// stp::ola_frame_sum with the residual from the pair; grid (ceil(y / 4 / 256), rows of the batch); row (c, k) goes to out + c * out_pitch + k * y.
 // emit: samples this push emits per channel -- nw * y, less in a final push whose last window is clipped.
 template <typename T, int NS, int NF>
 __global__ void __launch_bounds__(256)
@@ -98,51 +76,11 @@ stream_ola_kernel(const float* __restrict__ frs, const size_t slab, const Src sr
     const long long i = k * ysz + j;                      // output sample within the push's span of channel c; its input sample lies below n1 wherever i < emit
     if (i >= emit) return;
     const long long gx = (first + k) * ysz + (L - ysz) + j;      // the residual's input sample
-    const int t0 = j / H + 1;
-    int t1 = (N + j) / H;
-    if (t1 > OT - 1) t1 = OT - 1;
-    const float* fb = frs + (size_t)b * OT * N;
-    float s[4] = {0.f, 0.f, 0.f, 0.f};
+    float s[4], rr[4];
     float4 xv;
-    if constexpr (NF > 0) {
-        float4 v[NF][NS];
-#pragma unroll
-        for (int u = 0; u < NF; ++u) {
-            const int t = t0 + u <= t1 ? t0 + u : t1;
-            const size_t o = (size_t)t * N + (size_t)(N + j - H * t);
-#pragma unroll
-            for (int z = 0; z < NS; ++z) v[u][z] = *reinterpret_cast<const float4*>(fb + z * slab + o);
-        }
-        xv = src_quad<T>(src, c, gx);
-#pragma unroll
-        for (int u = 0; u < NF; ++u) {
-            const bool live = t0 + u <= t1;
-#pragma unroll
-            for (int z = 0; z < NS; ++z) {
-                s[0] += live ? v[u][z].x : 0.f; s[1] += live ? v[u][z].y : 0.f; s[2] += live ? v[u][z].z : 0.f; s[3] += live ? v[u][z].w : 0.f;
-            }
-        }
-    } else {
-        xv = src_quad<T>(src, c, gx);
-        for (int t = t0; t <= t1; ++t) {
-            const size_t o = (size_t)t * N + (size_t)(N + j - H * t);
-            float4 v[NS];
-#pragma unroll
-            for (int z = 0; z < NS; ++z) v[z] = *reinterpret_cast<const float4*>(fb + z * slab + o);
-#pragma unroll
-            for (int z = 0; z < NS; ++z) { s[0] += v[z].x; s[1] += v[z].y; s[2] += v[z].z; s[3] += v[z].w; }
-        }
-    }
-    const float xs[4] = {xv.x, xv.y, xv.z, xv.w};
-    float rr[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) rr[q] = 2.0f * (s[q] + 0.5f * xs[q]);
-    float* o = out + c * out_pitch + i;
-    if (i + 4 <= emit) *reinterpret_cast<float4*>(o) = make_float4(rr[0], rr[1], rr[2], rr[3]);
-    else {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) if (i + q < emit) o[q] = rr[q];
-    }
+    stp::ola_frame_sum<NS, NF>(frs + (size_t)b * OT * N, slab, N, H, OT, j, s, [&] { xv = src_quad<T>(src, c, gx); });
+    stp::ola_out4(s, xv, rr);
+    stp::store_quad_upto(out + c * out_pitch, rr, i, emit);
 }
 
 // Non-final pushes only (m % 4 == 0): quads [a1, n1) of every channel to the head of the other half; grid (ceil(held / 4 / 256), C).  held1 = n1 - a1 < L.
