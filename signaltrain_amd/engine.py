@@ -82,6 +82,76 @@ class RecordingCode:
 _warned_channels_unsupported = False
 
 
+# ---------------------------------------------------------------- the argument rules of the whole-signal inference entries, each stated once
+# Plain functions of tensors: they take the device, K and the window count as arguments and need neither an engine nor the library
+# (tests/test_infer_args_host.py runs them on CPU tensors).  `what` is the entry's name in front of every message.
+def _pcm(t):
+    """The ST_PCM_* value of a recording tensor."""
+    return _lib.PCM_S16 if t.dtype == torch.int16 else _lib.PCM_F32
+
+
+def _recording(what, name, t, device, nonempty=False):
+    """A recording argument as the library takes it: a 1-D float32 or int16 tensor on `device`, contiguous, and cloned if it starts off the boundary the
+    kernels' quads of four samples need (pcm_align in st_api.hip: 8 bytes for int16, 16 for float32)."""
+    if not (torch.is_tensor(t) and t.dim() == 1 and t.device == device and t.dtype in (torch.float32, torch.int16) and (t.numel() >= 1 or not nonempty)):
+        raise ValueError(f"{what}: {name} must be a {'non-empty ' if nonempty else ''}1-D float32 or int16 tensor on {device}")
+    t = t.contiguous()
+    return t.clone() if t.data_ptr() % (8 if t.dtype == torch.int16 else 16) else t
+
+
+def _recording_pair(what, signal, target, device, first="signal"):
+    """Input and target of a fit or a score: two recordings (_recording) of equal length in ONE format -- where the dtypes differ the int16 one becomes
+    float32 by the C rule, (float)((double)s / 32767.0), in a fresh (so aligned) tensor."""
+    signal, target = _recording(what, first, signal, device), _recording(what, "target", target, device)
+    if signal.numel() != target.numel():
+        raise ValueError(f"{what}: {first} has {signal.numel()} samples, target {target.numel()}")
+    if signal.dtype != target.dtype:
+        signal, target = ((t.double() / 32767.0).float() if t.dtype == torch.int16 else t for t in (signal, target))
+    return signal, target
+
+
+def _per_window(nwin, n):
+    return f": one row, or one per window ({nwin} windows for {n} samples)"
+
+
+def _knob_rows(what, knobs, K, device, allowed, per):
+    """(knobs as a contiguous float32 [rows, K] tensor on `device`, rows); (None, 1) for a model without knobs.  A row count outside `allowed` is refused,
+    `per` ends the message."""
+    if not K:
+        return None, 1
+    kn = torch.as_tensor(knobs).to(device=device, dtype=torch.float32).reshape(-1, K).contiguous()
+    rows = int(kn.shape[0])
+    if rows not in allowed:
+        raise ValueError(f"{what}: knobs has {rows} rows{per}")
+    return kn, rows
+
+
+def _knob_settings(what, knobs, K, nwin, n, device, strict=False):
+    """(S knob settings as a contiguous float32 [S, rows, K] tensor on `device`, rows 1 or nwin; whether ONE setting came as a 1-D [K]).  [S, K] becomes
+    [S, 1, K], and so does every other shape that is not 3-D unless `strict`: then only [S, K] and [S, rows, K] pass."""
+    kn = torch.as_tensor(knobs).to(device=device, dtype=torch.float32)
+    single = kn.dim() == 1
+    whole = kn.dim() == 3 and int(kn.shape[1]) in (1, nwin) and int(kn.shape[2]) == K
+    if strict and not (whole or (kn.dim() == 2 and int(kn.shape[1]) == K)):
+        raise ValueError(f"{what}: knobs must be [S, {K}] or [S, rows, {K}] with one row per setting, or one per window ({nwin} windows for {n} samples), "
+                         f"not {tuple(kn.shape)}")
+    if kn.dim() == 3 and not whole:
+        raise ValueError(f"{what}: knobs [S, rows, K] has {int(kn.shape[1])} rows per setting" + _per_window(nwin, n))
+    kn = (kn if whole else kn.reshape(-1, 1, K)).contiguous()
+    if int(kn.shape[0]) < 1:
+        raise ValueError(f"{what}: no knob setting")
+    return kn, single
+
+
+def _adam_state(state, like, device):
+    """(m, v, first step) of a knob fit: zeros and 1, or clones of what a previous call returned, float32 in the shape of the knobs `like`."""
+    if state is None:
+        return torch.zeros_like(like), torch.zeros_like(like), 1
+    m, v, first = state
+    m, v = (t.to(device=device, dtype=torch.float32).reshape(like.shape).contiguous().clone() for t in (m, v))
+    return m, v, int(first)
+
+
 class PredictStream:
     """A predict session of a StepEngine (StepEngine.open_stream; st_predict_stream_* in include/signaltrain_hip.h): C channels fed block by block in
     lockstep.  push() enqueues and returns device tensors; nothing synchronises with the host.  The parameter-only head of the workspace is built at open and
@@ -92,9 +162,7 @@ class PredictStream:
         B = int(batch or engine.max_batch)
         if B < 1 or self.channels < 1:
             raise ValueError(f"open_stream: channels = {channels}, batch = {B}")
-        d = engine.dims.with_batch(B)
-        d.prec, d.loss_scale, d.clip_all = _lib.PREC[engine.compute_dtype], engine.loss_scale, int(engine.clip_all)
-        self.dims = d
+        self.dims = d = engine._infer_dims("open_stream", B)
         lib = engine.lib
         if not lib.st_predict_supported(C.byref(d)):
             raise RuntimeError(f"open_stream: st_predict_supported refuses this geometry (T={d.T}, OT={d.OT}): the wide autoencoder geometries have no "
@@ -166,15 +234,10 @@ class PredictStream:
                     and (res.stride(1) == 1 or res.shape[1] <= 1) and res.data_ptr() % 16 == 0 and (Cn == 1 or (res.stride(0) % 4 == 0 and res.stride(0) >= emit))):
                 raise ValueError(f"PredictStream.push: out must be a float32 [C, >= {emit}] tensor on {e.device} with unit sample stride and 16-byte aligned rows")
             opitch = opitch if Cn == 1 else int(res.stride(0))
-        kn, rows = None, 1
-        if d.K:
-            kn = torch.as_tensor(knobs).to(device=e.device, dtype=torch.float32).reshape(-1, d.K).contiguous()
-            rows = int(kn.shape[0])
-            if rows not in (1, Cn):
-                raise ValueError(f"PredictStream.push: knobs has {rows} rows: one row, or one per channel ({Cn})")
+        kn, rows = _knob_rows("PredictStream.push", knobs, d.K, e.device, (1, Cn), f": one row, or one per channel ({Cn})")
         if e.step_count != self._built_at:
             self.refresh()
-        e._call("st_predict_stream_push", C.byref(d), _lib.ptr(e.params), C.byref(self.s), _lib.PCM_S16 if block.dtype == torch.int16 else _lib.PCM_F32,
+        e._call("st_predict_stream_push", C.byref(d), _lib.ptr(e.params), C.byref(self.s), _pcm(block),
                 C.c_void_p(block.data_ptr()) if m else None, m, pitch, int(bool(final)), _lib.ptr(kn), rows,
                 C.c_void_p(res.data_ptr()) if emit else None, opitch, _lib.ptr(self.state), _lib.ptr(self.ws), e._stream())
         res = res[:, :emit]
@@ -587,6 +650,42 @@ class StepEngine:
         return self.eval_acc.tolist()
 
     # ---------------------------------------------------------------- whole-signal inference on the device
+    def _infer_dims(self, what, batch):
+        """The dims of an inference entry: `batch` rows per internal batch (default max_batch) at this engine's compute dtype, loss scale and clip scope."""
+        B = int(batch or self.max_batch)
+        if B < 1:
+            raise ValueError(f"{what}: batch = {B}")
+        d = self.dims.with_batch(B)
+        d.prec, d.loss_scale, d.clip_all = _lib.PREC[self.compute_dtype], self.loss_scale, int(self.clip_all)
+        return d
+
+    def _kept(self, name):
+        """A dict the inference entries keep on this engine from call to call (made on first use)."""
+        return self.__dict__.setdefault(name, {})
+
+    # an entry's own workspace, by attribute: (its size function, the gate behind a size of 0, where the wide autoencoder geometries stay)
+    _OWN_WS = {"_predict_ws": ("st_predict_ws_bytes", "st_predict_supported", "forward()"),
+               "_pool_ws": ("st_eval_pool_ws_bytes", "st_eval_pool_supported", "forward()"),
+               "_decode_ws": ("st_decode_ws_bytes", "st_decode_supported", "predict_long's batched route"),
+               "_fit_ws": ("st_fit_knobs_ws_bytes", "st_fit_knobs_supported", "the batched route"),
+               "_multi_ws": ("st_knob_multi_ws_bytes", "st_fit_knobs_supported", "the batched route")}
+
+    def _own_ws(self, what, attr, d, *more):
+        """The workspace tensor self.<attr> an inference entry keeps for itself (_OWN_WS; `more`: what its size function takes behind the dims), allocated
+        on first use and grown, never shrunk.  A size query carves every batch 1 .. B (milliseconds at B = 1024): asked once per (B, more, dtype)."""
+        size_fn, gate, stay = self._OWN_WS[attr]
+        sizes = self._kept("_own_ws_sizes")
+        key = (attr, d.B, self.compute_dtype) + more
+        if key not in sizes:
+            sizes[key] = int(getattr(self.lib, size_fn)(C.byref(d), *more))
+        if sizes[key] <= 0:
+            raise RuntimeError(f"{what}: {gate} refuses this geometry (T={d.T}, OT={d.OT}): the wide autoencoder geometries stay on {stay}")
+        ws = getattr(self, attr, None)
+        if ws is None or ws.numel() < sizes[key]:
+            ws = torch.zeros(sizes[key], dtype=torch.uint8, device=self.device)
+            setattr(self, attr, ws)
+        return ws
+
     def predict_supported(self):
         """Whether predict_long() runs this geometry (st_predict_supported: the fused autoencoder geometries; host arithmetic only)."""
         return bool(self.lib.st_predict_supported(C.byref(self.dims.with_batch(1))))
@@ -597,40 +696,20 @@ class StepEngine:
         window); batch: windows per internal batch (default max_batch); out: a float32 device tensor of at least n - (L - y) samples to write into.
         Returns the n - (L - y) predicted samples as a float32 device tensor (empty where the signal is shorter than the first window's lookback).  No host
         sync.  The engine keeps a workspace of its own for this (st_predict_ws_bytes, allocated on first use): self.ws is not written; generation moves on."""
-        if not (torch.is_tensor(signal) and signal.dim() == 1 and signal.device == self.device and signal.dtype in (torch.float32, torch.int16)):
-            raise ValueError(f"predict_long: signal must be a 1-D float32 or int16 tensor on {self.device}")
-        signal = signal.contiguous()
-        if signal.data_ptr() % 16:
-            signal = signal.clone()           # a view that starts off a 16-byte boundary: the kernels read aligned quads
-        B = int(batch or self.max_batch)
-        if B < 1:
-            raise ValueError(f"predict_long: batch = {B}")
-        d = self.dims.with_batch(B)
-        d.prec, d.loss_scale, d.clip_all = _lib.PREC[self.compute_dtype], self.loss_scale, int(self.clip_all)
+        signal = _recording("predict_long", "signal", signal, self.device)
+        d = self._infer_dims("predict_long", batch)
         n = int(signal.numel())
         nwin, n_out = int(self.lib.st_predict_windows(C.byref(d), n)), int(self.lib.st_predict_out_samples(C.byref(d), n))
-        kn, rows = None, 1
-        if d.K:
-            kn = torch.as_tensor(knobs).to(device=self.device, dtype=torch.float32).reshape(-1, d.K).contiguous()
-            rows = int(kn.shape[0])
+        kn, rows = _knob_rows("predict_long", knobs, d.K, self.device, (1, nwin), _per_window(nwin, n))
         if out is None:
             out = torch.empty(n_out, dtype=torch.float32, device=self.device)
         elif not (out.dtype == torch.float32 and out.device == self.device and out.dim() == 1 and out.is_contiguous() and out.numel() >= n_out and out.data_ptr() % 16 == 0):
             raise ValueError(f"predict_long: out must be a contiguous, 16-byte aligned 1-D float32 tensor of at least {n_out} samples on {self.device}")
-        sizes = self.__dict__.setdefault("_predict_sizes", {})       # st_predict_ws_bytes carves every batch 1 .. B (milliseconds at B = 1024): once per (B, dtype)
-        if (B, self.compute_dtype) not in sizes:
-            sizes[(B, self.compute_dtype)] = int(self.lib.st_predict_ws_bytes(C.byref(d)))
-        need = sizes[(B, self.compute_dtype)]
-        if need <= 0:
-            raise RuntimeError(f"predict_long: st_predict_supported refuses this geometry (T={d.T}, OT={d.OT}): the wide autoencoder geometries stay on forward()")
-        if d.K and rows not in (1, nwin):
-            raise ValueError(f"predict_long: knobs has {rows} rows: one row, or one per window ({nwin} windows for {n} samples)")
-        if getattr(self, "_predict_ws", None) is None or self._predict_ws.numel() < need:
-            self._predict_ws = torch.zeros(need, dtype=torch.uint8, device=self.device)
+        ws = self._own_ws("predict_long", "_predict_ws", d)
         self.generation += 1
         if n_out > 0:
-            self._call("st_predict_long", C.byref(d), _lib.ptr(self.params), _lib.PCM_S16 if signal.dtype == torch.int16 else _lib.PCM_F32,
-                       C.c_void_p(signal.data_ptr()), n, _lib.ptr(kn), rows, C.c_void_p(out.data_ptr()), _lib.ptr(self._predict_ws), self._stream())
+            self._call("st_predict_long", C.byref(d), _lib.ptr(self.params), _pcm(signal), C.c_void_p(signal.data_ptr()), n, _lib.ptr(kn), rows,
+                       C.c_void_p(out.data_ptr()), _lib.ptr(ws), self._stream())
         return out[:n_out]
 
     # ---------------------------------------------------------------- a folder of recordings in one call
@@ -647,24 +726,19 @@ class StepEngine:
         time-aligned with the input, zeros over each file's first L - y samples (None unless want_out or pool_y is None).  No host sync once the tables
         are known.  The engine keeps a workspace of its own for this: self.ws is not written; generation moves on."""
         dev = self.device
-        if not (torch.is_tensor(pool_x) and pool_x.dim() == 1 and pool_x.device == dev and pool_x.dtype in (torch.float32, torch.int16) and pool_x.numel() >= 1):
-            raise ValueError(f"eval_pool: pool_x must be a non-empty 1-D float32 or int16 tensor on {dev}")
-        if pool_y is not None and not (torch.is_tensor(pool_y) and pool_y.shape == pool_x.shape and pool_y.device == dev and pool_y.dtype == pool_x.dtype):
-            raise ValueError("eval_pool: pool_y must match pool_x in shape, dtype and device (or be None)")
-        al = lambda t: t if t is None or (t.is_contiguous() and t.data_ptr() % 16 == 0) else t.contiguous().clone()
-        pool_x, pool_y = al(pool_x), al(pool_y)
+        pool_x = _recording("eval_pool", "pool_x", pool_x, dev, nonempty=True)
+        if pool_y is not None:
+            if not (torch.is_tensor(pool_y) and pool_y.shape == pool_x.shape and pool_y.device == dev and pool_y.dtype == pool_x.dtype):
+                raise ValueError("eval_pool: pool_y must match pool_x in shape, dtype and device (or be None)")
+            pool_y = _recording("eval_pool", "pool_y", pool_y, dev)
         want_out = bool(want_out or pool_y is None)
-        B = int(batch or self.max_batch)
-        if B < 1:
-            raise ValueError(f"eval_pool: batch = {B}")
-        d = self.dims.with_batch(B)
-        d.prec, d.loss_scale, d.clip_all = _lib.PREC[self.compute_dtype], self.loss_scale, int(self.clip_all)
+        d = self._infer_dims("eval_pool", batch)
         host = lambda t: np.ascontiguousarray(t.detach().cpu().numpy() if torch.is_tensor(t) else t, dtype=np.int64).reshape(-1)
         off_h, len_h = host(off), host(length)
         nfiles = int(len_h.size)
         if nfiles < 1 or off_h.size != nfiles:
             raise ValueError(f"eval_pool: off and length must hold one entry per file ({off_h.size} and {nfiles})")
-        tables = self.__dict__.setdefault("_pool_tables", {})       # the device tables and win_off: built once per (offsets, lengths, geometry) from the host lengths
+        tables = self._kept("_pool_tables")     # the device tables and win_off: built once per (offsets, lengths, geometry) from the host lengths
         key = (off_h.tobytes(), len_h.tobytes(), d.L, d.y)
         if key not in tables:
             tables.clear()
@@ -672,26 +746,15 @@ class StepEngine:
             rows = int(self.lib.st_eval_pool_rows(C.byref(d), len_h.ctypes.data_as(C.POINTER(C.c_longlong)), nfiles, win.ctypes.data_as(C.POINTER(C.c_longlong))))
             tables[key] = tuple(torch.from_numpy(a).to(dev) for a in (off_h, len_h, win)) + (rows,)
         off_d, len_d, win_d, rows = tables[key]
-        kn = None
-        if d.K:
-            kn = torch.as_tensor(knobs).to(device=dev, dtype=torch.float32).reshape(-1, d.K).contiguous()
-            if kn.shape[0] != nfiles:
-                raise ValueError(f"eval_pool: knobs has {kn.shape[0]} rows for {nfiles} files")
-        sizes = self.__dict__.setdefault("_pool_sizes", {})
-        if (B, self.compute_dtype) not in sizes:
-            sizes[(B, self.compute_dtype)] = int(self.lib.st_eval_pool_ws_bytes(C.byref(d)))
-        need = sizes[(B, self.compute_dtype)]
-        if need <= 0:
-            raise RuntimeError(f"eval_pool: st_eval_pool_supported refuses this geometry (T={d.T}, OT={d.OT}): the wide autoencoder geometries stay on forward()")
-        if getattr(self, "_pool_ws", None) is None or self._pool_ws.numel() < need:
-            self._pool_ws = torch.zeros(need, dtype=torch.uint8, device=dev)
+        kn, _ = _knob_rows("eval_pool", knobs, d.K, dev, (nfiles,), f" for {nfiles} files")
+        ws = self._own_ws("eval_pool", "_pool_ws", d)
         stats = torch.empty(nfiles, _lib.POOL_STATS, dtype=torch.float64, device=dev) if pool_y is not None else None
         out = torch.empty(pool_x.numel(), dtype=torch.float32, device=dev) if want_out else None
         self.generation += 1
-        self._call("st_eval_pool", C.byref(d), _lib.ptr(self.params), _lib.PCM_S16 if pool_x.dtype == torch.int16 else _lib.PCM_F32,
+        self._call("st_eval_pool", C.byref(d), _lib.ptr(self.params), _pcm(pool_x),
                    C.c_void_p(pool_x.data_ptr()), None if pool_y is None else C.c_void_p(pool_y.data_ptr()), C.c_void_p(off_d.data_ptr()), C.c_void_p(len_d.data_ptr()),
                    C.c_void_p(win_d.data_ptr()), nfiles, rows, int(pool_x.numel()), _lib.ptr(kn), None if stats is None else C.c_void_p(stats.data_ptr()),
-                   None if out is None else C.c_void_p(out.data_ptr()), _lib.ptr(self._pool_ws), self._stream())
+                   None if out is None else C.c_void_p(out.data_ptr()), _lib.ptr(ws), self._stream())
         return stats, out
 
     # ---------------------------------------------------------------- predict session: inference fed block by block
@@ -726,10 +789,9 @@ class StepEngine:
         L, y, K = self.dims.L, self.dims.y, self.dims.K
         n_out = max(n - (L - y), 0)
         sig = signal_2d.float() / 32767.0 if signal_2d.dtype == torch.int16 else signal_2d
-        nwin = 1 if n < L else -(-(n - L) // y) + 1
-        kn = torch.as_tensor(knobs).to(device=self.device, dtype=torch.float32).reshape(-1, K) if K else torch.zeros(1, 0, device=self.device)
-        if kn.shape[0] not in (1, C_):
-            raise ValueError(f"predict_channels: knobs has {kn.shape[0]} rows: one row, or one per channel ({C_})")
+        from .predict import _nwin
+        nwin = _nwin(n, L, y)
+        kn = _knob_rows("predict_channels", knobs, K, self.device, (1, C_), f": one row, or one per channel ({C_})")[0] if K else torch.zeros(1, 0, device=self.device)
         res = torch.empty(C_, n_out, dtype=torch.float32, device=self.device) if out is None else out
         bs = min(int(batch or self.max_batch), self.max_batch)
         for c in range(C_ if n_out else 0):
@@ -748,26 +810,6 @@ class StepEngine:
         d.prec = _lib.PREC[self.compute_dtype]
         return bool(self.lib.st_decode_supported(C.byref(d)))
 
-    def _coded_dims(self, what, batch):
-        B = int(batch or self.max_batch)
-        if B < 1:
-            raise ValueError(f"{what}: batch = {B}")
-        d = self.dims.with_batch(B)
-        d.prec, d.loss_scale, d.clip_all = _lib.PREC[self.compute_dtype], self.loss_scale, int(self.clip_all)
-        return d
-
-    def _coded_ws(self, what, d):
-        """The workspace of encode_long / decode_long: one of their own (st_decode_ws_bytes, allocated on first use), not predict_long's."""
-        sizes = self.__dict__.setdefault("_decode_sizes", {})
-        if (d.B, self.compute_dtype) not in sizes:
-            sizes[(d.B, self.compute_dtype)] = int(self.lib.st_decode_ws_bytes(C.byref(d)))
-        need = sizes[(d.B, self.compute_dtype)]
-        if need <= 0:
-            raise RuntimeError(f"{what}: st_decode_supported refuses this geometry (T={d.T}, OT={d.OT}): the wide autoencoder geometries stay on predict_long's batched route")
-        if getattr(self, "_decode_ws", None) is None or self._decode_ws.numel() < need:
-            self._decode_ws = torch.zeros(need, dtype=torch.uint8, device=self.device)
-        return self._decode_ws
-
     def _geometry_key(self):
         return tuple(getattr(self.dims, k) for k in ("L", "N", "H", "T", "OT", "F", "K", "y"))
 
@@ -776,20 +818,15 @@ class StepEngine:
         polar form and encoder layers 1..4 of both autoencoders.  signal as predict_long takes it.  Returns a RecordingCode for decode_long() and
         fit_knobs(code=...); it is valid for this geometry, this compute dtype, this recording and the parameters as they are now -- that the parameters have not
         changed since the encode is the caller's precondition.  No host sync; self.ws is not written."""
-        if not (torch.is_tensor(signal) and signal.dim() == 1 and signal.device == self.device and signal.dtype in (torch.float32, torch.int16)):
-            raise ValueError(f"encode_long: signal must be a 1-D float32 or int16 tensor on {self.device}")
-        signal = signal.contiguous()
-        if signal.data_ptr() % 16:
-            signal = signal.clone()
-        d = self._coded_dims("encode_long", batch)
-        ws = self._coded_ws("encode_long", d)
+        signal = _recording("encode_long", "signal", signal, self.device)
+        d = self._infer_dims("encode_long", batch)
+        ws = self._own_ws("encode_long", "_decode_ws", d)
         n = int(signal.numel())
         nwin = int(self.lib.st_predict_windows(C.byref(d), n))
         nbytes = int(self.lib.st_code_bytes(C.byref(d), n))
         code = torch.empty(max(nbytes, 16) // 4, dtype=torch.float32, device=self.device)
         if n > 0:
-            self._call("st_encode_long", C.byref(d), _lib.ptr(self.params), _lib.PCM_S16 if signal.dtype == torch.int16 else _lib.PCM_F32,
-                       C.c_void_p(signal.data_ptr()), n, _lib.ptr(code), _lib.ptr(ws), self._stream())
+            self._call("st_encode_long", C.byref(d), _lib.ptr(self.params), _pcm(signal), C.c_void_p(signal.data_ptr()), n, _lib.ptr(code), _lib.ptr(ws), self._stream())
         return RecordingCode(code, signal, n, nwin, self._geometry_key(), self.compute_dtype)
 
     def _check_code(self, what, code):
@@ -817,25 +854,14 @@ class StepEngine:
         per window); returns [S, n_out], row s what predict_long gives at setting s up to the order of a few sums.  out: a float32 device tensor [S, pitch] with
         pitch >= n_out, pitch % 4 == 0, 16-byte aligned rows, to write into.  batch need not be the batch of the encode.  No host sync; self.ws is not written."""
         self._check_code("decode_long", code)
-        d = self._coded_dims("decode_long", batch)
-        ws = self._coded_ws("decode_long", d)
+        d = self._infer_dims("decode_long", batch)
+        ws = self._own_ws("decode_long", "_decode_ws", d)
         n, nwin = code.n, code.nwin
         n_out = int(self.lib.st_predict_out_samples(C.byref(d), n))
-        single = False
+        kn, single, S, rows = None, False, 1, 1
         if d.K:
-            kn = torch.as_tensor(knobs).to(device=self.device, dtype=torch.float32)
-            single = kn.dim() == 1
-            if kn.dim() == 3:
-                if int(kn.shape[1]) not in (1, nwin) or int(kn.shape[2]) != d.K:
-                    raise ValueError(f"decode_long: knobs [S, rows, K] has {int(kn.shape[1])} rows per setting: one row, or one per window ({nwin} windows for {n} samples)")
-            else:
-                kn = kn.reshape(-1, 1, d.K)
-            kn = kn.contiguous()
+            kn, single = _knob_settings("decode_long", knobs, d.K, nwin, n, self.device)
             S, rows = int(kn.shape[0]), int(kn.shape[1])
-        else:
-            kn, S, rows = None, 1, 1
-        if S < 1:
-            raise ValueError("decode_long: no knob setting")
         pitch = (n_out + 3) // 4 * 4
         if out is None:
             out = torch.empty(S, pitch, dtype=torch.float32, device=self.device)
@@ -843,7 +869,7 @@ class StepEngine:
                   out.stride(0) >= n_out and out.stride(0) % 4 == 0 and int(out.shape[1]) >= min(n_out, out.stride(0)) and out.data_ptr() % 16 == 0):
             raise ValueError(f"decode_long: out must be a 16-byte aligned float32 tensor [S >= {S}, >= {n_out}] on {self.device} with a row pitch that is a multiple of 4")
         if n_out > 0:
-            self._call("st_decode_long", C.byref(d), _lib.ptr(self.params), _lib.ptr(code.code), _lib.PCM_S16 if code.signal.dtype == torch.int16 else _lib.PCM_F32,
+            self._call("st_decode_long", C.byref(d), _lib.ptr(self.params), _lib.ptr(code.code), _pcm(code.signal),
                        C.c_void_p(code.signal.data_ptr()), n, _lib.ptr(kn), rows, S, C.c_void_p(out.data_ptr()), int(out.stride(0)), _lib.ptr(ws), self._stream())
         y = out[:S, :n_out]
         return y[0] if single else y
@@ -852,6 +878,16 @@ class StepEngine:
     def fit_knobs_supported(self):
         """Whether fit_knobs() runs this geometry (st_fit_knobs_supported: predict_supported() and at least one knob; host arithmetic only)."""
         return bool(self.lib.st_fit_knobs_supported(C.byref(self.dims.with_batch(1))))
+
+    def _fit_args(self, what, first, signal, target, batch):
+        """What every knob fit and score does in front of its knobs: signal (named `first` in the messages) and target in one format, the dims of a model
+        that has knobs, the length and the window count."""
+        signal, target = _recording_pair(what, signal, target, self.device, first)
+        d = self._infer_dims(what, batch)
+        if d.K < 1:
+            raise ValueError(f"{what}: the model has no knobs")
+        n = int(signal.numel())
+        return d, signal, target, n, int(self.lib.st_predict_windows(C.byref(d), n))
 
     def fit_knobs(self, signal, target, knobs, steps=50, lr=0.05, betas=(0.9, 0.999), eps=1e-8, batch=None, state=None, want_grads=False):
         """The knob settings for which the model turns `signal` into `target`, fitted on the device in ONE C call (st_fit_knobs in include/signaltrain_hip.h):
@@ -870,100 +906,30 @@ class StepEngine:
             code = signal
             self._check_code("fit_knobs", code)
             signal = code.signal
-        for name, t in (("signal", signal), ("target", target)):
-            if not (torch.is_tensor(t) and t.dim() == 1 and t.device == self.device and t.dtype in (torch.float32, torch.int16)):
-                raise ValueError(f"fit_knobs: {name} must be a 1-D float32 or int16 tensor on {self.device}")
-        if signal.numel() != target.numel():
-            raise ValueError(f"fit_knobs: signal has {signal.numel()} samples, target {target.numel()}")
-        if signal.dtype != target.dtype:          # the C rule for int16: (float)((double)s / 32767.0)
-            signal, target = ((t.double() / 32767.0).float() if t.dtype == torch.int16 else t for t in (signal, target))
-        align = 8 if signal.dtype == torch.int16 else 16
-
-        def aligned(t):
-            t = t.contiguous()
-            return t.clone() if t.data_ptr() % align else t      # a view that starts off the boundary the kernels' quads need
-        signal, target = aligned(signal), aligned(target)
-        B = int(batch or self.max_batch)
-        if B < 1:
-            raise ValueError(f"fit_knobs: batch = {B}")
+        d, signal, target, n, nwin = self._fit_args("fit_knobs", "signal", signal, target, batch)
         steps = int(steps)
-        d = self.dims.with_batch(B)
-        d.prec, d.loss_scale, d.clip_all = _lib.PREC[self.compute_dtype], self.loss_scale, int(self.clip_all)
-        if d.K < 1:
-            raise ValueError("fit_knobs: the model has no knobs")
-        n = int(signal.numel())
-        nwin = int(self.lib.st_predict_windows(C.byref(d), n))
-        kn = torch.as_tensor(knobs).to(device=self.device, dtype=torch.float32).reshape(-1, d.K).clone()
-        rows = int(kn.shape[0])
-        if rows not in (1, nwin):
-            raise ValueError(f"fit_knobs: knobs has {rows} rows: one row, or one per window ({nwin} windows for {n} samples)")
-        if state is None:
-            m, v, first = torch.zeros_like(kn), torch.zeros_like(kn), 1
-        else:
-            m, v, first = state
-            m = m.to(device=self.device, dtype=torch.float32).reshape(rows, d.K).clone()
-            v = v.to(device=self.device, dtype=torch.float32).reshape(rows, d.K).clone()
-            first = int(first)
-        sizes = self.__dict__.setdefault("_fit_sizes", {})           # as predict_long: the size query carves every batch 1 .. B, once per (B, dtype)
-        if (B, self.compute_dtype) not in sizes:
-            sizes[(B, self.compute_dtype)] = int(self.lib.st_fit_knobs_ws_bytes(C.byref(d)))
-        need = sizes[(B, self.compute_dtype)]
-        if need <= 0:
-            raise RuntimeError(f"fit_knobs: st_fit_knobs_supported refuses this geometry (T={d.T}, OT={d.OT}): the wide autoencoder geometries stay on the batched route")
-        if getattr(self, "_fit_ws", None) is None or self._fit_ws.numel() < need:
-            self._fit_ws = torch.zeros(need, dtype=torch.uint8, device=self.device)
+        kn, rows = _knob_rows("fit_knobs", knobs, d.K, self.device, (1, nwin), _per_window(nwin, n))
+        kn = kn.clone()
+        m, v, first = _adam_state(state, kn, self.device)
+        ws = self._own_ws("fit_knobs", "_fit_ws", d)
         loss_hist = torch.zeros(max(steps, 0), dtype=torch.float64, device=self.device)
         grad_hist = torch.zeros(max(steps, 0), rows, d.K, dtype=torch.float32, device=self.device) if want_grads else None
         head = ("st_fit_knobs", C.byref(d), _lib.ptr(self.params)) if code is None else ("st_fit_knobs_coded", C.byref(d), _lib.ptr(self.params), _lib.ptr(code.code))
-        self._call(*head, _lib.PCM_S16 if signal.dtype == torch.int16 else _lib.PCM_F32,
-                   C.c_void_p(signal.data_ptr()), C.c_void_p(target.data_ptr()), n, _lib.ptr(kn), rows, _lib.ptr(m), _lib.ptr(v),
+        self._call(*head, _pcm(signal), C.c_void_p(signal.data_ptr()), C.c_void_p(target.data_ptr()), n, _lib.ptr(kn), rows, _lib.ptr(m), _lib.ptr(v),
                    first, steps, float(lr), float(betas[0]), float(betas[1]), float(eps),
-                   C.c_void_p(loss_hist.data_ptr()), _lib.ptr(grad_hist), _lib.ptr(self._fit_ws), self._stream())
+                   C.c_void_p(loss_hist.data_ptr()), _lib.ptr(grad_hist), _lib.ptr(ws), self._stream())
         shape = (d.K,) if (rows == 1 and torch.as_tensor(knobs).dim() == 1) else (rows, d.K)
         return kn.reshape(shape), loss_hist, grad_hist, (m, v, first + steps)
 
     # ---------------------------------------------------------------- many knob settings from one code
     def _multi_args(self, what, code, target, knobs, batch):
-        """What score_knobs and fit_knobs_multi share: the code's validity (fit_knobs' checks), the recordings in one format, the settings as [S, rows, K], the
-        dims and the workspace (st_knob_multi_ws_bytes, the engine's own, allocated on first use)."""
+        """What score_knobs and fit_knobs_multi share: the code's validity (fit_knobs' checks), the recordings in one format, the settings as [S, rows, K] --
+        cloned --, the dims and the workspace (st_knob_multi_ws_bytes, the engine's own)."""
         self._check_code(what, code)
-        signal = code.signal
-        if not (torch.is_tensor(target) and target.dim() == 1 and target.device == self.device and target.dtype in (torch.float32, torch.int16)):
-            raise ValueError(f"{what}: target must be a 1-D float32 or int16 tensor on {self.device}")
-        if signal.numel() != target.numel():
-            raise ValueError(f"{what}: the recording has {signal.numel()} samples, target {target.numel()}")
-        if signal.dtype != target.dtype:          # the C rule for int16: (float)((double)s / 32767.0)
-            signal, target = ((t.double() / 32767.0).float() if t.dtype == torch.int16 else t for t in (signal, target))
-        align = 8 if signal.dtype == torch.int16 else 16
-
-        def aligned(t):
-            t = t.contiguous()
-            return t.clone() if t.data_ptr() % align else t
-        signal, target = aligned(signal), aligned(target)
-        d = self._coded_dims(what, batch)
-        if d.K < 1:
-            raise ValueError(f"{what}: the model has no knobs")
-        n, nwin = code.n, code.nwin
-        kn = torch.as_tensor(knobs).to(device=self.device, dtype=torch.float32)
-        if kn.dim() == 2 and int(kn.shape[1]) == d.K:
-            kn = kn.reshape(-1, 1, d.K)
-        elif not (kn.dim() == 3 and int(kn.shape[1]) in (1, nwin) and int(kn.shape[2]) == d.K):
-            raise ValueError(f"{what}: knobs must be [S, {d.K}] or [S, rows, {d.K}] with one row per setting, or one per window ({nwin} windows for {n} samples), "
-                             f"not {tuple(kn.shape)}")
-        kn = kn.contiguous().clone()
+        d, signal, target, n, nwin = self._fit_args(what, "the recording", code.signal, target, batch)
+        kn = _knob_settings(what, knobs, d.K, nwin, n, self.device, strict=True)[0].clone()
         S = int(kn.shape[0])
-        if S < 1:
-            raise ValueError(f"{what}: no knob setting")
-        sizes = self.__dict__.setdefault("_multi_sizes", {})
-        if (d.B, S, self.compute_dtype) not in sizes:       # as fit_knobs: the size query carves every batch 1 .. B, once per (B, S, dtype)
-            sizes[(d.B, S, self.compute_dtype)] = int(self.lib.st_knob_multi_ws_bytes(C.byref(d), S))
-        need = sizes[(d.B, S, self.compute_dtype)]
-        if need <= 0:
-            raise RuntimeError(f"{what}: st_fit_knobs_supported refuses this geometry (T={d.T}, OT={d.OT}): the wide autoencoder geometries stay on the batched route")
-        if getattr(self, "_multi_ws", None) is None or self._multi_ws.numel() < need:
-            self._multi_ws = torch.zeros(need, dtype=torch.uint8, device=self.device)
-        fmt = _lib.PCM_S16 if signal.dtype == torch.int16 else _lib.PCM_F32
-        return d, signal, target, fmt, kn, S, n, nwin
+        return d, signal, target, kn, S, n, nwin, self._own_ws(what, "_multi_ws", d, S)
 
     def score_knobs(self, code, target, knobs, batch=None, per_window=False):
         """J = mean log-cosh of (model output - target) of the recording behind `code` (encode_long) at S knob settings, in ONE C call (st_score_knobs_coded in
@@ -972,11 +938,11 @@ class StepEngine:
         win_loss [S, nwin] float32), win_loss[s, w] window w's share of loss[s].  A recording of at most half a batch is stacked: rows of a batch are
         (setting, window) pairs (st_knob_multi_plan).  The code must be valid (fit_knobs' checks; that the parameters have not changed is the caller's
         precondition).  No host sync; self.ws is not written."""
-        d, signal, target, fmt, kn, S, n, nwin = self._multi_args("score_knobs", code, target, knobs, batch)
+        d, signal, target, kn, S, n, nwin, ws = self._multi_args("score_knobs", code, target, knobs, batch)
         loss = torch.zeros(S, dtype=torch.float64, device=self.device)
         win = torch.zeros(S, nwin, dtype=torch.float32, device=self.device) if per_window else None
-        self._call("st_score_knobs_coded", C.byref(d), _lib.ptr(self.params), _lib.ptr(code.code), fmt, C.c_void_p(signal.data_ptr()), C.c_void_p(target.data_ptr()), n,
-                   _lib.ptr(kn), int(kn.shape[1]), S, C.c_void_p(loss.data_ptr()), _lib.ptr(win), _lib.ptr(self._multi_ws), self._stream())
+        self._call("st_score_knobs_coded", C.byref(d), _lib.ptr(self.params), _lib.ptr(code.code), _pcm(signal), C.c_void_p(signal.data_ptr()),
+                   C.c_void_p(target.data_ptr()), n, _lib.ptr(kn), int(kn.shape[1]), S, C.c_void_p(loss.data_ptr()), _lib.ptr(win), _lib.ptr(ws), self._stream())
         return (loss, win) if per_window else loss
 
     def fit_knobs_multi(self, code, target, knobs, steps=50, lr=0.05, betas=(0.9, 0.999), eps=1e-8, batch=None, state=None, want_grads=False):
@@ -985,21 +951,15 @@ class StepEngine:
         (m, v, first_step) as a previous call returned it, so that calls chain (default: zeros and step 1), as fit_knobs.  Returns (knobs [S, ...] in the shape
         given, loss_hist [steps, S] float64, (m, v, next_step)) and, with want_grads=True, grads [steps, S, rows, K] behind them.  A recording of at most half a
         batch is stacked: rows of a batch are (setting, window) pairs (st_knob_multi_plan).  No host sync; self.ws is not written."""
-        d, signal, target, fmt, kn, S, n, nwin = self._multi_args("fit_knobs_multi", code, target, knobs, batch)
+        d, signal, target, kn, S, n, nwin, ws = self._multi_args("fit_knobs_multi", code, target, knobs, batch)
         steps = int(steps)
         rows = int(kn.shape[1])
-        if state is None:
-            m, v, first = torch.zeros_like(kn), torch.zeros_like(kn), 1
-        else:
-            m, v, first = state
-            m = m.to(device=self.device, dtype=torch.float32).reshape(S, rows, d.K).clone()
-            v = v.to(device=self.device, dtype=torch.float32).reshape(S, rows, d.K).clone()
-            first = int(first)
+        m, v, first = _adam_state(state, kn, self.device)
         loss_hist = torch.zeros(max(steps, 0), S, dtype=torch.float64, device=self.device)
         grads = torch.zeros(max(steps, 0), S, rows, d.K, dtype=torch.float32, device=self.device) if want_grads else None
-        self._call("st_fit_knobs_multi_coded", C.byref(d), _lib.ptr(self.params), _lib.ptr(code.code), fmt, C.c_void_p(signal.data_ptr()),
+        self._call("st_fit_knobs_multi_coded", C.byref(d), _lib.ptr(self.params), _lib.ptr(code.code), _pcm(signal), C.c_void_p(signal.data_ptr()),
                    C.c_void_p(target.data_ptr()), n, _lib.ptr(kn), rows, S, _lib.ptr(m), _lib.ptr(v), first, steps, float(lr), float(betas[0]), float(betas[1]),
-                   float(eps), C.c_void_p(loss_hist.data_ptr()), _lib.ptr(grads), _lib.ptr(self._multi_ws), self._stream())
+                   float(eps), C.c_void_p(loss_hist.data_ptr()), _lib.ptr(grads), _lib.ptr(ws), self._stream())
         shape = tuple(torch.as_tensor(knobs).shape)
         res = (kn.reshape(shape), loss_hist, (m.reshape(shape), v.reshape(shape), first + steps))
         return res + (grads,) if want_grads else res

@@ -27,6 +27,30 @@ _warned_sweep_unsupported = False
 _warned_search_unsupported = False
 
 
+def _nwin(n, chunk_size, out_chunk_size):
+    """Windows of a recording of n samples: audio.sliding_window's count (audio.py:42-45) -- one, then one more per started out_chunk_size behind chunk_size."""
+    return 1 if n < chunk_size else -(-(n - chunk_size) // out_chunk_size) + 1
+
+
+def _engine_for(what, model, device, rows, chunk_size, out_chunk_size):
+    """The model's engine for batches of `rows` windows on `device`, refused unless its geometry is the caller's chunk sizes."""
+    eng = model.engine(torch.empty((), dtype=torch.float32, device=device).expand(rows, chunk_size))      # shape and device only: nothing is read
+    if (eng.dims.L, eng.dims.y) != (chunk_size, out_chunk_size):
+        raise ValueError(f"{what}: chunk_size / out_chunk_size = {chunk_size} / {out_chunk_size}, the model has {eng.dims.L} / {eng.dims.y}")
+    return eng
+
+
+def _compand(a):
+    """audio.mu_compand of a host array, as contiguous float32 (an elementwise map: the whole recording once, where the reference compands every window)."""
+    from . import audio
+    return np.ascontiguousarray(audio.mu_compand(a), dtype=np.float32)
+
+
+def _logcosh(d):
+    """log cosh(d) elementwise, in the overflow-free form |d| + log1p(exp(-2 |d|)) - log 2: the term of every knob-fit objective."""
+    a = d.abs()
+    return a + torch.log1p(torch.exp(-2.0 * a)) - 0.6931471805599453
+
 
 def _windows(signal, chunk_size, step, device):
     """The zero-padded signal on the device and its overlapping windows as a strided view: audio.sliding_window's padding rule (audio.py:42-45)."""
@@ -80,9 +104,8 @@ def predict_long(signal, knobs_nn, model, chunk_size, out_chunk_size, sr=44100, 
             signal = (signal.astype(np.float64) / 32767.0).astype(np.float32)
     signal = np.ascontiguousarray(signal, dtype=np.float32)
     if compand:                                                        # predict_long.py:38-40 compands every window; the map is elementwise, so the signal once
-        from . import audio
         print("Companding input")
-        signal = np.ascontiguousarray(audio.mu_compand(signal), dtype=np.float32)
+        signal = _compand(signal)
     overlap = chunk_size - out_chunk_size
     step = chunk_size - overlap                                        # == out_chunk_size
     # zeros at the end until the windows tile the signal
@@ -107,9 +130,8 @@ def _resident(signal, device, compand):
     host = signal.detach().cpu().numpy() if torch.is_tensor(signal) else signal
     host = np.ascontiguousarray(host, dtype=np.float32)
     if compand:                                                        # a host map before the upload, as on the batched route
-        from . import audio
         print("Companding input")
-        host = np.ascontiguousarray(audio.mu_compand(host), dtype=np.float32)
+        host = _compand(host)
     return torch.from_numpy(host).to(device)
 
 
@@ -117,11 +139,9 @@ def _predict_device(signal, knobs_nn, model, chunk_size, out_chunk_size, device,
     """route="device" of predict_long; None where the library does not run this geometry that way (the caller then takes the batched route)."""
     global _warned_unsupported
     n = int(signal.shape[-1])
-    nwin = 1 if n < chunk_size else -(-(n - chunk_size) // out_chunk_size) + 1
+    nwin = _nwin(n, chunk_size, out_chunk_size)
     bs = max(min(int(batch_size), nwin), 1)
-    eng = model.engine(torch.empty((), dtype=torch.float32, device=device).expand(bs, chunk_size))      # shape and device only: nothing is read
-    if (eng.dims.L, eng.dims.y) != (chunk_size, out_chunk_size):
-        raise ValueError(f"predict_long: chunk_size / out_chunk_size = {chunk_size} / {out_chunk_size}, the model has {eng.dims.L} / {eng.dims.y}")
+    eng = _engine_for("predict_long", model, device, bs, chunk_size, out_chunk_size)
     if not eng.predict_supported():
         if not _warned_unsupported:
             _warned_unsupported = True
@@ -145,9 +165,7 @@ def predict_stream(blocks, knobs, model, chunk_size, out_chunk_size, device=None
     out_chunk_size) samples per channel.  knobs: [K] or [C, K], or a callable block_index -> knobs evaluated per block (knob automation at block rate).
     A numpy block yields a numpy array, a tensor block a device tensor (no host sync then).  batch_size: most (channel, window) rows per internal batch."""
     device = torch.device(device) if device is not None else next(model.parameters()).device
-    eng = model.engine(torch.empty((), dtype=torch.float32, device=device).expand(max(int(batch_size), 1), chunk_size))      # shape and device only: nothing is read
-    if (eng.dims.L, eng.dims.y) != (chunk_size, out_chunk_size):
-        raise ValueError(f"predict_stream: chunk_size / out_chunk_size = {chunk_size} / {out_chunk_size}, the model has {eng.dims.L} / {eng.dims.y}")
+    eng = _engine_for("predict_stream", model, device, max(int(batch_size), 1), chunk_size, out_chunk_size)
     session, held, index = None, None, 0
 
     def push(block, final):
@@ -187,11 +205,9 @@ def predict_sweep(signal, knob_settings, model, chunk_size, out_chunk_size, sr=4
     device = torch.device(device) if device is not None else next(model.parameters()).device
     if route == "device":
         n = int(signal.shape[-1])
-        nwin = 1 if n < chunk_size else -(-(n - chunk_size) // out_chunk_size) + 1
+        nwin = _nwin(n, chunk_size, out_chunk_size)
         bs = max(min(int(batch_size), nwin), 1)
-        eng = model.engine(torch.empty((), dtype=torch.float32, device=device).expand(bs, chunk_size))      # shape and device only: nothing is read
-        if (eng.dims.L, eng.dims.y) != (chunk_size, out_chunk_size):
-            raise ValueError(f"predict_sweep: chunk_size / out_chunk_size = {chunk_size} / {out_chunk_size}, the model has {eng.dims.L} / {eng.dims.y}")
+        eng = _engine_for("predict_sweep", model, device, bs, chunk_size, out_chunk_size)
         if eng.decode_supported():
             sig = _resident(signal, device, compand)
             if verbose:
@@ -236,8 +252,7 @@ def fit_knobs(signal, target, model, chunk_size, out_chunk_size, steps=50, lr=0.
     signal = np.ascontiguousarray(signal, dtype=np.float32); target = np.ascontiguousarray(target, dtype=np.float32)
     assert signal.shape == target.shape and signal.ndim == 1, (signal.shape, target.shape)
     if compand:
-        from . import audio
-        signal = np.ascontiguousarray(audio.mu_compand(signal), dtype=np.float32); target = np.ascontiguousarray(audio.mu_compand(target), dtype=np.float32)
+        signal, target = _compand(signal), _compand(target)
     x = _windows(signal, chunk_size, out_chunk_size, device)
     t = _windows(target, chunk_size, out_chunk_size, device)[:, chunk_size - out_chunk_size:]
     nwin = x.shape[0]
@@ -259,8 +274,7 @@ def fit_knobs(signal, target, model, chunk_size, out_chunk_size, steps=50, lr=0.
                 kb = kn.detach().reshape(1, K).expand(xb.shape[0], K).contiguous()
                 y_hat = eng.forward(xb, kb, save_for_backward=True)[0]
                 d = y_hat - tb
-                a = d.abs()
-                loss += (a + torch.log1p(torch.exp(-2.0 * a)) - 0.6931471805599453).sum() / n
+                loss += _logcosh(d).sum() / n
                 g_y = torch.tanh(d) / n
                 grad += eng.backward_with_knob_grad(xb, kb, g_y)[1].sum(0)
         history.append(float(loss.item()))
@@ -275,8 +289,7 @@ def fit_knobs(signal, target, model, chunk_size, out_chunk_size, steps=50, lr=0.
 
 def _logcosh_mean(y, t):
     """mean log cosh(y - t) in float64 on y's device: the objective of fit_knobs on outputs that exist."""
-    a = (y.double() - t.double()).abs()
-    return float((a + torch.log1p(torch.exp(-2.0 * a)) - 0.6931471805599453).mean().item())
+    return float(_logcosh(y.double() - t.double()).mean().item())
 
 
 def _never_worse(finals, final_losses, starts, start_losses):
@@ -308,16 +321,13 @@ def search_knobs(signal, target, model, chunk_size, out_chunk_size, candidates, 
     signal = np.ascontiguousarray(signal, dtype=np.float32); target = np.ascontiguousarray(target, dtype=np.float32)
     assert signal.shape == target.shape and signal.ndim == 1, (signal.shape, target.shape)
     n = int(signal.shape[0])
-    nwin = 1 if n < chunk_size else -(-(n - chunk_size) // out_chunk_size) + 1
+    nwin = _nwin(n, chunk_size, out_chunk_size)
     if route == "device":
         bs = max(int(batch_size), 1)                                       # not clipped to the window count: a short recording is stacked into the batch
-        eng = model.engine(torch.empty((), dtype=torch.float32, device=device).expand(min(bs, nwin), chunk_size))      # shape and device only: nothing is read
-        if (eng.dims.L, eng.dims.y) != (chunk_size, out_chunk_size):
-            raise ValueError(f"search_knobs: chunk_size / out_chunk_size = {chunk_size} / {out_chunk_size}, the model has {eng.dims.L} / {eng.dims.y}")
+        eng = _engine_for("search_knobs", model, device, min(bs, nwin), chunk_size, out_chunk_size)
         if eng.fit_knobs_supported():
             if compand:
-                from . import audio
-                signal = np.ascontiguousarray(audio.mu_compand(signal), dtype=np.float32); target = np.ascontiguousarray(audio.mu_compand(target), dtype=np.float32)
+                signal, target = _compand(signal), _compand(target)
             with torch.no_grad():
                 sig, tgt = torch.from_numpy(signal).to(device), torch.from_numpy(target).to(device)
                 code = eng.encode_long(sig, batch=min(bs, nwin))
@@ -335,10 +345,7 @@ def search_knobs(signal, target, model, chunk_size, out_chunk_size, candidates, 
 
     def objective(k):          # the batched route's J: over the nwin * out_chunk_size window outputs, the tail behind the recording's end against zeros
         y = predict_long(signal, k, model, chunk_size, out_chunk_size, compand=compand, batch_size=batch_size)
-        t = target
-        if compand:
-            from . import audio
-            t = np.ascontiguousarray(audio.mu_compand(target), dtype=np.float32)
+        t = _compand(target) if compand else target
         return _logcosh_mean(torch.from_numpy(np.ascontiguousarray(y)), torch.from_numpy(t[chunk_size - out_chunk_size:][:y.shape[0]]))
     scored = np.array([objective(k) for k in cand])
     order = np.argsort(scored, kind="stable")[:keep]
@@ -356,11 +363,9 @@ def _fit_device(signal, target, model, chunk_size, out_chunk_size, steps, lr, in
     signal = np.ascontiguousarray(signal, dtype=np.float32); target = np.ascontiguousarray(target, dtype=np.float32)
     assert signal.shape == target.shape and signal.ndim == 1, (signal.shape, target.shape)
     n = int(signal.shape[0])
-    nwin = 1 if n < chunk_size else -(-(n - chunk_size) // out_chunk_size) + 1
+    nwin = _nwin(n, chunk_size, out_chunk_size)
     bs = max(min(int(batch_size), nwin), 1)
-    eng = model.engine(torch.empty((), dtype=torch.float32, device=device).expand(bs, chunk_size))      # shape and device only: nothing is read
-    if (eng.dims.L, eng.dims.y) != (chunk_size, out_chunk_size):
-        raise ValueError(f"fit_knobs: chunk_size / out_chunk_size = {chunk_size} / {out_chunk_size}, the model has {eng.dims.L} / {eng.dims.y}")
+    eng = _engine_for("fit_knobs", model, device, bs, chunk_size, out_chunk_size)
     if not eng.fit_knobs_supported():
         if not _warned_fit_unsupported:
             _warned_fit_unsupported = True
@@ -368,8 +373,7 @@ def _fit_device(signal, target, model, chunk_size, out_chunk_size, steps, lr, in
                           "st_fit_knobs_supported); taking the batched route", RuntimeWarning, stacklevel=3)
         return None
     if compand:                                                        # a host map before the upload, as on the batched route
-        from . import audio
-        signal = np.ascontiguousarray(audio.mu_compand(signal), dtype=np.float32); target = np.ascontiguousarray(audio.mu_compand(target), dtype=np.float32)
+        signal, target = _compand(signal), _compand(target)
     K = int(model.num_knobs)
     kn0 = np.zeros(K, np.float32) if init is None else np.asarray(init, dtype=np.float32)
     kn0 = kn0.reshape(nwin, K) if (kn0.ndim == 2 and kn0.shape[0] == nwin and nwin > 1) else kn0.reshape(K)

@@ -168,6 +168,27 @@ def test_int16_signal_equals_its_float_image(level):
         assert float(b.abs().max()) > 0.1
 
 
+def test_int16_view_at_8_mod_16_is_read_in_place():
+    """An int16 recording that starts four samples (8 bytes) behind a 16-byte boundary is taken as it is -- the library reads int16 recordings as aligned
+    quads of four samples (pcm_align in st_api.hip) -- and gives the bits of an aligned clone of the same samples: predict_long, and encode_long + decode_long."""
+    eng, geo, P = engine("tiny", 3)
+    L, y = geo["L"], geo["y"]
+    n = L + 3 * y + 777 % y
+    assert int(eng.lib.st_predict_windows(C.byref(eng.dims), n)) == 5
+    buf = torch.zeros(n + 8, dtype=torch.int16, device=G.DEV)
+    view = buf[4:4 + n]
+    view.copy_(torch.from_numpy(np.round(signal(n, seed=11) * 30000).astype(np.int16)).to(G.DEV))
+    clone = view.clone()
+    assert buf.data_ptr() % 16 == 0 and view.data_ptr() % 16 == 8 and clone.data_ptr() % 16 == 0
+    kn = G.t(KN)
+    want = eng.predict_long(clone, kn)
+    assert want.numel() == n - (L - y) and float(want.abs().max()) > 0
+    assert torch.equal(eng.predict_long(view, kn), want)
+    code = eng.encode_long(view)
+    assert code.signal.data_ptr() == view.data_ptr()              # not copied
+    assert torch.equal(eng.decode_long(code, kn), eng.decode_long(eng.encode_long(clone), kn))
+
+
 def test_knob_automation():
     """One knob row per window (two settings alternating) against the oracle with the same per-window knobs at 1e-4; one row equals that row repeated
     over the windows bit for bit."""
