@@ -892,6 +892,39 @@ int st_live_feed_stream(int effect, unsigned family_mask, float synth_prob, int 
                         long long min_len, long long pool_samples,
                         float* x, float* y, float* knobs, long long* meta, float* scratch, void* stream);
 
+/* ---- a folder of recordings through an effect in one call: st_render_pool (csrc/st_render_pool.h) --------------------------------
+ * gen_dataset.py's step: every file of the folder WHOLE through the effect `effect` (an ST_FX_* id) at ONE knob setting per file.  The folder is the pool of
+ * st_file_feed / st_eval_pool: fmt, pool_x, file_off / file_len (device int64, in samples), pool_samples.  knobs_wc: device [nfiles][4], WORLD coordinates in the
+ * order of the effect's entry (4-control compressor: threshold dB, ratio, attack s, release s; ST_FX_COMP: threshold, ratio, attack / release s; ST_FX_LOWPASS:
+ * cutoff Hz; ST_FX_ECHO: delay in samples, ratio, echoes; ST_FX_DENOISE: strength); entries past the effect's count are not read.
+ * THE LAW.  For file f, after the offset and length clamps st_eval_pool applies (and len <= max_len), let xe be the float32 image of pool_x[file_off[f] .. + len)
+ * (ST_PCM_S16 converts as in st_file_feed) and len' = len rounded up to the multiple the effect's own entry demands, zeros appended.  Then out[file_off[f] + n],
+ * n in [0, len), is bit for bit sample n of
+ *   ST_FX_COMP4C    st_compressor_4c(xe, row f of knobs_wc, B = 1, L = ysz = len')        ST_FX_COMP     st_compressor(...), same arguments
+ *   ST_FX_LOWPASS   st_lowpass(...)                                                        ST_FX_ECHO     st_echo(...)
+ *   ST_FX_DENOISE   st_denoise_input(seed, first_file + f, xe, strength, 1, len') -- the noisy input; the target is the pool itself
+ *   ST_FX_DECOMP4C  as ST_FX_COMP4C -- the compressed input; the target is the pool itself
+ * seed / first_file: ST_FX_DENOISE only (file f is window first_file + f of the noise stream `seed`), ignored otherwise.
+ * Every sample of out inside a file's span is written; what lies between spans is not touched; a file of length 0 writes nothing.  The per-row NaN rules of the
+ * entries carry over per file: a cutoff outside (0, sr / 2) or an echo count outside 0 .. ST_ECHO_MAX makes that file's span NaN and nothing else.  file_off need
+ * not be a multiple of four.  Whatever the tables hold, no address outside [0, pool_samples) of the pool or of out is formed.  max_len: the longest file (host
+ * value); a longer device length is cut to it.
+ * scratch: st_render_pool_scratch_floats(effect, file_len_host, nfiles) floats, 16-byte aligned; its layout is the library's own ([per-file row offsets, built on
+ * the device from file_len | one row of round_up(len, 64) floats per file]; sized from the HOST lengths, which the device lengths must not exceed).  The size is 0
+ * for ST_FX_DENOISE (scratch may be NULL) and for bad arguments: a null table, nfiles < 1, a length < 0 or >= 2^31 - 64, an unknown effect.
+ * The 4-control compressor's attack / release chain is sequential per file: it runs one lane per file, 64 files per wave, each wave to the longest of its files.
+ * Asynchronous; no allocation, no hipMemcpy, no host synchronisation, no float atomics: a repeated call repeats its bits.
+ * Refused before any launch (ST_ERR_ARG, the rule in st_last_error()): a null required pointer (named); an unknown effect or fmt; nfiles < 1; pool_samples < 1;
+ * max_len < 0 or >= 2^31 - 64; sr <= 0; out or scratch not 16-byte aligned; pool_x not 16-byte aligned (int16: 8-byte); a null scratch where the size function
+ * is non-zero. */
+size_t st_render_pool_scratch_floats(int effect, const long long* file_len_host, int nfiles);   /* 0 for bad arguments */
+int st_render_pool(int effect, float sr, int fmt, const void* pool_x,
+                   const long long* file_off, const long long* file_len /* device int64 */, int nfiles,
+                   long long max_len /* host: the longest file */, long long pool_samples,
+                   const float* knobs_wc /* device [nfiles][4], world coordinates */,
+                   unsigned seed, unsigned long long first_file /* ST_FX_DENOISE only */,
+                   float* out /* [pool_samples] float32 */, float* scratch, void* stream);
+
 /* Gradient of the loss w.r.t. the (halved) input waveform, for callers with something trainable upstream of the model (the reference's
  * autograd provides it; nn_proc.py:307, cls_fe_dft.py:55-56).  Call right after st_model_bwd on the SAME workspace:
  *   gxh[b][n] = conv-transpose of the analysis output gradient with both bases, cropped by the Conv1d padding   [B][L]

@@ -37,8 +37,10 @@ if __name__ == "__main__":
     p.add_argument('--synthprob', metavar='P', type=float, default=0.0, help="with --inpath: the share of windows that are synthetic test signals instead, 0 to 1")
     p.add_argument('--preroll', metavar='N', type=int, default=0, help="with --inpath: samples of its own file the effect runs over in front of every recorded window, so "
                    "that the target carries the effect's state (the streamed target; a multiple of 4; 0 = the effect starts at zero state in every window)")
-    p.add_argument('--file-report', action='store_true', help="with --effect files: after the last epoch run every file of Val/ whole through the model at its own knob "
-                   "setting and print the per-file error table (one st_eval_pool call)")
+    p.add_argument('--file-report', action='store_true', help="with --effect files or --inpath: after the last epoch run every file of Val/ whole through the model at its own knob "
+                   "setting and print the per-file error table (one st_eval_pool call; with --inpath the targets are rendered by the live effect, one st_render_pool call)")
+    p.add_argument('--report-sp', type=int, default=None, metavar='N', help="with --inpath --file-report: N settings per knob, the grid over the first N ** K files of Val/ "
+                   "(default: seeded uniform settings)")
     p.add_argument('--freeze', default=None, type=lambda v: [n for n in v.split(',') if n], metavar='GROUPS',
                    help="comma-separated parameter groups that do not train: analysis, synthesis, aenc, phs_aenc, frontend (= analysis,synthesis: the autoencoders over fixed DFT bases)")
     p.add_argument('--unfreeze-epoch', type=int, default=None, metavar='E', help="with --freeze: the (0-based) epoch from which the frozen groups train as well (two-phase schedule)")
@@ -69,8 +71,10 @@ if __name__ == "__main__":
         raise SystemExit(f"--preroll {args.preroll}: a non-negative multiple of 4 samples")
     if args.preroll and args.inpath is None:
         raise SystemExit(f"--preroll {args.preroll} is the effect's history in front of windows of recorded input: give --inpath DIR as well")
-    if args.file_report and args.effect != 'files':
-        raise SystemExit("--file-report reports the recorded files of --path's Val/ folder: use it with --effect files")
+    if args.file_report and args.effect != 'files' and args.inpath is None:
+        raise SystemExit("--file-report reports the files of a Val/ folder, whole: use it with --effect files (recorded targets under --path) or with --inpath (the live effect)")
+    if args.report_sp is not None and (args.report_sp < 2 or not args.file_report or args.inpath is None):
+        raise SystemExit(f"--report-sp {args.report_sp}: at least 2 settings per knob, together with --inpath DIR --file-report")
     if args.inpath is not None and args.effect == 'files':
         raise SystemExit("--inpath runs a live effect on recorded input; --effect files trains on recorded input / target pairs (--path): give one")
 
@@ -93,6 +97,6 @@ if __name__ == "__main__":
                 target_type=args.target, lr_max=args.lrmax, in_checkpointname=args.checkpoint, compand=args.compand,
                 compute_dtype=args.dtype, device_feed=args.device_feed, resume_optimizer=args.resume_optimizer, device_eval=args.device_eval, choosers=args.choosers,
                 input_path=args.inpath, synth_prob=args.synthprob, preroll=args.preroll, freeze=args.freeze, unfreeze_epoch=args.unfreeze_epoch,
-                file_report=args.file_report)
+                file_report=args.file_report, report_settings_per=args.report_sp)
     if dist.is_initialized():
         dist.destroy_process_group()

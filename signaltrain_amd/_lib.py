@@ -151,6 +151,8 @@ SIGNATURES = {
     "st_eval_pool_rows": (C.c_longlong, [_D, C.POINTER(C.c_longlong), _i, C.POINTER(C.c_longlong)]),
     "st_eval_pool_ws_bytes": (C.c_size_t, [_D]),
     "st_eval_pool": (_i, [_D, _p, _i, _p, _p, _p, _p, _p, _i, C.c_longlong, C.c_longlong, _p, _p, _p, _p, _p]),
+    "st_render_pool_scratch_floats": (C.c_size_t, [_i, C.POINTER(C.c_longlong), _i]),
+    "st_render_pool": (_i, [_i, _f, _i, _p, _p, _p, _i, C.c_longlong, C.c_longlong, _p, C.c_uint, C.c_ulonglong, _p, _p, _p]),
     "st_loss_backward_p1": (_i, [_D, _p, _p, _p, _p, _p, _p, _p]),
     "st_loss_backward_p2": (_i, [_D, _p, _p, _p, _p, _p]),
     "st_loss_backward_p2_staged": (_i, [_D, _p, _p, _p, _p, _p, _p]),

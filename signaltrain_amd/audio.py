@@ -357,6 +357,20 @@ class Compressor_4c_OneSetting(Compressor_4c):
         self.knob_ranges = np.array([[-25.001, -25.], [4, 4.001], [5e-3, 5.001e-3], [2e-2, 2.001e-2]])
 
 
+def int2knobs(idx, knob_ranges, settings_per):
+    """audio.py:677-712: setting `idx` of the grid of `settings_per` equally spaced values per knob, as world-coordinate floats.  The knobs are the
+    digits of idx in base settings_per, the LAST knob varying fastest, and digit d of knob k stands for lo_k + (hi_k - lo_k) / (settings_per - 1) * d.
+      int2knobs(12345, [[-.5, .5]] * 4, 12) -> [0.13636..., -0.40909..., 0.22727..., 0.31818...]
+      int2knobs(100, [[1, 6]] * 3, 6) -> [3.0, 5.0, 5.0]        int2knobs(1234, [[0, 9]] * 4, 10) -> [1.0, 2.0, 3.0, 4.0]"""
+    sp, nk, idx = int(settings_per), len(knob_ranges), int(idx)
+    assert idx < sp ** nk, f"idx ({idx}) must be less than the number of grid points ({sp ** nk})"
+    digits = []
+    for _ in range(nk):
+        idx, d = divmod(idx, sp)
+        digits.append(d)
+    return [float(r[0] + (r[1] - r[0]) / (sp - 1) * d) for r, d in zip(knob_ranges, reversed(digits))]
+
+
 # ------------------------------------------------------------------------------------------------ wav files + file-defined effects
 def mu_compand(y, mu=32):
     """audio.py:339-340: mu-law companding (run_train.py --compand, datasets.py:218-220, utils/predict_long.py:38-40)."""

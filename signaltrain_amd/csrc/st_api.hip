@@ -27,6 +27,7 @@
 #include "st_predict.h"
 #include "st_predict_stream.h"
 #include "st_eval_pool.h"
+#include "st_render_pool.h"
 #include "st_decode.h"
 #include "st_fit.h"
 #include "st_multi.h"
@@ -3323,6 +3324,75 @@ extern "C" int st_live_feed_stream(int effect, unsigned family_mask, float synth
         return ST_OK;
     });
     ST_LAUNCHED(effect == ST_FX_DECOMP4C ? "stream_apply_inplace" : "stream_apply");
+    return ST_OK;
+}
+
+// ------------------------------------------------------------------------------ a folder of recordings through an effect (st_render_pool.h)
+// gen_dataset.py's render in one call: every file of the pool whole through the effect at its own knob setting.  The scratch is [row_off int64 [nfiles + 1], padded
+// to 64 floats | one row of round_up(len, 64) floats per file]; ST_FX_DENOISE streams from the pool to out and needs none.
+static const long long RENDER_LEN_LIMIT = (1ll << 31) - 64;      // a file's length and every row index stay inside 32 bits
+static size_t render_head_floats(int nfiles) { return ((size_t)2 * ((size_t)nfiles + 1) + 63) / 64 * 64; }
+extern "C" size_t st_render_pool_scratch_floats(int effect, const long long* file_len_host, int nfiles)
+{
+    if (!feed_effect_ok(effect) || !file_len_host || nfiles < 1) return 0;
+    size_t n = 0;
+    for (int f = 0; f < nfiles; ++f) {
+        const long long len = file_len_host[f];
+        if (len < 0 || len >= RENDER_LEN_LIMIT) return 0;
+        n += (size_t)((len + 63) & ~63ll);
+    }
+    return effect == ST_FX_DENOISE ? 0 : render_head_floats(nfiles) + n;
+}
+extern "C" int st_render_pool(int effect, float sr, int fmt, const void* pool_x, const long long* file_off, const long long* file_len, int nfiles,
+                              long long max_len, long long pool_samples, const float* knobs_wc, unsigned seed, unsigned long long first_file,
+                              float* out, float* scratch, void* stream)
+{
+    const char* who = "st_render_pool";
+    ST_REQ(feed_effect_ok(effect), "%s: effect = %d is not an ST_FX_* id", who, effect);
+    ST_REQ(fmt == ST_PCM_F32 || fmt == ST_PCM_S16, "%s: fmt = %d is neither ST_PCM_F32 nor ST_PCM_S16", who, fmt);
+    ST_REQ(nfiles >= 1, "%s: nfiles = %d must be at least 1", who, nfiles);
+    ST_REQ(pool_samples >= 1, "%s: pool_samples = %lld must be at least 1", who, pool_samples);
+    ST_REQ(max_len >= 0 && max_len < RENDER_LEN_LIMIT, "%s: max_len = %lld must lie in [0, 2^31 - 64)", who, max_len);
+    ST_REQ(sr > 0.f, "%s: sr = %g must be positive", who, (double)sr);
+    ST_TRY(check_ptr(who, "pool_x", pool_x, pcm_align(fmt)));
+    ST_TRY(check_ptr(who, "file_off", file_off, 1)); ST_TRY(check_ptr(who, "file_len", file_len, 1));
+    ST_TRY(check_ptr(who, "knobs_wc", knobs_wc, 1));
+    ST_TRY(check_ptr(who, "out", out, 16));
+    const bool needs_scratch = effect != ST_FX_DENOISE;
+    ST_REQ(scratch || !needs_scratch, "%s: null pointer (scratch, st_render_pool_scratch_floats() floats, is required for effect %d)", who, effect);
+    ST_REQ((reinterpret_cast<uintptr_t>(scratch) & 15) == 0, "%s: scratch must be 16-byte aligned", who);
+    if (max_len == 0) return ST_OK;      // every file is empty: nothing is written
+    str::Pool p{pool_x, file_off, file_len, nfiles, pool_samples, max_len, knobs_wc, nullptr, nullptr, out};
+    const long long tl = (max_len + str::TILE - 1) / str::TILE;
+    const dim3 tiled((unsigned)nfiles, (unsigned)(tl < 65535 ? tl : 65535));      // (file, 2048-sample tile); the kernels stride over the tiles beyond 65535
+    prof_mark("begin", stream);
+    if (effect == ST_FX_DENOISE) {
+        with_pcm(fmt, [&](auto z) { hipLaunchKernelGGL(str::render_denoise_kernel<decltype(z)>, tiled, dim3(256), 0, st_stream(stream), p, seed, first_file); });
+        ST_LAUNCHED("render_denoise"); return ST_OK;
+    }
+    p.row_off = reinterpret_cast<long long*>(scratch); p.rows = scratch + render_head_floats(nfiles);
+    hipLaunchKernelGGL(str::render_rows_kernel, dim3(1), dim3(256), 0, st_stream(stream), p);
+    ST_LAUNCHED("render_rows");
+    const bool gain = effect == ST_FX_COMP4C || effect == ST_FX_DECOMP4C;
+    with_pcm(fmt, [&](auto z) {
+        if (gain) hipLaunchKernelGGL((str::render_stage_kernel<decltype(z), true>), tiled, dim3(256), 0, st_stream(stream), p);
+        else hipLaunchKernelGGL((str::render_stage_kernel<decltype(z), false>), tiled, dim3(256), 0, st_stream(stream), p); });
+    ST_LAUNCHED("render_stage");
+    if (gain) {
+        hipLaunchKernelGGL(str::render_smooth_kernel, dim3((unsigned)(((long long)nfiles + 63) / 64)), dim3(64), 0, st_stream(stream), p, sr);
+        ST_LAUNCHED("render_smooth");
+        with_pcm(fmt, [&](auto z) { hipLaunchKernelGGL(str::render_apply_kernel<decltype(z)>, tiled, dim3(256), 0, st_stream(stream), p); });
+        ST_LAUNCHED("render_apply");
+    } else if (effect == ST_FX_ECHO) {
+        hipLaunchKernelGGL(str::render_echo_kernel, tiled, dim3(256), 0, st_stream(stream), p);
+        ST_LAUNCHED("render_echo");
+    } else if (effect == ST_FX_COMP) {
+        hipLaunchKernelGGL(str::render_scan_kernel<ST_FX_COMP>, dim3((unsigned)nfiles), dim3(256), 0, st_stream(stream), p, sr);
+        ST_LAUNCHED("render_scan_comp");
+    } else {
+        hipLaunchKernelGGL(str::render_scan_kernel<ST_FX_LOWPASS>, dim3((unsigned)nfiles), dim3(256), 0, st_stream(stream), p, sr);
+        ST_LAUNCHED("render_scan_lowpass");
+    }
     return ST_OK;
 }
 

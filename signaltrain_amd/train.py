@@ -204,7 +204,7 @@ def train(effect=None, epochs=100, n_data_points=200000, batch_size=20, device=N
           datapath=None, scale_factor=1, shrink_factor=4, apex_opt="O0", target_type="stream", lr_max=1e-4,
           in_checkpointname='modelcheckpoint.tar', compand=False, num_workers=10, device_feed=True, compute_dtype=None,
           resume_optimizer=False, device_eval=False, choosers=None, input_path=None, synth_prob=0.0, preroll=0, freeze=None, unfreeze_epoch=None,
-          file_report=False):
+          file_report=False, report_settings_per=None):
     """train.py:167-278.  datapath: directory with Train/ and Val/ wav pairs (datasets.AudioFileDataSet, the reference's
     file feed, e.g. the LA2A set of BASELINE configs[3]; pass effect=audio.FileEffect(datapath)); compand: mu-law compand that dataset's audio (datasets.py:218-220).
     apex_opt: "O0" = fp32 (the parity path); "O1" / "O2" / "O3" = the reference's Apex mixed precision (train.py:254-255),
@@ -233,10 +233,13 @@ def train(effect=None, epochs=100, n_data_points=200000, batch_size=20, device=N
     (st_train_step_groups).  unfreeze_epoch: the (0-based) epoch from which those groups train as well -- the two-phase schedule; None = frozen throughout.
     requires_grad flags set by hand (nn_proc.freeze_layers, st_model.freeze) are honoured in the same way, read at the head of every epoch.
     file_report: with datapath, after the last epoch every file of Val/ goes WHOLE through the model at its own knob setting and the per-file error table
-    is printed (datasets.AudioFileDataSet.evaluate: one st_eval_pool call, csrc/st_eval_pool.h)."""
+    is printed (datasets.AudioFileDataSet.evaluate: one st_eval_pool call, csrc/st_eval_pool.h).  With input_path, every file of Val/ is first rendered
+    whole through the live effect at one knob setting per file (datasets.AudioInputDataSet.evaluate: one st_render_pool call, csrc/st_render_pool.h) --
+    report_settings_per: the grid of that many settings per knob over the first files (audio.int2knobs), None = seeded uniform settings."""
     freeze = check_freeze(freeze)
-    if file_report and (datapath is None or target_type != "stream"):
-        raise ValueError("train(): file_report reports the recorded files of datapath's Val/ folder against their recorded targets: it needs datapath and target_type=\"stream\"")
+    if file_report and input_path is None and (datapath is None or target_type != "stream"):
+        raise ValueError("train(): file_report reports the files of a Val/ folder, whole: it needs datapath (recorded targets, target_type=\"stream\") or input_path "
+                         "(the live effect, one knob setting per file)")
     if unfreeze_epoch is not None and (not freeze or int(unfreeze_epoch) < 0):
         raise ValueError(f"train(): unfreeze_epoch = {unfreeze_epoch} needs a freeze list and a non-negative epoch")
     if input_path is not None and datapath is not None:
@@ -372,7 +375,12 @@ def train(effect=None, epochs=100, n_data_points=200000, batch_size=20, device=N
                start_epoch=start_epoch, start_iter=start_iter, lr_resume=lr_resume, device_eval=device_eval, freeze=freeze, unfreeze_epoch=unfreeze_epoch)
     if file_report and not (dist.is_initialized() and dist.get_rank() != 0):
         import os
-        rep = dataset_val.evaluate(model, device=device)
+        if input_path is not None:
+            rep = dataset_val.evaluate(model, settings_per=report_settings_per, seed=0, device=device)
+            names = datasets.render_names(effect, datasets.render_knobs(effect, len(dataset_val.x), settings_per=report_settings_per, seed=0)[1])[1]
+        else:
+            rep = dataset_val.evaluate(model, device=device)
+            names = [os.path.basename(f) for f in dataset_val.target_filenames]
         print("Val set, file by file (whole files, each at its own knob setting):")
-        print(datasets.format_file_report(rep, [os.path.basename(f) for f in dataset_val.target_filenames]))
+        print(datasets.format_file_report(rep, names))
     return model
